@@ -46,6 +46,10 @@ configuration (--pipeline 2 --streams 1, the collective behind the emit kernel o
 and labels the line "fallback": true; at N > 1 the ranks of the second attempt meet through a
 prefix of the launcher's store.  A process that has initialised a GPU is never re-executed.
 --direct runs the worker in this process (profilers; no fallback).
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step goes to DIR/<name>.npy (finite float32 /
+float64, at most 64 MB in all, a fixed seeded sample of the triangle records; NaN normals as 0 beside a mask): with the same arguments the inputs are the same, so two builds
+can be compared output for output.
 """
 import os
 
@@ -132,7 +136,12 @@ def parse(argv=None):
     ap.add_argument("--no-box", action="store_true", help="skip the memory calibration of this box (tools/calib/mix2 box, a fresh process after the timed regions)")
     ap.add_argument("--no-fallback", action="store_true", help="a failed worker is not followed by a second, conservative attempt")
     ap.add_argument("--direct", action="store_true", help="no supervisor: measure in this process (for profilers; no fallback, the watchdog still applies)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (finite float32 / float64, at most "
+                         "64 MB in all; larger outputs as a fixed, seeded sample): two builds run with the same arguments can be compared output for output")
     args = ap.parse_args(argv)
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.config == "stream2048":
         args.n = args.n or 2048
         args.kind = args.kind or "fbm8"
@@ -741,6 +750,79 @@ def per_chunk_counts(ex, n_chunks, bpv):
     return tris, active
 
 
+# ------------------------------------------------------------------------------------------------
+# --dump-outputs DIR: what the timed path computed in its last step, as DIR/<name>.npy (finite float32 / float64), so that two builds can be
+# compared output for output.  The inputs are seeded (the field is generated on the device from seed 1337): the same arguments give the
+# same inputs.  Outputs larger than the budget are a FIXED, SEEDED sample -- runs of consecutive records at run-aligned slots drawn with
+# DUMP_SEED -- saved beside the indices it took (triangle_index, block_tri_offsets_index).  At N > 1 every rank writes its own outputs as
+# <name>_rank<r>.npy.
+# ------------------------------------------------------------------------------------------------
+DUMP_BYTES_MAX = 64 << 20     # everything one run writes, all ranks together
+DUMP_SEED = 20251015
+DUMP_TRIANGLES = 1 << 18      # triangle records kept at N = 1 (/ N per rank): 256 runs of 1024, 33 MB with their block ids, NaN mask and indices
+DUMP_OFFSETS = 3 << 20        # block offsets kept whole up to this many entries at N = 1 (/ N per rank; 1024^3: 2^21 + 1), else sampled in runs
+
+
+def sample_indices(n, keep, run, seed=DUMP_SEED):
+    """Sorted element indices of a fixed, seeded sample of n elements: all of them when n <= keep, otherwise keep // run distinct
+    run-aligned runs of `run` consecutive elements."""
+    if n <= keep:
+        return np.arange(n, dtype=np.int64)
+    slots = np.sort(np.random.default_rng(seed).choice(n // run, size=max(keep // run, 1), replace=False))
+    return (slots[:, None] * run + np.arange(run)).ravel().astype(np.int64)
+
+
+def copy_records(ex, d_ptr, idx, itemsize):
+    """The records idx (sorted, in bounds) of a device array, as bytes: one blocking copy per run of consecutive records."""
+    if len(idx) == 0:
+        return np.zeros(0, np.uint8)
+    runs = np.split(idx, np.flatnonzero(np.diff(idx) != 1) + 1)
+    return np.concatenate([ex.copy_to_host(d_ptr + int(r[0]) * itemsize, len(r) * itemsize) for r in runs])
+
+
+def grid_outputs(ex, T, n_volumes, bpv, offs=None, world=1):
+    """What a caller of the grid path receives from the extract `ex` has just finished: T, per-volume {vertices, triangles}, the block
+    offsets, the 76-byte triangle records (positions / normals block-local, block ids) and, at N > 1, the global chunk offsets."""
+    from volumetricterrain_amd import TRI_DTYPE
+    tri_ptr, off_ptr, vc_ptr = ex.device_results()
+    vc = ex.copy_u32(vc_ptr, 2 * n_volumes).reshape(-1, 2).astype(np.float64)
+    assert int(vc[:, 1].sum()) == T, "the dumped context's volume counts do not add up to its step's T"
+    out = {"triangle_count": np.array([T], np.float64), "volume_counts": vc}
+    boffs = ex.copy_u32(off_ptr, n_volumes * bpv + 1).astype(np.float64)
+    if len(boffs) <= DUMP_OFFSETS // world:
+        out["block_tri_offsets"] = boffs
+    else:   # sampled: with its indices, half as many entries
+        bidx = sample_indices(len(boffs), DUMP_OFFSETS // world // 2, 4096)
+        out["block_tri_offsets"], out["block_tri_offsets_index"] = boffs[bidx], bidx.astype(np.float64)
+    if offs is not None:
+        out["chunk_offsets"] = np.asarray(offs, np.float64)
+    tidx = sample_indices(T, DUMP_TRIANGLES // world, 1024)
+    tris = copy_records(ex, tri_ptr, tidx, TRI_DTYPE.itemsize).view(TRI_DTYPE)
+    out["triangle_positions"] = np.stack([tris["p0"], tris["p1"], tris["p2"]], axis=1)
+    # a zero gradient gives a NaN normal, as in the reference (SampleNormal.compute:32): every written value is finite, so those components are
+    # written as 0 and triangle_normals_nan says which they are (1.0) -- a build that moves a NaN still differs from one that does not
+    nrm = np.stack([tris["n0"], tris["n1"], tris["n2"]], axis=1)
+    nan = np.isnan(nrm)
+    out["triangle_normals"] = np.where(nan, np.float32(0), nrm)
+    out["triangle_normals_nan"] = nan.astype(np.float32)
+    out["triangle_blocks"] = tris["block"].astype(np.float64)
+    out["triangle_index"] = tidx.astype(np.float64)
+    return out
+
+
+def write_outputs(out_dir, arrays, rank=0, world=1):
+    """DIR/<name>.npy (DIR/<name>_rank<r>.npy at N > 1); finite float32 / float64 only, this rank's share of DUMP_BYTES_MAX at most."""
+    nbytes = sum(a.nbytes + 128 for a in arrays.values())   # + the .npy header
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: str(a.dtype) for k, a in arrays.items()}
+    bad = [k for k, a in arrays.items() if not np.isfinite(a).all()]
+    assert not bad, "non-finite values in the outputs to dump: %s" % bad
+    assert nbytes <= DUMP_BYTES_MAX // world, "outputs of %d bytes exceed the dump budget" % nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def rehearse_ranks(torch, pipe, d_field, n_chunks_world, chunk, chunk_tris, chunk_active, worlds=(2, 4, 8), steps=48, assign="balanced", log=None):
     """EVERY rank of an N-rank run, one after the other, on this one GPU with the configuration `pipe` was built with (the shipped N > 1 default:
     four steps in flight on own-queue streams, the world-of-one collective on the rank's collective stream, the pinned read-back, the host's
@@ -1000,6 +1082,10 @@ def run_grid(args, torch, dist, wd):
         elapsed, total_tris = reduce_max_sum(elapsed, T, world, backend, torch, dist)
         if exchange:
             assert int(offs[-1, 1]) == int(total_tris), "gathered chunk counts do not add up to the ranks' triangle totals"
+        if args.dump_outputs:   # the last timed step's context, before any region behind this one reuses it
+            wd.stage("dump_outputs", 120)
+            last = pipe.slots[(args.steps - 1) % depth]
+            write_outputs(args.dump_outputs, grid_outputs(last.ex, int(T), n_chunks, bpv, offs if exchange else None, world), rank, world)
 
         ms_per_step = elapsed / args.steps * 1e3
         cells_total = float(world_dims[0]) * world_dims[1] * world_dims[2]
@@ -1262,6 +1348,8 @@ def run_stream(args, torch, dist, wd):
         loc[:n_chunks] = torch.from_numpy(counts.astype(np.int32))
         g = sharding.allgather_counts(loc.cuda() if backend == "nccl" else loc)
         assert int(g[..., 1].sum()) == int(total_tris)
+    if args.dump_outputs:   # what ChunkStream.run() returned for the last timed pass
+        write_outputs(args.dump_outputs, {"triangle_count": np.array([total], np.float64), "volume_counts": counts.astype(np.float64)}, rank, world)
     report("done")
     if rank == 0:
         step_s = elapsed / args.steps

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -130,6 +131,47 @@ def test_exchange_path_through_a_world_of_one_communicator():
     j2 = run([sys.executable, "bench.py", "--grid", "256", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-indexed", "--no-rehearsal", "--no-stream-record", "--no-terrain-record", "--no-box", "--pipeline", "2",
               "--gather-beside"], {"VTMC_BENCH_FORCE_COMM": "1"})
     assert j2["pipeline_depth"] == 2 and j2["triangles_total"] == j["triangles_total"]
+
+
+def _dumped(d):
+    return {f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs: the last timed step's outputs as float32 / float64 .npy files, 64 MB at most; the inputs are seeded, so a run with
+    another number of timed steps (its last step on another context) dumps the same arrays."""
+    base = [sys.executable, "bench.py", "--grid", "256", "--warmup", "1", "--no-cpu-baseline", "--no-indexed", "--no-rehearsal", "--no-stream-record",
+            "--no-terrain-record", "--no-box"]
+    j = run(base + ["--steps", "3", "--dump-outputs", str(tmp_path / "a")])
+    j2 = run(base + ["--steps", "6", "--dump-outputs", str(tmp_path / "b")])
+    assert j["steps"] == 3 and j2["steps"] == 6
+    a, b = _dumped(tmp_path / "a"), _dumped(tmp_path / "b")
+    assert set(a) == {"triangle_count", "volume_counts", "block_tri_offsets", "triangle_positions", "triangle_normals", "triangle_normals_nan",
+                      "triangle_blocks", "triangle_index"}
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    T = int(a["triangle_count"][0])
+    assert T == j["triangles_rank0"] and a["volume_counts"].shape == (8, 2) and int(a["volume_counts"][:, 1].sum()) == T
+    bo = a["block_tri_offsets"]
+    assert len(bo) == 8 * 16 ** 3 + 1 and bo[0] == 0 and bo[-1] == T and np.all(np.diff(bo) >= 0)
+    ids, blocks = a["triangle_index"].astype(np.int64), a["triangle_blocks"].astype(np.int64)
+    assert len(ids) == min(T, 1 << 18) and np.all(np.diff(ids) > 0) and ids[-1] < T
+    assert np.all(bo[blocks] <= ids) and np.all(ids < bo[blocks + 1])      # every sampled record lies in its own block's range
+    p, nrm, nan = a["triangle_positions"], a["triangle_normals"], a["triangle_normals_nan"]
+    assert p.shape == nrm.shape == nan.shape == (len(ids), 3, 3)
+    assert np.all((p >= 0) & (p <= 8))          # block-local cell units
+    # a zero gradient gives a NaN normal, as in the reference (tests/test_lifecycle.py): written as 0, flagged in the mask
+    assert set(np.unique(nan)) <= {0.0, 1.0} and np.all(nrm[nan == 1] == 0)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_dump_outputs_of_the_stream_config(tmp_path):
+    j = run([sys.executable, "bench.py", "--config", "stream2048", "--grid", "256", "--batch", "3", "--steps", "1", "--no-cpu-baseline",
+             "--dump-outputs", str(tmp_path)])
+    d = _dumped(tmp_path)
+    assert set(d) == {"triangle_count", "volume_counts"} and all(v.dtype == np.float64 and np.isfinite(v).all() for v in d.values())
+    assert int(d["triangle_count"][0]) == j["triangles_total"] == int(d["volume_counts"][:, 1].sum()) and d["volume_counts"].shape == (8, 2)
 
 
 def test_gpus_n_without_a_launcher_starts_its_own_ranks():
