@@ -6,7 +6,8 @@
 // sampler" stage for the benchmark grids: Ken Perlin's 2002 improved noise with a 256-entry
 // permutation from a SplitMix64-driven Fisher-Yates shuffle, summed over octaves, minus a vertical
 // ramp.  VALU + small LDS tables; writes are lane-contiguous along the stride-1 axis.
-#include "vtmc_internal.h"
+#include "vtmc_ctx.h"
+#include <cstring>
 #include <type_traits>
 #pragma clang diagnostic ignored "-Winline-asm"   // the sign words' v_writelane names m0 as clobbered: a reserved register, which this file's kernels never use otherwise
 
@@ -495,3 +496,113 @@ hipError_t launch_density(const DensityLaunch &dl, const unsigned char *d_perm, 
 size_t density_rows_bytes(int n_volumes, int dy, int dz) { return (size_t)n_volumes * (size_t)(dy > dz ? dy : dz) * kRowDwords * sizeof(float); }
 
 }  // namespace vtmc
+
+using namespace vtmc;
+
+extern "C" {
+
+int32_t vtmc_density_fill_device_async(vtmc_ctx *ctx, const vtmc_density_params *params, const int32_t *origins, int32_t n_volumes,
+                                 int32_t dim_x, int32_t dim_y, int32_t dim_z, int64_t stride_x, int64_t stride_y,
+                                 int64_t stride_z, int64_t volume_stride, float *d_out, void *stream)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (!params || !origins || !d_out) return fail(ctx, VTMC_ERR_INVALID_ARG, "null argument");
+    if (n_volumes <= 0 || dim_x <= 0 || dim_y <= 0 || dim_z <= 0 || params->octaves < 1 || params->octaves > 16)
+        return fail(ctx, VTMC_ERR_INVALID_ARG, "bad volume count, dims or octaves");
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    if (!ctx->perm_valid || ctx->perm_seed != params->seed) {
+        unsigned char perm[256];
+        density_permutation(params->seed, perm);
+        if (int rc = ensure(ctx, ctx->perm, 256)) return rc;
+        VTMC_HIP(ctx, hipStreamSynchronize(st));  // nothing queued may still read the old table
+        VTMC_HIP(ctx, hipMemcpy(ctx->perm.p, perm, 256, hipMemcpyHostToDevice));
+        ctx->perm_seed = params->seed;
+        ctx->perm_valid = true;
+    }
+    const size_t rows_bytes = density_rows_bytes(n_volumes, dim_y, dim_z);
+    if (ctx->origins.bytes < sizeof(int32_t) * 3 * (size_t)n_volumes || ctx->yrows.bytes < rows_bytes)
+        VTMC_HIP(ctx, hipStreamSynchronize(st));  // about to reallocate
+    if (int rc = ensure(ctx, ctx->origins, sizeof(int32_t) * 3 * (size_t)n_volumes)) return rc;
+    if (int rc = ensure(ctx, ctx->yrows, rows_bytes)) return rc;
+    // The caller's array is only borrowed for this call: it is copied into pinned staging and uploaded from there, stream-ordered
+    // behind any earlier fill of this context that still reads the previous origins.  No wait on `st`: a host that pipelines
+    // batches on one stream (streaming.ChunkStream) must be able to queue this fill behind an extract that is still running.
+    const size_t org_bytes = sizeof(int32_t) * 3 * (size_t)n_volumes;
+    if (ctx->origins_upload_pending) VTMC_HIP(ctx, hipEventSynchronize(ctx->ev_origins));   // the previous upload has left the staging words
+    if (ctx->h_origins.bytes < org_bytes) VTMC_HIP(ctx, pin(ctx->h_origins, org_bytes));
+    memcpy(ctx->h_origins.p, origins, org_bytes);
+    // Pinned staging never rides the context's own-queue stream (a CU-mask stream with pinned copies on it hung a C++ host at process exit,
+    // profiles/r05/stream_overlap.txt): the ordinary stream carries the upload, behind the previous fill (which still reads the previous
+    // origins) and ahead of this one, by events.
+    hipStream_t up = st;
+    if (ctx->queue_stream && st == ctx->queue_stream) {
+        up = ctx->stream;
+        if (ctx->fill_timed) VTMC_HIP(ctx, hipStreamWaitEvent(up, ctx->ev_fill[1], 0));
+    }
+    VTMC_HIP(ctx, hipMemcpyAsync(ctx->origins.p, ctx->h_origins.p, org_bytes, hipMemcpyHostToDevice, up));
+    VTMC_HIP(ctx, hipEventRecord(ctx->ev_origins, up));
+    if (up != st) VTMC_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_origins, 0));
+    ctx->origins_upload_pending = true;
+    DensityLaunch dl{};
+    dl.frequency = params->frequency;
+    dl.lacunarity = params->lacunarity;
+    dl.gain = params->gain;
+    dl.ramp_scale = params->ramp_scale;
+    dl.ramp_center = params->ramp_center;
+    dl.octaves = params->octaves;
+    dl.dx = dim_x;
+    dl.dy = dim_y;
+    dl.dz = dim_z;
+    dl.sx = stride_x;
+    dl.sy = stride_y;
+    dl.sz = stride_z;
+    dl.sv = volume_stride;
+    dl.n_volumes = n_volumes;
+    dl.ablate = ctx->tune.density_ablate;
+    dl.wgs_per_cu = ctx->tune.density_wgs_per_cu;
+    // the samples' sign bits for the classify stage of this same buffer (the streaming driver's setting)
+    unsigned long long *d_signs = nullptr;
+    ctx->sign_of.valid = false;
+    if (ctx->tune.fill_keeps_signs && density_writes_signs(dl)) {
+        const size_t sb = density_sign_words(dl) * sizeof(unsigned long long);
+        if (ctx->signs.bytes < sb) VTMC_HIP(ctx, hipStreamSynchronize(st));  // about to reallocate
+        if (int rc = ensure(ctx, ctx->signs, sb)) return rc;
+        d_signs = (unsigned long long *)ctx->signs.p;
+        ctx->sign_of.valid = true;
+        ctx->sign_of.d_out = d_out;
+        ctx->sign_of.dx = dim_x;
+        ctx->sign_of.dy = dim_y;
+        ctx->sign_of.dz = dim_z;
+        ctx->sign_of.n_volumes = n_volumes;
+        ctx->sign_of.sv = volume_stride;
+    }
+    VTMC_HIP(ctx, hipEventRecord(ctx->ev_fill[0], st));
+    VTMC_HIP(ctx, launch_density(dl, (const unsigned char *)ctx->perm.p, (const int *)ctx->origins.p, (float *)ctx->yrows.p, d_out, d_signs, st));
+    VTMC_HIP(ctx, hipEventRecord(ctx->ev_fill[1], st));
+    ctx->fill_timed = true;
+    return VTMC_OK;
+}
+
+int32_t vtmc_last_fill_ms(vtmc_ctx *ctx, float *ms)
+{
+    if (!ctx || !ms) return VTMC_ERR_INVALID_ARG;
+    if (!ctx->fill_timed) return fail(ctx, VTMC_ERR_NO_RESULT, "last_fill_ms before any density fill");
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    VTMC_HIP(ctx, hipEventSynchronize(ctx->ev_fill[1]));
+    VTMC_HIP(ctx, hipEventElapsedTime(ms, ctx->ev_fill[0], ctx->ev_fill[1]));
+    return VTMC_OK;
+}
+
+int32_t vtmc_density_fill_device(vtmc_ctx *ctx, const vtmc_density_params *params, const int32_t *origins, int32_t n_volumes,
+                                 int32_t dim_x, int32_t dim_y, int32_t dim_z, int64_t stride_x, int64_t stride_y,
+                                 int64_t stride_z, int64_t volume_stride, float *d_out, void *stream)
+{
+    if (int32_t rc = vtmc_density_fill_device_async(ctx, params, origins, n_volumes, dim_x, dim_y, dim_z, stride_x, stride_y, stride_z,
+                                                    volume_stride, d_out, stream))
+        return rc;
+    VTMC_HIP(ctx, hipStreamSynchronize(stream ? (hipStream_t)stream : ctx->stream));
+    return VTMC_OK;
+}
+
+}  // extern "C"

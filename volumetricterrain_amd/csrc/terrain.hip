@@ -16,7 +16,11 @@
 // counter-based hash of (seed, event, sample index, draw index) -- same ranges, same number of
 // draws per sample (2 per add, 4 per erode, 1 per Init sample), deterministic; the CPU oracle
 // restates the same hash (oracle/terrain_ref.c).
-#include "vtmc_internal.h"
+#include "vtmc_ctx.h"
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstring>
 
 namespace vtmc {
 
@@ -156,4 +160,222 @@ hipError_t launch_terrain_modify(float *grid, const TerrainShape &sh, const Terr
     return launch_end();
 }
 
+static int saturating_int(float f)   // of a floor / ceil: Mathf.FloorToInt / CeilToInt, saturating
+{
+    return f <= -2147483648.0f ? INT32_MIN : (f >= 2147483648.0f ? INT32_MAX : (int)f);
+}
+
+// the terrain's blocks per axis, and f(bx, by, bz) for every block in block-id order (x fastest)
+static std::array<int, 3> block_counts(const TerrainShape &sh) { return {(sh.dim_x - 2) / 8, (sh.dim_y - 2) / 8, (sh.dim_z - 2) / 8}; }
+template <class F>
+static void for_each_block(const std::array<int, 3> &nb, F f)
+{
+    for (int bz = 0; bz < nb[2]; ++bz)
+        for (int by = 0; by < nb[1]; ++by)
+            for (int bx = 0; bx < nb[0]; ++bx) f(bx, by, bz);
+}
+
+// a modifier's kernel arguments: its AABB in sample indices, [low, up] clamped to the grid (up[] is also what the dirty blocks are found from)
+static TerrainModifierArgs sample_range(const TerrainShape &sh, const vtmc_modifier &md, int low[3], int up[3])
+{
+    TerrainModifierArgs a{};
+    a.kind = md.kind;
+    a.add_or_erode = md.add_or_erode ? 1 : 0;
+    memcpy(a.p, md.p, sizeof a.p);
+    const int top[3] = {sh.dim_x - 1, sh.dim_y - 1, sh.dim_z - 1};
+    int ext[3];
+    for (int k = 0; k < 3; ++k) {
+        // world -> sample index: (world - TerrainOrigin) / _voxelScale, floor / ceil, clamp (VoxelTerrain.cs:273-281)
+        low[k] = std::max(saturating_int(std::floor((md.lower[k] - sh.origin[k]) / sh.scale)), 0);
+        up[k] = std::min(saturating_int(std::ceil((md.upper[k] - sh.origin[k]) / sh.scale)), top[k]);
+        // extents in 64 bits: floor/ceil saturate at INT32_MIN/MAX, so an inverted or far-away AABB must
+        // come out as an empty range (the reference's loops simply do not execute, VoxelTerrain.cs:284-286),
+        // never as a wrapped positive size; low >= 0 and up <= top bound a valid extent by the grid
+        const long long e = (long long)up[k] - (long long)low[k] + 1;
+        ext[k] = e <= 0 || low[k] > top[k] ? 0 : (int)std::min<long long>(e, (long long)top[k] - low[k] + 1);
+    }
+    a.lx = low[0], a.ly = low[1], a.lz = low[2];
+    a.dx = ext[0], a.dy = ext[1], a.dz = ext[2];
+    return a;
+}
+
+// dirty blocks: up >= 8b && low <= 8b + 8 on every axis (VoxelTerrain.cs:307-317), as index ranges; returns how many were newly marked
+static size_t mark_dirty_blocks(const int low[3], const int up[3], const std::array<int, 3> &nb, std::vector<uint8_t> &mark)
+{
+    int b0[3], b1[3];
+    for (int k = 0; k < 3; ++k) {
+        // b <= up / 8 and b >= (low - 8) / 8 rounded up; the reference's loops leave an empty
+        // (low > up) AABB with its block tests, so the same arithmetic is used for it
+        const long long lo = (long long)low[k] - 8, hi = up[k];
+        const long long f = lo <= 0 ? 0 : (lo + 7) / 8;
+        const long long l = std::min<long long>(hi < 0 ? -1 : hi / 8, nb[k] - 1);
+        if (f > l) return 0;
+        b0[k] = (int)f;
+        b1[k] = (int)l;
+    }
+    size_t n_new = 0;
+    for (int bz = b0[2]; bz <= b1[2]; ++bz)
+        for (int by = b0[1]; by <= b1[1]; ++by) {
+            uint8_t *row = &mark[(size_t)nb[0] * ((size_t)by + (size_t)nb[1] * bz)];
+            for (int bx = b0[0]; bx <= b1[0]; ++bx) {
+                n_new += !row[bx];
+                row[bx] = 1;
+            }
+        }
+    return n_new;
+}
+
 }  // namespace vtmc
+
+using namespace vtmc;
+
+extern "C" {
+
+int32_t vtmc_terrain_init(vtmc_ctx *ctx, int32_t width, int32_t elevation, int32_t height, float voxel_scale,
+                          const float terrain_origin[3], uint64_t seed)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (!terrain_origin) return fail(ctx, VTMC_ERR_INVALID_ARG, "terrain_origin is null");
+    if (int rc = check_dims(ctx, width, elevation, height)) return rc;
+    // VoxelTerrain.cs:141-142
+    if (width + 1 > 1025 || elevation + 1 > 1025 || height + 1 > 1025)
+        return fail(ctx, VTMC_ERR_DIMS, "too high resolution (exceeds 1025)");
+    if (!(voxel_scale > 0.0f)) return fail(ctx, VTMC_ERR_INVALID_ARG, "voxel_scale must be positive");
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->has_terrain = false;
+    ctx->has_result = false;
+    TerrainShape sh{};
+    sh.dim_x = width + 2;
+    sh.dim_y = elevation + 2;
+    sh.dim_z = height + 2;
+    sh.scale = voxel_scale;
+    memcpy(sh.origin, terrain_origin, sizeof sh.origin);
+    sh.seed = seed;
+    const long long n = (long long)sh.dim_x * sh.dim_y * sh.dim_z;
+    if (int rc = ensure(ctx, ctx->terrain, sizeof(float) * (size_t)n)) return rc;
+    VTMC_HIP(ctx, launch_terrain_fill((float *)ctx->terrain.p, n, seed, ctx->n_cus, ctx->stream));
+    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->tshape = sh;
+    ctx->terrain_events = 0;
+    ctx->dirty.clear();
+    ctx->dirty_is_all = false;
+    ctx->has_terrain = true;
+    return VTMC_OK;
+}
+
+int32_t vtmc_terrain_update(vtmc_ctx *ctx, const vtmc_modifier *mods, int32_t n_mods, int32_t *n_dirty_blocks, int32_t *tri_count)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_update before terrain_init");
+    if (n_mods < 0 || (n_mods > 0 && !mods)) return fail(ctx, VTMC_ERR_INVALID_ARG, "mods is null or n_mods < 0");
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    const TerrainShape &sh = ctx->tshape;
+    const auto nb = block_counts(sh);
+    std::vector<uint8_t> mark((size_t)nb[0] * nb[1] * nb[2], 0);
+    size_t n_marked = 0;
+    for (int32_t i = 0; i < n_mods; ++i) {
+        const vtmc_modifier &md = mods[i];
+        if (md.kind < VTMC_MOD_PLANE || md.kind > VTMC_MOD_HEIGHTMAP) return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: unknown kind %d", i, md.kind);
+        if (md.kind == VTMC_MOD_HEIGHTMAP && (!md.data || md.data_dims[0] < 1 || md.data_dims[1] < 1))
+            return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: heightmap data / dims missing", i);
+        int low[3], up[3];
+        TerrainModifierArgs a = sample_range(sh, md, low, up);
+        a.event = ++ctx->terrain_events;
+        if (md.kind == VTMC_MOD_HEIGHTMAP && a.dx > 0 && a.dy > 0 && a.dz > 0) {
+            // _heightmap (IslandModifier.cs:36) goes to the device; an earlier modifier of this queue may
+            // still be reading the previous one, hence the drain before the buffer is touched
+            const size_t bytes = sizeof(float) * (size_t)md.data_dims[0] * (size_t)md.data_dims[1];
+            VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (int rc = ensure(ctx, ctx->heightmap, bytes)) return rc;
+            VTMC_HIP(ctx, hipMemcpy(ctx->heightmap.p, md.data, bytes, hipMemcpyHostToDevice));
+            a.data = (const float *)ctx->heightmap.p;
+            a.dims0 = md.data_dims[0];
+            a.dims1 = md.data_dims[1];
+        }
+        if (a.dx > 0 && a.dy > 0 && a.dz > 0) VTMC_HIP(ctx, launch_terrain_modify((float *)ctx->terrain.p, sh, a, ctx->stream));
+        if (n_marked < mark.size()) n_marked += mark_dirty_blocks(low, up, nb, mark);
+    }
+    // _nextUpdateblocks (VoxelTerrain.cs:321), ordered by block id; a full rebuild needs no list
+    ctx->dirty.clear();
+    ctx->dirty_is_all = n_marked == mark.size();
+    if (!ctx->dirty_is_all) {
+        ctx->dirty.reserve(n_marked * 3);
+        size_t id = 0;
+        for_each_block(nb, [&](int bx, int by, int bz) {
+            if (mark[id++]) ctx->dirty.insert(ctx->dirty.end(), {bx, by, bz});
+        });
+    }
+    if (n_dirty_blocks) *n_dirty_blocks = (int32_t)n_marked;
+    // BatchUpdate (VoxelTerrain.cs:322-323: only when the set is not empty) on the resident grid
+    BlockSpace sp = dense_space((const float *)ctx->terrain.p, sh.dim_x - 2, sh.dim_y - 2, sh.dim_z - 2, 1, sh.dim_x, (int64_t)sh.dim_x * sh.dim_y, 1, 0);
+    int n_volumes = 1;
+    if (!ctx->dirty_is_all) {  // a proper subset: device block list; every block: the dense streaming path
+        if (int rc = upload_block_list(ctx, ctx->dirty.data(), (int)n_marked, sp)) return rc;
+        n_volumes = 0;
+    }
+    return extract_core(ctx, sp, n_volumes, tri_count);
+}
+
+int32_t vtmc_terrain_dirty_blocks(vtmc_ctx *ctx, int32_t *dst, int32_t capacity_blocks, int32_t *n_blocks)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_dirty_blocks before terrain_init");
+    const auto nb = block_counts(ctx->tshape);
+    const size_t n = ctx->dirty_is_all ? (size_t)nb[0] * nb[1] * nb[2] : ctx->dirty.size() / 3;
+    if (n_blocks) *n_blocks = (int32_t)n;
+    if (!dst) return VTMC_OK;  // size query
+    if ((size_t)std::max(capacity_blocks, 0) < n) return fail(ctx, VTMC_ERR_CAPACITY, "capacity %d < %zu dirty blocks", capacity_blocks, n);
+    if (ctx->dirty_is_all)
+        for_each_block(nb, [&](int bx, int by, int bz) {
+            *dst++ = bx;
+            *dst++ = by;
+            *dst++ = bz;
+        });
+    else if (n)
+        memcpy(dst, ctx->dirty.data(), n * 3 * sizeof(int32_t));
+    return VTMC_OK;
+}
+
+int32_t vtmc_terrain_read_samples(vtmc_ctx *ctx, float *dst, int64_t stride_x, int64_t stride_y, int64_t stride_z)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_read_samples before terrain_init");
+    if (!dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "dst is null");
+    if (stride_x <= 0 || stride_y <= 0 || stride_z <= 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "strides must be positive");
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    const TerrainShape &sh = ctx->tshape;
+    const size_t n = (size_t)sh.dim_x * sh.dim_y * sh.dim_z;
+    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (stride_x == 1 && stride_y == sh.dim_x && stride_z == (int64_t)sh.dim_x * sh.dim_y) {
+        VTMC_HIP(ctx, hipMemcpy(dst, ctx->terrain.p, n * sizeof(float), hipMemcpyDeviceToHost));
+        return VTMC_OK;
+    }
+    std::vector<float> tmp(n);
+    VTMC_HIP(ctx, hipMemcpy(tmp.data(), ctx->terrain.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    size_t i = 0;
+    for (int z = 0; z < sh.dim_z; ++z)
+        for (int y = 0; y < sh.dim_y; ++y)
+            for (int x = 0; x < sh.dim_x; ++x) dst[x * stride_x + y * stride_y + z * stride_z] = tmp[i++];
+    return VTMC_OK;
+}
+
+int32_t vtmc_terrain_device_grid(vtmc_ctx *ctx, const float **d_samples, int64_t strides[3], int32_t dims[3])
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_device_grid before terrain_init");
+    const TerrainShape &sh = ctx->tshape;
+    if (d_samples) *d_samples = (const float *)ctx->terrain.p;
+    if (strides) {
+        strides[0] = 1;
+        strides[1] = sh.dim_x;
+        strides[2] = (int64_t)sh.dim_x * sh.dim_y;
+    }
+    if (dims) {
+        dims[0] = sh.dim_x;
+        dims[1] = sh.dim_y;
+        dims[2] = sh.dim_z;
+    }
+    return VTMC_OK;
+}
+
+}  // extern "C"

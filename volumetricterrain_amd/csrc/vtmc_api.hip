@@ -1,174 +1,24 @@
-// vtmc_api.hip -- the C ABI of include/vtmc.h: context, scratch management and the host-side
-// control flow that VoxelTerrain.BatchUpdate performs around its three dispatches
-// (reference: Unity-Project/Assets/Scripts/VoxelTerrain.cs:330-477).
+// vtmc_api.hip -- the extract entry points of include/vtmc.h, the host-side control flow that VoxelTerrain.BatchUpdate performs around
+// its three dispatches (reference: Unity-Project/Assets/Scripts/VoxelTerrain.cs:330-477) and the result readers.  The context: context.hip.
 //
 // Differences from the reference's control flow, by design:
-//  * buffers are owned by the context and only grow (the reference allocates and releases six
-//    ComputeBuffers per call, VoxelTerrain.cs:368-414, 469-476);
 //  * there is no mid-pipeline read-back (VoxelTerrain.cs:394-395): classify -> scan -> emit are
 //    queued back to back, {T, nActive} live in device memory, and the host reads T once at the end;
 //    the emit kernel itself refuses to run past the triangle buffer's capacity, in which case the
-//    buffer is grown and only the emit stage is queued again;
-//  * no CPU fallback of any kind: without a HIP device vtmc_create fails.
-#include "mc_tables_packed.h"
+//    buffer is grown and only the emit stage is queued again.
 #include "vtmc_ctx.h"
 
 #include <algorithm>
-#include <climits>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <new>
-#include <string>
-#include <vector>
 
 using namespace vtmc;
 typedef VtmcDevBuf DevBuf;
 
 namespace {
-thread_local std::string g_create_error;
 // pinned tile staging a context keeps between dirty-list calls; anything larger is given back by the next small call
 constexpr size_t kStageKeepBytes = (size_t)32 << 20;
 constexpr int kStageTrimAfter = 8;   // an over-sized staging buffer goes after this many consecutive small calls: a host that alternates a big brush with small edits keeps it
-}  // namespace
-
-namespace vtmc {
-
-// STREAMS OUTLIVE THEIR CONTEXTS (round 6).  vtmc_context_stream hands raw hipStream_t handles to the host, and host-side objects keep
-// referring to them after vtmc_destroy -- events recorded on them, a framework's stream wrapper, a caching allocator that records an event on
-// the stream when it frees a pinned buffer that was copied on it: round 5's aborts in the interpreter's tear-down.  A context therefore does
-// not destroy its streams: vtmc_destroy drains them and parks them here, per device and kind, and the next context on that device takes a
-// parked one.  Bounded by the largest number of contexts alive at once.  At process exit they are left to the runtime, as a framework's own
-// streams are: an atexit handler that destroyed them (tried in round 6) runs after a profiler's tool library has torn its stream
-// bookkeeping down -- rocprofv3 then aborts inside hipStreamDestroy -- and is not what decides how a process ends under ROCm 7.2 anyway
-// ("Streams": copies on a CU-mask stream do, whatever is destroyed when).  VTMC_STREAM_POOL=0 in the environment (test
-// switch) restores destruction in vtmc_destroy.
-namespace {
-struct StreamPool {
-    std::mutex m;
-    std::vector<std::pair<int, hipStream_t>> parked[2];   // [0] ordinary non-blocking streams, [1] streams on a hardware queue of their own
-};
-StreamPool &stream_pool()
-{
-    static StreamPool *p = new StreamPool;   // never destructed: no static destructor that could run beside the HIP runtime's own at exit
-    return *p;
-}
-bool env_is(const char *name, const char *value)
-{
-    const char *v = getenv(name);
-    return v && !strcmp(v, value);
-}
-bool stream_pool_enabled()
-{
-    static const bool on = !env_is("VTMC_STREAM_POOL", "0");
-    return on;
-}
-}  // namespace
-
-// A stream of `device` (current): own_queue = made by hipExtStreamCreateWithCUMask with every CU named -- such a stream always sits on a
-// hardware queue of its own, ordinary streams share a handful (profiles/r05/stream_overlap.txt).
-hipError_t take_stream(int device, bool own_queue, int n_cus, hipStream_t *out)
-{
-    if (stream_pool_enabled()) {
-        StreamPool &sp = stream_pool();
-        std::lock_guard<std::mutex> g(sp.m);
-        auto &v = sp.parked[own_queue ? 1 : 0];
-        for (size_t i = v.size(); i-- > 0;)   // the one parked last
-            if (v[i].first == device) {
-                *out = v[i].second;
-                v.erase(v.begin() + (long)i);
-                return hipSuccess;
-            }
-    }
-    if (!own_queue) return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
-    std::vector<uint32_t> mask((size_t)(n_cus + 31) / 32, 0xFFFFFFFFu);
-    if (n_cus % 32) mask.back() = (1u << (n_cus % 32)) - 1u;
-    return hipExtStreamCreateWithCUMask(out, (uint32_t)mask.size(), mask.data());
-}
-// every parked stream of every device is destroyed now (vtmc_release_streams); the contexts alive keep theirs
-int release_parked_streams()
-{
-    StreamPool &sp = stream_pool();
-    std::vector<std::pair<int, hipStream_t>> all;
-    {
-        std::lock_guard<std::mutex> g(sp.m);
-        for (auto &v : sp.parked) {
-            all.insert(all.end(), v.begin(), v.end());
-            v.clear();
-        }
-    }
-    int prev = 0;
-    const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-    for (auto &ds : all) {
-        if (hipSetDevice(ds.first) != hipSuccess) continue;
-        quiet(hipStreamSynchronize(ds.second));
-        quiet(hipStreamDestroy(ds.second));
-    }
-    if (have_prev) quiet(hipSetDevice(prev));
-    return (int)all.size();
-}
-
-// the stream is idle (the caller synchronised it)
-void park_stream(int device, bool own_queue, hipStream_t s)
-{
-    if (!s) return;
-    if (!stream_pool_enabled()) {
-        quiet(hipStreamDestroy(s));
-        return;
-    }
-    StreamPool &sp = stream_pool();
-    std::lock_guard<std::mutex> g(sp.m);
-    sp.parked[own_queue ? 1 : 0].emplace_back(device, s);
-}
-
-int fail(vtmc_ctx *ctx, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (ctx) ctx->err = buf;
-    else g_create_error = buf;
-    return code;
-}
-
-const char *create_error_text() { return g_create_error.c_str(); }
-
-int ensure(vtmc_ctx *ctx, DevBuf &b, size_t bytes)
-{
-    if (b.bytes >= bytes && b.p) return VTMC_OK;
-    if (b.p) VTMC_HIP(ctx, hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-    size_t want = std::max<size_t>(bytes, 256);
-    VTMC_HIP(ctx, hipMalloc(&b.p, want));
-    b.bytes = want;
-    return VTMC_OK;
-}
-
-void release(DevBuf &b)
-{
-    if (b.p) quiet(hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-}
-
-// Pinned staging is freed in ONE place, and pointer and size are cleared together: a buffer freed with its size left standing
-// is written to by the next call that finds it "large enough" (round 3's double free).
-void release_pinned(void **p, size_t *bytes)
-{
-    if (*p) quiet(hipHostFree(*p));
-    *p = nullptr;
-    if (bytes) *bytes = 0;
-}
-
-}  // namespace vtmc
-
-namespace {
 
 // One launch of the emit stage on the pending extract's stream, followed by the asynchronous copy of
 // the scan's totals into pinned memory.  The kernel itself refuses to run past its buffers' capacity
@@ -265,7 +115,7 @@ int extract_queue(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, uint32_t f
     const bool dense = !sp.list && !(flags & (VTMC_FLAG_WANT_CASES | VTMC_FLAG_NO_DENSE_PATH)) &&
                        ((sp.sx == 1 && sp.nx >= 32) || (sp.sx != 1 && sp.sz == 1 && sp.nbz * 8 >= 32));
 
-    ctx->h_totals[8] = 0u;   // the scan's look-back time-out word
+    ctx->h_totals.p[8] = 0u;   // the scan's look-back time-out word
     unsigned long long *ctrl = (unsigned long long *)ctx->partials.p;
     const int n_ctrl = (int)(ctrl_words * (indexed ? 2 : 1));
     VTMC_HIP(ctx, hipEventRecord(ctx->ev[0], stream));
@@ -332,7 +182,7 @@ int place_outputs(vtmc_ctx *ctx)
         }
         return VTMC_OK;
     };
-    auto take = [&](Set &st) { st.a = A; st.b = B; A = DevBuf{}; B = DevBuf{}; };
+    auto take = [&](Set &st) { st.a = std::move(A); st.b = std::move(B); };
     ctx->place_n = 0;
     ctx->place_kept = 0;
     Set best;
@@ -360,19 +210,35 @@ int place_outputs(vtmc_ctx *ctx)
                 std::swap(cand, best);
                 ctx->place_kept = k;
             }
-            losers.push_back(cand);
+            losers.push_back(std::move(cand));
         }
-        for (Set &l : losers) {
-            release(l.a);
-            release(l.b);
-        }
-        A = best.a;
-        B = best.b;
+        losers.clear();
+        A = std::move(best.a);
+        B = std::move(best.b);
     }
     quiet(hipEventDestroy(t0));
     quiet(hipEventDestroy(t1));
     if (rc) return rc;
     VTMC_HIP(ctx, hipStreamSynchronize(pe.stream));   // the kept buffers hold a complete result (every candidate was emitted in full)
+    return VTMC_OK;
+}
+
+// stage_ms[0..2] = classify, scan, emit (with stage_events = 1), [3] = the whole extract, from the events of the finished extract
+int record_stage_ms(vtmc_ctx *ctx, bool placed)
+{
+    float a = 0, b = 0, c = 0;
+    if (ctx->tune.stage_events) {
+        VTMC_HIP(ctx, hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]));
+        VTMC_HIP(ctx, hipEventElapsedTime(&b, ctx->ev[1], ctx->ev[2]));
+        VTMC_HIP(ctx, hipEventElapsedTime(&c, ctx->ev[2], ctx->ev[3]));
+    } else {
+        VTMC_HIP(ctx, hipEventElapsedTime(&ctx->stage_ms[3], ctx->ev[0], ctx->ev[3]));
+    }
+    if (placed) c = ctx->place_ms[ctx->place_kept];   // ev[3] stands behind the last candidate's launch: this extract's emit stage is the kept candidate's run
+    if (ctx->tune.stage_events || placed) ctx->stage_ms[3] = a + b + c;
+    ctx->stage_ms[0] = a;
+    ctx->stage_ms[1] = b;
+    ctx->stage_ms[2] = c;
     return VTMC_OK;
 }
 
@@ -392,12 +258,12 @@ int extract_finish(vtmc_ctx *ctx, int64_t *tri_count)
             // the event behind the emit launch, not the whole stream: work queued behind the extract (the next batch's sampler,
             // a collective, the caller's own copies) keeps running while the host takes this result
             VTMC_HIP(ctx, hipEventSynchronize(ctx->ev[3]));
-            if (ctx->h_totals[8]) {
+            if (ctx->h_totals.p[8]) {
                 ctx->pending.active = false;
                 return fail(ctx, VTMC_ERR_DEVICE, "scan: a look-back wait timed out (a predecessor tile never published)");
             }
-            const uint64_t T = ((uint64_t)ctx->h_totals[3] << 32) | ctx->h_totals[2];
-            const uint64_t V = pe.indexed ? (((uint64_t)ctx->h_totals[7] << 32) | ctx->h_totals[6]) : 0ull;
+            const uint64_t T = ((uint64_t)ctx->h_totals.p[3] << 32) | ctx->h_totals.p[2];
+            const uint64_t V = pe.indexed ? (((uint64_t)ctx->h_totals.p[7] << 32) | ctx->h_totals.p[6]) : 0ull;
             if (T > 0x7fffffffull || V > 0x7fffffffull) {
                 ctx->pending.active = false;
                 return fail(ctx, VTMC_ERR_TOO_LARGE, "%llu triangles / %llu vertices exceed the int32 range of the ABI",
@@ -428,22 +294,7 @@ int extract_finish(vtmc_ctx *ctx, int64_t *tri_count)
             placed = ctx->place_n > 0;
         }
         ctx->place_pending = false;
-        float a = 0, b = 0, c = 0;
-        if (ctx->tune.stage_events) {
-            VTMC_HIP(ctx, hipEventElapsedTime(&a, ctx->ev[0], ctx->ev[1]));
-            VTMC_HIP(ctx, hipEventElapsedTime(&b, ctx->ev[1], ctx->ev[2]));
-            VTMC_HIP(ctx, hipEventElapsedTime(&c, ctx->ev[2], ctx->ev[3]));
-            ctx->stage_ms[3] = a + b + c;
-        } else {
-            VTMC_HIP(ctx, hipEventElapsedTime(&ctx->stage_ms[3], ctx->ev[0], ctx->ev[3]));
-        }
-        if (placed) {   // ev[3] stands behind the last candidate's launch: this extract's emit stage is the kept candidate's run
-            c = ctx->place_ms[ctx->place_kept];
-            ctx->stage_ms[3] = a + b + c;
-        }
-        ctx->stage_ms[0] = a;
-        ctx->stage_ms[1] = b;
-        ctx->stage_ms[2] = c;
+        if (int rc = record_stage_ms(ctx, placed)) return rc;
     }
     ctx->pending.active = false;
     ctx->has_result = true;
@@ -457,10 +308,85 @@ int extract_finish(vtmc_ctx *ctx, int64_t *tri_count)
     return VTMC_OK;
 }
 
-int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, uint32_t flags, hipStream_t stream, int64_t *tri_count)
+// upload the memory span a strided host grid occupies; returns device pointer in ctx->input
+int upload_grid(vtmc_ctx *ctx, const float *grid, int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz)
 {
-    if (int rc = extract_queue(ctx, sp, n_volumes, flags, stream)) return rc;
-    return extract_finish(ctx, tri_count);
+    if (sx <= 0 || sy <= 0 || sz <= 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "strides must be positive");
+    const size_t span = (size_t)(nx + 1) * sx + (size_t)(ny + 1) * sy + (size_t)(nz + 1) * sz + 1;
+    if (int rc = ensure(ctx, ctx->input, span * sizeof(float))) return rc;
+    VTMC_HIP(ctx, hipMemcpyAsync(ctx->input.p, grid, span * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    return VTMC_OK;
+}
+
+// the last result's per-block offsets (n_blocks + 1 words) into dst, when the caller asked for them
+int copy_offsets(vtmc_ctx *ctx, int32_t *dst, const DevBuf &offsets)
+{
+    if (!dst) return VTMC_OK;
+    if (ctx->last_blocks > 0) VTMC_HIP(ctx, hipMemcpy(dst, offsets.p, sizeof(uint32_t) * ((size_t)ctx->last_blocks + 1), hipMemcpyDeviceToHost));
+    else dst[0] = 0;
+    return VTMC_OK;
+}
+
+// Pinned staging of `bytes` of gathered tiles, or null (none to be had, or a huge dirty set: the caller takes the pageable route).  A
+// larger one than kStageKeepBytes is trimmed back to it once kStageTrimAfter calls in a row were small (freeing and re-pinning tens of MB
+// costs milliseconds and a device sync each way).
+float *stage_buffer(vtmc_ctx *ctx, size_t bytes)
+{
+    if (bytes > ((size_t)256 << 20)) return nullptr;
+    const bool small = ctx->h_stage.bytes > kStageKeepBytes && bytes <= kStageKeepBytes / 4;
+    ctx->h_stage_small_calls = small ? ctx->h_stage_small_calls + 1 : 0;
+    const bool trim = small && ctx->h_stage_small_calls >= kStageTrimAfter;
+    if (bytes > ctx->h_stage.bytes || trim) {
+        ctx->h_stage_small_calls = 0;
+        quiet(pin(ctx->h_stage, trim ? kStageKeepBytes : std::max(bytes + bytes / 4, (size_t)1 << 20)));   // optional: null goes pageable
+    }
+    return ctx->h_stage.p;
+}
+
+// The 10x10x10 sample tile of every listed block, gathered out of the strided host grid as BatchUpdate does (VoxelTerrain.cs:341-361), into
+// pinned staging when it can be had (one DMA straight from where the gather wrote instead of the runtime's staged copy of a pageable
+// vector, profiles/r03/dropin_route.txt), else into `pageable`; null when out of host memory.
+const float *gather_tiles(vtmc_ctx *ctx, const float *grid, int64_t sx, int64_t sy, int64_t sz, const int32_t *block_list, int32_t n_blocks,
+                          std::vector<float> &pageable)
+{
+    float *tiles = stage_buffer(ctx, (size_t)n_blocks * VTMC_TILE_SAMPLES * sizeof(float));
+    if (!tiles) {   // no pinned memory to be had (or a huge dirty set): the pageable route
+        try {
+            pageable.resize((size_t)n_blocks * VTMC_TILE_SAMPLES);
+        } catch (const std::bad_alloc &) {
+            return nullptr;
+        }
+        tiles = pageable.data();
+    }
+    for (int32_t b = 0; b < n_blocks; ++b) {
+        const int32_t *p = block_list + 3 * (size_t)b;
+        const float *org = grid + 8 * ((int64_t)p[0] * sx + (int64_t)p[1] * sy + (int64_t)p[2] * sz);
+        float *t = tiles + (size_t)b * VTMC_TILE_SAMPLES;
+        // the innermost loop walks the grid axis with the smallest stride (z for a C# float[,,]): the reads stay in one or two cache lines
+        if (sz < sx) {
+            for (int ix = 0; ix < 10; ++ix)
+                for (int iy = 0; iy < 10; ++iy)
+                    for (int iz = 0; iz < 10; ++iz) t[ix + 10 * iy + 100 * iz] = org[ix * sx + iy * sy + iz * sz];
+        } else {
+            for (int iz = 0; iz < 10; ++iz)
+                for (int iy = 0; iy < 10; ++iy)
+                    for (int ix = 0; ix < 10; ++ix) t[ix + 10 * iy + 100 * iz] = org[ix * sx + iy * sy + iz * sz];
+        }
+    }
+    return tiles;
+}
+
+}  // namespace
+
+namespace vtmc {
+
+int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, int32_t *tri_count)
+{
+    int64_t T = 0;
+    if (int rc = extract_queue(ctx, sp, n_volumes, 0, ctx->stream)) return rc;
+    if (int rc = extract_finish(ctx, &T)) return rc;
+    if (tri_count) *tri_count = (int32_t)T;
+    return VTMC_OK;
 }
 
 int check_dims(vtmc_ctx *ctx, int nx, int ny, int nz)
@@ -469,16 +395,6 @@ int check_dims(vtmc_ctx *ctx, int nx, int ny, int nz)
     // VoxelTerrain.cs:138-139 "block size must align to terrain size"
     if (nx % 8 || ny % 8 || nz % 8)
         return fail(ctx, VTMC_ERR_DIMS, "block size must align to terrain size (%dx%dx%d is not a multiple of 8)", nx, ny, nz);
-    return VTMC_OK;
-}
-
-// upload the memory span a strided host grid occupies; returns device pointer in ctx->input
-int upload_grid(vtmc_ctx *ctx, const float *grid, int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz)
-{
-    if (sx <= 0 || sy <= 0 || sz <= 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "strides must be positive");
-    const size_t span = (size_t)(nx + 1) * sx + (size_t)(ny + 1) * sy + (size_t)(nz + 1) * sz + 1;
-    if (int rc = ensure(ctx, ctx->input, span * sizeof(float))) return rc;
-    VTMC_HIP(ctx, hipMemcpyAsync(ctx->input.p, grid, span * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     return VTMC_OK;
 }
 
@@ -505,106 +421,18 @@ BlockSpace dense_space(const float *d_base, int nx, int ny, int nz, int64_t sx, 
     return sp;
 }
 
-}  // namespace
+int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp)
+{
+    if (int rc = ensure(ctx, ctx->list, sizeof(int32_t) * 3 * (size_t)std::max(n, 1))) return rc;
+    if (n > 0) VTMC_HIP(ctx, hipMemcpyAsync(ctx->list.p, xyz, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    sp.list = (const int *)ctx->list.p;
+    sp.n_blocks = n;
+    return VTMC_OK;
+}
+
+}  // namespace vtmc
 
 extern "C" {
-
-const char *vtmc_version(void) { return "vtmc 0.1 gfx950"; }
-
-int32_t vtmc_create(int32_t device, vtmc_ctx **out_ctx)
-{
-    if (!out_ctx) return fail(nullptr, VTMC_ERR_INVALID_ARG, "out_ctx is null");
-    *out_ctx = nullptr;
-    int n_dev = 0;
-    hipError_t e = hipGetDeviceCount(&n_dev);
-    if (e != hipSuccess || n_dev <= 0)
-        return fail(nullptr, VTMC_ERR_DEVICE, "no HIP device available (%s); this library has no CPU path",
-                    e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
-    if (device < 0 || device >= n_dev) return fail(nullptr, VTMC_ERR_INVALID_ARG, "device %d out of range [0,%d)", device, n_dev);
-    vtmc_ctx *ctx = new (std::nothrow) vtmc_ctx();
-    if (!ctx) return fail(nullptr, VTMC_ERR_DEVICE, "out of host memory");
-    ctx->device = device;
-    auto bail = [&](const char *what, hipError_t err) {
-        std::string msg = std::string(what) + ": " + hipGetErrorString(err);
-        vtmc_destroy(ctx);
-        return fail(nullptr, VTMC_ERR_DEVICE, "%s", msg.c_str());
-    };
-    if ((e = hipSetDevice(device)) != hipSuccess) return bail("hipSetDevice", e);
-    hipDeviceProp_t prop;
-    if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return bail("hipGetDeviceProperties", e);
-    ctx->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    // test switch (tests/test_own_queue_cpp_host.py): the context's MAIN stream on a hardware queue of its own, pinned staging and read-backs
-    // included -- the configuration whose C++ host hung at process exit in round 5 ("Streams")
-    ctx->stream_own_queue = env_is("VTMC_TEST_MAIN_STREAM_OWN_QUEUE", "1");
-    if ((e = take_stream(device, ctx->stream_own_queue, ctx->n_cus, &ctx->stream)) != hipSuccess) return bail("hipStreamCreate", e);
-    for (auto &ev : ctx->ev)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
-    for (auto &ev : ctx->ev_fill)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipEventCreateWithFlags(&ctx->ev_origins, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    if ((e = hipHostMalloc((void **)&ctx->h_totals, 64 * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess)
-        return bail("hipHostMalloc", e);
-    memset(ctx->h_totals, 0, 64 * sizeof(uint32_t));
-    if ((e = hipHostGetDevicePointer((void **)&ctx->h_totals_dev, ctx->h_totals, 0)) != hipSuccess) return bail("hipHostGetDevicePointer", e);
-
-    // tables: VoxelTerrain.cs:151-156 uploads three int tables; here the packed 2 KB vert table and a
-    // 256-byte triangle-count table (the edge-mask table is implied by the vert table)
-    static const unsigned long long packed[VTMC_MC_TABLE_WORDS] = VTMC_MC_TABLE_INIT;
-    unsigned char tri_num[256];
-    for (int c = 0; c < 256; ++c) tri_num[c] = (unsigned char)(packed[c] >> 60);
-    if (ensure(ctx, ctx->d_vert, sizeof packed) || ensure(ctx, ctx->d_trinum, sizeof tri_num)) {
-        std::string msg = ctx->err;
-        vtmc_destroy(ctx);
-        return fail(nullptr, VTMC_ERR_DEVICE, "%s", msg.c_str());
-    }
-    if ((e = hipMemcpy(ctx->d_vert.p, packed, sizeof packed, hipMemcpyHostToDevice)) != hipSuccess) return bail("table upload", e);
-    if ((e = hipMemcpy(ctx->d_trinum.p, tri_num, sizeof tri_num, hipMemcpyHostToDevice)) != hipSuccess) return bail("table upload", e);
-    ctx->tables.vert_packed = (const unsigned long long *)ctx->d_vert.p;
-    ctx->tables.tri_num = (const unsigned char *)ctx->d_trinum.p;
-    *out_ctx = ctx;
-    return VTMC_OK;
-}
-
-int32_t vtmc_destroy(vtmc_ctx *ctx)
-{
-    if (!ctx) return VTMC_OK;
-    quiet(hipSetDevice(ctx->device));
-    // 1. nothing of this context is still running: a queued extract nobody finished (on whatever stream the caller named), the own-queue
-    //    stream, the collective's stream, the ordinary stream -- BEFORE anything they use is released (round 5 freed device and pinned memory
-    //    first and synchronised the own-queue stream last)
-    if (ctx->pending.active && ctx->pending.stream) quiet(hipStreamSynchronize(ctx->pending.stream));
-    if (ctx->queue_stream) quiet(hipStreamSynchronize(ctx->queue_stream));
-    if (ctx->comm_stream) quiet(hipStreamSynchronize(ctx->comm_stream));
-    if (ctx->stream) quiet(hipStreamSynchronize(ctx->stream));
-    comm_release(ctx);   // drains the collectives queued through the communicator (also on a stream of the caller's), then lets go of it
-    // 2. the streams: parked for the next context of this device, never destroyed -- handles from vtmc_context_stream stay valid for host-side
-    //    objects that outlive the context (see StreamPool above; VTMC_STREAM_POOL=0: destroyed here, ahead of the events and the memory)
-    park_stream(ctx->device, false, ctx->comm_stream);
-    park_stream(ctx->device, true, ctx->queue_stream);
-    park_stream(ctx->device, ctx->stream_own_queue, ctx->stream);
-    ctx->comm_stream = ctx->queue_stream = ctx->stream = nullptr;
-    // 3. events, 4. device buffers and pinned memory
-    if (ctx->ev_origins) quiet(hipEventDestroy(ctx->ev_origins));
-    for (auto &ev : ctx->ev)
-        if (ev) quiet(hipEventDestroy(ev));
-    for (auto &ev : ctx->ev_fill)
-        if (ev) quiet(hipEventDestroy(ev));
-    if (ctx->ev_gather) quiet(hipEventDestroy(ctx->ev_gather));
-    if (ctx->ev_last_gather) quiet(hipEventDestroy(ctx->ev_last_gather));
-    if (ctx->ev_comm_chain) quiet(hipEventDestroy(ctx->ev_comm_chain));
-    for (DevBuf *b : {&ctx->d_vert, &ctx->d_trinum, &ctx->counts, &ctx->offsets, &ctx->active, &ctx->partials, &ctx->totals,
-                      &ctx->volcounts, &ctx->cases, &ctx->tris, &ctx->input, &ctx->list, &ctx->perm, &ctx->origins, &ctx->yrows, &ctx->signs, &ctx->terrain, &ctx->heightmap,
-                      &ctx->vcounts, &ctx->voffsets, &ctx->vtotals, &ctx->verts, &ctx->indices, &ctx->chunk_image,
-                      &ctx->comm_send})
-        release(*b);
-    release_pinned((void **)&ctx->h_totals, nullptr);
-    release_pinned((void **)&ctx->h_origins, &ctx->h_origins_bytes);
-    release_pinned((void **)&ctx->h_stage, &ctx->h_stage_bytes);
-    delete ctx;
-    return VTMC_OK;
-}
-
-const char *vtmc_last_error(const vtmc_ctx *ctx) { return ctx ? ctx->err.c_str() : create_error_text(); }
 
 int32_t vtmc_extract_blocks(vtmc_ctx *ctx, const float *samples, int32_t n_blocks, int32_t *tri_count)
 {
@@ -618,14 +446,10 @@ int32_t vtmc_extract_blocks(vtmc_ctx *ctx, const float *samples, int32_t n_block
     }
     // the tile buffer is a batch of n_blocks volumes of one 8^3 block each
     BlockSpace sp = dense_space((const float *)ctx->input.p, 8, 8, 8, 1, 10, 100, n_blocks, VTMC_TILE_SAMPLES);
-    int64_t T = 0;
-    if (int rc = extract_core(ctx, sp, 0, 0, ctx->stream, &T)) {
-        // the caller's `samples` are only borrowed for this call: a failure behind the asynchronous upload must not return while the DMA still reads them
-        if (n_blocks > 0) quiet(hipStreamSynchronize(ctx->stream));
-        return rc;
-    }
-    if (tri_count) *tri_count = (int32_t)T;
-    return VTMC_OK;
+    const int rc = extract_core(ctx, sp, 0, tri_count);
+    // the caller's `samples` are only borrowed for this call: a failure behind the asynchronous upload must not return while the DMA still reads them
+    if (rc && n_blocks > 0) quiet(hipStreamSynchronize(ctx->stream));
+    return rc;
 }
 
 int32_t vtmc_extract_grid(vtmc_ctx *ctx, const float *grid, int32_t nx, int32_t ny, int32_t nz, int64_t stride_x,
@@ -646,74 +470,22 @@ int32_t vtmc_extract_grid(vtmc_ctx *ctx, const float *grid, int32_t nx, int32_t 
                             sp.nbx, sp.nby, sp.nbz);
         }
         const size_t span = (size_t)(nx + 1) * stride_x + (size_t)(ny + 1) * stride_y + (size_t)(nz + 1) * stride_z + 1;
-        if ((size_t)n_blocks * VTMC_TILE_SAMPLES * 2 < span) {
-            // small dirty set on a large grid: gather tiles on the host exactly as BatchUpdate does
-            // (VoxelTerrain.cs:341-361) so only B*4000 bytes cross PCIe instead of the whole grid
+        if ((size_t)n_blocks * VTMC_TILE_SAMPLES * 2 < span) {   // small dirty set on a large grid: only B*4000 bytes cross PCIe
             if (stride_x <= 0 || stride_y <= 0 || stride_z <= 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "strides must be positive");
-            // The tiles are gathered into PINNED memory of the context (grown on demand, kept): the upload is then one DMA straight from
-            // where the gather wrote, instead of the runtime's staged copy of a pageable vector (profiles/r03/dropin_route.txt).
-            const size_t tile_bytes = (size_t)n_blocks * VTMC_TILE_SAMPLES * sizeof(float);
             std::vector<float> pageable;
-            float *tiles = nullptr;
-            if (tile_bytes <= ((size_t)256 << 20)) {
-                // kept between calls up to kStageKeepBytes; a larger one (a one-off big edit) is trimmed back to kStageKeepBytes once
-                // kStageTrimAfter calls in a row were small (freeing and re-pinning tens of MB costs milliseconds and a device sync each way)
-                const bool small = ctx->h_stage_bytes > kStageKeepBytes && tile_bytes <= kStageKeepBytes / 4;
-                ctx->h_stage_small_calls = small ? ctx->h_stage_small_calls + 1 : 0;
-                const bool trim = small && ctx->h_stage_small_calls >= kStageTrimAfter;
-                if (tile_bytes > ctx->h_stage_bytes || trim) {
-                    release_pinned((void **)&ctx->h_stage, &ctx->h_stage_bytes);
-                    ctx->h_stage_small_calls = 0;
-                    const size_t want = trim ? kStageKeepBytes : std::max(tile_bytes + tile_bytes / 4, (size_t)1 << 20);
-                    const hipError_t e = hipHostMalloc((void **)&ctx->h_stage, want, hipHostMallocDefault);
-                    if (e == hipSuccess) ctx->h_stage_bytes = want;
-                    else ctx->h_stage = nullptr, quiet(e);   // optional: the pageable route below takes over
-                }
-                tiles = ctx->h_stage;
-            }
-            if (!tiles) {   // no pinned memory to be had (or a huge dirty set): the pageable route
-                try {
-                    pageable.resize((size_t)n_blocks * VTMC_TILE_SAMPLES);
-                } catch (const std::bad_alloc &) {
-                    return fail(ctx, VTMC_ERR_DEVICE, "out of host memory gathering %d tiles", n_blocks);
-                }
-                tiles = pageable.data();
-            }
-            for (int32_t b = 0; b < n_blocks; ++b) {
-                const int32_t *p = block_list + 3 * (size_t)b;
-                const float *org = grid + 8 * ((int64_t)p[0] * stride_x + (int64_t)p[1] * stride_y + (int64_t)p[2] * stride_z);
-                float *t = tiles + (size_t)b * VTMC_TILE_SAMPLES;
-                // the innermost loop walks the grid axis with the smallest stride (z for a C# float[,,]): the reads stay in one or two cache lines
-                if (stride_z < stride_x) {
-                    for (int ix = 0; ix < 10; ++ix)
-                        for (int iy = 0; iy < 10; ++iy)
-                            for (int iz = 0; iz < 10; ++iz) t[ix + 10 * iy + 100 * iz] = org[ix * stride_x + iy * stride_y + iz * stride_z];
-                } else {
-                    for (int iz = 0; iz < 10; ++iz)
-                        for (int iy = 0; iy < 10; ++iy)
-                            for (int ix = 0; ix < 10; ++ix) t[ix + 10 * iy + 100 * iz] = org[ix * stride_x + iy * stride_y + iz * stride_z];
-                }
-            }
+            const float *tiles = gather_tiles(ctx, grid, stride_x, stride_y, stride_z, block_list, n_blocks, pageable);
+            if (!tiles) return fail(ctx, VTMC_ERR_DEVICE, "out of host memory gathering %d tiles", n_blocks);
             // blocking: the staging buffer is free again when it returns -- also when it fails behind its upload (extract_blocks drains the stream then)
             return vtmc_extract_blocks(ctx, tiles, n_blocks, tri_count);
         }
-        if (int rc = upload_grid(ctx, grid, nx, ny, nz, stride_x, stride_y, stride_z)) return rc;
-        if (int rc = ensure(ctx, ctx->list, sizeof(int32_t) * 3 * (size_t)std::max(n_blocks, 1))) return rc;
-        if (n_blocks > 0)
-            VTMC_HIP(ctx, hipMemcpyAsync(ctx->list.p, block_list, sizeof(int32_t) * 3 * (size_t)n_blocks, hipMemcpyHostToDevice, ctx->stream));
-        sp.list = (const int *)ctx->list.p;
-        sp.n_blocks = n_blocks;
-    } else {
-        if (int rc = upload_grid(ctx, grid, nx, ny, nz, stride_x, stride_y, stride_z)) return rc;
     }
+    if (int rc = upload_grid(ctx, grid, nx, ny, nz, stride_x, stride_y, stride_z)) return rc;
+    if (block_list)
+        if (int rc = upload_block_list(ctx, block_list, n_blocks, sp)) return rc;
     sp.base = (const float *)ctx->input.p;
-    int64_t T = 0;
-    if (int rc = extract_core(ctx, sp, block_list ? 0 : 1, 0, ctx->stream, &T)) {
-        quiet(hipStreamSynchronize(ctx->stream));   // the uploads above borrow the caller's arrays: nothing of them is in flight when an error returns
-        return rc;
-    }
-    if (tri_count) *tri_count = (int32_t)T;
-    return VTMC_OK;
+    const int rc = extract_core(ctx, sp, block_list ? 0 : 1, tri_count);
+    if (rc) quiet(hipStreamSynchronize(ctx->stream));   // the uploads above borrow the caller's arrays: nothing of them is in flight when an error returns
+    return rc;
 }
 
 int32_t vtmc_extract_grid_sharded(vtmc_ctx *ctx, const float *grid, int32_t nx, int32_t ny, int32_t nz, int64_t stride_x,
@@ -737,11 +509,7 @@ int32_t vtmc_extract_grid_sharded(vtmc_ctx *ctx, const float *grid, int32_t nx, 
         const int cx = c % ncx, cy = (c / ncx) % ncy, cz = c / (ncx * ncy);
         for (int bz = 0; bz < cb; ++bz)
             for (int by = 0; by < cb; ++by)
-                for (int bx = 0; bx < cb; ++bx) {
-                    list.push_back(cx * cb + bx);
-                    list.push_back(cy * cb + by);
-                    list.push_back(cz * cb + bz);
-                }
+                for (int bx = 0; bx < cb; ++bx) list.insert(list.end(), {cx * cb + bx, cy * cb + by, cz * cb + bz});
         ++n_local;
     }
     if (n_local_chunks) *n_local_chunks = n_local;
@@ -749,20 +517,14 @@ int32_t vtmc_extract_grid_sharded(vtmc_ctx *ctx, const float *grid, int32_t nx, 
         return fail(ctx, VTMC_ERR_CAPACITY, "chunk_counts holds %d chunks, need %d", chunk_counts_capacity, n_local);
     if (int rc = upload_grid(ctx, grid, nx, ny, nz, stride_x, stride_y, stride_z)) return rc;
     const int n_blocks = n_local * bpc;
-    if (int rc = ensure(ctx, ctx->list, sizeof(int32_t) * 3 * (size_t)std::max(n_blocks, 1))) return rc;
-    if (n_blocks > 0)
-        VTMC_HIP(ctx, hipMemcpyAsync(ctx->list.p, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, ctx->stream));
     BlockSpace sp = dense_space((const float *)ctx->input.p, nx, ny, nz, stride_x, stride_y, stride_z, 1, 0);
-    sp.list = (const int *)ctx->list.p;
-    sp.n_blocks = n_blocks;
+    if (int rc = upload_block_list(ctx, list.data(), n_blocks, sp)) return rc;
     sp.bpv = bpc;  // chunk-major list: each local chunk is a contiguous run of bpc blocks
-    int64_t T = 0;
-    if (int rc = extract_core(ctx, sp, n_local, 0, ctx->stream, &T)) return rc;
-    if (chunk_counts && n_local > 0) {
-        if (n_blocks > 0)
-            VTMC_HIP(ctx, hipMemcpy(chunk_counts, ctx->volcounts.p, sizeof(uint32_t) * 2 * (size_t)n_local, hipMemcpyDeviceToHost));
-    }
-    if (tri_count) *tri_count = (int32_t)T;
+    int32_t T = 0;
+    if (int rc = extract_core(ctx, sp, n_local, &T)) return rc;
+    if (chunk_counts && n_local > 0 && n_blocks > 0)
+        VTMC_HIP(ctx, hipMemcpy(chunk_counts, ctx->volcounts.p, sizeof(uint32_t) * 2 * (size_t)n_local, hipMemcpyDeviceToHost));
+    if (tri_count) *tri_count = T;
     return VTMC_OK;
 }
 
@@ -794,16 +556,8 @@ int32_t vtmc_read_indexed_mesh(vtmc_ctx *ctx, vtmc_vertex *vertices, int64_t ver
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->last_verts > 0) VTMC_HIP(ctx, hipMemcpy(vertices, ctx->verts.p, sizeof(vtmc_vertex) * (size_t)ctx->last_verts, hipMemcpyDeviceToHost));
     if (ctx->last_tris > 0) VTMC_HIP(ctx, hipMemcpy(indices, ctx->indices.p, sizeof(int32_t) * 3 * (size_t)ctx->last_tris, hipMemcpyDeviceToHost));
-    const size_t nb = (size_t)ctx->last_blocks + 1;
-    if (block_vertex_offsets) {
-        if (ctx->last_blocks > 0) VTMC_HIP(ctx, hipMemcpy(block_vertex_offsets, ctx->voffsets.p, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
-        else block_vertex_offsets[0] = 0;
-    }
-    if (block_tri_offsets) {
-        if (ctx->last_blocks > 0) VTMC_HIP(ctx, hipMemcpy(block_tri_offsets, ctx->offsets.p, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
-        else block_tri_offsets[0] = 0;
-    }
-    return VTMC_OK;
+    if (int rc = copy_offsets(ctx, block_vertex_offsets, ctx->voffsets)) return rc;
+    return copy_offsets(ctx, block_tri_offsets, ctx->offsets);
 }
 
 int32_t vtmc_device_indexed_results(vtmc_ctx *ctx, const vtmc_vertex **d_vertices, const int32_t **d_indices,
@@ -828,12 +582,7 @@ int32_t vtmc_read_triangles(vtmc_ctx *ctx, vtmc_triangle *dst, int64_t capacity,
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->last_tris > 0)
         VTMC_HIP(ctx, hipMemcpy(dst, ctx->tris.p, sizeof(vtmc_triangle) * (size_t)ctx->last_tris, hipMemcpyDeviceToHost));
-    if (block_tri_offsets) {
-        if (ctx->last_blocks > 0)
-            VTMC_HIP(ctx, hipMemcpy(block_tri_offsets, ctx->offsets.p, sizeof(uint32_t) * ((size_t)ctx->last_blocks + 1), hipMemcpyDeviceToHost));
-        else block_tri_offsets[0] = 0;
-    }
-    return VTMC_OK;
+    return copy_offsets(ctx, block_tri_offsets, ctx->offsets);
 }
 
 int32_t vtmc_read_cases(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity)
@@ -848,12 +597,11 @@ int32_t vtmc_read_cases(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity)
     // materialise _CornerFlags on demand with the per-block classify kernel (the input of the last
     // extract is still resident: ctx-owned for host entry points, caller-owned for device ones)
     if (int rc = ensure(ctx, ctx->cases, (size_t)need)) return rc;
-    DevBuf tmp;
+    DevBuf tmp;   // freed on every path out
     if (int rc = ensure(ctx, tmp, sizeof(uint32_t) * (size_t)ctx->last_blocks)) return rc;
     hipError_t e = launch_classify_blocks(ctx->last_space, ctx->tables, (uint32_t *)tmp.p, (uint8_t *)ctx->cases.p, nullptr, ctx->n_cus, nullptr, 0, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(dst, ctx->cases.p, (size_t)need, hipMemcpyDeviceToHost);
-    release(tmp);
     if (e != hipSuccess) return fail(ctx, VTMC_ERR_DEVICE, "read_cases: %s", hipGetErrorString(e));
     return VTMC_OK;
 }
@@ -870,18 +618,8 @@ int32_t vtmc_last_counts(const vtmc_ctx *ctx, int32_t *n_blocks, int32_t *tri_co
 int32_t vtmc_extract_volumes_device(vtmc_ctx *ctx, const vtmc_volume_batch *batch, void *stream, uint32_t flags,
                                     int64_t *tri_count)
 {
-    if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!batch || !batch->d_samples) return fail(ctx, VTMC_ERR_INVALID_ARG, "batch or batch->d_samples is null");
-    if (int rc = check_dims(ctx, batch->nx, batch->ny, batch->nz)) return rc;
-    if (batch->n_volumes < 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "n_volumes < 0");
-    if (batch->stride_x <= 0 || batch->stride_y <= 0 || batch->stride_z <= 0 || batch->volume_stride < 0)
-        return fail(ctx, VTMC_ERR_INVALID_ARG, "strides must be positive");
-    const long long bpv = (long long)(batch->nx / 8) * (batch->ny / 8) * (batch->nz / 8);
-    if (bpv * batch->n_volumes > 0x7fffffffll) return fail(ctx, VTMC_ERR_TOO_LARGE, "more than 2^31-1 blocks");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    BlockSpace sp = dense_space(batch->d_samples, batch->nx, batch->ny, batch->nz, batch->stride_x, batch->stride_y,
-                                batch->stride_z, batch->n_volumes, batch->volume_stride);
-    return extract_core(ctx, sp, batch->n_volumes, flags, stream ? (hipStream_t)stream : ctx->stream, tri_count);
+    if (int32_t rc = vtmc_extract_volumes_device_async(ctx, batch, stream, flags)) return rc;
+    return extract_finish(ctx, tri_count);
 }
 
 int32_t vtmc_extract_volumes_device_async(vtmc_ctx *ctx, const vtmc_volume_batch *batch, void *stream, uint32_t flags)
@@ -950,32 +688,6 @@ int32_t vtmc_reserve_triangles(vtmc_ctx *ctx, int64_t capacity)
     return rc;
 }
 
-int32_t vtmc_context_stream(vtmc_ctx *ctx, int32_t own_queue, void **stream)
-{
-    if (!ctx || !stream) return VTMC_ERR_INVALID_ARG;
-    *stream = nullptr;
-    if (!own_queue) {
-        *stream = (void *)ctx->stream;
-        return VTMC_OK;
-    }
-    // A stream on a HARDWARE QUEUE OF ITS OWN.  Ordinary HIP streams share a handful of queues, and two contexts whose streams land on one
-    // queue run their steps strictly one behind the other; on queues of their own, step k + 1's classify kernel starts on the CUs step k's
-    // emit kernel leaves as it drains (profiles/r05/stream_overlap.txt: -4..5 % of a 1024^3 step, -20 % of a rank's step of an 8-rank run).
-    // A stream made with a CU mask always gets its queue; the mask names every CU.  Taken on first request (a parked one of an earlier
-    // context, or a new one); parked again, not destroyed, by vtmc_destroy: the handle stays valid until the process exits.
-    if (!ctx->queue_stream) {
-        VTMC_HIP(ctx, hipSetDevice(ctx->device));
-        const hipError_t e = take_stream(ctx->device, true, ctx->n_cus, &ctx->queue_stream);
-        if (e != hipSuccess) {
-            quiet(e);
-            ctx->queue_stream = nullptr;
-            return fail(ctx, VTMC_ERR_DEVICE, "hipExtStreamCreateWithCUMask failed: %s", hipGetErrorString(e));
-        }
-    }
-    *stream = (void *)ctx->queue_stream;
-    return VTMC_OK;
-}
-
 int32_t vtmc_last_placement(const vtmc_ctx *ctx, float ms[16], int32_t *n_candidates, int32_t *kept)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
@@ -985,385 +697,11 @@ int32_t vtmc_last_placement(const vtmc_ctx *ctx, float ms[16], int32_t *n_candid
     return VTMC_OK;
 }
 
-int32_t vtmc_release_streams(void)
-{
-    return release_parked_streams();
-}
-
 int32_t vtmc_last_stage_ms(vtmc_ctx *ctx, float ms[4])
 {
     if (!ctx || !ms) return VTMC_ERR_INVALID_ARG;
     if (!ctx->has_result) return fail(ctx, VTMC_ERR_NO_RESULT, "last_stage_ms before any extract");
     memcpy(ms, ctx->stage_ms, sizeof ctx->stage_ms);
-    return VTMC_OK;
-}
-
-int32_t vtmc_set_tuning(vtmc_ctx *ctx, const char *key, int32_t value)
-{
-    if (!ctx || !key) return VTMC_ERR_INVALID_ARG;
-    const std::string k(key);
-    // every key below selects code that tests/test_tuning_matrix.py compares with the oracle; a value outside a key's range is refused
-    auto ranged = [&](int &field, int lo, int hi) {
-        if (value < lo || value > hi) return fail(ctx, VTMC_ERR_INVALID_ARG, "tuning key '%s': %d is outside [%d, %d]", key, value, lo, hi);
-        field = value;
-        return (int)VTMC_OK;
-    };
-    if (k == "emit_fast_math") return ranged(ctx->tune.emit_fast_math, 0, 1);
-    if (k == "emit_once") return ranged(ctx->tune.emit_once, 0, 1);
-    if (k == "emit_dynamic") return ranged(ctx->tune.emit_dynamic, 0, 1);
-    if (k == "emit_sub_log2") return ranged(ctx->tune.emit_sub_log2, 0, 4);
-    if (k == "emit_row_masks") return ranged(ctx->tune.emit_row_masks, 0, 1);
-    if (k == "emit_wgs_per_cu") return ranged(ctx->tune.emit_wgs_per_cu, 0, 8);
-    // residency caps work by unused dynamic LDS; ONE workgroup per CU would ask for the whole 160 KB, which the runtime answers with abort(): refused
-    if ((k == "classify_wgs_per_cu" || k == "density_wgs_per_cu") && value == 1)
-        return fail(ctx, VTMC_ERR_INVALID_ARG, "tuning key '%s': a cap of one workgroup per CU is not supported (0: none, or 2 and more)", key);
-    if (k == "classify_wgs_per_cu") return ranged(ctx->tune.classify_wgs_per_cu, 0, 7);
-    if (k == "density_wgs_per_cu") return ranged(ctx->tune.density_wgs_per_cu, 0, 3);
-    if (k == "gather_beside") return ranged(ctx->tune.gather_beside, 0, 1);
-    if (k == "place_outputs") return ranged(ctx->tune.place_outputs, 0, 16);
-    if (k == "stage_events") return ranged(ctx->tune.stage_events, 0, 1);
-    if (k == "invalidate_signs") {   // the caller wrote to (or re-used the address of) a buffer the last fill left sign bits for
-        ctx->sign_of.valid = false;
-        return VTMC_OK;
-    }
-    if (k == "fill_keeps_signs") {
-        ctx->sign_of.valid = false;
-        return ranged(ctx->tune.fill_keeps_signs, 0, 1);
-    }
-#ifdef VTMC_DIAGNOSTICS   // output INVALID: diagnostic builds only (the product's kernels do not contain these branches)
-    if (k == "emit_ablate") ctx->tune.emit_ablate = value;
-    else if (k == "classify_ablate") ctx->tune.classify_ablate = value;
-    else if (k == "density_ablate") ctx->tune.density_ablate = value;
-    else
-#endif
-    return fail(ctx, VTMC_ERR_INVALID_ARG, "unknown tuning key '%s'", key);
-    return VTMC_OK;
-}
-
-int32_t vtmc_terrain_init(vtmc_ctx *ctx, int32_t width, int32_t elevation, int32_t height, float voxel_scale,
-                          const float terrain_origin[3], uint64_t seed)
-{
-    if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!terrain_origin) return fail(ctx, VTMC_ERR_INVALID_ARG, "terrain_origin is null");
-    if (int rc = check_dims(ctx, width, elevation, height)) return rc;
-    // VoxelTerrain.cs:141-142
-    if (width + 1 > 1025 || elevation + 1 > 1025 || height + 1 > 1025)
-        return fail(ctx, VTMC_ERR_DIMS, "too high resolution (exceeds 1025)");
-    if (!(voxel_scale > 0.0f)) return fail(ctx, VTMC_ERR_INVALID_ARG, "voxel_scale must be positive");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->has_terrain = false;
-    ctx->has_result = false;
-    TerrainShape sh{};
-    sh.dim_x = width + 2;
-    sh.dim_y = elevation + 2;
-    sh.dim_z = height + 2;
-    sh.scale = voxel_scale;
-    memcpy(sh.origin, terrain_origin, sizeof sh.origin);
-    sh.seed = seed;
-    const long long n = (long long)sh.dim_x * sh.dim_y * sh.dim_z;
-    if (int rc = ensure(ctx, ctx->terrain, sizeof(float) * (size_t)n)) return rc;
-    VTMC_HIP(ctx, launch_terrain_fill((float *)ctx->terrain.p, n, seed, ctx->n_cus, ctx->stream));
-    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->tshape = sh;
-    ctx->terrain_events = 0;
-    ctx->dirty.clear();
-    ctx->dirty_is_all = false;
-    ctx->has_terrain = true;
-    return VTMC_OK;
-}
-
-int32_t vtmc_terrain_update(vtmc_ctx *ctx, const vtmc_modifier *mods, int32_t n_mods, int32_t *n_dirty_blocks, int32_t *tri_count)
-{
-    if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_update before terrain_init");
-    if (n_mods < 0 || (n_mods > 0 && !mods)) return fail(ctx, VTMC_ERR_INVALID_ARG, "mods is null or n_mods < 0");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    const TerrainShape &sh = ctx->tshape;
-    const int W = sh.dim_x - 2, E = sh.dim_y - 2, H = sh.dim_z - 2;
-    const int nbx = W / 8, nby = E / 8, nbz = H / 8;
-    std::vector<uint8_t> mark((size_t)nbx * nby * nbz, 0);
-    size_t n_marked = 0;
-    auto floor_to_int = [](float v) {  // Mathf.FloorToInt, saturating
-        const float f = std::floor(v);
-        return f <= -2147483648.0f ? INT32_MIN : (f >= 2147483648.0f ? INT32_MAX : (int)f);
-    };
-    auto ceil_to_int = [](float v) {
-        const float f = std::ceil(v);
-        return f <= -2147483648.0f ? INT32_MIN : (f >= 2147483648.0f ? INT32_MAX : (int)f);
-    };
-    for (int32_t i = 0; i < n_mods; ++i) {
-        const vtmc_modifier &md = mods[i];
-        if (md.kind < VTMC_MOD_PLANE || md.kind > VTMC_MOD_HEIGHTMAP) return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: unknown kind %d", i, md.kind);
-        if (md.kind == VTMC_MOD_HEIGHTMAP && (!md.data || md.data_dims[0] < 1 || md.data_dims[1] < 1))
-            return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: heightmap data / dims missing", i);
-        // world -> sample index: (world - TerrainOrigin) / _voxelScale, floor / ceil, clamp (VoxelTerrain.cs:273-281)
-        int low[3], up[3];
-        const int top[3] = {W + 1, E + 1, H + 1};
-        for (int a = 0; a < 3; ++a) {
-            low[a] = std::max(floor_to_int((md.lower[a] - sh.origin[a]) / sh.scale), 0);
-            up[a] = std::min(ceil_to_int((md.upper[a] - sh.origin[a]) / sh.scale), top[a]);
-        }
-        TerrainModifierArgs a{};
-        a.kind = md.kind;
-        a.add_or_erode = md.add_or_erode ? 1 : 0;
-        memcpy(a.p, md.p, sizeof a.p);
-        a.lx = low[0];
-        a.ly = low[1];
-        a.lz = low[2];
-        // extents in 64 bits: floor/ceil saturate at INT32_MIN/MAX, so an inverted or far-away AABB must
-        // come out as an empty range (the reference's loops simply do not execute, VoxelTerrain.cs:284-286),
-        // never as a wrapped positive size; low >= 0 and up <= top bound a valid extent by the grid
-        int ext[3];
-        for (int k = 0; k < 3; ++k) {
-            const long long e = (long long)up[k] - (long long)low[k] + 1;
-            ext[k] = e <= 0 ? 0 : (int)std::min<long long>(e, (long long)top[k] - low[k] + 1);
-            if (low[k] > top[k]) ext[k] = 0;
-        }
-        a.dx = ext[0];
-        a.dy = ext[1];
-        a.dz = ext[2];
-        a.event = ++ctx->terrain_events;
-        if (md.kind == VTMC_MOD_HEIGHTMAP && a.dx > 0 && a.dy > 0 && a.dz > 0) {
-            // _heightmap (IslandModifier.cs:36) goes to the device; an earlier modifier of this queue may
-            // still be reading the previous one, hence the drain before the buffer is touched
-            const size_t bytes = sizeof(float) * (size_t)md.data_dims[0] * (size_t)md.data_dims[1];
-            VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (int rc = ensure(ctx, ctx->heightmap, bytes)) return rc;
-            VTMC_HIP(ctx, hipMemcpy(ctx->heightmap.p, md.data, bytes, hipMemcpyHostToDevice));
-            a.data = (const float *)ctx->heightmap.p;
-            a.dims0 = md.data_dims[0];
-            a.dims1 = md.data_dims[1];
-        }
-        if (a.dx > 0 && a.dy > 0 && a.dz > 0) VTMC_HIP(ctx, launch_terrain_modify((float *)ctx->terrain.p, sh, a, ctx->stream));
-        // dirty blocks: up >= 8b && low <= 8b + 8 on every axis (VoxelTerrain.cs:307-317), as index ranges
-        int b0[3], b1[3];
-        const int nb[3] = {nbx, nby, nbz};
-        bool any = true;
-        for (int k = 0; k < 3; ++k) {
-            // b <= up / 8 and b >= (low - 8) / 8 rounded up; the reference's loops leave an empty
-            // (low > up) AABB with its block tests, so the same arithmetic is used for it
-            const long long lo = (long long)low[k] - 8, hi = up[k];
-            long long f = lo <= 0 ? 0 : (lo + 7) / 8;
-            long long l = hi < 0 ? -1 : hi / 8;
-            if (l > nb[k] - 1) l = nb[k] - 1;
-            b0[k] = (int)f;
-            b1[k] = (int)l;
-            if (f > l) any = false;
-        }
-        if (any && n_marked < mark.size())
-            for (int bz = b0[2]; bz <= b1[2]; ++bz)
-                for (int by = b0[1]; by <= b1[1]; ++by) {
-                    uint8_t *row = &mark[(size_t)nbx * ((size_t)by + (size_t)nby * bz)];
-                    for (int bx = b0[0]; bx <= b1[0]; ++bx) {
-                        n_marked += !row[bx];
-                        row[bx] = 1;
-                    }
-                }
-    }
-    // _nextUpdateblocks (VoxelTerrain.cs:321), ordered by block id; a full rebuild needs no list
-    ctx->dirty.clear();
-    ctx->dirty_is_all = n_marked == mark.size();
-    if (!ctx->dirty_is_all) {
-        ctx->dirty.reserve(n_marked * 3);
-        for (int bz = 0; bz < nbz; ++bz)
-            for (int by = 0; by < nby; ++by)
-                for (int bx = 0; bx < nbx; ++bx)
-                    if (mark[(size_t)bx + (size_t)nbx * ((size_t)by + (size_t)nby * bz)]) {
-                        ctx->dirty.push_back(bx);
-                        ctx->dirty.push_back(by);
-                        ctx->dirty.push_back(bz);
-                    }
-    }
-    if (n_dirty_blocks) *n_dirty_blocks = (int32_t)n_marked;
-    // BatchUpdate (VoxelTerrain.cs:322-323: only when the set is not empty) on the resident grid
-    BlockSpace sp = dense_space((const float *)ctx->terrain.p, W, E, H, 1, sh.dim_x, (int64_t)sh.dim_x * sh.dim_y, 1, 0);
-    int n_volumes = 1;
-    if (!ctx->dirty_is_all) {  // a proper subset: device block list; every block: the dense streaming path
-        if (int rc = ensure(ctx, ctx->list, sizeof(int32_t) * 3 * std::max<size_t>(n_marked, 1))) return rc;
-        if (n_marked > 0)
-            VTMC_HIP(ctx, hipMemcpyAsync(ctx->list.p, ctx->dirty.data(), sizeof(int32_t) * 3 * n_marked, hipMemcpyHostToDevice, ctx->stream));
-        sp.list = (const int *)ctx->list.p;
-        sp.n_blocks = (int)n_marked;
-        n_volumes = 0;
-    }
-    int64_t T = 0;
-    if (int rc = extract_core(ctx, sp, n_volumes, 0, ctx->stream, &T)) return rc;
-    if (tri_count) *tri_count = (int32_t)T;
-    return VTMC_OK;
-}
-
-int32_t vtmc_terrain_dirty_blocks(vtmc_ctx *ctx, int32_t *dst, int32_t capacity_blocks, int32_t *n_blocks)
-{
-    if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_dirty_blocks before terrain_init");
-    const TerrainShape &sh = ctx->tshape;
-    const int nbx = (sh.dim_x - 2) / 8, nby = (sh.dim_y - 2) / 8, nbz = (sh.dim_z - 2) / 8;
-    const size_t n = ctx->dirty_is_all ? (size_t)nbx * nby * nbz : ctx->dirty.size() / 3;
-    if (n_blocks) *n_blocks = (int32_t)n;
-    if (!dst) return VTMC_OK;  // size query
-    if ((size_t)std::max(capacity_blocks, 0) < n) return fail(ctx, VTMC_ERR_CAPACITY, "capacity %d < %zu dirty blocks", capacity_blocks, n);
-    if (ctx->dirty_is_all) {
-        int32_t *o = dst;
-        for (int bz = 0; bz < nbz; ++bz)
-            for (int by = 0; by < nby; ++by)
-                for (int bx = 0; bx < nbx; ++bx) {
-                    *o++ = bx;
-                    *o++ = by;
-                    *o++ = bz;
-                }
-    } else if (n) {
-        memcpy(dst, ctx->dirty.data(), n * 3 * sizeof(int32_t));
-    }
-    return VTMC_OK;
-}
-
-int32_t vtmc_terrain_read_samples(vtmc_ctx *ctx, float *dst, int64_t stride_x, int64_t stride_y, int64_t stride_z)
-{
-    if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_read_samples before terrain_init");
-    if (!dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "dst is null");
-    if (stride_x <= 0 || stride_y <= 0 || stride_z <= 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "strides must be positive");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    const TerrainShape &sh = ctx->tshape;
-    const size_t n = (size_t)sh.dim_x * sh.dim_y * sh.dim_z;
-    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (stride_x == 1 && stride_y == sh.dim_x && stride_z == (int64_t)sh.dim_x * sh.dim_y) {
-        VTMC_HIP(ctx, hipMemcpy(dst, ctx->terrain.p, n * sizeof(float), hipMemcpyDeviceToHost));
-        return VTMC_OK;
-    }
-    std::vector<float> tmp(n);
-    VTMC_HIP(ctx, hipMemcpy(tmp.data(), ctx->terrain.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    size_t i = 0;
-    for (int z = 0; z < sh.dim_z; ++z)
-        for (int y = 0; y < sh.dim_y; ++y)
-            for (int x = 0; x < sh.dim_x; ++x) dst[x * stride_x + y * stride_y + z * stride_z] = tmp[i++];
-    return VTMC_OK;
-}
-
-int32_t vtmc_terrain_device_grid(vtmc_ctx *ctx, const float **d_samples, int64_t strides[3], int32_t dims[3])
-{
-    if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_device_grid before terrain_init");
-    const TerrainShape &sh = ctx->tshape;
-    if (d_samples) *d_samples = (const float *)ctx->terrain.p;
-    if (strides) {
-        strides[0] = 1;
-        strides[1] = sh.dim_x;
-        strides[2] = (int64_t)sh.dim_x * sh.dim_y;
-    }
-    if (dims) {
-        dims[0] = sh.dim_x;
-        dims[1] = sh.dim_y;
-        dims[2] = sh.dim_z;
-    }
-    return VTMC_OK;
-}
-
-int32_t vtmc_density_fill_device_async(vtmc_ctx *ctx, const vtmc_density_params *params, const int32_t *origins, int32_t n_volumes,
-                                 int32_t dim_x, int32_t dim_y, int32_t dim_z, int64_t stride_x, int64_t stride_y,
-                                 int64_t stride_z, int64_t volume_stride, float *d_out, void *stream)
-{
-    if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!params || !origins || !d_out) return fail(ctx, VTMC_ERR_INVALID_ARG, "null argument");
-    if (n_volumes <= 0 || dim_x <= 0 || dim_y <= 0 || dim_z <= 0 || params->octaves < 1 || params->octaves > 16)
-        return fail(ctx, VTMC_ERR_INVALID_ARG, "bad volume count, dims or octaves");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    if (!ctx->perm_valid || ctx->perm_seed != params->seed) {
-        unsigned char perm[256];
-        density_permutation(params->seed, perm);
-        if (int rc = ensure(ctx, ctx->perm, 256)) return rc;
-        VTMC_HIP(ctx, hipStreamSynchronize(st));  // nothing queued may still read the old table
-        VTMC_HIP(ctx, hipMemcpy(ctx->perm.p, perm, 256, hipMemcpyHostToDevice));
-        ctx->perm_seed = params->seed;
-        ctx->perm_valid = true;
-    }
-    const size_t rows_bytes = density_rows_bytes(n_volumes, dim_y, dim_z);
-    if (ctx->origins.bytes < sizeof(int32_t) * 3 * (size_t)n_volumes || ctx->yrows.bytes < rows_bytes)
-        VTMC_HIP(ctx, hipStreamSynchronize(st));  // about to reallocate
-    if (int rc = ensure(ctx, ctx->origins, sizeof(int32_t) * 3 * (size_t)n_volumes)) return rc;
-    if (int rc = ensure(ctx, ctx->yrows, rows_bytes)) return rc;
-    // The caller's array is only borrowed for this call: it is copied into pinned staging and uploaded from there, stream-ordered
-    // behind any earlier fill of this context that still reads the previous origins.  No wait on `st`: a host that pipelines
-    // batches on one stream (streaming.ChunkStream) must be able to queue this fill behind an extract that is still running.
-    const size_t org_bytes = sizeof(int32_t) * 3 * (size_t)n_volumes;
-    if (ctx->origins_upload_pending) VTMC_HIP(ctx, hipEventSynchronize(ctx->ev_origins));   // the previous upload has left the staging words
-    if (ctx->h_origins_bytes < org_bytes) {
-        release_pinned((void **)&ctx->h_origins, &ctx->h_origins_bytes);
-        VTMC_HIP(ctx, hipHostMalloc((void **)&ctx->h_origins, org_bytes, hipHostMallocDefault));
-        ctx->h_origins_bytes = org_bytes;
-    }
-    memcpy(ctx->h_origins, origins, org_bytes);
-    // Pinned staging never rides the context's own-queue stream (a CU-mask stream with pinned copies on it hung a C++ host at process exit,
-    // profiles/r05/stream_overlap.txt): the ordinary stream carries the upload, behind the previous fill (which still reads the previous
-    // origins) and ahead of this one, by events.
-    hipStream_t up = st;
-    if (ctx->queue_stream && st == ctx->queue_stream) {
-        up = ctx->stream;
-        if (ctx->fill_timed) VTMC_HIP(ctx, hipStreamWaitEvent(up, ctx->ev_fill[1], 0));
-    }
-    VTMC_HIP(ctx, hipMemcpyAsync(ctx->origins.p, ctx->h_origins, org_bytes, hipMemcpyHostToDevice, up));
-    VTMC_HIP(ctx, hipEventRecord(ctx->ev_origins, up));
-    if (up != st) VTMC_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_origins, 0));
-    ctx->origins_upload_pending = true;
-    DensityLaunch dl{};
-    dl.frequency = params->frequency;
-    dl.lacunarity = params->lacunarity;
-    dl.gain = params->gain;
-    dl.ramp_scale = params->ramp_scale;
-    dl.ramp_center = params->ramp_center;
-    dl.octaves = params->octaves;
-    dl.dx = dim_x;
-    dl.dy = dim_y;
-    dl.dz = dim_z;
-    dl.sx = stride_x;
-    dl.sy = stride_y;
-    dl.sz = stride_z;
-    dl.sv = volume_stride;
-    dl.n_volumes = n_volumes;
-    dl.ablate = ctx->tune.density_ablate;
-    dl.wgs_per_cu = ctx->tune.density_wgs_per_cu;
-    // the samples' sign bits for the classify stage of this same buffer (the streaming driver's setting)
-    unsigned long long *d_signs = nullptr;
-    ctx->sign_of.valid = false;
-    if (ctx->tune.fill_keeps_signs && density_writes_signs(dl)) {
-        const size_t sb = density_sign_words(dl) * sizeof(unsigned long long);
-        if (ctx->signs.bytes < sb) VTMC_HIP(ctx, hipStreamSynchronize(st));  // about to reallocate
-        if (int rc = ensure(ctx, ctx->signs, sb)) return rc;
-        d_signs = (unsigned long long *)ctx->signs.p;
-        ctx->sign_of.valid = true;
-        ctx->sign_of.d_out = d_out;
-        ctx->sign_of.dx = dim_x;
-        ctx->sign_of.dy = dim_y;
-        ctx->sign_of.dz = dim_z;
-        ctx->sign_of.n_volumes = n_volumes;
-        ctx->sign_of.sv = volume_stride;
-    }
-    VTMC_HIP(ctx, hipEventRecord(ctx->ev_fill[0], st));
-    VTMC_HIP(ctx, launch_density(dl, (const unsigned char *)ctx->perm.p, (const int *)ctx->origins.p, (float *)ctx->yrows.p, d_out, d_signs, st));
-    VTMC_HIP(ctx, hipEventRecord(ctx->ev_fill[1], st));
-    ctx->fill_timed = true;
-    return VTMC_OK;
-}
-
-int32_t vtmc_last_fill_ms(vtmc_ctx *ctx, float *ms)
-{
-    if (!ctx || !ms) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->fill_timed) return fail(ctx, VTMC_ERR_NO_RESULT, "last_fill_ms before any density fill");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    VTMC_HIP(ctx, hipEventSynchronize(ctx->ev_fill[1]));
-    VTMC_HIP(ctx, hipEventElapsedTime(ms, ctx->ev_fill[0], ctx->ev_fill[1]));
-    return VTMC_OK;
-}
-
-int32_t vtmc_density_fill_device(vtmc_ctx *ctx, const vtmc_density_params *params, const int32_t *origins, int32_t n_volumes,
-                                 int32_t dim_x, int32_t dim_y, int32_t dim_z, int64_t stride_x, int64_t stride_y,
-                                 int64_t stride_z, int64_t volume_stride, float *d_out, void *stream)
-{
-    if (int32_t rc = vtmc_density_fill_device_async(ctx, params, origins, n_volumes, dim_x, dim_y, dim_z, stride_x, stride_y, stride_z,
-                                                    volume_stride, d_out, stream))
-        return rc;
-    VTMC_HIP(ctx, hipStreamSynchronize(stream ? (hipStream_t)stream : ctx->stream));
     return VTMC_OK;
 }
 

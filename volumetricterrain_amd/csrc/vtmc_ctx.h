@@ -1,17 +1,43 @@
 // vtmc_ctx.h -- the context object behind include/vtmc.h and the small host helpers every
-// translation unit of the C-ABI layer shares (vtmc_api.hip, chunk_io.hip, comm.hip).  Not installed.
+// translation unit of the C-ABI layer shares (context.hip, vtmc_api.hip, terrain.hip, density.hip, chunk_io.hip, comm.hip).  Not installed.
 #ifndef VTMC_CTX_H
 #define VTMC_CTX_H
 #include "../../include/vtmc.h"
 #include "vtmc_internal.h"
 
 #include <string>
+#include <utility>
 #include <vector>
 
-struct VtmcDevBuf {
-    void *p = nullptr;
+namespace vtmc {
+// Memory a context owns: device memory (VtmcDevBuf, grown by ensure) or pinned host memory (VtmcPinnedBuf, allocated by pin).  Move-only, so
+// one object names one allocation, and freed by its destructor.  Pointer and size are always cleared together: a buffer freed with its size
+// left standing is written to by the next call that finds it "large enough" (round 3's double free).
+template <typename T, hipError_t (*Free)(void *)>
+struct OwnedBuf {
+    T *p = nullptr;
     size_t bytes = 0;
+    OwnedBuf() = default;
+    OwnedBuf(OwnedBuf &&o) noexcept { swap(o); }
+    OwnedBuf &operator=(OwnedBuf o) noexcept { return swap(o); }   // `o` takes what this held and frees it
+    ~OwnedBuf() { release(); }
+    OwnedBuf &swap(OwnedBuf &o) noexcept
+    {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+        return *this;
+    }
+    void release()
+    {
+        if (p) quiet(Free(p));
+        p = nullptr;
+        bytes = 0;
+    }
 };
+}  // namespace vtmc
+typedef vtmc::OwnedBuf<void, hipFree> VtmcDevBuf;
+template <typename T>
+using VtmcPinnedBuf = vtmc::OwnedBuf<T, hipHostFree>;
 
 // An extract that has been queued on a stream and not yet completed by extract_finish().
 struct VtmcPending {
@@ -40,7 +66,7 @@ struct vtmc_ctx {
     bool last_indexed = false;
     int64_t last_verts = 0;
     uint32_t *h_totals_dev = nullptr;  // the same pinned words as the device sees them (the fused scan writes its totals there)
-    uint32_t *h_totals = nullptr;  // pinned: the scan's totals ({T sat, nActive, T lo, T hi}, then the vertex scan's), 64 words
+    VtmcPinnedBuf<uint32_t> h_totals;  // pinned: the scan's totals ({T sat, nActive, T lo, T hi}, then the vertex scan's), 64 words
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // [0..3] stage timing, [4] staging copies
     VtmcDevBuf signs;               // the sign volume of the last z-walk fill (tuning key "fill_keeps_signs")
     struct {
@@ -49,11 +75,9 @@ struct vtmc_ctx {
         int dx = 0, dy = 0, dz = 0, n_volumes = 0;
         long long sv = 0;
     } sign_of;                      // which buffer / layout `signs` describes
-    float *h_stage = nullptr;       // pinned staging of host-gathered tiles (vtmc_extract_grid with a dirty list)
-    size_t h_stage_bytes = 0;
+    VtmcPinnedBuf<float> h_stage;   // pinned staging of host-gathered tiles (vtmc_extract_grid with a dirty list)
     int h_stage_small_calls = 0;    // consecutive calls that needed far less than an over-sized staging buffer holds (the trim waits for kStageTrimAfter of them)
-    int32_t *h_origins = nullptr;   // pinned staging of the sampler's chunk origins
-    size_t h_origins_bytes = 0;
+    VtmcPinnedBuf<int32_t> h_origins;   // pinned staging of the sampler's chunk origins
     hipEvent_t ev_origins = nullptr;   // behind the upload from h_origins
     bool origins_upload_pending = false;
     float stage_ms[4] = {0, 0, 0, 0};
@@ -102,13 +126,23 @@ namespace vtmc {
 // sets the context's (or, with ctx == nullptr, the thread's create-) error text and returns `code`
 int fail(vtmc_ctx *ctx, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
 int ensure(vtmc_ctx *ctx, VtmcDevBuf &b, size_t bytes);  // grow-only device buffer
-void release(VtmcDevBuf &b);
-const char *create_error_text();
-void comm_release(vtmc_ctx *ctx);  // comm.hip: called by vtmc_destroy
-// vtmc_api.hip: a context's streams come from (and return to) a per-device pool and are never destroyed -- see StreamPool there
+inline void release(VtmcDevBuf &b) { b.release(); }
+template <typename T>
+hipError_t pin(VtmcPinnedBuf<T> &b, size_t bytes)   // replaces the buffer; empty when it fails
+{
+    b.release();
+    const hipError_t e = hipHostMalloc((void **)&b.p, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) b.bytes = bytes;
+    else b.p = nullptr;
+    return e;
+}
+// a context's streams come from (and return to) a per-device pool and are never destroyed -- see StreamPool there
 hipError_t take_stream(int device, bool own_queue, int n_cus, hipStream_t *out);
-void park_stream(int device, bool own_queue, hipStream_t s);
-int release_parked_streams();
+void comm_release(vtmc_ctx *ctx);  // comm.hip: called by vtmc_destroy
+int check_dims(vtmc_ctx *ctx, int nx, int ny, int nz);
+BlockSpace dense_space(const float *d_base, int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz, int n_volumes, int64_t sv);
+int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp);   // sp then walks the (bx,by,bz) list
+int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, int32_t *tri_count);   // queued on the context's stream and finished
 }  // namespace vtmc
 
 #define VTMC_HIP(ctx, expr)                                                                                \
