@@ -325,6 +325,44 @@ int32_t vtmc_terrain_read_samples(vtmc_ctx *ctx, float *dst, int64_t stride_x, i
 /* Device pointer + element strides of the grid (x fastest), for GPU-resident callers. */
 int32_t vtmc_terrain_device_grid(vtmc_ctx *ctx, const float **d_samples, int64_t strides[3], int32_t dims[3]);
 
+/* ------------------------------------------------------------------------------------------
+ * Ray picking -- replaces the Physics.Raycast of the interactive edit (SceneManager.cs:114-131)
+ * against the MeshColliders that BatchUpdate cooks from the extracted mesh (VoxelTerrain.cs:448-465),
+ * without any mesh on the host.  The surface is the triangle set vtmc_extract_grid emits for every
+ * block with emit_fast_math = 0 (positions bit for bit), a block-local vertex p of block b lying at
+ * world origin + (8b + p) * voxel_scale.  A ray is (o, d) in world space, d of any non-zero length;
+ * the nearest triangle with 0 <= distance <= max_distance along d/|d| is reported.  Faces are
+ * single-sided as a MeshCollider's: a triangle counts when dot(d, cross(p1-p0, p2-p0)) < 0 (its normal
+ * points from solid to air); VTMC_RAY_TWO_SIDED counts both sides.  Zero-area triangles are never hit.
+ * A ray with a zero or non-finite direction or a non-finite origin is a miss.  max_distance may be
+ * +inf; NaN or <= 0 is VTMC_ERR_INVALID_ARG.  Results are deterministic and do not depend on the
+ * grid's strides.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct vtmc_ray_hit {
+    float distance;        /* world units along the normalised direction; -1: no hit */
+    float point[3];        /* world */
+    float normal[3];       /* unit face normal cross(p1-p0, p2-p0) of the hit triangle (world) */
+    float barycentric[2];  /* (u, v): point = (1-u-v) p0 + u p1 + v p2 */
+    int32_t block[3];      /* (bx, by, bz); -1 on a miss */
+    int32_t cell;          /* x + 8y + 64z inside the block; -1 on a miss */
+    int32_t triangle;      /* i of the case's triangle list, 0..4; -1: no hit */
+} vtmc_ray_hit;            /* 56 bytes; (block, cell, triangle) names one triangle of the canonical order */
+
+#define VTMC_RAY_TWO_SIDED 1u
+
+/* Physics.Raycast against the terrain of vtmc_terrain_init / _update: host arrays (n_rays x 3 floats each),
+ * synchronous, hits[n_rays].  VTMC_ERR_NO_RESULT before vtmc_terrain_init. */
+int32_t vtmc_terrain_raycast(vtmc_ctx *ctx, const float *origins, const float *directions, int32_t n_rays,
+                             float max_distance, uint32_t flags, vtmc_ray_hit *hits);
+
+/* The same query on any device grid of (nx+2, ny+2, nz+2) samples (element strides as vtmc_extract_grid), device
+ * rays and hits, queued on `stream` (NULL = the context's stream) without synchronising. */
+int32_t vtmc_raycast_device(vtmc_ctx *ctx, const float *d_grid, int32_t nx, int32_t ny, int32_t nz,
+                            int64_t stride_x, int64_t stride_y, int64_t stride_z,
+                            const float origin[3], float voxel_scale,
+                            const float *d_origins, const float *d_directions, int32_t n_rays,
+                            float max_distance, uint32_t flags, vtmc_ray_hit *d_hits, void *stream);
+
 /* The same fill without the final synchronisation: queued on `stream` (NULL = the context's stream)
  * and ordered only by it, so a streaming driver can generate batch k+1 on one context / stream while
  * batch k is extracted on another (BASELINE config "2048^3 streaming grid, double-buffered chunks").

@@ -19,6 +19,11 @@ assert TRI_DTYPE.itemsize == 76  # CSTriangle.stride, VoxelTerrain.cs:36
 
 VERTEX_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3)])   # vtmc_vertex
 assert VERTEX_DTYPE.itemsize == 24
+# vtmc_ray_hit: one answer of vtmc_terrain_raycast / vtmc_raycast_device
+RAY_HIT_DTYPE = np.dtype([("distance", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3), ("barycentric", "<f4", 2),
+                          ("block", "<i4", 3), ("cell", "<i4"), ("triangle", "<i4")])
+assert RAY_HIT_DTYPE.itemsize == 56
+RAY_TWO_SIDED = 1
 OUTPUT_SOUP, OUTPUT_INDEXED = 0, 1
 
 OK = 0
@@ -37,6 +42,7 @@ SYMBOLS = [
     "vtmc_comm_unique_id", "vtmc_comm_init_rank", "vtmc_comm_destroy", "vtmc_comm_share", "vtmc_allgather_volume_counts",
     "vtmc_copy_to_host", "vtmc_chunk_write", "vtmc_chunk_read",
     "vtmc_extract_volumes_device_async", "vtmc_extract_finish", "vtmc_last_fill_ms", "vtmc_context_stream", "vtmc_release_streams", "vtmc_last_placement",
+    "vtmc_terrain_raycast", "vtmc_raycast_device",
 ]
 COMM_ID_BYTES = 128
 
@@ -140,6 +146,10 @@ def load(path=None):
     L.vtmc_terrain_dirty_blocks.argtypes = [vp, vp, i32, P(i32)]
     L.vtmc_terrain_read_samples.argtypes = [vp, vp, i64, i64, i64]
     L.vtmc_terrain_device_grid.argtypes = [vp, P(vp), P(i64 * 3), P(i32 * 3)]
+    if not explicit or hasattr(L, "vtmc_terrain_raycast"):
+        L.vtmc_terrain_raycast.argtypes = [vp, vp, vp, i32, ctypes.c_float, u32, vp]
+        L.vtmc_raycast_device.argtypes = [vp, vp, i32, i32, i32, i64, i64, i64, P(ctypes.c_float * 3), ctypes.c_float,
+                                          vp, vp, i32, ctypes.c_float, u32, vp, vp]
     L.vtmc_comm_unique_id.argtypes = [vp]
     L.vtmc_comm_init_rank.argtypes = [vp, vp, i32, i32]
     L.vtmc_comm_destroy.argtypes = [vp]

@@ -1,0 +1,410 @@
+// raycast.hip -- ray picking against the marching-cubes surface of a density grid (hand-written gfx950 / CDNA4, wave64).
+//
+// Replaces the Physics.Raycast of the interactive edit (paths relative to /root/reference/Unity-Project/Assets/Scripts/):
+//   SceneManager.cs:114-131  Physics.Raycast(cursor ray) -> hit.point -> TerrainEngine.ModifyTerrain
+//   VoxelTerrain.cs:448-465  the per-block MeshColliders that query runs against          -> raycast_kernel
+// The surface is never materialised: cells along the ray are classified and their triangles rebuilt from the samples with the
+// arithmetic of the exact-mode emit (CollectTriNum.compute:41-64 case, MarchingCube.compute:119-151 vertices and winding), so a
+// cell's triangles equal the extracted ones bit for bit (the library is built with -ffp-contract=off; `/` is correctly rounded).
+//
+// One workgroup of kWaves waves per ray.  The ray is clipped to the meshed box [0,nx]x[0,ny]x[0,nz] (grid units) and the clipped
+// parameter interval cut into 64 * kWaves equal sub-intervals, one per lane; a lane walks the cells of its sub-interval with a 3-D
+// DDA (Amanatides & Woo), kBatch cells at a time: the kBatch * 8 corner loads of a batch are all issued before the first is
+// used, so a lane waits about one memory latency per batch instead of one per cell.  After each batch the workgroup agrees
+// (one barrier) on the lowest lane that has a hit: lanes after it stop -- their cells lie farther along the ray.  The answer is
+// the nearest hit over all lanes (lowest lane on a tie): a wave reduction, then the kWaves wave results through LDS.
+//
+// Intersection: watertight ray / triangle test (Woop, Benthin & Wald 2013) in float64 on the exact grid-unit vertices 8b + p, so
+// two triangles sharing an edge cannot both miss a ray crossing it.  Everything after the vertex positions is float64: the
+// ray transform is the same for every triangle, and nothing depends on the grid's layout or on which lane tested a cell.
+#include "vtmc_ctx.h"
+#include <cmath>
+#include <cstring>
+
+namespace vtmc {
+
+constexpr int kWaves = 4;                 // waves per ray
+constexpr int kRayThreads = 64 * kWaves;  // lanes (= sub-intervals) per ray
+constexpr int kBatch = 4;                 // cells a lane loads before it evaluates them
+
+struct RaycastArgs {
+    const float *grid;
+    long long sx, sy, sz;  // element strides
+    int n[3];              // cells per axis
+    double origin[3];      // world position of sample (0,0,0)
+    double scale;          // voxel_scale
+    const float *ro, *rd;  // n_rays x 3 each
+    vtmc_ray_hit *hits;
+    int n_rays;
+    float max_distance;
+    int two_sided;
+    const unsigned long long *vert_packed;  // DeviceTables::vert_packed
+};
+
+// cube corner c of MarchingCube.compute:46-50 ({0,0,0},{1,0,0},{1,1,0},{0,1,0},{0,0,1},{1,0,1},{1,1,1},{0,1,1}) along each axis
+__device__ __forceinline__ int corner_x(int c) { return (c ^ (c >> 1)) & 1; }
+__device__ __forceinline__ int corner_y(int c) { return (c >> 1) & 1; }
+__device__ __forceinline__ int corner_z(int c) { return (c >> 2) & 1; }
+// endpoints of cube edge e, MarchingCube.compute:40-43 ({0,1},{1,2},{2,3},{3,0},{4,5},{5,6},{6,7},{7,4},{0,4},{1,5},{2,6},{3,7})
+__device__ __forceinline__ int edge_a(int e) { return e < 8 ? e : e - 8; }
+__device__ __forceinline__ int edge_b(int e) { return e < 8 ? (e & 4) | ((e + 1) & 3) : e - 4; }
+
+// s[i] for a runtime i as a tree of selects on i's bits: a runtime index into a register array (or a chain of i == q
+// selects, which the compiler folds back into one) puts the array in scratch
+__device__ __forceinline__ float pick8(const float (&s)[8], int i)
+{
+    const bool b0 = i & 1, b1 = i & 2, b2 = i & 4;
+    const float s01 = b0 ? s[1] : s[0], s23 = b0 ? s[3] : s[2], s45 = b0 ? s[5] : s[4], s67 = b0 ? s[7] : s[6];
+    const float s03 = b1 ? s23 : s01, s47 = b1 ? s67 : s45;
+    return b2 ? s47 : s03;
+}
+__device__ __forceinline__ double pick3(double x, double y, double z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
+
+// Block-local position of the vertex on cube edge e of the cell with block-local corner (lx, ly, lz): MarchingCube.compute:119-133
+// as the exact-mode emit and the oracle evaluate it -- t = -a / (b - a), p = u + t * (v - u), endpoints in the reference's order.
+__device__ __forceinline__ void edge_vertex(const float (&s)[8], int lx, int ly, int lz, int e, float p[3])
+{
+    const int a = edge_a(e), b = edge_b(e);
+    const float va = pick8(s, a), vb = pick8(s, b);
+    const float t = (-va) / (vb - va);
+    const int l[3] = {lx, ly, lz};
+    const int oa[3] = {corner_x(a), corner_y(a), corner_z(a)}, ob[3] = {corner_x(b), corner_y(b), corner_z(b)};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float u = (float)l[k] + (float)oa[k];
+        const float v = (float)l[k] + (float)ob[k];
+        p[k] = u + t * (v - u);
+    }
+}
+
+struct Ray {
+    double o[3], d[3];  // grid units; d = unit world direction / voxel_scale, so the parameter is the world distance
+    int kx, ky, kz;     // Woop's axis permutation
+    double Sx, Sy, Sz;  // ... and shear
+};
+
+struct Best {
+    double t = INFINITY;
+    float u = 0.f, v = 0.f, nrm[3] = {0.f, 0.f, 0.f};
+    int c[3] = {0, 0, 0};
+    int tri = -1;
+};
+
+// the triangles of one cell (global cell index c, corner samples s in MarchingCube.compute order) against the ray
+__device__ __forceinline__ void intersect_cell(const RaycastArgs &a, const unsigned long long *s_cases, const Ray &r, const float (&s)[8], int cx, int cy,
+                                               int cz, Best &best)
+{
+    unsigned cs = 0;  // CollectTriNum.compute:41-51: strict '>', NaN is outside
+#pragma unroll
+    for (int q = 0; q < 8; ++q) cs |= (unsigned)(s[q] > 0.f) << q;
+    if (cs == 0u || cs == 255u) return;  // the two cases without triangles (edge mask 0)
+    const unsigned long long w = s_cases[cs];
+    const int lx = cx & 7, ly = cy & 7, lz = cz & 7;
+    const double bx = (double)(cx - lx), by = (double)(cy - ly), bz = (double)(cz - lz);
+    for (int i = 0; i < 5; ++i) {
+        const int e0 = (int)(w >> (12 * i)) & 15, e1 = (int)(w >> (12 * i + 4)) & 15, e2 = (int)(w >> (12 * i + 8)) & 15;
+        if (e0 == 15) continue;  // MarchingCube.compute:141
+        float p0[3], p1[3], p2[3];
+        edge_vertex(s, lx, ly, lz, e0, p0);
+        edge_vertex(s, lx, ly, lz, e2, p1);  // winding swap, MarchingCube.compute:151
+        edge_vertex(s, lx, ly, lz, e1, p2);
+        // grid units, exact: 8b + p
+        const double P0[3] = {bx + p0[0], by + p0[1], bz + p0[2]};
+        const double P1[3] = {bx + p1[0], by + p1[1], bz + p1[2]};
+        const double P2[3] = {bx + p2[0], by + p2[1], bz + p2[2]};
+        const double e1x = P1[0] - P0[0], e1y = P1[1] - P0[1], e1z = P1[2] - P0[2];
+        const double e2x = P2[0] - P0[0], e2y = P2[1] - P0[1], e2z = P2[2] - P0[2];
+        const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+        const double nn = nx * nx + ny * ny + nz * nz;
+        if (!(nn > 0.0)) continue;  // zero area, or a NaN sample on the way
+        if (!a.two_sided && !(nx * r.d[0] + ny * r.d[1] + nz * r.d[2] < 0.0)) continue;  // single-sided: the face must look at the ray
+        // Woop, Benthin & Wald 2013
+        const double Ax0 = P0[0] - r.o[0], Ay0 = P0[1] - r.o[1], Az0 = P0[2] - r.o[2];
+        const double Bx0 = P1[0] - r.o[0], By0 = P1[1] - r.o[1], Bz0 = P1[2] - r.o[2];
+        const double Cx0 = P2[0] - r.o[0], Cy0 = P2[1] - r.o[1], Cz0 = P2[2] - r.o[2];
+        const double Akz = pick3(Ax0, Ay0, Az0, r.kz), Bkz = pick3(Bx0, By0, Bz0, r.kz), Ckz = pick3(Cx0, Cy0, Cz0, r.kz);
+        const double Ax = pick3(Ax0, Ay0, Az0, r.kx) - r.Sx * Akz, Ay = pick3(Ax0, Ay0, Az0, r.ky) - r.Sy * Akz;
+        const double Bx = pick3(Bx0, By0, Bz0, r.kx) - r.Sx * Bkz, By = pick3(Bx0, By0, Bz0, r.ky) - r.Sy * Bkz;
+        const double Cx = pick3(Cx0, Cy0, Cz0, r.kx) - r.Sx * Ckz, Cy = pick3(Cx0, Cy0, Cz0, r.ky) - r.Sy * Ckz;
+        const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+        if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) continue;
+        const double det = U + V + W;
+        if (det == 0.0) continue;
+        const double T = U * (r.Sz * Akz) + V * (r.Sz * Bkz) + W * (r.Sz * Ckz);
+        const double t = T / det;
+        if (!(t >= 0.0) || !((float)t <= a.max_distance) || !(t < best.t)) continue;
+        const double inv = 1.0 / sqrt(nn);
+        best.t = t;
+        best.u = (float)(V / det);
+        best.v = (float)(W / det);
+        best.nrm[0] = (float)(nx * inv);
+        best.nrm[1] = (float)(ny * inv);
+        best.nrm[2] = (float)(nz * inv);
+        best.c[0] = cx;
+        best.c[1] = cy;
+        best.c[2] = cz;
+        best.tri = i;
+    }
+}
+
+__device__ __forceinline__ bool finite3(const float *v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
+
+__global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
+{
+    static_assert(kRayThreads == 256, "one table word per thread");
+    __shared__ unsigned long long s_cases[256];  // the case table (DeviceTables::vert_packed), read by the first barrier of the walk
+    __shared__ int s_first[kWaves];
+    __shared__ double s_t[kWaves];
+    __shared__ int s_lane[kWaves];
+    const int ray = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    s_cases[tid] = a.vert_packed[tid];
+    const float o[3] = {a.ro[3ll * ray], a.ro[3ll * ray + 1], a.ro[3ll * ray + 2]};
+    const float d[3] = {a.rd[3ll * ray], a.rd[3ll * ray + 1], a.rd[3ll * ray + 2]};
+
+    Ray r;
+    double dn[3] = {0.0, 0.0, 0.0};
+    bool ok = finite3(o) && finite3(d);
+    double t_in = 0.0, t_out = -1.0;
+    if (ok) {
+        const double len = sqrt((double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2]);
+        ok = len > 0.0;
+        t_out = (double)a.max_distance;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            dn[k] = (double)d[k] / len;
+            r.o[k] = ((double)o[k] - a.origin[k]) / a.scale;
+            r.d[k] = dn[k] / a.scale;
+            // slab clip against the meshed box [0, n]: every triangle lies inside it
+            if (r.d[k] != 0.0) {
+                double t0 = (0.0 - r.o[k]) / r.d[k], t1 = ((double)a.n[k] - r.o[k]) / r.d[k];
+                if (t0 > t1) {
+                    const double x = t0;
+                    t0 = t1;
+                    t1 = x;
+                }
+                t_in = fmax(t_in, t0);
+                t_out = fmin(t_out, t1);
+            } else if (r.o[k] < 0.0 || r.o[k] > (double)a.n[k]) {
+                ok = false;
+            }
+        }
+        ok = ok && t_in <= t_out;
+    }
+    Best best;
+    bool active = ok;
+    int c[3] = {0, 0, 0}, step[3] = {0, 0, 0};
+    double tmax[3] = {INFINITY, INFINITY, INFINITY}, inv[3] = {0.0, 0.0, 0.0}, tb = 0.0;
+    if (ok) {
+        const double ad[3] = {fabs(r.d[0]), fabs(r.d[1]), fabs(r.d[2])};
+        r.kz = ad[0] >= ad[1] && ad[0] >= ad[2] ? 0 : (ad[1] >= ad[2] ? 1 : 2);
+        r.kx = r.kz == 2 ? 0 : r.kz + 1;
+        r.ky = r.kx == 2 ? 0 : r.kx + 1;
+        const double dkz = pick3(r.d[0], r.d[1], r.d[2], r.kz);
+        if (dkz < 0.0) {
+            const int x = r.kx;
+            r.kx = r.ky;
+            r.ky = x;
+        }
+        r.Sx = pick3(r.d[0], r.d[1], r.d[2], r.kx) / dkz;
+        r.Sy = pick3(r.d[0], r.d[1], r.d[2], r.ky) / dkz;
+        r.Sz = 1.0 / dkz;
+        // this lane's sub-interval [ta, tb] and the cell it starts in
+        const double span = t_out - t_in;
+        const double ta = t_in + span * ((double)tid / kRayThreads);
+        tb = tid == kRayThreads - 1 ? t_out : t_in + span * ((double)(tid + 1) / kRayThreads);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double p = r.o[k] + ta * r.d[k];
+            int ci = (int)fmin(fmax(floor(p), 0.0), (double)(a.n[k] - 1));
+            c[k] = ci;
+            step[k] = r.d[k] > 0.0 ? 1 : (r.d[k] < 0.0 ? -1 : 0);
+            if (step[k]) {
+                inv[k] = 1.0 / r.d[k];   // the walk multiplies: a float64 division per step costs a dozen instructions
+                tmax[k] = ((double)(ci + (step[k] > 0)) - r.o[k]) * inv[k];
+            }
+        }
+    }
+    int budget = a.n[0] + a.n[1] + a.n[2] + 3;  // no lane walks more cells than a ray can cross
+    const long long corner[8] = {0, a.sx, a.sx + a.sy, a.sy, a.sz, a.sx + a.sz, a.sx + a.sy + a.sz, a.sy + a.sz};
+
+    while (__syncthreads_or(active)) {
+        float s[kBatch][8];
+        int cc[kBatch][3];
+        bool valid[kBatch];
+#pragma unroll
+        for (int j = 0; j < kBatch; ++j) {
+            valid[j] = active;
+            cc[j][0] = c[0];
+            cc[j][1] = c[1];
+            cc[j][2] = c[2];
+            if (active) {
+                const float *base = a.grid + ((long long)c[0] * a.sx + (long long)c[1] * a.sy + (long long)c[2] * a.sz);
+#pragma unroll
+                for (int q = 0; q < 8; ++q) s[j][q] = base[corner[q]];
+                // next cell: leave through the nearest face; stop past the sub-interval or the box
+                const int k = tmax[0] <= tmax[1] ? (tmax[0] <= tmax[2] ? 0 : 2) : (tmax[1] <= tmax[2] ? 1 : 2);
+                const double t_exit = fmin(tmax[0], fmin(tmax[1], tmax[2]));
+                if (!(t_exit <= tb) || --budget <= 0) {
+                    active = false;
+                } else {
+#pragma unroll
+                    for (int kk = 0; kk < 3; ++kk)   // axis by axis: a runtime index into c / tmax would put them in scratch
+                        if (kk == k) {
+                            c[kk] += step[kk];
+                            tmax[kk] = ((double)(c[kk] + (step[kk] > 0)) - r.o[kk]) * inv[kk];
+                            if (c[kk] < 0 || c[kk] >= a.n[kk]) active = false;
+                        }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kBatch; ++j)
+            if (valid[j]) intersect_cell(a, s_cases, r, s[j], cc[j][0], cc[j][1], cc[j][2], best);
+        // the lowest lane with a hit: every later lane's cells lie farther along the ray, so those lanes (and it) are done
+        const unsigned long long hit = __ballot(best.t < INFINITY);
+        if (lane == 0) s_first[wave] = hit ? wave * 64 + __builtin_ctzll(hit) : kRayThreads;
+        __syncthreads();
+        int first = kRayThreads;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) first = min(first, s_first[w]);
+        if (tid >= first) active = false;
+    }
+
+    // nearest hit: min over the wave, then over the waves (lowest lane on a tie)
+    double m = best.t;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
+    const unsigned long long at = __ballot(best.t == m);
+    if (lane == 0) {
+        s_t[wave] = m;
+        s_lane[wave] = wave * 64 + __builtin_ctzll(at);
+    }
+    __syncthreads();
+    double gm = s_t[0];
+    int winner = s_lane[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w)
+        if (s_t[w] < gm) {
+            gm = s_t[w];
+            winner = s_lane[w];
+        }
+    if (!(gm < INFINITY)) winner = 0;
+    if (tid != winner) return;
+    vtmc_ray_hit h;
+    if (best.t < INFINITY) {
+        h.distance = (float)best.t;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            h.point[k] = (float)((double)o[k] + best.t * dn[k]);
+            h.normal[k] = best.nrm[k];
+            h.block[k] = best.c[k] >> 3;
+        }
+        h.barycentric[0] = best.u;
+        h.barycentric[1] = best.v;
+        h.cell = (best.c[0] & 7) + 8 * (best.c[1] & 7) + 64 * (best.c[2] & 7);
+        h.triangle = best.tri;
+    } else {
+        h.distance = -1.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            h.point[k] = 0.f;
+            h.normal[k] = 0.f;
+            h.block[k] = -1;
+        }
+        h.barycentric[0] = h.barycentric[1] = 0.f;
+        h.cell = -1;
+        h.triangle = -1;
+    }
+    a.hits[ray] = h;
+}
+
+static hipError_t launch_raycast(const RaycastArgs &a, hipStream_t stream)
+{
+    launch_begin();
+    hipLaunchKernelGGL(raycast_kernel, dim3((unsigned)a.n_rays), dim3(kRayThreads), 0, stream, a);
+    return launch_end();
+}
+
+// the argument rules both entry points share
+static int check_rays(vtmc_ctx *ctx, int32_t n_rays, bool null_arg, float max_distance, uint32_t flags)
+{
+    if (n_rays < 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "n_rays < 0");
+    if (n_rays > 0 && null_arg) return fail(ctx, VTMC_ERR_INVALID_ARG, "null argument");
+    if (!(max_distance > 0.0f)) return fail(ctx, VTMC_ERR_INVALID_ARG, "max_distance must be positive (+inf allowed)");
+    if (flags & ~VTMC_RAY_TWO_SIDED) return fail(ctx, VTMC_ERR_INVALID_ARG, "unknown ray flags 0x%x", flags);
+    return VTMC_OK;
+}
+
+static RaycastArgs raycast_args(const vtmc_ctx *ctx, const float *grid, int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz,
+                                const float origin[3], float scale, float max_distance, uint32_t flags)
+{
+    RaycastArgs a{};
+    a.grid = grid;
+    a.sx = sx, a.sy = sy, a.sz = sz;
+    a.n[0] = nx, a.n[1] = ny, a.n[2] = nz;
+    for (int k = 0; k < 3; ++k) a.origin[k] = origin[k];
+    a.scale = scale;
+    a.max_distance = max_distance;
+    a.two_sided = (flags & VTMC_RAY_TWO_SIDED) ? 1 : 0;
+    a.vert_packed = ctx->tables.vert_packed;
+    return a;
+}
+
+}  // namespace vtmc
+
+using namespace vtmc;
+
+extern "C" {
+
+int32_t vtmc_raycast_device(vtmc_ctx *ctx, const float *d_grid, int32_t nx, int32_t ny, int32_t nz, int64_t stride_x, int64_t stride_y,
+                            int64_t stride_z, const float origin[3], float voxel_scale, const float *d_origins, const float *d_directions,
+                            int32_t n_rays, float max_distance, uint32_t flags, vtmc_ray_hit *d_hits, void *stream)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (int rc = check_rays(ctx, n_rays, !d_grid || !origin || !d_origins || !d_directions || !d_hits, max_distance, flags)) return rc;
+    if (int rc = check_dims(ctx, nx, ny, nz)) return rc;
+    if (n_rays == 0) return VTMC_OK;
+    if (!(voxel_scale > 0.0f) || !std::isfinite(voxel_scale)) return fail(ctx, VTMC_ERR_INVALID_ARG, "voxel_scale must be positive and finite");
+    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) return fail(ctx, VTMC_ERR_INVALID_ARG, "origin is not finite");
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    RaycastArgs a = raycast_args(ctx, d_grid, nx, ny, nz, stride_x, stride_y, stride_z, origin, voxel_scale, max_distance, flags);
+    a.ro = d_origins;
+    a.rd = d_directions;
+    a.hits = d_hits;
+    a.n_rays = n_rays;
+    VTMC_HIP(ctx, launch_raycast(a, stream ? (hipStream_t)stream : ctx->stream));
+    return VTMC_OK;
+}
+
+int32_t vtmc_terrain_raycast(vtmc_ctx *ctx, const float *origins, const float *directions, int32_t n_rays, float max_distance, uint32_t flags,
+                             vtmc_ray_hit *hits)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (int rc = check_rays(ctx, n_rays, !origins || !directions || !hits, max_distance, flags)) return rc;
+    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_raycast before terrain_init");
+    if (n_rays == 0) return VTMC_OK;
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    const TerrainShape &sh = ctx->tshape;
+    // device: origins | directions | hits; the pinned staging holds the same bytes
+    const size_t ray_bytes = sizeof(float) * 3 * (size_t)n_rays, hit_bytes = sizeof(vtmc_ray_hit) * (size_t)n_rays;
+    const size_t bytes = 2 * ray_bytes + hit_bytes;
+    if (int rc = ensure(ctx, ctx->rays, bytes)) return rc;
+    if (ctx->h_rays.bytes < bytes) VTMC_HIP(ctx, pin(ctx->h_rays, bytes));
+    unsigned char *h = ctx->h_rays.p, *dv = (unsigned char *)ctx->rays.p;
+    memcpy(h, origins, ray_bytes);
+    memcpy(h + ray_bytes, directions, ray_bytes);
+    VTMC_HIP(ctx, hipMemcpyAsync(dv, h, 2 * ray_bytes, hipMemcpyHostToDevice, ctx->stream));
+    RaycastArgs a = raycast_args(ctx, (const float *)ctx->terrain.p, sh.dim_x - 2, sh.dim_y - 2, sh.dim_z - 2, 1, sh.dim_x,
+                                 (int64_t)sh.dim_x * sh.dim_y, sh.origin, sh.scale, max_distance, flags);
+    a.ro = (const float *)dv;
+    a.rd = (const float *)(dv + ray_bytes);
+    a.hits = (vtmc_ray_hit *)(dv + 2 * ray_bytes);
+    a.n_rays = n_rays;
+    VTMC_HIP(ctx, launch_raycast(a, ctx->stream));
+    VTMC_HIP(ctx, hipMemcpyAsync(h + 2 * ray_bytes, dv + 2 * ray_bytes, hit_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(hits, h + 2 * ray_bytes, hit_bytes);
+    return VTMC_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // vtmc_ctx.h -- the context object behind include/vtmc.h and the small host helpers every
-// translation unit of the C-ABI layer shares (context.hip, vtmc_api.hip, terrain.hip, density.hip, chunk_io.hip, comm.hip).  Not installed.
+// translation unit of the C-ABI layer shares (context.hip, vtmc_api.hip, terrain.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip).  Not installed.
 #ifndef VTMC_CTX_H
 #define VTMC_CTX_H
 #include "../../include/vtmc.h"
@@ -101,6 +101,9 @@ struct vtmc_ctx {
     uint32_t terrain_events = 0;
     std::vector<int32_t> dirty;  // (bx,by,bz) of the last vtmc_terrain_update, ordered by block id
     bool dirty_is_all = false;   // ... or every block (the list is then materialised on demand only)
+    // raycast.hip: the rays and hits of vtmc_terrain_raycast (device, then their pinned staging)
+    VtmcDevBuf rays;
+    VtmcPinnedBuf<unsigned char> h_rays;
     uint64_t perm_seed = 0;
     bool perm_valid = false;
     // chunk_io.hip: file image being assembled / last image read

@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from ._lib import COMM_ID_BYTES, RAY_HIT_DTYPE, RAY_TWO_SIDED, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
 
 
 def _ptr(a):
@@ -292,6 +292,28 @@ class Extractor:
         sx, sy, sz = elem_strides(grid)
         self._check(self._L.vtmc_terrain_read_samples(self._h, _ptr(grid), sx, sy, sz))
         return grid
+
+    # -- ray picking: Physics.Raycast of the interactive edit (SceneManager.cs:114-131) on the device ---------------
+    def terrain_raycast(self, origins, directions, max_distance=float("inf"), two_sided=False):
+        """Nearest surface hit of each ray (world-space origins / directions, (n, 3)) on the resident terrain: a RAY_HIT_DTYPE
+        array, distance -1 and triangle -1 for a miss."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("origins and directions differ in length")
+        hits = np.zeros(len(o), RAY_HIT_DTYPE)
+        self._check(self._L.vtmc_terrain_raycast(self._h, _ptr(o), _ptr(d), len(o), max_distance,
+                                                 RAY_TWO_SIDED if two_sided else 0, _ptr(hits)))
+        return hits
+
+    def raycast_device(self, d_grid, n, strides, origin, voxel_scale, d_origins, d_directions, n_rays, d_hits,
+                       max_distance=float("inf"), two_sided=False, stream=None):
+        """vtmc_raycast_device: device addresses (int) of the grid, the rays and n_rays RAY_HIT_DTYPE records; n = (nx, ny, nz) cells,
+        element strides.  Queued on `stream`, not synchronised."""
+        org = (ctypes.c_float * 3)(*origin)
+        self._check(self._L.vtmc_raycast_device(self._h, d_grid, n[0], n[1], n[2], strides[0], strides[1], strides[2], ctypes.byref(org),
+                                                voxel_scale, d_origins, d_directions, n_rays, max_distance,
+                                                RAY_TWO_SIDED if two_sided else 0, d_hits, stream))
 
     def density_fill_device(self, params, origins, dims, strides, volume_stride, d_out, stream=None, wait=True):
         """wait=False queues the fill on `stream` without synchronising (vtmc_density_fill_device_async)."""
