@@ -63,3 +63,19 @@ def all_cases_tile():
     neg = tiles < 0
     tiles[neg] = -(0.25 + rng.random(int(neg.sum()))).astype(np.float32)
     return tiles.reshape(4, 1000)
+
+
+def all_cases_grid(order="x", seed=7):
+    """all_cases_tile() as one grid of 16 x 8 x 16 cells (2 x 1 x 2 blocks): cell (2i, 2j, 2k) holds case i + 8j + 32k, its
+    corners sampled nowhere else, for the 254 cases with triangles (0 and 255 stay empty).  Every other sample is outside, so the
+    cells in between hold the pieces of surface that join the isolated cells' triangles to nothing."""
+    g = _idx((18, 10, 18), order)
+    rng = np.random.default_rng(seed)
+    g[...] = -(0.25 + rng.random(g.shape)).astype(np.float32)   # distinct magnitudes: no gradient vanishes
+    off = [(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1)]
+    for case in range(1, 255):
+        i, j, k = case % 8, (case // 8) % 4, case // 32
+        for c, (ox, oy, oz) in enumerate(off):
+            if (case >> c) & 1:
+                g[2 * i + ox, 2 * j + oy, 2 * k + oz] = np.float32(0.25 + rng.random())
+    return g

@@ -11,7 +11,9 @@ gaps between neighbouring cells of the reference's own mesh).  A ray lying in a 
 x - y = c) runs through the cells' shared and inner edges and is ambiguous wherever it hits, so the ray sets hold few of them.  Ambiguous rays must stay under 1 % of a test's rays, and a hit
 reported for one must lie on some candidate.  Every other ray: hit / miss agree, |distance - ref| <= 2e-4 scale + 1e-6 ref, point
 within 2e-4 cells of o + distance d/|d|, unit normal within 1e-4, and (block, cell, triangle) equal whenever the next distinct
-triangle hit is more than 1e-3 cells farther.
+triangle hit is more than 1e-3 cells farther.  On top of that, every non-ambiguous ray with a reference hit is held to float32
+precision by tight_check_ray (distance within 2 ulps, normal within 3e-7, barycentrics within 4e-7 of an extended-precision
+Moller-Trumbore on the named triangle; derivation in its docstring), except grazing rays (|cos| < 1e-4), which are counted.
 """
 import ctypes
 import os
@@ -42,9 +44,14 @@ class Surface:
         self.cell = np.repeat(np.tile(np.arange(512), len(blocks)), counts)
         self.tri = np.arange(len(tris)) - starts
         self.block = np.asarray(blocks, np.int64)[tris["block"]]
-        p = np.stack([tris["p0"], tris["p1"], tris["p2"]], 1).astype(np.float64)
-        self.P = np.asarray(origin, np.float64) + (8.0 * self.block[:, None, :] + p) * float(scale)
+        self.p = np.stack([tris["p0"], tris["p1"], tris["p2"]], 1)   # float32, block-local
+        self.case = np.repeat(cases.ravel(), counts)
+        self.origin = np.asarray(origin, np.float64)
+        self.P = self.origin + (8.0 * self.block[:, None, :] + self.p.astype(np.float64)) * float(scale)
         self.scale = float(scale)
+        code = self._code(self.block, self.cell, self.tri)
+        self._by_code = np.argsort(code, kind="stable")
+        self._codes = code[self._by_code]
         n = np.cross(self.P[:, 1] - self.P[:, 0], self.P[:, 2] - self.P[:, 0])
         nn = np.linalg.norm(n, axis=1)
         self.ok = np.isfinite(nn) & (nn > 0)                      # zero-area triangles are never hit
@@ -55,6 +62,19 @@ class Surface:
         self.bounds = np.searchsorted(inv.ravel()[self.order], np.arange(len(ub) + 1))
         self.lo = np.asarray(origin, np.float64) + 8.0 * ub * scale - 1e-6
         self.hi = self.lo + 8.0 * scale + 2e-6
+
+    @staticmethod
+    def _code(block, cell, tri):
+        b = np.asarray(block, np.int64).reshape(-1, 3)
+        return ((b[:, 2] * 4096 + b[:, 1]) * 4096 + b[:, 0]) * 2560 + np.asarray(cell, np.int64) * 5 + np.asarray(tri, np.int64)
+
+    def lookup(self, block, cell, tri):
+        """Index of the triangle (block, cell, tri) of the canonical order, or -1 when the surface has no such triangle."""
+        if min(*block, cell, tri) < 0 or cell >= 512 or tri >= 5:
+            return -1
+        c = self._code(block, cell, tri)[0]
+        i = np.searchsorted(self._codes, c)
+        return int(self._by_code[i]) if i < len(self._codes) and self._codes[i] == c else -1
 
     @classmethod
     def of_grid(cls, oracle_mod, grid, origin=(0.0, 0.0, 0.0), scale=1.0):
@@ -96,10 +116,10 @@ class Surface:
 
 
 def reference(surf, origins, directions, max_distance=np.inf, two_sided=False):
-    """Per ray: dict(hit, t, point, normal, key, gap, ambiguous, trace)."""
+    """Per ray: dict(hit, t, point, normal, key, gap, ambiguous, trace, ray); ray = (origin, direction) as given, in float64."""
     out = []
     for o, d in zip(np.asarray(origins, np.float64), np.asarray(directions, np.float64)):
-        r = dict(hit=False, t=np.inf, ambiguous=False, trace=None)
+        r = dict(hit=False, t=np.inf, ambiguous=False, trace=None, ray=(o, d))
         n = np.linalg.norm(d)
         if not (np.all(np.isfinite(o)) and np.all(np.isfinite(d)) and n > 0):
             out.append(r)
@@ -148,6 +168,108 @@ def compare(hits, ref, scale, label):
         if r["gap"] > 1e-3:
             assert (tuple(h["block"]), int(h["cell"]), int(h["triangle"])) == r["key"], (label, i, h, r["key"])
     return n_amb
+
+
+GRAZE_COS = 1e-4        # |cos(ray, face normal)| below this: a grazing ray, held to compare()'s bounds only
+
+
+def exact_triangle(surf, j, o, d):
+    """Moller-Trumbore for triangle j of the surface in extended precision (np.longdouble) on its grid-unit vertices 8b + p, which
+    hold the record's float32 positions exactly; o, d: the ray as given (world, d of any length).  Where np.longdouble is only
+    float64 the bounds of tight_check_ray still hold: they budget float64 error on both sides."""
+    L = np.longdouble
+    P = 8 * surf.block[j].astype(L)[None, :] + surf.p[j].astype(L)
+    og = (np.asarray(o, L) - surf.origin.astype(L)) / L(surf.scale)
+    D = np.asarray(d, L)
+    dn = D / np.sqrt((D * D).sum())
+    e1, e2 = P[1] - P[0], P[2] - P[0]
+    n = np.cross(e1, e2)
+    nn = np.sqrt((n * n).sum())
+    pv = np.cross(dn, e2)
+    det = (e1 * pv).sum()
+    tv = og - P[0]
+    q = np.cross(tv, e1)
+    edges = [np.sqrt((e * e).sum()) for e in (e1, e2, e2 - e1)]
+    return dict(t=float((e2 * q).sum() / det * L(surf.scale)), u=float((tv * pv).sum() / det), v=float((dn * q).sum() / det),
+                unit=(n / nn).astype(np.float64), cos=float(abs((n * dn).sum()) / nn), dn=dn.astype(np.float64),
+                R=float(max(np.abs(og).max(), np.abs(P).max())) + 1.0, e1=float(edges[0]), e2=float(edges[1]),
+                emax=float(max(edges)), nn=float(nn))
+
+
+def _ulp(x):
+    return float(np.spacing(np.float32(abs(x))))
+
+
+def tight_check_ray(h, r, surf):
+    """The float32-precision agreement rule for one non-ambiguous ray with a reference hit; returns the triangle's |cos| with the
+    ray.  Raises AssertionError on any disagreement.  Grazing rays (|cos| < GRAZE_COS) are only checked for the key.
+
+    The hit's (block, cell, triangle) must name a triangle of the oracle's surface that the reference ray hits.  The expected values
+    come from exact_triangle() on that record (extended precision, the float32 vertices exact), so the bounds are those of the
+    kernel's own float64 arithmetic plus the final rounding to float32:
+      * distance: |distance - float32(t_ref)| <= 2 ulp + floor, and the named triangle's own t within floor of t_ref (it is the
+        nearest).  floor = 2^-45 (R scale + R_w) (1 + e^2/|n|) / |cos|: the kernel's float64 watertight test on grid units and the
+        reference's float64 Moller-Trumbore on world units each move their vertices by a few eps64 * R (R: the largest coordinate
+        of ray origin and vertices, grid units; R_w the same in world units), which moves the plane's t by that over |cos|, and
+        the barycentric weights by eps64 R e / (|n| |cos|) (e: the longest edge, |n| = |cross(e1, e2)|), whose error reaches t
+        through the triangle's extent e; 2^-45 = 128 eps64 covers the few dozen roundings of either test.
+      * normal: each component within 3e-7 (float32 rounding of a unit vector is 3e-8) + 2^-48 |e1| |e2| / |n| (the float64
+        cross product's cancellation) of float32(unit(cross(p1 - p0, p2 - p0))).
+      * barycentric: u, v within 4e-7 + 2^-45 R e / (|n| |cos|) of the extended-precision Moller-Trumbore (u, v), and
+        (1-u-v) p0 + u p1 + v p2 within 2 ulp(|point|) + that bound times (|e1| + |e2|) scale of point.
+      * point: within 2 ulp(|point|) + ulp(distance) + floor of o + distance d/|d| per component.
+    """
+    key = (tuple(int(x) for x in h["block"]), int(h["cell"]), int(h["triangle"]))
+    j = surf.lookup(*key)
+    assert j >= 0, ("the hit names no triangle of the surface", key)
+    (idx, t, _, _, _, hit, _), _, _ = r["trace"]
+    assert hit[idx == j].any(), ("the hit names a triangle the reference ray does not hit", key, r["key"])
+    o, d = r["ray"]
+    x = exact_triangle(surf, j, o, d)
+    if x["cos"] < GRAZE_COS:
+        return x["cos"]
+    scale = surf.scale
+    R_w = max(np.abs(o).max(), np.abs(surf.P[j]).max()) + scale
+    floor = 2.0 ** -45 * (x["R"] * scale + R_w) * (1.0 + x["emax"] ** 2 / x["nn"]) / x["cos"]
+    dist, t_ref = float(h["distance"]), float(r["t"])
+    t32 = float(np.float32(t_ref))
+    assert abs(dist - t32) <= 2 * _ulp(t32) + floor, ("distance", dist, t32, (dist - t32) / _ulp(t32), floor)
+    assert abs(x["t"] - t_ref) <= floor, ("the named triangle is not the nearest", x["t"], t_ref, floor)
+    tol_n = 3e-7 + 2.0 ** -48 * x["e1"] * x["e2"] / x["nn"]
+    want_n = x["unit"].astype(np.float32).astype(np.float64)
+    assert np.abs(h["normal"].astype(np.float64) - want_n).max() <= tol_n, ("normal", h["normal"], want_n, tol_n)
+    u, v = (float(c) for c in h["barycentric"])
+    tol_uv = 4e-7 + 2.0 ** -45 * x["R"] * x["emax"] / (x["nn"] * x["cos"])
+    assert abs(u - x["u"]) <= tol_uv and abs(v - x["v"]) <= tol_uv, ("barycentric", (u, v), (x["u"], x["v"]), tol_uv)
+    point = h["point"].astype(np.float64)
+    pmax = float(np.abs(point).max())
+    W = surf.P[j]
+    rec = (1.0 - u - v) * W[0] + u * W[1] + v * W[2]
+    tol_r = 2 * _ulp(pmax) + tol_uv * (x["e1"] + x["e2"]) * scale + floor
+    assert np.abs(rec - point).max() <= tol_r, ("barycentric does not land on point", rec, point, tol_r)
+    want_p = np.asarray(o, np.float64) + dist * x["dn"]
+    assert np.abs(point - want_p).max() <= 2 * _ulp(pmax) + _ulp(dist) + floor, ("point", point, want_p)
+    return x["cos"]
+
+
+def check_tight(hits, ref, surf, label):
+    """tight_check_ray on every non-ambiguous ray with a reference hit (compare() has already matched hit / miss); returns
+    (rays checked, grazing rays among them)."""
+    n_chk = n_graze = 0
+    for i, (h, r) in enumerate(zip(hits, ref)):
+        if r["ambiguous"] or not r["hit"]:
+            continue
+        try:
+            cos = tight_check_ray(h, r, surf)
+        except AssertionError as e:
+            raise AssertionError((label, i, h, r["key"], r["t"]) + tuple(e.args)) from None
+        n_chk += 1
+        n_graze += cos < GRAZE_COS
+    return n_chk, n_graze
+
+
+def report(label, n_rays, n_amb, tight):
+    print("raycast %s: %d rays, %d ambiguous, %d tight-checked, %d grazing" % (label, n_rays, n_amb, tight[0], tight[1]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -327,7 +449,9 @@ def test_perlin64_device_rays_both_layouts(oracle_mod):
             assert hx.tobytes() == hz.tobytes(), "x-fastest and z-fastest grids give different hits"
             surf = Surface.of_grid(oracle_mod, grid, origin, scale)
             ref = reference(surf, o, D, two_sided=two_sided)
-            n_amb = compare(hx, ref, scale, "scale %g two_sided %d" % (scale, two_sided))
+            label = "scale %g two_sided %d" % (scale, two_sided)
+            n_amb = compare(hx, ref, scale, label)
+            report("perlin64 " + label, len(o), n_amb, check_tight(hx, ref, surf, label))
             assert n_amb < 0.01 * len(o), n_amb
             assert (hx["triangle"] >= 0).sum() > len(o) // 3
 
@@ -372,6 +496,7 @@ def test_demo_world_terrain_raycast_follows_the_edits(oracle_mod):
             surf = Surface.of_grid(oracle_mod, ex.terrain_read_samples())
             ref = reference(surf, O, D)
             n_amb = compare(hits, ref, 1.0, "demo world")
+            report("demo world", k, n_amb, check_tight(hits, ref, surf, "demo world"))
             assert n_amb < 0.01 * k, n_amb
             assert (hits["triangle"] >= 0).sum() > k // 2
             if mods is first:
@@ -380,9 +505,10 @@ def test_demo_world_terrain_raycast_follows_the_edits(oracle_mod):
 
 
 @pytest.mark.gpu
-def test_edge_cases():
+def test_edge_cases(oracle_mod):
     """Zero rays, degenerate rays, max_distance, a ray that misses the box, argument errors, and a field with NaN samples: no NaN
-    in any hit, and rays that touch no NaN cell answer exactly as on the NaN-free field."""
+    in any hit, and rays that touch no NaN cell answer exactly as on the NaN-free field, whose hits pass the tight check (0 of the
+    2048 rays ambiguous, measured with the reference alone)."""
     import torch
     import volumetricterrain_amd as vt
     n = (32, 32, 32)
@@ -434,6 +560,11 @@ def test_edge_cases():
         O = rng.uniform(-10, 42, (2048, 3)).astype(np.float32)
         D = (rng.uniform(2, 30, (2048, 3)) - O).astype(np.float32)
         base = _cast(ex, d_g.data_ptr(), n, st, (0, 0, 0), 1.0, O, D)
+        surf = Surface.of_grid(oracle_mod, g)
+        ref = reference(surf, O, D)
+        n_amb = compare(base, ref, 1.0, "sphere")
+        report("sphere", len(O), n_amb, check_tight(base, ref, surf, "sphere"))
+        assert n_amb < 0.01 * len(O), n_amb
         gn = g.copy()
         gn[10:15, 18:24, 12:17] = np.nan
         gn[20, 5, 9] = np.nan
@@ -487,7 +618,7 @@ def test_long_rays_on_a_1024_grid(oracle_mod):
         hits = _cast(ex, g.data_ptr(), (n, n, n), (1, dim, dim * dim), (0, 0, 0), 1.0, O, D)
         off = torch.tensor((np.arange(10)[None, None, :] + dim * np.arange(10)[None, :, None] + dim * dim * np.arange(10)[:, None, None]).ravel(),
                            dtype=torch.int64, device="cuda")   # tile[ix + 10 iy + 100 iz]
-        n_amb = 0
+        n_amb, tight = 0, [0, 0]
         for grp in range(4):
             sel = np.arange(grp, len(O), 4)
             blocks = set()
@@ -510,6 +641,8 @@ def test_long_rays_on_a_1024_grid(oracle_mod):
             surf = Surface(oracle_mod, tris, blocks, cases)
             ref = reference(surf, O[sel], D[sel])
             n_amb += compare(hits[sel], ref, 1.0, "1024^3 group %d" % grp)
+            tight = [a + b for a, b in zip(tight, check_tight(hits[sel], ref, surf, "1024^3 group %d" % grp))]
             del tiles
+        report("1024^3 long rays", len(O), n_amb, tight)
         assert n_amb < 0.01 * len(O), n_amb
         assert (hits["triangle"] >= 0).sum() > 128
