@@ -325,6 +325,24 @@ int32_t vtmc_terrain_read_samples(vtmc_ctx *ctx, float *dst, int64_t stride_x, i
 /* Device pointer + element strides of the grid (x fastest), for GPU-resident callers. */
 int32_t vtmc_terrain_device_grid(vtmc_ctx *ctx, const float **d_samples, int64_t strides[3], int32_t dims[3]);
 
+/* Undo / redo of terrain edits (off by default; not in the reference).  vtmc_terrain_set_history(ctx, max_bytes) allocates a device
+ * journal of max_bytes and clears the history; 0 turns history off and frees it.  While history is on, a vtmc_terrain_update that
+ * writes at least one sample records one step: per modifier, the samples of its clamped sample box as they were before (4 bytes per
+ * sample, each box rounded up to 256 bytes) and the bounds its dirty blocks were found from.  A call that writes no sample (an empty
+ * queue, modifiers wholly outside the grid) records nothing and keeps both stacks.  A step discards every undone step; the oldest
+ * steps are dropped until it fits (steps of equal size S: floor(max_bytes / S) are kept; the journal is a ring).  A step larger than
+ * max_bytes, or an update that fails after writing, clears the history.  vtmc_terrain_init clears it and keeps the budget.
+ *
+ * vtmc_terrain_undo restores the newest step's boxes bit for bit in reverse modifier order, vtmc_terrain_redo puts the newest undone
+ * step's values back in modifier order (no modifier is evaluated again); each then extracts that step's dirty set as its update did,
+ * and returns, lists (vtmc_terrain_dirty_blocks) and leaves for the read_* / raycast calls exactly what vtmc_terrain_update does.
+ * Neither changes the event counter the clamp draws of later updates hash.  VTMC_ERR_NO_RESULT when there is nothing to undo / redo,
+ * with nothing changed.  vtmc_terrain_history reports the steps that can be undone / redone and the journal bytes they hold. */
+int32_t vtmc_terrain_set_history(vtmc_ctx *ctx, int64_t max_bytes);
+int32_t vtmc_terrain_undo(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_count);
+int32_t vtmc_terrain_redo(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_count);
+int32_t vtmc_terrain_history(const vtmc_ctx *ctx, int32_t *n_undo, int32_t *n_redo, int64_t *bytes_used);
+
 /* ------------------------------------------------------------------------------------------
  * Ray picking -- replaces the Physics.Raycast of the interactive edit (SceneManager.cs:114-131)
  * against the MeshColliders that BatchUpdate cooks from the extracted mesh (VoxelTerrain.cs:448-465),

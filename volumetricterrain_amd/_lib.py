@@ -43,6 +43,7 @@ SYMBOLS = [
     "vtmc_copy_to_host", "vtmc_chunk_write", "vtmc_chunk_read",
     "vtmc_extract_volumes_device_async", "vtmc_extract_finish", "vtmc_last_fill_ms", "vtmc_context_stream", "vtmc_release_streams", "vtmc_last_placement",
     "vtmc_terrain_raycast", "vtmc_raycast_device",
+    "vtmc_terrain_set_history", "vtmc_terrain_undo", "vtmc_terrain_redo", "vtmc_terrain_history",
 ]
 COMM_ID_BYTES = 128
 
@@ -146,6 +147,11 @@ def load(path=None):
     L.vtmc_terrain_dirty_blocks.argtypes = [vp, vp, i32, P(i32)]
     L.vtmc_terrain_read_samples.argtypes = [vp, vp, i64, i64, i64]
     L.vtmc_terrain_device_grid.argtypes = [vp, P(vp), P(i64 * 3), P(i32 * 3)]
+    if not explicit or hasattr(L, "vtmc_terrain_set_history"):
+        L.vtmc_terrain_set_history.argtypes = [vp, i64]
+        L.vtmc_terrain_undo.argtypes = [vp, P(i32), P(i32)]
+        L.vtmc_terrain_redo.argtypes = [vp, P(i32), P(i32)]
+        L.vtmc_terrain_history.argtypes = [vp, P(i32), P(i32), P(i64)]
     if not explicit or hasattr(L, "vtmc_terrain_raycast"):
         L.vtmc_terrain_raycast.argtypes = [vp, vp, vp, i32, ctypes.c_float, u32, vp]
         L.vtmc_raycast_device.argtypes = [vp, vp, i32, i32, i32, i64, i64, i64, P(ctypes.c_float * 3), ctypes.c_float,

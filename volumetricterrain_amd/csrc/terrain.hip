@@ -140,6 +140,65 @@ __global__ __launch_bounds__(256) void terrain_modify_kernel(float *__restrict__
     }
 }
 
+// terrain_modify_kernel with the edit journal: the sample it replaces also goes to image[ix + dx*(iy + dy*iz)], the modifier's box x
+// fastest, so a wave stores 256 contiguous bytes beside the row it reads and writes (12 bytes per touched sample instead of 8).  The
+// body repeats terrain_modify_kernel's line for line; that kernel stays as it is so history off runs exactly the code it ran before.
+__global__ __launch_bounds__(256) void terrain_modify_journal_kernel(float *__restrict__ grid, float *__restrict__ image, TerrainShape sh,
+                                                                     TerrainModifierArgs m)
+{
+    const int ix = blockIdx.x * 64 + threadIdx.x, iz = blockIdx.y * 4 + threadIdx.y, iy0 = blockIdx.z * kYRun;
+    if (ix >= m.dx || iz >= m.dz) return;
+    const int x = m.lx + ix, z = m.lz + iz;
+    const float px = (float)x * sh.scale + sh.origin[0];
+    const float pz = (float)z * sh.scale + sh.origin[2];
+    const float col = column_term(m, px, pz);
+    const int iy1 = iy0 + kYRun < m.dy ? iy0 + kYRun : m.dy;
+    const uint64_t row = (uint64_t)ix + (uint64_t)m.dx * (uint64_t)m.dy * (uint64_t)iz;  // image index of (ix, 0, iz); a box reaches 4.3 GB
+    for (int iy = iy0; iy < iy1; ++iy) {
+        const int y = m.ly + iy;
+        const float py = (float)y * sh.scale + sh.origin[1];
+        const uint64_t sample = (uint64_t)x + (uint64_t)sh.dim_x * ((uint64_t)y + (uint64_t)sh.dim_y * (uint64_t)z);
+        const float q = m.kind == 3 ? col - py : query_density(m, px, py, pz);
+        const float md = clamp_drawn(q, sh.seed, m.event, sample, 0u);
+        const float s = grid[sample];
+        image[row + (uint64_t)m.dx * (uint64_t)iy] = s;
+        float r;
+        if (m.add_or_erode) {
+            r = s > md ? s : md;
+        } else {
+            const float minus_md = -md;
+            r = clamp_drawn(s < minus_md ? s : minus_md, sh.seed, m.event, sample, 2u);
+        }
+        grid[sample] = r;
+    }
+}
+
+// Undo / redo of one box: grid box <-> its journal image, 32-bit copies (NaN payloads and -0 survive), 16 bytes per sample.  Same
+// launch shape and image order as terrain_modify_journal_kernel.
+__global__ __launch_bounds__(256) void terrain_swap_kernel(uint32_t *__restrict__ grid, uint32_t *__restrict__ image, TerrainShape sh, TerrainBox b)
+{
+    const int ix = blockIdx.x * 64 + threadIdx.x, iz = blockIdx.y * 4 + threadIdx.y, iy0 = blockIdx.z * kYRun;
+    if (ix >= b.dx || iz >= b.dz) return;
+    const uint64_t x = (uint64_t)(b.lx + ix), z = (uint64_t)(b.lz + iz);
+    const int iy1 = iy0 + kYRun < b.dy ? iy0 + kYRun : b.dy;
+    const uint64_t row = (uint64_t)ix + (uint64_t)b.dx * (uint64_t)b.dy * (uint64_t)iz;
+    const uint64_t s0 = x + (uint64_t)sh.dim_x * ((uint64_t)(b.ly + iy0) + (uint64_t)sh.dim_y * z), j0 = row + (uint64_t)b.dx * (uint64_t)iy0;
+    // every load of the run is issued before the first store: 2 * kYRun loads in flight per lane, not 2
+    uint32_t g[kYRun], h[kYRun];
+#pragma unroll
+    for (int k = 0; k < kYRun; ++k)
+        if (iy0 + k < iy1) {
+            g[k] = grid[s0 + (uint64_t)sh.dim_x * k];
+            h[k] = image[j0 + (uint64_t)b.dx * k];
+        }
+#pragma unroll
+    for (int k = 0; k < kYRun; ++k)
+        if (iy0 + k < iy1) {
+            grid[s0 + (uint64_t)sh.dim_x * k] = h[k];
+            image[j0 + (uint64_t)b.dx * k] = g[k];
+        }
+}
+
 hipError_t launch_terrain_fill(float *grid, long long n, uint64_t seed, int n_cus, hipStream_t stream)
 {
     long long wgs = (n + 255) / 256;
@@ -157,6 +216,25 @@ hipError_t launch_terrain_modify(float *grid, const TerrainShape &sh, const Terr
     launch_begin();
     hipLaunchKernelGGL(terrain_modify_kernel, dim3((unsigned)((m.dx + 63) / 64), (unsigned)((m.dz + 3) / 4), (unsigned)((m.dy + kYRun - 1) / kYRun)),
                        dim3(64, 4, 1), 0, stream, grid, sh, m);
+    return launch_end();
+}
+
+static dim3 box_grid(const TerrainBox &b) { return dim3((unsigned)((b.dx + 63) / 64), (unsigned)((b.dz + 3) / 4), (unsigned)((b.dy + kYRun - 1) / kYRun)); }
+
+static hipError_t launch_terrain_modify_journal(float *grid, float *image, const TerrainShape &sh, const TerrainModifierArgs &m, hipStream_t stream)
+{
+    const TerrainBox b{m.lx, m.ly, m.lz, m.dx, m.dy, m.dz};
+    if ((m.dz + 3) / 4 > 65535 || (m.dy + kYRun - 1) / kYRun > 65535) return hipErrorInvalidValue;
+    launch_begin();
+    hipLaunchKernelGGL(terrain_modify_journal_kernel, box_grid(b), dim3(64, 4, 1), 0, stream, grid, image, sh, m);
+    return launch_end();
+}
+
+static hipError_t launch_terrain_swap(float *grid, float *image, const TerrainShape &sh, const TerrainBox &b, hipStream_t stream)
+{
+    if ((b.dz + 3) / 4 > 65535 || (b.dy + kYRun - 1) / kYRun > 65535) return hipErrorInvalidValue;
+    launch_begin();
+    hipLaunchKernelGGL(terrain_swap_kernel, box_grid(b), dim3(64, 4, 1), 0, stream, (uint32_t *)grid, (uint32_t *)image, sh, b);
     return launch_end();
 }
 
@@ -225,6 +303,110 @@ static size_t mark_dirty_blocks(const int low[3], const int up[3], const std::ar
     return n_new;
 }
 
+static int check_modifier(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i)
+{
+    if (md.kind < VTMC_MOD_PLANE || md.kind > VTMC_MOD_HEIGHTMAP) return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: unknown kind %d", i, md.kind);
+    if (md.kind == VTMC_MOD_HEIGHTMAP && (!md.data || md.data_dims[0] < 1 || md.data_dims[1] < 1))
+        return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: heightmap data / dims missing", i);
+    return VTMC_OK;
+}
+
+// _nextUpdateblocks (VoxelTerrain.cs:321) from the marks, ordered by block id (a full rebuild needs no list), then BatchUpdate
+// (VoxelTerrain.cs:322-323) on the resident grid
+static int extract_dirty(vtmc_ctx *ctx, const std::vector<uint8_t> &mark, size_t n_marked, int32_t *n_dirty_blocks, int32_t *tri_count)
+{
+    const TerrainShape &sh = ctx->tshape;
+    const auto nb = block_counts(sh);
+    ctx->dirty.clear();
+    ctx->dirty_is_all = n_marked == mark.size();
+    if (!ctx->dirty_is_all) {
+        ctx->dirty.reserve(n_marked * 3);
+        size_t id = 0;
+        for_each_block(nb, [&](int bx, int by, int bz) {
+            if (mark[id++]) ctx->dirty.insert(ctx->dirty.end(), {bx, by, bz});
+        });
+    }
+    if (n_dirty_blocks) *n_dirty_blocks = (int32_t)n_marked;
+    BlockSpace sp = dense_space((const float *)ctx->terrain.p, sh.dim_x - 2, sh.dim_y - 2, sh.dim_z - 2, 1, sh.dim_x, (int64_t)sh.dim_x * sh.dim_y, 1, 0);
+    int n_volumes = 1;
+    if (!ctx->dirty_is_all) {  // a proper subset: device block list; every block: the dense streaming path
+        if (int rc = upload_block_list(ctx, ctx->dirty.data(), (int)n_marked, sp)) return rc;
+        n_volumes = 0;
+    }
+    return extract_core(ctx, sp, n_volumes, tri_count);
+}
+
+static void history_clear(vtmc_ctx *ctx)
+{
+    ctx->hist.clear();
+    ctx->hist_done = 0;
+}
+
+static bool box_empty(const TerrainBox &b) { return b.dx <= 0 || b.dy <= 0 || b.dz <= 0; }
+
+// journal bytes of a box image: 4 per sample, rounded up to 256
+static size_t image_bytes(const TerrainBox &b) { return box_empty(b) ? 0 : ((size_t)4 * b.dx * b.dy * b.dz + 255) / 256 * 256; }
+
+// Places the step of a (validated) queue in the arena before anything is written: the boxes and dirty-rule bounds of every modifier,
+// back to back.  A step that writes no sample comes back empty and changes nothing; one larger than the arena comes back empty and
+// clears the history.  Otherwise every undone step is dropped, and then the oldest steps until the step's range of the ring is free.
+static VtmcHistoryStep plan_step(vtmc_ctx *ctx, const vtmc_modifier *mods, int32_t n_mods)
+{
+    VtmcHistoryStep st;
+    st.boxes.resize((size_t)n_mods);
+    for (int32_t i = 0; i < n_mods; ++i) {
+        VtmcHistoryBox &hb = st.boxes[i];
+        const TerrainModifierArgs a = sample_range(ctx->tshape, mods[i], hb.low, hb.up);
+        hb.box = TerrainBox{a.lx, a.ly, a.lz, a.dx, a.dy, a.dz};
+        hb.off = st.bytes;
+        st.bytes += image_bytes(hb.box);
+    }
+    const size_t cap = ctx->journal.bytes;
+    if (st.bytes == 0 || st.bytes > cap) {
+        if (st.bytes) history_clear(ctx);
+        st.boxes.clear();
+        return st;
+    }
+    ctx->hist.resize(ctx->hist_done);  // a new step discards redo
+    const size_t head = ctx->hist.empty() ? 0 : ctx->hist.back().off + ctx->hist.back().bytes;
+    st.off = head + st.bytes <= cap ? head : 0;
+    if (st.off == 0)  // wrapped: the steps between head and the arena's end are the oldest ones, and the ring wraps only once
+        while (!ctx->hist.empty() && ctx->hist.front().off >= head) ctx->hist.pop_front();
+    while (!ctx->hist.empty() && ctx->hist.front().off < st.off + st.bytes && st.off < ctx->hist.front().off + ctx->hist.front().bytes)
+        ctx->hist.pop_front();
+    ctx->hist_done = ctx->hist.size();
+    for (VtmcHistoryBox &hb : st.boxes) hb.off += st.off;
+    return st;
+}
+
+// vtmc_terrain_undo / _redo: swaps the step's boxes with their images (undo newest-first in reverse queue order, redo in queue order),
+// then extracts the step's dirty set as its update did
+static int32_t history_step(vtmc_ctx *ctx, bool undo, int32_t *n_dirty_blocks, int32_t *tri_count)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_%s before terrain_init", undo ? "undo" : "redo");
+    if (undo ? ctx->hist_done == 0 : ctx->hist_done == ctx->hist.size())
+        return fail(ctx, VTMC_ERR_NO_RESULT, "nothing to %s", undo ? "undo" : "redo");
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t k = undo ? ctx->hist_done - 1 : ctx->hist_done;
+    const VtmcHistoryStep &st = ctx->hist[k];
+    const auto nb = block_counts(ctx->tshape);
+    std::vector<uint8_t> mark((size_t)nb[0] * nb[1] * nb[2], 0);
+    size_t n_marked = 0;
+    const size_t n = st.boxes.size();
+    for (size_t i = 0; i < n; ++i) {
+        const VtmcHistoryBox &hb = st.boxes[undo ? n - 1 - i : i];
+        if (!box_empty(hb.box))
+            if (hipError_t e = launch_terrain_swap((float *)ctx->terrain.p, (float *)((char *)ctx->journal.p + hb.off), ctx->tshape, hb.box, ctx->stream)) {
+                history_clear(ctx);  // some boxes swapped, some not: no image is what its step says any more
+                VTMC_HIP(ctx, e);
+            }
+        if (n_marked < mark.size()) n_marked += mark_dirty_blocks(hb.low, hb.up, nb, mark);
+    }
+    ctx->hist_done = undo ? k : k + 1;
+    return extract_dirty(ctx, mark, n_marked, n_dirty_blocks, tri_count);
+}
+
 }  // namespace vtmc
 
 using namespace vtmc;
@@ -244,6 +426,7 @@ int32_t vtmc_terrain_init(vtmc_ctx *ctx, int32_t width, int32_t elevation, int32
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     ctx->has_terrain = false;
     ctx->has_result = false;
+    history_clear(ctx);
     TerrainShape sh{};
     sh.dim_x = width + 2;
     sh.dim_y = elevation + 2;
@@ -273,11 +456,25 @@ int32_t vtmc_terrain_update(vtmc_ctx *ctx, const vtmc_modifier *mods, int32_t n_
     const auto nb = block_counts(sh);
     std::vector<uint8_t> mark((size_t)nb[0] * nb[1] * nb[2], 0);
     size_t n_marked = 0;
+    // history on: the whole queue is checked and its step placed before the first write (history off: a bad modifier fails where it stands)
+    VtmcHistoryStep step;
+    if (ctx->journal.p) {
+        for (int32_t i = 0; i < n_mods; ++i)
+            if (int rc = check_modifier(ctx, mods[i], i)) return rc;
+        step = plan_step(ctx, mods, n_mods);
+    }
+    const bool journaled = !step.boxes.empty();
+    struct ClearOnFailure {   // an update that fails after its first write leaves no image its step would claim
+        vtmc_ctx *ctx;
+        bool armed;
+        ~ClearOnFailure()
+        {
+            if (armed) history_clear(ctx);
+        }
+    } guard{ctx, journaled};
     for (int32_t i = 0; i < n_mods; ++i) {
         const vtmc_modifier &md = mods[i];
-        if (md.kind < VTMC_MOD_PLANE || md.kind > VTMC_MOD_HEIGHTMAP) return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: unknown kind %d", i, md.kind);
-        if (md.kind == VTMC_MOD_HEIGHTMAP && (!md.data || md.data_dims[0] < 1 || md.data_dims[1] < 1))
-            return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: heightmap data / dims missing", i);
+        if (int rc = check_modifier(ctx, md, i)) return rc;
         int low[3], up[3];
         TerrainModifierArgs a = sample_range(sh, md, low, up);
         a.event = ++ctx->terrain_events;
@@ -292,28 +489,56 @@ int32_t vtmc_terrain_update(vtmc_ctx *ctx, const vtmc_modifier *mods, int32_t n_
             a.dims0 = md.data_dims[0];
             a.dims1 = md.data_dims[1];
         }
-        if (a.dx > 0 && a.dy > 0 && a.dz > 0) VTMC_HIP(ctx, launch_terrain_modify((float *)ctx->terrain.p, sh, a, ctx->stream));
+        if (a.dx > 0 && a.dy > 0 && a.dz > 0) {
+            if (journaled)
+                VTMC_HIP(ctx, launch_terrain_modify_journal((float *)ctx->terrain.p, (float *)((char *)ctx->journal.p + step.boxes[i].off), sh, a, ctx->stream));
+            else
+                VTMC_HIP(ctx, launch_terrain_modify((float *)ctx->terrain.p, sh, a, ctx->stream));
+        }
         if (n_marked < mark.size()) n_marked += mark_dirty_blocks(low, up, nb, mark);
     }
-    // _nextUpdateblocks (VoxelTerrain.cs:321), ordered by block id; a full rebuild needs no list
-    ctx->dirty.clear();
-    ctx->dirty_is_all = n_marked == mark.size();
-    if (!ctx->dirty_is_all) {
-        ctx->dirty.reserve(n_marked * 3);
-        size_t id = 0;
-        for_each_block(nb, [&](int bx, int by, int bz) {
-            if (mark[id++]) ctx->dirty.insert(ctx->dirty.end(), {bx, by, bz});
-        });
+    if (journaled) {
+        ctx->hist.push_back(std::move(step));
+        ctx->hist_done = ctx->hist.size();
     }
-    if (n_dirty_blocks) *n_dirty_blocks = (int32_t)n_marked;
-    // BatchUpdate (VoxelTerrain.cs:322-323: only when the set is not empty) on the resident grid
-    BlockSpace sp = dense_space((const float *)ctx->terrain.p, sh.dim_x - 2, sh.dim_y - 2, sh.dim_z - 2, 1, sh.dim_x, (int64_t)sh.dim_x * sh.dim_y, 1, 0);
-    int n_volumes = 1;
-    if (!ctx->dirty_is_all) {  // a proper subset: device block list; every block: the dense streaming path
-        if (int rc = upload_block_list(ctx, ctx->dirty.data(), (int)n_marked, sp)) return rc;
-        n_volumes = 0;
+    const int rc = extract_dirty(ctx, mark, n_marked, n_dirty_blocks, tri_count);
+    guard.armed = rc != VTMC_OK && journaled;
+    return rc;
+}
+
+int32_t vtmc_terrain_set_history(vtmc_ctx *ctx, int64_t max_bytes)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (max_bytes < 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "max_bytes < 0");
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    history_clear(ctx);
+    // the only place the arena is allocated or freed: hipMalloc / hipFree synchronise, an update or undo must not
+    if (ctx->journal.bytes != (size_t)max_bytes) {
+        VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));   // a journaled write or a swap may still be using the old arena
+        ctx->journal.release();
+        if (max_bytes > 0) {
+            VTMC_HIP(ctx, hipMalloc(&ctx->journal.p, (size_t)max_bytes));
+            ctx->journal.bytes = (size_t)max_bytes;
+        }
     }
-    return extract_core(ctx, sp, n_volumes, tri_count);
+    return VTMC_OK;
+}
+
+int32_t vtmc_terrain_undo(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_count) { return history_step(ctx, true, n_dirty_blocks, tri_count); }
+
+int32_t vtmc_terrain_redo(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_count) { return history_step(ctx, false, n_dirty_blocks, tri_count); }
+
+int32_t vtmc_terrain_history(const vtmc_ctx *ctx, int32_t *n_undo, int32_t *n_redo, int64_t *bytes_used)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (n_undo) *n_undo = (int32_t)ctx->hist_done;
+    if (n_redo) *n_redo = (int32_t)(ctx->hist.size() - ctx->hist_done);
+    if (bytes_used) {
+        int64_t b = 0;
+        for (const VtmcHistoryStep &st : ctx->hist) b += (int64_t)st.bytes;
+        *bytes_used = b;
+    }
+    return VTMC_OK;
 }
 
 int32_t vtmc_terrain_dirty_blocks(vtmc_ctx *ctx, int32_t *dst, int32_t capacity_blocks, int32_t *n_blocks)

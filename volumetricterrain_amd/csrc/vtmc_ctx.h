@@ -5,11 +5,16 @@
 #include "../../include/vtmc.h"
 #include "vtmc_internal.h"
 
+#include <deque>
 #include <string>
 #include <utility>
 #include <vector>
 
 namespace vtmc {
+struct TerrainBox {
+    int lx, ly, lz;  // first sample
+    int dx, dy, dz;  // samples per axis (0 on some axis: the modifier wrote nothing)
+};
 // Memory a context owns: device memory (VtmcDevBuf, grown by ensure) or pinned host memory (VtmcPinnedBuf, allocated by pin).  Move-only, so
 // one object names one allocation, and freed by its destructor.  Pointer and size are always cleared together: a buffer freed with its size
 // left standing is written to by the next call that finds it "large enough" (round 3's double free).
@@ -38,6 +43,20 @@ struct OwnedBuf {
 typedef vtmc::OwnedBuf<void, hipFree> VtmcDevBuf;
 template <typename T>
 using VtmcPinnedBuf = vtmc::OwnedBuf<T, hipHostFree>;
+
+// One modifier of a recorded vtmc_terrain_update: its sample box, where the box's image lies in the journal arena, and the clamped
+// AABB the dirty-block rule reads (kept for every modifier, also those whose box is empty, so an undo dirties what the update did).
+struct VtmcHistoryBox {
+    vtmc::TerrainBox box;
+    int low[3], up[3];
+    size_t off = 0;  // bytes into the arena
+};
+// One recorded update: its boxes in queue order, laid out back to back in [off, off + bytes) of the arena.  The images hold the
+// samples as they were before the step while it is done, and as they were after it while it is undone.
+struct VtmcHistoryStep {
+    std::vector<VtmcHistoryBox> boxes;
+    size_t off = 0, bytes = 0;
+};
 
 // An extract that has been queued on a stream and not yet completed by extract_finish().
 struct VtmcPending {
@@ -101,6 +120,11 @@ struct vtmc_ctx {
     uint32_t terrain_events = 0;
     std::vector<int32_t> dirty;  // (bx,by,bz) of the last vtmc_terrain_update, ordered by block id
     bool dirty_is_all = false;   // ... or every block (the list is then materialised on demand only)
+    // terrain.hip: the edit journal (vtmc_terrain_set_history / _undo / _redo).  `journal` is the arena, max_bytes long, allocated by
+    // set_history only; the steps are placed in it as a ring, oldest first.  hist[0, hist_done) can be undone, hist[hist_done, end) redone.
+    VtmcDevBuf journal;
+    std::deque<VtmcHistoryStep> hist;
+    size_t hist_done = 0;
     // raycast.hip: the rays and hits of vtmc_terrain_raycast (device, then their pinned staging)
     VtmcDevBuf rays;
     VtmcPinnedBuf<unsigned char> h_rays;

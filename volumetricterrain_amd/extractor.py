@@ -274,6 +274,29 @@ class Extractor:
                                                 ctypes.byref(nd), ctypes.byref(t)))
         return nd.value, t.value
 
+    def terrain_set_history(self, max_bytes):
+        """Undo / redo of terrain_update calls in a device journal of max_bytes (0: history off, the default)."""
+        self._check(self._L.vtmc_terrain_set_history(self._h, int(max_bytes)))
+
+    def terrain_undo(self):
+        """Takes the newest recorded terrain_update back and extracts its dirty blocks.  Returns (number of dirty blocks, T);
+        VtmcError ERR_NO_RESULT when there is nothing to undo."""
+        nd, t = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._L.vtmc_terrain_undo(self._h, ctypes.byref(nd), ctypes.byref(t)))
+        return nd.value, t.value
+
+    def terrain_redo(self):
+        """Re-applies the newest undone step, as terrain_undo.  Returns (number of dirty blocks, T)."""
+        nd, t = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._L.vtmc_terrain_redo(self._h, ctypes.byref(nd), ctypes.byref(t)))
+        return nd.value, t.value
+
+    def terrain_history(self):
+        """(steps that can be undone, steps that can be redone, journal bytes they hold)."""
+        nu, nr, b = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        self._check(self._L.vtmc_terrain_history(self._h, ctypes.byref(nu), ctypes.byref(nr), ctypes.byref(b)))
+        return nu.value, nr.value, b.value
+
     def terrain_dirty_blocks(self):
         n = ctypes.c_int32()
         self._check(self._L.vtmc_terrain_dirty_blocks(self._h, None, 0, ctypes.byref(n)))
