@@ -282,6 +282,23 @@ int32_t vtmc_device_indexed_results(vtmc_ctx *ctx, const vtmc_vertex **d_vertice
 #define VTMC_MOD_HEIGHTMAP 3 /* IslandModifier.cs:34-73    f = bilinear(_heightmap)(x, z) - y; p[0] = _island.width,
                                                            p[1] = _island.height; data = _heightmap (host pointer,
                                                            float[data_dims[0], data_dims[1]] row-major as the C# float[,]) */
+#define VTMC_MOD_SMOOTH 4    /* sculpt brush (not in the reference): p[0..2] = centre c (world), p[3] = radius r, p[4] = strength s */
+#define VTMC_MOD_FLATTEN 5   /* sculpt brush (not in the reference): p[0..2] = centre c (a point of the plane), p[3] = radius r,
+                                                           p[4] = strength s, p[5..7] = plane normal n (the mirrors normalise it;
+                                                           used as given) */
+/* The brushes (kinds 4 and 5) take their box from lower / upper as kinds 0-3 do (the mirrors pass c -/+ r), mark dirty blocks by the
+ * same rule and take one event number each (they draw nothing with it); add_or_erode is ignored.  A brush sees what the earlier
+ * modifiers of its queue wrote.  Per sample of the box, FP32 in this order (px, py, pz as for kinds 0-3: (float)x * scale + origin):
+ *   d = sqrtf((dx*dx + dy*dy) + dz*dz) with dx = px - c0 ...;  t = 1 - d / r;  t = t + t;  t = clamp(t, 0, 1);  w = s * t
+ *   w == 0: the sample keeps its 32 bits;  otherwise S' = S + (T - S) * w
+ * VTMC_MOD_SMOOTH: T = the 27-point box mean of the samples as they were before this modifier (none of its own writes is visible to
+ *   it), a neighbour index outside the grid clamped to [0, dim-1] on its axis:  R(y,z) = (s[x-1] + s[x]) + s[x+1];
+ *   P(z) = (R(y-1,z) + R(y,z)) + R(y+1,z);  T = ((P(z-1) + P(z)) + P(z+1)) / 27.
+ * VTMC_MOD_FLATTEN: g = ((n0*(c0-px) + n1*(c1-py)) + n2*(c2-pz)) / scale;  T = clamp(g, -1, 1): solid below the plane (n up), air
+ *   above it, linear in grid units within one sample of it, so with s = 1 the surface lies on the plane where a cell's corners are
+ *   all within r/2 of c.
+ * VTMC_ERR_INVALID_ARG (the modifier's index in vtmc_last_error) for c not finite, r not finite or <= 0, s not finite or outside
+ * [0, 1], and for flatten n not finite or dot(n, n) == 0.  The journal records a brush's box (no halo), as any modifier's. */
 
 /* One queued TerrainModifier (TerrainModifier.cs:19-33).  lower / upper are the values the C#
  * LowerBound / UpperBound properties return (world space): the shim copies them, so Unity's

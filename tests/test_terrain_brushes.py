@@ -1,0 +1,420 @@
+"""Sculpt brushes on the device-resident terrain (VTMC_MOD_SMOOTH / VTMC_MOD_FLATTEN): every write bit for bit against a numpy FP32
+restatement of include/vtmc.h's rule, in its order of operations (numpy's float32 + - * / sqrt are correctly rounded and never
+fused, as the library's are under -ffp-contract=off).  Queues that mix brushes with kinds 0-3 run the reference kinds on the CPU twin
+oracle.Terrain and the brushes on its memory, one event number each.
+
+Grids are compared as uint32; triangles as in test_terrain.py: offsets and `block` exact, floats within 1e-5."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import volumetricterrain_amd as vt
+from volumetricterrain_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32 = np.float32
+DIMS, SCALE, ORIGIN, SEED = (64, 24, 48), 1.0, (0.0, 0.0, 0.0), 4321
+WORLD = [("plane", (9.375, (-1, -1), (70, 70), True)), ("sphere", ((20.5, 10.25, 30.0), 7.5, True)),
+         ("sphere", ((44.0, 9.5, 16.0), 6.0, False)), ("cylinder", ((5.0, 12.0, 5.0), (1.0, 0.25, 0.5), 50.0, 3.0, True))]
+
+
+# -- the numpy reference ----------------------------------------------------------------------------------------------------------------
+def saturating_int(v):
+    return -2 ** 31 if v <= -2147483648.0 else (2 ** 31 - 1 if v >= 2147483648.0 else int(v))
+
+
+def sample_range(m, dims_s, scale, origin):
+    """terrain.hip's sample_range: ([low], [up]) clamped as the dirty rule reads them, and the box (first sample, extent)."""
+    low, up, first, ext = [], [], [], []
+    for k in range(3):
+        top = dims_s[k] - 1
+        lo = max(saturating_int(np.floor((f32(m.lower[k]) - f32(origin[k])) / f32(scale))), 0)
+        hi = min(saturating_int(np.ceil((f32(m.upper[k]) - f32(origin[k])) / f32(scale))), top)
+        e = hi - lo + 1
+        low.append(lo)
+        up.append(hi)
+        first.append(lo)
+        ext.append(0 if e <= 0 or lo > top else min(e, top - lo + 1))
+    return low, up, first, ext
+
+
+def dirty_ids(low, up, nb):
+    """mark_dirty_blocks: up >= 8b && low <= 8b + 8 on every axis."""
+    r = []
+    for k in range(3):
+        lo, hi = low[k] - 8, up[k]
+        f = 0 if lo <= 0 else (lo + 7) // 8
+        last = min(-1 if hi < 0 else hi // 8, nb[k] - 1)
+        if f > last:
+            return set()
+        r.append(range(f, last + 1))
+    return {bx + nb[0] * (by + nb[1] * bz) for bz in r[2] for by in r[1] for bx in r[0]}
+
+
+def image_bytes(ext):
+    n = ext[0] * ext[1] * ext[2]
+    return 0 if min(ext) <= 0 else (4 * n + 255) // 256 * 256
+
+
+def brush_values(mem, m, first, ext, scale, origin):
+    """New values of the box first..first+ext of mem ([z, y, x], the pre-brush samples) under brush struct m."""
+    (lx, ly, lz), (dx, dy, dz) = first, ext
+    Dz, Dy, Dx = mem.shape
+    c0, c1, c2, r, s = (f32(v) for v in m.p[0:5])
+    S = mem[lz:lz + dz, ly:ly + dy, lx:lx + dx]
+    px = np.arange(lx, lx + dx).astype(f32) * f32(scale) + f32(origin[0])
+    py = np.arange(ly, ly + dy).astype(f32) * f32(scale) + f32(origin[1])
+    pz = np.arange(lz, lz + dz).astype(f32) * f32(scale) + f32(origin[2])
+    ddx, ddy, ddz = px - c0, py - c1, pz - c2
+    d = np.sqrt(((ddx * ddx)[None, None, :] + (ddy * ddy)[None, :, None]) + (ddz * ddz)[:, None, None])
+    t = f32(1) - d / r
+    t = t + t
+    t = np.where(t < 0, f32(0), np.where(t > 1, f32(1), t))
+    w = s * t
+    if m.kind == _lib.MOD_SMOOTH:
+        zi = np.clip(np.arange(lz - 1, lz + dz + 1), 0, Dz - 1)
+        yi = np.clip(np.arange(ly - 1, ly + dy + 1), 0, Dy - 1)
+        xi = np.clip(np.arange(lx - 1, lx + dx + 1), 0, Dx - 1)
+        G = mem[np.ix_(zi, yi, xi)]
+        R = (G[:, :, :-2] + G[:, :, 1:-1]) + G[:, :, 2:]
+        P = (R[:, :-2] + R[:, 1:-1]) + R[:, 2:]
+        T = ((P[:-2] + P[1:-1]) + P[2:]) / f32(27)
+    else:
+        n0, n1, n2 = (f32(v) for v in m.p[5:8])
+        g = ((n0 * (c0 - px)[None, None, :] + n1 * (c1 - py)[None, :, None]) + n2 * (c2 - pz)[:, None, None]) / f32(scale)
+        T = np.where(g < -1, f32(-1), np.where(g > 1, f32(1), g))
+    out = S + (T - S) * w
+    return np.where(w == 0, S, out).astype(f32)
+
+
+def apply_brush(ref, m):
+    """One brush on the twin's memory, one event number; returns the block ids it dirties."""
+    dims_s = tuple(d + 2 for d in ref.dims)
+    low, up, first, ext = sample_range(m, dims_s, ref.scale, ref.origin)
+    if min(ext) > 0:
+        (lx, ly, lz), (dx, dy, dz) = first, ext
+        ref._mem[lz:lz + dz, ly:ly + dy, lx:lx + dx] = brush_values(ref._mem, m, first, ext, ref.scale, ref.origin)
+    ref.events += 1
+    nb = tuple(d // 8 for d in ref.dims)
+    return dirty_ids(low, up, nb)
+
+
+# -- device / twin plumbing -------------------------------------------------------------------------------------------------------------
+def gpu_mod(spec):
+    kind, args = spec
+    return {"plane": vt.PlaneModifier, "sphere": vt.SphereModifier, "cylinder": vt.CylinderModifier,
+            "smooth": vt.SmoothModifier, "flatten": vt.FlattenModifier}[kind](*args)
+
+
+def oracle_mod_of(oracle_mod, spec):
+    kind, args = spec
+    return {"plane": oracle_mod.plane_modifier, "sphere": oracle_mod.sphere_modifier,
+            "cylinder": oracle_mod.cylinder_modifier}[kind](*args)
+
+
+def twin_update(ref, oracle_mod, specs):
+    """The queue on the twin: reference kinds through oracle.Terrain, brushes through numpy.  Returns the dirty list by block id."""
+    nb = tuple(d // 8 for d in ref.dims)
+    ids = set()
+    for spec in specs:
+        if spec[0] in ("smooth", "flatten"):
+            ids |= apply_brush(ref, gpu_mod(spec).to_struct())
+        else:
+            d = ref.update([oracle_mod_of(oracle_mod, spec)])
+            ids |= {int(bx + nb[0] * (by + nb[1] * bz)) for bx, by, bz in d}
+    ids = np.array(sorted(ids), np.int64)
+    return np.stack([ids % nb[0], (ids // nb[0]) % nb[1], ids // (nb[0] * nb[1])], axis=1).astype(np.int32).reshape(-1, 3)
+
+
+def both_update(ex, ref, oracle_mod, specs):
+    got = ex.terrain_update([gpu_mod(s) for s in specs])
+    return got, twin_update(ref, oracle_mod, specs)
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def assert_grid(ex, want):
+    assert np.array_equal(bits(ex.terrain_read_samples()), bits(want))
+
+
+def assert_triangles(ex, oracle_mod, grid, dirty, T):
+    want, want_offs, _ = oracle_mod.extract_grid(np.ascontiguousarray(grid), dirty, threads=8)
+    assert T == len(want)
+    if T:
+        got, offs = ex.read_triangles()
+        assert np.array_equal(offs, want_offs) and np.array_equal(got["block"], want["block"])
+        for f in ("p0", "p1", "p2", "n0", "n1", "n2"):
+            assert np.abs(got[f] - want[f]).max() <= 1e-5
+
+
+def assert_update(ex, ref, oracle_mod, specs):
+    (n_dirty, T), dirty = both_update(ex, ref, oracle_mod, specs)
+    assert_grid(ex, ref.grid)
+    assert n_dirty == len(dirty) and np.array_equal(ex.terrain_dirty_blocks(), dirty)
+    assert_triangles(ex, oracle_mod, ref.grid, dirty, T)
+    return n_dirty, T
+
+
+def world(oracle_mod, history=0):
+    ex = vt.Extractor(0)
+    ex.terrain_init(*DIMS, SCALE, ORIGIN, SEED)
+    ref = oracle_mod.Terrain(*DIMS, SCALE, ORIGIN, SEED)
+    both_update(ex, ref, oracle_mod, WORLD)
+    assert_grid(ex, ref.grid)
+    if history:
+        ex.terrain_set_history(history)
+    return ex, ref
+
+
+def invalid(ex, mods):
+    with pytest.raises(vt.VtmcError) as e:
+        ex.terrain_update(mods)
+    assert e.value.code == _lib.ERR_INVALID_ARG
+    return str(e.value)
+
+
+def raw_brush(kind, p):
+    """A vtmc_modifier the mirrors would refuse to build: kind with parameters p, box c -/+ 4."""
+    m = _lib.Modifier(kind, 1)
+    m.p[0:len(p)] = tuple(float(v) for v in p)
+    c = [v if np.isfinite(v) else 0.0 for v in p[0:3]]
+    m.lower[:] = tuple(v - 4.0 for v in c)
+    m.upper[:] = tuple(v + 4.0 for v in c)
+    return m
+
+
+# -- CPU: the interface -----------------------------------------------------------------------------------------------------------------
+def test_header_defines_the_brush_kinds():
+    text = open(os.path.join(ROOT, "include", "vtmc.h")).read()
+    for name, value in (("VTMC_MOD_SMOOTH", _lib.MOD_SMOOTH), ("VTMC_MOD_FLATTEN", _lib.MOD_FLATTEN)):
+        m = re.search(r"#define\s+%s\s+(\d+)" % name, text)
+        assert m and int(m.group(1)) == value, name
+    assert (_lib.MOD_SMOOTH, _lib.MOD_FLATTEN) == (4, 5)
+
+
+def test_smooth_mirror_struct_and_bounds():
+    b = vt.SmoothModifier((10.1, 3.3, -7.7), 2.6, 0.35)
+    m = b.to_struct()
+    c, r = np.array([10.1, 3.3, -7.7], f32), f32(2.6)
+    assert m.kind == _lib.MOD_SMOOTH
+    assert np.array_equal(np.array(m.lower, f32), c - r) and np.array_equal(np.array(m.lower, f32), b.LowerBound)
+    assert np.array_equal(np.array(m.upper, f32), c + r) and np.array_equal(np.array(m.upper, f32), b.UpperBound)
+    assert np.array_equal(np.array(m.p, f32), np.array([*c, r, 0.35, 0, 0, 0], f32))
+    assert vt.SmoothModifier((0, 0, 0), 1.0).to_struct().p[4] == 1.0   # default strength
+
+
+def test_flatten_mirror_struct_bounds_and_normal():
+    b = vt.FlattenModifier((1.5, 2.0, 3.0), (0.0, 3.0, 4.0), 5.25, 0.5)
+    m = b.to_struct()
+    c, r = np.array([1.5, 2.0, 3.0], f32), f32(5.25)
+    assert m.kind == _lib.MOD_FLATTEN
+    assert np.array_equal(np.array(m.lower, f32), c - r) and np.array_equal(np.array(m.upper, f32), c + r)
+    assert np.array_equal(np.array(m.p, f32), np.array([*c, r, 0.5, 0.0, 0.6, 0.8], f32))
+    d = np.array([0.3, -1.7, 0.45], f32)
+    n = np.array(vt.FlattenModifier((0, 0, 0), d, 1.0).to_struct().p[5:8], f32)
+    cyl = np.array(vt.CylinderModifier((0, 0, 0), d, 1.0, 1.0).to_struct().p[3:6], f32)   # the same normalisation as the axis
+    assert np.array_equal(n, cyl) and abs(float(np.dot(n, n)) - 1.0) < 1e-6
+
+
+@pytest.mark.parametrize("args", [
+    ((np.nan, 0, 0), 1.0, 1.0), ((0, np.inf, 0), 1.0, 1.0), ((0, 0, 0), 0.0, 1.0), ((0, 0, 0), -1.0, 1.0), ((0, 0, 0), np.inf, 1.0),
+    ((0, 0, 0), np.nan, 1.0), ((0, 0, 0), 1.0, -0.1), ((0, 0, 0), 1.0, 1.5), ((0, 0, 0), 1.0, np.nan), ((0, 0, 0), 1.0, np.inf)])
+def test_brush_mirrors_reject_what_the_library_rejects(args):
+    c, r, s = args
+    with pytest.raises(ValueError):
+        vt.SmoothModifier(c, r, s)
+    with pytest.raises(ValueError):
+        vt.FlattenModifier(c, (0, 1, 0), r, s)
+
+
+@pytest.mark.parametrize("n", [(0, 0, 0), (np.nan, 1, 0), (0, np.inf, 0), (1e-30, 0, 0)])
+def test_flatten_mirror_rejects_a_bad_normal(n):
+    with pytest.raises(ValueError):
+        vt.FlattenModifier((0, 0, 0), n, 1.0)
+
+
+def test_brush_strength_limits_are_accepted():
+    for s in (0.0, 1.0):
+        vt.SmoothModifier((0, 0, 0), 1.0, s)
+        vt.FlattenModifier((0, 0, 0), (0, 1, 0), 1.0, s)
+
+
+# -- GPU ----------------------------------------------------------------------------------------------------------------------------------
+SMOOTHS = [((30.0, 10.5, 20.0), 6.0, 1.0), ((12.3, 8.7, 33.1), 9.5, 0.4), ((40.25, 11.0, 30.5), 3.5, 0.85),
+           ((0.0, 0.0, 0.0), 5.0, 1.0), ((65.0, 25.0, 49.0), 4.5, 0.7)]          # the last two: grid corners (edge-clamped halo)
+
+
+@pytest.mark.gpu
+def test_gpu_smooth_bitwise(oracle_mod):
+    ex, ref = world(oracle_mod)
+    with ex:
+        for c, r, s in SMOOTHS:
+            n_dirty, T = assert_update(ex, ref, oracle_mod, [("smooth", (c, r, s))])
+            assert n_dirty > 0
+        before = ref.grid.copy()
+        assert assert_update(ex, ref, oracle_mod, [("smooth", ((-50.0, -50.0, -50.0), 3.0, 1.0))]) == (0, 0)   # wholly outside
+        assert_grid(ex, before)
+        assert len(ex.terrain_dirty_blocks()) == 0
+        n_dirty, T = assert_update(ex, ref, oracle_mod, [("smooth", ((32.0, 12.0, 24.0), 60.0, 0.9))])   # the box covers the grid
+        assert n_dirty == 8 * 3 * 6 and T > 0
+
+
+@pytest.mark.gpu
+def test_gpu_smooth_twice_in_one_queue_reads_its_own_predecessor(oracle_mod):
+    """Two overlapping smooths and a large one after a small one: the stage grows mid-queue and each brush sees the one before."""
+    ex, ref = world(oracle_mod)
+    with ex:
+        assert_update(ex, ref, oracle_mod, [("smooth", ((30.0, 10.0, 20.0), 3.0, 1.0)), ("smooth", ((31.0, 10.5, 21.0), 4.0, 1.0)),
+                                            ("smooth", ((30.0, 11.0, 22.0), 20.0, 0.6)), ("smooth", ((20.0, 9.0, 30.0), 5.0, 1.0))])
+
+
+FLATTENS = [((30.0, 10.5, 20.0), (0.0, 1.0, 0.0), 7.0, 1.0), ((12.3, 8.7, 33.1), (0.3, 1.0, -0.2), 9.5, 0.6),
+            ((40.0, 9.0, 25.0), (1.0, 0.0, 0.0), 5.0, 1.0), ((20.0, 12.0, 12.0), (-1.0, -0.5, 0.7), 8.0, 0.45),
+            ((0.0, 2.0, 0.0), (0.1, 1.0, 0.1), 6.0, 1.0)]
+
+
+@pytest.mark.gpu
+def test_gpu_flatten_bitwise(oracle_mod):
+    ex, ref = world(oracle_mod)
+    with ex:
+        for c, n, r, s in FLATTENS:
+            n_dirty, T = assert_update(ex, ref, oracle_mod, [("flatten", (c, n, r, s))])
+            assert n_dirty > 0
+        before = ref.grid.copy()
+        n_dirty, T = assert_update(ex, ref, oracle_mod, [("flatten", ((30.0, 10.0, 20.0), (0.2, 1.0, 0.0), 9.0, 0.0))])   # s = 0
+        assert n_dirty > 0
+        assert_grid(ex, before)
+        assert assert_update(ex, ref, oracle_mod, [("flatten", ((200.0, 10.0, 20.0), (0.0, 1.0, 0.0), 9.0, 1.0))]) == (0, 0)
+        assert_grid(ex, before)
+
+
+MIXED = [("sphere", ((28.0, 11.0, 22.0), 6.0, True)), ("smooth", ((30.0, 11.0, 23.0), 7.0, 0.8)),
+         ("cylinder", ((18.0, 10.0, 15.0), (1.0, 0.1, 0.6), 25.0, 2.5, False)), ("flatten", ((27.0, 10.0, 21.0), (0.2, 1.0, 0.1), 8.0, 0.9)),
+         ("sphere", ((31.0, 9.0, 24.0), 4.0, False))]
+
+
+@pytest.mark.gpu
+def test_gpu_mixed_queue(oracle_mod):
+    ex, ref = world(oracle_mod)
+    with ex:
+        events = ref.events
+        assert_update(ex, ref, oracle_mod, MIXED)
+        assert ref.events == events + len(MIXED)
+        # the clamp draws of a reference kind after the brushes hash the event numbers the brushes took
+        assert_update(ex, ref, oracle_mod, [("sphere", ((36.0, 10.0, 30.0), 5.0, True)), ("smooth", ((36.0, 10.0, 30.0), 6.0, 1.0)),
+                                            ("sphere", ((20.0, 10.0, 30.0), 5.0, False))])
+
+
+@pytest.mark.gpu
+def test_gpu_flatten_puts_the_surface_on_the_plane():
+    dims, scale, origin = (64, 32, 48), 0.5, (-3.0, 1.0, 2.0)
+    c, r = np.array([13.0, 9.6, 14.0], f32), 8.0
+    brush = vt.FlattenModifier(c, (0.25, 1.0, -0.15), r, 1.0)
+    n = np.array(brush.to_struct().p[5:8], np.float64)
+    rng = np.random.default_rng(5)
+    bumps = [vt.SphereModifier((float(rng.uniform(4, 24)), 9.0 + float(rng.uniform(-1, 1)), float(rng.uniform(6, 22))),
+                               float(rng.uniform(0.8, 2.0)), bool(i & 1)) for i in range(24)]
+    with vt.Extractor(0) as ex:
+        ex.terrain_init(*dims, scale, origin, 9)
+        ex.terrain_update([vt.PlaneModifier(9.25, (-10, -10), (100, 100), True)] + bumps)
+        n_dirty, T = ex.terrain_update([brush])
+        assert T > 0
+        tris, _ = ex.read_triangles()
+        blocks = ex.terrain_dirty_blocks().astype(np.float64)
+        near = 0
+        for f in ("p0", "p1", "p2"):
+            v = np.asarray(origin, np.float64) + (8.0 * blocks[tris["block"]] + tris[f].astype(np.float64)) * scale
+            inside = np.linalg.norm(v - c, axis=1) <= r / 2 - 2 * scale
+            near += int(inside.sum())
+            dist = np.abs((v[inside] - c) @ n)
+            assert dist.size == 0 or dist.max() <= 1e-4 * scale, dist.max()
+        assert near > 50
+        o = (c + 5.0 * n).astype(f32)
+        hit = ex.terrain_raycast(o[None], (-n).astype(f32)[None])[0]
+        assert hit["triangle"] >= 0 and abs(float(hit["distance"]) - 5.0) <= 1e-3
+        assert np.abs(hit["point"].astype(np.float64) - c).max() <= 1e-3
+
+
+def step_bytes(ref, specs):
+    dims_s = tuple(d + 2 for d in ref.dims)
+    return sum(image_bytes(sample_range(gpu_mod(s).to_struct(), dims_s, ref.scale, ref.origin)[3]) for s in specs)
+
+
+HISTORY_STEPS = [
+    [("smooth", ((30.0, 10.5, 20.0), 6.0, 1.0))],
+    [("flatten", ((12.3, 8.7, 33.1), (0.3, 1.0, -0.2), 9.5, 0.6))],
+    MIXED,
+    [("smooth", ((0.0, 0.0, 0.0), 5.0, 1.0)), ("flatten", ((40.0, 9.0, 25.0), (1.0, 0.0, 0.0), 5.0, 1.0))],
+    [("smooth", ((32.0, 12.0, 24.0), 60.0, 0.9))],                                      # the whole grid
+]
+
+
+@pytest.mark.gpu
+def test_gpu_history_restores_brushes_bitwise(oracle_mod):
+    ex, ref = world(oracle_mod, history=64 << 20)
+    with ex:
+        snaps, results, want_bytes = [ref.grid.copy()], [], 0
+        for specs in HISTORY_STEPS:
+            results.append(assert_update(ex, ref, oracle_mod, specs) + (ex.terrain_dirty_blocks(),))
+            snaps.append(ref.grid.copy())
+            want_bytes += step_bytes(ref, specs)
+        assert ex.terrain_history() == (len(HISTORY_STEPS), 0, want_bytes)   # the boxes' images, no halo
+        # bad brushes: refused before anything is written, the history untouched
+        events = ref.events
+        for bad in (raw_brush(_lib.MOD_SMOOTH, (30, 10, 20, -1.0, 1.0)), raw_brush(_lib.MOD_SMOOTH, (30, 10, 20, 3.0, 1.5)),
+                    raw_brush(_lib.MOD_SMOOTH, (np.nan, 10, 20, 3.0, 1.0)), raw_brush(_lib.MOD_SMOOTH, (30, 10, 20, np.inf, 1.0)),
+                    raw_brush(_lib.MOD_FLATTEN, (30, 10, 20, 3.0, 1.0, 0, 0, 0)),
+                    raw_brush(_lib.MOD_FLATTEN, (30, 10, 20, 3.0, 1.0, 0, np.nan, 1)),
+                    raw_brush(_lib.MOD_FLATTEN, (30, 10, 20, 3.0, np.nan, 0, 1, 0))):
+            msg = invalid(ex, [vt.SphereModifier((30.0, 10.0, 20.0), 4.0, True), bad])
+            assert "modifier 1" in msg, msg
+            assert_grid(ex, snaps[-1])
+            assert ex.terrain_history() == (len(HISTORY_STEPS), 0, want_bytes)
+        assert ref.events == events
+        for k in reversed(range(len(HISTORY_STEPS))):
+            n_dirty, T = ex.terrain_undo()
+            assert_grid(ex, snaps[k])
+            assert n_dirty == results[k][0] and np.array_equal(ex.terrain_dirty_blocks(), results[k][2])
+            assert_triangles(ex, oracle_mod, snaps[k], results[k][2], T)
+        for k in range(len(HISTORY_STEPS)):
+            n_dirty, T = ex.terrain_redo()
+            assert_grid(ex, snaps[k + 1])
+            assert (n_dirty, T) == results[k][:2]
+        assert ex.terrain_history() == (len(HISTORY_STEPS), 0, want_bytes)
+        # the event counter ran on through the undo / redo: the next mixed queue still matches the twin
+        assert_update(ex, ref, oracle_mod, MIXED)
+
+
+@pytest.mark.gpu
+def test_gpu_history_off_rejects_bad_brushes(oracle_mod):
+    ex, ref = world(oracle_mod)
+    with ex:
+        msg = invalid(ex, [raw_brush(_lib.MOD_FLATTEN, (30, 10, 20, 3.0, 1.0, np.inf, 0, 0))])
+        assert "modifier 0" in msg, msg
+        assert_grid(ex, ref.grid)
+        msg = invalid(ex, [raw_brush(6, (30, 10, 20, 3.0, 1.0))])
+        assert "unknown kind" in msg, msg
+
+
+@pytest.mark.gpu
+def test_gpu_smooth_a_1024_cube_terrain():
+    """A smooth whose box covers a 1026^3-sample grid (4.3 GB: 64-bit offsets in the stage, the grid and the kernels' indices),
+    checked sample for sample on six full z-slabs, the first and the last among them."""
+    W = 1024
+    with vt.Extractor(0) as ex:
+        ex.terrain_init(W, W, W, 1.0, (0.0, 0.0, 0.0), 17)
+        ex.terrain_update([vt.PlaneModifier(500.5, (-1, -1), (W + 2, W + 2), True), vt.SphereModifier((300.0, 500.0, 700.0), 40.0, True),
+                           vt.SphereModifier((700.0, 505.0, 300.0), 60.0, False), vt.SphereModifier((512.0, 1000.0, 1020.0), 30.0, True)])
+        before = ex.terrain_read_samples().transpose(2, 1, 0)     # [z, y, x], x fastest
+        brush = vt.SmoothModifier((512.0, 500.0, 512.0), 1100.0, 0.8)
+        m = brush.to_struct()
+        n_dirty, T = ex.terrain_update([brush])
+        assert n_dirty == (W // 8) ** 3 and T > 0
+        after = ex.terrain_read_samples().transpose(2, 1, 0)
+        for z in (0, 1, 333, 512, W, W + 1):
+            want = brush_values(before, m, (0, 0, z), (W + 2, W + 2, 1), 1.0, (0.0, 0.0, 0.0))
+            assert np.array_equal(bits(after[z:z + 1]), bits(want)), z

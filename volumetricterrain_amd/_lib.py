@@ -48,6 +48,7 @@ SYMBOLS = [
 COMM_ID_BYTES = 128
 
 MOD_PLANE, MOD_SPHERE, MOD_CYLINDER, MOD_HEIGHTMAP = 0, 1, 2, 3
+MOD_SMOOTH, MOD_FLATTEN = 4, 5   # sculpt brushes (not in the reference)
 
 
 class Modifier(ctypes.Structure):

@@ -8,7 +8,7 @@ order of the C# expressions.
 """
 import numpy as np
 
-from ._lib import MOD_CYLINDER, MOD_HEIGHTMAP, MOD_PLANE, MOD_SPHERE, Modifier
+from ._lib import MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, Modifier
 
 _f = np.float32
 FLOAT_MIN_VALUE = _f(-3.4028234663852886e38)  # C# float.MinValue
@@ -149,3 +149,53 @@ class IslandModifier(TerrainModifier):
     def attach(self, m):
         m.data = self._heightmap.ctypes.data   # borrowed: this object outlives the call
         m.data_dims[:] = self._heightmap.shape
+
+
+# -- sculpt brushes (not in the reference; include/vtmc.h VTMC_MOD_SMOOTH / VTMC_MOD_FLATTEN) ------------------------------------------
+# Stencil edits with no pointwise QueryDensity: a brush blends each sample of its box towards a target by w = s * clamp01(2 (1 - d / r)).
+# The box is c -/+ r; AddOrErode is ignored by the library.
+
+def _check_brush(center, radius, strength):
+    if not np.isfinite(center).all():
+        raise ValueError("brush centre must be finite")
+    if not np.isfinite(radius) or not radius > 0:
+        raise ValueError("brush radius must be finite and > 0")
+    if not np.isfinite(strength) or not 0 <= strength <= 1:
+        raise ValueError("brush strength must lie in [0, 1]")
+
+
+class SmoothModifier(TerrainModifier):
+    """Relaxes the surface under the brush: each sample towards the 27-point mean of its neighbours as they were before the brush."""
+    kind = MOD_SMOOTH
+
+    def __init__(self, center, radius, strength=1.0):
+        self._center, self._radius, self._strength = _vec(center), _f(radius), _f(strength)
+        _check_brush(self._center, self._radius, self._strength)
+
+    @property
+    def LowerBound(self):
+        return (self._center - self._radius).astype(_f)
+
+    @property
+    def UpperBound(self):
+        return (self._center + self._radius).astype(_f)
+
+    def params(self):
+        return [*self._center, self._radius, self._strength]
+
+
+class FlattenModifier(SmoothModifier):
+    """Pulls the surface under the brush onto the plane through `center` with normal `normal` (solid on the side -normal points to)."""
+    kind = MOD_FLATTEN
+
+    def __init__(self, center, normal, radius, strength=1.0):
+        super().__init__(center, radius, strength)
+        n = _vec(normal)
+        with np.errstate(over="ignore", under="ignore"):
+            nn = _dot(n, n) if np.isfinite(n).all() else _f(np.nan)
+        if not np.isfinite(nn) or nn == 0:
+            raise ValueError("flatten normal must be finite and non-zero")
+        self._normal = (n / _f(np.sqrt(nn))).astype(_f)   # normalised as CylinderModifier's axis
+
+    def params(self):
+        return [*self._center, self._radius, self._strength, *self._normal]
