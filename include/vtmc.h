@@ -398,6 +398,60 @@ int32_t vtmc_raycast_device(vtmc_ctx *ctx, const float *d_grid, int32_t nx, int3
                             const float *d_origins, const float *d_directions, int32_t n_rays,
                             float max_distance, uint32_t flags, vtmc_ray_hit *d_hits, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sphere casts and closest points -- the queries a moving body makes against the MeshColliders that
+ * BatchUpdate cooks from the read-back mesh (VoxelTerrain.cs:168, 464): Physics.SphereCast, and
+ * Physics.CheckSphere / Collider.ClosestPoint / Physics.ComputePenetration.  The surface is the ray
+ * picking's: the triangles vtmc_extract_grid emits in exact mode, vertex p of block b at world
+ * origin + (8b + p) * voxel_scale.  Zero-area triangles and cells with a NaN corner never count.  All
+ * distances are world units.
+ *
+ * Sphere cast: a ball of radius r >= 0 centred at o, swept along d/|d|.  The answer is the smallest
+ * t in [0, max_distance] at which the closed ball around o + t d/|d| meets a closed triangle; a
+ * triangle the ball touches at the start gives t = 0.  The face rule is the raycast's, per triangle
+ * and for face, edge and vertex contacts alike: a triangle counts when dot(d, cross(p1-p0, p2-p0)) < 0,
+ * or always with VTMC_RAY_TWO_SIDED.  r = 0 is the ray of vtmc_terrain_raycast.
+ *
+ * Closest point: the point q of the surface nearest to a centre c among the triangles within r of it,
+ * every triangle counting (no face rule); flags are reserved and must be 0.
+ *
+ * Ties (equal t, or equal distance) go to the smallest canonical index (block bx + nbx (by + nby bz),
+ * cell x + 8y + 64z, triangle i): results depend neither on the grid's strides nor on the launch.
+ * A query with a zero or non-finite direction, or a non-finite origin / centre, is a miss.
+ * VTMC_ERR_INVALID_ARG: n < 0; a null pointer with n > 0; max_distance NaN or <= 0 (+inf allowed);
+ * unknown flags; a host radius that is NaN, infinite, negative or above
+ * VTMC_SPHERE_MAX_RADIUS_CELLS * voxel_scale (the error text names the query).  The _device calls do not
+ * read their device radii on the host: there such a query is a miss.  n = 0 does nothing.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct vtmc_sphere_hit {
+    float distance;   /* sphere cast: centre travel along d/|d|; closest point: |c - q|; -1 = miss */
+    float point[3];   /* contact / closest point on the surface (world) */
+    float normal[3];  /* unit, from `point` towards the centre at contact; the triangle's unit face normal when that is 0 */
+    int32_t block[3]; /* -1 on a miss */
+    int32_t cell;     /* x + 8y + 64z; -1 on a miss */
+    int32_t triangle; /* 0..4; -1 on a miss */
+} vtmc_sphere_hit;    /* 48 bytes */
+
+#define VTMC_SPHERE_MAX_RADIUS_CELLS 16   /* r / voxel_scale above this: VTMC_ERR_INVALID_ARG */
+
+/* On the terrain of vtmc_terrain_init / _update: host arrays (origins, directions, centers: n x 3 floats;
+ * radii: n floats), synchronous, hits[n].  VTMC_ERR_NO_RESULT before vtmc_terrain_init. */
+int32_t vtmc_terrain_spherecast(vtmc_ctx *ctx, const float *origins, const float *directions, const float *radii,
+                                int32_t n, float max_distance, uint32_t flags, vtmc_sphere_hit *hits);
+int32_t vtmc_terrain_closest_point(vtmc_ctx *ctx, const float *centers, const float *radii, int32_t n, uint32_t flags,
+                                   vtmc_sphere_hit *hits);
+
+/* The same queries on any device grid (as vtmc_raycast_device), device arrays, queued on `stream`
+ * (NULL = the context's stream) without synchronising. */
+int32_t vtmc_spherecast_device(vtmc_ctx *ctx, const float *d_grid, int32_t nx, int32_t ny, int32_t nz,
+                               int64_t stride_x, int64_t stride_y, int64_t stride_z, const float origin[3], float voxel_scale,
+                               const float *d_origins, const float *d_directions, const float *d_radii, int32_t n,
+                               float max_distance, uint32_t flags, vtmc_sphere_hit *d_hits, void *stream);
+int32_t vtmc_closest_point_device(vtmc_ctx *ctx, const float *d_grid, int32_t nx, int32_t ny, int32_t nz,
+                                  int64_t stride_x, int64_t stride_y, int64_t stride_z, const float origin[3], float voxel_scale,
+                                  const float *d_centers, const float *d_radii, int32_t n, uint32_t flags,
+                                  vtmc_sphere_hit *d_hits, void *stream);
+
 /* The same fill without the final synchronisation: queued on `stream` (NULL = the context's stream)
  * and ordered only by it, so a streaming driver can generate batch k+1 on one context / stream while
  * batch k is extracted on another (BASELINE config "2048^3 streaming grid, double-buffered chunks").

@@ -1,0 +1,809 @@
+"""Sphere casts and closest points (vtmc_terrain_spherecast / _closest_point, vtmc_spherecast_device / vtmc_closest_point_device):
+the Physics.SphereCast / CheckSphere / ClosestPoint queries a moving body makes against the MeshColliders (VoxelTerrain.cs:168, 464),
+against the surface vtmc_extract_grid emits in exact mode, checked against a CPU reference kept here.
+
+The reference takes the oracle's triangles of the same grid (test_raycast.Surface: oracle.extract_grid, exact arithmetic, placed in
+the world in float64), drops zero-area triangles and those of cells with a NaN corner, prefilters candidates by block AABBs grown by r,
+and evaluates every candidate in float64: a sphere cast is the minimum over face, edge (capsule) and vertex contacts with t = 0 for a
+triangle the ball touches at the start (Moller-Trumbore for r = 0); a closest point is Ericson's closest point on a triangle.  Ties go
+to the smallest canonical (block, cell, triangle).
+
+Agreement rule, per query.  The runners-up are the candidates whose t (or distance) lies within NEAR = 1e-7 cells of the best.  Both
+sides evaluate every candidate in float64, so candidates farther apart than that are ordered alike; a wider band catches genuine
+distinct contacts: on a faceted sphere, neighbouring facets are nearly coplanar and a ball touches several of them within 1e-4 cells
+of each other at different points (measured: 32 of 256 sweeps onto fields.sphere with a 1e-4 band, 40 % with shared-point ties
+included), although the kernel and the reference name the same triangle for every one of them.  A query with
+none is held to: hit / miss, |distance - ref| <= 2e-4 scale + 1e-6 ref, point within 2e-4 cells, normal within 1e-4, and (block,
+cell, triangle) exactly.  So is a query whose runners-up tie with the best exactly at t = 0 (the ball starts on several triangles
+and no candidate's start distance lies within NEAR of r): the smallest index wins there on both sides.  A query whose
+runners-up touch at the same point (within 2e-4 cells: a vertex or edge several triangles share) names one of them; its distance,
+point and the normal of the named triangle are checked.  The rest are AMBIGUOUS: only the distance has to agree, and they must stay
+under 1 % of a test's queries.
+"""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import fields
+from test_raycast import Surface, compare as compare_rays, reference as ray_reference
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIT_BYTES = 48
+NEAR = 1e-7     # cells: runners-up (see the module docstring)
+PT_TOL = 2e-4   # cells
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# CPU reference
+# ---------------------------------------------------------------------------------------------------------------------------------
+def closest_points(p, A, B, C):
+    """Ericson, Real-Time Collision Detection 5.1.5, vectorised: the point of each triangle (A, B, C: (m, 3)) nearest to p ((3,) or
+    (m, 3))."""
+    ab, ac = B - A, C - A
+    dot = lambda x, y: np.einsum("ij,ij->i", x, y)
+    ap, bp, cp = p - A, p - B, p - C
+    d1, d2, d3, d4, d5, d6 = dot(ab, ap), dot(ac, ap), dot(ab, bp), dot(ac, bp), dot(ab, cp), dot(ac, cp)
+    vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w_ab, w_ac = d1 / (d1 - d3), d2 / (d2 - d6)
+        w_bc = (d4 - d3) / ((d4 - d3) + (d5 - d6))
+        den = 1.0 / (va + vb + vc)
+        inside = A + ab * (vb * den)[:, None] + ac * (vc * den)[:, None]
+        choices = [A, B, A + w_ab[:, None] * ab, C, A + w_ac[:, None] * ac, B + w_bc[:, None] * (C - B)]   # unselected ones may be NaN
+    conds = [(d1 <= 0) & (d2 <= 0), (d3 >= 0) & (d4 <= d3), (vc <= 0) & (d1 >= 0) & (d3 <= 0), (d6 >= 0) & (d5 <= d6),
+             (vb <= 0) & (d2 >= 0) & (d6 <= 0), (va <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0)]
+    return np.select([c[:, None] for c in conds], choices, inside)
+
+
+def sweep_times(o, d, r, P, n):
+    """First contact t >= 0 of a ball of radius r > 0 from o along unit d with each triangle P (m, 3, 3), normals n = cross(e1, e2);
+    inf where there is none.  Face contact inside the triangle, else the edge cylinders and the vertex spheres."""
+    A, B, C = P[:, 0], P[:, 1], P[:, 2]
+    dot = lambda x, y: np.einsum("ij,ij->i", x, y)
+    q = closest_points(o, A, B, C)
+    start = ((o - q) ** 2).sum(1) <= r * r
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nh = n / np.linalg.norm(n, axis=1)[:, None]
+        dist0 = dot(o - A, nh)
+        vn = nh @ d
+        face = ((dist0 > r) & (vn < 0)) | ((dist0 < -r) & (vn > 0))
+        side = np.where(dist0 > 0, 1.0, -1.0)
+        s = (dist0 - side * r) / -vn
+        c = o + s[:, None] * d - (side * r)[:, None] * nh
+        inside = np.ones(len(P), bool)
+        for a, b in ((A, B), (B, C), (C, A)):
+            inside &= dot(np.cross(b - a, c - a), n) >= 0
+        t_face = np.where(face & inside, s, np.inf)
+        t_other = np.full(len(P), np.inf)
+        for a, b in ((A, B), (B, C), (C, A)):
+            e, m = b - a, o - a
+            dd, md, ud = dot(e, e), dot(m, e), e @ d
+            qa, qb, qc = dd - ud * ud, dd * (m @ d) - md * ud, dd * (dot(m, m) - r * r) - md * md
+            disc = qb * qb - qa * qc
+            se = qc / (-qb + np.sqrt(disc))
+            k = md + se * ud
+            ok = (qa > 0) & (qc > 0) & (qb < 0) & (disc >= 0) & (k >= 0) & (k <= dd)
+            t_other = np.minimum(t_other, np.where(ok, se, np.inf))
+            mv = o - a
+            bv, cv = mv @ d, dot(mv, mv) - r * r
+            dv = bv * bv - cv
+            sv = cv / (-bv + np.sqrt(dv))
+            t_other = np.minimum(t_other, np.where((cv > 0) & (bv < 0) & (dv >= 0), sv, np.inf))
+    return np.where(start, 0.0, np.where(np.isfinite(t_face), t_face, t_other))
+
+
+def ray_times(o, d, P):
+    """Moller-Trumbore (r = 0): t of each triangle the ray hits (inclusive edges), inf elsewhere."""
+    e1, e2 = P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        pv = np.cross(d, e2)
+        det = np.einsum("ij,ij->i", e1, pv)
+        tv = o - P[:, 0]
+        u = np.einsum("ij,ij->i", tv, pv) / det
+        qv = np.cross(tv, e1)
+        v = (qv @ d) / det
+        t = np.einsum("ij,ij->i", e2, qv) / det
+        ok = (det != 0) & (u >= 0) & (v >= 0) & (u + v <= 1) & (t >= 0)
+    return np.where(ok, t, np.inf)
+
+
+class SphereSurface:
+    """test_raycast.Surface plus what the sphere queries need: usable triangles, canonical codes, block AABBs."""
+
+    def __init__(self, oracle_mod, grid, origin=(0.0, 0.0, 0.0), scale=1.0, nan_grid=None):
+        """nan_grid: `grid` with some samples set to NaN (the oracle is never run on NaN samples): the surface is grid's without the
+        triangles of cells with a NaN corner, which is nan_grid's, since every other cell has the same eight samples in both."""
+        s = self.s = Surface.of_grid(oracle_mod, grid, origin, scale)
+        self.scale = float(scale)
+        g = np.isnan(np.asarray(grid if nan_grid is None else nan_grid))
+        nanc = np.zeros(tuple(x - 1 for x in g.shape), bool)
+        for dx in (0, 1):
+            for dy in (0, 1):
+                for dz in (0, 1):
+                    nanc |= g[dx:dx + nanc.shape[0], dy:dy + nanc.shape[1], dz:dz + nanc.shape[2]]
+        c = 8 * s.block + np.stack([s.cell & 7, (s.cell >> 3) & 7, s.cell >> 6], 1)
+        self.use = s.ok & ~nanc[c[:, 0], c[:, 1], c[:, 2]]
+        self.code = Surface._code(s.block, s.cell, s.tri)
+        self.normal = np.cross(s.P[:, 1] - s.P[:, 0], s.P[:, 2] - s.P[:, 0])
+
+    def _blocks(self, lo, hi):
+        s = self.s
+        sel = np.nonzero(np.all((s.hi >= lo) & (s.lo <= hi), axis=1))[0]
+        if not len(sel):
+            return np.zeros(0, np.int64)
+        idx = np.concatenate([s.order[s.bounds[b]:s.bounds[b + 1]] for b in sel])
+        return idx[self.use[idx]]
+
+    def _blocks_along(self, o, d, r, max_distance):
+        s = self.s
+        lo, hi = s.lo - r, s.hi + r
+        with np.errstate(divide="ignore", invalid="ignore"):
+            inv = 1.0 / d
+            t0, t1 = (lo - o) * inv, (hi - o) * inv
+            tn = np.nanmax(np.minimum(t0, t1), axis=1)
+            tf = np.nanmin(np.maximum(t0, t1), axis=1)
+            inside = np.all((d != 0) | ((o >= lo) & (o <= hi)), axis=1)
+        sel = np.nonzero(inside & (tn <= tf) & (tf >= 0) & (tn <= max_distance))[0]
+        if not len(sel):
+            return np.zeros(0, np.int64)
+        idx = np.concatenate([s.order[s.bounds[b]:s.bounds[b + 1]] for b in sel])
+        return idx[self.use[idx]]
+
+    def contact(self, j, centre, r_zero):
+        """(point, normal) of triangle j for a ball centred at `centre` (world)."""
+        P = self.s.P[j]
+        q = closest_points(centre, P[None, 0], P[None, 1], P[None, 2])[0]
+        v = centre - q
+        nv = np.linalg.norm(v)
+        if r_zero or not nv > 0:
+            return q, self.normal[j] / np.linalg.norm(self.normal[j])
+        return q, v / nv
+
+    def cast(self, o, d, r, max_distance=np.inf, two_sided=False):
+        res = dict(hit=False, kind="strict")
+        o, d = np.asarray(o, np.float64), np.asarray(d, np.float64)
+        ln = np.linalg.norm(d)
+        if not (np.all(np.isfinite(o)) and np.all(np.isfinite(d)) and ln > 0):
+            return res
+        d = d / ln
+        idx = self._blocks_along(o, d, r, max_distance)
+        if len(idx):
+            front = (self.normal[idx] @ d < 0) | two_sided
+            idx = idx[front]
+        if not len(idx):
+            return res
+        P = self.s.P[idx]
+        t = ray_times(o, d, P) if r == 0 else sweep_times(o, d, r, P, self.normal[idx])
+        t = np.where(np.float32(t) <= np.float32(max_distance), t, np.inf)
+        if not np.isfinite(t).any():
+            return res
+        res.update(self._pick(idx, t, lambda j, tt: o + tt * d, r == 0))
+        if res["kind"] != "strict" and res["t"] == 0.0 and all(tt == 0.0 for tt in res["near_t"]):
+            q = closest_points(o, P[:, 0], P[:, 1], P[:, 2])
+            dist = np.sqrt(((o - q) ** 2).sum(1))
+            if not np.any(np.abs(dist - r) < NEAR * self.scale):
+                res["kind"] = "strict"   # an exact tie at the start: the smallest index on both sides
+        res["o"], res["d"] = o, d
+        return res
+
+    def closest(self, c, r):
+        res = dict(hit=False, kind="strict")
+        c = np.asarray(c, np.float64)
+        if not np.all(np.isfinite(c)):
+            return res
+        idx = self._blocks(c - r, c + r)
+        if not len(idx):
+            return res
+        P = self.s.P[idx]
+        q = closest_points(c, P[:, 0], P[:, 1], P[:, 2])
+        dist = np.sqrt(((c - q) ** 2).sum(1))
+        dist = np.where(dist <= r, dist, np.inf)
+        if not np.isfinite(dist).any():
+            return res
+        res.update(self._pick(idx, dist, lambda j, tt: c, False))
+        return res
+
+    def _pick(self, idx, t, centre_at, r_zero):
+        order = np.lexsort((self.code[idx], t))
+        k = order[0]
+        best = t[k]
+        near = [m for m in order[1:] if t[m] <= best + NEAR * self.scale]
+        j = idx[k]
+        pts = {}
+        for m in [k] + near:
+            pts[int(idx[m])] = self.contact(idx[m], centre_at(idx[m], t[m]), r_zero)
+        kind = "strict"
+        if near:
+            same = all(np.abs(pts[int(idx[m])][0] - pts[int(j)][0]).max() <= PT_TOL * self.scale for m in near)
+            kind = "tied" if same else "ambiguous"
+        key = lambda jj: (tuple(int(x) for x in self.s.block[jj]), int(self.s.cell[jj]), int(self.s.tri[jj]))
+        return dict(hit=True, t=float(best), j=int(j), key=key(j), point=pts[int(j)][0], normal=pts[int(j)][1], kind=kind,
+                    near_t=[float(t[m]) for m in near], tie={key(int(jj)): pts[jj] for jj in pts})
+
+
+def compare(hits, ref, scale, label):
+    """Asserts the agreement rule; returns (ambiguous, tied) counts."""
+    n_amb = n_tied = 0
+    for i, (h, r) in enumerate(zip(hits, ref)):
+        got = h["triangle"] >= 0
+        if got:
+            assert np.isfinite(h["distance"]) and h["distance"] >= 0, (label, i, h)
+            assert np.isfinite(h["point"]).all() and np.isfinite(h["normal"]).all(), (label, i, h)
+            assert abs(np.linalg.norm(h["normal"].astype(np.float64)) - 1.0) < 1e-5, (label, i, h)
+        else:
+            assert h["distance"] == -1.0 and h["cell"] == -1 and tuple(h["block"]) == (-1, -1, -1), (label, i, h)
+        assert got == r["hit"], (label, i, "gpu hit" if got else "gpu miss", r.get("t"), r.get("kind"), h)
+        if not got:
+            continue
+        dist = float(h["distance"])
+        assert abs(dist - r["t"]) <= 2e-4 * scale + 1e-6 * r["t"], (label, i, dist, r["t"], r["kind"])
+        if r["kind"] == "ambiguous":
+            n_amb += 1
+            continue
+        key = (tuple(int(x) for x in h["block"]), int(h["cell"]), int(h["triangle"]))
+        if r["kind"] == "strict":
+            assert key == r["key"], (label, i, key, r["key"], dist, r["t"])
+            point, normal = r["point"], r["normal"]
+        else:
+            n_tied += 1
+            assert key in r["tie"], (label, i, key, list(r["tie"]))
+            point, normal = r["tie"][key]
+        assert np.abs(h["point"].astype(np.float64) - point).max() <= PT_TOL * scale + 1e-6 * np.abs(point).max(), (label, i, h["point"], point)
+        assert np.abs(h["normal"].astype(np.float64) - normal).max() <= 1e-4, (label, i, h["normal"], normal, r["kind"])
+    return n_amb, n_tied
+
+
+def report(label, n, amb_tied):
+    print("sphere queries %s: %d queries, %d ambiguous, %d tied at a shared point" % (label, n, amb_tied[0], amb_tied[1]))
+
+
+def check(hits, ref, scale, label):
+    amb_tied = compare(hits, ref, scale, label)
+    report(label, len(ref), amb_tied)
+    assert amb_tied[0] < 0.01 * len(ref), (label, amb_tied)
+    return amb_tied
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# CPU tests: the ABI surface and the reference itself
+# ---------------------------------------------------------------------------------------------------------------------------------
+NAMES = ("vtmc_terrain_spherecast", "vtmc_terrain_closest_point", "vtmc_spherecast_device", "vtmc_closest_point_device")
+
+
+def test_header_declares_and_library_exports_the_sphere_calls():
+    import volumetricterrain_amd as vt
+    text = open(os.path.join(ROOT, "include", "vtmc.h")).read()
+    lib = vt.load()
+    for name in NAMES:
+        assert re.search(r"int32_t\s+%s\s*\(" % name, text), name
+        assert hasattr(lib, name), name
+    assert "#define VTMC_SPHERE_MAX_RADIUS_CELLS 16" in text
+    assert vt.SPHERE_HIT_DTYPE.itemsize == HIT_BYTES
+    assert [vt.SPHERE_HIT_DTYPE.fields[f][1] for f in ("distance", "point", "normal", "block", "cell", "triangle")] == [0, 4, 16, 28, 40, 44]
+
+
+def test_sphere_hit_layout_and_argument_rules_from_c(tmp_path):
+    """A pedantic C99 host: the 48-byte record and its offsets, and null / negative arguments answered with status codes."""
+    import volumetricterrain_amd as vt
+    if not shutil.which("gcc"):
+        pytest.skip("gcc not installed")
+    vt.load()
+    src = tmp_path / "sphere_host.c"
+    src.write_text("""
+#include "vtmc.h"
+#include <stddef.h>
+#include <stdio.h>
+int main(void)
+{
+    float o[3] = {0, 0, 0}, d[3] = {0, -1, 0}, r = 0.5f;
+    vtmc_sphere_hit h;
+    if (sizeof h != 48) return 2;
+    if (offsetof(vtmc_sphere_hit, distance) != 0 || offsetof(vtmc_sphere_hit, point) != 4 || offsetof(vtmc_sphere_hit, normal) != 16 ||
+        offsetof(vtmc_sphere_hit, block) != 28 || offsetof(vtmc_sphere_hit, cell) != 40 || offsetof(vtmc_sphere_hit, triangle) != 44) return 3;
+    if (VTMC_SPHERE_MAX_RADIUS_CELLS != 16) return 4;
+    if (vtmc_terrain_spherecast(NULL, o, d, &r, 1, 1.0f, 0u, &h) != VTMC_ERR_INVALID_ARG) return 5;
+    if (vtmc_terrain_closest_point(NULL, o, &r, 1, 0u, &h) != VTMC_ERR_INVALID_ARG) return 6;
+    if (vtmc_spherecast_device(NULL, NULL, 8, 8, 8, 1, 10, 100, o, 1.0f, NULL, NULL, NULL, 1, 1.0f, VTMC_RAY_TWO_SIDED, NULL, NULL) != VTMC_ERR_INVALID_ARG)
+        return 7;
+    if (vtmc_closest_point_device(NULL, NULL, 8, 8, 8, 1, 10, 100, o, 1.0f, NULL, NULL, -3, 0u, NULL, NULL) != VTMC_ERR_INVALID_ARG) return 8;
+    puts("ok");
+    return 0;
+}
+""")
+    inc, lib = os.path.join(ROOT, "include"), vt.library_path()
+    exe = tmp_path / "sphere_host"
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", inc, str(src), "-o", str(exe), lib,
+                    "-Wl,-rpath," + os.path.dirname(lib)], check=True, capture_output=True, text=True)
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "ok" in p.stdout, (p.returncode, p.stdout, p.stderr[-500:])
+
+
+def test_integration_has_the_sphere_query_stubs():
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name in NAMES:
+        assert re.search(r"\[DllImport\([^\]]*\)\]\s*public static extern int %s\s*\(" % name, text), name
+    assert "struct VtmcSphereHit" in text
+
+
+def test_reference_plane_known_answers(oracle_mod):
+    """f = h - y puts every vertex at y = h: a ball swept down from y0 touches at y0 - r - h with normal +y, from below only two-sided;
+    a closest-point query at height y answers |y - h| with normal sign(y - h) y."""
+    h = 9.375
+    surf = SphereSurface(oracle_mod, fields.plane((32, 16, 24), h))
+    rng = np.random.default_rng(3)
+    for r in (0.0, 0.25, 1.0, 3.0):
+        o = np.stack([rng.uniform(4, 28, 16), np.full(16, 15.5), rng.uniform(4, 20, 16)], 1)
+        for oo in o:
+            res = surf.cast(oo, [0.0, -1.0, 0.0], r)
+            assert res["hit"] and abs(res["t"] - (oo[1] - r - h)) < 1e-9, (r, res)
+            if res["kind"] != "ambiguous":
+                assert np.allclose(res["normal"], [0, 1, 0]) and abs(res["point"][1] - h) < 1e-9
+            assert not surf.cast(oo - [0, 15, 0], [0.0, 1.0, 0.0], r)["hit"]
+            up = surf.cast(oo - [0, 15, 0], [0.0, 1.0, 0.0], r, two_sided=True)
+            assert up["hit"] and abs(up["t"] - (h - (oo[1] - 15) - r)) < 1e-9
+            assert not surf.cast(oo, [0.0, -1.0, 0.0], r, max_distance=oo[1] - r - h - 1e-3)["hit"]
+    for y in (8.0, 9.0, 10.5, 12.0):
+        res = surf.closest([13.3, y, 11.7], 4.0)
+        assert res["hit"] and abs(res["t"] - abs(y - h)) < 1e-9 and np.allclose(res["normal"], [0, np.sign(y - h), 0])
+    assert not surf.closest([13.3, 2.0, 11.7], 4.0)["hit"]
+
+
+def test_reference_sweep_contacts_edges_and_vertices():
+    """The sweep's three contact kinds on one triangle, against closed forms."""
+    P = np.array([[[0.0, 0.0, 0.0], [4.0, 0.0, 0.0], [0.0, 0.0, 4.0]]])
+    n = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])   # (0, -16, 0)
+    down = np.array([0.0, -1.0, 0.0])
+    assert sweep_times(np.array([1.0, 5.0, 1.0]), down, 1.0, P, n)[0] == pytest.approx(4.0)        # face
+    assert sweep_times(np.array([-0.6, 5.0, 1.0]), down, 1.0, P, n)[0] == pytest.approx(5.0 - 0.8)  # edge x = 0
+    assert sweep_times(np.array([-0.6, 5.0, -0.8]), down, 1.0, P, n)[0] == pytest.approx(5.0)       # vertex 0 at distance 1
+    assert sweep_times(np.array([-0.6, 0.5, 1.0]), down, 1.0, P, n)[0] == 0.0                       # touching at the start
+    assert np.isinf(sweep_times(np.array([-2.0, 5.0, 1.0]), down, 1.0, P, n)[0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# GPU helpers
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _device(a):
+    import torch
+    return torch.from_numpy(np.array(a, copy=True, order="C")).cuda()
+
+
+def _cast(ex, g, n, strides, origin, scale, o, d, r, max_distance=float("inf"), two_sided=False):
+    import torch
+    import volumetricterrain_amd as vt
+    d_o, d_d, d_r = _device(np.float32(o)), _device(np.float32(d)), _device(np.broadcast_to(np.float32(r), (len(o),)))
+    d_h = torch.full((len(o) * HIT_BYTES,), 0x5A, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    ex.spherecast_device(g, n, strides, origin, scale, d_o.data_ptr(), d_d.data_ptr(), d_r.data_ptr(), len(o), d_h.data_ptr(),
+                         max_distance, two_sided)
+    return ex.copy_to_host(d_h.data_ptr(), len(o) * HIT_BYTES).view(vt.SPHERE_HIT_DTYPE)
+
+
+def _closest(ex, g, n, strides, origin, scale, c, r):
+    import torch
+    import volumetricterrain_amd as vt
+    d_c, d_r = _device(np.float32(c)), _device(np.broadcast_to(np.float32(r), (len(c),)))
+    d_h = torch.full((len(c) * HIT_BYTES,), 0x5A, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    ex.closest_point_device(g, n, strides, origin, scale, d_c.data_ptr(), d_r.data_ptr(), len(c), d_h.data_ptr())
+    return ex.copy_to_host(d_h.data_ptr(), len(c) * HIT_BYTES).view(vt.SPHERE_HIT_DTYPE)
+
+
+def _raycast(ex, g, n, strides, origin, scale, o, d, max_distance=float("inf"), two_sided=False):
+    import torch
+    import volumetricterrain_amd as vt
+    d_o, d_d = _device(np.float32(o)), _device(np.float32(d))
+    d_h = torch.empty(len(o) * 56, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    ex.raycast_device(g, n, strides, origin, scale, d_o.data_ptr(), d_d.data_ptr(), len(o), d_h.data_ptr(), max_distance, two_sided)
+    return ex.copy_to_host(d_h.data_ptr(), len(o) * 56).view(vt.RAY_HIT_DTYPE)
+
+
+class DeviceGrid:
+    """A host grid [x, y, z] on the device, x fastest (order 'x') or z fastest (order 'z')."""
+
+    def __init__(self, grid, order="x"):
+        g = np.asarray(grid, np.float32)
+        mem = g.transpose(2, 1, 0) if order == "x" else g
+        self.t = _device(mem.ravel())
+        dx, dy, dz = g.shape
+        self.strides = (1, dx, dx * dy) if order == "x" else (dy * dz, dz, 1)
+        self.n = (dx - 2, dy - 2, dz - 2)
+        self.ptr = self.t.data_ptr()
+
+
+def _sweeps(n, k, rng, r_max):
+    """Sweeps through an n box (cells): from outside towards a point of the box, and from inside in any direction."""
+    n = np.asarray(n, float)
+    c = n / 2
+    u = rng.normal(size=(k, 3))
+    u /= np.linalg.norm(u, axis=1)[:, None]
+    o = c + u * rng.uniform(0.6, 1.0, (k, 1)) * n.max()
+    d = rng.uniform(0, 1, (k, 3)) * n - o
+    half = k // 2
+    o[half:] = rng.uniform(0, 1, (k - half, 3)) * n
+    d[half:] = rng.normal(size=(k - half, 3))
+    r = rng.uniform(0, r_max, k)
+    r[rng.random(k) < 0.1] = 0.0
+    return o, d, r
+
+
+def _perlin(vt, ex, n, order="x"):
+    import torch
+    dims = tuple(x + 2 for x in n)
+    g = torch.empty(int(np.prod(dims)), dtype=torch.float32, device="cuda")
+    st = (1, dims[0], dims[0] * dims[1]) if order == "x" else (dims[1] * dims[2], dims[2], 1)
+    ex.density_fill_device(vt.density_params("perlin3d", max(n)), [[0, 0, 0]], dims, st, 0, g.data_ptr())
+    return g, st
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# GPU tests
+# ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_argument_rules_return_their_code_and_write_nothing():
+    import torch
+    import volumetricterrain_amd as vt
+    with vt.Extractor(0) as ex:
+        L, h = ex._L, ex._h
+        o = np.zeros((2, 3), np.float32)
+        d = np.tile(np.float32([0, -1, 0]), (2, 1))
+        r = np.full(2, 0.5, np.float32)
+        hits = np.full(2 * HIT_BYTES, 0x5A, np.uint8)
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        # before terrain_init
+        assert L.vtmc_terrain_spherecast(h, p(o), p(d), p(r), 2, 1.0, 0, p(hits)) == vt._lib.ERR_NO_RESULT
+        assert L.vtmc_terrain_closest_point(h, p(o), p(r), 2, 0, p(hits)) == vt._lib.ERR_NO_RESULT
+        ex.terrain_init(32, 16, 32, 0.5, (0.0, 0.0, 0.0), 1)
+        ex.terrain_update([vt.PlaneModifier(6.5, (-1, -1), (40, 40), True)])
+        bad = [
+            lambda: L.vtmc_terrain_spherecast(h, p(o), p(d), p(r), -1, 1.0, 0, p(hits)),
+            lambda: L.vtmc_terrain_spherecast(h, None, p(d), p(r), 2, 1.0, 0, p(hits)),
+            lambda: L.vtmc_terrain_spherecast(h, p(o), None, p(r), 2, 1.0, 0, p(hits)),
+            lambda: L.vtmc_terrain_spherecast(h, p(o), p(d), None, 2, 1.0, 0, p(hits)),
+            lambda: L.vtmc_terrain_spherecast(h, p(o), p(d), p(r), 2, 1.0, 0, None),
+            lambda: L.vtmc_terrain_spherecast(h, p(o), p(d), p(r), 2, float("nan"), 0, p(hits)),
+            lambda: L.vtmc_terrain_spherecast(h, p(o), p(d), p(r), 2, 0.0, 0, p(hits)),
+            lambda: L.vtmc_terrain_spherecast(h, p(o), p(d), p(r), 2, -1.0, 0, p(hits)),
+            lambda: L.vtmc_terrain_spherecast(h, p(o), p(d), p(r), 2, 1.0, 2, p(hits)),
+            lambda: L.vtmc_terrain_closest_point(h, p(o), p(r), -1, 0, p(hits)),
+            lambda: L.vtmc_terrain_closest_point(h, None, p(r), 2, 0, p(hits)),
+            lambda: L.vtmc_terrain_closest_point(h, p(o), None, 2, 0, p(hits)),
+            lambda: L.vtmc_terrain_closest_point(h, p(o), p(r), 2, 0, None),
+            lambda: L.vtmc_terrain_closest_point(h, p(o), p(r), 2, 1, p(hits)),
+        ]
+        for i, f in enumerate(bad):
+            assert f() == vt._lib.ERR_INVALID_ARG, i
+            assert (hits == 0x5A).all(), i
+        # radius rules: the error names the query (voxel_scale 0.5: the limit is 8.0)
+        for v in (float("nan"), float("inf"), -0.25, np.nextafter(np.float32(8.0), np.float32(9.0))):
+            rr = np.array([0.5, v], np.float32)
+            assert L.vtmc_terrain_spherecast(h, p(o), p(d), p(rr), 2, 1.0, 0, p(hits)) == vt._lib.ERR_INVALID_ARG, v
+            assert "query 1" in L.vtmc_last_error(h).decode(), L.vtmc_last_error(h)
+            assert L.vtmc_terrain_closest_point(h, p(o), p(rr), 2, 0, p(hits)) == vt._lib.ERR_INVALID_ARG, v
+            assert "query 1" in L.vtmc_last_error(h).decode()
+            assert (hits == 0x5A).all(), v
+        assert L.vtmc_terrain_spherecast(h, None, None, None, 0, 1.0, 0, None) == 0
+        assert L.vtmc_terrain_closest_point(h, None, None, 0, 0, None) == 0
+        # the device calls
+        g = torch.zeros(34 ** 3, dtype=torch.float32, device="cuda")
+        org = (ctypes.c_float * 3)(0, 0, 0)
+        dh = torch.full((2 * HIT_BYTES,), 0x5A, dtype=torch.uint8, device="cuda")
+        do, dd, dr = _device(o), _device(d), _device(r)
+        args = lambda n, md, fl, hp: (h, g.data_ptr(), 32, 32, 32, 1, 34, 34 * 34, ctypes.byref(org), 1.0, do.data_ptr(), dd.data_ptr(),
+                                      dr.data_ptr(), n, md, fl, hp, None)
+        for n_, md, fl, hp in ((-1, 1.0, 0, dh.data_ptr()), (2, 1.0, 0, None), (2, float("nan"), 0, dh.data_ptr()), (2, 0.0, 0, dh.data_ptr()),
+                               (2, 1.0, 4, dh.data_ptr())):
+            assert L.vtmc_spherecast_device(*args(n_, md, fl, hp)) == vt._lib.ERR_INVALID_ARG
+        cargs = lambda n, fl, hp: (h, g.data_ptr(), 32, 32, 32, 1, 34, 34 * 34, ctypes.byref(org), 1.0, do.data_ptr(), dr.data_ptr(), n, fl, hp, None)
+        for n_, fl, hp in ((-1, 0, dh.data_ptr()), (2, 0, None), (2, 1, dh.data_ptr())):
+            assert L.vtmc_closest_point_device(*cargs(n_, fl, hp)) == vt._lib.ERR_INVALID_ARG
+        torch.cuda.synchronize()
+        assert (dh.cpu().numpy() == 0x5A).all()
+
+
+@pytest.mark.gpu
+def test_plane_known_answers_on_the_resident_terrain():
+    """A plane terrain at height h (voxel_scale 0.5, shifted origin): straight down from y0 gives y0 - r - h; a closest-point query at
+    height y gives |y - h| with normal +-y; from below only two-sided."""
+    import volumetricterrain_amd as vt
+    scale, org, h_cells = 0.5, (3.0, -2.0, 1.0), 20.5
+    h = org[1] + h_cells * scale
+    rng = np.random.default_rng(4)
+    with vt.Extractor(0) as ex:
+        ex.terrain_init(64, 40, 48, scale, org, 1)
+        ex.terrain_update([vt.PlaneModifier(h, (-1, -1), (80, 80), True)])   # world height: the vertices lie at y = h exactly
+        k = 64
+        xz = np.stack([org[0] + rng.uniform(2, 30, k), np.zeros(k), org[2] + rng.uniform(2, 22, k)], 1)
+        for r in (0.0, 0.3, 1.0, 4.0, 8.0):
+            o = xz + [0, h + 9.0, 0]
+            hits = ex.terrain_spherecast(o, np.tile([0, -1, 0], (k, 1)), r)
+            assert (hits["triangle"] >= 0).all(), r
+            np.testing.assert_allclose(hits["distance"], 9.0 - r, atol=2e-4 * scale + 1e-6 * 9)
+            np.testing.assert_allclose(hits["point"][:, 1], h, atol=2e-4 * scale)
+            np.testing.assert_allclose(hits["normal"], np.tile([0, 1, 0], (k, 1)), atol=1e-4)
+            below = ex.terrain_spherecast(xz + [0, h - 9.5, 0], np.tile([0, 1, 0], (k, 1)), r)
+            assert (below["triangle"] < 0).all()
+            below = ex.terrain_spherecast(xz + [0, h - 9.5, 0], np.tile([0, 1, 0], (k, 1)), r, two_sided=True)
+            np.testing.assert_allclose(below["distance"], 9.5 - r, atol=2e-4 * scale + 1e-6 * 9.5)
+        for y in (-3.0, -0.7, 0.0, 0.4, 2.5):
+            c = xz + [0, h + y, 0]
+            hits = ex.terrain_closest_point(c, 3.5)
+            assert (hits["triangle"] >= 0).all(), y
+            np.testing.assert_allclose(hits["distance"], abs(y), atol=2e-4 * scale)
+            want = [0, 1, 0] if y >= 0 else [0, -1, 0]
+            np.testing.assert_allclose(hits["normal"], np.tile(want, (k, 1)), atol=1e-4)
+            np.testing.assert_allclose(hits["point"][:, [0, 2]], c[:, [0, 2]], atol=2e-4 * scale + 1e-5)
+        assert (ex.terrain_closest_point(xz + [0, h + 4.0, 0], 3.5)["triangle"] < 0).all()
+
+
+@pytest.mark.gpu
+def test_sphere_terrain_against_reference_and_analytic(oracle_mod):
+    """f = R - |x - c|: sweeps aimed at the centre from outside and closest points around it match the reference of the MC mesh, and
+    the analytic sphere within the faceting error."""
+    import volumetricterrain_amd as vt
+    c, R = np.array([16.3, 15.7, 16.1]), 9.5
+    grid = fields.sphere((32, 32, 32), c, R)
+    surf = SphereSurface(oracle_mod, grid)
+    rng = np.random.default_rng(5)
+    k = 256
+    u = rng.normal(size=(k, 3))
+    u /= np.linalg.norm(u, axis=1)[:, None]
+    r = rng.uniform(0, 4, k)
+    o = c + 30.0 * u
+    with vt.Extractor(0) as ex:
+        dg = DeviceGrid(grid)
+        hits = _cast(ex, dg.ptr, dg.n, dg.strides, (0.0, 0.0, 0.0), 1.0, o, -u, r)
+        check(hits, [surf.cast(oo, -uu, float(rr)) for oo, uu, rr in zip(np.float32(o), np.float32(u), np.float32(r))], 1.0, "sphere cast")
+        np.testing.assert_allclose(hits["distance"], 30.0 - R - r, atol=0.1)
+        cc = c + rng.uniform(5, 14, (k, 1)) * u
+        ch = _closest(ex, dg.ptr, dg.n, dg.strides, (0.0, 0.0, 0.0), 1.0, cc, 6.0)
+        check(ch, [surf.closest(x, 6.0) for x in np.float32(cc)], 1.0, "sphere closest")
+        want = np.abs(np.linalg.norm(cc - c, axis=1) - R)
+        hit = ch["triangle"] >= 0
+        assert hit.sum() > k // 2
+        np.testing.assert_allclose(ch["distance"][hit], want[hit], atol=0.1)
+        rho = np.linalg.norm(cc - c, axis=1)
+        radial = (cc - c) / rho[:, None] * np.sign(rho - R)[:, None]
+        clear = hit & (np.abs(rho - R) > 0.2)   # farther from the sphere than the mesh's faceting: the normal points the radial way
+        assert (np.einsum("ij,ij->i", ch["normal"][clear], radial[clear]) > 0.95).all()
+
+
+@pytest.mark.gpu
+def test_zero_radius_equals_the_raycast(oracle_mod):
+    """4096 rays on perlin 64^3, single- and two-sided: the r = 0 sweep names the raycast's triangle at the raycast's distance for every
+    ray the ray reference does not call ambiguous; and both agree with that reference."""
+    import volumetricterrain_amd as vt
+    from test_raycast import _rays_perlin
+    n = 64
+    with vt.Extractor(0) as ex:
+        g, st = _perlin(vt, ex, (n, n, n))
+        grid = g.cpu().numpy().reshape(n + 2, n + 2, n + 2).transpose(2, 1, 0)
+        O, D = _rays_perlin(n, 4096, 17)
+        surf = Surface.of_grid(oracle_mod, grid)
+        for two_sided in (False, True):
+            sh = _cast(ex, g.data_ptr(), (n, n, n), st, (0.0, 0.0, 0.0), 1.0, O, D, 0.0, two_sided=two_sided)
+            rh = _raycast(ex, g.data_ptr(), (n, n, n), st, (0.0, 0.0, 0.0), 1.0, O, D, two_sided=two_sided)
+            ref = ray_reference(surf, O, D, two_sided=two_sided)
+            n_amb = compare_rays(rh, ref, 1.0, "raycast")
+            assert n_amb < 0.01 * len(O)
+            checked = 0
+            for i, (a, b, r) in enumerate(zip(sh, rh, ref)):
+                if r["ambiguous"]:
+                    continue
+                assert (a["triangle"] >= 0) == (b["triangle"] >= 0), (i, a, b)
+                if b["triangle"] < 0:
+                    continue
+                assert (tuple(a["block"]), a["cell"], a["triangle"]) == (tuple(b["block"]), b["cell"], b["triangle"]), (i, a, b)
+                assert abs(float(a["distance"]) - float(b["distance"])) <= 2e-4 + 1e-6 * float(b["distance"]), (i, a, b)
+                assert np.abs(a["normal"] - b["normal"]).max() <= 1e-4 and np.abs(a["point"] - b["point"]).max() <= 2e-4 + 1e-6 * n
+                checked += 1
+            print("r = 0 against raycast, two_sided %d: %d rays, %d checked, %d ambiguous" % (two_sided, len(O), checked, n_amb))
+            assert checked > len(O) // 3
+
+
+@pytest.mark.gpu
+def test_monotone_in_radius_and_the_two_queries_agree():
+    """The same sweeps at r = 0.25, 1, 3 give non-increasing distances; every two-sided hit at t > 0 has a closest point at distance r
+    (within 2e-4 cells) from its centre at contact."""
+    import volumetricterrain_amd as vt
+    n = 64
+    rng = np.random.default_rng(8)
+    with vt.Extractor(0) as ex:
+        g, st = _perlin(vt, ex, (n, n, n))
+        o, d, _ = _sweeps((n, n, n), 2048, rng, 1.0)
+        o, d = np.float32(o).astype(np.float64), np.float32(d).astype(np.float64)   # what the kernel sees
+        prev = None
+        for r in (0.25, 1.0, 3.0):
+            hits = _cast(ex, g.data_ptr(), (n, n, n), st, (0.0, 0.0, 0.0), 1.0, o, d, r, two_sided=True)
+            t = np.where(hits["triangle"] >= 0, hits["distance"].astype(np.float64), np.inf)
+            if prev is not None:
+                assert (t <= prev + 1e-6).all(), np.nonzero(t > prev + 1e-6)
+            prev = t
+            sel = np.nonzero((hits["triangle"] >= 0) & (hits["distance"] > 0))[0]
+            assert len(sel) > 500
+            dn = d[sel] / np.linalg.norm(d[sel], axis=1)[:, None]
+            c = (o[sel] + hits["distance"][sel, None].astype(np.float64) * dn).astype(np.float32)
+            ch = _closest(ex, g.data_ptr(), (n, n, n), st, (0.0, 0.0, 0.0), 1.0, c, r * (1 + 1e-4))
+            miss = np.nonzero(ch["triangle"] < 0)[0]
+            assert not len(miss), (r, len(miss), len(sel), hits[sel[miss[:4]]], c[miss[:4]], o[sel[miss[:4]]], d[sel[miss[:4]]])
+            np.testing.assert_allclose(ch["distance"], r, atol=2e-4)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(64, 64, 64), (40, 16, 72)])
+def test_random_sweeps_and_balls_against_the_reference(oracle_mod, shape):
+    """Seeded sweeps and balls with r in [0, 8] cells on a perlin grid (cubic, and non-cubic at voxel_scale 0.5 off the origin),
+    single- and two-sided, against the CPU reference."""
+    import volumetricterrain_amd as vt
+    scale, org = (1.0, (0.0, 0.0, 0.0)) if shape[0] == 64 else (0.5, (3.25, -7.5, 1.0))
+    rng = np.random.default_rng(sum(shape))
+    with vt.Extractor(0) as ex:
+        g, st = _perlin(vt, ex, shape)
+        dims = tuple(x + 2 for x in shape)
+        grid = g.cpu().numpy().reshape(dims[2], dims[1], dims[0]).transpose(2, 1, 0)
+        surf = SphereSurface(oracle_mod, grid, org, scale)
+        o, d, r = _sweeps(shape, 600, rng, 8.0)
+        ow = (np.float32(org) + o * scale).astype(np.float32)
+        rw = (r * scale).astype(np.float32)
+        for two_sided in (False, True):
+            hits = _cast(ex, g.data_ptr(), shape, st, org, scale, ow, d, rw, two_sided=two_sided)
+            ref = [surf.cast(a, b, float(c), two_sided=two_sided) for a, b, c in zip(ow.astype(np.float64), np.float32(d), rw)]
+            check(hits, ref, scale, "sweeps %s two_sided %d" % (shape, two_sided))
+            assert (hits["triangle"] >= 0).sum() > len(o) // 3
+        c = (np.float32(org) + rng.uniform(0, 1, (600, 3)) * np.asarray(shape) * scale).astype(np.float32)
+        rc = (rng.uniform(0, 8, 600) * scale).astype(np.float32)
+        ch = _closest(ex, g.data_ptr(), shape, st, org, scale, c, rc)
+        check(ch, [surf.closest(a, float(b)) for a, b in zip(c.astype(np.float64), rc)], scale, "balls %s" % (shape,))
+        assert (ch["triangle"] >= 0).sum() > 100
+
+
+@pytest.mark.gpu
+def test_layouts_and_repeats_give_identical_records():
+    """x-fastest and z-fastest copies of one grid, and a repeated call: byte-identical records."""
+    import volumetricterrain_amd as vt
+    shape = (48, 32, 40)
+    rng = np.random.default_rng(12)
+    with vt.Extractor(0) as ex:
+        gx, sx = _perlin(vt, ex, shape, "x")
+        gz, sz = _perlin(vt, ex, shape, "z")
+        o, d, r = _sweeps(shape, 1024, rng, 6.0)
+        c = rng.uniform(0, 1, (1024, 3)) * shape
+        a = _cast(ex, gx.data_ptr(), shape, sx, (0.0, 0.0, 0.0), 1.0, o, d, r)
+        b = _cast(ex, gz.data_ptr(), shape, sz, (0.0, 0.0, 0.0), 1.0, o, d, r)
+        a2 = _cast(ex, gx.data_ptr(), shape, sx, (0.0, 0.0, 0.0), 1.0, o, d, r)
+        assert a.tobytes() == b.tobytes() == a2.tobytes()
+        assert (a["triangle"] >= 0).sum() > 300
+        a = _closest(ex, gx.data_ptr(), shape, sx, (0.0, 0.0, 0.0), 1.0, c, r)
+        b = _closest(ex, gz.data_ptr(), shape, sz, (0.0, 0.0, 0.0), 1.0, c, r)
+        a2 = _closest(ex, gx.data_ptr(), shape, sx, (0.0, 0.0, 0.0), 1.0, c, r)
+        assert a.tobytes() == b.tobytes() == a2.tobytes()
+        assert (a["triangle"] >= 0).sum() > 100
+
+
+@pytest.mark.gpu
+def test_resident_terrain_follows_its_edits(oracle_mod):
+    """terrain_init, then a plane, a sphere edit, a smooth brush and an undo: after each, both queries answer for the current grid."""
+    import volumetricterrain_amd as vt
+    rng = np.random.default_rng(14)
+    k = 256
+    o = np.stack([rng.uniform(4, 60, k), np.full(k, 44.0), rng.uniform(4, 60, k)], 1)
+    d = np.stack([rng.uniform(-0.3, 0.3, k), -np.ones(k), rng.uniform(-0.3, 0.3, k)], 1)
+    r = rng.uniform(0, 3, k)
+    c = np.stack([rng.uniform(4, 60, k), rng.uniform(10, 30, k), rng.uniform(4, 60, k)], 1)
+    with vt.Extractor(0) as ex:
+        ex.terrain_init(64, 48, 64, 1.0, (0.0, 0.0, 0.0), 1)
+        ex.terrain_set_history(64 << 20)
+        steps = [[vt.PlaneModifier(20.5, (-1, -1), (80, 80), True)], [vt.SphereModifier((32.0, 20.0, 32.0), 12.0, True)],
+                 [vt.SmoothModifier((30.0, 26.0, 30.0), 10.0, 1.0)], "undo"]
+        seen = []
+        for step in steps:
+            if step == "undo":
+                ex.terrain_undo()
+            else:
+                ex.terrain_update(step)
+            surf = SphereSurface(oracle_mod, ex.terrain_read_samples())
+            hits = ex.terrain_spherecast(o, d, r)
+            check(hits, [surf.cast(a, b, float(x)) for a, b, x in zip(np.float32(o), np.float32(d), np.float32(r))], 1.0, "terrain %s" % step)
+            ch = ex.terrain_closest_point(c, 6.0)
+            check(ch, [surf.closest(a, 6.0) for a in np.float32(c)], 1.0, "terrain closest %s" % step)
+            seen.append(hits["distance"].copy())
+        assert not np.array_equal(seen[0], seen[1]) and not np.array_equal(seen[1], seen[2])
+        assert np.array_equal(seen[1], seen[3])   # the undo took the brush back
+
+
+@pytest.mark.gpu
+def test_limits(oracle_mod):
+    """The largest radius, a start inside the surface, sweeps from outside the grid, NaN samples and max_distance around a contact."""
+    import volumetricterrain_amd as vt
+    shape = (32, 32, 32)
+    rng = np.random.default_rng(15)
+    with vt.Extractor(0) as ex:
+        grid = fields.sphere(shape, (16.3, 15.7, 16.1), 9.5)
+        dg = DeviceGrid(grid)
+        surf = SphereSurface(oracle_mod, grid)
+        z = (0.0, 0.0, 0.0)
+        # radius exactly VTMC_SPHERE_MAX_RADIUS_CELLS (voxel_scale 1), from far outside the grid
+        u = rng.normal(size=(64, 3))
+        u /= np.linalg.norm(u, axis=1)[:, None]
+        o = np.array([16.3, 15.7, 16.1]) + 60.0 * u
+        hits = _cast(ex, dg.ptr, dg.n, dg.strides, z, 1.0, o, -u, 16.0)
+        check(hits, [surf.cast(a, -b, 16.0) for a, b in zip(np.float32(o), np.float32(u))], 1.0, "r = 16")
+        np.testing.assert_allclose(hits["distance"], 60.0 - 9.5 - 16.0, atol=0.1)
+        ch = _closest(ex, dg.ptr, dg.n, dg.strides, z, 1.0, np.float32(o * 0.3 + 16 * 0.7), 16.0)
+        assert (ch["triangle"] >= 0).all()
+        # a start inside the surface, touching it: t = 0, two-sided and single-sided from outside
+        on = np.array([16.3, 15.7, 16.1]) + 9.5 * u
+        hits = _cast(ex, dg.ptr, dg.n, dg.strides, z, 1.0, on + 0.2 * u, u, 0.5, two_sided=True)
+        assert (hits["distance"] == 0).all() and (hits["triangle"] >= 0).all()
+        check(hits, [surf.cast(a, b, 0.5, two_sided=True) for a, b in zip(np.float32(on + 0.2 * u), np.float32(u))], 1.0, "start inside")
+        hits = _cast(ex, dg.ptr, dg.n, dg.strides, z, 1.0, on + 0.2 * u, -u, 0.5)
+        assert (hits["distance"] == 0).all()
+        # sweeps that start outside the grid and miss it, or pass it by
+        far = _cast(ex, dg.ptr, dg.n, dg.strides, z, 1.0, np.float32([[-40, 16, 16], [16, 80, 16], [-40, 16, 16]]),
+                    np.float32([[-1, 0, 0], [0, 1, 0], [0, 1, 0]]), 3.0)
+        assert (far["triangle"] < 0).all() and (far["distance"] == -1).all()
+        # max_distance just before and just after the contact
+        o1 = np.float32([[16.3, 40.0, 16.1]])
+        d1 = np.float32([[0, -1, 0]])
+        t = float(_cast(ex, dg.ptr, dg.n, dg.strides, z, 1.0, o1, d1, 1.5)["distance"][0])
+        assert t > 0
+        assert _cast(ex, dg.ptr, dg.n, dg.strides, z, 1.0, o1, d1, 1.5, max_distance=float(np.nextafter(np.float32(t), np.float32(0))))["triangle"][0] < 0
+        assert _cast(ex, dg.ptr, dg.n, dg.strides, z, 1.0, o1, d1, 1.5, max_distance=t)["distance"][0] == t
+        assert _cast(ex, dg.ptr, dg.n, dg.strides, z, 1.0, o1, d1, 1.5, max_distance=t * 1.01)["distance"][0] == t
+        # degenerate queries are misses
+        bad = _cast(ex, dg.ptr, dg.n, dg.strides, z, 1.0, np.float32([[np.nan, 1, 1], [16, 40, 16], [16, 40, 16]]),
+                    np.float32([[0, -1, 0], [0, 0, 0], [np.inf, -1, 0]]), 1.0)
+        assert (bad["triangle"] < 0).all()
+        # NaN samples: no NaN in any record, and the answers are the reference's, which drops every cell with a NaN corner
+        gn = grid.copy()
+        gn[rng.integers(0, 34, 400), rng.integers(0, 34, 400), rng.integers(0, 34, 400)] = np.nan
+        dn = DeviceGrid(gn)
+        sn = SphereSurface(oracle_mod, grid, nan_grid=gn)
+        o, d, r = _sweeps(shape, 512, rng, 4.0)
+        hits = _cast(ex, dn.ptr, dn.n, dn.strides, z, 1.0, o, d, r, two_sided=True)
+        assert np.isfinite(hits["distance"]).all() and np.isfinite(hits["point"]).all() and np.isfinite(hits["normal"]).all()
+        check(hits, [sn.cast(a, b, float(c), two_sided=True) for a, b, c in zip(np.float32(o), np.float32(d), np.float32(r))], 1.0, "NaN")
+        cc = rng.uniform(0, 32, (512, 3))
+        ch = _closest(ex, dn.ptr, dn.n, dn.strides, z, 1.0, cc, r)
+        check(ch, [sn.closest(a, float(b)) for a, b in zip(np.float32(cc), np.float32(r))], 1.0, "NaN closest")
+
+
+@pytest.mark.gpu
+def test_far_corner_of_a_1024_cube_z_fastest():
+    """A 1024^3 perlin grid stored z fastest (its far corner lies past 2^31 elements): sweeps and balls near the far corner answer as
+    on a 64^3 window of the same field cut out around them."""
+    import torch
+    import volumetricterrain_amd as vt
+    n, dim = 1024, 1026
+    rng = np.random.default_rng(16)
+    with vt.Extractor(0) as ex:
+        prm = vt.density_params("perlin3d", n)
+        g = torch.empty(dim ** 3, dtype=torch.float32, device="cuda")
+        ex.density_fill_device(prm, [[0, 0, 0]], (dim, dim, dim), (dim * dim, dim, 1), 0, g.data_ptr())
+        lo = 960   # the window [960, 1024]^3 cells
+        w = g.view(dim, dim, dim)[lo:, lo:, lo:].contiguous()   # [x, y, z], z fastest
+        o = lo + rng.uniform(8, 56, (256, 3))
+        d = rng.normal(size=(256, 3))
+        r = rng.uniform(0, 6, 256)
+        full = _cast(ex, g.data_ptr(), (n, n, n), (dim * dim, dim, 1), (0.0, 0.0, 0.0), 1.0, o, d, r, max_distance=6.0, two_sided=True)
+        win = _cast(ex, w.data_ptr(), (64, 64, 64), (66 * 66, 66, 1), (float(lo),) * 3, 1.0, o, d, r, max_distance=6.0, two_sided=True)
+        hit = full["triangle"] >= 0
+        assert hit.sum() > 50
+        assert np.array_equal(hit, win["triangle"] >= 0)
+        np.testing.assert_allclose(full["distance"][hit], win["distance"][hit], atol=1e-4)
+        np.testing.assert_allclose(full["point"][hit], win["point"][hit], atol=2e-4)
+        np.testing.assert_array_equal(full["block"][hit], win["block"][hit] + lo // 8)
+        c = lo + rng.uniform(8, 56, (256, 3))
+        full = _closest(ex, g.data_ptr(), (n, n, n), (dim * dim, dim, 1), (0.0, 0.0, 0.0), 1.0, c, r)
+        win = _closest(ex, w.data_ptr(), (64, 64, 64), (66 * 66, 66, 1), (float(lo),) * 3, 1.0, c, r)
+        hit = full["triangle"] >= 0
+        assert hit.sum() > 20 and np.array_equal(hit, win["triangle"] >= 0)
+        np.testing.assert_allclose(full["distance"][hit], win["distance"][hit], atol=1e-4)
+        np.testing.assert_array_equal(full["cell"][hit], win["cell"][hit])
+        del g, w

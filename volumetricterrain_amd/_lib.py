@@ -24,6 +24,11 @@ RAY_HIT_DTYPE = np.dtype([("distance", "<f4"), ("point", "<f4", 3), ("normal", "
                           ("block", "<i4", 3), ("cell", "<i4"), ("triangle", "<i4")])
 assert RAY_HIT_DTYPE.itemsize == 56
 RAY_TWO_SIDED = 1
+# vtmc_sphere_hit: one answer of vtmc_terrain_spherecast / _closest_point and their _device forms
+SPHERE_HIT_DTYPE = np.dtype([("distance", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3), ("block", "<i4", 3), ("cell", "<i4"),
+                             ("triangle", "<i4")])
+assert SPHERE_HIT_DTYPE.itemsize == 48
+SPHERE_MAX_RADIUS_CELLS = 16
 OUTPUT_SOUP, OUTPUT_INDEXED = 0, 1
 
 OK = 0
@@ -44,6 +49,7 @@ SYMBOLS = [
     "vtmc_extract_volumes_device_async", "vtmc_extract_finish", "vtmc_last_fill_ms", "vtmc_context_stream", "vtmc_release_streams", "vtmc_last_placement",
     "vtmc_terrain_raycast", "vtmc_raycast_device",
     "vtmc_terrain_set_history", "vtmc_terrain_undo", "vtmc_terrain_redo", "vtmc_terrain_history",
+    "vtmc_terrain_spherecast", "vtmc_terrain_closest_point", "vtmc_spherecast_device", "vtmc_closest_point_device",
 ]
 COMM_ID_BYTES = 128
 
@@ -157,6 +163,13 @@ def load(path=None):
         L.vtmc_terrain_raycast.argtypes = [vp, vp, vp, i32, ctypes.c_float, u32, vp]
         L.vtmc_raycast_device.argtypes = [vp, vp, i32, i32, i32, i64, i64, i64, P(ctypes.c_float * 3), ctypes.c_float,
                                           vp, vp, i32, ctypes.c_float, u32, vp, vp]
+    if not explicit or hasattr(L, "vtmc_terrain_spherecast"):
+        L.vtmc_terrain_spherecast.argtypes = [vp, vp, vp, vp, i32, ctypes.c_float, u32, vp]
+        L.vtmc_terrain_closest_point.argtypes = [vp, vp, vp, i32, u32, vp]
+        L.vtmc_spherecast_device.argtypes = [vp, vp, i32, i32, i32, i64, i64, i64, P(ctypes.c_float * 3), ctypes.c_float,
+                                             vp, vp, vp, i32, ctypes.c_float, u32, vp, vp]
+        L.vtmc_closest_point_device.argtypes = [vp, vp, i32, i32, i32, i64, i64, i64, P(ctypes.c_float * 3), ctypes.c_float,
+                                                vp, vp, i32, u32, vp, vp]
     L.vtmc_comm_unique_id.argtypes = [vp]
     L.vtmc_comm_init_rank.argtypes = [vp, vp, i32, i32]
     L.vtmc_comm_destroy.argtypes = [vp]

@@ -1,0 +1,135 @@
+// mc_cell.h -- one cell's marching-cubes triangles rebuilt from its eight samples, and the watertight ray / triangle test, shared by
+// the surface queries (raycast.hip, spherequery.hip) so both see the same triangles bit for bit (gfx950, wave64).
+//
+// The arithmetic is the exact-mode emit's (CollectTriNum.compute:41-64 case, MarchingCube.compute:119-151 vertices and winding): the
+// library is built with -ffp-contract=off and `/` is correctly rounded, so a rebuilt triangle equals the extracted one.  The case table
+// (DeviceTables::vert_packed, 256 words of 5 x 12 bits) is read from LDS: each kernel copies it there with load_case_table.
+#ifndef VTMC_MC_CELL_H
+#define VTMC_MC_CELL_H
+#include <cmath>
+
+namespace vtmc {
+
+// cube corner c of MarchingCube.compute:46-50 ({0,0,0},{1,0,0},{1,1,0},{0,1,0},{0,0,1},{1,0,1},{1,1,1},{0,1,1}) along each axis
+__device__ __forceinline__ int corner_x(int c) { return (c ^ (c >> 1)) & 1; }
+__device__ __forceinline__ int corner_y(int c) { return (c >> 1) & 1; }
+__device__ __forceinline__ int corner_z(int c) { return (c >> 2) & 1; }
+// endpoints of cube edge e, MarchingCube.compute:40-43 ({0,1},{1,2},{2,3},{3,0},{4,5},{5,6},{6,7},{7,4},{0,4},{1,5},{2,6},{3,7})
+__device__ __forceinline__ int edge_a(int e) { return e < 8 ? e : e - 8; }
+__device__ __forceinline__ int edge_b(int e) { return e < 8 ? (e & 4) | ((e + 1) & 3) : e - 4; }
+
+// s[i] for a runtime i as a tree of selects on i's bits: a runtime index into a register array (or a chain of i == q
+// selects, which the compiler folds back into one) puts the array in scratch
+__device__ __forceinline__ float pick8(const float (&s)[8], int i)
+{
+    const bool b0 = i & 1, b1 = i & 2, b2 = i & 4;
+    const float s01 = b0 ? s[1] : s[0], s23 = b0 ? s[3] : s[2], s45 = b0 ? s[5] : s[4], s67 = b0 ? s[7] : s[6];
+    const float s03 = b1 ? s23 : s01, s47 = b1 ? s67 : s45;
+    return b2 ? s47 : s03;
+}
+__device__ __forceinline__ double pick3(double x, double y, double z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
+
+// Block-local position of the vertex on cube edge e of the cell with block-local corner (lx, ly, lz): MarchingCube.compute:119-133
+// as the exact-mode emit and the oracle evaluate it -- t = -a / (b - a), p = u + t * (v - u), endpoints in the reference's order.
+__device__ __forceinline__ void edge_vertex(const float (&s)[8], int lx, int ly, int lz, int e, float p[3])
+{
+    const int a = edge_a(e), b = edge_b(e);
+    const float va = pick8(s, a), vb = pick8(s, b);
+    const float t = (-va) / (vb - va);
+    const int l[3] = {lx, ly, lz};
+    const int oa[3] = {corner_x(a), corner_y(a), corner_z(a)}, ob[3] = {corner_x(b), corner_y(b), corner_z(b)};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float u = (float)l[k] + (float)oa[k];
+        const float v = (float)l[k] + (float)ob[k];
+        p[k] = u + t * (v - u);
+    }
+}
+
+// the case table in LDS: one word per thread of a 256-thread workgroup (the caller's next barrier publishes it)
+__device__ __forceinline__ void load_case_table(unsigned long long *s_cases, const unsigned long long *vert_packed, int tid)
+{
+    s_cases[tid] = vert_packed[tid];
+}
+
+// CollectTriNum.compute:41-51: strict '>', NaN is outside; 0 and 255 are the two cases without triangles
+__device__ __forceinline__ unsigned cell_case(const float (&s)[8])
+{
+    unsigned cs = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) cs |= (unsigned)(s[q] > 0.f) << q;
+    return cs;
+}
+
+// Triangle i of the cell with global corner (cx, cy, cz) whose case word is w: its vertices in grid units, exact (8b + p), wound as
+// the emit writes them (MarchingCube.compute:151 swaps the last two).  False when the case has fewer than i + 1 triangles.
+__device__ __forceinline__ bool cell_triangle(unsigned long long w, const float (&s)[8], int cx, int cy, int cz, int i, double P0[3],
+                                              double P1[3], double P2[3])
+{
+    const int e0 = (int)(w >> (12 * i)) & 15, e1 = (int)(w >> (12 * i + 4)) & 15, e2 = (int)(w >> (12 * i + 8)) & 15;
+    if (e0 == 15) return false;  // MarchingCube.compute:141
+    const int lx = cx & 7, ly = cy & 7, lz = cz & 7;
+    const double bx = (double)(cx - lx), by = (double)(cy - ly), bz = (double)(cz - lz);
+    float p0[3], p1[3], p2[3];
+    edge_vertex(s, lx, ly, lz, e0, p0);
+    edge_vertex(s, lx, ly, lz, e2, p1);  // winding swap, MarchingCube.compute:151
+    edge_vertex(s, lx, ly, lz, e1, p2);
+    P0[0] = bx + p0[0], P0[1] = by + p0[1], P0[2] = bz + p0[2];
+    P1[0] = bx + p1[0], P1[1] = by + p1[1], P1[2] = bz + p1[2];
+    P2[0] = bx + p2[0], P2[1] = by + p2[1], P2[2] = bz + p2[2];
+    return true;
+}
+
+// A ray for the watertight test (Woop, Benthin & Wald 2013): origin and direction in grid units, the axis permutation and the shear.
+struct Ray {
+    double o[3], d[3];
+    int kx, ky, kz;
+    double Sx, Sy, Sz;
+};
+
+// the permutation and shear of r.d (r.d non-zero)
+__device__ __forceinline__ void ray_setup(Ray &r)
+{
+    const double ad[3] = {fabs(r.d[0]), fabs(r.d[1]), fabs(r.d[2])};
+    r.kz = ad[0] >= ad[1] && ad[0] >= ad[2] ? 0 : (ad[1] >= ad[2] ? 1 : 2);
+    r.kx = r.kz == 2 ? 0 : r.kz + 1;
+    r.ky = r.kx == 2 ? 0 : r.kx + 1;
+    const double dkz = pick3(r.d[0], r.d[1], r.d[2], r.kz);
+    if (dkz < 0.0) {
+        const int x = r.kx;
+        r.kx = r.ky;
+        r.ky = x;
+    }
+    r.Sx = pick3(r.d[0], r.d[1], r.d[2], r.kx) / dkz;
+    r.Sy = pick3(r.d[0], r.d[1], r.d[2], r.ky) / dkz;
+    r.Sz = 1.0 / dkz;
+}
+
+// The watertight test of the ray against triangle (P0, P1, P2): false on a miss or an edge-on triangle; else t (in the units of
+// r.d's parameter) and the barycentric weights V / det, W / det of P1 and P2.
+__device__ __forceinline__ bool ray_triangle(const Ray &r, const double P0[3], const double P1[3], const double P2[3], double &t, double &V,
+                                             double &W, double &det)
+{
+    const double Ax0 = P0[0] - r.o[0], Ay0 = P0[1] - r.o[1], Az0 = P0[2] - r.o[2];
+    const double Bx0 = P1[0] - r.o[0], By0 = P1[1] - r.o[1], Bz0 = P1[2] - r.o[2];
+    const double Cx0 = P2[0] - r.o[0], Cy0 = P2[1] - r.o[1], Cz0 = P2[2] - r.o[2];
+    const double Akz = pick3(Ax0, Ay0, Az0, r.kz), Bkz = pick3(Bx0, By0, Bz0, r.kz), Ckz = pick3(Cx0, Cy0, Cz0, r.kz);
+    const double Ax = pick3(Ax0, Ay0, Az0, r.kx) - r.Sx * Akz, Ay = pick3(Ax0, Ay0, Az0, r.ky) - r.Sy * Akz;
+    const double Bx = pick3(Bx0, By0, Bz0, r.kx) - r.Sx * Bkz, By = pick3(Bx0, By0, Bz0, r.ky) - r.Sy * Bkz;
+    const double Cx = pick3(Cx0, Cy0, Cz0, r.kx) - r.Sx * Ckz, Cy = pick3(Cx0, Cy0, Cz0, r.ky) - r.Sy * Ckz;
+    const double U = Cx * By - Cy * Bx;
+    V = Ax * Cy - Ay * Cx;
+    W = Bx * Ay - By * Ax;
+    if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) return false;
+    det = U + V + W;
+    if (det == 0.0) return false;
+    const double T = U * (r.Sz * Akz) + V * (r.Sz * Bkz) + W * (r.Sz * Ckz);
+    t = T / det;
+    return true;
+}
+
+__device__ __forceinline__ bool finite3(const float *v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
+
+}  // namespace vtmc
+
+#endif

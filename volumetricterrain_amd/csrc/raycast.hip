@@ -18,6 +18,7 @@
 // two triangles sharing an edge cannot both miss a ray crossing it.  Everything after the vertex positions is float64: the
 // ray transform is the same for every triangle, and nothing depends on the grid's layout or on which lane tested a cell.
 #include "vtmc_ctx.h"
+#include "mc_cell.h"
 #include <cmath>
 #include <cstring>
 
@@ -41,48 +42,6 @@ struct RaycastArgs {
     const unsigned long long *vert_packed;  // DeviceTables::vert_packed
 };
 
-// cube corner c of MarchingCube.compute:46-50 ({0,0,0},{1,0,0},{1,1,0},{0,1,0},{0,0,1},{1,0,1},{1,1,1},{0,1,1}) along each axis
-__device__ __forceinline__ int corner_x(int c) { return (c ^ (c >> 1)) & 1; }
-__device__ __forceinline__ int corner_y(int c) { return (c >> 1) & 1; }
-__device__ __forceinline__ int corner_z(int c) { return (c >> 2) & 1; }
-// endpoints of cube edge e, MarchingCube.compute:40-43 ({0,1},{1,2},{2,3},{3,0},{4,5},{5,6},{6,7},{7,4},{0,4},{1,5},{2,6},{3,7})
-__device__ __forceinline__ int edge_a(int e) { return e < 8 ? e : e - 8; }
-__device__ __forceinline__ int edge_b(int e) { return e < 8 ? (e & 4) | ((e + 1) & 3) : e - 4; }
-
-// s[i] for a runtime i as a tree of selects on i's bits: a runtime index into a register array (or a chain of i == q
-// selects, which the compiler folds back into one) puts the array in scratch
-__device__ __forceinline__ float pick8(const float (&s)[8], int i)
-{
-    const bool b0 = i & 1, b1 = i & 2, b2 = i & 4;
-    const float s01 = b0 ? s[1] : s[0], s23 = b0 ? s[3] : s[2], s45 = b0 ? s[5] : s[4], s67 = b0 ? s[7] : s[6];
-    const float s03 = b1 ? s23 : s01, s47 = b1 ? s67 : s45;
-    return b2 ? s47 : s03;
-}
-__device__ __forceinline__ double pick3(double x, double y, double z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
-
-// Block-local position of the vertex on cube edge e of the cell with block-local corner (lx, ly, lz): MarchingCube.compute:119-133
-// as the exact-mode emit and the oracle evaluate it -- t = -a / (b - a), p = u + t * (v - u), endpoints in the reference's order.
-__device__ __forceinline__ void edge_vertex(const float (&s)[8], int lx, int ly, int lz, int e, float p[3])
-{
-    const int a = edge_a(e), b = edge_b(e);
-    const float va = pick8(s, a), vb = pick8(s, b);
-    const float t = (-va) / (vb - va);
-    const int l[3] = {lx, ly, lz};
-    const int oa[3] = {corner_x(a), corner_y(a), corner_z(a)}, ob[3] = {corner_x(b), corner_y(b), corner_z(b)};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float u = (float)l[k] + (float)oa[k];
-        const float v = (float)l[k] + (float)ob[k];
-        p[k] = u + t * (v - u);
-    }
-}
-
-struct Ray {
-    double o[3], d[3];  // grid units; d = unit world direction / voxel_scale, so the parameter is the world distance
-    int kx, ky, kz;     // Woop's axis permutation
-    double Sx, Sy, Sz;  // ... and shear
-};
-
 struct Best {
     double t = INFINITY;
     float u = 0.f, v = 0.f, nrm[3] = {0.f, 0.f, 0.f};
@@ -94,44 +53,21 @@ struct Best {
 __device__ __forceinline__ void intersect_cell(const RaycastArgs &a, const unsigned long long *s_cases, const Ray &r, const float (&s)[8], int cx, int cy,
                                                int cz, Best &best)
 {
-    unsigned cs = 0;  // CollectTriNum.compute:41-51: strict '>', NaN is outside
-#pragma unroll
-    for (int q = 0; q < 8; ++q) cs |= (unsigned)(s[q] > 0.f) << q;
+    const unsigned cs = cell_case(s);
     if (cs == 0u || cs == 255u) return;  // the two cases without triangles (edge mask 0)
     const unsigned long long w = s_cases[cs];
-    const int lx = cx & 7, ly = cy & 7, lz = cz & 7;
-    const double bx = (double)(cx - lx), by = (double)(cy - ly), bz = (double)(cz - lz);
+#pragma unroll 1
     for (int i = 0; i < 5; ++i) {
-        const int e0 = (int)(w >> (12 * i)) & 15, e1 = (int)(w >> (12 * i + 4)) & 15, e2 = (int)(w >> (12 * i + 8)) & 15;
-        if (e0 == 15) continue;  // MarchingCube.compute:141
-        float p0[3], p1[3], p2[3];
-        edge_vertex(s, lx, ly, lz, e0, p0);
-        edge_vertex(s, lx, ly, lz, e2, p1);  // winding swap, MarchingCube.compute:151
-        edge_vertex(s, lx, ly, lz, e1, p2);
-        // grid units, exact: 8b + p
-        const double P0[3] = {bx + p0[0], by + p0[1], bz + p0[2]};
-        const double P1[3] = {bx + p1[0], by + p1[1], bz + p1[2]};
-        const double P2[3] = {bx + p2[0], by + p2[1], bz + p2[2]};
+        double P0[3], P1[3], P2[3];
+        if (!cell_triangle(w, s, cx, cy, cz, i, P0, P1, P2)) continue;
         const double e1x = P1[0] - P0[0], e1y = P1[1] - P0[1], e1z = P1[2] - P0[2];
         const double e2x = P2[0] - P0[0], e2y = P2[1] - P0[1], e2z = P2[2] - P0[2];
         const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
         const double nn = nx * nx + ny * ny + nz * nz;
         if (!(nn > 0.0)) continue;  // zero area, or a NaN sample on the way
         if (!a.two_sided && !(nx * r.d[0] + ny * r.d[1] + nz * r.d[2] < 0.0)) continue;  // single-sided: the face must look at the ray
-        // Woop, Benthin & Wald 2013
-        const double Ax0 = P0[0] - r.o[0], Ay0 = P0[1] - r.o[1], Az0 = P0[2] - r.o[2];
-        const double Bx0 = P1[0] - r.o[0], By0 = P1[1] - r.o[1], Bz0 = P1[2] - r.o[2];
-        const double Cx0 = P2[0] - r.o[0], Cy0 = P2[1] - r.o[1], Cz0 = P2[2] - r.o[2];
-        const double Akz = pick3(Ax0, Ay0, Az0, r.kz), Bkz = pick3(Bx0, By0, Bz0, r.kz), Ckz = pick3(Cx0, Cy0, Cz0, r.kz);
-        const double Ax = pick3(Ax0, Ay0, Az0, r.kx) - r.Sx * Akz, Ay = pick3(Ax0, Ay0, Az0, r.ky) - r.Sy * Akz;
-        const double Bx = pick3(Bx0, By0, Bz0, r.kx) - r.Sx * Bkz, By = pick3(Bx0, By0, Bz0, r.ky) - r.Sy * Bkz;
-        const double Cx = pick3(Cx0, Cy0, Cz0, r.kx) - r.Sx * Ckz, Cy = pick3(Cx0, Cy0, Cz0, r.ky) - r.Sy * Ckz;
-        const double U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
-        if ((U < 0.0 || V < 0.0 || W < 0.0) && (U > 0.0 || V > 0.0 || W > 0.0)) continue;
-        const double det = U + V + W;
-        if (det == 0.0) continue;
-        const double T = U * (r.Sz * Akz) + V * (r.Sz * Bkz) + W * (r.Sz * Ckz);
-        const double t = T / det;
+        double t, V, W, det;
+        if (!ray_triangle(r, P0, P1, P2, t, V, W, det)) continue;
         if (!(t >= 0.0) || !((float)t <= a.max_distance) || !(t < best.t)) continue;
         const double inv = 1.0 / sqrt(nn);
         best.t = t;
@@ -147,8 +83,6 @@ __device__ __forceinline__ void intersect_cell(const RaycastArgs &a, const unsig
     }
 }
 
-__device__ __forceinline__ bool finite3(const float *v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
-
 __global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
 {
     static_assert(kRayThreads == 256, "one table word per thread");
@@ -157,11 +91,11 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
     __shared__ double s_t[kWaves];
     __shared__ int s_lane[kWaves];
     const int ray = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    s_cases[tid] = a.vert_packed[tid];
+    load_case_table(s_cases, a.vert_packed, tid);
     const float o[3] = {a.ro[3ll * ray], a.ro[3ll * ray + 1], a.ro[3ll * ray + 2]};
     const float d[3] = {a.rd[3ll * ray], a.rd[3ll * ray + 1], a.rd[3ll * ray + 2]};
 
-    Ray r;
+    Ray r;  // grid units; d = unit world direction / voxel_scale, so the parameter is the world distance
     double dn[3] = {0.0, 0.0, 0.0};
     bool ok = finite3(o) && finite3(d);
     double t_in = 0.0, t_out = -1.0;
@@ -195,19 +129,7 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
     int c[3] = {0, 0, 0}, step[3] = {0, 0, 0};
     double tmax[3] = {INFINITY, INFINITY, INFINITY}, inv[3] = {0.0, 0.0, 0.0}, tb = 0.0;
     if (ok) {
-        const double ad[3] = {fabs(r.d[0]), fabs(r.d[1]), fabs(r.d[2])};
-        r.kz = ad[0] >= ad[1] && ad[0] >= ad[2] ? 0 : (ad[1] >= ad[2] ? 1 : 2);
-        r.kx = r.kz == 2 ? 0 : r.kz + 1;
-        r.ky = r.kx == 2 ? 0 : r.kx + 1;
-        const double dkz = pick3(r.d[0], r.d[1], r.d[2], r.kz);
-        if (dkz < 0.0) {
-            const int x = r.kx;
-            r.kx = r.ky;
-            r.ky = x;
-        }
-        r.Sx = pick3(r.d[0], r.d[1], r.d[2], r.kx) / dkz;
-        r.Sy = pick3(r.d[0], r.d[1], r.d[2], r.ky) / dkz;
-        r.Sz = 1.0 / dkz;
+        ray_setup(r);
         // this lane's sub-interval [ta, tb] and the cell it starts in
         const double span = t_out - t_in;
         const double ta = t_in + span * ((double)tid / kRayThreads);

@@ -128,7 +128,7 @@ struct vtmc_ctx {
     // terrain.hip: the stage of a VTMC_MOD_SMOOTH brush (its box plus a one-sample halo, before the brush), grow-only; grown only after
     // the stream has drained, since an earlier smooth of the same queue may still be reading it
     VtmcDevBuf brush;
-    // raycast.hip: the rays and hits of vtmc_terrain_raycast (device, then their pinned staging)
+    // raycast.hip, spherequery.hip: the queries and hits of vtmc_terrain_raycast / _spherecast / _closest_point (device, then their pinned staging)
     VtmcDevBuf rays;
     VtmcPinnedBuf<unsigned char> h_rays;
     uint64_t perm_seed = 0;

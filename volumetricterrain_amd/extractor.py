@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, RAY_HIT_DTYPE, RAY_TWO_SIDED, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from ._lib import COMM_ID_BYTES, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
 
 
 def _ptr(a):
@@ -337,6 +337,48 @@ class Extractor:
         self._check(self._L.vtmc_raycast_device(self._h, d_grid, n[0], n[1], n[2], strides[0], strides[1], strides[2], ctypes.byref(org),
                                                 voxel_scale, d_origins, d_directions, n_rays, max_distance,
                                                 RAY_TWO_SIDED if two_sided else 0, d_hits, stream))
+
+    # -- sphere queries: Physics.SphereCast / CheckSphere / ClosestPoint against the MeshColliders (VoxelTerrain.cs:168, 464) -------
+    @staticmethod
+    def _radii(radii, n):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(radii, np.float32), (n,)))   # a scalar, or one value per query
+
+    def terrain_spherecast(self, origins, directions, radii, max_distance=float("inf"), two_sided=False):
+        """First contact of each swept sphere (world-space origins / directions, (n, 3); radii: a scalar or (n,)) with the resident
+        terrain: a SPHERE_HIT_DTYPE array, distance -1 and triangle -1 for a miss."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("origins and directions differ in length")
+        r = self._radii(radii, len(o))
+        hits = np.zeros(len(o), SPHERE_HIT_DTYPE)
+        self._check(self._L.vtmc_terrain_spherecast(self._h, _ptr(o), _ptr(d), _ptr(r), len(o), max_distance,
+                                                    RAY_TWO_SIDED if two_sided else 0, _ptr(hits)))
+        return hits
+
+    def terrain_closest_point(self, centers, radii):
+        """Nearest surface point within each ball (world-space centres, (n, 3); radii: a scalar or (n,)) on the resident terrain: a
+        SPHERE_HIT_DTYPE array, distance -1 and triangle -1 when no triangle is within the radius."""
+        c = np.ascontiguousarray(centers, np.float32).reshape(-1, 3)
+        r = self._radii(radii, len(c))
+        hits = np.zeros(len(c), SPHERE_HIT_DTYPE)
+        self._check(self._L.vtmc_terrain_closest_point(self._h, _ptr(c), _ptr(r), len(c), 0, _ptr(hits)))
+        return hits
+
+    def spherecast_device(self, d_grid, n, strides, origin, voxel_scale, d_origins, d_directions, d_radii, n_queries, d_hits,
+                          max_distance=float("inf"), two_sided=False, stream=None):
+        """vtmc_spherecast_device: device addresses (int) of the grid, the queries and n_queries SPHERE_HIT_DTYPE records; n = (nx, ny,
+        nz) cells, element strides.  Queued on `stream`, not synchronised."""
+        org = (ctypes.c_float * 3)(*origin)
+        self._check(self._L.vtmc_spherecast_device(self._h, d_grid, n[0], n[1], n[2], strides[0], strides[1], strides[2], ctypes.byref(org),
+                                                   voxel_scale, d_origins, d_directions, d_radii, n_queries, max_distance,
+                                                   RAY_TWO_SIDED if two_sided else 0, d_hits, stream))
+
+    def closest_point_device(self, d_grid, n, strides, origin, voxel_scale, d_centers, d_radii, n_queries, d_hits, stream=None):
+        """vtmc_closest_point_device: as spherecast_device, for closest-point queries."""
+        org = (ctypes.c_float * 3)(*origin)
+        self._check(self._L.vtmc_closest_point_device(self._h, d_grid, n[0], n[1], n[2], strides[0], strides[1], strides[2], ctypes.byref(org),
+                                                      voxel_scale, d_centers, d_radii, n_queries, 0, d_hits, stream))
 
     def density_fill_device(self, params, origins, dims, strides, volume_stride, d_out, stream=None, wait=True):
         """wait=False queues the fill on `stream` without synchronising (vtmc_density_fill_device_async)."""
