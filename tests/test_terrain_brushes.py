@@ -12,6 +12,7 @@ import pytest
 
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib
+from terrain_twin import assert_grid, assert_triangles, bits, gpu_mod, oracle_mod_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -102,18 +103,6 @@ def apply_brush(ref, m):
 
 
 # -- device / twin plumbing -------------------------------------------------------------------------------------------------------------
-def gpu_mod(spec):
-    kind, args = spec
-    return {"plane": vt.PlaneModifier, "sphere": vt.SphereModifier, "cylinder": vt.CylinderModifier,
-            "smooth": vt.SmoothModifier, "flatten": vt.FlattenModifier}[kind](*args)
-
-
-def oracle_mod_of(oracle_mod, spec):
-    kind, args = spec
-    return {"plane": oracle_mod.plane_modifier, "sphere": oracle_mod.sphere_modifier,
-            "cylinder": oracle_mod.cylinder_modifier}[kind](*args)
-
-
 def twin_update(ref, oracle_mod, specs):
     """The queue on the twin: reference kinds through oracle.Terrain, brushes through numpy.  Returns the dirty list by block id."""
     nb = tuple(d // 8 for d in ref.dims)
@@ -131,24 +120,6 @@ def twin_update(ref, oracle_mod, specs):
 def both_update(ex, ref, oracle_mod, specs):
     got = ex.terrain_update([gpu_mod(s) for s in specs])
     return got, twin_update(ref, oracle_mod, specs)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_grid(ex, want):
-    assert np.array_equal(bits(ex.terrain_read_samples()), bits(want))
-
-
-def assert_triangles(ex, oracle_mod, grid, dirty, T):
-    want, want_offs, _ = oracle_mod.extract_grid(np.ascontiguousarray(grid), dirty, threads=8)
-    assert T == len(want)
-    if T:
-        got, offs = ex.read_triangles()
-        assert np.array_equal(offs, want_offs) and np.array_equal(got["block"], want["block"])
-        for f in ("p0", "p1", "p2", "n0", "n1", "n2"):
-            assert np.abs(got[f] - want[f]).max() <= 1e-5
 
 
 def assert_update(ex, ref, oracle_mod, specs):

@@ -11,6 +11,7 @@ import pytest
 
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib
+from terrain_twin import assert_grid, assert_triangles, bits, gpu_mod, oracle_mod_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NO_RESULT = _lib.ERR_NO_RESULT
@@ -32,40 +33,10 @@ STEPS = [
 ]
 
 
-def gpu_mod(spec):
-    kind, args = spec
-    return {"plane": vt.PlaneModifier, "sphere": vt.SphereModifier, "cylinder": vt.CylinderModifier,
-            "island": vt.IslandModifier}[kind](*args)
-
-
-def oracle_mod_of(oracle_mod, spec):
-    kind, args = spec
-    return {"plane": oracle_mod.plane_modifier, "sphere": oracle_mod.sphere_modifier,
-            "cylinder": oracle_mod.cylinder_modifier, "island": oracle_mod.heightmap_modifier}[kind](*args)
-
-
 def both_update(ex, ref, oracle_mod, specs):
     """The same queue on the device and on the twin; returns the device's (n_dirty, T) and the twin's dirty list."""
     got = ex.terrain_update([gpu_mod(s) for s in specs])
     return got, ref.update([oracle_mod_of(oracle_mod, s) for s in specs])
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_grid(ex, want):
-    assert np.array_equal(bits(ex.terrain_read_samples()), bits(want))
-
-
-def assert_triangles(ex, oracle_mod, grid, dirty, T):
-    want, want_offs, _ = oracle_mod.extract_grid(np.ascontiguousarray(grid), dirty, threads=8)
-    assert T == len(want)
-    if T:
-        got, offs = ex.read_triangles()
-        assert np.array_equal(offs, want_offs) and np.array_equal(got["block"], want["block"])
-        for f in ("p0", "p1", "p2", "n0", "n1", "n2"):
-            assert np.abs(got[f] - want[f]).max() <= 1e-5
 
 
 def no_result(fn):

@@ -1,5 +1,6 @@
-// mc_cell.h -- one cell's marching-cubes triangles rebuilt from its eight samples, and the watertight ray / triangle test, shared by
-// the surface queries (raycast.hip, spherequery.hip) so both see the same triangles bit for bit (gfx950, wave64).
+// mc_cell.h -- what the surface queries (raycast.hip, spherequery.hip) share on the device, so both see the same triangles bit for bit
+// (gfx950, wave64): the description of the surface (SurfaceGrid, CornerOffsets, load_cell), one cell's marching-cubes triangles rebuilt
+// from its eight samples, and the watertight ray / triangle test.
 //
 // The arithmetic is the exact-mode emit's (CollectTriNum.compute:41-64 case, MarchingCube.compute:119-151 vertices and winding): the
 // library is built with -ffp-contract=off and `/` is correctly rounded, so a rebuilt triangle equals the extracted one.  The case table
@@ -44,6 +45,30 @@ __device__ __forceinline__ void edge_vertex(const float (&s)[8], int lx, int ly,
         const float v = (float)l[k] + (float)ob[k];
         p[k] = u + t * (v - u);
     }
+}
+
+// The surface a query runs against: the marching-cubes surface of n[0] x n[1] x n[2] cells of a density grid in any memory order.  The
+// first member of both kernels' arguments (raycast.hip, spherequery.hip); filled by surface_of_grid / surface_of_terrain (surface_query.h).
+struct SurfaceGrid {
+    const float *grid;
+    long long sx, sy, sz;                   // element strides
+    int n[3];                               // cells per axis
+    double origin[3];                       // world position of sample (0,0,0)
+    double scale;                           // voxel_scale
+    const unsigned long long *vert_packed;  // DeviceTables::vert_packed
+};
+
+// element offsets of a cell's eight corners from its first, in MarchingCube.compute order: built once per kernel, outside its walk
+struct CornerOffsets {
+    long long c[8];
+    __device__ __forceinline__ explicit CornerOffsets(const SurfaceGrid &g) : c{0, g.sx, g.sx + g.sy, g.sy, g.sz, g.sx + g.sz, g.sx + g.sy + g.sz, g.sy + g.sz} {}
+};
+// the eight corner samples of cell (cx, cy, cz): one straight run of loads, nothing waits between them
+__device__ __forceinline__ void load_cell(const SurfaceGrid &g, const CornerOffsets &o, int cx, int cy, int cz, float (&s)[8])
+{
+    const float *base = g.grid + ((long long)cx * g.sx + (long long)cy * g.sy + (long long)cz * g.sz);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) s[q] = base[o.c[q]];
 }
 
 // the case table in LDS: one word per thread of a 256-thread workgroup (the caller's next barrier publishes it)

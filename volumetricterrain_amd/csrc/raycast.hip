@@ -17,10 +17,7 @@
 // Intersection: watertight ray / triangle test (Woop, Benthin & Wald 2013) in float64 on the exact grid-unit vertices 8b + p, so
 // two triangles sharing an edge cannot both miss a ray crossing it.  Everything after the vertex positions is float64: the
 // ray transform is the same for every triangle, and nothing depends on the grid's layout or on which lane tested a cell.
-#include "vtmc_ctx.h"
-#include "mc_cell.h"
-#include <cmath>
-#include <cstring>
+#include "surface_query.h"
 
 namespace vtmc {
 
@@ -29,17 +26,12 @@ constexpr int kRayThreads = 64 * kWaves;  // lanes (= sub-intervals) per ray
 constexpr int kBatch = 4;                 // cells a lane loads before it evaluates them
 
 struct RaycastArgs {
-    const float *grid;
-    long long sx, sy, sz;  // element strides
-    int n[3];              // cells per axis
-    double origin[3];      // world position of sample (0,0,0)
-    double scale;          // voxel_scale
+    SurfaceGrid g;
     const float *ro, *rd;  // n_rays x 3 each
     vtmc_ray_hit *hits;
     int n_rays;
     float max_distance;
     int two_sided;
-    const unsigned long long *vert_packed;  // DeviceTables::vert_packed
 };
 
 struct Best {
@@ -91,7 +83,8 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
     __shared__ double s_t[kWaves];
     __shared__ int s_lane[kWaves];
     const int ray = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    load_case_table(s_cases, a.vert_packed, tid);
+    const SurfaceGrid &g = a.g;
+    load_case_table(s_cases, g.vert_packed, tid);
     const float o[3] = {a.ro[3ll * ray], a.ro[3ll * ray + 1], a.ro[3ll * ray + 2]};
     const float d[3] = {a.rd[3ll * ray], a.rd[3ll * ray + 1], a.rd[3ll * ray + 2]};
 
@@ -106,11 +99,11 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             dn[k] = (double)d[k] / len;
-            r.o[k] = ((double)o[k] - a.origin[k]) / a.scale;
-            r.d[k] = dn[k] / a.scale;
+            r.o[k] = ((double)o[k] - g.origin[k]) / g.scale;
+            r.d[k] = dn[k] / g.scale;
             // slab clip against the meshed box [0, n]: every triangle lies inside it
             if (r.d[k] != 0.0) {
-                double t0 = (0.0 - r.o[k]) / r.d[k], t1 = ((double)a.n[k] - r.o[k]) / r.d[k];
+                double t0 = (0.0 - r.o[k]) / r.d[k], t1 = ((double)g.n[k] - r.o[k]) / r.d[k];
                 if (t0 > t1) {
                     const double x = t0;
                     t0 = t1;
@@ -118,7 +111,7 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
                 }
                 t_in = fmax(t_in, t0);
                 t_out = fmin(t_out, t1);
-            } else if (r.o[k] < 0.0 || r.o[k] > (double)a.n[k]) {
+            } else if (r.o[k] < 0.0 || r.o[k] > (double)g.n[k]) {
                 ok = false;
             }
         }
@@ -137,7 +130,7 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const double p = r.o[k] + ta * r.d[k];
-            int ci = (int)fmin(fmax(floor(p), 0.0), (double)(a.n[k] - 1));
+            int ci = (int)fmin(fmax(floor(p), 0.0), (double)(g.n[k] - 1));
             c[k] = ci;
             step[k] = r.d[k] > 0.0 ? 1 : (r.d[k] < 0.0 ? -1 : 0);
             if (step[k]) {
@@ -146,8 +139,9 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
             }
         }
     }
-    int budget = a.n[0] + a.n[1] + a.n[2] + 3;  // no lane walks more cells than a ray can cross
-    const long long corner[8] = {0, a.sx, a.sx + a.sy, a.sy, a.sz, a.sx + a.sz, a.sx + a.sy + a.sz, a.sy + a.sz};
+    int budget = g.n[0] + g.n[1] + g.n[2] + 3;  // no lane walks more cells than a ray can cross
+
+    const CornerOffsets corner(g);
 
     while (__syncthreads_or(active)) {
         float s[kBatch][8];
@@ -160,9 +154,7 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
             cc[j][1] = c[1];
             cc[j][2] = c[2];
             if (active) {
-                const float *base = a.grid + ((long long)c[0] * a.sx + (long long)c[1] * a.sy + (long long)c[2] * a.sz);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) s[j][q] = base[corner[q]];
+                load_cell(g, corner, c[0], c[1], c[2], s[j]);
                 // next cell: leave through the nearest face; stop past the sub-interval or the box
                 const int k = tmax[0] <= tmax[1] ? (tmax[0] <= tmax[2] ? 0 : 2) : (tmax[1] <= tmax[2] ? 1 : 2);
                 const double t_exit = fmin(tmax[0], fmin(tmax[1], tmax[2]));
@@ -174,7 +166,7 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
                         if (kk == k) {
                             c[kk] += step[kk];
                             tmax[kk] = ((double)(c[kk] + (step[kk] > 0)) - r.o[kk]) * inv[kk];
-                            if (c[kk] < 0 || c[kk] >= a.n[kk]) active = false;
+                            if (c[kk] < 0 || c[kk] >= g.n[kk]) active = false;
                         }
                 }
             }
@@ -247,29 +239,12 @@ static hipError_t launch_raycast(const RaycastArgs &a, hipStream_t stream)
     return launch_end();
 }
 
-// the argument rules both entry points share
 static int check_rays(vtmc_ctx *ctx, int32_t n_rays, bool null_arg, float max_distance, uint32_t flags)
 {
-    if (n_rays < 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "n_rays < 0");
-    if (n_rays > 0 && null_arg) return fail(ctx, VTMC_ERR_INVALID_ARG, "null argument");
-    if (!(max_distance > 0.0f)) return fail(ctx, VTMC_ERR_INVALID_ARG, "max_distance must be positive (+inf allowed)");
+    if (int rc = check_batch(ctx, n_rays, "n_rays", null_arg)) return rc;
+    if (int rc = check_max_distance(ctx, max_distance)) return rc;
     if (flags & ~VTMC_RAY_TWO_SIDED) return fail(ctx, VTMC_ERR_INVALID_ARG, "unknown ray flags 0x%x", flags);
     return VTMC_OK;
-}
-
-static RaycastArgs raycast_args(const vtmc_ctx *ctx, const float *grid, int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz,
-                                const float origin[3], float scale, float max_distance, uint32_t flags)
-{
-    RaycastArgs a{};
-    a.grid = grid;
-    a.sx = sx, a.sy = sy, a.sz = sz;
-    a.n[0] = nx, a.n[1] = ny, a.n[2] = nz;
-    for (int k = 0; k < 3; ++k) a.origin[k] = origin[k];
-    a.scale = scale;
-    a.max_distance = max_distance;
-    a.two_sided = (flags & VTMC_RAY_TWO_SIDED) ? 1 : 0;
-    a.vert_packed = ctx->tables.vert_packed;
-    return a;
 }
 
 }  // namespace vtmc
@@ -284,16 +259,10 @@ int32_t vtmc_raycast_device(vtmc_ctx *ctx, const float *d_grid, int32_t nx, int3
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
     if (int rc = check_rays(ctx, n_rays, !d_grid || !origin || !d_origins || !d_directions || !d_hits, max_distance, flags)) return rc;
-    if (int rc = check_dims(ctx, nx, ny, nz)) return rc;
-    if (n_rays == 0) return VTMC_OK;
-    if (!(voxel_scale > 0.0f) || !std::isfinite(voxel_scale)) return fail(ctx, VTMC_ERR_INVALID_ARG, "voxel_scale must be positive and finite");
-    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) return fail(ctx, VTMC_ERR_INVALID_ARG, "origin is not finite");
+    if (n_rays == 0) return check_dims(ctx, nx, ny, nz);
+    RaycastArgs a{{}, d_origins, d_directions, d_hits, n_rays, max_distance, (flags & VTMC_RAY_TWO_SIDED) ? 1 : 0};
+    if (int rc = surface_of_grid(ctx, d_grid, nx, ny, nz, stride_x, stride_y, stride_z, origin, voxel_scale, &a.g)) return rc;
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    RaycastArgs a = raycast_args(ctx, d_grid, nx, ny, nz, stride_x, stride_y, stride_z, origin, voxel_scale, max_distance, flags);
-    a.ro = d_origins;
-    a.rd = d_directions;
-    a.hits = d_hits;
-    a.n_rays = n_rays;
     VTMC_HIP(ctx, launch_raycast(a, stream ? (hipStream_t)stream : ctx->stream));
     return VTMC_OK;
 }
@@ -306,27 +275,14 @@ int32_t vtmc_terrain_raycast(vtmc_ctx *ctx, const float *origins, const float *d
     if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_raycast before terrain_init");
     if (n_rays == 0) return VTMC_OK;
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    const TerrainShape &sh = ctx->tshape;
-    // device: origins | directions | hits; the pinned staging holds the same bytes
-    const size_t ray_bytes = sizeof(float) * 3 * (size_t)n_rays, hit_bytes = sizeof(vtmc_ray_hit) * (size_t)n_rays;
-    const size_t bytes = 2 * ray_bytes + hit_bytes;
-    if (int rc = ensure(ctx, ctx->rays, bytes)) return rc;
-    if (ctx->h_rays.bytes < bytes) VTMC_HIP(ctx, pin(ctx->h_rays, bytes));
-    unsigned char *h = ctx->h_rays.p, *dv = (unsigned char *)ctx->rays.p;
-    memcpy(h, origins, ray_bytes);
-    memcpy(h + ray_bytes, directions, ray_bytes);
-    VTMC_HIP(ctx, hipMemcpyAsync(dv, h, 2 * ray_bytes, hipMemcpyHostToDevice, ctx->stream));
-    RaycastArgs a = raycast_args(ctx, (const float *)ctx->terrain.p, sh.dim_x - 2, sh.dim_y - 2, sh.dim_z - 2, 1, sh.dim_x,
-                                 (int64_t)sh.dim_x * sh.dim_y, sh.origin, sh.scale, max_distance, flags);
-    a.ro = (const float *)dv;
-    a.rd = (const float *)(dv + ray_bytes);
-    a.hits = (vtmc_ray_hit *)(dv + 2 * ray_bytes);
-    a.n_rays = n_rays;
+    const size_t ray_bytes = sizeof(float) * 3 * (size_t)n_rays;
+    const float *const src[3] = {origins, directions, nullptr};
+    const size_t bytes[3] = {ray_bytes, ray_bytes, 0};
+    QueryStage st;
+    if (int rc = stage_queries(ctx, src, bytes, sizeof(vtmc_ray_hit) * (size_t)n_rays, &st)) return rc;
+    const RaycastArgs a{surface_of_terrain(ctx), st.in[0], st.in[1], (vtmc_ray_hit *)st.hits, n_rays, max_distance, (flags & VTMC_RAY_TWO_SIDED) ? 1 : 0};
     VTMC_HIP(ctx, launch_raycast(a, ctx->stream));
-    VTMC_HIP(ctx, hipMemcpyAsync(h + 2 * ray_bytes, dv + 2 * ray_bytes, hit_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(hits, h + 2 * ray_bytes, hit_bytes);
-    return VTMC_OK;
+    return fetch_hits(ctx, st, hits);
 }
 
 }  // extern "C"

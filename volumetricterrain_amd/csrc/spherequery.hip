@@ -18,10 +18,7 @@
 // three edge cylinders and the three vertex spheres.  r = 0 is the raycast's watertight test.  Closest point: Ericson §5.1.5.  Ties in
 // t or distance go to the smallest canonical index (block bx + nbx (by + nby bz), cell x + 8y + 64z, triangle i), so the answer
 // depends neither on the grid's strides nor on the launch shape nor on which lane tested a cell.
-#include "vtmc_ctx.h"
-#include "mc_cell.h"
-#include <cmath>
-#include <cstring>
+#include "surface_query.h"
 
 namespace vtmc {
 
@@ -33,18 +30,16 @@ constexpr double kPad = 1e-3;                 // cells: slack on every conservat
 constexpr unsigned long long kNoKey = ~0ull;  // the key of "no triangle"
 
 struct SphereArgs {
-    const float *grid;
-    long long sx, sy, sz;  // element strides
-    int n[3];              // cells per axis
-    double origin[3];      // world position of sample (0,0,0)
-    double scale;          // voxel_scale
-    const float *qo, *qd, *qr;  // per query: origin / centre (x3), direction (x3, casts only), radius
+    SurfaceGrid g;
+    // hits before the inputs: in this order the compiler groups the argument loads so that the kernels are one s_waitcnt shorter than with
+    // the case table last, and the walk's loops lie 4 bytes from where they did then; with the inputs first they lie 20 bytes off, which
+    // cost the 1024-cell sweep that meets no surface 1.1 % (profiles/r10/edit_refactor/README.md)
     vtmc_sphere_hit *hits;
+    const float *qo, *qd, *qr;  // per query: origin / centre (x3), direction (x3, casts only), radius
     int n_q;
     float max_distance;  // casts only
     float max_radius;    // VTMC_SPHERE_MAX_RADIUS_CELLS * voxel_scale
     int two_sided;
-    const unsigned long long *vert_packed;  // DeviceTables::vert_packed
 };
 
 __device__ __forceinline__ double dot3(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -195,7 +190,7 @@ __device__ __forceinline__ void query_cell(const SphereArgs &a, const unsigned l
     const unsigned cs = cell_case(s);
     if (nan || cs == 0u || cs == 255u) return;
     const unsigned long long w = s_cases[cs];
-    const int nbx = a.n[0] >> 3, nby = a.n[1] >> 3;
+    const int nbx = a.g.n[0] >> 3, nby = a.g.n[1] >> 3;
     const unsigned long long cell_key =
         ((unsigned long long)((cx >> 3) + nbx * ((cy >> 3) + (long long)nby * (cz >> 3))) * 512ull + (unsigned)((cx & 7) + 8 * (cy & 7) + 64 * (cz & 7))) * 5ull;
 #pragma unroll 1
@@ -212,7 +207,7 @@ __device__ __forceinline__ void query_cell(const SphereArgs &a, const unsigned l
         if (Cast) {
             if (!a.two_sided && !(dot3(n, q.u) < 0.0)) continue;  // single-sided: the face must look at the sweep
             if (q.R > 0.0) {
-                t = sweep_triangle(q.o, q.u, P, n, nn, q.R) * a.scale;
+                t = sweep_triangle(q.o, q.u, P, n, nn, q.R) * a.g.scale;
             } else {
                 double V, W, det;
                 if (!ray_triangle(q.ray, P[0], P[1], P[2], t, V, W, det)) continue;
@@ -267,7 +262,7 @@ __global__ __launch_bounds__(kSqThreads) void sphere_query_kernel(SphereArgs a)
     __shared__ double s_t[kSqWaves];
     __shared__ unsigned long long s_key[kSqWaves];
     const int qi = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    load_case_table(s_cases, a.vert_packed, tid);
+    load_case_table(s_cases, a.g.vert_packed, tid);
     const float o[3] = {a.qo[3ll * qi], a.qo[3ll * qi + 1], a.qo[3ll * qi + 2]};
     float d[3] = {0.f, 0.f, 0.f};
     if (Cast) {
@@ -283,24 +278,24 @@ __global__ __launch_bounds__(kSqThreads) void sphere_query_kernel(SphereArgs a)
     bool ok = finite3(o) && rad >= 0.f && rad <= a.max_radius;
     double s_in = 0.0, s_out = 0.0;  // the sweep in grid units along u
     if (ok) {
-        q.R = (double)rad / a.scale;
+        q.R = (double)rad / a.g.scale;
         double len = 1.0;
         if (Cast) {
             ok = finite3(d);
             len = sqrt((double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2]);
             ok = ok && len > 0.0;
-            s_out = (double)a.max_distance / a.scale * (1.0 + 1e-9) + kPad;   // (float)t <= max_distance decides exactly
+            s_out = (double)a.max_distance / a.g.scale * (1.0 + 1e-9) + kPad;   // (float)t <= max_distance decides exactly
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            q.o[k] = ((double)o[k] - a.origin[k]) / a.scale;
+            q.o[k] = ((double)o[k] - a.g.origin[k]) / a.g.scale;
             dn[k] = Cast ? (double)d[k] / len : 0.0;
             q.u[k] = dn[k];
             q.ray.o[k] = q.o[k];
-            q.ray.d[k] = dn[k] / a.scale;
+            q.ray.d[k] = dn[k] / a.g.scale;
             if (!Cast) continue;
             // slab clip against the meshed box [0, n] grown by R: no triangle is within R of a centre outside it
-            const double lo = -q.R - kPad, hi = (double)a.n[k] + q.R + kPad;
+            const double lo = -q.R - kPad, hi = (double)a.g.n[k] + q.R + kPad;
             if (q.u[k] != 0.0) {
                 double t0 = (lo - q.o[k]) / q.u[k], t1 = (hi - q.o[k]) / q.u[k];
                 if (t0 > t1) {
@@ -320,7 +315,7 @@ __global__ __launch_bounds__(kSqThreads) void sphere_query_kernel(SphereArgs a)
 
     double bt = INFINITY;
     unsigned long long bkey = kNoKey;
-    const long long corner[8] = {0, a.sx, a.sx + a.sy, a.sy, a.sz, a.sx + a.sz, a.sx + a.sy + a.sz, a.sy + a.sz};
+    const CornerOffsets corner(a.g);
     const double reach = q.R + 0.8660254037844387 + kPad;  // a cell centre this far from the segment: no point of the cell is within R
     double sa = s_in;
     __syncthreads();  // s_cases
@@ -334,8 +329,8 @@ __global__ __launch_bounds__(kSqThreads) void sphere_query_kernel(SphereArgs a)
             A[k] = q.o[k] + sa * q.u[k];
             Bv[k] = q.o[k] + sb * q.u[k];
             const double l = fmin(A[k], Bv[k]) - q.R - kPad, h = fmax(A[k], Bv[k]) + q.R + kPad;
-            lo[k] = (int)fmin(fmax(floor(l), 0.0), (double)a.n[k]);           // clamped before the conversion: a far centre is
-            const int hi = (int)fmax(fmin(floor(h), (double)(a.n[k] - 1)), -1.0);  // finite but may not fit an int
+            lo[k] = (int)fmin(fmax(floor(l), 0.0), (double)a.g.n[k]);           // clamped before the conversion: a far centre is
+            const int hi = (int)fmax(fmin(floor(h), (double)(a.g.n[k] - 1)), -1.0);  // finite but may not fit an int
             ext[k] = hi >= lo[k] ? hi - lo[k] + 1 : 0;
             count *= ext[k];
         }
@@ -365,9 +360,7 @@ __global__ __launch_bounds__(kSqThreads) void sphere_query_kernel(SphereArgs a)
                 for (int k = 0; k < 3; ++k) m[k] -= f * seg[k];
                 valid[j] = dot3(m, m) <= reach * reach;
                 if (!valid[j]) continue;
-                const float *g = a.grid + ((long long)cc[j][0] * a.sx + (long long)cc[j][1] * a.sy + (long long)cc[j][2] * a.sz);
-#pragma unroll
-                for (int c = 0; c < 8; ++c) s[j][c] = g[corner[c]];
+                load_cell(a.g, corner, cc[j][0], cc[j][1], cc[j][2], s[j]);
             }
 #pragma unroll
             for (int j = 0; j < kSqBatch; ++j)
@@ -375,7 +368,7 @@ __global__ __launch_bounds__(kSqThreads) void sphere_query_kernel(SphereArgs a)
         }
         reduce_best(bt, bkey, s_t, s_key, wave, lane);
         // a contact at t <= sb involves a cell within R of the segment up to sb: all of those have been tested
-        if (!Cast || bt <= sb * a.scale || sb >= s_out) break;
+        if (!Cast || bt <= sb * a.g.scale || sb >= s_out) break;
         sa = sb;
     }
     if (tid != 0) return;
@@ -392,22 +385,20 @@ __global__ __launch_bounds__(kSqThreads) void sphere_query_kernel(SphereArgs a)
     h.triangle = -1;
     if (ok && bkey != kNoKey) {
         // rebuild the winning triangle from its canonical index
-        const int nbx = a.n[0] >> 3, nby = a.n[1] >> 3;
+        const int nbx = a.g.n[0] >> 3, nby = a.g.n[1] >> 3;
         const int tri = (int)(bkey % 5ull), cell = (int)((bkey / 5ull) % 512ull);
         const long long blk = (long long)(bkey / 2560ull);
         const int bx = (int)(blk % nbx), by = (int)((blk / nbx) % nby), bz = (int)(blk / ((long long)nbx * nby));
         const int cx = 8 * bx + (cell & 7), cy = 8 * by + ((cell >> 3) & 7), cz = 8 * bz + (cell >> 6);
-        const float *g = a.grid + ((long long)cx * a.sx + (long long)cy * a.sy + (long long)cz * a.sz);
         float s[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) s[c] = g[corner[c]];
+        load_cell(a.g, corner, cx, cy, cz, s);
         double P[3][3];
         cell_triangle(s_cases[cell_case(s)], s, cx, cy, cz, tri, P[0], P[1], P[2]);
         double e1[3], e2[3], n[3], c[3], p[3], cp[3];
         sub3(P[1], P[0], e1);
         sub3(P[2], P[0], e2);
         cross3(e1, e2, n);
-        const double s_hit = Cast ? bt / a.scale : 0.0;  // grid units along u
+        const double s_hit = Cast ? bt / a.g.scale : 0.0;  // grid units along u
 #pragma unroll
         for (int k = 0; k < 3; ++k) c[k] = q.o[k] + s_hit * q.u[k];
         closest_on_triangle(c, P[0], P[1], P[2], p);
@@ -415,10 +406,10 @@ __global__ __launch_bounds__(kSqThreads) void sphere_query_kernel(SphereArgs a)
         const double dist = sqrt(dot3(cp, cp));
         const double inv = (Cast && q.R == 0.0) || !(dist > 0.0) ? 1.0 / sqrt(dot3(n, n)) : 1.0 / dist;
         const double *nv = (Cast && q.R == 0.0) || !(dist > 0.0) ? n : cp;
-        h.distance = Cast ? (float)bt : (float)(dist * a.scale);
+        h.distance = Cast ? (float)bt : (float)(dist * a.g.scale);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            h.point[k] = (float)(a.origin[k] + p[k] * a.scale);
+            h.point[k] = (float)(a.g.origin[k] + p[k] * a.g.scale);
             h.normal[k] = (float)(nv[k] * inv);
         }
         h.block[0] = bx, h.block[1] = by, h.block[2] = bz;
@@ -439,9 +430,9 @@ static hipError_t launch_sphere_query(const SphereArgs &a, hipStream_t stream)
 // the argument rules the four entry points share (max_distance: casts only)
 static int check_queries(vtmc_ctx *ctx, int32_t n, bool null_arg, bool cast, float max_distance, uint32_t flags)
 {
-    if (n < 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "n < 0");
-    if (n > 0 && null_arg) return fail(ctx, VTMC_ERR_INVALID_ARG, "null argument");
-    if (cast && !(max_distance > 0.0f)) return fail(ctx, VTMC_ERR_INVALID_ARG, "max_distance must be positive (+inf allowed)");
+    if (int rc = check_batch(ctx, n, "n", null_arg)) return rc;
+    if (cast)
+        if (int rc = check_max_distance(ctx, max_distance)) return rc;
     if (cast && (flags & ~VTMC_RAY_TWO_SIDED)) return fail(ctx, VTMC_ERR_INVALID_ARG, "unknown sphere cast flags 0x%x", flags);
     if (!cast && flags) return fail(ctx, VTMC_ERR_INVALID_ARG, "closest-point flags are reserved and must be 0 (got 0x%x)", flags);
     return VTMC_OK;
@@ -460,20 +451,10 @@ static int check_radii(vtmc_ctx *ctx, const float *radii, int32_t n, float scale
     return VTMC_OK;
 }
 
-static SphereArgs sphere_args(const vtmc_ctx *ctx, const float *grid, int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz,
-                              const float origin[3], float scale, float max_distance, uint32_t flags)
+// the arguments of a batch but for its surface
+static SphereArgs sphere_args(const float *o, const float *d, const float *r, vtmc_sphere_hit *hits, int32_t n, float scale, float max_distance, uint32_t flags)
 {
-    SphereArgs a{};
-    a.grid = grid;
-    a.sx = sx, a.sy = sy, a.sz = sz;
-    a.n[0] = nx, a.n[1] = ny, a.n[2] = nz;
-    for (int k = 0; k < 3; ++k) a.origin[k] = origin[k];
-    a.scale = scale;
-    a.max_distance = max_distance;
-    a.max_radius = max_radius(scale);
-    a.two_sided = (flags & VTMC_RAY_TWO_SIDED) ? 1 : 0;
-    a.vert_packed = ctx->tables.vert_packed;
-    return a;
+    return SphereArgs{{}, hits, o, d, r, n, max_distance, max_radius(scale), (flags & VTMC_RAY_TWO_SIDED) ? 1 : 0};
 }
 
 static int device_query(vtmc_ctx *ctx, bool cast, const float *d_grid, int32_t nx, int32_t ny, int32_t nz, int64_t sx, int64_t sy,
@@ -482,17 +463,10 @@ static int device_query(vtmc_ctx *ctx, bool cast, const float *d_grid, int32_t n
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
     if (int rc = check_queries(ctx, n, !d_grid || !origin || !d_o || (cast && !d_d) || !d_r || !d_hits, cast, max_distance, flags)) return rc;
-    if (int rc = check_dims(ctx, nx, ny, nz)) return rc;
-    if (n == 0) return VTMC_OK;
-    if (!(voxel_scale > 0.0f) || !std::isfinite(voxel_scale)) return fail(ctx, VTMC_ERR_INVALID_ARG, "voxel_scale must be positive and finite");
-    if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2])) return fail(ctx, VTMC_ERR_INVALID_ARG, "origin is not finite");
+    if (n == 0) return check_dims(ctx, nx, ny, nz);
+    SphereArgs a = sphere_args(d_o, d_d, d_r, d_hits, n, voxel_scale, max_distance, flags);
+    if (int rc = surface_of_grid(ctx, d_grid, nx, ny, nz, sx, sy, sz, origin, voxel_scale, &a.g)) return rc;
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    SphereArgs a = sphere_args(ctx, d_grid, nx, ny, nz, sx, sy, sz, origin, voxel_scale, max_distance, flags);
-    a.qo = d_o;
-    a.qd = d_d;
-    a.qr = d_r;
-    a.hits = d_hits;
-    a.n_q = n;
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     VTMC_HIP(ctx, cast ? launch_sphere_query<true>(a, st) : launch_sphere_query<false>(a, st));
     return VTMC_OK;
@@ -505,33 +479,17 @@ static int terrain_query(vtmc_ctx *ctx, bool cast, const float *o, const float *
     if (int rc = check_queries(ctx, n, !o || (cast && !d) || !r || !hits, cast, max_distance, flags)) return rc;
     if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain sphere query before terrain_init");
     if (n == 0) return VTMC_OK;
-    const TerrainShape &sh = ctx->tshape;
-    if (int rc = check_radii(ctx, r, n, sh.scale)) return rc;
+    if (int rc = check_radii(ctx, r, n, ctx->tshape.scale)) return rc;
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    // device: origins | directions (casts) | radii | hits; the pinned staging holds the same bytes
-    const size_t vec_bytes = sizeof(float) * 3 * (size_t)n, r_bytes = sizeof(float) * (size_t)n;
-    const size_t hit_off = ((cast ? 2 : 1) * vec_bytes + r_bytes + 15) & ~(size_t)15, hit_bytes = sizeof(vtmc_sphere_hit) * (size_t)n;
-    const size_t bytes = hit_off + hit_bytes;
-    if (int rc = ensure(ctx, ctx->rays, bytes)) return rc;
-    if (ctx->h_rays.bytes < bytes) VTMC_HIP(ctx, pin(ctx->h_rays, bytes));
-    unsigned char *h = ctx->h_rays.p, *dv = (unsigned char *)ctx->rays.p;
-    const size_t r_off = (cast ? 2 : 1) * vec_bytes;
-    memcpy(h, o, vec_bytes);
-    if (cast) memcpy(h + vec_bytes, d, vec_bytes);
-    memcpy(h + r_off, r, r_bytes);
-    VTMC_HIP(ctx, hipMemcpyAsync(dv, h, r_off + r_bytes, hipMemcpyHostToDevice, ctx->stream));
-    SphereArgs a = sphere_args(ctx, (const float *)ctx->terrain.p, sh.dim_x - 2, sh.dim_y - 2, sh.dim_z - 2, 1, sh.dim_x,
-                               (int64_t)sh.dim_x * sh.dim_y, sh.origin, sh.scale, max_distance, flags);
-    a.qo = (const float *)dv;
-    a.qd = cast ? (const float *)(dv + vec_bytes) : nullptr;
-    a.qr = (const float *)(dv + r_off);
-    a.hits = (vtmc_sphere_hit *)(dv + hit_off);
-    a.n_q = n;
+    const size_t vec_bytes = sizeof(float) * 3 * (size_t)n;
+    const float *const src[3] = {o, cast ? d : nullptr, r};
+    const size_t bytes[3] = {vec_bytes, cast ? vec_bytes : 0, sizeof(float) * (size_t)n};
+    QueryStage st;
+    if (int rc = stage_queries(ctx, src, bytes, sizeof(vtmc_sphere_hit) * (size_t)n, &st)) return rc;
+    SphereArgs a = sphere_args(st.in[0], st.in[1], st.in[2], (vtmc_sphere_hit *)st.hits, n, ctx->tshape.scale, max_distance, flags);
+    a.g = surface_of_terrain(ctx);
     VTMC_HIP(ctx, cast ? launch_sphere_query<true>(a, ctx->stream) : launch_sphere_query<false>(a, ctx->stream));
-    VTMC_HIP(ctx, hipMemcpyAsync(h + hit_off, dv + hit_off, hit_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(hits, h + hit_off, hit_bytes);
-    return VTMC_OK;
+    return fetch_hits(ctx, st, hits);
 }
 
 }  // namespace vtmc

@@ -110,25 +110,52 @@ __device__ __forceinline__ float column_term(const TerrainModifierArgs &m, float
 
 constexpr int kYRun = 16;  // samples along y per thread
 
-// launch shape: 64 x 4 threads = 64 samples along x (the stride-1 axis) of 4 z-planes; a thread walks
-// kYRun samples along y; grid = (x segments, z quads, y runs)
-__global__ __launch_bounds__(256) void terrain_modify_kernel(float *__restrict__ grid, TerrainShape sh, TerrainModifierArgs m)
+// ---- the box walk every kernel below shares --------------------------------------------------------------------------------------
+// launch shape: 64 x 4 threads = 64 samples along x (the stride-1 axis) of 4 z-planes; a thread walks kYRun samples along y;
+// grid = (x segments, z quads, y runs)
+// A thread's place in a box (a TerrainBox, or a TerrainModifierArgs for its six ints).  The box is asked, not stored: a kernel reads
+// dy only behind its bounds test, as the kernels did when each wrote this out.
+struct BoxThread {
+    int ix, iz, iy0;  // this thread's column of the box and the first sample of its run along y
+    __device__ __forceinline__ BoxThread() : ix(blockIdx.x * 64 + threadIdx.x), iz(blockIdx.y * 4 + threadIdx.y), iy0(blockIdx.z * kYRun) {}
+    template <class Box>
+    __device__ __forceinline__ bool inside(const Box &b) const { return ix < b.dx && iz < b.dz; }
+    template <class Box>
+    __device__ __forceinline__ int iy1(const Box &b) const { return iy0 + kYRun < b.dy ? iy0 + kYRun : b.dy; }  // the run is [iy0, iy1)
+};
+// sample (x, y, z) of the grid, x fastest; 64 bits: the hash counts samples with it
+__device__ __forceinline__ uint64_t grid_index(const TerrainShape &sh, int x, int y, int z)
 {
-    const int ix = blockIdx.x * 64 + threadIdx.x, iz = blockIdx.y * 4 + threadIdx.y, iy0 = blockIdx.z * kYRun;
-    if (ix >= m.dx || iz >= m.dz) return;
-    const int x = m.lx + ix, z = m.lz + iz;
+    return (uint64_t)x + (uint64_t)sh.dim_x * ((uint64_t)y + (uint64_t)sh.dim_y * (uint64_t)z);
+}
+// sample (ix, iy, iz) of a box in its journal image or stage, x fastest, so a wave stores 256 contiguous bytes; a box reaches 4.3 GB
+template <class Box>
+__device__ __forceinline__ uint64_t box_index(const Box &b, int ix, int iy, int iz)
+{
+    return (uint64_t)ix + (uint64_t)b.dx * ((uint64_t)iy + (uint64_t)b.dy * (uint64_t)iz);
+}
+
+// kJournal (history on): the sample it replaces also goes to the box's image (12 bytes per touched sample instead of 8).  History off
+// runs the instruction sequence the kernel had before it was a template (profiles/r10/edit_refactor/README.md).
+template <bool kJournal>
+__global__ __launch_bounds__(256) void terrain_modify_kernel(float *__restrict__ grid, float *__restrict__ image, TerrainShape sh, TerrainModifierArgs m)
+{
+    const BoxThread t;
+    if (!t.inside(m)) return;
+    const int x = m.lx + t.ix, z = m.lz + t.iz;
     // worldPos = new Vector3(x, y, z) * _voxelScale + TerrainOrigin (VoxelTerrain.cs:290)
     const float px = (float)x * sh.scale + sh.origin[0];
     const float pz = (float)z * sh.scale + sh.origin[2];
     const float col = column_term(m, px, pz);
-    const int iy1 = iy0 + kYRun < m.dy ? iy0 + kYRun : m.dy;
-    for (int iy = iy0; iy < iy1; ++iy) {
+    const uint64_t row = box_index(m, t.ix, 0, t.iz);  // image index of (ix, 0, iz); sample iy lies iy rows of dx further
+    for (int iy = t.iy0, iy1 = t.iy1(m); iy < iy1; ++iy) {
         const int y = m.ly + iy;
         const float py = (float)y * sh.scale + sh.origin[1];
-        const uint64_t sample = (uint64_t)x + (uint64_t)sh.dim_x * ((uint64_t)y + (uint64_t)sh.dim_y * (uint64_t)z);
+        const uint64_t sample = grid_index(sh, x, y, z);
         const float q = m.kind == 3 ? col - py : query_density(m, px, py, pz);  // IslandModifier: elevation - pos.y
         const float md = clamp_drawn(q, sh.seed, m.event, sample, 0u);
         const float s = grid[sample];
+        if (kJournal) image[row + (uint64_t)m.dx * (uint64_t)iy] = s;
         float r;
         if (m.add_or_erode) {
             r = s > md ? s : md;  // Mathf.Max(S, md)
@@ -140,60 +167,24 @@ __global__ __launch_bounds__(256) void terrain_modify_kernel(float *__restrict__
     }
 }
 
-// terrain_modify_kernel with the edit journal: the sample it replaces also goes to image[ix + dx*(iy + dy*iz)], the modifier's box x
-// fastest, so a wave stores 256 contiguous bytes beside the row it reads and writes (12 bytes per touched sample instead of 8).  The
-// body repeats terrain_modify_kernel's line for line; that kernel stays as it is so history off runs exactly the code it ran before.
-__global__ __launch_bounds__(256) void terrain_modify_journal_kernel(float *__restrict__ grid, float *__restrict__ image, TerrainShape sh,
-                                                                     TerrainModifierArgs m)
-{
-    const int ix = blockIdx.x * 64 + threadIdx.x, iz = blockIdx.y * 4 + threadIdx.y, iy0 = blockIdx.z * kYRun;
-    if (ix >= m.dx || iz >= m.dz) return;
-    const int x = m.lx + ix, z = m.lz + iz;
-    const float px = (float)x * sh.scale + sh.origin[0];
-    const float pz = (float)z * sh.scale + sh.origin[2];
-    const float col = column_term(m, px, pz);
-    const int iy1 = iy0 + kYRun < m.dy ? iy0 + kYRun : m.dy;
-    const uint64_t row = (uint64_t)ix + (uint64_t)m.dx * (uint64_t)m.dy * (uint64_t)iz;  // image index of (ix, 0, iz); a box reaches 4.3 GB
-    for (int iy = iy0; iy < iy1; ++iy) {
-        const int y = m.ly + iy;
-        const float py = (float)y * sh.scale + sh.origin[1];
-        const uint64_t sample = (uint64_t)x + (uint64_t)sh.dim_x * ((uint64_t)y + (uint64_t)sh.dim_y * (uint64_t)z);
-        const float q = m.kind == 3 ? col - py : query_density(m, px, py, pz);
-        const float md = clamp_drawn(q, sh.seed, m.event, sample, 0u);
-        const float s = grid[sample];
-        image[row + (uint64_t)m.dx * (uint64_t)iy] = s;
-        float r;
-        if (m.add_or_erode) {
-            r = s > md ? s : md;
-        } else {
-            const float minus_md = -md;
-            r = clamp_drawn(s < minus_md ? s : minus_md, sh.seed, m.event, sample, 2u);
-        }
-        grid[sample] = r;
-    }
-}
-
-// Undo / redo of one box: grid box <-> its journal image, 32-bit copies (NaN payloads and -0 survive), 16 bytes per sample.  Same
-// launch shape and image order as terrain_modify_journal_kernel.
+// Undo / redo of one box: grid box <-> its journal image, 32-bit copies (NaN payloads and -0 survive), 16 bytes per sample.
 __global__ __launch_bounds__(256) void terrain_swap_kernel(uint32_t *__restrict__ grid, uint32_t *__restrict__ image, TerrainShape sh, TerrainBox b)
 {
-    const int ix = blockIdx.x * 64 + threadIdx.x, iz = blockIdx.y * 4 + threadIdx.y, iy0 = blockIdx.z * kYRun;
-    if (ix >= b.dx || iz >= b.dz) return;
-    const uint64_t x = (uint64_t)(b.lx + ix), z = (uint64_t)(b.lz + iz);
-    const int iy1 = iy0 + kYRun < b.dy ? iy0 + kYRun : b.dy;
-    const uint64_t row = (uint64_t)ix + (uint64_t)b.dx * (uint64_t)b.dy * (uint64_t)iz;
-    const uint64_t s0 = x + (uint64_t)sh.dim_x * ((uint64_t)(b.ly + iy0) + (uint64_t)sh.dim_y * z), j0 = row + (uint64_t)b.dx * (uint64_t)iy0;
+    const BoxThread t;
+    if (!t.inside(b)) return;
+    const uint64_t s0 = grid_index(sh, b.lx + t.ix, b.ly + t.iy0, b.lz + t.iz), j0 = box_index(b, t.ix, t.iy0, t.iz);
+    const int iy1 = t.iy1(b);
     // every load of the run is issued before the first store: 2 * kYRun loads in flight per lane, not 2
     uint32_t g[kYRun], h[kYRun];
 #pragma unroll
     for (int k = 0; k < kYRun; ++k)
-        if (iy0 + k < iy1) {
+        if (t.iy0 + k < iy1) {
             g[k] = grid[s0 + (uint64_t)sh.dim_x * k];
             h[k] = image[j0 + (uint64_t)b.dx * k];
         }
 #pragma unroll
     for (int k = 0; k < kYRun; ++k)
-        if (iy0 + k < iy1) {
+        if (t.iy0 + k < iy1) {
             grid[s0 + (uint64_t)sh.dim_x * k] = h[k];
             image[j0 + (uint64_t)b.dx * k] = g[k];
         }
@@ -214,21 +205,20 @@ __device__ __forceinline__ float brush_weight(const TerrainModifierArgs &m, floa
 }
 
 // Flatten: T = clamp((n . (c - p)) / scale, -1, 1), solid below the plane through c, air above it, linear in grid units within one
-// sample of it.  Pointwise: terrain_modify_kernel's launch shape; kJournal also stores every sample of the box into its image.
+// sample of it.  Pointwise; kJournal also stores every sample of the box into its image.
 template <bool kJournal>
 __global__ __launch_bounds__(256) void terrain_flatten_kernel(float *__restrict__ grid, float *__restrict__ image, TerrainShape sh, TerrainModifierArgs m)
 {
-    const int ix = blockIdx.x * 64 + threadIdx.x, iz = blockIdx.y * 4 + threadIdx.y, iy0 = blockIdx.z * kYRun;
-    if (ix >= m.dx || iz >= m.dz) return;
-    const int x = m.lx + ix, z = m.lz + iz;
+    const BoxThread t;
+    if (!t.inside(m)) return;
+    const int x = m.lx + t.ix, z = m.lz + t.iz;
     const float px = (float)x * sh.scale + sh.origin[0];
     const float pz = (float)z * sh.scale + sh.origin[2];
-    const int iy1 = iy0 + kYRun < m.dy ? iy0 + kYRun : m.dy;
-    const uint64_t row = (uint64_t)ix + (uint64_t)m.dx * (uint64_t)m.dy * (uint64_t)iz;
-    for (int iy = iy0; iy < iy1; ++iy) {
+    const uint64_t row = box_index(m, t.ix, 0, t.iz);  // image index of (ix, 0, iz); sample iy lies iy rows of dx further
+    for (int iy = t.iy0, iy1 = t.iy1(m); iy < iy1; ++iy) {
         const int y = m.ly + iy;
         const float py = (float)y * sh.scale + sh.origin[1];
-        const uint64_t sample = (uint64_t)x + (uint64_t)sh.dim_x * ((uint64_t)y + (uint64_t)sh.dim_y * (uint64_t)z);
+        const uint64_t sample = grid_index(sh, x, y, z);
         const float w = brush_weight(m, px, py, pz);
         if (!kJournal && w == 0.0f) continue;
         const float s = grid[sample];
@@ -240,23 +230,21 @@ __global__ __launch_bounds__(256) void terrain_flatten_kernel(float *__restrict_
     }
 }
 
-// Smooth, pass 1: the brush's box plus a one-sample halo, intersected with the grid (box h), copied to the stage, x fastest:
-// stage[(x - h.lx) + h.dx * ((y - h.ly) + h.dy * (z - h.lz))].  Launch shape and load-before-store order of terrain_swap_kernel.
+// Smooth, pass 1: the brush's box plus a one-sample halo, intersected with the grid (box h), copied to the stage.  Load-before-store
+// order of terrain_swap_kernel.
 __global__ __launch_bounds__(256) void terrain_stage_kernel(const float *__restrict__ grid, float *__restrict__ stage, TerrainShape sh, TerrainBox h)
 {
-    const int ix = blockIdx.x * 64 + threadIdx.x, iz = blockIdx.y * 4 + threadIdx.y, iy0 = blockIdx.z * kYRun;
-    if (ix >= h.dx || iz >= h.dz) return;
-    const uint64_t x = (uint64_t)(h.lx + ix), z = (uint64_t)(h.lz + iz);
-    const int iy1 = iy0 + kYRun < h.dy ? iy0 + kYRun : h.dy;
-    const uint64_t s0 = x + (uint64_t)sh.dim_x * ((uint64_t)(h.ly + iy0) + (uint64_t)sh.dim_y * z);
-    const uint64_t j0 = (uint64_t)ix + (uint64_t)h.dx * ((uint64_t)iy0 + (uint64_t)h.dy * (uint64_t)iz);
+    const BoxThread t;
+    if (!t.inside(h)) return;
+    const int iy1 = t.iy1(h);
+    const uint64_t s0 = grid_index(sh, h.lx + t.ix, h.ly + t.iy0, h.lz + t.iz), j0 = box_index(h, t.ix, t.iy0, t.iz);
     float v[kYRun];
 #pragma unroll
     for (int k = 0; k < kYRun; ++k)
-        if (iy0 + k < iy1) v[k] = grid[s0 + (uint64_t)sh.dim_x * k];
+        if (t.iy0 + k < iy1) v[k] = grid[s0 + (uint64_t)sh.dim_x * k];
 #pragma unroll
     for (int k = 0; k < kYRun; ++k)
-        if (iy0 + k < iy1) stage[j0 + (uint64_t)h.dx * k] = v[k];
+        if (t.iy0 + k < iy1) stage[j0 + (uint64_t)h.dx * k] = v[k];
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -274,11 +262,10 @@ __global__ __launch_bounds__(256) void terrain_smooth_kernel(float *__restrict__
                                                              TerrainShape sh, TerrainModifierArgs m, TerrainBox h)
 {
     __shared__ float tile[2][kTile];
+    const BoxThread bt;
     const int tx = threadIdx.x, tz = threadIdx.y, t = tz * 64 + tx;
-    const int ix = blockIdx.x * 64 + tx, iz = blockIdx.y * 4 + tz, iy0 = blockIdx.z * kYRun;
     const int ox = m.lx - h.lx, oy = m.ly - h.ly, oz = m.lz - h.lz;  // the box's first sample in the stage (0 or 1 per axis)
-    const int iy1 = iy0 + kYRun < m.dy ? iy0 + kYRun : m.dy;
-    const int n_planes = iy1 - iy0 + 2;                                // uniform over the workgroup
+    const int n_planes = bt.iy1(m) - bt.iy0 + 2;                          // uniform over the workgroup
     const uint64_t plane = (uint64_t)h.dx * (uint64_t)h.dy;
     // this lane's tile entries t and t + 256 (the second for t < kTile - 256 only)
     const bool two = t + 256 < kTile;
@@ -291,15 +278,16 @@ __global__ __launch_bounds__(256) void terrain_smooth_kernel(float *__restrict__
 #pragma unroll
     for (int k = 0; k < kYRun + 2; ++k)
         if (k < n_planes) {
-            const uint64_t sy = (uint64_t)h.dx * (uint64_t)clampi(iy0 + oy - 1 + k, 0, h.dy - 1);
+            const uint64_t sy = (uint64_t)h.dx * (uint64_t)clampi(bt.iy0 + oy - 1 + k, 0, h.dy - 1);
             v0[k] = stage[c0 + sy];
             if (two) v1[k] = stage[c1 + sy];
         }
-    const bool live = ix < m.dx && iz < m.dz;
-    const int x = m.lx + ix, z = m.lz + iz;
+    // BoxThread::inside, written out: through the call the compiler nests the 15 unrolled write-backs in two branches instead of one mask
+    const bool live = bt.ix < m.dx && bt.iz < m.dz;
+    const int x = m.lx + bt.ix, z = m.lz + bt.iz;
     const float px = (float)x * sh.scale + sh.origin[0];
     const float pz = (float)z * sh.scale + sh.origin[2];
-    const uint64_t row = (uint64_t)ix + (uint64_t)m.dx * (uint64_t)m.dy * (uint64_t)iz;
+    const uint64_t row = box_index(m, bt.ix, 0, bt.iz);
     float ra[3] = {0.0f, 0.0f, 0.0f}, rb[3] = {0.0f, 0.0f, 0.0f}, sb = 0.0f;  // R of planes k-2 and k-1 at z-1, z, z+1; S of plane k-1
 #pragma unroll
     for (int k = 0; k < kYRun + 2; ++k) {
@@ -317,9 +305,9 @@ __global__ __launch_bounds__(256) void terrain_smooth_kernel(float *__restrict__
             }
             const float sc = tl[(tz + 1) * kTileX + tx + 1];
             if (k >= 2 && live) {
-                const int iy = iy0 + k - 2, y = m.ly + iy;
+                const int iy = bt.iy0 + k - 2, y = m.ly + iy;
                 const float py = (float)y * sh.scale + sh.origin[1];
-                const uint64_t sample = (uint64_t)x + (uint64_t)sh.dim_x * ((uint64_t)y + (uint64_t)sh.dim_y * (uint64_t)z);
+                const uint64_t sample = grid_index(sh, x, y, z);
                 if (kJournal) image[row + (uint64_t)m.dx * (uint64_t)iy] = sb;
                 const float w = brush_weight(m, px, py, pz);
                 if (w != 0.0f) {
@@ -348,48 +336,27 @@ hipError_t launch_terrain_fill(float *grid, long long n, uint64_t seed, int n_cu
     return launch_end();
 }
 
-hipError_t launch_terrain_modify(float *grid, const TerrainShape &sh, const TerrainModifierArgs &m, hipStream_t stream)
-{
-    if (m.dx <= 0 || m.dy <= 0 || m.dz <= 0) return hipSuccess;
-    if ((m.dz + 3) / 4 > 65535 || (m.dy + kYRun - 1) / kYRun > 65535) return hipErrorInvalidValue;
-    launch_begin();
-    hipLaunchKernelGGL(terrain_modify_kernel, dim3((unsigned)((m.dx + 63) / 64), (unsigned)((m.dz + 3) / 4), (unsigned)((m.dy + kYRun - 1) / kYRun)),
-                       dim3(64, 4, 1), 0, stream, grid, sh, m);
-    return launch_end();
-}
+static TerrainBox box_of(const TerrainModifierArgs &m) { return TerrainBox{m.lx, m.ly, m.lz, m.dx, m.dy, m.dz}; }
+static bool box_empty(const TerrainBox &b) { return b.dx <= 0 || b.dy <= 0 || b.dz <= 0; }
 
 static dim3 box_grid(const TerrainBox &b) { return dim3((unsigned)((b.dx + 63) / 64), (unsigned)((b.dz + 3) / 4), (unsigned)((b.dy + kYRun - 1) / kYRun)); }
+static bool box_launchable(const TerrainBox &b) { return (b.dz + 3) / 4 <= 65535 && (b.dy + kYRun - 1) / kYRun <= 65535; }  // grid y, z: 16 bits
 
-static hipError_t launch_terrain_modify_journal(float *grid, float *image, const TerrainShape &sh, const TerrainModifierArgs &m, hipStream_t stream)
+// the one launch of a box kernel, on a non-empty box
+template <class... Params, class... Args>
+static hipError_t launch_box(void (*kernel)(Params...), const TerrainBox &b, hipStream_t stream, Args... args)
 {
-    const TerrainBox b{m.lx, m.ly, m.lz, m.dx, m.dy, m.dz};
-    if ((m.dz + 3) / 4 > 65535 || (m.dy + kYRun - 1) / kYRun > 65535) return hipErrorInvalidValue;
-    launch_begin();
-    hipLaunchKernelGGL(terrain_modify_journal_kernel, box_grid(b), dim3(64, 4, 1), 0, stream, grid, image, sh, m);
-    return launch_end();
-}
-
-static hipError_t launch_terrain_swap(float *grid, float *image, const TerrainShape &sh, const TerrainBox &b, hipStream_t stream)
-{
-    if ((b.dz + 3) / 4 > 65535 || (b.dy + kYRun - 1) / kYRun > 65535) return hipErrorInvalidValue;
-    launch_begin();
-    hipLaunchKernelGGL(terrain_swap_kernel, box_grid(b), dim3(64, 4, 1), 0, stream, (uint32_t *)grid, (uint32_t *)image, sh, b);
-    return launch_end();
-}
-
-static bool box_launchable(const TerrainBox &b) { return (b.dz + 3) / 4 <= 65535 && (b.dy + kYRun - 1) / kYRun <= 65535; }
-
-// VTMC_MOD_FLATTEN on a non-empty box; image: the box's journal image, or null (history off)
-static hipError_t launch_terrain_flatten(float *grid, float *image, const TerrainShape &sh, const TerrainModifierArgs &m, hipStream_t stream)
-{
-    const TerrainBox b{m.lx, m.ly, m.lz, m.dx, m.dy, m.dz};
     if (!box_launchable(b)) return hipErrorInvalidValue;
     launch_begin();
-    if (image)
-        hipLaunchKernelGGL(terrain_flatten_kernel<true>, box_grid(b), dim3(64, 4, 1), 0, stream, grid, image, sh, m);
-    else
-        hipLaunchKernelGGL(terrain_flatten_kernel<false>, box_grid(b), dim3(64, 4, 1), 0, stream, grid, image, sh, m);
+    hipLaunchKernelGGL(kernel, box_grid(b), dim3(64, 4, 1), 0, stream, args...);
     return launch_end();
+}
+
+// declared by vtmc_internal.h, whose text the traffic constant of the extract path is tied to: kept for that declaration, vtmc_terrain_update
+// goes through launch_box itself
+hipError_t launch_terrain_modify(float *grid, const TerrainShape &sh, const TerrainModifierArgs &m, hipStream_t stream)
+{
+    return box_empty(box_of(m)) ? hipSuccess : launch_box(terrain_modify_kernel<false>, box_of(m), stream, grid, (float *)nullptr, sh, m);
 }
 
 // the stage box of a smooth: its (non-empty) box grown by one sample per side, intersected with the grid
@@ -398,22 +365,6 @@ static TerrainBox smooth_stage_box(const TerrainShape &sh, const TerrainModifier
     const int lx = std::max(m.lx - 1, 0), ly = std::max(m.ly - 1, 0), lz = std::max(m.lz - 1, 0);
     const int ux = std::min(m.lx + m.dx, sh.dim_x - 1), uy = std::min(m.ly + m.dy, sh.dim_y - 1), uz = std::min(m.lz + m.dz, sh.dim_z - 1);
     return TerrainBox{lx, ly, lz, ux - lx + 1, uy - ly + 1, uz - lz + 1};
-}
-
-// VTMC_MOD_SMOOTH on a non-empty box: stage (box h of smooth_stage_box), then smooth; image as launch_terrain_flatten
-static hipError_t launch_terrain_smooth(float *grid, float *image, float *stage, const TerrainShape &sh, const TerrainModifierArgs &m,
-                                        const TerrainBox &h, hipStream_t stream)
-{
-    const TerrainBox b{m.lx, m.ly, m.lz, m.dx, m.dy, m.dz};
-    if (!box_launchable(b) || !box_launchable(h)) return hipErrorInvalidValue;
-    launch_begin();
-    hipLaunchKernelGGL(terrain_stage_kernel, box_grid(h), dim3(64, 4, 1), 0, stream, (const float *)grid, stage, sh, h);
-    if (hipError_t e = launch_end()) return e;
-    if (image)
-        hipLaunchKernelGGL(terrain_smooth_kernel<true>, box_grid(b), dim3(64, 4, 1), 0, stream, grid, image, (const float *)stage, sh, m, h);
-    else
-        hipLaunchKernelGGL(terrain_smooth_kernel<false>, box_grid(b), dim3(64, 4, 1), 0, stream, grid, image, (const float *)stage, sh, m, h);
-    return launch_end();
 }
 
 static int saturating_int(float f)   // of a floor / ceil: Mathf.FloorToInt / CeilToInt, saturating
@@ -531,8 +482,6 @@ static void history_clear(vtmc_ctx *ctx)
     ctx->hist_done = 0;
 }
 
-static bool box_empty(const TerrainBox &b) { return b.dx <= 0 || b.dy <= 0 || b.dz <= 0; }
-
 // journal bytes of a box image: 4 per sample, rounded up to 256
 static size_t image_bytes(const TerrainBox &b) { return box_empty(b) ? 0 : ((size_t)4 * b.dx * b.dy * b.dz + 255) / 256 * 256; }
 
@@ -546,7 +495,7 @@ static VtmcHistoryStep plan_step(vtmc_ctx *ctx, const vtmc_modifier *mods, int32
     for (int32_t i = 0; i < n_mods; ++i) {
         VtmcHistoryBox &hb = st.boxes[i];
         const TerrainModifierArgs a = sample_range(ctx->tshape, mods[i], hb.low, hb.up);
-        hb.box = TerrainBox{a.lx, a.ly, a.lz, a.dx, a.dy, a.dz};
+        hb.box = box_of(a);
         hb.off = st.bytes;
         st.bytes += image_bytes(hb.box);
     }
@@ -586,7 +535,8 @@ static int32_t history_step(vtmc_ctx *ctx, bool undo, int32_t *n_dirty_blocks, i
     for (size_t i = 0; i < n; ++i) {
         const VtmcHistoryBox &hb = st.boxes[undo ? n - 1 - i : i];
         if (!box_empty(hb.box))
-            if (hipError_t e = launch_terrain_swap((float *)ctx->terrain.p, (float *)((char *)ctx->journal.p + hb.off), ctx->tshape, hb.box, ctx->stream)) {
+            if (hipError_t e = launch_box(terrain_swap_kernel, hb.box, ctx->stream, (uint32_t *)ctx->terrain.p,
+                                          (uint32_t *)((char *)ctx->journal.p + hb.off), ctx->tshape, hb.box)) {
                 history_clear(ctx);  // some boxes swapped, some not: no image is what its step says any more
                 VTMC_HIP(ctx, e);
             }
@@ -667,7 +617,8 @@ int32_t vtmc_terrain_update(vtmc_ctx *ctx, const vtmc_modifier *mods, int32_t n_
         int low[3], up[3];
         TerrainModifierArgs a = sample_range(sh, md, low, up);
         a.event = ++ctx->terrain_events;
-        if (md.kind == VTMC_MOD_HEIGHTMAP && a.dx > 0 && a.dy > 0 && a.dz > 0) {
+        const TerrainBox b = box_of(a);
+        if (md.kind == VTMC_MOD_HEIGHTMAP && !box_empty(b)) {
             // _heightmap (IslandModifier.cs:36) goes to the device; an earlier modifier of this queue may
             // still be reading the previous one, hence the drain before the buffer is touched
             const size_t bytes = sizeof(float) * (size_t)md.data_dims[0] * (size_t)md.data_dims[1];
@@ -678,22 +629,25 @@ int32_t vtmc_terrain_update(vtmc_ctx *ctx, const vtmc_modifier *mods, int32_t n_
             a.dims0 = md.data_dims[0];
             a.dims1 = md.data_dims[1];
         }
-        if (a.dx > 0 && a.dy > 0 && a.dz > 0) {
-            float *image = journaled ? (float *)((char *)ctx->journal.p + step.boxes[i].off) : nullptr;
-            if (md.kind == VTMC_MOD_FLATTEN) {
-                VTMC_HIP(ctx, launch_terrain_flatten((float *)ctx->terrain.p, image, sh, a, ctx->stream));
-            } else if (md.kind == VTMC_MOD_SMOOTH) {
+        if (!box_empty(b)) {
+            float *grid = (float *)ctx->terrain.p, *image = journaled ? (float *)((char *)ctx->journal.p + step.boxes[i].off) : nullptr;
+            if (md.kind == VTMC_MOD_SMOOTH) {
                 const TerrainBox h = smooth_stage_box(sh, a);
                 const size_t bytes = sizeof(float) * (size_t)h.dx * (size_t)h.dy * (size_t)h.dz;
                 if (ctx->brush.bytes < bytes) {  // an earlier smooth of this queue may still be reading the stage
                     VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
                     if (int rc = ensure(ctx, ctx->brush, bytes)) return rc;
                 }
-                VTMC_HIP(ctx, launch_terrain_smooth((float *)ctx->terrain.p, image, (float *)ctx->brush.p, sh, a, h, ctx->stream));
-            } else if (journaled)
-                VTMC_HIP(ctx, launch_terrain_modify_journal((float *)ctx->terrain.p, image, sh, a, ctx->stream));
-            else
-                VTMC_HIP(ctx, launch_terrain_modify((float *)ctx->terrain.p, sh, a, ctx->stream));
+                // h contains b (sample_range clips b to the grid, smooth_stage_box only grows it), so a box too large to launch fails
+                // here, before anything is written
+                float *stage = (float *)ctx->brush.p;
+                VTMC_HIP(ctx, launch_box(terrain_stage_kernel, h, ctx->stream, grid, stage, sh, h));
+                VTMC_HIP(ctx, launch_box(image ? terrain_smooth_kernel<true> : terrain_smooth_kernel<false>, b, ctx->stream, grid, image, stage, sh, a, h));
+            } else if (md.kind == VTMC_MOD_FLATTEN) {
+                VTMC_HIP(ctx, launch_box(image ? terrain_flatten_kernel<true> : terrain_flatten_kernel<false>, b, ctx->stream, grid, image, sh, a));
+            } else {  // the reference's modifiers, kinds 0-3
+                VTMC_HIP(ctx, launch_box(image ? terrain_modify_kernel<true> : terrain_modify_kernel<false>, b, ctx->stream, grid, image, sh, a));
+            }
         }
         if (n_marked < mark.size()) n_marked += mark_dirty_blocks(low, up, nb, mark);
     }
