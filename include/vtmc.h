@@ -300,6 +300,36 @@ int32_t vtmc_device_indexed_results(vtmc_ctx *ctx, const vtmc_vertex **d_vertice
  * VTMC_ERR_INVALID_ARG (the modifier's index in vtmc_last_error) for c not finite, r not finite or <= 0, s not finite or outside
  * [0, 1], and for flatten n not finite or dot(n, n) == 0.  The journal records a brush's box (no halo), as any modifier's. */
 
+#define VTMC_MOD_NOISE 8     /* fractal noise: the device form of RidgedMultifractalModifier (TerrainModifier.cs:158-196) and its fBm and
+                                                           billow relatives.  p[0] = frequency f (per world unit), p[1] = lacunarity L,
+                                                           p[2] = gain g, p[3] = amplitude a, p[4] = bias b, p[5] = ramp scale rs,
+                                                           p[6] = ramp centre rc (world y), p[7] = ridge offset h (ridged only;
+                                                           LibNoise's is 1); data_dims[0] = seed (the C# int _seed),
+                                                           data_dims[1] = octaves | basis << 8 (octaves 1..16; basis 0 fBm, 1 billow,
+                                                           2 ridged multifractal); data is not read.  Kinds 6 and 7 are not defined. */
+/* The noise is THE LIBRARY'S OWN: Ken Perlin's 2002 improved noise over the 256-entry permutation of the density sampler (a Fisher-Yates
+ * shuffle driven by SplitMix64 of (uint64_t)(uint32_t)seed, as vtmc_density_fill_device uses for vtmc_density_params.seed).  The
+ * reference's modifier wraps LibNoise, which it does not vendor: no value here is LibNoise's and parity with it is not claimed.
+ * A noise modifier takes its box from lower / upper, marks dirty blocks, is journaled and takes one event number exactly as kinds 0-3,
+ * in queue order with every other kind.  Per sample of the box, FP32, one IEEE operation per step, in this order (px, py, pz as for
+ * kinds 0-3: (float)x * scale + origin; noise3 = the improved noise, value in about [-1, 1]):
+ *   x = px * f;  y = py * f;  z = pz * f;  amp = 1;  sum = 0;  w = 1
+ *   for o in 0 .. octaves-1:
+ *     n = noise3(x, y, z)
+ *     fBm:     sum = sum + amp * n
+ *     billow:  t = fabsf(n);  t = t + t;  t = t - 1;  sum = sum + amp * t
+ *     ridged:  r = h - fabsf(n);  r = r * r;  r = r * w;  w = r + r;  w = w < 0 ? 0 : (w > 1 ? 1 : w);  sum = sum + amp * r
+ *     x = x * L;  y = y * L;  z = z * L;  amp = amp * g
+ *   q = a * sum;  q = q + b;  q = q - (py - rc) * rs
+ *   md = Clamp(q, void, full) with draws 0 / 1; then add_or_erode 1: S = max(S, md); 0: S = Clamp(min(S, -md), void, full), draws 2 / 3:
+ *   the write of kinds 0-3.
+ * With basis 0, a = 1, b = 0, scale 1 and origin 0 the value q is what vtmc_density_fill_device's definition gives for the same
+ * vtmc_density_params at integer positions.
+ * VTMC_ERR_INVALID_ARG (the modifier's index in vtmc_last_error, nothing written by it): any of p[0..7] not finite; octaves outside
+ * 1..16; basis outside 0..2; or lattice coordinates that can reach 2^24 in magnitude inside the modifier's clamped sample box: the
+ * largest |world coordinate| of the box's corner samples times |f| * max(1, |L|)^(octaves - 1), evaluated in double, must be below
+ * 2^24 (beyond it the lattice fraction carries no information and the float -> int conversion differs between targets). */
+
 /* One queued TerrainModifier (TerrainModifier.cs:19-33).  lower / upper are the values the C#
  * LowerBound / UpperBound properties return (world space): the shim copies them, so Unity's
  * Vector3.ProjectOnPlane stays on the C# side. */

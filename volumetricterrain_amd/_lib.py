@@ -55,6 +55,7 @@ COMM_ID_BYTES = 128
 
 MOD_PLANE, MOD_SPHERE, MOD_CYLINDER, MOD_HEIGHTMAP = 0, 1, 2, 3
 MOD_SMOOTH, MOD_FLATTEN = 4, 5   # sculpt brushes (not in the reference)
+MOD_NOISE = 8                     # fBm / billow / ridged noise (RidgedMultifractalModifier's device form); 6 and 7 are not defined
 
 
 class Modifier(ctypes.Structure):

@@ -7,6 +7,7 @@
 // permutation from a SplitMix64-driven Fisher-Yates shuffle, summed over octaves, minus a vertical
 // ramp.  VALU + small LDS tables; writes are lane-contiguous along the stride-1 axis.
 #include "vtmc_ctx.h"
+#include "perlin_device.h"   // fade / mixf / gradf / noise3: the one Perlin of the library
 #include <cstring>
 #include <type_traits>
 #pragma clang diagnostic ignored "-Winline-asm"   // the sign words' v_writelane names m0 as clobbered: a reserved register, which this file's kernels never use otherwise
@@ -31,36 +32,6 @@ void density_permutation(uint64_t seed, unsigned char perm[256])
         perm[i] = perm[j];
         perm[j] = t;
     }
-}
-
-__device__ __forceinline__ float fade(float t) { return t * t * t * (t * (t * 6.0f - 15.0f) + 10.0f); }
-__device__ __forceinline__ float mixf(float t, float a, float b) { return a + t * (b - a); }
-__device__ __forceinline__ float gradf(int hash, float x, float y, float z)
-{
-    int h = hash & 15;
-    float u = h < 8 ? x : y;
-    float v = h < 4 ? y : ((h == 12 || h == 14) ? x : z);
-    return ((h & 1) == 0 ? u : -u) + ((h & 2) == 0 ? v : -v);
-}
-
-__device__ __forceinline__ float noise3(const unsigned char *p, float x, float y, float z)
-{
-    float fx = floorf(x), fy = floorf(y), fz = floorf(z);
-    int X = (int)fx & 255, Y = (int)fy & 255, Z = (int)fz & 255;
-    x -= fx;
-    y -= fy;
-    z -= fz;
-    float u = fade(x), v = fade(y), w = fade(z);
-#define VTMC_P(i) ((int)p[(i) & 255])
-    int A = VTMC_P(X) + Y, AA = VTMC_P(A) + Z, AB = VTMC_P(A + 1) + Z;
-    int B = VTMC_P(X + 1) + Y, BA = VTMC_P(B) + Z, BB = VTMC_P(B + 1) + Z;
-    float r = mixf(w,
-                   mixf(v, mixf(u, gradf(VTMC_P(AA), x, y, z), gradf(VTMC_P(BA), x - 1, y, z)),
-                        mixf(u, gradf(VTMC_P(AB), x, y - 1, z), gradf(VTMC_P(BB), x - 1, y - 1, z))),
-                   mixf(v, mixf(u, gradf(VTMC_P(AA + 1), x, y, z - 1), gradf(VTMC_P(BA + 1), x - 1, y, z - 1)),
-                        mixf(u, gradf(VTMC_P(AB + 1), x, y - 1, z - 1), gradf(VTMC_P(BB + 1), x - 1, y - 1, z - 1))));
-#undef VTMC_P
-    return r;
 }
 
 // Per-sample form (more than 8 octaves): one workgroup = 256 consecutive samples along the fast axis; blockIdx.x enumerates
@@ -89,7 +60,7 @@ __global__ __launch_bounds__(256) void density_generic_kernel(DensityLaunch dl, 
     float x = px * dl.frequency, y = py * dl.frequency, z = pz * dl.frequency;
     float amp = 1.0f, sum = 0.0f;
     for (int o = 0; o < dl.octaves; ++o) {
-        sum = sum + amp * noise3(s_perm, x, y, z);
+        sum = sum + amp * noise3(PermBytes{s_perm}, x, y, z);
         x *= dl.lacunarity;
         y *= dl.lacunarity;
         z *= dl.lacunarity;

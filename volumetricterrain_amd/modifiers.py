@@ -8,7 +8,7 @@ order of the C# expressions.
 """
 import numpy as np
 
-from ._lib import MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, Modifier
+from ._lib import MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, Modifier
 
 _f = np.float32
 FLOAT_MIN_VALUE = _f(-3.4028234663852886e38)  # C# float.MinValue
@@ -199,3 +199,48 @@ class FlattenModifier(SmoothModifier):
 
     def params(self):
         return [*self._center, self._radius, self._strength, *self._normal]
+
+
+# -- noise (include/vtmc.h VTMC_MOD_NOISE) -----------------------------------------------------------------------------------------------
+NOISE_BASES = {"fbm": 0, "billow": 1, "ridged": 2}
+
+
+class NoiseModifier(TerrainModifier):
+    """Fractal noise evaluated on the device: the form RidgedMultifractalModifier (TerrainModifier.cs:158-196) takes here, plus fBm and
+    billow.  density = amplitude * sum_o(gain^o * basis(noise(p * frequency * lacunarity^o))) + bias - (p.y - ramp_center) * ramp_scale.
+    The noise is the library's own Perlin over the density sampler's permutation of `seed`; the reference wraps LibNoise, which it does
+    not vendor, so the values are not LibNoise's.  lower / upper None: the reference class's bounds (0, 0, 0) .. (1000, 1000, 1000)
+    (TerrainModifier.cs:178-191)."""
+    kind = MOD_NOISE
+
+    def __init__(self, seed, octaves, frequency, lacunarity=2.0, gain=0.5, basis="fbm", amplitude=1.0, bias=0.0, ramp_scale=0.0,
+                 ramp_center=0.0, ridge_offset=1.0, lower=None, upper=None, add_or_erode=True):
+        if basis not in NOISE_BASES:
+            raise ValueError("noise basis must be one of %s" % ", ".join(NOISE_BASES))
+        if int(octaves) != octaves or not 1 <= octaves <= 16:
+            raise ValueError("noise octaves must be an integer in 1..16")
+        with np.errstate(over="ignore"):
+            self._p = np.array([frequency, lacunarity, gain, amplitude, bias, ramp_scale, ramp_center, ridge_offset], np.float64).astype(_f)
+        if not np.isfinite(self._p).all():
+            raise ValueError("noise parameters must be finite")
+        if not -2 ** 31 <= int(seed) < 2 ** 32:
+            raise ValueError("noise seed must fit 32 bits")
+        self._seed = int(seed) - 2 ** 32 if int(seed) >= 2 ** 31 else int(seed)   # the C# int _seed
+        self._octaves, self._basis = int(octaves), NOISE_BASES[basis]
+        self._low = _vec((0.0, 0.0, 0.0) if lower is None else lower)
+        self._up = _vec((1000.0, 1000.0, 1000.0) if upper is None else upper)
+        self.AddOrErode = add_or_erode
+
+    @property
+    def LowerBound(self):
+        return self._low
+
+    @property
+    def UpperBound(self):
+        return self._up
+
+    def params(self):
+        return list(self._p)
+
+    def attach(self, m):
+        m.data_dims[:] = (self._seed, self._octaves | (self._basis << 8))
