@@ -5,7 +5,9 @@
 //          counter on this access width (MI355X_MICROARCH.md: "other access widths are uncalibrated");
 //   mix  : a perfectly coalesced stream that reads 3 and writes 7 of every 10 float4 (the emit kernel's
 //          read : write mix, 1.45 GB : 3.38 GB) -- what the memory system gives that mix at best.
-// usage: calib rows|mix [MiB]      prints one JSON line; under rocprofv3 --pmc FETCH_SIZE the first gives
+//   read : a perfectly coalesced read-only stream of [MiB] MiB (default 4129 = a 1026^3 float grid), every byte once, 4 float4 in
+//          flight per lane -- what tools/terrain_io_bench.py sets the brick-flag kernel of terrain_io.hip beside.
+// usage: calib rows|mix|read [MiB]      prints one JSON line; under rocprofv3 --pmc FETCH_SIZE the first gives
 //                                  the counter / known-bytes factor.
 #include <hip/hip_runtime.h>
 
@@ -61,6 +63,20 @@ __global__ __launch_bounds__(256) void mix_kernel(const float4 *__restrict__ in,
     }
 }
 
+__global__ __launch_bounds__(256) void read_kernel(const float4 *__restrict__ in, size_t n_vec, float *__restrict__ sink)
+{
+    const size_t T = (size_t)gridDim.x * 256, t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    float acc = 0.0f;
+    for (size_t i = t; i < n_vec; i += 4 * T) {
+        float4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = i + k * T < n_vec ? in[i + k * T] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc += (v[k].x + v[k].y) + (v[k].z + v[k].w);
+    }
+    if (acc == 1.2345e30f) sink[0] = acc;
+}
+
 int main(int argc, char **argv)
 {
     const char *what = argc > 1 ? argv[1] : "rows";
@@ -87,6 +103,25 @@ int main(int argc, char **argv)
         printf("{\"kernel\": \"rows_kernel\", \"rows\": %.0f, \"known_bytes\": %.0f, \"ms\": %.4f, \"GBps_of_row_bytes\": %.1f, "
                "\"note\": \"every 40-byte row read exactly once; compare with FETCH_SIZE (KiB) of the same dispatch\"}\n",
                rows, bytes, best, bytes / best / 1e6);
+    } else if (!strcmp(what, "read")) {
+        const size_t mib = argc > 2 ? (size_t)atol(argv[2]) : 4129, n_vec = mib * (1u << 20) / sizeof(float4);
+        float4 *in;
+        float *sink;
+        CK(hipMalloc(&in, sizeof(float4) * n_vec));
+        CK(hipMalloc(&sink, 64));
+        CK(hipMemset(in, 0, sizeof(float4) * n_vec));
+        float best = 1e30f, all[5];
+        for (int it = 0; it < 5; ++it) {
+            CK(hipEventRecord(e0));
+            hipLaunchKernelGGL(read_kernel, dim3((unsigned)((n_vec + 1023) / 1024)), dim3(256), 0, 0, in, n_vec, sink);
+            CK(hipEventRecord(e1));
+            CK(hipEventSynchronize(e1));
+            CK(hipEventElapsedTime(&all[it], e0, e1));
+            if (all[it] < best) best = all[it];
+        }
+        const double bytes = 16.0 * n_vec;
+        printf("{\"kernel\": \"read_kernel\", \"read_bytes\": %.0f, \"ms\": %.4f, \"ms_all\": [%.4f, %.4f, %.4f, %.4f, %.4f], \"TBps\": %.3f}\n", bytes, best,
+               all[0], all[1], all[2], all[3], all[4], bytes / best / 1e9);
     } else {
         const size_t T = 256 * 256 * 16, n_iter = 12;   // 1M threads: 3 x 16 MB read, 7 x 16 MB written per iteration
         float4 *in, *out;

@@ -24,6 +24,7 @@ RAY_HIT_DTYPE = np.dtype([("distance", "<f4"), ("point", "<f4", 3), ("normal", "
                           ("block", "<i4", 3), ("cell", "<i4"), ("triangle", "<i4")])
 assert RAY_HIT_DTYPE.itemsize == 56
 RAY_TWO_SIDED = 1
+TERRAIN_SAVE_EXACT, TERRAIN_LOAD_NO_EXTRACT = 1, 1
 # vtmc_sphere_hit: one answer of vtmc_terrain_spherecast / _closest_point and their _device forms
 SPHERE_HIT_DTYPE = np.dtype([("distance", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3), ("block", "<i4", 3), ("cell", "<i4"),
                              ("triangle", "<i4")])
@@ -50,6 +51,7 @@ SYMBOLS = [
     "vtmc_terrain_raycast", "vtmc_raycast_device",
     "vtmc_terrain_set_history", "vtmc_terrain_undo", "vtmc_terrain_redo", "vtmc_terrain_history",
     "vtmc_terrain_spherecast", "vtmc_terrain_closest_point", "vtmc_spherecast_device", "vtmc_closest_point_device",
+    "vtmc_terrain_save", "vtmc_terrain_load", "vtmc_terrain_write_samples",
 ]
 COMM_ID_BYTES = 128
 
@@ -171,6 +173,10 @@ def load(path=None):
                                              vp, vp, vp, i32, ctypes.c_float, u32, vp, vp]
         L.vtmc_closest_point_device.argtypes = [vp, vp, i32, i32, i32, i64, i64, i64, P(ctypes.c_float * 3), ctypes.c_float,
                                                 vp, vp, i32, u32, vp, vp]
+    if not explicit or hasattr(L, "vtmc_terrain_save"):
+        L.vtmc_terrain_save.argtypes = [vp, ctypes.c_char_p, u32, P(i64)]
+        L.vtmc_terrain_load.argtypes = [vp, ctypes.c_char_p, u32, P(i32), P(i32)]
+        L.vtmc_terrain_write_samples.argtypes = [vp, vp, i64, i64, i64]
     L.vtmc_comm_unique_id.argtypes = [vp]
     L.vtmc_comm_init_rank.argtypes = [vp, vp, i32, i32]
     L.vtmc_comm_destroy.argtypes = [vp]

@@ -18,21 +18,13 @@
 // restates the same hash (oracle/terrain_ref.c).
 #include "vtmc_ctx.h"
 #include "perlin_device.h"
+#include "terrain_hash.h"
 #include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstring>
 
 namespace vtmc {
-
-__host__ __device__ __forceinline__ float terrain_uniform(uint64_t seed, uint32_t event, uint64_t sample, uint32_t draw)
-{
-    uint64_t z = (seed ^ ((uint64_t)event << 40) ^ (sample << 2) ^ (uint64_t)draw) + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (float)(uint32_t)(z >> 40) * 5.9604644775390625e-08f;  // 24 bits * 2^-24: exact, in [0,1)
-}
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi)  // Mathf.Clamp
 {
@@ -650,10 +642,18 @@ static int extract_dirty(vtmc_ctx *ctx, const std::vector<uint8_t> &mark, size_t
     return extract_core(ctx, sp, n_volumes, tri_count);
 }
 
-static void history_clear(vtmc_ctx *ctx)
+void history_clear(vtmc_ctx *ctx)   // vtmc_ctx.h: terrain_io.hip clears the history too
 {
     ctx->hist.clear();
     ctx->hist_done = 0;
+}
+
+// vtmc_terrain_load: every block is dirty, as after a world build (vtmc_ctx.h)
+int terrain_extract_all(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_count)
+{
+    const auto nb = block_counts(ctx->tshape);
+    const std::vector<uint8_t> mark((size_t)nb[0] * nb[1] * nb[2], 1);
+    return extract_dirty(ctx, mark, mark.size(), n_dirty_blocks, tri_count);
 }
 
 // journal bytes of a box image: 4 per sample, rounded up to 256

@@ -1,5 +1,5 @@
 // vtmc_ctx.h -- the context object behind include/vtmc.h and the small host helpers every translation unit of the C-ABI layer shares
-// (context.hip, vtmc_api.hip, terrain.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
+// (context.hip, vtmc_api.hip, terrain.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
 #ifndef VTMC_CTX_H
 #define VTMC_CTX_H
 #include "../../include/vtmc.h"
@@ -133,6 +133,10 @@ struct vtmc_ctx {
     VtmcPinnedBuf<unsigned char> h_rays;
     uint64_t perm_seed = 0;
     bool perm_valid = false;
+    // terrain_io.hip (vtmc_terrain_save / _load): per-brick flags, kinds, RAW counts, slots and RAW list, the scan's control words, and the
+    // two halves of the slice stage on the device and (pinned) on the host; all grow-only, the stages a fixed size
+    VtmcDevBuf tio_bricks, tio_stage;
+    VtmcPinnedBuf<unsigned char> h_tio;
     // chunk_io.hip: file image being assembled / last image read
     VtmcDevBuf chunk_image;
     // comm.hip: RCCL communicator (opaque ncclComm_t) + the padded send buffer of the counts all-gather
@@ -173,6 +177,9 @@ int check_dims(vtmc_ctx *ctx, int nx, int ny, int nz);
 BlockSpace dense_space(const float *d_base, int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz, int n_volumes, int64_t sv);
 int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp);   // sp then walks the (bx,by,bz) list
 int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, int32_t *tri_count);   // queued on the context's stream and finished
+// terrain.hip, for terrain_io.hip
+void history_clear(vtmc_ctx *ctx);
+int terrain_extract_all(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_count);   // extracts every block of the resident terrain, as an update that dirtied all of them
 }  // namespace vtmc
 
 #define VTMC_HIP(ctx, expr)                                                                                \

@@ -316,6 +316,33 @@ class Extractor:
         self._check(self._L.vtmc_terrain_read_samples(self._h, _ptr(grid), sx, sy, sz))
         return grid
 
+    # -- saving a session: the resident terrain as a sparse brick file (terrainfile.py) ---------------------------
+    def terrain_save(self, path, exact=False):
+        """Writes the resident terrain to `path` (classified, compacted and packed on the device); exact=True stores every brick raw.
+        Changes nothing in the context.  Returns the file's size in bytes."""
+        n = ctypes.c_int64()
+        self._check(self._L.vtmc_terrain_save(self._h, str(path).encode(), _lib.TERRAIN_SAVE_EXACT if exact else 0, ctypes.byref(n)))
+        return n.value
+
+    def terrain_load(self, path, extract=True):
+        """(Re)initialises the terrain from a file of terrain_save / terrainfile.write_terrain, with or without an earlier terrain_init,
+        and extracts every block unless extract=False.  Returns (number of dirty blocks, T)."""
+        nd, t = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._L.vtmc_terrain_load(self._h, str(path).encode(), 0 if extract else _lib.TERRAIN_LOAD_NO_EXTRACT,
+                                              ctypes.byref(nd), ctypes.byref(t)))
+        dims = (ctypes.c_int32 * 3)()
+        self._check(self._L.vtmc_terrain_device_grid(self._h, None, None, ctypes.byref(dims)))
+        self._terrain_dims = tuple(d - 2 for d in dims)   # for terrain_read_samples
+        return nd.value, t.value
+
+    def terrain_write_samples(self, grid):
+        """The inverse of terrain_read_samples: grid indexed [x, y, z], shape (W+2, E+2, H+2), any positive strides.  Clears the history,
+        extracts nothing."""
+        if tuple(grid.shape) != tuple(d + 2 for d in self._terrain_dims):
+            raise ValueError("grid shape %r does not match the terrain's samples" % (tuple(grid.shape),))
+        sx, sy, sz = elem_strides(grid)
+        self._check(self._L.vtmc_terrain_write_samples(self._h, _ptr(grid), sx, sy, sz))
+
     # -- ray picking: Physics.Raycast of the interactive edit (SceneManager.cs:114-131) on the device ---------------
     def terrain_raycast(self, origins, directions, max_distance=float("inf"), two_sided=False):
         """Nearest surface hit of each ray (world-space origins / directions, (n, 3)) on the resident terrain: a RAY_HIT_DTYPE
