@@ -7,10 +7,10 @@ import numpy as np
 import pytest
 
 import fields
+from extract_checks import ATOL, assert_tris_match, device_view_i32
 
 pytestmark = pytest.mark.gpu
 
-ATOL = 1e-5  # north_star tolerance for positions / normals
 
 
 @pytest.fixture
@@ -24,20 +24,6 @@ def ex():
     e = vt.Extractor(0)
     yield e
     e.close()
-
-
-def assert_tris_match(got, want, atol=ATOL):
-    assert len(got) == len(want)
-    assert np.array_equal(got["block"], want["block"])
-    worst = 0.0
-    for f in ("p0", "p1", "p2", "n0", "n1", "n2"):
-        g, w = got[f], want[f]
-        nan_g, nan_w = np.isnan(g), np.isnan(w)
-        assert np.array_equal(nan_g, nan_w), "NaN pattern differs in " + f
-        d = np.abs(np.where(nan_w, 0, g) - np.where(nan_w, 0, w))
-        worst = max(worst, float(d.max()) if d.size else 0.0)
-    assert worst <= atol, "max abs deviation %g > %g" % (worst, atol)
-    return worst
 
 
 def test_exact_mode_is_bit_compatible_with_oracle(ex, oracle_mod):
@@ -308,18 +294,6 @@ def test_device_volume_batch_matches_grid(ex, oracle_mod):
     vc = ex.copy_u32(vc_ptr, 16).reshape(8, 2)
     assert np.array_equal(vc[:, 1], [len(w) for w in want])
     assert np.array_equal(vc[:, 0], 3 * vc[:, 1])
-
-
-class _DeviceArray:
-    """Exposes a raw device pointer to torch through __cuda_array_interface__ (no copy, no HIP binding)."""
-
-    def __init__(self, ptr, count):
-        self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": "<i4", "data": (int(ptr), False), "version": 2}
-
-
-def device_view_i32(ptr, count):
-    import torch
-    return torch.as_tensor(_DeviceArray(ptr, count), device="cuda")
 
 
 def test_sharded_host_entry(ex, oracle_mod):

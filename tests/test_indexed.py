@@ -8,9 +8,8 @@ import numpy as np
 import pytest
 
 import fields
+from extract_checks import ATOL, FLOATS, check_against_oracle
 
-ATOL = 1e-5
-FLOATS = ("p0", "p1", "p2", "n0", "n1", "n2")
 
 
 def test_oracle_welded_mesh_deindexes_to_the_soup(oracle_mod):
@@ -43,28 +42,6 @@ def ex():
     e = vt.Extractor(0)
     yield e
     e.close()
-
-
-def check_against_oracle(ex, oracle_mod, g, blocks=None, exact_floats=False):
-    want_v, want_i, want_vo, want_to = oracle_mod.extract_grid_indexed(g, blocks)
-    soup, _, _ = oracle_mod.extract_grid(g, blocks, threads=8)
-    T = ex.extract_grid(g, blocks)
-    assert T == len(want_i)
-    verts, idx, voffs, toffs = ex.read_indexed_mesh()
-    assert np.array_equal(voffs, want_vo) and np.array_equal(toffs, want_to)
-    assert np.array_equal(idx, want_i)
-    for f in ("position", "normal"):
-        nan_w = np.isnan(want_v[f])
-        assert np.array_equal(np.isnan(verts[f]), nan_w)
-        d = np.abs(np.where(nan_w, 0, verts[f]) - np.where(nan_w, 0, want_v[f]))
-        worst = float(d.max()) if d.size else 0.0
-        assert worst <= (0.0 if exact_floats else ATOL), (f, worst)
-    back = oracle_mod.deindex(verts, idx, voffs, toffs)
-    assert np.array_equal(back["block"], soup["block"])
-    for f in FLOATS:
-        ok = ~np.isnan(soup[f])
-        assert np.abs(back[f][ok] - soup[f][ok]).max(initial=0.0) <= ATOL
-    return len(verts), T
 
 
 @pytest.mark.gpu

@@ -14,10 +14,8 @@ import numpy as np
 import pytest
 
 import fields
-from test_gpu_parity import device_view_i32
-from test_indexed import check_against_oracle
-from test_random_shapes import smooth_field
-from test_raycast import _cast, _long_rays
+from extract_checks import check_against_oracle, device_view_i32, smooth_field
+from surface_twin import _cast, _long_rays
 
 FAST_ATOL = 2e-6
 ROW = 19   # int32 words of one 76-byte record: 18 floats and the block id

@@ -8,12 +8,12 @@ import numpy as np
 import pytest
 
 import fields
+from extract_checks import ATOL, smooth_field
 
 # VTMC_FUZZ_SEEDS=200 widens the sweep for a one-off hunt (the default keeps the suite short)
 N_SEEDS = int(os.environ.get("VTMC_FUZZ_SEEDS", "12"))
 
 pytestmark = pytest.mark.gpu
-ATOL = 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -22,21 +22,6 @@ def ex():
     e = vt.Extractor(0)
     yield e
     e.close()
-
-
-def smooth_field(rng, n, order):
-    """A few random plane waves: surfaces of varying density, some cells with exact zeros."""
-    g = fields._idx((n[0] + 2, n[1] + 2, n[2] + 2), order)
-    x, y, z = np.meshgrid(*[np.arange(d + 2, dtype=np.float32) for d in n], indexing="ij")
-    acc = np.zeros(x.shape, np.float32)
-    for _ in range(rng.integers(1, 5)):
-        k = rng.normal(size=3).astype(np.float32) * np.float32(rng.uniform(0.05, 0.9))
-        acc += np.float32(rng.uniform(0.3, 1.0)) * np.sin(k[0] * x + k[1] * y + k[2] * z + np.float32(rng.uniform(0, 6.28)))
-    acc += np.float32(rng.uniform(-0.5, 0.5))
-    if rng.random() < 0.3:
-        acc = np.where(rng.random(acc.shape) < 0.05, np.float32(0.0), acc)
-    g[...] = acc.astype(np.float32)
-    return g
 
 
 def check(got, want):

@@ -1,19 +1,18 @@
-"""Ray picking held to float32 precision (test_raycast.tight_check_ray): every marching-cubes case and triangle slot aimed at on
+"""Ray picking held to float32 precision (surface_twin.tight_check_ray): every marching-cubes case and triangle slot aimed at on
 purpose, memory layouts and non-cubic boxes, the max_distance cut-off, the terrain entry point in a scaled and shifted world, and
 stream ordering.  The CPU tests show that the tight checker rejects the mistakes a rewrite of the kernel could make, and that the
 aimed ray sets reach every (case, slot) pair of the table.
 
-Ambiguous rays (test_raycast's rule), measured with the reference alone: the aimed rays 0 of 6560 (all-cases grid) and 0 of 13120
+Ambiguous rays (surface_twin's rule), measured with the reference alone: the aimed rays 0 of 6560 (all-cases grid) and 0 of 13120
 (64^3 random field); the layout rays 0, 1 and 0 of 1200 (the three box configurations); the terrain rays 0 of 600, one- and
 two-sided; the cut-off rays 2 of 240.  Each test's cap is set a little above its own rate.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 import fields
-from test_raycast import HIT_BYTES, Surface, _cast, _device, check_tight, compare, reference, report, tight_check_ray
+from surface_twin import (RAY_HIT_BYTES, DeviceGrid, Surface, _cast, _device, _rays_perlin, check_tight, compare, reference, report,
+                          tight_check_ray)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -326,12 +325,12 @@ def _cast_each(ex, d_g, n, st, origin, scale, o, d, mds, two_sided=False):
     import torch
     import volumetricterrain_amd as vt
     d_o, d_d = _device(o), _device(d)
-    d_h = torch.zeros(len(o) * HIT_BYTES, dtype=torch.uint8, device="cuda")
+    d_h = torch.zeros(len(o) * RAY_HIT_BYTES, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     for i, md in enumerate(mds):
-        ex.raycast_device(d_g, n, st, origin, scale, d_o.data_ptr() + 12 * i, d_d.data_ptr() + 12 * i, 1, d_h.data_ptr() + HIT_BYTES * i,
+        ex.raycast_device(d_g, n, st, origin, scale, d_o.data_ptr() + 12 * i, d_d.data_ptr() + 12 * i, 1, d_h.data_ptr() + RAY_HIT_BYTES * i,
                           float(md), two_sided)
-    return ex.copy_to_host(d_h.data_ptr(), len(o) * HIT_BYTES).view(vt.RAY_HIT_DTYPE)
+    return ex.copy_to_host(d_h.data_ptr(), len(o) * RAY_HIT_BYTES).view(vt.RAY_HIT_DTYPE)
 
 
 @pytest.mark.gpu
@@ -343,7 +342,6 @@ def test_max_distance_cut_off_moves_no_hit(oracle_mod):
     exact distance, point and normal (0, 1, 0), also with max_distance equal to that distance."""
     import torch
     import volumetricterrain_amd as vt
-    from test_raycast import _rays_perlin
     n, dim = 64, 66
     st = (1, dim, dim * dim)
     with vt.Extractor(0) as ex:
@@ -416,13 +414,11 @@ def test_terrain_raycast_in_a_scaled_shifted_world(oracle_mod):
         ex.terrain_init(64, 32, 48, scale, origin, 5)
         ex.terrain_update(mods)
         surf = Surface.of_grid(oracle_mod, ex.terrain_read_samples(), origin, scale)
-        p, st, dims = ctypes.c_void_p(), (ctypes.c_int64 * 3)(), (ctypes.c_int32 * 3)()
-        ex._check(ex._L.vtmc_terrain_device_grid(ex._h, ctypes.byref(p), ctypes.byref(st), ctypes.byref(dims)))
-        n = tuple(int(x) - 2 for x in dims)
-        assert n == (64, 32, 48)
+        dg = DeviceGrid.of_terrain(ex)
+        assert dg.n == (64, 32, 48)
         for two_sided in (False, True):
             hits = ex.terrain_raycast(O, D, two_sided=two_sided)
-            dev = _cast(ex, p.value, n, tuple(st), origin, scale, O, D, two_sided=two_sided)
+            dev = _cast(ex, dg.ptr, dg.n, dg.strides, origin, scale, O, D, two_sided=two_sided)
             assert hits.tobytes() == dev.tobytes(), two_sided
             ref = reference(surf, O, D, two_sided=two_sided)
             label = "scaled terrain two_sided %d" % two_sided
@@ -453,7 +449,6 @@ def test_fill_then_raycast_on_one_stream_without_a_host_sync():
     before the fill: the hits equal those of the synchronous fill and cast."""
     import torch
     import volumetricterrain_amd as vt
-    from test_raycast import _rays_perlin
     n, dim = 256, 258
     st = (1, dim, dim * dim)
     prm = vt.density_params("perlin3d", n)
@@ -465,13 +460,13 @@ def test_fill_then_raycast_on_one_stream_without_a_host_sync():
         assert (want["triangle"] >= 0).sum() > len(O) // 3
         g2 = torch.full((dim ** 3,), float("nan"), dtype=torch.float32, device="cuda")
         d_o, d_d = _device(O), _device(D)
-        d_h = torch.zeros(len(O) * HIT_BYTES, dtype=torch.uint8, device="cuda")
+        d_h = torch.zeros(len(O) * RAY_HIT_BYTES, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         s = torch.cuda.Stream()
         ex.density_fill_device(prm, [[0, 0, 0]], (dim,) * 3, st, 0, g2.data_ptr(), stream=s.cuda_stream, wait=False)
         ex.raycast_device(g2.data_ptr(), (n,) * 3, st, (0, 0, 0), 1.0, d_o.data_ptr(), d_d.data_ptr(), len(O), d_h.data_ptr(),
                           stream=s.cuda_stream)
-        got = ex.copy_to_host(d_h.data_ptr(), len(O) * HIT_BYTES, stream=s.cuda_stream).view(vt.RAY_HIT_DTYPE)
+        got = ex.copy_to_host(d_h.data_ptr(), len(O) * RAY_HIT_BYTES, stream=s.cuda_stream).view(vt.RAY_HIT_DTYPE)
         s.synchronize()
         assert got.tobytes() == want.tobytes()
         del s

@@ -2,7 +2,7 @@
 the Physics.SphereCast / CheckSphere / ClosestPoint queries a moving body makes against the MeshColliders (VoxelTerrain.cs:168, 464),
 against the surface vtmc_extract_grid emits in exact mode, checked against a CPU reference kept here.
 
-The reference takes the oracle's triangles of the same grid (test_raycast.Surface: oracle.extract_grid, exact arithmetic, placed in
+The reference takes the oracle's triangles of the same grid (surface_twin.Surface: oracle.extract_grid, exact arithmetic, placed in
 the world in float64), drops zero-area triangles and those of cells with a NaN corner, prefilters candidates by block AABBs grown by r,
 and evaluates every candidate in float64: a sphere cast is the minimum over face, edge (capsule) and vertex contacts with t = 0 for a
 triangle the ball touches at the start (Moller-Trumbore for r = 0); a closest point is Ericson's closest point on a triangle.  Ties go
@@ -30,10 +30,10 @@ import numpy as np
 import pytest
 
 import fields
-from test_raycast import Surface, compare as compare_rays, reference as ray_reference
+from surface_twin import DeviceGrid, Surface, _cast as _raycast, _device, _rays_perlin, compare as compare_rays, reference as ray_reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIT_BYTES = 48
+SPHERE_HIT_BYTES = 48   # sizeof(vtmc_sphere_hit); the 56-byte ray record is surface_twin.RAY_HIT_BYTES
 NEAR = 1e-7     # cells: runners-up (see the module docstring)
 PT_TOL = 2e-4   # cells
 
@@ -113,7 +113,7 @@ def ray_times(o, d, P):
 
 
 class SphereSurface:
-    """test_raycast.Surface plus what the sphere queries need: usable triangles, canonical codes, block AABBs."""
+    """surface_twin.Surface plus what the sphere queries need: usable triangles, canonical codes, block AABBs."""
 
     def __init__(self, oracle_mod, grid, origin=(0.0, 0.0, 0.0), scale=1.0, nan_grid=None):
         """nan_grid: `grid` with some samples set to NaN (the oracle is never run on NaN samples): the surface is grid's without the
@@ -283,7 +283,7 @@ def test_header_declares_and_library_exports_the_sphere_calls():
         assert re.search(r"int32_t\s+%s\s*\(" % name, text), name
         assert hasattr(lib, name), name
     assert "#define VTMC_SPHERE_MAX_RADIUS_CELLS 16" in text
-    assert vt.SPHERE_HIT_DTYPE.itemsize == HIT_BYTES
+    assert vt.SPHERE_HIT_DTYPE.itemsize == SPHERE_HIT_BYTES
     assert [vt.SPHERE_HIT_DTYPE.fields[f][1] for f in ("distance", "point", "normal", "block", "cell", "triangle")] == [0, 4, 16, 28, 40, 44]
 
 
@@ -368,53 +368,25 @@ def test_reference_sweep_contacts_edges_and_vertices():
 # ---------------------------------------------------------------------------------------------------------------------------------
 # GPU helpers
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _device(a):
-    import torch
-    return torch.from_numpy(np.array(a, copy=True, order="C")).cuda()
-
-
 def _cast(ex, g, n, strides, origin, scale, o, d, r, max_distance=float("inf"), two_sided=False):
     import torch
     import volumetricterrain_amd as vt
     d_o, d_d, d_r = _device(np.float32(o)), _device(np.float32(d)), _device(np.broadcast_to(np.float32(r), (len(o),)))
-    d_h = torch.full((len(o) * HIT_BYTES,), 0x5A, dtype=torch.uint8, device="cuda")
+    d_h = torch.full((len(o) * SPHERE_HIT_BYTES,), 0x5A, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     ex.spherecast_device(g, n, strides, origin, scale, d_o.data_ptr(), d_d.data_ptr(), d_r.data_ptr(), len(o), d_h.data_ptr(),
                          max_distance, two_sided)
-    return ex.copy_to_host(d_h.data_ptr(), len(o) * HIT_BYTES).view(vt.SPHERE_HIT_DTYPE)
+    return ex.copy_to_host(d_h.data_ptr(), len(o) * SPHERE_HIT_BYTES).view(vt.SPHERE_HIT_DTYPE)
 
 
 def _closest(ex, g, n, strides, origin, scale, c, r):
     import torch
     import volumetricterrain_amd as vt
     d_c, d_r = _device(np.float32(c)), _device(np.broadcast_to(np.float32(r), (len(c),)))
-    d_h = torch.full((len(c) * HIT_BYTES,), 0x5A, dtype=torch.uint8, device="cuda")
+    d_h = torch.full((len(c) * SPHERE_HIT_BYTES,), 0x5A, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     ex.closest_point_device(g, n, strides, origin, scale, d_c.data_ptr(), d_r.data_ptr(), len(c), d_h.data_ptr())
-    return ex.copy_to_host(d_h.data_ptr(), len(c) * HIT_BYTES).view(vt.SPHERE_HIT_DTYPE)
-
-
-def _raycast(ex, g, n, strides, origin, scale, o, d, max_distance=float("inf"), two_sided=False):
-    import torch
-    import volumetricterrain_amd as vt
-    d_o, d_d = _device(np.float32(o)), _device(np.float32(d))
-    d_h = torch.empty(len(o) * 56, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    ex.raycast_device(g, n, strides, origin, scale, d_o.data_ptr(), d_d.data_ptr(), len(o), d_h.data_ptr(), max_distance, two_sided)
-    return ex.copy_to_host(d_h.data_ptr(), len(o) * 56).view(vt.RAY_HIT_DTYPE)
-
-
-class DeviceGrid:
-    """A host grid [x, y, z] on the device, x fastest (order 'x') or z fastest (order 'z')."""
-
-    def __init__(self, grid, order="x"):
-        g = np.asarray(grid, np.float32)
-        mem = g.transpose(2, 1, 0) if order == "x" else g
-        self.t = _device(mem.ravel())
-        dx, dy, dz = g.shape
-        self.strides = (1, dx, dx * dy) if order == "x" else (dy * dz, dz, 1)
-        self.n = (dx - 2, dy - 2, dz - 2)
-        self.ptr = self.t.data_ptr()
+    return ex.copy_to_host(d_h.data_ptr(), len(c) * SPHERE_HIT_BYTES).view(vt.SPHERE_HIT_DTYPE)
 
 
 def _sweeps(n, k, rng, r_max):
@@ -454,7 +426,7 @@ def test_argument_rules_return_their_code_and_write_nothing():
         o = np.zeros((2, 3), np.float32)
         d = np.tile(np.float32([0, -1, 0]), (2, 1))
         r = np.full(2, 0.5, np.float32)
-        hits = np.full(2 * HIT_BYTES, 0x5A, np.uint8)
+        hits = np.full(2 * SPHERE_HIT_BYTES, 0x5A, np.uint8)
         p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
         # before terrain_init
         assert L.vtmc_terrain_spherecast(h, p(o), p(d), p(r), 2, 1.0, 0, p(hits)) == vt._lib.ERR_NO_RESULT
@@ -493,7 +465,7 @@ def test_argument_rules_return_their_code_and_write_nothing():
         # the device calls
         g = torch.zeros(34 ** 3, dtype=torch.float32, device="cuda")
         org = (ctypes.c_float * 3)(0, 0, 0)
-        dh = torch.full((2 * HIT_BYTES,), 0x5A, dtype=torch.uint8, device="cuda")
+        dh = torch.full((2 * SPHERE_HIT_BYTES,), 0x5A, dtype=torch.uint8, device="cuda")
         do, dd, dr = _device(o), _device(d), _device(r)
         args = lambda n, md, fl, hp: (h, g.data_ptr(), 32, 32, 32, 1, 34, 34 * 34, ctypes.byref(org), 1.0, do.data_ptr(), dd.data_ptr(),
                                       dr.data_ptr(), n, md, fl, hp, None)
@@ -579,7 +551,6 @@ def test_zero_radius_equals_the_raycast(oracle_mod):
     """4096 rays on perlin 64^3, single- and two-sided: the r = 0 sweep names the raycast's triangle at the raycast's distance for every
     ray the ray reference does not call ambiguous; and both agree with that reference."""
     import volumetricterrain_amd as vt
-    from test_raycast import _rays_perlin
     n = 64
     with vt.Extractor(0) as ex:
         g, st = _perlin(vt, ex, (n, n, n))

@@ -3,11 +3,13 @@ density write + dirty-block selection (VoxelTerrain.cs:121-149, 262-325) against
 restatement oracle/terrain_ref.c, and the restatement itself against analytic answers.
 
 Grid samples are FP32 results of the reference's own expression order: the bar is bit-exact.
+The spec -> modifier constructors are terrain_twin.py's, the twin the other terrain tests share.
 """
 import numpy as np
 import pytest
 
 import volumetricterrain_amd as vt
+from terrain_twin import gpu_mod, island_heightmap, oracle_mod_of
 
 
 SPECS = [
@@ -19,32 +21,12 @@ SPECS = [
 ]
 
 
-def island_heightmap(res=(48, 40)):
-    """A smooth synthetic island: what Island.GetElevation would have filled in (IslandModifier.cs:85-91)."""
-    u = np.linspace(-1, 1, res[0], dtype=np.float32)[:, None]
-    v = np.linspace(-1, 1, res[1], dtype=np.float32)[None, :]
-    return (14.0 * np.exp(-2.5 * (u * u + v * v)) + 1.5 * np.sin(5 * u) * np.cos(4 * v) + 3.0).astype(np.float32)
-
-
-def build(spec):
-    kind, args = spec
-    return {"plane": vt.PlaneModifier, "sphere": vt.SphereModifier, "cylinder": vt.CylinderModifier,
-            "island": vt.IslandModifier}[kind](*args)
-
-
-def build_oracle(oracle_mod, spec):
-    """The same modifier through the oracle's own (independent) bound formulas."""
-    kind, args = spec
-    return {"plane": oracle_mod.plane_modifier, "sphere": oracle_mod.sphere_modifier,
-            "cylinder": oracle_mod.cylinder_modifier, "island": oracle_mod.heightmap_modifier}[kind](*args)
-
-
 def queue():
-    return [build(s) for s in SPECS]
+    return [gpu_mod(s) for s in SPECS]
 
 
 def oracle_mods(oracle_mod, specs):
-    return [build_oracle(oracle_mod, s) for s in specs]
+    return [oracle_mod_of(oracle_mod, s) for s in specs]
 
 
 def test_host_bounds_match_the_oracles_restatement(oracle_mod):
@@ -122,7 +104,7 @@ def test_gpu_terrain_matches_oracle_bitwise(oracle_mod):
             assert np.abs(got[f] - want[f]).max() <= 1e-5
         # interactive edits: erosions + a modifier outside the world, one Update each
         for spec in SPECS[2:]:
-            n_dirty, T = ex.terrain_update([build(spec)])
+            n_dirty, T = ex.terrain_update([gpu_mod(spec)])
             want_dirty = ref.update(oracle_mods(oracle_mod, [spec]))
             assert np.array_equal(ex.terrain_read_samples(), ref.grid)
             assert np.array_equal(ex.terrain_dirty_blocks(), want_dirty)
@@ -146,7 +128,7 @@ def test_gpu_terrain_scaled_world_and_full_rebuild(oracle_mod):
     with vt.Extractor(0) as ex:
         ex.terrain_init(*dims, scale, origin, seed)
         ref = oracle_mod.Terrain(*dims, scale, origin, seed)
-        n_dirty, T = ex.terrain_update([build(sp) for sp in specs])
+        n_dirty, T = ex.terrain_update([gpu_mod(sp) for sp in specs])
         want_dirty = ref.update(oracle_mods(oracle_mod, specs))
         assert n_dirty == len(want_dirty) == 8 * 4 * 8
         assert np.array_equal(ex.terrain_read_samples(), ref.grid)
@@ -212,7 +194,7 @@ def test_gpu_world_build_with_island_heightmap(oracle_mod):
     with vt.Extractor(0) as ex:
         ex.terrain_init(*dims, scale, origin, seed)
         ref = oracle_mod.Terrain(*dims, scale, origin, seed)
-        n_dirty, T = ex.terrain_update([build(s) for s in specs])
+        n_dirty, T = ex.terrain_update([gpu_mod(s) for s in specs])
         want_dirty = ref.update(oracle_mods(oracle_mod, specs))
         assert np.array_equal(ex.terrain_read_samples(), ref.grid)
         assert n_dirty == len(want_dirty) == 8 * 4 * 8

@@ -1,7 +1,6 @@
-"""Sculpt brushes on the device-resident terrain (VTMC_MOD_SMOOTH / VTMC_MOD_FLATTEN): every write bit for bit against a numpy FP32
-restatement of include/vtmc.h's rule, in its order of operations (numpy's float32 + - * / sqrt are correctly rounded and never
-fused, as the library's are under -ffp-contract=off).  Queues that mix brushes with kinds 0-3 run the reference kinds on the CPU twin
-oracle.Terrain and the brushes on its memory, one event number each.
+"""Sculpt brushes on the device-resident terrain (VTMC_MOD_SMOOTH / VTMC_MOD_FLATTEN): every write bit for bit against the twin of
+terrain_twin.py, whose brush_values is a numpy FP32 restatement of include/vtmc.h's rule.  Queues that mix brushes with kinds 0-3 run
+the reference kinds on the CPU twin oracle.Terrain and the brushes on its memory, one event number each (terrain_twin.twin_update).
 
 Grids are compared as uint32; triangles as in test_terrain.py: offsets and `block` exact, floats within 1e-5."""
 import os
@@ -12,7 +11,8 @@ import pytest
 
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib
-from terrain_twin import assert_grid, assert_triangles, bits, gpu_mod, oracle_mod_of
+import terrain_twin
+from terrain_twin import assert_grid, assert_triangles, assert_update, bits, brush_values, invalid, step_bytes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -21,131 +21,8 @@ WORLD = [("plane", (9.375, (-1, -1), (70, 70), True)), ("sphere", ((20.5, 10.25,
          ("sphere", ((44.0, 9.5, 16.0), 6.0, False)), ("cylinder", ((5.0, 12.0, 5.0), (1.0, 0.25, 0.5), 50.0, 3.0, True))]
 
 
-# -- the numpy reference ----------------------------------------------------------------------------------------------------------------
-def saturating_int(v):
-    return -2 ** 31 if v <= -2147483648.0 else (2 ** 31 - 1 if v >= 2147483648.0 else int(v))
-
-
-def sample_range(m, dims_s, scale, origin):
-    """terrain.hip's sample_range: ([low], [up]) clamped as the dirty rule reads them, and the box (first sample, extent)."""
-    low, up, first, ext = [], [], [], []
-    for k in range(3):
-        top = dims_s[k] - 1
-        lo = max(saturating_int(np.floor((f32(m.lower[k]) - f32(origin[k])) / f32(scale))), 0)
-        hi = min(saturating_int(np.ceil((f32(m.upper[k]) - f32(origin[k])) / f32(scale))), top)
-        e = hi - lo + 1
-        low.append(lo)
-        up.append(hi)
-        first.append(lo)
-        ext.append(0 if e <= 0 or lo > top else min(e, top - lo + 1))
-    return low, up, first, ext
-
-
-def dirty_ids(low, up, nb):
-    """mark_dirty_blocks: up >= 8b && low <= 8b + 8 on every axis."""
-    r = []
-    for k in range(3):
-        lo, hi = low[k] - 8, up[k]
-        f = 0 if lo <= 0 else (lo + 7) // 8
-        last = min(-1 if hi < 0 else hi // 8, nb[k] - 1)
-        if f > last:
-            return set()
-        r.append(range(f, last + 1))
-    return {bx + nb[0] * (by + nb[1] * bz) for bz in r[2] for by in r[1] for bx in r[0]}
-
-
-def image_bytes(ext):
-    n = ext[0] * ext[1] * ext[2]
-    return 0 if min(ext) <= 0 else (4 * n + 255) // 256 * 256
-
-
-def brush_values(mem, m, first, ext, scale, origin):
-    """New values of the box first..first+ext of mem ([z, y, x], the pre-brush samples) under brush struct m."""
-    (lx, ly, lz), (dx, dy, dz) = first, ext
-    Dz, Dy, Dx = mem.shape
-    c0, c1, c2, r, s = (f32(v) for v in m.p[0:5])
-    S = mem[lz:lz + dz, ly:ly + dy, lx:lx + dx]
-    px = np.arange(lx, lx + dx).astype(f32) * f32(scale) + f32(origin[0])
-    py = np.arange(ly, ly + dy).astype(f32) * f32(scale) + f32(origin[1])
-    pz = np.arange(lz, lz + dz).astype(f32) * f32(scale) + f32(origin[2])
-    ddx, ddy, ddz = px - c0, py - c1, pz - c2
-    d = np.sqrt(((ddx * ddx)[None, None, :] + (ddy * ddy)[None, :, None]) + (ddz * ddz)[:, None, None])
-    t = f32(1) - d / r
-    t = t + t
-    t = np.where(t < 0, f32(0), np.where(t > 1, f32(1), t))
-    w = s * t
-    if m.kind == _lib.MOD_SMOOTH:
-        zi = np.clip(np.arange(lz - 1, lz + dz + 1), 0, Dz - 1)
-        yi = np.clip(np.arange(ly - 1, ly + dy + 1), 0, Dy - 1)
-        xi = np.clip(np.arange(lx - 1, lx + dx + 1), 0, Dx - 1)
-        G = mem[np.ix_(zi, yi, xi)]
-        R = (G[:, :, :-2] + G[:, :, 1:-1]) + G[:, :, 2:]
-        P = (R[:, :-2] + R[:, 1:-1]) + R[:, 2:]
-        T = ((P[:-2] + P[1:-1]) + P[2:]) / f32(27)
-    else:
-        n0, n1, n2 = (f32(v) for v in m.p[5:8])
-        g = ((n0 * (c0 - px)[None, None, :] + n1 * (c1 - py)[None, :, None]) + n2 * (c2 - pz)[:, None, None]) / f32(scale)
-        T = np.where(g < -1, f32(-1), np.where(g > 1, f32(1), g))
-    out = S + (T - S) * w
-    return np.where(w == 0, S, out).astype(f32)
-
-
-def apply_brush(ref, m):
-    """One brush on the twin's memory, one event number; returns the block ids it dirties."""
-    dims_s = tuple(d + 2 for d in ref.dims)
-    low, up, first, ext = sample_range(m, dims_s, ref.scale, ref.origin)
-    if min(ext) > 0:
-        (lx, ly, lz), (dx, dy, dz) = first, ext
-        ref._mem[lz:lz + dz, ly:ly + dy, lx:lx + dx] = brush_values(ref._mem, m, first, ext, ref.scale, ref.origin)
-    ref.events += 1
-    nb = tuple(d // 8 for d in ref.dims)
-    return dirty_ids(low, up, nb)
-
-
-# -- device / twin plumbing -------------------------------------------------------------------------------------------------------------
-def twin_update(ref, oracle_mod, specs):
-    """The queue on the twin: reference kinds through oracle.Terrain, brushes through numpy.  Returns the dirty list by block id."""
-    nb = tuple(d // 8 for d in ref.dims)
-    ids = set()
-    for spec in specs:
-        if spec[0] in ("smooth", "flatten"):
-            ids |= apply_brush(ref, gpu_mod(spec).to_struct())
-        else:
-            d = ref.update([oracle_mod_of(oracle_mod, spec)])
-            ids |= {int(bx + nb[0] * (by + nb[1] * bz)) for bx, by, bz in d}
-    ids = np.array(sorted(ids), np.int64)
-    return np.stack([ids % nb[0], (ids // nb[0]) % nb[1], ids // (nb[0] * nb[1])], axis=1).astype(np.int32).reshape(-1, 3)
-
-
-def both_update(ex, ref, oracle_mod, specs):
-    got = ex.terrain_update([gpu_mod(s) for s in specs])
-    return got, twin_update(ref, oracle_mod, specs)
-
-
-def assert_update(ex, ref, oracle_mod, specs):
-    (n_dirty, T), dirty = both_update(ex, ref, oracle_mod, specs)
-    assert_grid(ex, ref.grid)
-    assert n_dirty == len(dirty) and np.array_equal(ex.terrain_dirty_blocks(), dirty)
-    assert_triangles(ex, oracle_mod, ref.grid, dirty, T)
-    return n_dirty, T
-
-
 def world(oracle_mod, history=0):
-    ex = vt.Extractor(0)
-    ex.terrain_init(*DIMS, SCALE, ORIGIN, SEED)
-    ref = oracle_mod.Terrain(*DIMS, SCALE, ORIGIN, SEED)
-    both_update(ex, ref, oracle_mod, WORLD)
-    assert_grid(ex, ref.grid)
-    if history:
-        ex.terrain_set_history(history)
-    return ex, ref
-
-
-def invalid(ex, mods):
-    with pytest.raises(vt.VtmcError) as e:
-        ex.terrain_update(mods)
-    assert e.value.code == _lib.ERR_INVALID_ARG
-    return str(e.value)
+    return terrain_twin.world(oracle_mod, DIMS, SCALE, ORIGIN, SEED, WORLD, history)
 
 
 def raw_brush(kind, p):
@@ -308,11 +185,6 @@ def test_gpu_flatten_puts_the_surface_on_the_plane():
         hit = ex.terrain_raycast(o[None], (-n).astype(f32)[None])[0]
         assert hit["triangle"] >= 0 and abs(float(hit["distance"]) - 5.0) <= 1e-3
         assert np.abs(hit["point"].astype(np.float64) - c).max() <= 1e-3
-
-
-def step_bytes(ref, specs):
-    dims_s = tuple(d + 2 for d in ref.dims)
-    return sum(image_bytes(sample_range(gpu_mod(s).to_struct(), dims_s, ref.scale, ref.origin)[3]) for s in specs)
 
 
 HISTORY_STEPS = [

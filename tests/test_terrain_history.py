@@ -1,6 +1,6 @@
 """Undo / redo of terrain edits (vtmc_terrain_set_history / _undo / _redo / _history): the journal restores the resident grid bit for
-bit and an undo or redo returns what an update of the same dirty set returns.  The CPU twin oracle.Terrain is rewound by writing a
-saved copy into its memory while its event counter runs on, as the library's does.
+bit and an undo or redo returns what an update of the same dirty set returns.  The CPU twin (terrain_twin.py, on oracle.Terrain) is
+rewound by writing a saved copy into its memory while its event counter runs on, as the library's does.
 
 Grids are compared as uint32 (NaN payloads, -0); triangles as in test_terrain.py: offsets and `block` exact, floats within 1e-5."""
 import os
@@ -11,10 +11,9 @@ import pytest
 
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib
-from terrain_twin import assert_grid, assert_triangles, bits, gpu_mod, oracle_mod_of
+from terrain_twin import assert_grid, assert_triangles, bits, both_update, gpu_mod, island_heightmap, no_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NO_RESULT = _lib.ERR_NO_RESULT
 PROTOTYPES = [
     "int32_t vtmc_terrain_set_history(vtmc_ctx *ctx, int64_t max_bytes);",
     "int32_t vtmc_terrain_undo(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_count);",
@@ -31,18 +30,6 @@ STEPS = [
     [("cylinder", ((5.0, 12.0, 5.0), (1.0, 0.25, 0.5), 30.0, 3.0, False))],
     [("sphere", ((30.0, 10.0, 24.0), 6.0, True)), ("sphere", ((33.0, 11.0, 26.0), 5.0, False))],  # two overlapping boxes
 ]
-
-
-def both_update(ex, ref, oracle_mod, specs):
-    """The same queue on the device and on the twin; returns the device's (n_dirty, T) and the twin's dirty list."""
-    got = ex.terrain_update([gpu_mod(s) for s in specs])
-    return got, ref.update([oracle_mod_of(oracle_mod, s) for s in specs])
-
-
-def no_result(fn):
-    with pytest.raises(vt.VtmcError) as e:
-        fn()
-    assert e.value.code == NO_RESULT
 
 
 # -- CPU: the interface ---------------------------------------------------------------------------------------------------------------
@@ -218,16 +205,10 @@ def test_gpu_history_is_off_by_default(oracle_mod):
         assert_grid(ex, ref.grid)
 
 
-def island_heightmap(res=(48, 40)):
-    u = np.linspace(-1, 1, res[0], dtype=np.float32)[:, None]
-    v = np.linspace(-1, 1, res[1], dtype=np.float32)[None, :]
-    return (28.0 * np.exp(-2.5 * (u * u + v * v)) + 3.0 * np.sin(5 * u) * np.cos(4 * v) + 6.0).astype(np.float32)
-
-
 @pytest.mark.gpu
 def test_gpu_full_rebuild_undo(oracle_mod):
     dims, seed = (128, 48, 128), 77
-    specs = [("island", (island_heightmap(), 128.0, 128.0, 60.0, True)),
+    specs = [("island", (island_heightmap(height=28.0), 128.0, 128.0, 60.0, True)),
              ("cylinder", ((16.0, 20.0, 20.0), (1.0, -0.1, 0.6), 80.0, 3.0, False))]
     n_blocks = 16 * 6 * 16
     with vt.Extractor(0) as ex:

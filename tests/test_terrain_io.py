@@ -1,6 +1,6 @@
 """Saving a session: the resident terrain as a sparse brick file (vtmc_terrain_save / _load / _write_samples, terrainfile.py).
 
-The CPU half checks the format's numpy mirror on a twin world (oracle.Terrain plus the numpy smooth brush of test_terrain_brushes.py):
+The CPU half checks the format's numpy mirror on a twin world (terrain_twin.py: oracle.Terrain plus the numpy smooth brush):
 RAW bricks survive bit for bit, elided samples come back inside their sign class, and -- the point of the brick rule -- the oracle's
 full extraction of the reconstructed grid is the extraction of the original grid, record for record.  The GPU half checks the library
 against that mirror (kind tables, files read across, grids as uint32) and the same mesh exactness on the device, byte for byte.
@@ -17,8 +17,8 @@ import pytest
 
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib, terrainfile as tf
-from terrain_twin import assert_grid, assert_triangles, bits, gpu_mod, oracle_mod_of
-from test_terrain_brushes import apply_brush
+from surface_twin import DeviceGrid
+from terrain_twin import assert_grid, assert_triangles, bits, gpu_mod, twin_update, world
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -51,24 +51,11 @@ def plant(grid):
     w[NEG0_AT] = NEG0_BITS
 
 
-def twin_apply(ref, oracle_mod, specs):
-    """The queue on the twin, one event number per modifier; returns the dirty list by block id."""
-    nb = tuple(d // 8 for d in ref.dims)
-    ids = set()
-    for spec in specs:
-        if spec[0] == "smooth":
-            ids |= apply_brush(ref, gpu_mod(spec).to_struct())
-        else:
-            ids |= {int(bx + nb[0] * (by + nb[1] * bz)) for bx, by, bz in ref.update([oracle_mod_of(oracle_mod, spec)])}
-    ids = np.array(sorted(ids), np.int64)
-    return np.stack([ids % nb[0], (ids // nb[0]) % nb[1], ids // (nb[0] * nb[1])], axis=1).astype(np.int32).reshape(-1, 3)
-
-
 def twin_world(oracle_mod):
     """The twin world's grid ([x, y, z], read-only) and its event counter; built once."""
     if "world" not in _cache:
         ref = oracle_mod.Terrain(*DIMS, SCALE, ORIGIN, SEED)
-        twin_apply(ref, oracle_mod, WORLD)
+        twin_update(ref, oracle_mod, WORLD)
         plant(ref.grid)
         grid = ref.grid.copy(order="F")   # x fastest
         grid.setflags(write=False)
@@ -254,23 +241,14 @@ def test_mirror_rejects_hostile_files(oracle_mod, tmp_path_factory, tmp_path):
 def gpu_world(oracle_mod, history=0):
     """The twin world on the device, by the same queue (so the event counters agree), the NaN and the -0 written through
     terrain_write_samples."""
-    grid, events = twin_world(oracle_mod)
-    ex = vt.Extractor(0)
-    ex.terrain_init(*DIMS, SCALE, ORIGIN, SEED)
-    ex.terrain_update([gpu_mod(s) for s in WORLD])
+    ex, _ = world(oracle_mod, DIMS, SCALE, ORIGIN, SEED, WORLD)
     g = ex.terrain_read_samples()
     plant(g)
     ex.terrain_write_samples(g)
-    assert_grid(ex, grid)
+    assert_grid(ex, twin_world(oracle_mod)[0])
     if history:
         ex.terrain_set_history(history)
     return ex
-
-
-def device_grid(ex):
-    p, st, dims = ctypes.c_void_p(), (ctypes.c_int64 * 3)(), (ctypes.c_int32 * 3)()
-    ex._check(ex._L.vtmc_terrain_device_grid(ex._h, ctypes.byref(p), ctypes.byref(st), ctypes.byref(dims)))
-    return p.value, tuple(int(d) - 2 for d in dims), tuple(int(s) for s in st)
 
 
 def full_mesh(ex, indexed):
@@ -356,8 +334,8 @@ def test_gpu_mesh_is_exact_across_save_and_load(oracle_mod, tmp_path, fast_math,
     with gpu_world(oracle_mod) as ex:
         ex.set_tuning(emit_fast_math=fast_math)
         ex.set_output_mode(indexed)
-        p, n, strides = device_grid(ex)
-        T = ex.extract_volumes_device(p, n, strides)
+        dg = DeviceGrid.of_terrain(ex)
+        T = ex.extract_volumes_device(dg.ptr, dg.n, dg.strides)
         before, before_queries = full_mesh(ex, indexed), queries(ex)
         ex.terrain_save(path)
     assert (tf.read_header(path)["n_raw"] + 1) * 2 < 9 * 9 * 7   # most of the grid was elided
@@ -407,7 +385,7 @@ def test_gpu_state_after_load(oracle_mod, tmp_path):
             ex.terrain_undo()
         assert e.value.code == NO_RESULT
         n_dirty, T = ex.terrain_update([gpu_mod(s) for s in AFTER])
-        dirty = twin_apply(ref, oracle_mod, AFTER)
+        dirty = twin_update(ref, oracle_mod, AFTER)
         assert_grid(ex, ref.grid)   # the clamp draws of the edit hashed events saved + 2, saved + 3
         assert n_dirty == len(dirty) and np.array_equal(ex.terrain_dirty_blocks(), dirty)
         assert_triangles(ex, oracle_mod, ref.grid, dirty, T)
@@ -472,9 +450,9 @@ def test_gpu_write_samples_in_every_order(oracle_mod):
             assert np.array_equal(bits(ex.terrain_read_samples()), bits(field)), name
             assert np.array_equal(bits(ex.terrain_read_samples(order="z")), bits(field)), name
         ex.terrain_write_samples(clean)   # the field without the planted specials: its mesh is the oracle's
-        p, n, strides = device_grid(ex)
-        assert n == dims
-        T = ex.extract_volumes_device(p, n, strides)
+        dg = DeviceGrid.of_terrain(ex)
+        assert dg.n == dims
+        T = ex.extract_volumes_device(dg.ptr, dg.n, dg.strides)
         assert T > 500
         assert_triangles(ex, oracle_mod, clean, oracle_mod.all_blocks(*dims), T)
         with pytest.raises(ValueError):

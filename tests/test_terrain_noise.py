@@ -1,8 +1,8 @@
 """The noise modifier of the device-resident terrain (VTMC_MOD_NOISE: fBm, billow, ridged multifractal): every write bit for bit against
-a numpy FP32 restatement of include/vtmc.h's rule, in its order of operations (numpy's float32 + - * floor abs are correctly rounded and
-never fused, as the library's are under -ffp-contract=off), and a numpy twin of the clamp draws (terrain_uniform / clamp_drawn).
+the twin of terrain_twin.py, whose noise_density is a numpy FP32 restatement of include/vtmc.h's rule and whose csg_write restates the
+clamp draws (terrain_uniform / clamp_drawn).
 
-The yardstick is itself checked on the CPU against the committed oracle, not against the code under test: the twin's fBm equals
+That yardstick is itself checked here on the CPU against the committed oracle, not against the code under test: the twin's fBm equals
 oracle/density_ref.c bit for bit, its permutation equals the oracle's, and its clamp draws and add / erode rule reproduce an oracle.Terrain
 update.  Queues that mix kinds run the reference kinds on oracle.Terrain and brushes and noise on its memory, one event number each.
 
@@ -16,196 +16,21 @@ import pytest
 
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib
-from terrain_twin import assert_grid, assert_triangles, bits, gpu_mod, oracle_mod_of
-from test_terrain_brushes import WORLD, apply_brush, dirty_ids, image_bytes, sample_range
+import terrain_twin
+from terrain_twin import (assert_grid, assert_triangles, assert_update, bits, csg_write, gpu_mod, invalid, noise_density, oracle_mod_of,
+                          permutation, positions, sample_range, step_bytes)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-f32, u64 = np.float32, np.uint64
+f32 = np.float32
 DIMS, SEED = (64, 24, 48), 4321
+WORLD = [("plane", (9.375, (-1, -1), (70, 70), True)), ("sphere", ((20.5, 10.25, 30.0), 7.5, True)),
+         ("sphere", ((44.0, 9.5, 16.0), 6.0, False)), ("cylinder", ((5.0, 12.0, 5.0), (1.0, 0.25, 0.5), 50.0, 3.0, True))]
 PLACES = [(1.0, (0.0, 0.0, 0.0)), (0.5, (-3.25, 1.5, 2.125))]   # (voxel scale, terrain origin)
 BASES = ("fbm", "billow", "ridged")
 
 
-# -- the numpy reference ----------------------------------------------------------------------------------------------------------------
-def permutation(seed):
-    """density_permutation: Fisher-Yates driven by SplitMix64(seed)."""
-    M = (1 << 64) - 1
-    perm, s = list(range(256)), seed & M
-    for i in range(255, 0, -1):
-        s = (s + 0x9E3779B97F4A7C15) & M
-        z = s
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
-        z ^= z >> 31
-        j = z % (i + 1)
-        perm[i], perm[j] = perm[j], perm[i]
-    return np.array(perm, np.int64)
-
-
-def fade(t):
-    return t * t * t * (t * (t * f32(6) - f32(15)) + f32(10))
-
-
-def mix(t, a, b):
-    return a + t * (b - a)
-
-
-def grad(h, x, y, z):
-    h = h & 15
-    u = np.where(h < 8, x, y)
-    v = np.where(h < 4, y, np.where((h == 12) | (h == 14), x, z))
-    return np.where((h & 1) == 0, u, -u) + np.where((h & 2) == 0, v, -v)
-
-
-def noise3(perm, x, y, z):
-    """Improved noise on float32 arrays of one shape; lattice coordinates stay far below 2^24 (the library rejects the rest)."""
-    fx, fy, fz = np.floor(x), np.floor(y), np.floor(z)
-    X, Y, Z = fx.astype(np.int64) & 255, fy.astype(np.int64) & 255, fz.astype(np.int64) & 255
-    x, y, z = x - fx, y - fy, z - fz
-    u, v, w = fade(x), fade(y), fade(z)
-    P = lambda i: perm[i & 255]   # noqa: E731
-    A = P(X) + Y
-    AA, AB = P(A) + Z, P(A + 1) + Z
-    B = P(X + 1) + Y
-    BA, BB = P(B) + Z, P(B + 1) + Z
-    one = f32(1)
-    return mix(w,
-               mix(v, mix(u, grad(P(AA), x, y, z), grad(P(BA), x - one, y, z)),
-                   mix(u, grad(P(AB), x, y - one, z), grad(P(BB), x - one, y - one, z))),
-               mix(v, mix(u, grad(P(AA + 1), x, y, z - one), grad(P(BA + 1), x - one, y, z - one)),
-                   mix(u, grad(P(AB + 1), x, y - one, z - one), grad(P(BB + 1), x - one, y - one, z - one))))
-
-
-def noise_density(perm, px, py, pz, octaves, basis, f, L, g, a=1.0, b=0.0, rs=0.0, rc=0.0, h=1.0):
-    """q of include/vtmc.h at world positions px, py, pz (float32, broadcast to one [z, y, x] shape)."""
-    f, L, g, a, b, rs, rc, h = (f32(v) for v in (f, L, g, a, b, rs, rc, h))
-    px, py, pz = np.broadcast_arrays(px, py, pz)
-    x, y, z = px * f, py * f, pz * f
-    amp, total, w = f32(1), np.zeros(px.shape, f32), np.ones(px.shape, f32)
-    for _ in range(octaves):
-        n = noise3(perm, x, y, z)
-        if basis == 0:
-            total = total + amp * n
-        elif basis == 1:
-            t = np.abs(n)
-            t = t + t
-            t = t - f32(1)
-            total = total + amp * t
-        else:
-            r = h - np.abs(n)
-            r = r * r
-            r = r * w
-            w = r + r
-            w = np.where(w < 0, f32(0), np.where(w > 1, f32(1), w))
-            total = total + amp * r
-        x, y, z = x * L, y * L, z * L
-        amp = f32(amp * g)
-    q = a * total
-    q = q + b
-    q = q - (py - rc) * rs
-    assert q.dtype == f32
-    return q
-
-
-def terrain_uniform(seed, event, sample, draw):
-    """terrain.hip's counter hash: sample a uint64 array; 24 bits * 2^-24, exact in float32."""
-    with np.errstate(over="ignore"):
-        z = (u64(seed) ^ u64(event << 40) ^ (sample << u64(2)) ^ u64(draw)) + u64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> u64(30))) * u64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> u64(27))) * u64(0x94D049BB133111EB)
-    z = z ^ (z >> u64(31))
-    return (z >> u64(40)).astype(f32) * f32(5.9604644775390625e-08)
-
-
-def clamp_drawn(v, seed, event, sample, k):
-    """Mathf.Clamp(v, void, full), void = draw k - 2, full = draw k + 1 + 1.  Returns (values, clamped low, clamped high)."""
-    lo = terrain_uniform(seed, event, sample, k) - f32(2)
-    hi = terrain_uniform(seed, event, sample, k + 1) + f32(1)
-    low, high = (v < -1) & (v < lo), ~(v < -1) & (v > 1) & (v > hi)
-    return np.where(low, lo, np.where(high, hi, v)), low, high
-
-
-TAKEN = {"low": 0, "high": 0}   # clamp branches the twin took on a modifier's own density (asserted where the issue asks)
-
-
-def csg_write(ref, first, ext, q, add):
-    """The write of kinds 0-3 and 8 on the twin's memory: q the density of the box [z, y, x]; takes the next event number."""
-    (lx, ly, lz), (dx, dy, dz) = first, ext
-    event = ref.events + 1
-    if min(ext) > 0:
-        Dx, Dy = ref.dims[0] + 2, ref.dims[1] + 2
-        zz, yy, xx = np.meshgrid(np.arange(lz, lz + dz, dtype=u64), np.arange(ly, ly + dy, dtype=u64), np.arange(lx, lx + dx, dtype=u64),
-                                 indexing="ij")
-        sample = xx + u64(Dx) * (yy + u64(Dy) * zz)
-        md, low, high = clamp_drawn(q, ref.seed, event, sample, 0)
-        TAKEN["low"] += int(low.sum())
-        TAKEN["high"] += int(high.sum())
-        S = ref._mem[lz:lz + dz, ly:ly + dy, lx:lx + dx]
-        if add:
-            r = np.where(S > md, S, md)
-        else:
-            r, _, _ = clamp_drawn(np.where(S < -md, S, -md), ref.seed, event, sample, 2)
-        ref._mem[lz:lz + dz, ly:ly + dy, lx:lx + dx] = r.astype(f32)
-    ref.events = event
-
-
-def positions(ref, first, ext):
-    return [np.arange(first[k], first[k] + ext[k]).astype(f32) * f32(ref.scale) + f32(ref.origin[k]) for k in range(3)]
-
-
-def apply_noise(ref, m):
-    """One VTMC_MOD_NOISE struct on the twin's memory; returns the block ids it dirties."""
-    dims_s = tuple(d + 2 for d in ref.dims)
-    low, up, first, ext = sample_range(m, dims_s, ref.scale, ref.origin)
-    q = None
-    if min(ext) > 0:
-        px, py, pz = positions(ref, first, ext)
-        perm = permutation(m.data_dims[0] & 0xFFFFFFFF)
-        q = noise_density(perm, px[None, None, :], py[None, :, None], pz[:, None, None], m.data_dims[1] & 255, m.data_dims[1] >> 8, *m.p[0:8])
-    csg_write(ref, first, ext, q, bool(m.add_or_erode))
-    return dirty_ids(low, up, tuple(d // 8 for d in ref.dims))
-
-
-# -- device / twin plumbing -------------------------------------------------------------------------------------------------------------
-def any_mod(spec):
-    return vt.NoiseModifier(**spec[1]) if spec[0] == "noise" else gpu_mod(spec)
-
-
-def twin_update(ref, oracle_mod, specs):
-    nb = tuple(d // 8 for d in ref.dims)
-    ids = set()
-    for spec in specs:
-        if spec[0] == "noise":
-            ids |= apply_noise(ref, any_mod(spec).to_struct())
-        elif spec[0] in ("smooth", "flatten"):
-            ids |= apply_brush(ref, gpu_mod(spec).to_struct())
-        else:
-            d = ref.update([oracle_mod_of(oracle_mod, spec)])
-            ids |= {int(bx + nb[0] * (by + nb[1] * bz)) for bx, by, bz in d}
-    ids = np.array(sorted(ids), np.int64)
-    return np.stack([ids % nb[0], (ids // nb[0]) % nb[1], ids // (nb[0] * nb[1])], axis=1).astype(np.int32).reshape(-1, 3)
-
-
-def assert_update(ex, ref, oracle_mod, specs):
-    n_dirty, T = ex.terrain_update([any_mod(s) for s in specs])
-    dirty = twin_update(ref, oracle_mod, specs)
-    assert_grid(ex, ref.grid)
-    assert n_dirty == len(dirty) and np.array_equal(ex.terrain_dirty_blocks(), dirty)
-    assert_triangles(ex, oracle_mod, ref.grid, dirty, T)
-    return n_dirty, T
-
-
 def world(oracle_mod, place=PLACES[0], history=0):
-    scale, origin = place
-    ex = vt.Extractor(0)
-    ex.terrain_init(*DIMS, scale, origin, SEED)
-    ref = oracle_mod.Terrain(*DIMS, scale, origin, SEED)
-    ex.terrain_update([gpu_mod(s) for s in WORLD])
-    twin_update(ref, oracle_mod, WORLD)
-    assert_grid(ex, ref.grid)
-    if history:
-        ex.terrain_set_history(history)
-    return ex, ref
+    return terrain_twin.world(oracle_mod, DIMS, *place, SEED, WORLD, history)
 
 
 def noise(basis="fbm", add=True, lower=None, upper=None, **kw):
@@ -221,13 +46,6 @@ def raw_noise(p=(0.1, 2.0, 0.5, 1.0, 0.0, 0.0, 0.0, 1.0), seed=5, octaves=4, bas
     m.lower[:], m.upper[:] = lower, upper
     m.data_dims[:] = (seed, octaves | (basis << 8))
     return m
-
-
-def invalid(ex, mods):
-    with pytest.raises(vt.VtmcError) as e:
-        ex.terrain_update(mods)
-    assert e.value.code == _lib.ERR_INVALID_ARG
-    return str(e.value)
 
 
 # -- CPU: the interface -----------------------------------------------------------------------------------------------------------------
@@ -294,7 +112,7 @@ def test_twin_clamp_draws_reproduce_an_oracle_terrain_update(oracle_mod):
     dims, scale, origin, seed = (32, 24, 40), 0.75, (-2.5, 1.25, 3.0), 991
     ref, twin = oracle_mod.Terrain(*dims, scale, origin, seed), oracle_mod.Terrain(*dims, scale, origin, seed)
     dims_s = tuple(d + 2 for d in dims)
-    TAKEN.update(low=0, high=0)
+    taken = np.zeros(2, np.int64)
     for spec in (("plane", (9.375, (-5, -5), (60, 60), True)), ("sphere", ((10.0, 8.0, 16.0), 6.5, False)), ("sphere", ((14.0, 9.0, 20.0), 4.0, True))):
         om = oracle_mod_of(oracle_mod, spec)
         ref.update([om])
@@ -305,9 +123,9 @@ def test_twin_clamp_draws_reproduce_an_oracle_terrain_update(oracle_mod):
         else:
             ddx, ddy, ddz = px - f32(om.p[0]), py - f32(om.p[1]), pz - f32(om.p[2])
             q = f32(om.p[3]) - np.sqrt(((ddx * ddx)[None, None, :] + (ddy * ddy)[None, :, None]) + (ddz * ddz)[:, None, None])
-        csg_write(twin, first, ext, q, bool(om.add_or_erode))
+        taken += csg_write(twin, first, ext, q, bool(om.add_or_erode))
         assert np.array_equal(bits(twin._mem), bits(ref._mem)), spec
-    assert twin.events == ref.events == 3 and TAKEN["low"] > 0 and TAKEN["high"] > 0
+    assert twin.events == ref.events == 3 and taken[0] > 0 and taken[1] > 0
 
 
 # -- GPU ----------------------------------------------------------------------------------------------------------------------------------
@@ -328,14 +146,14 @@ def boxes(place):
 def test_gpu_noise_bitwise(oracle_mod, basis, add, place):
     ex, ref = world(oracle_mod, place)
     with ex:
-        TAKEN.update(low=0, high=0)
+        taken = {"low": 0, "high": 0}
         inner, clipped, thin, outside = boxes(place)
         f = 0.09 / place[0]
         # amplitude 3 (and a bias that centres the billow / ridged sums): both clamp branches are taken
         common = dict(frequency=f, amplitude=3.0, bias={"fbm": 0.0, "billow": 1.5, "ridged": -3.0}[basis], ridge_offset=0.95)
-        n_dirty, T = assert_update(ex, ref, oracle_mod, [noise(basis, add, *inner, octaves=5, **common)])
+        n_dirty, T = assert_update(ex, ref, oracle_mod, [noise(basis, add, *inner, octaves=5, **common)], taken)
         assert n_dirty > 0 and T > 0
-        assert TAKEN["low"] > 0 and TAKEN["high"] > 0, TAKEN
+        assert taken["low"] > 0 and taken["high"] > 0, taken
         n_dirty, _ = assert_update(ex, ref, oracle_mod, [noise(basis, add, *clipped, octaves=3, seed=-5, lacunarity=2.3, gain=0.6, ramp_scale=0.2 / place[0],
                                                                ramp_center=clipped[1][1] - 3 * place[0], **common)])
         assert n_dirty > 0
@@ -399,11 +217,6 @@ HISTORY_STEPS = [
     [noise("billow", True, (-10.0, -10.0, -10.0), (100.0, 100.0, 100.0), frequency=0.05, ramp_scale=0.2, ramp_center=9.0)],   # the whole grid
     [("smooth", ((30.0, 10.5, 20.0), 6.0, 1.0)), noise("fbm", False, (20.0, 8.0, 10.0), (44.0, 14.0, 30.0), frequency=0.2, octaves=2)],
 ]
-
-
-def step_bytes(ref, specs):
-    dims_s = tuple(d + 2 for d in ref.dims)
-    return sum(image_bytes(sample_range(any_mod(s).to_struct(), dims_s, ref.scale, ref.origin)[3]) for s in specs)
 
 
 @pytest.mark.gpu
@@ -548,8 +361,8 @@ def test_gpu_the_same_queue_twice_gives_the_same_bits():
     for _ in range(2):
         with vt.Extractor(0) as ex:
             ex.terrain_init(*DIMS, 0.5, (-3.25, 1.5, 2.125), SEED)
-            ex.terrain_update([any_mod(s) for s in WORLD])
-            T = ex.terrain_update([any_mod(s) for s in MIXED])[1]
+            ex.terrain_update([gpu_mod(s) for s in WORLD])
+            T = ex.terrain_update([gpu_mod(s) for s in MIXED])[1]
             tris, offs = ex.read_triangles()
             grids.append((bits(ex.terrain_read_samples()).copy(), T, tris.tobytes(), offs.tobytes()))
     assert np.array_equal(grids[0][0], grids[1][0]) and grids[0][1:] == grids[1][1:]

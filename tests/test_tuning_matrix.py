@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import fields
-from test_gpu_parity import assert_tris_match
+from extract_checks import assert_tris_match
 
 pytestmark = pytest.mark.gpu
 
