@@ -14,6 +14,7 @@
 #ifndef VTMC_HOST_VOXEL_TERRAIN_HPP
 #define VTMC_HOST_VOXEL_TERRAIN_HPP
 
+#include <cmath>
 #include <cstdint>
 #include <deque>
 #include <functional>
@@ -171,6 +172,60 @@ public:
         d.dims[1] = _heightRes;
         return true;
     }
+};
+
+// New (not in the reference): pastes a stamp the vtmc context keeps in device memory (vtmc_stamp_create / _capture, VTMC_MOD_STAMP of
+// include/vtmc.h) with its centre at _position, turned by the quaternion _rotation (x, y, z, w; any non-zero length) and with _pitch world
+// units between neighbouring stamp samples.  Device-resident terrains only: the samples live on the GPU, so QueryDensity throws.
+// LowerBound / UpperBound: the world AABB of the turned stamp box, t_i -/+ sum_j |R_ij| * h * (n_j - 1) / 2, in double, rounded to float.
+class StampModifier : public TerrainModifier {
+public:
+    enum Mode { Add, Erode, Replace };
+    int _stampId;
+    int _dims[3];
+    Vector3 _position;
+    float _rotation[4];
+    float _pitch;
+    Mode _mode;
+    StampModifier(int stampId, int nx, int ny, int nz, Vector3 position, float qx, float qy, float qz, float qw, float pitch, Mode mode)
+        : _stampId(stampId), _dims{nx, ny, nz}, _position(position), _rotation{qx, qy, qz, qw}, _pitch(pitch), _mode(mode)
+    {
+        const double n2 = (double)qx * qx + (double)qy * qy + (double)qz * qz + (double)qw * qw;
+        if (stampId <= 0 || nx < 2 || ny < 2 || nz < 2 || nx > 1026 || ny > 1026 || nz > 1026 || (long long)nx * ny * nz > (1ll << 27) ||
+            !std::isfinite(position.x) || !std::isfinite(position.y) || !std::isfinite(position.z) || !std::isfinite(n2) || !(n2 > 0) ||
+            !std::isfinite(pitch) || !(pitch > 0))
+            throw std::invalid_argument("StampModifier: invalid stamp id, dims, position, rotation or pitch");
+        AddOrErode = mode != Erode;
+        double x = qx, y = qy, z = qz, w = qw;
+        const double n = std::sqrt(x * x + y * y + z * z + w * w);
+        x /= n, y /= n, z /= n, w /= n;
+        const double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)},
+                                {2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)},
+                                {2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)}};
+        const double h = pitch;
+        for (int i = 0; i < 3; ++i) {
+            _ext[i] = 0;
+            for (int j = 0; j < 3; ++j) _ext[i] += std::fabs(R[i][j]) * h * (_dims[j] - 1) / 2;
+        }
+    }
+    Vector3 LowerBound() const override { return {(float)(_position.x - _ext[0]), (float)(_position.y - _ext[1]), (float)(_position.z - _ext[2])}; }
+    Vector3 UpperBound() const override { return {(float)(_position.x + _ext[0]), (float)(_position.y + _ext[1]), (float)(_position.z + _ext[2])}; }
+    float QueryDensity(const Vector3 &) const override { throw std::logic_error("StampModifier has no host density: its samples live on the device"); }
+    bool Describe(ModifierDesc &d) const override
+    {
+        d.kind = 9;
+        d.p[0] = _position.x;
+        d.p[1] = _position.y;
+        d.p[2] = _position.z;
+        for (int k = 0; k < 4; ++k) d.p[3 + k] = _rotation[k];
+        d.p[7] = _pitch;
+        d.dims[0] = _stampId;
+        d.dims[1] = _mode == Replace ? 1 : 0;
+        return true;
+    }
+
+private:
+    double _ext[3];
 };
 
 // What replaces a block's Unity Mesh (VoxelTerrain.cs:448-465): unindexed soup, indices 0..n-1.

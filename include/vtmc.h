@@ -330,6 +330,43 @@ int32_t vtmc_device_indexed_results(vtmc_ctx *ctx, const vtmc_vertex **d_vertice
  * largest |world coordinate| of the box's corner samples times |f| * max(1, |L|)^(octaves - 1), evaluated in double, must be below
  * 2^24 (beyond it the lattice fraction carries no information and the float -> int conversion differs between targets). */
 
+#define VTMC_MOD_STAMP 9     /* pastes a stamp (vtmc_stamp_create / _capture below), turned and resized: p[0..2] = t, the world position
+                                                           of the stamp's centre; p[3..6] = quaternion (x, y, z, w) of any non-zero
+                                                           length, stamp axes -> world; p[7] = h, world units between neighbouring
+                                                           stamp samples (> 0); data_dims[0] = stamp id; data_dims[1] = mode: 0 CSG
+                                                           (add_or_erode decides, as for kinds 0-3), 1 replace (add_or_erode ignored);
+                                                           data is not read.  Not in the reference. */
+/* A stamp modifier takes its box from lower / upper (the mirrors pass the world AABB of the turned stamp box; the box only has to contain
+ * the footprint, which the kernel tests per sample), marks dirty blocks, is journaled (its box, no halo) and takes one event number exactly
+ * as kinds 0-3, in queue order with every other kind, and sees what the earlier modifiers of its queue wrote.  Undo and redo swap the
+ * journal's images and never read the stamp again: a stamp destroyed after a paste breaks neither.  Densities are not rescaled with h.
+ * On the host, in double, from the floats of p:
+ *   n = sqrt(x*x + y*y + z*z + w*w);  x /= n;  y /= n;  z /= n;  w /= n
+ *   R00 = 1 - 2*(y*y + z*z);  R01 = 2*(x*y - z*w);      R02 = 2*(x*z + y*w)
+ *   R10 = 2*(x*y + z*w);      R11 = 1 - 2*(x*x + z*z);  R12 = 2*(y*z - x*w)
+ *   R20 = 2*(x*z - y*w);      R21 = 2*(y*z + x*w);      R22 = 1 - 2*(x*x + y*y)
+ *   M[i][j] = (float)(R[j][i] / (double)h)   (the inverse rotation over the pitch, rounded once);  c_k = (float)(n_k - 1) * 0.5f
+ * Per sample of the box, FP32, one IEEE operation per step, in this order (px, py, pz as for kinds 0-3: (float)x * scale + origin; s the
+ * stamp, (nx, ny, nz) its dims):
+ *   dx = px - t0;  dy = py - t1;  dz = pz - t2
+ *   u = ((M00*dx + M01*dy) + M02*dz) + c0;   v and w alike with rows 1 and 2 of M and c1, c2
+ *   outside the footprint -- !(u >= 0 && u <= nx-1), or the same for v or w (a NaN included): the sample keeps its 32 bits
+ *   i = (int)floorf(u);  i' = min(i + 1, nx - 1);  fu = u - (float)i;     j, j', fv from v and k, k', fw from w alike
+ *   a00 = s[i,j,k] + (s[i',j,k] - s[i,j,k]) * fu;   a10 the same at j';  a01 at k';  a11 at j', k'
+ *   b0 = a00 + (a10 - a00) * fv;  b1 = a01 + (a11 - a01) * fv;  q = b0 + (b1 - b0) * fw
+ *   mode 0: md = Clamp(q, void, full) with draws 0 / 1; then add_or_erode 1: S = max(S, md); 0: S = Clamp(min(S, -md), void, full), draws
+ *           2 / 3: the write of kinds 0-3
+ *   mode 1: fabsf(q) <= 2: S = q;  otherwise S = Clamp(q, void, full), draws 0 / 1
+ * (i' is clamped rather than i: on the footprint's upper faces, u = nx-1 exactly, the weight is 0 and the value is s[nx-1] itself, not
+ * s[nx-2] + (s[nx-1] - s[nx-2]) * 1, which rounds.)
+ * Mode 1 makes copy and paste exact.  A stamp captured from the grid and pasted with the identity quaternion (0, 0, 0, 1), h = the voxel
+ * scale, its centre a whole number of samples from where it was taken, and positions for which u, v, w come out as whole numbers (a
+ * power-of-two scale with an origin on its lattice, for one), has every weight 0: a + (b - a) * 0 is a for the finite values a grid holds,
+ * the 32 bits of the captured samples are written back, and the blocks the box covers mesh exactly as the source's did.  The one exception
+ * is the sign of a zero: -0 comes back as +0 where (b - a) * 0 is +0.
+ * VTMC_ERR_INVALID_ARG (the modifier's index in vtmc_last_error, nothing written by it): any of p[0..7] not finite; a quaternion of
+ * length 0; h <= 0; an unknown (or destroyed) stamp id; a mode outside 0..1. */
+
 /* One queued TerrainModifier (TerrainModifier.cs:19-33).  lower / upper are the values the C#
  * LowerBound / UpperBound properties return (world space): the shim copies them, so Unity's
  * Vector3.ProjectOnPlane stays on the C# side. */
@@ -435,6 +472,28 @@ int32_t vtmc_terrain_save(vtmc_ctx *ctx, const char *path, uint32_t flags, int64
 int32_t vtmc_terrain_load(vtmc_ctx *ctx, const char *path, uint32_t flags, int32_t *n_dirty_blocks, int32_t *tri_count);
 
 int32_t vtmc_terrain_write_samples(vtmc_ctx *ctx, const float *src, int64_t stride_x, int64_t stride_y, int64_t stride_z);
+
+/* Stamps: density volumes the context keeps in device memory, for VTMC_MOD_STAMP to paste (not in the reference, whose modifiers are
+ * analytic): authored content -- a sculpted rock, a prefab tunnel section -- or a captured piece of the terrain, caves and overhangs included,
+ * pasted as often as wanted without another upload.  A stamp is nx * ny * nz FP32 samples, x fastest; each of nx, ny, nz lies in 2..1026
+ * and nx * ny * nz is at most 2^27 (anything else: VTMC_ERR_INVALID_ARG).  Ids are positive, count up per context and are never reused in
+ * it.  Stamps are no part of the terrain: they survive vtmc_terrain_init, vtmc_terrain_load, undo and redo, they are not written to the
+ * terrain file (a host that wants to keep one reads it with vtmc_stamp_read), and vtmc_destroy frees them.  An unknown or destroyed id
+ * answers VTMC_ERR_INVALID_ARG.
+ *   vtmc_stamp_create   uploads host samples, sample (x, y, z) = src[x*stride_x + y*stride_y + z*stride_z] (element strides, all positive).
+ *                       A sample that is not finite is refused with VTMC_ERR_INVALID_ARG before anything is uploaded.
+ *   vtmc_stamp_capture  copies the box [first_sample, first_sample + n) of the resident grid on the device, as 32-bit copies: nothing crosses
+ *                       PCIe.  The box must lie inside the (W+2, E+2, H+2) grid (VTMC_ERR_INVALID_ARG); VTMC_ERR_NO_RESULT without a terrain.
+ *                       It changes nothing in the terrain: not the grid, the history, the event counter or the last result.
+ *   vtmc_stamp_info     the dims of a stamp.
+ *   vtmc_stamp_read     copies a stamp to the host with element strides as vtmc_stamp_create's.
+ *   vtmc_stamp_destroy  frees it; a step of the history that pasted it is still undone and redone. */
+int32_t vtmc_stamp_create(vtmc_ctx *ctx, const float *src, int32_t nx, int32_t ny, int32_t nz, int64_t stride_x, int64_t stride_y,
+                          int64_t stride_z, int32_t *stamp_id);
+int32_t vtmc_stamp_capture(vtmc_ctx *ctx, const int32_t first_sample[3], int32_t nx, int32_t ny, int32_t nz, int32_t *stamp_id);
+int32_t vtmc_stamp_info(const vtmc_ctx *ctx, int32_t stamp_id, int32_t dims[3]);
+int32_t vtmc_stamp_read(vtmc_ctx *ctx, int32_t stamp_id, float *dst, int64_t stride_x, int64_t stride_y, int64_t stride_z);
+int32_t vtmc_stamp_destroy(vtmc_ctx *ctx, int32_t stamp_id);
 
 /* ------------------------------------------------------------------------------------------
  * Ray picking -- replaces the Physics.Raycast of the interactive edit (SceneManager.cs:114-131)

@@ -52,11 +52,14 @@ SYMBOLS = [
     "vtmc_terrain_set_history", "vtmc_terrain_undo", "vtmc_terrain_redo", "vtmc_terrain_history",
     "vtmc_terrain_spherecast", "vtmc_terrain_closest_point", "vtmc_spherecast_device", "vtmc_closest_point_device",
     "vtmc_terrain_save", "vtmc_terrain_load", "vtmc_terrain_write_samples",
+    "vtmc_stamp_create", "vtmc_stamp_capture", "vtmc_stamp_info", "vtmc_stamp_read", "vtmc_stamp_destroy",
 ]
 COMM_ID_BYTES = 128
 
 MOD_PLANE, MOD_SPHERE, MOD_CYLINDER, MOD_HEIGHTMAP = 0, 1, 2, 3
 MOD_SMOOTH, MOD_FLATTEN = 4, 5   # sculpt brushes (not in the reference)
+MOD_STAMP = 9                     # pastes a stamp (vtmc_stamp_*) through a rotation and a pitch
+STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27
 MOD_NOISE = 8                     # fBm / billow / ridged noise (RidgedMultifractalModifier's device form); 6 and 7 are not defined
 
 
@@ -177,6 +180,12 @@ def load(path=None):
         L.vtmc_terrain_save.argtypes = [vp, ctypes.c_char_p, u32, P(i64)]
         L.vtmc_terrain_load.argtypes = [vp, ctypes.c_char_p, u32, P(i32), P(i32)]
         L.vtmc_terrain_write_samples.argtypes = [vp, vp, i64, i64, i64]
+    if not explicit or hasattr(L, "vtmc_stamp_create"):
+        L.vtmc_stamp_create.argtypes = [vp, vp, i32, i32, i32, i64, i64, i64, P(i32)]
+        L.vtmc_stamp_capture.argtypes = [vp, P(i32 * 3), i32, i32, i32, P(i32)]
+        L.vtmc_stamp_info.argtypes = [vp, i32, P(i32 * 3)]
+        L.vtmc_stamp_read.argtypes = [vp, i32, vp, i64, i64, i64]
+        L.vtmc_stamp_destroy.argtypes = [vp, i32]
     L.vtmc_comm_unique_id.argtypes = [vp]
     L.vtmc_comm_init_rank.argtypes = [vp, vp, i32, i32]
     L.vtmc_comm_destroy.argtypes = [vp]

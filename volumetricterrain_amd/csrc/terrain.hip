@@ -18,7 +18,8 @@
 // restates the same hash (oracle/terrain_ref.c).
 #include "vtmc_ctx.h"
 #include "perlin_device.h"
-#include "terrain_hash.h"
+#include "terrain_box.h"
+#include "terrain_stamp.h"
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -30,21 +31,6 @@ __device__ __forceinline__ float clampf(float v, float lo, float hi)  // Mathf.C
 {
     if (v < lo) v = lo;
     else if (v > hi) v = hi;
-    return v;
-}
-
-// Mathf.Clamp(v, voidDensity, fullDensity) with void = draw k, full = draw k+1.  void lies in [-2,-1)
-// and full in [1,2), so a value in [-1,1] is never clamped and neither draw is evaluated for it; the
-// result is the same as drawing both (each draw is a pure function of its counter).
-__device__ __forceinline__ float clamp_drawn(float v, uint64_t seed, uint32_t event, uint64_t sample, uint32_t k)
-{
-    if (v < -1.0f) {
-        const float lo = terrain_uniform(seed, event, sample, k) - 2.0f;
-        if (v < lo) v = lo;
-    } else if (v > 1.0f) {
-        const float hi = terrain_uniform(seed, event, sample, k + 1u) + 1.0f;
-        if (v > hi) v = hi;
-    }
     return v;
 }
 
@@ -99,33 +85,6 @@ __device__ __forceinline__ float column_term(const TerrainModifierArgs &m, float
     const float h0 = lerp_unity(h00, h01, v - (float)v0);
     const float h1 = lerp_unity(h10, h11, v - (float)v0);
     return lerp_unity(h0, h1, u - (float)u0);
-}
-
-constexpr int kYRun = 16;  // samples along y per thread
-
-// ---- the box walk every kernel below shares --------------------------------------------------------------------------------------
-// launch shape: 64 x 4 threads = 64 samples along x (the stride-1 axis) of 4 z-planes; a thread walks kYRun samples along y;
-// grid = (x segments, z quads, y runs)
-// A thread's place in a box (a TerrainBox, or a TerrainModifierArgs for its six ints).  The box is asked, not stored: a kernel reads
-// dy only behind its bounds test, as the kernels did when each wrote this out.
-struct BoxThread {
-    int ix, iz, iy0;  // this thread's column of the box and the first sample of its run along y
-    __device__ __forceinline__ BoxThread() : ix(blockIdx.x * 64 + threadIdx.x), iz(blockIdx.y * 4 + threadIdx.y), iy0(blockIdx.z * kYRun) {}
-    template <class Box>
-    __device__ __forceinline__ bool inside(const Box &b) const { return ix < b.dx && iz < b.dz; }
-    template <class Box>
-    __device__ __forceinline__ int iy1(const Box &b) const { return iy0 + kYRun < b.dy ? iy0 + kYRun : b.dy; }  // the run is [iy0, iy1)
-};
-// sample (x, y, z) of the grid, x fastest; 64 bits: the hash counts samples with it
-__device__ __forceinline__ uint64_t grid_index(const TerrainShape &sh, int x, int y, int z)
-{
-    return (uint64_t)x + (uint64_t)sh.dim_x * ((uint64_t)y + (uint64_t)sh.dim_y * (uint64_t)z);
-}
-// sample (ix, iy, iz) of a box in its journal image or stage, x fastest, so a wave stores 256 contiguous bytes; a box reaches 4.3 GB
-template <class Box>
-__device__ __forceinline__ uint64_t box_index(const Box &b, int ix, int iy, int iz)
-{
-    return (uint64_t)ix + (uint64_t)b.dx * ((uint64_t)iy + (uint64_t)b.dy * (uint64_t)iz);
 }
 
 // kJournal (history on): the sample it replaces also goes to the box's image (12 bytes per touched sample instead of 8).  History off
@@ -452,26 +411,18 @@ hipError_t launch_terrain_fill(float *grid, long long n, uint64_t seed, int n_cu
 }
 
 static TerrainBox box_of(const TerrainModifierArgs &m) { return TerrainBox{m.lx, m.ly, m.lz, m.dx, m.dy, m.dz}; }
-static bool box_empty(const TerrainBox &b) { return b.dx <= 0 || b.dy <= 0 || b.dz <= 0; }
-
-static dim3 box_grid(const TerrainBox &b) { return dim3((unsigned)((b.dx + 63) / 64), (unsigned)((b.dz + 3) / 4), (unsigned)((b.dy + kYRun - 1) / kYRun)); }
-static bool box_launchable(const TerrainBox &b) { return (b.dz + 3) / 4 <= 65535 && (b.dy + kYRun - 1) / kYRun <= 65535; }  // grid y, z: 16 bits
-
-// the one launch of a box kernel, on a non-empty box
-template <class... Params, class... Args>
-static hipError_t launch_box(void (*kernel)(Params...), const TerrainBox &b, hipStream_t stream, Args... args)
-{
-    if (!box_launchable(b)) return hipErrorInvalidValue;
-    launch_begin();
-    hipLaunchKernelGGL(kernel, box_grid(b), dim3(64, 4, 1), 0, stream, args...);
-    return launch_end();
-}
 
 // declared by vtmc_internal.h, whose text the traffic constant of the extract path is tied to: kept for that declaration, vtmc_terrain_update
 // goes through launch_box itself
 hipError_t launch_terrain_modify(float *grid, const TerrainShape &sh, const TerrainModifierArgs &m, hipStream_t stream)
 {
     return box_empty(box_of(m)) ? hipSuccess : launch_box(terrain_modify_kernel<false>, box_of(m), stream, grid, (float *)nullptr, sh, m);
+}
+
+// vtmc_stamp_capture (terrain_stamp.h): a box of the grid as 32-bit copies, the copy a smooth stages its box with
+hipError_t launch_terrain_copy_box(const float *grid, float *dst, const TerrainShape &sh, const TerrainBox &b, hipStream_t stream)
+{
+    return launch_box(terrain_stage_kernel, b, stream, grid, dst, sh, b);
 }
 
 // the stage box of a smooth: its (non-empty) box grown by one sample per side, intersected with the grid
@@ -589,8 +540,9 @@ static NoiseKernel noise_kernel(bool journal, int basis)
 
 static int check_modifier(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i)
 {
-    if ((md.kind < VTMC_MOD_PLANE || md.kind > VTMC_MOD_FLATTEN) && md.kind != VTMC_MOD_NOISE)
+    if ((md.kind < VTMC_MOD_PLANE || md.kind > VTMC_MOD_FLATTEN) && md.kind != VTMC_MOD_NOISE && md.kind != VTMC_MOD_STAMP)
         return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: unknown kind %d", i, md.kind);
+    if (md.kind == VTMC_MOD_STAMP) return check_stamp_modifier(ctx, md, i);
     if (md.kind == VTMC_MOD_NOISE) {
         for (int k = 0; k < 8; ++k)
             if (!std::isfinite(md.p[k])) return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: noise parameter p[%d] not finite", i, k);
@@ -821,6 +773,8 @@ int32_t vtmc_terrain_update(vtmc_ctx *ctx, const vtmc_modifier *mods, int32_t n_
                 VTMC_HIP(ctx, launch_box(image ? terrain_flatten_kernel<true> : terrain_flatten_kernel<false>, b, ctx->stream, grid, image, sh, a));
             } else if (md.kind == VTMC_MOD_NOISE) {
                 VTMC_HIP(ctx, launch_box(noise_kernel(image != nullptr, noise_basis(md)), b, ctx->stream, grid, image, sh, noise_args(md, a)));
+            } else if (md.kind == VTMC_MOD_STAMP) {
+                VTMC_HIP(ctx, launch_stamp_paste(ctx, md, a, grid, image, ctx->stream));
             } else {  // the reference's modifiers, kinds 0-3
                 VTMC_HIP(ctx, launch_box(image ? terrain_modify_kernel<true> : terrain_modify_kernel<false>, b, ctx->stream, grid, image, sh, a));
             }

@@ -1,11 +1,12 @@
 // vtmc_ctx.h -- the context object behind include/vtmc.h and the small host helpers every translation unit of the C-ABI layer shares
-// (context.hip, vtmc_api.hip, terrain.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
+// (context.hip, vtmc_api.hip, terrain.hip, terrain_stamp.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
 #ifndef VTMC_CTX_H
 #define VTMC_CTX_H
 #include "../../include/vtmc.h"
 #include "vtmc_internal.h"
 
 #include <deque>
+#include <map>
 #include <string>
 #include <utility>
 #include <vector>
@@ -56,6 +57,12 @@ struct VtmcHistoryBox {
 struct VtmcHistoryStep {
     std::vector<VtmcHistoryBox> boxes;
     size_t off = 0, bytes = 0;
+};
+
+// One stamp (vtmc_stamp_create / _capture): nx * ny * nz FP32 samples in device memory, x fastest.
+struct VtmcStamp {
+    VtmcDevBuf samples;
+    int nx = 0, ny = 0, nz = 0;
 };
 
 // An extract that has been queued on a stream and not yet completed by extract_finish().
@@ -128,6 +135,10 @@ struct vtmc_ctx {
     // terrain.hip: the stage of a VTMC_MOD_SMOOTH brush (its box plus a one-sample halo, before the brush), grow-only; grown only after
     // the stream has drained, since an earlier smooth of the same queue may still be reading it
     VtmcDevBuf brush;
+    // terrain_stamp.hip: the stamps by id; ids count up from 1 and are never reused.  No part of the terrain: vtmc_terrain_init / _load and the
+    // history leave them alone, vtmc_destroy frees them.
+    std::map<int32_t, VtmcStamp> stamps;
+    int32_t next_stamp_id = 1;
     // raycast.hip, spherequery.hip: the queries and hits of vtmc_terrain_raycast / _spherecast / _closest_point (device, then their pinned staging)
     VtmcDevBuf rays;
     VtmcPinnedBuf<unsigned char> h_rays;

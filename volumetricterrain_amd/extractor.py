@@ -343,6 +343,40 @@ class Extractor:
         sx, sy, sz = elem_strides(grid)
         self._check(self._L.vtmc_terrain_write_samples(self._h, _ptr(grid), sx, sy, sz))
 
+    # -- stamps: density volumes the context keeps in HBM for StampModifier to paste ---------------------------------
+    def stamp_create(self, samples):
+        """A stamp from host samples: a float32 array indexed [x, y, z] (any positive strides), every sample finite.  Returns its id."""
+        samples = np.asarray(samples)
+        sx, sy, sz = elem_strides(samples)
+        if min(sx, sy, sz) <= 0:
+            raise ValueError("stamp strides must be positive")
+        sid = ctypes.c_int32()
+        self._check(self._L.vtmc_stamp_create(self._h, _ptr(samples), *samples.shape, sx, sy, sz, ctypes.byref(sid)))
+        return sid.value
+
+    def stamp_capture(self, first, dims):
+        """A stamp copied on the device from the resident grid: the samples [first, first + dims) per axis.  Returns its id."""
+        f = (ctypes.c_int32 * 3)(*(int(v) for v in first))
+        sid = ctypes.c_int32()
+        self._check(self._L.vtmc_stamp_capture(self._h, ctypes.byref(f), *(int(n) for n in dims), ctypes.byref(sid)))
+        return sid.value
+
+    def stamp_dims(self, stamp_id):
+        d = (ctypes.c_int32 * 3)()
+        self._check(self._L.vtmc_stamp_info(self._h, int(stamp_id), ctypes.byref(d)))
+        return tuple(d)
+
+    def stamp_read(self, stamp_id):
+        """The stamp's samples indexed [x, y, z] (x fastest in memory): what a host stores to keep a stamp."""
+        nx, ny, nz = self.stamp_dims(stamp_id)
+        out = np.empty((nz, ny, nx), np.float32).transpose(2, 1, 0)
+        sx, sy, sz = elem_strides(out)
+        self._check(self._L.vtmc_stamp_read(self._h, int(stamp_id), _ptr(out), sx, sy, sz))
+        return out
+
+    def stamp_destroy(self, stamp_id):
+        self._check(self._L.vtmc_stamp_destroy(self._h, int(stamp_id)))
+
     # -- ray picking: Physics.Raycast of the interactive edit (SceneManager.cs:114-131) on the device ---------------
     def terrain_raycast(self, origins, directions, max_distance=float("inf"), two_sided=False):
         """Nearest surface hit of each ray (world-space origins / directions, (n, 3)) on the resident terrain: a RAY_HIT_DTYPE

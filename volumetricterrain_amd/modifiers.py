@@ -8,7 +8,8 @@ order of the C# expressions.
 """
 import numpy as np
 
-from ._lib import MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, Modifier
+from ._lib import (MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP, STAMP_MAX_DIM, STAMP_MAX_SAMPLES,
+                   STAMP_MIN_DIM, Modifier)
 
 _f = np.float32
 FLOAT_MIN_VALUE = _f(-3.4028234663852886e38)  # C# float.MinValue
@@ -244,3 +245,64 @@ class NoiseModifier(TerrainModifier):
 
     def attach(self, m):
         m.data_dims[:] = (self._seed, self._octaves | (self._basis << 8))
+
+
+# -- stamps (include/vtmc.h VTMC_MOD_STAMP) ----------------------------------------------------------------------------------------------
+STAMP_MODES = ("add", "erode", "replace")
+
+
+def stamp_rotation(q):
+    """The rotation matrix (stamp axes -> world) of include/vtmc.h's rule: the float32 quaternion (x, y, z, w) normalised in double."""
+    x, y, z, w = (float(v) for v in np.asarray(q, _f))
+    n = float(np.sqrt(x * x + y * y + z * z + w * w))
+    x, y, z, w = x / n, y / n, z / n, w / n
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], np.float64)
+
+
+class StampModifier(TerrainModifier):
+    """Pastes stamp `stamp_id` (Extractor.stamp_create / stamp_capture; `dims` = its (nx, ny, nz), Extractor.stamp_dims) with its centre at
+    `position`, turned by the quaternion `rotation` (x, y, z, w; any non-zero length) and with `pitch` world units between neighbouring
+    stamp samples.  mode "add" / "erode": the CSG write of the other modifiers; "replace": the stamp's values are written, which makes a
+    captured stamp pasted unturned at the voxel scale an exact copy.  The bounds are the world AABB of the turned stamp box; the kernel
+    tests the footprint per sample."""
+    kind = MOD_STAMP
+
+    def __init__(self, stamp_id, dims, position, rotation=(0.0, 0.0, 0.0, 1.0), pitch=1.0, mode="add"):
+        if mode not in STAMP_MODES:
+            raise ValueError("stamp mode must be one of %s" % ", ".join(STAMP_MODES))
+        if int(stamp_id) != stamp_id or not 0 < stamp_id < 2 ** 31:
+            raise ValueError("stamp id must be a positive 32-bit integer")
+        dims = tuple(int(n) for n in dims)
+        if len(dims) != 3 or not all(STAMP_MIN_DIM <= n <= STAMP_MAX_DIM for n in dims) or dims[0] * dims[1] * dims[2] > STAMP_MAX_SAMPLES:
+            raise ValueError("stamp dims must be three numbers in %d..%d with a product of at most 2^27" % (STAMP_MIN_DIM, STAMP_MAX_DIM))
+        with np.errstate(over="ignore"):
+            self._position = np.asarray(position, np.float64).astype(_f).reshape(3)
+            self._rotation = np.asarray(rotation, np.float64).astype(_f).reshape(4)
+            self._pitch = _f(pitch)
+        if not (np.isfinite(self._position).all() and np.isfinite(self._rotation).all() and np.isfinite(self._pitch)):
+            raise ValueError("stamp position, rotation and pitch must be finite")
+        if not (self._rotation.astype(np.float64) ** 2).sum() > 0:
+            raise ValueError("stamp rotation must be a quaternion of non-zero length")
+        if not self._pitch > 0:
+            raise ValueError("stamp pitch must be > 0")
+        self._id, self._dims, self._mode = int(stamp_id), dims, mode
+        self.AddOrErode = mode != "erode"
+        # ext_i = sum_j |R_ij| * h * (n_j - 1) / 2, in double
+        R, h = stamp_rotation(self._rotation), float(self._pitch)
+        self._ext = np.array([sum(abs(R[i][j]) * h * (dims[j] - 1) / 2 for j in range(3)) for i in range(3)], np.float64)
+
+    @property
+    def LowerBound(self):
+        return (self._position.astype(np.float64) - self._ext).astype(_f)
+
+    @property
+    def UpperBound(self):
+        return (self._position.astype(np.float64) + self._ext).astype(_f)
+
+    def params(self):
+        return [*self._position, *self._rotation, self._pitch]
+
+    def attach(self, m):
+        m.data_dims[:] = (self._id, 1 if self._mode == "replace" else 0)
