@@ -416,6 +416,11 @@ int32_t vtmc_terrain_device_grid(vtmc_ctx *ctx, const float **d_samples, int64_t
  * queue, modifiers wholly outside the grid) records nothing and keeps both stacks.  A step discards every undone step; the oldest
  * steps are dropped until it fits (steps of equal size S: floor(max_bytes / S) are kept; the journal is a ring).  A step larger than
  * max_bytes, or an update that fails after writing, clears the history.  vtmc_terrain_init clears it and keeps the budget.
+ * Where a step lies: its bytes are one contiguous range of the journal.  After the undone steps are discarded it begins where the
+ * newest remaining step ends (at offset 0 when none remains), or at offset 0 when it would reach past max_bytes from there; the bytes
+ * it leaves behind at the journal's end stay unused until the ring comes round.  Then the oldest steps are dropped until no remaining
+ * step shares a byte with the new one and the offsets of the remaining steps and the new one, read oldest to newest, fall at most once
+ * (the ring wraps once): a step stranded at the journal's end behind a step that wrapped goes before any step in front of it does.
  *
  * vtmc_terrain_undo restores the newest step's boxes bit for bit in reverse modifier order, vtmc_terrain_redo puts the newest undone
  * step's values back in modifier order (no modifier is evaluated again); each then extracts that step's dirty set as its update did,

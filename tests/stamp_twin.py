@@ -20,6 +20,11 @@ def gpu_mod(spec):
     return vt.StampModifier(**spec[1]) if spec[0] == "stamp" else terrain_twin.gpu_mod(spec)
 
 
+def gpu_struct(spec):
+    """terrain_twin.gpu_struct for queues that hold stamps: the struct of a spec, its AABB overridden where the spec carries one."""
+    return terrain_twin.gpu_struct(spec, gpu_mod)
+
+
 def stamp_map(p, dims):
     """(M, c) of the header's rule from the floats of p: M[i][j] = (float)(R[j][i] / (double)h), c_k = (float)(n_k - 1) * 0.5f."""
     x, y, z, w = (float(f32(v)) for v in p[3:7])
@@ -93,30 +98,30 @@ def apply_stamp(ref, m, s):
     return ids, n_in
 
 
-def twin_update(ref, oracle_mod, specs, stamps, counts=None):
+def twin_update(ref, oracle_mod, specs, stamps, counts=None, taken=None):
     """terrain_twin.twin_update with "stamp" specs run here; stamps: {id: samples [x, y, z]}.  counts: a list that receives each stamp
-    modifier's number of samples inside the footprint."""
+    modifier's number of samples inside the footprint; taken: handed on to terrain_twin.twin_update."""
     nb = tuple(d // 8 for d in ref.dims)
     ids = set()
     for spec in specs:
         if spec[0] == "stamp":
-            hit, n_in = apply_stamp(ref, gpu_mod(spec).to_struct(), stamps[spec[1]["stamp_id"]])
+            hit, n_in = apply_stamp(ref, gpu_struct(spec), stamps[spec[1]["stamp_id"]])
             ids |= hit
             if counts is not None:
                 counts.append(n_in)
         else:
-            ids |= {int(bx + nb[0] * (by + nb[1] * bz)) for bx, by, bz in terrain_twin.twin_update(ref, oracle_mod, [spec])}
+            ids |= {int(bx + nb[0] * (by + nb[1] * bz)) for bx, by, bz in terrain_twin.twin_update(ref, oracle_mod, [spec], taken)}
     return block_list(ids, nb)
 
 
 def step_bytes(ref, specs):
     """terrain_twin.step_bytes' rule -- the boxes' images, no halo -- for queues that hold stamps."""
-    return sum(image_bytes(box_of(ref, gpu_mod(s).to_struct())[1]) for s in specs)
+    return sum(image_bytes(box_of(ref, gpu_struct(s))[1]) for s in specs)
 
 
 def assert_update(ex, ref, oracle_mod, specs, stamps, counts=None):
     """terrain_twin.assert_update for queues that hold stamps: the grid and the dirty list bit for bit, triangles within the bar."""
-    n_dirty, T = ex.terrain_update([gpu_mod(s) for s in specs])
+    n_dirty, T = ex.terrain_update([gpu_struct(s) for s in specs])
     dirty = twin_update(ref, oracle_mod, specs, stamps, counts)
     assert_grid(ex, ref.grid)
     assert n_dirty == len(dirty) and np.array_equal(ex.terrain_dirty_blocks(), dirty)

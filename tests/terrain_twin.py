@@ -23,18 +23,34 @@ f32, u64 = np.float32, np.uint64
 # -- modifier specs -----------------------------------------------------------------------------------------------------------------------
 def gpu_mod(spec):
     """The device's modifier of any spec; a noise spec carries NoiseModifier's keyword arguments."""
-    kind, args = spec
+    kind, args = spec[0], spec[1]
     if kind == "noise":
         return vt.NoiseModifier(**args)
     return {"plane": vt.PlaneModifier, "sphere": vt.SphereModifier, "cylinder": vt.CylinderModifier, "island": vt.IslandModifier,
             "smooth": vt.SmoothModifier, "flatten": vt.FlattenModifier}[kind](*args)
 
 
+def with_box(m, spec, keep=None):
+    """A spec may carry a third entry (lower, upper): the AABB the struct m gets in place of its modifier's own, set after to_struct()
+    (session_twin.py: boxes of exact sample extents).  keep: what the struct borrows memory from (a heightmap) and must outlive."""
+    if len(spec) > 2:
+        m.lower[:], m.upper[:] = (tuple(float(f32(v)) for v in b) for b in spec[2])
+    if keep is not None:
+        m._keep = keep
+    return m
+
+
+def gpu_struct(spec, mod_of=gpu_mod):
+    """The vtmc_modifier of a spec, its AABB overridden where the spec says so: what the device is handed and the numpy kinds read."""
+    mod = mod_of(spec)
+    return with_box(mod.to_struct(), spec, mod)
+
+
 def oracle_mod_of(oracle_mod, spec):
-    """The reference's kinds only, through the oracle's own (independent) bound formulas."""
-    kind, args = spec
-    return {"plane": oracle_mod.plane_modifier, "sphere": oracle_mod.sphere_modifier,
-            "cylinder": oracle_mod.cylinder_modifier, "island": oracle_mod.heightmap_modifier}[kind](*args)
+    """The reference's kinds only, through the oracle's own (independent) bound formulas (an overridden AABB apart)."""
+    kind, args = spec[0], spec[1]
+    return with_box({"plane": oracle_mod.plane_modifier, "sphere": oracle_mod.sphere_modifier,
+                     "cylinder": oracle_mod.cylinder_modifier, "island": oracle_mod.heightmap_modifier}[kind](*args), spec)
 
 
 def island_heightmap(res=(48, 40), height=14.0):
@@ -98,7 +114,7 @@ def box_of(ref, m):
 
 def step_bytes(ref, specs):
     """What the journal keeps of one update: the boxes' images, no halo."""
-    return sum(image_bytes(box_of(ref, gpu_mod(s).to_struct())[1]) for s in specs)
+    return sum(image_bytes(box_of(ref, gpu_struct(s))[1]) for s in specs)
 
 
 # -- the write rule of kinds 0-3 and 8 ------------------------------------------------------------------------------------------------------
@@ -281,13 +297,13 @@ def twin_update(ref, oracle_mod, specs, taken=None):
     ids = set()
     for spec in specs:
         if spec[0] == "noise":
-            hit, (low, high) = apply_noise(ref, gpu_mod(spec).to_struct())
+            hit, (low, high) = apply_noise(ref, gpu_struct(spec))
             ids |= hit
             if taken is not None:
                 taken["low"] += low
                 taken["high"] += high
         elif spec[0] in ("smooth", "flatten"):
-            ids |= apply_brush(ref, gpu_mod(spec).to_struct())
+            ids |= apply_brush(ref, gpu_struct(spec))
         else:
             ids |= {int(bx + nb[0] * (by + nb[1] * bz)) for bx, by, bz in ref.update([oracle_mod_of(oracle_mod, spec)])}
     return block_list(ids, nb)
@@ -295,7 +311,7 @@ def twin_update(ref, oracle_mod, specs, taken=None):
 
 def both_update(ex, ref, oracle_mod, specs, taken=None):
     """The same queue on the device, in one call, and on the twin; returns the device's (n_dirty, T) and the twin's dirty list."""
-    got = ex.terrain_update([gpu_mod(s) for s in specs])
+    got = ex.terrain_update([gpu_struct(s) for s in specs])
     return got, twin_update(ref, oracle_mod, specs, taken)
 
 
