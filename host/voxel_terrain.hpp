@@ -14,6 +14,7 @@
 #ifndef VTMC_HOST_VOXEL_TERRAIN_HPP
 #define VTMC_HOST_VOXEL_TERRAIN_HPP
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <deque>
@@ -226,6 +227,44 @@ public:
 
 private:
     double _ext[3];
+};
+
+// New (not in the reference, which queues one eroding CylinderModifier per river segment, RiverRenderer.cs:151-170): carves or builds
+// along curves in one pass, the union of tapered capsules over _segments (VTMC_MOD_PATH of include/vtmc.h): 8 floats per segment,
+// ax, ay, az, ra, bx, by, bz, rb.  Device-resident terrains only: this mirror holds the struct and the bounds, so QueryDensity throws.
+// LowerBound / UpperBound: the AABB of all end points grown by their radii, in float.
+class PathModifier : public TerrainModifier {
+public:
+    std::vector<float> _segments;
+    explicit PathModifier(std::vector<float> segments, bool addOrErode = false) : _segments(std::move(segments))
+    {
+        const size_t n = _segments.size() / 8;
+        if (n < 1 || n > 65536 || _segments.size() % 8) throw std::invalid_argument("PathModifier: 1..65536 segments of 8 floats each");
+        AddOrErode = addOrErode;
+        for (int k = 0; k < 3; ++k) _low[k] = std::numeric_limits<float>::infinity(), _up[k] = -std::numeric_limits<float>::infinity();
+        for (size_t s = 0; s < n; ++s)
+            for (int end = 0; end < 2; ++end) {
+                const float *e = &_segments[8 * s + 4 * end];
+                if (!std::isfinite(e[0]) || !std::isfinite(e[1]) || !std::isfinite(e[2]) || !std::isfinite(e[3]) || e[3] < 0 || std::fabs(e[3]) > 1048576.0f ||
+                    std::fabs(e[0]) > 1048576.0f || std::fabs(e[1]) > 1048576.0f || std::fabs(e[2]) > 1048576.0f)
+                    throw std::invalid_argument("PathModifier: end points and radii must be finite, at most 2^20 in magnitude, radii not negative");
+                for (int k = 0; k < 3; ++k) _low[k] = std::min(_low[k], e[k] - e[3]), _up[k] = std::max(_up[k], e[k] + e[3]);
+            }
+    }
+    Vector3 LowerBound() const override { return {_low[0], _low[1], _low[2]}; }
+    Vector3 UpperBound() const override { return {_up[0], _up[1], _up[2]}; }
+    float QueryDensity(const Vector3 &) const override { throw std::logic_error("PathModifier has no host density: it is evaluated on the device"); }
+    bool Describe(ModifierDesc &d) const override
+    {
+        d.kind = 10;
+        d.data = _segments.data();
+        d.dims[0] = (int)(_segments.size() / 8);
+        d.dims[1] = 8;
+        return true;
+    }
+
+private:
+    float _low[3], _up[3];
 };
 
 // What replaces a block's Unity Mesh (VoxelTerrain.cs:448-465): unindexed soup, indices 0..n-1.

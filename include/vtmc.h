@@ -367,6 +367,42 @@ int32_t vtmc_device_indexed_results(vtmc_ctx *ctx, const vtmc_vertex **d_vertice
  * VTMC_ERR_INVALID_ARG (the modifier's index in vtmc_last_error, nothing written by it): any of p[0..7] not finite; a quaternion of
  * length 0; h <= 0; an unknown (or destroyed) stamp id; a mode outside 0..1. */
 
+#define VTMC_MOD_PATH 10     /* carves or builds along curves: the union of tapered capsules over a segment soup (rivers, tunnels, roads,
+                                                           shafts; polylines, trees and disjoint pieces alike).  data = host pointer,
+                                                           borrowed for the call and copied to the device: data_dims[0] = n_seg
+                                                           segments (1..65536) of data_dims[1] = 8 floats each,
+                                                           ax, ay, az, ra, bx, by, bz, rb: the world-space end points and the radius
+                                                           at each end (round ends, radius linear along the segment).  p[0..7] are
+                                                           not read.  add_or_erode as for kinds 0-3 (a river or a tunnel is erode). */
+/* The shape is THE LIBRARY'S OWN.  The reference carves its rivers with one flat-ended eroding CylinderModifier per segment
+ * (RiverRenderer.cs:151-170, TerrainEngine.cs:97-99), which leaves wedge-shaped gaps on the outside of every bend; a path is one modifier,
+ * one event number and one journal box, and its values are not those of that cylinder queue.
+ * A path modifier takes its box from lower / upper (the mirrors pass the AABB of all end points grown by their radii), writes EVERY sample
+ * of the box, marks dirty blocks, is journaled (its box, no halo) and takes one event number exactly as kinds 0-3, in queue order with every
+ * other kind, and sees what the earlier modifiers of its queue wrote.  Two path modifiers of one queue each read their own data.
+ * On the host, per segment, FP32, one IEEE operation per step:
+ *   ex = bx - ax;  ey = by - ay;  ez = bz - az
+ *   ll = (ex*ex + ey*ey) + ez*ez;  il = ll >= 1e-30f ? 1.0f / ll : 0.0f;  dr = rb - ra
+ * Per sample of the box, FP32, one IEEE operation per step, segments in increasing index (px, py, pz as for kinds 0-3:
+ * (float)x * scale + origin):
+ *   q = -inf
+ *   per segment:
+ *     dx = px - ax;  dy = py - ay;  dz = pz - az
+ *     t = ((dx*ex + dy*ey) + dz*ez) * il;  t = t < 0 ? 0 : (t > 1 ? 1 : t)
+ *     cx = dx - ex*t;  cy = dy - ey*t;  cz = dz - ez*t
+ *     d = sqrtf((cx*cx + cy*cy) + cz*cz);  r = ra + dr*t;  f = r - d
+ *     if (f > q) q = f
+ *   md = Clamp(q, void, full) with draws 0 / 1; then add_or_erode 1: S = max(S, md); 0: S = Clamp(min(S, -md), void, full), draws 2 / 3:
+ *   the write of kinds 0-3.
+ * (The increasing order matters only for the sign of a zero.)  Two properties:
+ *  - a single segment with a == b and ra == rb == r, given SphereModifier's box, writes what VTMC_MOD_SPHERE with centre a and radius r
+ *    writes, bit for bit: il = 0, t = +-0, c = d, f = r - |p - a|;
+ *  - the result never depends on how the kernel prunes segments.  A workgroup skips a segment only when f < -2 on every sample of its
+ *    tile, and any q < -2 (the initial -inf included) clamps to the same drawn void value.
+ * VTMC_ERR_INVALID_ARG (the modifier's index in vtmc_last_error, nothing written by it): data null; n_seg outside 1..65536;
+ * data_dims[1] != 8; any of a segment's 8 floats not finite; a radius below 0; a coordinate or radius above 2^20 in magnitude (so every
+ * product above stays finite for sample positions of that size). */
+
 /* One queued TerrainModifier (TerrainModifier.cs:19-33).  lower / upper are the values the C#
  * LowerBound / UpperBound properties return (world space): the shim copies them, so Unity's
  * Vector3.ProjectOnPlane stays on the C# side. */
@@ -376,7 +412,7 @@ typedef struct vtmc_modifier {
     float lower[3];
     float upper[3];
     float p[8];
-    const float *data;    /* VTMC_MOD_HEIGHTMAP only: borrowed for the call, copied to the device */
+    const float *data;    /* VTMC_MOD_HEIGHTMAP and VTMC_MOD_PATH only: borrowed for the call, copied to the device */
     int32_t data_dims[2];
 } vtmc_modifier;
 

@@ -60,6 +60,8 @@ MOD_PLANE, MOD_SPHERE, MOD_CYLINDER, MOD_HEIGHTMAP = 0, 1, 2, 3
 MOD_SMOOTH, MOD_FLATTEN = 4, 5   # sculpt brushes (not in the reference)
 MOD_STAMP = 9                     # pastes a stamp (vtmc_stamp_*) through a rotation and a pitch
 STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27
+MOD_PATH = 10                     # union of tapered capsules over a segment soup: rivers, tunnels, roads in one pass
+PATH_CHUNK, PATH_MAX_SEGMENTS = 256, 65536   # csrc/terrain_path.h: segments a workgroup prunes at a time; the most a modifier may hold
 MOD_NOISE = 8                     # fBm / billow / ridged noise (RidgedMultifractalModifier's device form); 6 and 7 are not defined
 
 

@@ -19,6 +19,7 @@
 #include "vtmc_ctx.h"
 #include "perlin_device.h"
 #include "terrain_box.h"
+#include "terrain_path.h"
 #include "terrain_stamp.h"
 #include <algorithm>
 #include <array>
@@ -540,9 +541,10 @@ static NoiseKernel noise_kernel(bool journal, int basis)
 
 static int check_modifier(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i)
 {
-    if ((md.kind < VTMC_MOD_PLANE || md.kind > VTMC_MOD_FLATTEN) && md.kind != VTMC_MOD_NOISE && md.kind != VTMC_MOD_STAMP)
+    if ((md.kind < VTMC_MOD_PLANE || md.kind > VTMC_MOD_FLATTEN) && md.kind != VTMC_MOD_NOISE && md.kind != VTMC_MOD_STAMP && md.kind != VTMC_MOD_PATH)
         return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: unknown kind %d", i, md.kind);
     if (md.kind == VTMC_MOD_STAMP) return check_stamp_modifier(ctx, md, i);
+    if (md.kind == VTMC_MOD_PATH) return check_path_modifier(ctx, md, i);
     if (md.kind == VTMC_MOD_NOISE) {
         for (int k = 0; k < 8; ++k)
             if (!std::isfinite(md.p[k])) return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: noise parameter p[%d] not finite", i, k);
@@ -775,6 +777,8 @@ int32_t vtmc_terrain_update(vtmc_ctx *ctx, const vtmc_modifier *mods, int32_t n_
                 VTMC_HIP(ctx, launch_box(noise_kernel(image != nullptr, noise_basis(md)), b, ctx->stream, grid, image, sh, noise_args(md, a)));
             } else if (md.kind == VTMC_MOD_STAMP) {
                 VTMC_HIP(ctx, launch_stamp_paste(ctx, md, a, grid, image, ctx->stream));
+            } else if (md.kind == VTMC_MOD_PATH) {  // stages its segments in the context's buffer, as the heightmap above
+                if (int rc = launch_path(ctx, md, a, grid, image, ctx->stream)) return rc;
             } else {  // the reference's modifiers, kinds 0-3
                 VTMC_HIP(ctx, launch_box(image ? terrain_modify_kernel<true> : terrain_modify_kernel<false>, b, ctx->stream, grid, image, sh, a));
             }

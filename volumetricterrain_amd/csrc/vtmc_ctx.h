@@ -1,5 +1,5 @@
 // vtmc_ctx.h -- the context object behind include/vtmc.h and the small host helpers every translation unit of the C-ABI layer shares
-// (context.hip, vtmc_api.hip, terrain.hip, terrain_stamp.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
+// (context.hip, vtmc_api.hip, terrain.hip, terrain_stamp.hip, terrain_path.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
 #ifndef VTMC_CTX_H
 #define VTMC_CTX_H
 #include "../../include/vtmc.h"
@@ -139,6 +139,9 @@ struct vtmc_ctx {
     // history leave them alone, vtmc_destroy frees them.
     std::map<int32_t, VtmcStamp> stamps;
     int32_t next_stamp_id = 1;
+    // terrain_path.hip: the segment records of the VTMC_MOD_PATH modifier being applied, grow-only; written only after the stream has
+    // drained, since an earlier path modifier of the same queue may still be reading it
+    VtmcDevBuf path;
     // raycast.hip, spherequery.hip: the queries and hits of vtmc_terrain_raycast / _spherecast / _closest_point (device, then their pinned staging)
     VtmcDevBuf rays;
     VtmcPinnedBuf<unsigned char> h_rays;

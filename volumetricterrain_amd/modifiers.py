@@ -8,8 +8,8 @@ order of the C# expressions.
 """
 import numpy as np
 
-from ._lib import (MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP, STAMP_MAX_DIM, STAMP_MAX_SAMPLES,
-                   STAMP_MIN_DIM, Modifier)
+from ._lib import (MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP, PATH_MAX_SEGMENTS,
+                   STAMP_MAX_DIM, STAMP_MAX_SAMPLES, STAMP_MIN_DIM, Modifier)
 
 _f = np.float32
 FLOAT_MIN_VALUE = _f(-3.4028234663852886e38)  # C# float.MinValue
@@ -306,3 +306,76 @@ class StampModifier(TerrainModifier):
 
     def attach(self, m):
         m.data_dims[:] = (self._id, 1 if self._mode == "replace" else 0)
+
+
+# -- paths (include/vtmc.h VTMC_MOD_PATH) ------------------------------------------------------------------------------------------------
+PATH_MAX_COORDINATE = 2.0 ** 20
+
+
+class PathModifier(TerrainModifier):
+    """Carves (or, with addOrErode, builds) along curves in one pass: the union of tapered capsules over `segments`, an (n, 8) float32
+    array of ax, ay, az, ra, bx, by, bz, rb -- the world-space end points and the radius at each end; round ends, the radius linear in
+    between.  A segment soup: polylines (from_polyline), trees such as the reference's RiverNode (from_tree) and disjoint pieces alike.
+    The library's own shape, not the value of the reference's queue of one eroding CylinderModifier per river segment
+    (RiverRenderer.cs:151-170).  The bounds are the AABB of all end points grown by their radii, in float32."""
+    kind = MOD_PATH
+
+    def __init__(self, segments, addOrErode=False):
+        with np.errstate(over="ignore"):
+            seg = np.ascontiguousarray(np.asarray(segments, np.float64).astype(_f))
+        if seg.ndim != 2 or seg.shape[1] != 8 or not 1 <= seg.shape[0] <= PATH_MAX_SEGMENTS:
+            raise ValueError("path segments must be an (n, 8) array with n in 1..%d" % PATH_MAX_SEGMENTS)
+        if not np.isfinite(seg).all():
+            raise ValueError("path segments must be finite")
+        if (seg[:, [3, 7]] < 0).any():
+            raise ValueError("path radii must not be negative")
+        if (np.abs(seg) > PATH_MAX_COORDINATE).any():
+            raise ValueError("path coordinates and radii must not exceed 2^20 in magnitude")
+        self._segments = seg
+        self.AddOrErode = addOrErode
+
+    @classmethod
+    def from_polyline(cls, points, radii, addOrErode=False):
+        """One segment per pair of neighbouring points; radii: one number, or one per point."""
+        pts = np.asarray(points, np.float64).reshape(-1, 3)
+        if len(pts) < 2:
+            raise ValueError("a polyline needs at least two points")
+        r = np.broadcast_to(np.asarray(radii, np.float64), (len(pts),))
+        return cls(np.column_stack([pts[:-1], r[:-1], pts[1:], r[1:]]), addOrErode)
+
+    @classmethod
+    def from_tree(cls, positions, radii, parent, addOrErode=False):
+        """One segment per node that has a parent (parent[i] >= 0), in node order, from the parent's position to the node's with the
+        radius of each end: the shape of the reference's RiverNode tree."""
+        pts = np.asarray(positions, np.float64).reshape(-1, 3)
+        r = np.broadcast_to(np.asarray(radii, np.float64), (len(pts),))
+        par = np.asarray(parent, np.int64).reshape(-1)
+        if len(par) != len(pts) or (par >= len(pts)).any():
+            raise ValueError("parent must name a node, or be negative for a root, once per position")
+        kids = np.nonzero(par >= 0)[0]
+        if not len(kids):
+            raise ValueError("a tree needs at least one node with a parent")
+        up = par[kids]
+        return cls(np.column_stack([pts[up], r[up], pts[kids], r[kids]]), addOrErode)
+
+    @property
+    def segments(self):
+        return self._segments
+
+    @property
+    def LowerBound(self):
+        s = self._segments
+        return np.minimum((s[:, 0:3] - s[:, 3:4]).min(axis=0), (s[:, 4:7] - s[:, 7:8]).min(axis=0)).astype(_f)
+
+    @property
+    def UpperBound(self):
+        s = self._segments
+        return np.maximum((s[:, 0:3] + s[:, 3:4]).max(axis=0), (s[:, 4:7] + s[:, 7:8]).max(axis=0)).astype(_f)
+
+    def params(self):
+        return []
+
+    def attach(self, m):
+        m.data = self._segments.ctypes.data   # borrowed: the struct keeps the array alive
+        m.data_dims[:] = self._segments.shape
+        m._keep = self._segments
