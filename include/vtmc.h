@@ -536,6 +536,69 @@ int32_t vtmc_stamp_info(const vtmc_ctx *ctx, int32_t stamp_id, int32_t dims[3]);
 int32_t vtmc_stamp_read(vtmc_ctx *ctx, int32_t stamp_id, float *dst, int64_t stride_x, int64_t stride_y, int64_t stride_z);
 int32_t vtmc_stamp_destroy(vtmc_ctx *ctx, int32_t stamp_id);
 
+/* Mesh stamps: a closed triangle mesh -- a rock, an arch, a prefab tunnel mouth -- voxelized on the device into an ordinary stamp (not in
+ * the reference).  positions = n_vertices x 3 floats, indices = n_triangles x 3 vertex numbers; both are host pointers, borrowed for the
+ * call and copied to the device.  Stamp sample (i, j, k) lies at px = (float)i * h + first[0], py = (float)j * h + first[1],
+ * pz = (float)k * h + first[2] (the form terrain positions take; monotonic in the index).  The result is a stamp like any other: an id from
+ * the context's counter, the dims limits above, x fastest, read by vtmc_stamp_read, pasted by VTMC_MOD_STAMP, freed by vtmc_stamp_destroy
+ * or vtmc_destroy.  The call needs no terrain and changes nothing in one: not the grid, the history, the event counter or the last result.
+ *
+ * A sample's value is s = sigma * min(dmin / h, VTMC_MESH_BAND): the distance to the nearest triangle in stamp samples, positive inside
+ * (solid, the library's sign), saturating at +-3.  A paste clamps by its own rule and anything beyond +-2 draws a void or full value, so
+ * the band loses nothing.  THE RULE, one IEEE operation per step in the order written (library built with -ffp-contract=off):
+ *
+ * On the host, FP32:  reach = the largest of h, |first[k]|, |(float)(n_k - 1) * h + first[k]| and every |coordinate| of a triangle's
+ * vertices;  g = 3.0f * h + 1e-4f * reach.
+ *
+ * Per triangle, v0, v1, v2 are its three vertices in ascending order of (x, then y, then z) of their values, so neither the order in
+ * which a triangle names its vertices nor the order of the triangles changes a bit of the result; min_k, max_k are their float extremes
+ * per axis.
+ *
+ * Distance, FP32.  dmin = +inf; per triangle (a, b, c) = (v0, v1, v2):
+ *   the triangle bids only inside its reach box: px >= min_x - g && px <= max_x + g, and the same for y and z; there
+ *   ab = b - a;  ac = c - a;  ap = p - a;  bp = p - b;  cp = p - c                    (per component)
+ *   d1 = ab.ap;  d2 = ac.ap;  d3 = ab.bp;  d4 = ac.bp;  d5 = ab.cp;  d6 = ac.cp       (u.v = (ux*vx + uy*vy) + uz*vz)
+ *   vc = d1*d4 - d3*d2;  vb = d5*d2 - d1*d6;  va = d3*d6 - d5*d4
+ *   the first region that holds (Voronoi regions of the triangle, Ericson 5.1.5), q = (a + ab*wb) + ac*wc per component unless said:
+ *     d1 <= 0 && d2 <= 0:                           wb = 0, wc = 0                      (vertex a)
+ *     d3 >= 0 && d4 <= d3:                          wb = 1, wc = 0                      (vertex b)
+ *     vc <= 0 && d1 >= 0 && d3 <= 0:                wb = d1 / (d1 - d3), wc = 0         (edge ab)
+ *     d6 >= 0 && d5 <= d6:                          wb = 0, wc = 1                      (vertex c)
+ *     vb <= 0 && d2 >= 0 && d6 <= 0:                wb = 0, wc = d2 / (d2 - d6)         (edge ac)
+ *     va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0:      w = (d4 - d3) / ((d4 - d3) + (d5 - d6));  q = b + w*(c - b)   (edge bc)
+ *     otherwise:                                    den = 1 / ((va + vb) + vc);  wb = vb*den;  wc = vc*den         (face)
+ *   cx = px - qx;  cy = py - qy;  cz = pz - qz;  d = sqrtf((cx*cx + cy*cy) + cz*cz);  if (d < dmin) dmin = d
+ * A d that is NaN (a triangle without area can give one) bids nothing, so dmin does not depend on the order of the triangles.  The reach
+ * box hides nothing the band would show: outside it a closest point found to within 1e-4 * reach is farther than 3h.  It is part of the
+ * rule so that the result never depends on how the kernel prunes triangles, whatever the rounding does to a sliver's closest point.
+ *
+ * Sign: sigma = +1 iff an odd number of triangles cover p and lie in front of it, along a ray from p towards +x; else -1.  Even-odd, so
+ * the winding order is irrelevant and a self-intersecting closed mesh gets even-odd semantics.  FP64 from the float inputs (each float
+ * converted exactly), comparisons of floats as they are:
+ *   covers:  per edge (v0 v1), (v1 v2), (v2 v0) of the triangle, its end points ordered lo, hi by (z, then y) of their values (hi is the
+ *     one with the larger z, or with equal z the larger y):  the edge straddles iff lo.z <= pz && pz < hi.z (half-open: a horizontal edge
+ *     never does);  a straddling edge counts iff  (hi.y - lo.y)*(pz - lo.z) - (py - lo.y)*(hi.z - lo.z) > 0.
+ *     The triangle covers p iff an odd number of its edges count and min_y <= py && py <= max_y.
+ *     (The order is by value, so both triangles at a shared edge compute the same determinant: a ray through an edge or a vertex is
+ *     claimed by exactly one of them.)
+ *   in front:  px >= max_x: no;  px < min_x: yes;  otherwise with u = v1 - v0, w = v2 - v0,
+ *     n.x = u.y*w.z - u.z*w.y;  n.y = u.z*w.x - u.x*w.z;  n.z = u.x*w.y - u.y*w.x
+ *     t = (n.x*(px - v0.x) + n.y*(py - v0.y)) + n.z*(pz - v0.z);   in front iff (t < 0 && n.x > 0) || (t > 0 && n.x < 0)
+ *     (a triangle with n.x == 0 never counts).
+ * Then r = dmin / h;  m = r < 3.0f ? r : 3.0f;  s = sigma > 0 ? m : -m  (no triangle in reach: +-3; on the surface: +-0).
+ *
+ * VTMC_ERR_INVALID_ARG, with nothing allocated and no id taken: a null pointer; n_triangles outside 1..VTMC_MESH_MAX_TRIANGLES;
+ * n_vertices < 3; an index outside 0..n_vertices-1; a position that is not finite or above 2^20 in magnitude; first not finite; h not
+ * finite or <= 0; dims outside the stamp limits; flags other than VTMC_MESH_TRUST_CLOSED; a mesh that is not closed, unless that flag
+ * is set.  Closed means: after dropping the triangles that repeat an index, every undirected index pair is used by exactly two
+ * triangles (checked on the host; vtmc_last_error names the first offending edge).  Vertices are told apart by index, not by position:
+ * weld duplicates first.  With VTMC_MESH_TRUST_CLOSED the rule is applied to whatever triangles are given. */
+#define VTMC_MESH_MAX_TRIANGLES (1 << 20)
+#define VTMC_MESH_BAND 3.0f              /* stamp values saturate at +-3 grid units */
+#define VTMC_MESH_TRUST_CLOSED 1u        /* skip the host's closed-mesh check */
+int32_t vtmc_stamp_from_mesh(vtmc_ctx *ctx, const float *positions, int32_t n_vertices, const int32_t *indices, int32_t n_triangles,
+                             const float first[3], float h, int32_t nx, int32_t ny, int32_t nz, uint32_t flags, int32_t *stamp_id);
+
 /* ------------------------------------------------------------------------------------------
  * Ray picking -- replaces the Physics.Raycast of the interactive edit (SceneManager.cs:114-131)
  * against the MeshColliders that BatchUpdate cooks from the extracted mesh (VoxelTerrain.cs:448-465),

@@ -53,6 +53,7 @@ SYMBOLS = [
     "vtmc_terrain_spherecast", "vtmc_terrain_closest_point", "vtmc_spherecast_device", "vtmc_closest_point_device",
     "vtmc_terrain_save", "vtmc_terrain_load", "vtmc_terrain_write_samples",
     "vtmc_stamp_create", "vtmc_stamp_capture", "vtmc_stamp_info", "vtmc_stamp_read", "vtmc_stamp_destroy",
+    "vtmc_stamp_from_mesh",
 ]
 COMM_ID_BYTES = 128
 
@@ -60,6 +61,7 @@ MOD_PLANE, MOD_SPHERE, MOD_CYLINDER, MOD_HEIGHTMAP = 0, 1, 2, 3
 MOD_SMOOTH, MOD_FLATTEN = 4, 5   # sculpt brushes (not in the reference)
 MOD_STAMP = 9                     # pastes a stamp (vtmc_stamp_*) through a rotation and a pitch
 STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27
+MESH_MAX_TRIANGLES, MESH_BAND, MESH_TRUST_CLOSED = 1 << 20, 3.0, 1   # vtmc_stamp_from_mesh: the most triangles, the band in stamp samples, the flag
 MOD_PATH = 10                     # union of tapered capsules over a segment soup: rivers, tunnels, roads in one pass
 PATH_CHUNK, PATH_MAX_SEGMENTS = 256, 65536   # csrc/terrain_path.h: segments a workgroup prunes at a time; the most a modifier may hold
 MOD_NOISE = 8                     # fBm / billow / ridged noise (RidgedMultifractalModifier's device form); 6 and 7 are not defined
@@ -188,6 +190,8 @@ def load(path=None):
         L.vtmc_stamp_info.argtypes = [vp, i32, P(i32 * 3)]
         L.vtmc_stamp_read.argtypes = [vp, i32, vp, i64, i64, i64]
         L.vtmc_stamp_destroy.argtypes = [vp, i32]
+    if not explicit or hasattr(L, "vtmc_stamp_from_mesh"):
+        L.vtmc_stamp_from_mesh.argtypes = [vp, vp, i32, vp, i32, P(ctypes.c_float * 3), ctypes.c_float, i32, i32, i32, u32, P(i32)]
     L.vtmc_comm_unique_id.argtypes = [vp]
     L.vtmc_comm_init_rank.argtypes = [vp, vp, i32, i32]
     L.vtmc_comm_destroy.argtypes = [vp]

@@ -30,6 +30,45 @@ __device__ __forceinline__ float pick8(const float (&s)[8], int i)
 }
 __device__ __forceinline__ double pick3(double x, double y, double z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
 
+// Ericson §5.1.5: the point q of triangle (a, b, c) nearest to p, by Voronoi region (vertex, edge, face) from six dot products.  One IEEE
+// operation per step in the order written here (a dot is (x*x' + y*y') + z*z'), in the precision of T: the surface queries call it in
+// double (spherequery.hip), the mesh voxelizer in float, where include/vtmc.h states it step by step (vtmc_stamp_from_mesh).
+template <class T>
+__device__ __forceinline__ void closest_on_triangle(const T *p, const T *a, const T *b, const T *c, T *q)
+{
+    const T ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+    const T ap[3] = {p[0] - a[0], p[1] - a[1], p[2] - a[2]};
+    const T d1 = ab[0] * ap[0] + ab[1] * ap[1] + ab[2] * ap[2], d2 = ac[0] * ap[0] + ac[1] * ap[1] + ac[2] * ap[2];
+    T wb = 0, wc = 0;  // q = a + wb ab + wc ac, except on edge bc
+    const T bp[3] = {p[0] - b[0], p[1] - b[1], p[2] - b[2]};
+    const T d3 = ab[0] * bp[0] + ab[1] * bp[1] + ab[2] * bp[2], d4 = ac[0] * bp[0] + ac[1] * bp[1] + ac[2] * bp[2];
+    const T cp[3] = {p[0] - c[0], p[1] - c[1], p[2] - c[2]};
+    const T d5 = ab[0] * cp[0] + ab[1] * cp[1] + ab[2] * cp[2], d6 = ac[0] * cp[0] + ac[1] * cp[1] + ac[2] * cp[2];
+    const T vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    if (d1 <= 0 && d2 <= 0) {
+        // vertex a
+    } else if (d3 >= 0 && d4 <= d3) {
+        wb = 1;  // vertex b
+    } else if (vc <= 0 && d1 >= 0 && d3 <= 0) {
+        wb = d1 / (d1 - d3);  // edge ab
+    } else if (d6 >= 0 && d5 <= d6) {
+        wc = 1;  // vertex c
+    } else if (vb <= 0 && d2 >= 0 && d6 <= 0) {
+        wc = d2 / (d2 - d6);  // edge ac
+    } else if (va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0) {
+        const T w = (d4 - d3) / ((d4 - d3) + (d5 - d6));  // edge bc
+#pragma unroll
+        for (int k = 0; k < 3; ++k) q[k] = b[k] + w * (c[k] - b[k]);
+        return;
+    } else {
+        const T den = 1 / (va + vb + vc);  // inside the face
+        wb = vb * den;
+        wc = vc * den;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) q[k] = a[k] + ab[k] * wb + ac[k] * wc;
+}
+
 // Block-local position of the vertex on cube edge e of the cell with block-local corner (lx, ly, lz): MarchingCube.compute:119-133
 // as the exact-mode emit and the oracle evaluate it -- t = -a / (b - a), p = u + t * (v - u), endpoints in the reference's order.
 __device__ __forceinline__ void edge_vertex(const float (&s)[8], int lx, int ly, int lz, int e, float p[3])

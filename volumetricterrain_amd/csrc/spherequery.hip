@@ -56,43 +56,7 @@ __device__ __forceinline__ void sub3(const double *a, const double *b, double *c
     c[2] = a[2] - b[2];
 }
 
-// Ericson §5.1.5: the point q of triangle (a, b, c) nearest to p
-__device__ __forceinline__ void closest_on_triangle(const double *p, const double *a, const double *b, const double *c, double *q)
-{
-    double ab[3], ac[3], ap[3], bp[3], cp[3];
-    sub3(b, a, ab);
-    sub3(c, a, ac);
-    sub3(p, a, ap);
-    const double d1 = dot3(ab, ap), d2 = dot3(ac, ap);
-    double wb = 0.0, wc = 0.0;  // q = a + wb ab + wc ac, except on edge bc
-    sub3(p, b, bp);
-    const double d3 = dot3(ab, bp), d4 = dot3(ac, bp);
-    sub3(p, c, cp);
-    const double d5 = dot3(ab, cp), d6 = dot3(ac, cp);
-    const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-    if (d1 <= 0.0 && d2 <= 0.0) {
-        // vertex a
-    } else if (d3 >= 0.0 && d4 <= d3) {
-        wb = 1.0;  // vertex b
-    } else if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
-        wb = d1 / (d1 - d3);  // edge ab
-    } else if (d6 >= 0.0 && d5 <= d6) {
-        wc = 1.0;  // vertex c
-    } else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
-        wc = d2 / (d2 - d6);  // edge ac
-    } else if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {
-        const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));  // edge bc
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = b[k] + w * (c[k] - b[k]);
-        return;
-    } else {
-        const double den = 1.0 / (va + vb + vc);  // inside the face
-        wb = vb * den;
-        wc = vc * den;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) q[k] = a[k] + ab[k] * wb + ac[k] * wc;
-}
+// closest_on_triangle (Ericson §5.1.5) is mc_cell.h's: the mesh voxelizer (stamp_mesh.hip) evaluates the same routine in FP32
 
 // the first s >= 0 at which the point o + s u (u unit) comes within R of the line point set {a + k (b - a), k in [0, 1]}'s cylinder
 // part (the end caps are the vertex spheres); INFINITY when it never does or starts inside the infinite cylinder

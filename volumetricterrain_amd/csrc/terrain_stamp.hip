@@ -163,7 +163,7 @@ hipError_t launch_stamp_paste(vtmc_ctx *ctx, const vtmc_modifier &md, const Terr
     return launch_box(stamp_kernel(image != nullptr, mode), TerrainBox{a.lx, a.ly, a.lz, a.dx, a.dy, a.dz}, stream, grid, image, ctx->tshape, s);
 }
 
-static int check_stamp_dims(vtmc_ctx *ctx, int32_t nx, int32_t ny, int32_t nz)
+int check_stamp_dims(vtmc_ctx *ctx, int32_t nx, int32_t ny, int32_t nz)
 {
     for (int32_t n : {nx, ny, nz})
         if (n < kStampMinDim || n > kStampMaxDim)
@@ -174,13 +174,13 @@ static int check_stamp_dims(vtmc_ctx *ctx, int32_t nx, int32_t ny, int32_t nz)
 }
 
 // a new stamp of the given (checked) dims with its device memory allocated; the id is taken only when that succeeded
-static int new_stamp(vtmc_ctx *ctx, int32_t nx, int32_t ny, int32_t nz, VtmcStamp &st)
+int new_stamp(vtmc_ctx *ctx, int32_t nx, int32_t ny, int32_t nz, VtmcStamp &st)
 {
     st.nx = nx, st.ny = ny, st.nz = nz;
     return ensure(ctx, st.samples, sizeof(float) * (size_t)nx * (size_t)ny * (size_t)nz);
 }
 
-static int32_t keep_stamp(vtmc_ctx *ctx, VtmcStamp &st)
+int32_t keep_stamp(vtmc_ctx *ctx, VtmcStamp &st)
 {
     const int32_t id = ctx->next_stamp_id++;
     ctx->stamps.emplace(id, std::move(st));

@@ -10,7 +10,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from ._lib import COMM_ID_BYTES, MESH_TRUST_CLOSED, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from .modifiers import mesh_stamp_args
 
 
 def _ptr(a):
@@ -359,6 +360,16 @@ class Extractor:
         f = (ctypes.c_int32 * 3)(*(int(v) for v in first))
         sid = ctypes.c_int32()
         self._check(self._L.vtmc_stamp_capture(self._h, ctypes.byref(f), *(int(n) for n in dims), ctypes.byref(sid)))
+        return sid.value
+
+    def stamp_from_mesh(self, vertices, triangles, first, pitch, dims, trust_closed=False):
+        """A stamp voxelized on the device from a closed triangle mesh: vertices (n, 3), triangles (m, 3) vertex numbers; sample (i, j, k)
+        lies at first + pitch * (i, j, k) (modifiers.mesh_stamp_box gives first and dims for a mesh).  The values are the signed distance
+        to the surface in stamp samples, positive inside, clamped to +-MESH_BAND.  trust_closed skips the closed-mesh check.  Returns its id."""
+        v, t, f, h, dims = mesh_stamp_args(vertices, triangles, first, pitch, dims)
+        sid = ctypes.c_int32()
+        self._check(self._L.vtmc_stamp_from_mesh(self._h, _ptr(v), len(v), _ptr(t), len(t), ctypes.byref((ctypes.c_float * 3)(*f)), float(h), *dims,
+                                                 MESH_TRUST_CLOSED if trust_closed else 0, ctypes.byref(sid)))
         return sid.value
 
     def stamp_dims(self, stamp_id):

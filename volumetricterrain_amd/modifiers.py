@@ -8,8 +8,8 @@ order of the C# expressions.
 """
 import numpy as np
 
-from ._lib import (MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP, PATH_MAX_SEGMENTS,
-                   STAMP_MAX_DIM, STAMP_MAX_SAMPLES, STAMP_MIN_DIM, Modifier)
+from ._lib import (MESH_MAX_TRIANGLES, MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP,
+                   PATH_MAX_SEGMENTS, STAMP_MAX_DIM, STAMP_MAX_SAMPLES, STAMP_MIN_DIM, Modifier)
 
 _f = np.float32
 FLOAT_MIN_VALUE = _f(-3.4028234663852886e38)  # C# float.MinValue
@@ -306,6 +306,59 @@ class StampModifier(TerrainModifier):
 
     def attach(self, m):
         m.data_dims[:] = (self._id, 1 if self._mode == "replace" else 0)
+
+
+# -- mesh stamps (include/vtmc.h vtmc_stamp_from_mesh) ------------------------------------------------------------------------------------
+MESH_MAX_COORDINATE = 2.0 ** 20
+
+
+def _stamp_dims(dims):
+    dims = tuple(int(n) for n in dims)
+    if len(dims) != 3 or not all(STAMP_MIN_DIM <= n <= STAMP_MAX_DIM for n in dims) or dims[0] * dims[1] * dims[2] > STAMP_MAX_SAMPLES:
+        raise ValueError("stamp dims must be three numbers in %d..%d with a product of at most 2^27" % (STAMP_MIN_DIM, STAMP_MAX_DIM))
+    return dims
+
+
+def mesh_stamp_box(vertices, pitch, margin=4):
+    """The stamp box of a mesh, (first, dims, centre): the mesh's AABB grown by `margin` samples and snapped to the lattice of `pitch`
+    (first = pitch * (floor(min / pitch) - margin), the last sample at pitch * (ceil(max / pitch) + margin)), and the world position
+    centre = first + pitch * (dims - 1) / 2 that StampModifier(position=centre, pitch=pitch) needs to put every sample back where it was
+    voxelized.  Mesh -> stamp -> a paste turned by q at twice the size:
+        first, dims, centre = mesh_stamp_box(v, pitch); sid = ex.stamp_from_mesh(v, tri, first, pitch, dims)
+        ex.terrain_update([StampModifier(sid, dims, where, rotation=q, pitch=2 * pitch).to_struct()])"""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3)
+    h = float(_f(pitch))
+    if not (len(v) and np.isfinite(v).all() and np.isfinite(h) and h > 0 and int(margin) == margin and margin >= 0):
+        raise ValueError("mesh_stamp_box needs finite vertices, a finite pitch > 0 and a whole margin >= 0")
+    lo = np.floor(v.min(axis=0) / h).astype(np.int64) - int(margin)
+    hi = np.ceil(v.max(axis=0) / h).astype(np.int64) + int(margin)
+    dims = _stamp_dims(hi - lo + 1)
+    first = (lo * h).astype(_f)
+    centre = (first.astype(np.float64) + h * (np.array(dims) - 1) / 2).astype(_f)
+    return first, dims, centre
+
+
+def mesh_stamp_args(vertices, triangles, first, pitch, dims):
+    """What vtmc_stamp_from_mesh takes, checked as the library checks it (ValueError here, VTMC_ERR_INVALID_ARG there) except for the
+    closed-mesh rule, which stays the library's: (positions float32 (n, 3), indices int32 (m, 3), first float32 (3,), pitch, dims)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = np.ascontiguousarray(np.asarray(vertices, np.float64).astype(_f))
+        f = np.asarray(first, np.float64).astype(_f).reshape(-1)
+        h = _f(pitch)
+    t = np.asarray(triangles)
+    if v.ndim != 2 or v.shape[1] != 3 or len(v) < 3:
+        raise ValueError("mesh vertices must be an (n, 3) array with n >= 3")
+    if t.ndim != 2 or t.shape[1] != 3 or not 1 <= len(t) <= MESH_MAX_TRIANGLES or t.dtype.kind not in "iu":
+        raise ValueError("mesh triangles must be an (m, 3) integer array with m in 1..%d" % MESH_MAX_TRIANGLES)
+    if t.min() < 0 or t.max() >= len(v):
+        raise ValueError("mesh triangle index outside the %d vertices" % len(v))
+    if not np.isfinite(v).all() or np.abs(v).max() > MESH_MAX_COORDINATE:
+        raise ValueError("mesh positions must be finite and at most 2^20 in magnitude")
+    if f.shape != (3,) or not np.isfinite(f).all():
+        raise ValueError("first must be three finite numbers")
+    if not (np.isfinite(h) and h > 0):
+        raise ValueError("mesh stamp pitch must be finite and > 0")
+    return v, np.ascontiguousarray(t, np.int32), f, h, _stamp_dims(dims)
 
 
 # -- paths (include/vtmc.h VTMC_MOD_PATH) ------------------------------------------------------------------------------------------------
