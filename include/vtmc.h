@@ -214,7 +214,13 @@ int32_t vtmc_last_placement(const vtmc_ctx *ctx, float ms[16], int32_t *n_candid
 
 /* Synthetic density sampler (the reference has no noise field of its own):
  * density = sum_{o<octaves} gain^o * perlin(p*frequency*lacunarity^o) - (p.y - ramp_center)*ramp_scale,
- * p = volume origin + sample index, FP32, Perlin 2002 improved noise with a SplitMix64 permutation. */
+ * p = volume origin + sample index, FP32, Perlin 2002 improved noise with a SplitMix64 permutation.
+ * The lattice coordinate of octave o is the FP32 chain x = (float)(origin + index) * frequency, then x = x * lacunarity per octave; its
+ * cell is (int)floorf(x), which is defined only below 2^31.  Any frequency, lacunarity and gain are accepted (negative, zero, below 1)
+ * as long as the chain stays inside that range: VTMC_ERR_INVALID_ARG, nothing written, when the largest |origin + index| of any volume
+ * and axis times |frequency| * max(1, |lacunarity|)^(octaves - 1), evaluated in double with 2^-19 on top for the chain's own roundings,
+ * is not below 2^31 (frequency or lacunarity that are not finite included), or when origin + dim - 1 leaves int32.  From 2^24 on a
+ * coordinate has no fraction left: that octave is 0, which is the definition's value there, not an error. */
 typedef struct vtmc_density_params {
     uint64_t seed;
     float frequency;

@@ -8,6 +8,8 @@
 // ramp.  VALU + small LDS tables; writes are lane-contiguous along the stride-1 axis.
 #include "vtmc_ctx.h"
 #include "perlin_device.h"   // fade / mixf / gradf / noise3: the one Perlin of the library
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <type_traits>
 #pragma clang diagnostic ignored "-Winline-asm"   // the sign words' v_writelane names m0 as clobbered: a reserved register, which this file's kernels never use otherwise
@@ -114,7 +116,10 @@ __global__ __launch_bounds__(256) void density_row_kernel(DensityLaunch dl, cons
     if (idx >= dl.n_volumes * n_steps) return;
     const int vol = idx / n_steps, j = idx - vol * n_steps;
     const float pw = (float)(origins[3 * vol + axis] + j);
-    float y = pw * dl.frequency, yp = (pw - 1.0f) * dl.frequency;
+    // the previous step's coordinate as ITS thread converts it: from 2^24 on, pw - 1.0f is not (float)(index - 1) (both round, to different
+    // neighbours), and a `prev` that is not the previous row's `cell` keeps a stale face
+    const float pp = (float)((long long)origins[3 * vol + axis] + j - 1);
+    float y = pw * dl.frequency, yp = pp * dl.frequency;
     float *row = rows + (long long)idx * kRowDwords;
     unsigned m1 = 0, m2 = 0, yc[2] = {0, 0};
     for (int o = 0; o < 8; ++o) {
@@ -466,6 +471,23 @@ hipError_t launch_density(const DensityLaunch &dl, const unsigned char *d_perm, 
 
 size_t density_rows_bytes(int n_volumes, int dy, int dz) { return (size_t)n_volumes * (size_t)(dy > dz ? dy : dz) * kRowDwords * sizeof(float); }
 
+// The largest magnitude a lattice coordinate of the fill can take: the largest |origin + index| of any volume and axis times
+// |f| * max(1, |L|)^(octaves - 1), in double, with 2^-19 on top for the roundings of the FP32 chain (at most 17 of 2^-24 each).  The
+// kernels convert floorf of it to int: undefined from 2^31 on.  Infinite for a sample index outside int32; NaN for parameters that are not finite.
+static double density_lattice_reach(const vtmc_density_params *prm, const int32_t *origins, int n_volumes, int dx, int dy, int dz)
+{
+    const int dims[3] = {dx, dy, dz};
+    long long far = 0;
+    for (int v = 0; v < n_volumes; ++v)
+        for (int a = 0; a < 3; ++a) {
+            const long long lo = origins[3 * v + a], hi = lo + dims[a] - 1;
+            if (hi > 0x7fffffffll) return INFINITY;
+            far = std::max(far, std::max(lo < 0 ? -lo : lo, hi < 0 ? -hi : hi));
+        }
+    const double f = std::fabs((double)prm->frequency), l = std::fabs((double)prm->lacunarity);
+    return (double)far * f * std::pow(l > 1.0 ? l : 1.0, prm->octaves - 1) * (1.0 + 1.0 / 524288.0);
+}
+
 }  // namespace vtmc
 
 using namespace vtmc;
@@ -480,6 +502,11 @@ int32_t vtmc_density_fill_device_async(vtmc_ctx *ctx, const vtmc_density_params 
     if (!params || !origins || !d_out) return fail(ctx, VTMC_ERR_INVALID_ARG, "null argument");
     if (n_volumes <= 0 || dim_x <= 0 || dim_y <= 0 || dim_z <= 0 || params->octaves < 1 || params->octaves > 16)
         return fail(ctx, VTMC_ERR_INVALID_ARG, "bad volume count, dims or octaves");
+    {
+        const double reach = density_lattice_reach(params, origins, n_volumes, dim_x, dim_y, dim_z);
+        if (!(reach < 2147483648.0))
+            return fail(ctx, VTMC_ERR_INVALID_ARG, "density lattice coordinates reach %g in these volumes (limit 2^31)", reach);
+    }
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     if (!ctx->perm_valid || ctx->perm_seed != params->seed) {
