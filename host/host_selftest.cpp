@@ -89,6 +89,32 @@ static int cpu_tests()
     CHECK(vt.Sample(16, 16, 16) <= -1.0f);                // -clamp(4,..) = -full -> void range
     CHECK(rec->blocks.size() == 8);                       // AABB [12,20]: up >= 8b && low <= 8b+8 holds for b = 1, 2 only
     for (const Int3 &b : rec->blocks) CHECK(b._x >= 1 && b._x <= 2 && b._y >= 1 && b._y <= 2 && b._z >= 1 && b._z <= 2);
+
+    {  // SetControlMap's two errors (VoxelTerrain.cs:187-195) come before anything reaches the backend; the layer needs a resident terrain
+        auto message = [&](const std::vector<Color> &map, int group) -> std::string {
+            try {
+                vt.SetControlMap(map, group);
+            } catch (const UnityException &e) {
+                return e.what();
+            }
+            return "";
+        };
+        vt._matControlFineness = 1;
+        const std::vector<Color> map(16 * 16 * 16);
+        CHECK(message(map, 0) == "invalid control map group" && message(map, 3) == "invalid control map group");
+        CHECK(message(std::vector<Color>(100), 1) == "invalid control map data size");
+        vt._matControlFineness = 2;
+        CHECK(message(map, 2) == "invalid control map data size");
+        vt._matControlFineness = 1;
+        CHECK(message(map, 1).find("device-resident") != std::string::npos);   // this terrain keeps its samples on the host
+        bool refused = false;
+        try {
+            MaterialStroke(Vector3(0, 0, 0), -1.0f, 0);
+        } catch (const std::invalid_argument &) {
+            refused = true;
+        }
+        CHECK(refused);
+    }
     return 0;
 }
 
@@ -178,6 +204,22 @@ static int gpu_resident_run(const std::string &out)
             fv.write(reinterpret_cast<const char *>(&m.vertices[(size_t)i]), 12);
             fn.write(reinterpret_cast<const char *>(&m.normals[(size_t)i]), 12);
         }
+    }
+    {   // the material layer: a control map, a stroke, and the weights of the edit's vertices
+        vt._matControlFineness = 1;
+        std::vector<Color> map(16 * 16 * 16);
+        for (Color &c : map) c.g = 1.0f;                                  // all grass: channel 1
+        vt.SetControlMap(map, 1);
+        vt.Paint({MaterialStroke(Vector3(5.0f, 4.0f, 9.0f), 6.0f, 2)});   // rock around the dig: channel 2
+        const std::vector<uint8_t> &w = vt.VertexMaterials();
+        if (w.size() != (size_t)vt.LastTriangleCount() * 3 * 8) return 4;
+        size_t rock = 0;
+        for (size_t v = 0; v < w.size(); v += 8) {
+            if (w[v] != 0 || w[v + 3] != 0 || w[v + 4] != 0) return 5;    // only channels 1 and 2 were ever set
+            rock += w[v + 2] > w[v + 1];
+        }
+        std::printf("resident materials: %zu vertices, %zu mostly rock\n", w.size() / 8, rock);
+        if (rock == 0) return 6;
     }
     vt.Free();
     std::printf("HOST-RESIDENT-OK\n");

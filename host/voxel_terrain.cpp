@@ -181,6 +181,37 @@ public:
             throw UnityException(std::string("vtmc_terrain_read_samples: ") + vtmc_last_error(_ctx));
     }
 
+    int MaterialInit(int fineness) override
+    {
+        if (vtmc_material_init(_ctx, fineness) != VTMC_OK) throw UnityException(std::string("vtmc_material_init: ") + vtmc_last_error(_ctx));
+        return 16 * fineness;
+    }
+    void MaterialSetControlMap(const Color *mapData, int group) override
+    {
+        if (vtmc_material_set_control_map(_ctx, reinterpret_cast<const float *>(mapData), group) != VTMC_OK)
+            throw UnityException(std::string("vtmc_material_set_control_map: ") + vtmc_last_error(_ctx));
+    }
+    void MaterialPaint(const std::vector<MaterialStroke> &strokes) override
+    {
+        std::vector<vtmc_material_stroke> s(strokes.size());
+        for (size_t i = 0; i < strokes.size(); i++) {
+            s[i].center[0] = strokes[i]._center.x, s[i].center[1] = strokes[i]._center.y, s[i].center[2] = strokes[i]._center.z;
+            s[i].radius = strokes[i]._radius;
+            s[i].strength = strokes[i]._strength;
+            s[i].channel = strokes[i]._channel;
+        }
+        if (vtmc_material_paint(_ctx, s.data(), (int32_t)s.size()) != VTMC_OK)
+            throw UnityException(std::string("vtmc_material_paint: ") + vtmc_last_error(_ctx));
+    }
+    void MaterialVertices(std::vector<uint8_t> &out) override
+    {
+        int64_t n = 0;
+        if (vtmc_material_vertices(_ctx, &n) != VTMC_OK) throw UnityException(std::string("vtmc_material_vertices: ") + vtmc_last_error(_ctx));
+        out.resize((size_t)n * VTMC_MATERIAL_CHANNELS);
+        if (vtmc_material_read_vertices(_ctx, out.data(), n) != VTMC_OK)
+            throw UnityException(std::string("vtmc_material_read_vertices: ") + vtmc_last_error(_ctx));
+    }
+
 private:
     vtmc_ctx *_ctx = nullptr;
     int _dims[3] = {0, 0, 0};
@@ -215,7 +246,41 @@ void VoxelTerrain::Init()
     }
     _nextUpdateblocks.clear();
     _modifierQueue.clear();
+    _hasMaterialLayer = false;  // vtmc_terrain_init drops the layer
+    _vertexMaterials.clear();
     _initialised = true;
+}
+
+void VoxelTerrain::EnsureMaterialLayer()
+{
+    if (!_initialised || !_deviceResident) throw UnityException("the material layer needs an initialised device-resident terrain");
+    if (_hasMaterialLayer) return;
+    _matControlFineness = std::min(std::max(_matControlFineness, 1), 8);  // Mathf.Clamp, VoxelTerrain.cs:191
+    _backend->MaterialInit(_matControlFineness);
+    _hasMaterialLayer = true;
+}
+
+// VoxelTerrain.cs:186-209
+void VoxelTerrain::SetControlMap(const Color *mapData, size_t length, int group)
+{
+    if (group < 1 || group > 2) throw UnityException("invalid control map group");
+    const size_t controlMapSize = (size_t)std::min(std::max(_matControlFineness, 1), 8) * 16;
+    if (!mapData || length != controlMapSize * controlMapSize * controlMapSize) throw UnityException("invalid control map data size");
+    EnsureMaterialLayer();
+    _backend->MaterialSetControlMap(mapData, group);
+}
+
+void VoxelTerrain::Paint(const std::vector<MaterialStroke> &strokes)
+{
+    EnsureMaterialLayer();
+    _backend->MaterialPaint(strokes);
+}
+
+const std::vector<uint8_t> &VoxelTerrain::VertexMaterials()
+{
+    EnsureMaterialLayer();
+    _backend->MaterialVertices(_vertexMaterials);
+    return _vertexMaterials;
 }
 
 // VoxelTerrain.cs:214-245

@@ -4,12 +4,14 @@
 //
 // Same names, argument meaning and error behaviour as the C# class, so a maintainer can diff them:
 //   Init / InsertModifier / Update / Free          VoxelTerrain.cs:121, :251, :262, :214
+//   SetControlMap, _matControlFineness             VoxelTerrain.cs:186-209, :113 (device-resident terrains: the layer of vtmc_material_*)
 //   BatchUpdate (private there, public here for tests) VoxelTerrain.cs:330-477
 //   _width/_elevation/_height, _voxelScale, TerrainOrigin, blockSize, maxSampleResolution
 // What differs on purpose: the three ComputeShader fields and the nine ComputeBuffer bindings
 // (VoxelTerrain.cs:64-66, :370-421) are replaced by ONE vtmc context (include/vtmc.h); Unity
-// objects (GameObject / Mesh / MeshCollider / Material, SetControlMap) have no equivalent here --
-// a block's result is a plain BlockMesh {vertices, normals, triangles}.  No CPU extraction path
+// objects (GameObject / Mesh / MeshCollider / Material) have no equivalent here --
+// a block's result is a plain BlockMesh {vertices, normals, triangles}; the control maps SetControlMap hands to the Material live in the
+// context's material layer instead, and what the shaders would sample from them comes back per vertex (VertexMaterials).  No CPU extraction path
 // exists: without libvtmc.so + a HIP device Init() throws.
 #ifndef VTMC_HOST_VOXEL_TERRAIN_HPP
 #define VTMC_HOST_VOXEL_TERRAIN_HPP
@@ -48,6 +50,11 @@ struct Vector3 {
 struct Vector2 {
     float x = 0, y = 0;
 };
+// UnityEngine.Color stand-in
+struct Color {
+    float r = 0, g = 0, b = 0, a = 0;
+};
+static_assert(sizeof(Color) == 16, "a Color[] is read as rgba floats");
 
 namespace MathHelper {
 // Utility.cs:17-47 -- the block-index key
@@ -267,6 +274,23 @@ private:
     float _low[3], _up[3];
 };
 
+// New (not in the reference, which can only replace a control map whole): one paint stroke on the material layer (vtmc_material_stroke
+// of include/vtmc.h).  Every texel within _radius of _center (world space) is blended towards the one-hot of _channel (0..3: control map
+// 1's r, g, b, a; 4..7: control map 2's) by _strength * clamp01(2 (1 - d / _radius)).
+struct MaterialStroke {
+    Vector3 _center;
+    float _radius;
+    int _channel;
+    float _strength;
+    MaterialStroke(Vector3 center, float radius, int channel, float strength = 1.0f)
+        : _center(center), _radius(radius), _channel(channel), _strength(strength)
+    {
+        if (!std::isfinite(center.x) || !std::isfinite(center.y) || !std::isfinite(center.z) || !std::isfinite(radius) || !(radius > 0) ||
+            !std::isfinite(strength) || !(strength >= 0 && strength <= 1) || channel < 0 || channel > 7)
+            throw std::invalid_argument("MaterialStroke: invalid centre, radius, channel or strength");
+    }
+};
+
 // What replaces a block's Unity Mesh (VoxelTerrain.cs:448-465): unindexed soup, indices 0..n-1.
 struct BlockMesh {
     std::vector<Vector3> vertices;
@@ -308,6 +332,13 @@ struct ExtractBackend {
         throw std::logic_error("TerrainUpdate on a backend without device-resident terrain");
     }
     virtual void TerrainReadSamples(std::vector<float> &) { throw std::logic_error("TerrainReadSamples unsupported"); }
+
+    // Material layer of a device-resident terrain (vtmc_material_*).  MaterialInit returns the layer's size C = 16 * fineness.
+    virtual int MaterialInit(int) { throw std::logic_error("MaterialInit on a backend without a material layer"); }
+    virtual void MaterialSetControlMap(const Color *, int) { throw std::logic_error("MaterialSetControlMap unsupported"); }
+    virtual void MaterialPaint(const std::vector<MaterialStroke> &) { throw std::logic_error("MaterialPaint unsupported"); }
+    // 8 bytes per vertex of the last TerrainUpdate's result: vertex 3 t + v of triangle t
+    virtual void MaterialVertices(std::vector<uint8_t> &) { throw std::logic_error("MaterialVertices unsupported"); }
 };
 
 class VoxelTerrain {
@@ -324,6 +355,7 @@ public:
     // Queues holding a modifier the device cannot evaluate (Describe() == false) are refused.
     bool _deviceResident = false;
     uint64_t _seed = 1;                               // seed of the device-side void / full values
+    int _matControlFineness = 8;                      // VoxelTerrain.cs:113: control maps of 16 * fineness texels per axis, clamped to 1..8
 
     VoxelTerrain();
     ~VoxelTerrain();
@@ -338,6 +370,13 @@ public:
     void InsertModifier(std::shared_ptr<TerrainModifier> modifier);     // VoxelTerrain.cs:251-254
     void Update();                                                      // VoxelTerrain.cs:262-325
     void BatchUpdate();                                                 // VoxelTerrain.cs:330-477
+    // VoxelTerrain.cs:186-209, device-resident terrains: mapData = (16 * _matControlFineness)^3 Colors, x fastest; group 1 or 2 (the
+    // reference's Triplanar8Tex material has two).  Throws the reference's two errors.  The layer is created on the first call after Init.
+    void SetControlMap(const Color *mapData, size_t length, int group);
+    void SetControlMap(const std::vector<Color> &mapData, int group) { SetControlMap(mapData.data(), mapData.size(), group); }
+    void Paint(const std::vector<MaterialStroke> &strokes);             // new: vtmc_material_paint; creates the layer when there is none
+    // new: the material weights of the last Update's triangles, 8 bytes per vertex in the order of its triangles (3 per triangle)
+    const std::vector<uint8_t> &VertexMaterials();
 
     // -- inspection (tests, callers that consume the meshes) ----------------------------------
     const BlockMesh &Block(int x, int y, int z) const { return _blocks[((size_t)x * (_elevation / blockSize) + y) * (_height / blockSize) + z]; }
@@ -351,6 +390,9 @@ public:
 
 private:
     void ApplyMeshes(const std::vector<CSTriangle> &csTriangles, const std::vector<int> &offsets);  // VoxelTerrain.cs:430-465
+    void EnsureMaterialLayer();
+    bool _hasMaterialLayer = false;
+    std::vector<uint8_t> _vertexMaterials;
     std::vector<float> _voxelSamples;  // float[W+2, E+2, H+2], row-major, z fastest (VoxelTerrain.cs:145)
     std::vector<BlockMesh> _blocks;    // GameObject[,,] stand-in (VoxelTerrain.cs:61)
     std::vector<MathHelper::Int3> _nextUpdateblocks, _lastUpdateBlocks;

@@ -606,6 +606,83 @@ int32_t vtmc_stamp_from_mesh(vtmc_ctx *ctx, const float *positions, int32_t n_ve
                              const float first[3], float h, int32_t nx, int32_t ny, int32_t nz, uint32_t flags, int32_t *stamp_id);
 
 /* ------------------------------------------------------------------------------------------
+ * Material layer -- the device form of VoxelTerrain.SetControlMap (VoxelTerrain.cs:186-209, filled by TerrainEngine.cs:107-142): the two
+ * 3-D RGBA8 splat textures the triplanar shaders sample at (worldPos - _Offset) * _Scale (Triplanar8Tex.shader:97,193), kept in HBM beside
+ * the density grid, a paint brush on them (not in the reference, which can only replace a texture whole, from the CPU), and the material
+ * weights of every vertex of an extracted mesh, so that a consumer that is not Unity's sampler -- a collider's surface type, a footstep
+ * sound, an exporter, vertex colours -- needs no 3-D texture.
+ *
+ * The layer is a cube of C = 16 * fineness texels per axis, fineness 1..8 (the reference clamps it so, VoxelTerrain.cs:191).  A texel
+ * holds VTMC_MATERIAL_CHANNELS = 8 bytes at byte offset 8 * (i + C*(j + C*k)), x fastest as the reference's map[x + y*C + z*C*C]:
+ * channels 0..3 are group 1's r, g, b, a (_matControlTex1), channels 4..7 group 2's.  The cube spans the terrain's W x E x H cells,
+ * stretched per axis, as _Scale = 1 / TerrainSize does.  All arithmetic below is FP32, one IEEE operation per step in the order written
+ * (library built with -ffp-contract=off); rintf rounds ties to even, as Mathf.Round.
+ *
+ * vtmc_material_init  needs a terrain (VTMC_ERR_NO_RESULT without one); fineness outside 1..8 is VTMC_ERR_INVALID_ARG.  Allocates the cube
+ *   and sets every texel to (255,0,0,0, 0,0,0,0), as TerrainSample starts with _matComponents[0] = 1.  Calling it again replaces the layer.
+ *   vtmc_terrain_init and vtmc_terrain_load drop the layer (the dims may change); every other material call without a layer answers
+ *   VTMC_ERR_NO_RESULT.  The layer is no part of the terrain file, whose format stays as it is: a host persists it with
+ *   vtmc_material_read / _write.
+ * vtmc_material_set_control_map  group is 1 or 2; rgba is C^3 x 4 floats, a Color[] in the texel order above.  Each channel becomes
+ *   (uint8)rintf(clamp(c, 0, 1) * 255.0f); the other group's four bytes are kept.  The float image crosses PCIe and is quantised on the
+ *   device.  A NaN anywhere in the image is VTMC_ERR_INVALID_ARG, with nothing written.
+ * vtmc_material_write / _read  copy the whole C^3 x 8 bytes; *size (may be NULL) receives C.  vtmc_material_read with dst = NULL is the
+ *   size query.
+ *
+ * vtmc_material_paint  applies n_strokes strokes in order.  On the host, per axis:  ts_x = ((float)W * voxel_scale) / (float)C, with E and
+ *   H for y and z.  Per texel (i, j, k) and stroke (c, r, s, channel):
+ *     px = ((float)i + 0.5f) * ts_x + origin_x;  py, pz alike;  dx = px - c0;  dy, dz alike
+ *     d = sqrtf((dx*dx + dy*dy) + dz*dz);  t = 1 - d / r;  t = t + t;  t = clamp(t, 0, 1);  w = s * t      (the sculpt brushes' falloff)
+ *     w == 0: the texel keeps its bytes;  otherwise per channel k:
+ *       v = (float)old[k];  T = (k == channel) ? 255.0f : 0.0f;  v = v + (T - v) * w;  new[k] = (uint8)rintf(v)     (in [0, 255] unclamped)
+ *   A stroke does not wrap: texels are 0..C-1 per axis, paint near one face never reaches the opposite one.  The rule is pointwise, so the
+ *   result does not depend on which box of texels the kernel walks or on its applying every stroke of the call to a texel in one pass.
+ *   VTMC_ERR_INVALID_ARG (the stroke's index in vtmc_last_error, nothing written by the call): a centre that is not finite; r not finite or
+ *   <= 0; s not finite or outside [0, 1]; a channel outside 0..7; n_strokes outside 0..VTMC_MATERIAL_MAX_STROKES; null strokes with
+ *   n_strokes > 0.
+ *   Paint is NOT journaled: vtmc_terrain_undo / _redo restore densities and leave the layer alone (an editor that wants to undo paint
+ *   keeps the bytes of vtmc_material_read, 8 C^3 of them at most 16 MB).  Paint takes no event number, marks no block dirty, extracts
+ *   nothing and leaves the last result and its vertex weights as they are.
+ *
+ * vtmc_material_vertices  computes the weights of every vertex of the result the context holds, 8 bytes per vertex, into a library-owned,
+ *   grow-only buffer; *n_vertices (may be NULL) receives n.  The result must come from the resident terrain -- vtmc_terrain_update, _undo,
+ *   _redo, or _load with extraction -- in either output mode.  Soup: vertex 3*t + v of triangle t in record order, n = 3*T.  Indexed: one
+ *   per vtmc_vertex, n = V.  Per vertex, with (bx, by, bz) the block of the dirty list its `block` field (soup) or the block vertex
+ *   offsets (indexed) name, and sx = (float)C / (float)W computed once on the host (E and H for y and z):
+ *     gx = (float)(8*bx) + position.x;  tx = gx * sx;  tx = tx - 0.5f
+ *     i0 = (int)floorf(tx);  fx = tx - (float)i0;  i0 = ((i0 % C) + C) % C;  i1 = (i0 + 1) % C
+ *       (the texture's Repeat wrap: tx = -0.5 at gx = 0 reads texels C-1 and 0);  j0, j1, fy and k0, k1, fz alike
+ *     per channel, bytes converted to float, in the stamp's lerp form:
+ *       a00 = m[i0,j0,k0] + (m[i1,j0,k0] - m[i0,j0,k0]) * fx;  a10 the same at j1;  a01 at k1;  a11 at j1, k1
+ *       b0 = a00 + (a10 - a00) * fy;  b1 = a01 + (a11 - a01) * fy;  q = b0 + (b1 - b0) * fz;  out = (uint8)rintf(q)
+ *   The filter is THE LIBRARY'S OWN: a trilinear filter in FP32.  A texture unit filters with fixed-point weights of a few bits; its
+ *   values are not reproduced and parity with a GPU sampler is not claimed.
+ *   VTMC_ERR_NO_RESULT without a layer, without a result, or when the result did not come from the terrain (vtmc_extract_*).  T = 0 is
+ *   success with 0 vertices.  The weights belong to one result: after any later extract they are stale, and vtmc_material_read_vertices /
+ *   _device_results answer VTMC_ERR_NO_RESULT until vtmc_material_vertices runs again.
+ * vtmc_material_read_vertices  copies the n x 8 bytes; a capacity below n is VTMC_ERR_INVALID_ARG.
+ * vtmc_material_device_results  the device pointer of the same (valid until the next vtmc_material_vertices / destroy).
+ * ------------------------------------------------------------------------------------------ */
+#define VTMC_MATERIAL_CHANNELS 8
+#define VTMC_MATERIAL_MAX_STROKES 4096
+
+typedef struct vtmc_material_stroke {
+    float center[3];   /* world */
+    float radius;
+    float strength;    /* [0, 1] */
+    int32_t channel;   /* 0..7 */
+} vtmc_material_stroke;
+
+int32_t vtmc_material_init(vtmc_ctx *ctx, int32_t fineness);
+int32_t vtmc_material_set_control_map(vtmc_ctx *ctx, const float *rgba, int32_t group);
+int32_t vtmc_material_write(vtmc_ctx *ctx, const uint8_t *src);
+int32_t vtmc_material_read(vtmc_ctx *ctx, uint8_t *dst, int32_t *size);
+int32_t vtmc_material_paint(vtmc_ctx *ctx, const vtmc_material_stroke *strokes, int32_t n_strokes);
+int32_t vtmc_material_vertices(vtmc_ctx *ctx, int64_t *n_vertices);
+int32_t vtmc_material_read_vertices(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity_vertices);
+int32_t vtmc_material_device_results(vtmc_ctx *ctx, const uint8_t **d_weights, int64_t *n_vertices);
+
+/* ------------------------------------------------------------------------------------------
  * Ray picking -- replaces the Physics.Raycast of the interactive edit (SceneManager.cs:114-131)
  * against the MeshColliders that BatchUpdate cooks from the extracted mesh (VoxelTerrain.cs:448-465),
  * without any mesh on the host.  The surface is the triangle set vtmc_extract_grid emits for every

@@ -54,6 +54,8 @@ SYMBOLS = [
     "vtmc_terrain_save", "vtmc_terrain_load", "vtmc_terrain_write_samples",
     "vtmc_stamp_create", "vtmc_stamp_capture", "vtmc_stamp_info", "vtmc_stamp_read", "vtmc_stamp_destroy",
     "vtmc_stamp_from_mesh",
+    "vtmc_material_init", "vtmc_material_set_control_map", "vtmc_material_write", "vtmc_material_read", "vtmc_material_paint",
+    "vtmc_material_vertices", "vtmc_material_read_vertices", "vtmc_material_device_results",
 ]
 COMM_ID_BYTES = 128
 
@@ -64,6 +66,7 @@ STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27
 MESH_MAX_TRIANGLES, MESH_BAND, MESH_TRUST_CLOSED = 1 << 20, 3.0, 1   # vtmc_stamp_from_mesh: the most triangles, the band in stamp samples, the flag
 MOD_PATH = 10                     # union of tapered capsules over a segment soup: rivers, tunnels, roads in one pass
 PATH_CHUNK, PATH_MAX_SEGMENTS = 256, 65536   # csrc/terrain_path.h: segments a workgroup prunes at a time; the most a modifier may hold
+MATERIAL_CHANNELS, MATERIAL_MAX_STROKES = 8, 4096   # the material layer: bytes per texel and per vertex; the most strokes of one paint call
 MOD_NOISE = 8                     # fBm / billow / ridged noise (RidgedMultifractalModifier's device form); 6 and 7 are not defined
 
 
@@ -73,6 +76,11 @@ class Modifier(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("add_or_erode", ctypes.c_int32), ("lower", ctypes.c_float * 3),
                 ("upper", ctypes.c_float * 3), ("p", ctypes.c_float * 8), ("data", ctypes.c_void_p),
                 ("data_dims", ctypes.c_int32 * 2)]
+
+
+class MaterialStroke(ctypes.Structure):
+    """vtmc_material_stroke: one paint stroke on the material layer, centre in world space."""
+    _fields_ = [("center", ctypes.c_float * 3), ("radius", ctypes.c_float), ("strength", ctypes.c_float), ("channel", ctypes.c_int32)]
 
 
 class VolumeBatch(ctypes.Structure):
@@ -192,6 +200,15 @@ def load(path=None):
         L.vtmc_stamp_destroy.argtypes = [vp, i32]
     if not explicit or hasattr(L, "vtmc_stamp_from_mesh"):
         L.vtmc_stamp_from_mesh.argtypes = [vp, vp, i32, vp, i32, P(ctypes.c_float * 3), ctypes.c_float, i32, i32, i32, u32, P(i32)]
+    if not explicit or hasattr(L, "vtmc_material_init"):
+        L.vtmc_material_init.argtypes = [vp, i32]
+        L.vtmc_material_set_control_map.argtypes = [vp, vp, i32]
+        L.vtmc_material_write.argtypes = [vp, vp]
+        L.vtmc_material_read.argtypes = [vp, vp, P(i32)]
+        L.vtmc_material_paint.argtypes = [vp, vp, i32]
+        L.vtmc_material_vertices.argtypes = [vp, P(i64)]
+        L.vtmc_material_read_vertices.argtypes = [vp, vp, i64]
+        L.vtmc_material_device_results.argtypes = [vp, P(vp), P(i64)]
     L.vtmc_comm_unique_id.argtypes = [vp]
     L.vtmc_comm_init_rank.argtypes = [vp, vp, i32, i32]
     L.vtmc_comm_destroy.argtypes = [vp]

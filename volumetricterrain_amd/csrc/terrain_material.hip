@@ -1,0 +1,407 @@
+// terrain_material.hip -- the material layer: the device form of VoxelTerrain.SetControlMap (VoxelTerrain.cs:186-209), a paint brush on it
+// and the material weights of every vertex of an extracted mesh (vtmc_material_*).  The rule, operation by operation, is in
+// include/vtmc.h; the kernels follow it bit for bit (library built with -ffp-contract=off).  The host half -- argument checks, the
+// per-axis factors, the texel box of a paint call -- is terrain_material.h.
+//
+// The vertex pass is the hot one: one pass over the result of an extract.  A soup record is 19 dwords, so a lane that reads "its" record
+// walks memory at a 76-byte stride; instead a workgroup loads a tile of kMatTile records as consecutive 16-byte pieces into LDS (every
+// 128-byte line arrives whole either way, and only once), then each VERTEX gets a lane: vertex 3t + v reads dwords 3v..3v+2 and 18 of
+// record t from LDS.  Consecutive lanes own consecutive vertices, so their 8-byte results are consecutive in memory and the store is
+// coalesced as it stands: no LDS stage on the way out.  Per vertex the kernel fetches 8 texels, each as one 8-byte load; the cube is at
+// most 128^3 x 8 B = 16 MB, read-shared by every wave, and lives in L2 and the Infinity Cache.  Traffic that must reach HBM:
+// 76 T read + 24 T written (soup), 24 V + 8 V (indexed).
+#include "terrain_material.h"
+#include "vtmc_ctx.h"
+#include <cmath>
+
+namespace vtmc {
+
+constexpr int kMatTile = 256;  // records (triangles or vertices) per workgroup, one workgroup of 256 threads per tile
+
+struct MaterialVertexArgs {
+    const uint2 *layer;  // C^3 texels, x fastest
+    int C;
+    float s[3];       // texels per cell, per axis
+    const int *list;  // device (bx, by, bz) triples of the dirty list, or null: every block, b = bx + nbx * (by + nby * bz)
+    uint32_t n_blocks;
+    int nbx, nby;
+    FastDiv d_nbx, d_nby;
+};
+
+struct MaterialPaintArgs {
+    float ts[3], origin[3];
+    int C;
+    int lo[3], n[3];  // the texel box the launch walks
+    int n_strokes;
+};
+
+// tx = g * s - 0.5 cut into the texel below it, wrapped as a Repeat texture, the one after it, and the weight
+__device__ __forceinline__ void material_axis(float g, float s, int C, int &i0, int &i1, float &f)
+{
+    float t = g * s;
+    t = t - 0.5f;
+    i0 = (int)floorf(t);
+    f = t - (float)i0;
+    // ((i0 % C) + C) % C; a vertex of the terrain gives i0 in -1..C-1, which needs no division
+    if (i0 == -1) i0 = C - 1;
+    else if ((unsigned)i0 >= (unsigned)C) i0 = ((i0 % C) + C) % C;
+    i1 = i0 + 1 == C ? 0 : i0 + 1;
+}
+
+__device__ __forceinline__ float material_channel(uint2 w, int k) { return (float)(((k < 4 ? w.x : w.y) >> (8 * (k & 3))) & 0xffu); }
+
+// a + (b - a) * f per channel k of two texels
+__device__ __forceinline__ float material_lerp(uint2 a, uint2 b, int k, float f)
+{
+    const float x = material_channel(a, k), y = material_channel(b, k);
+    return x + (y - x) * f;
+}
+
+// the 8 weights of a vertex at block-local position p of block b (an index into the dirty list)
+__device__ __forceinline__ uint2 material_weights(const MaterialVertexArgs &a, uint32_t b, float p0, float p1, float p2)
+{
+    if (b >= a.n_blocks) b = a.n_blocks - 1;  // never taken for a result of the library; keeps a foreign record inside the list
+    int bx, by, bz;
+    if (a.list) {
+        bx = a.list[3 * (size_t)b], by = a.list[3 * (size_t)b + 1], bz = a.list[3 * (size_t)b + 2];
+    } else {
+        const unsigned q = a.d_nbx.quot(b);
+        bx = (int)(b - q * (unsigned)a.nbx);
+        bz = (int)a.d_nby.quot(q);
+        by = (int)(q - (unsigned)bz * (unsigned)a.nby);
+    }
+    const float gx = (float)(8 * bx) + p0, gy = (float)(8 * by) + p1, gz = (float)(8 * bz) + p2;
+    int i0, i1, j0, j1, k0, k1;
+    float fx, fy, fz;
+    material_axis(gx, a.s[0], a.C, i0, i1, fx);
+    material_axis(gy, a.s[1], a.C, j0, j1, fy);
+    material_axis(gz, a.s[2], a.C, k0, k1, fz);
+    const int C = a.C;
+    const int r00 = C * (j0 + C * k0), r10 = C * (j1 + C * k0), r01 = C * (j0 + C * k1), r11 = C * (j1 + C * k1);
+    const uint2 *__restrict__ m = a.layer;
+    const uint2 m000 = m[r00 + i0], m100 = m[r00 + i1], m010 = m[r10 + i0], m110 = m[r10 + i1];
+    const uint2 m001 = m[r01 + i0], m101 = m[r01 + i1], m011 = m[r11 + i0], m111 = m[r11 + i1];
+    uint32_t out[2] = {0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float a00 = material_lerp(m000, m100, k, fx), a10 = material_lerp(m010, m110, k, fx);
+        const float a01 = material_lerp(m001, m101, k, fx), a11 = material_lerp(m011, m111, k, fx);
+        const float b0 = a00 + (a10 - a00) * fy, b1 = a01 + (a11 - a01) * fy;
+        const float q = b0 + (b1 - b0) * fz;
+        out[k >> 2] |= ((uint32_t)rintf(q) & 0xffu) << (8 * (k & 3));
+    }
+    return make_uint2(out[0], out[1]);
+}
+
+// `nd` consecutive dwords from src (16-byte aligned) into LDS: 16-byte pieces, the last one dword by dword where it is not whole
+__device__ __forceinline__ void material_load_tile(uint32_t *lds, const uint32_t *__restrict__ src, uint32_t nd)
+{
+    for (uint32_t q = threadIdx.x; 4 * q < nd; q += 256) {
+        if (4 * q + 4 <= nd) {
+            *reinterpret_cast<uint4 *>(lds + 4 * q) = *reinterpret_cast<const uint4 *>(src + 4 * q);
+        } else {
+            for (uint32_t d = 4 * q; d < nd; ++d) lds[d] = src[d];
+        }
+    }
+}
+
+// soup: tris = T records of 19 dwords (vtmc_triangle); out[3t + v] = the weights of corner v of triangle t
+__global__ __launch_bounds__(256) void material_soup_kernel(const uint32_t *__restrict__ tris, uint32_t n_tris, uint2 *__restrict__ out, MaterialVertexArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t rec[kMatTile * 19];
+    const uint32_t t0 = blockIdx.x * (uint32_t)kMatTile;
+    const uint32_t nt = n_tris - t0 < (uint32_t)kMatTile ? n_tris - t0 : (uint32_t)kMatTile;
+    material_load_tile(rec, tris + (size_t)t0 * 19, nt * 19);  // tile base: 256 * 76 bytes per tile, 16-byte aligned
+    __syncthreads();
+    for (uint32_t v = threadIdx.x; v < 3 * nt; v += 256) {
+        const uint32_t t = v / 3, c = v - 3 * t;
+        const uint32_t *r = rec + 19 * t;
+        const uint2 w = material_weights(a, r[18], __uint_as_float(r[3 * c]), __uint_as_float(r[3 * c + 1]), __uint_as_float(r[3 * c + 2]));
+        out[(size_t)t0 * 3 + v] = w;
+    }
+}
+
+// the largest b in [lo, hi] with off[b] <= v (off[lo] <= v holds): the block whose vertex range holds v, empty blocks skipped
+__device__ __forceinline__ uint32_t material_block_of(const uint32_t *__restrict__ off, uint32_t lo, uint32_t hi, uint32_t v)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (off[mid] <= v) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// indexed: verts = V records of 6 dwords (vtmc_vertex), voffsets = the n_blocks + 1 per-block vertex offsets; out[v] = the weights of
+// vertex v.  Two lanes find the blocks of the tile's first and last vertex; every lane then searches only between them.
+__global__ __launch_bounds__(256) void material_indexed_kernel(const uint32_t *__restrict__ verts, uint32_t n_verts, const uint32_t *__restrict__ voffsets,
+                                                               uint2 *__restrict__ out, MaterialVertexArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t rec[kMatTile * 6];
+    __shared__ uint32_t range[2];
+    const uint32_t v0 = blockIdx.x * (uint32_t)kMatTile;
+    const uint32_t nv = n_verts - v0 < (uint32_t)kMatTile ? n_verts - v0 : (uint32_t)kMatTile;
+    material_load_tile(rec, verts + (size_t)v0 * 6, nv * 6);  // tile base: 256 * 24 bytes per tile, 16-byte aligned
+    if (threadIdx.x < 2) range[threadIdx.x] = material_block_of(voffsets, 0u, a.n_blocks - 1, threadIdx.x ? v0 + nv - 1 : v0);
+    __syncthreads();
+    if (threadIdx.x < nv) {
+        const uint32_t v = v0 + threadIdx.x;
+        const uint32_t b = material_block_of(voffsets, range[0], range[1], v);
+        const uint32_t *r = rec + 6 * threadIdx.x;
+        out[v] = material_weights(a, b, __uint_as_float(r[0]), __uint_as_float(r[1]), __uint_as_float(r[2]));
+    }
+}
+
+// every texel (255,0,0,0, 0,0,0,0): TerrainSample starts with _matComponents[0] = 1
+__global__ __launch_bounds__(256) void material_fill_kernel(uint2 *__restrict__ layer, uint32_t n)
+{
+    const uint32_t id = blockIdx.x * 256u + threadIdx.x;
+    if (id < n) layer[id] = make_uint2(255u, 0u);
+}
+
+__device__ __forceinline__ uint32_t material_quantise(float c)
+{
+    c = c < 0.0f ? 0.0f : (c > 1.0f ? 1.0f : c);
+    return (uint32_t)rintf(c * 255.0f);
+}
+
+// set_control_map: the Color of every texel into the four bytes of its group (half 0: group 1, half 1: group 2), the other four kept
+__global__ __launch_bounds__(256) void material_quantise_kernel(uint32_t *__restrict__ layer, const float4 *__restrict__ img, uint32_t n, int half)
+{
+    const uint32_t id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= n) return;
+    const float4 c = img[id];
+    layer[2 * (size_t)id + half] = material_quantise(c.x) | material_quantise(c.y) << 8 | material_quantise(c.z) << 16 | material_quantise(c.w) << 24;
+}
+
+// paint: a thread per texel of the box, every stroke of the call in order; the strokes are read at a wave-uniform index
+__global__ __launch_bounds__(256) void material_paint_kernel(uint2 *__restrict__ layer, const vtmc_material_stroke *__restrict__ strokes, MaterialPaintArgs a)
+{
+    const uint32_t id = blockIdx.x * 256u + threadIdx.x;
+    if (id >= (uint32_t)a.n[0] * (uint32_t)a.n[1] * (uint32_t)a.n[2]) return;
+    const uint32_t row = id / (uint32_t)a.n[0];
+    const int i = a.lo[0] + (int)(id - row * (uint32_t)a.n[0]);
+    const int j = a.lo[1] + (int)(row % (uint32_t)a.n[1]), k = a.lo[2] + (int)(row / (uint32_t)a.n[1]);
+    const float px = ((float)i + 0.5f) * a.ts[0] + a.origin[0];
+    const float py = ((float)j + 0.5f) * a.ts[1] + a.origin[1];
+    const float pz = ((float)k + 0.5f) * a.ts[2] + a.origin[2];
+    uint2 *texel = layer + (i + a.C * (j + a.C * k));
+    const uint2 old = *texel;
+    float v[8];
+#pragma unroll
+    for (int ch = 0; ch < 8; ++ch) v[ch] = material_channel(old, ch);
+    bool touched = false;
+    for (int s = 0; s < a.n_strokes; ++s) {
+        const vtmc_material_stroke st = strokes[s];
+        const float dx = px - st.center[0], dy = py - st.center[1], dz = pz - st.center[2];
+        const float d = sqrtf((dx * dx + dy * dy) + dz * dz);
+        float t = 1.0f - d / st.radius;
+        t = t + t;
+        t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+        const float w = st.strength * t;
+        if (w == 0.0f) continue;
+        touched = true;
+#pragma unroll
+        for (int ch = 0; ch < 8; ++ch) {
+            const float T = ch == st.channel ? 255.0f : 0.0f;
+            v[ch] = rintf(v[ch] + (T - v[ch]) * w);  // the byte the stroke leaves, as the float the next stroke reads
+        }
+    }
+    if (!touched) return;
+    uint32_t out[2] = {0u, 0u};
+#pragma unroll
+    for (int ch = 0; ch < 8; ++ch) out[ch >> 2] |= ((uint32_t)v[ch] & 0xffu) << (8 * (ch & 3));
+    *texel = make_uint2(out[0], out[1]);
+}
+
+void material_drop(vtmc_ctx *ctx)
+{
+    ctx->mat_c = 0;
+    ctx->mat_vertices = 0;
+    ctx->mat_weights_epoch = 0;
+    release(ctx->material);
+    release(ctx->mat_image);
+}
+
+static size_t material_texels(const vtmc_ctx *ctx) { return (size_t)ctx->mat_c * ctx->mat_c * ctx->mat_c; }
+
+static int need_layer(vtmc_ctx *ctx, const char *who)
+{
+    if (!ctx->mat_c) return fail(ctx, VTMC_ERR_NO_RESULT, "%s before material_init", who);
+    return VTMC_OK;
+}
+
+static void terrain_cells(const vtmc_ctx *ctx, int cells[3])
+{
+    cells[0] = ctx->tshape.dim_x - 2, cells[1] = ctx->tshape.dim_y - 2, cells[2] = ctx->tshape.dim_z - 2;
+}
+
+static bool weights_current(const vtmc_ctx *ctx) { return ctx->mat_c && ctx->has_result && ctx->mat_weights_epoch == ctx->result_epoch; }
+
+}  // namespace vtmc
+
+using namespace vtmc;
+
+extern "C" {
+
+int32_t vtmc_material_init(vtmc_ctx *ctx, int32_t fineness)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "material_init before terrain_init");
+    const int C = material_size(fineness);
+    if (!C) return fail(ctx, VTMC_ERR_INVALID_ARG, "fineness %d not in %d..%d", fineness, kMaterialMinFineness, kMaterialMaxFineness);
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    material_drop(ctx);
+    const size_t n = (size_t)C * C * C;
+    if (int rc = ensure(ctx, ctx->material, n * VTMC_MATERIAL_CHANNELS)) return rc;
+    launch_begin();
+    hipLaunchKernelGGL(material_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (uint2 *)ctx->material.p, (uint32_t)n);
+    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->mat_c = C;
+    return VTMC_OK;
+}
+
+int32_t vtmc_material_set_control_map(vtmc_ctx *ctx, const float *rgba, int32_t group)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (int rc = need_layer(ctx, "material_set_control_map")) return rc;
+    if (!rgba) return fail(ctx, VTMC_ERR_INVALID_ARG, "rgba is null");
+    if (group != 1 && group != 2) return fail(ctx, VTMC_ERR_INVALID_ARG, "invalid group %d: expected 1 or 2", group);  // VoxelTerrain.cs:188-189
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = material_texels(ctx), bytes = n * 4 * sizeof(float);
+    // the image goes through the pinned stage, checked on the way in; without one, from where it lies
+    float *stage = pinned_stage(ctx, bytes);
+    const long long bad = stage ? material_copy_checked(stage, rgba, n * 4) : material_first_nan(rgba, n * 4);
+    if (bad >= 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "set_control_map: channel %lld of texel %lld is NaN", bad % 4, bad / 4);
+    if (int rc = ensure(ctx, ctx->mat_image, bytes)) return rc;
+    VTMC_HIP(ctx, hipMemcpyAsync(ctx->mat_image.p, stage ? stage : rgba, bytes, hipMemcpyHostToDevice, ctx->stream));
+    launch_begin();
+    hipLaunchKernelGGL(material_quantise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (uint32_t *)ctx->material.p,
+                       (const float4 *)ctx->mat_image.p, (uint32_t)n, group - 1);
+    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the stage and rgba are free again
+    return VTMC_OK;
+}
+
+int32_t vtmc_material_write(vtmc_ctx *ctx, const uint8_t *src)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (int rc = need_layer(ctx, "material_write")) return rc;
+    if (!src) return fail(ctx, VTMC_ERR_INVALID_ARG, "src is null");
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VTMC_HIP(ctx, hipMemcpy(ctx->material.p, src, material_texels(ctx) * VTMC_MATERIAL_CHANNELS, hipMemcpyHostToDevice));
+    return VTMC_OK;
+}
+
+int32_t vtmc_material_read(vtmc_ctx *ctx, uint8_t *dst, int32_t *size)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (int rc = need_layer(ctx, "material_read")) return rc;
+    if (size) *size = ctx->mat_c;
+    if (!dst) return VTMC_OK;  // size query
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VTMC_HIP(ctx, hipMemcpy(dst, ctx->material.p, material_texels(ctx) * VTMC_MATERIAL_CHANNELS, hipMemcpyDeviceToHost));
+    return VTMC_OK;
+}
+
+int32_t vtmc_material_paint(vtmc_ctx *ctx, const vtmc_material_stroke *strokes, int32_t n_strokes)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (int rc = need_layer(ctx, "material_paint")) return rc;
+    if (n_strokes < 0 || n_strokes > VTMC_MATERIAL_MAX_STROKES)
+        return fail(ctx, VTMC_ERR_INVALID_ARG, "n_strokes %d not in 0..%d", n_strokes, VTMC_MATERIAL_MAX_STROKES);
+    if (n_strokes > 0 && !strokes) return fail(ctx, VTMC_ERR_INVALID_ARG, "strokes is null");
+    const char *fault = nullptr;
+    const int32_t bad = material_check_strokes(strokes, n_strokes, &fault);
+    if (bad >= 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "stroke %d: %s", bad, fault);
+    if (n_strokes == 0) return VTMC_OK;
+    MaterialPaintArgs a{};
+    int cells[3];
+    terrain_cells(ctx, cells);
+    a.C = ctx->mat_c;
+    material_texel_size(cells, ctx->tshape.scale, a.C, a.ts);
+    for (int k = 0; k < 3; ++k) a.origin[k] = ctx->tshape.origin[k];
+    const MaterialBox box = material_paint_box(strokes, n_strokes, a.ts, a.origin, a.C);
+    const size_t n = (size_t)box.n[0] * box.n[1] * box.n[2];
+    if (n == 0) return VTMC_OK;  // no stroke reaches a texel
+    for (int k = 0; k < 3; ++k) a.lo[k] = box.lo[k], a.n[k] = box.n[k];
+    a.n_strokes = n_strokes;
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure(ctx, ctx->mat_strokes, sizeof(vtmc_material_stroke) * VTMC_MATERIAL_MAX_STROKES)) return rc;
+    VTMC_HIP(ctx, hipMemcpyAsync(ctx->mat_strokes.p, strokes, sizeof(vtmc_material_stroke) * (size_t)n_strokes, hipMemcpyHostToDevice, ctx->stream));
+    launch_begin();
+    hipLaunchKernelGGL(material_paint_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (uint2 *)ctx->material.p,
+                       (const vtmc_material_stroke *)ctx->mat_strokes.p, a);
+    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // strokes is borrowed for the call; the next call may overwrite mat_strokes
+    return VTMC_OK;
+}
+
+int32_t vtmc_material_vertices(vtmc_ctx *ctx, int64_t *n_vertices)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (int rc = need_layer(ctx, "material_vertices")) return rc;
+    if (!ctx->has_result) return fail(ctx, VTMC_ERR_NO_RESULT, "material_vertices before any extract");
+    if (!ctx->has_terrain || ctx->terrain_result_epoch != ctx->result_epoch)
+        return fail(ctx, VTMC_ERR_NO_RESULT, "material_vertices: the last result did not come from the resident terrain");
+    const int64_t n = ctx->last_indexed ? ctx->last_verts : 3 * ctx->last_tris;
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    if (n > 0) {
+        if (int rc = ensure(ctx, ctx->mat_weights, (size_t)n * VTMC_MATERIAL_CHANNELS)) return rc;
+        MaterialVertexArgs a{};
+        int cells[3];
+        terrain_cells(ctx, cells);
+        a.layer = (const uint2 *)ctx->material.p;
+        a.C = ctx->mat_c;
+        material_vertex_scale(cells, a.C, a.s);
+        const BlockSpace &sp = ctx->last_space;
+        a.list = sp.list;
+        a.n_blocks = (uint32_t)ctx->last_blocks;
+        a.nbx = sp.nbx, a.nby = sp.nby;
+        a.d_nbx = sp.d_nbx, a.d_nby = sp.d_nby;
+        launch_begin();
+        if (ctx->last_indexed) {
+            const uint32_t V = (uint32_t)ctx->last_verts;
+            hipLaunchKernelGGL(material_indexed_kernel, dim3((V + kMatTile - 1) / kMatTile), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->verts.p, V,
+                               (const uint32_t *)ctx->voffsets.p, (uint2 *)ctx->mat_weights.p, a);
+        } else {
+            const uint32_t T = (uint32_t)ctx->last_tris;
+            hipLaunchKernelGGL(material_soup_kernel, dim3((T + kMatTile - 1) / kMatTile), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->tris.p, T,
+                               (uint2 *)ctx->mat_weights.p, a);
+        }
+        VTMC_HIP(ctx, launch_end());
+        VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    ctx->mat_vertices = n;
+    ctx->mat_weights_epoch = ctx->result_epoch;
+    if (n_vertices) *n_vertices = n;
+    return VTMC_OK;
+}
+
+int32_t vtmc_material_read_vertices(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity_vertices)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (!weights_current(ctx)) return fail(ctx, VTMC_ERR_NO_RESULT, "material_read_vertices: no vertex weights of the current result (call vtmc_material_vertices)");
+    if (capacity_vertices < ctx->mat_vertices)
+        return fail(ctx, VTMC_ERR_INVALID_ARG, "capacity %lld < %lld vertices", (long long)capacity_vertices, (long long)ctx->mat_vertices);
+    if (ctx->mat_vertices == 0) return VTMC_OK;
+    if (!dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "dst is null");
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    VTMC_HIP(ctx, hipMemcpy(dst, ctx->mat_weights.p, (size_t)ctx->mat_vertices * VTMC_MATERIAL_CHANNELS, hipMemcpyDeviceToHost));
+    return VTMC_OK;
+}
+
+int32_t vtmc_material_device_results(vtmc_ctx *ctx, const uint8_t **d_weights, int64_t *n_vertices)
+{
+    if (!ctx) return VTMC_ERR_INVALID_ARG;
+    if (!weights_current(ctx)) return fail(ctx, VTMC_ERR_NO_RESULT, "material_device_results: no vertex weights of the current result (call vtmc_material_vertices)");
+    if (d_weights) *d_weights = (const uint8_t *)ctx->mat_weights.p;
+    if (n_vertices) *n_vertices = ctx->mat_vertices;
+    return VTMC_OK;
+}
+
+}  // extern "C"

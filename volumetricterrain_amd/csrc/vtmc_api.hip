@@ -298,6 +298,7 @@ int extract_finish(vtmc_ctx *ctx, int64_t *tri_count)
     }
     ctx->pending.active = false;
     ctx->has_result = true;
+    ++ctx->result_epoch;
     ctx->last_space = pe.sp;
     ctx->last_blocks = pe.sp.n_blocks;
     ctx->last_volumes = pe.n_volumes;
@@ -388,6 +389,8 @@ int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, int32_t *tr
     if (tri_count) *tri_count = (int32_t)T;
     return VTMC_OK;
 }
+
+float *pinned_stage(vtmc_ctx *ctx, size_t bytes) { return stage_buffer(ctx, bytes); }
 
 int check_dims(vtmc_ctx *ctx, int nx, int ny, int nz)
 {

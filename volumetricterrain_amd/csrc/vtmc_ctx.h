@@ -1,5 +1,5 @@
 // vtmc_ctx.h -- the context object behind include/vtmc.h and the small host helpers every translation unit of the C-ABI layer shares
-// (context.hip, vtmc_api.hip, terrain.hip, terrain_stamp.hip, stamp_mesh.hip, terrain_path.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
+// (context.hip, vtmc_api.hip, terrain.hip, terrain_stamp.hip, stamp_mesh.hip, terrain_path.hip, terrain_material.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
 #ifndef VTMC_CTX_H
 #define VTMC_CTX_H
 #include "../../include/vtmc.h"
@@ -119,6 +119,8 @@ struct vtmc_ctx {
     int last_blocks = 0;
     int last_volumes = 0;
     int64_t last_tris = 0;
+    uint64_t result_epoch = 0;          // counts the finished extracts: names the result the context holds
+    uint64_t terrain_result_epoch = 0;  // the result_epoch of the last extract of the resident terrain's dirty set (terrain.hip)
     vtmc::Tuning tune;
     // device-resident terrain (vtmc_terrain_*)
     VtmcDevBuf terrain, heightmap;
@@ -142,6 +144,12 @@ struct vtmc_ctx {
     // terrain_path.hip: the segment records of the VTMC_MOD_PATH modifier being applied, grow-only; written only after the stream has
     // drained, since an earlier path modifier of the same queue may still be reading it
     VtmcDevBuf path;
+    // terrain_material.hip: the material layer (mat_c^3 texels of 8 bytes; mat_c = 0: none), the float image of a set_control_map on its way
+    // to the quantising kernel, the strokes of a paint call, and the vertex weights (8 bytes per vertex) of the result mat_weights_epoch names
+    VtmcDevBuf material, mat_image, mat_strokes, mat_weights;
+    int mat_c = 0;
+    int64_t mat_vertices = 0;
+    uint64_t mat_weights_epoch = 0;
     // raycast.hip, spherequery.hip: the queries and hits of vtmc_terrain_raycast / _spherecast / _closest_point (device, then their pinned staging)
     VtmcDevBuf rays;
     VtmcPinnedBuf<unsigned char> h_rays;
@@ -189,6 +197,8 @@ hipError_t take_stream(int device, bool own_queue, int n_cus, hipStream_t *out);
 void comm_release(vtmc_ctx *ctx);  // comm.hip: called by vtmc_destroy
 int check_dims(vtmc_ctx *ctx, int nx, int ny, int nz);
 BlockSpace dense_space(const float *d_base, int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz, int n_volumes, int64_t sv);
+float *pinned_stage(vtmc_ctx *ctx, size_t bytes);   // the pinned stage of host-gathered data (vtmc_api.hip), grown to `bytes`; null: none to be had, go pageable
+void material_drop(vtmc_ctx *ctx);   // terrain_material.hip: vtmc_terrain_init / _load drop the layer
 int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp);   // sp then walks the (bx,by,bz) list
 int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, int32_t *tri_count);   // queued on the context's stream and finished
 // terrain.hip, for terrain_io.hip

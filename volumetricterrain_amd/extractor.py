@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, MESH_TRUST_CLOSED, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from ._lib import COMM_ID_BYTES, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
 from .modifiers import mesh_stamp_args
 
 
@@ -387,6 +387,71 @@ class Extractor:
 
     def stamp_destroy(self, stamp_id):
         self._check(self._L.vtmc_stamp_destroy(self._h, int(stamp_id)))
+
+    # -- material layer: VoxelTerrain.SetControlMap's splat volumes in HBM, paint, and per-vertex weights -------------
+    def material_init(self, fineness):
+        """The control volume of 16 * fineness texels per axis (fineness 1..8) over the resident terrain, every texel (255,0,0,0, 0,0,0,0).
+        Returns the size C.  terrain_init / terrain_load drop it."""
+        self._check(self._L.vtmc_material_init(self._h, int(fineness)))
+        return self.material_size()
+
+    def material_size(self):
+        c = ctypes.c_int32()
+        self._check(self._L.vtmc_material_read(self._h, None, ctypes.byref(c)))
+        return c.value
+
+    def set_control_map(self, colors, group):
+        """VoxelTerrain.SetControlMap: `colors` holds C^3 RGBA floats in the order of the reference's Color[] (x fastest; a (C, C, C, 4)
+        array indexed [k, j, i] is one), quantised on the device into the four bytes of `group` (1 or 2)."""
+        c = self.material_size()
+        colors = np.ascontiguousarray(colors, np.float32)
+        if colors.size != c * c * c * 4:
+            raise ValueError("invalid data size: expected %d x 4 floats" % (c * c * c))   # VoxelTerrain.cs:194-195
+        self._check(self._L.vtmc_material_set_control_map(self._h, _ptr(colors), int(group)))
+
+    def material_read(self):
+        """The layer as a (C, C, C, 8) uint8 array indexed [k, j, i, channel]."""
+        c = self.material_size()
+        out = np.empty((c, c, c, MATERIAL_CHANNELS), np.uint8)
+        self._check(self._L.vtmc_material_read(self._h, _ptr(out), None))
+        return out
+
+    def material_write(self, a):
+        """The inverse of material_read."""
+        c = self.material_size()
+        a = np.ascontiguousarray(a, np.uint8)
+        if a.shape != (c, c, c, MATERIAL_CHANNELS):
+            raise ValueError("layer shape %r is not (%d, %d, %d, %d)" % (a.shape, c, c, c, MATERIAL_CHANNELS))
+        self._check(self._L.vtmc_material_write(self._h, _ptr(a)))
+
+    def paint(self, strokes):
+        """Applies MaterialStroke objects (or vtmc_material_stroke structs) in order, in one pass over the texels they reach."""
+        strokes = [s.to_struct() if hasattr(s, "to_struct") else s for s in strokes]
+        arr = (_lib.MaterialStroke * max(len(strokes), 1))()
+        for i, s in enumerate(strokes):
+            ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(s), ctypes.sizeof(_lib.MaterialStroke))
+        self._check(self._L.vtmc_material_paint(self._h, ctypes.cast(arr, ctypes.c_void_p), len(strokes)))
+
+    def material_vertices(self):
+        """Computes the material weights of every vertex of the result the context holds (from terrain_update / undo / redo / load) and
+        leaves them on the device.  Returns their number: 3 T (soup) or V (indexed)."""
+        n = ctypes.c_int64()
+        self._check(self._L.vtmc_material_vertices(self._h, ctypes.byref(n)))
+        return n.value
+
+    def vertex_materials(self):
+        """material_vertices, then the weights as an (n, 8) uint8 array: row 3 t + v for corner v of soup triangle t, or one row per
+        vtmc_vertex of the indexed mesh."""
+        n = self.material_vertices()
+        out = np.empty((n, MATERIAL_CHANNELS), np.uint8)
+        self._check(self._L.vtmc_material_read_vertices(self._h, _ptr(out), n))
+        return out
+
+    def material_device_results(self):
+        """(device address of the vertex weights, their number) of the last material_vertices."""
+        p, n = ctypes.c_void_p(), ctypes.c_int64()
+        self._check(self._L.vtmc_material_device_results(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
 
     # -- ray picking: Physics.Raycast of the interactive edit (SceneManager.cs:114-131) on the device ---------------
     def terrain_raycast(self, origins, directions, max_distance=float("inf"), two_sided=False):

@@ -8,7 +8,8 @@ order of the C# expressions.
 """
 import numpy as np
 
-from ._lib import (MESH_MAX_TRIANGLES, MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP,
+from . import _lib
+from ._lib import (MATERIAL_CHANNELS, MESH_MAX_TRIANGLES, MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP,
                    PATH_MAX_SEGMENTS, STAMP_MAX_DIM, STAMP_MAX_SAMPLES, STAMP_MIN_DIM, Modifier)
 
 _f = np.float32
@@ -200,6 +201,28 @@ class FlattenModifier(SmoothModifier):
 
     def params(self):
         return [*self._center, self._radius, self._strength, *self._normal]
+
+
+# -- material paint (include/vtmc.h vtmc_material_paint) -----------------------------------------------------------------------------------
+class MaterialStroke:
+    """One paint stroke on the material layer (Extractor.paint): every texel within `radius` of `center` (world space) is blended towards
+    the one-hot of `channel` (0..3: group 1's r, g, b, a; 4..7: group 2's) by w = strength * clamp01(2 (1 - d / radius)), the sculpt
+    brushes' falloff.  No TerrainModifier: paint is not queued with the density edits, not journaled and extracts nothing."""
+
+    def __init__(self, center, radius, channel, strength=1.0):
+        with np.errstate(over="ignore"):
+            self._center = np.asarray(center, np.float64).astype(_f).reshape(3)
+            self._radius, self._strength = _f(radius), _f(strength)
+        _check_brush(self._center, self._radius, self._strength)
+        if int(channel) != channel or not 0 <= channel < MATERIAL_CHANNELS:
+            raise ValueError("stroke channel must be an integer in 0..%d" % (MATERIAL_CHANNELS - 1))
+        self._channel = int(channel)
+
+    def to_struct(self):
+        s = _lib.MaterialStroke()
+        s.center[:] = tuple(float(x) for x in self._center)
+        s.radius, s.strength, s.channel = float(self._radius), float(self._strength), self._channel
+        return s
 
 
 # -- noise (include/vtmc.h VTMC_MOD_NOISE) -----------------------------------------------------------------------------------------------
