@@ -683,6 +683,65 @@ int32_t vtmc_material_read_vertices(vtmc_ctx *ctx, uint8_t *dst, int64_t capacit
 int32_t vtmc_material_device_results(vtmc_ctx *ctx, const uint8_t **d_weights, int64_t *n_vertices);
 
 /* ------------------------------------------------------------------------------------------
+ * Ambient occlusion -- the second per-vertex attribute of a terrain extract (not in the reference): one byte per vertex, computed on the
+ * device from the resident density grid, in either output mode.  255 = fully open, 0 = fully occluded at strength 1.  It is THE LIBRARY'S
+ * OWN measure, a clamped-density march along 26 lattice directions; it is no ray-traced visibility integral and parity with any
+ * renderer's AO is not claimed.  Density above 0 is solid; the CSG clamp saturates the interior to [1, 2), hence the clamp to 1.  Its
+ * life cycle is that of the vertex material weights: computed on demand for the result the context holds, library-owned, stale after the
+ * next extract.  Derived data: neither saved with the terrain nor journaled.
+ *
+ * All arithmetic is FP32, one IEEE operation per step in the order written (library built with -ffp-contract=off); / and sqrtf are
+ * correctly rounded, rintf rounds ties to even.
+ *
+ * Host, once per call, S = steps:   Rg = radius / voxel_scale;   for s = 1..S:  h[s] = Rg * ((float)s / (float)S);
+ *   fall[s] = 1.0f - (float)(s - 1) / (float)S.
+ * Directions: the 26 lattice directions (i, j, k) in {-1, 0, 1}^3 without (0, 0, 0), numbered m = 0..25 in ascending order of
+ *   (i+1) + 3*(j+1) + 9*(k+1);  d_m = ((float)i * len, (float)j * len, (float)k * len), len by the number of non-zero components:
+ *   one 1.0f, two 0.70710678f, three 0.57735027f (the literals are part of the rule).
+ * Per vertex: position p and normal n as the record holds them (soup corner 3t + v, or vtmc_vertex v; the normal is the un-normalised
+ *   gradient normal the extract wrote), block (bx, by, bz) found as vtmc_material_vertices finds it.
+ *     gx = (float)(8*bx) + p.x;  gy, gz alike                            (grid sample coordinates: sample i sits at i)
+ *     l = sqrtf((n.x*n.x + n.y*n.y) + n.z*n.z)
+ *     if (!(l > 0) || !(l < INFINITY)):  out = 255                       (the NaN normal of a flat gradient: unoccluded)
+ *     else  N = n / l per component;  num = 0;  den = 0;  for m = 0..25 in order:
+ *       c = (N.x*d.x + N.y*d.y) + N.z*d.z;   if (!(c > 0)) skip this direction
+ *       o = 0;  for s = 1..S:
+ *         qx = gx + d.x*h[s];  qy, qz alike;   r = fetch(q);   r = r > 0 ? (r < 1 ? r : 1) : 0      (a NaN sample occludes nothing)
+ *         r = r * fall[s];   if (r > o) o = r
+ *       num = num + c*o;   den = den + c
+ *     a = 1.0f - strength * (num / den);   a = a > 0 ? (a < 1 ? a : 1) : 0;   out = (uint8)rintf(a * 255.0f)
+ *   den > 0 always holds: some lattice direction makes less than 55 degrees with any unit vector.
+ * fetch(q) reads the (W+2, E+2, H+2) grid with clamp-to-edge.  Per axis with n samples:
+ *     t = q < 0 ? 0 : (q > (float)(n-1) ? (float)(n-1) : q);   i0 = (int)floorf(t);   if (i0 > n-2) i0 = n-2;   f = t - (float)i0
+ *   and the eight samples are combined in the material rule's lerp form a + (b - a)*f, along x, then y, then z.
+ * The grid is read as it is at the time of the call.  The rule is pointwise: the result depends neither on the launch shape nor on how
+ * the kernel stages samples.
+ *
+ * vtmc_ao_vertices  computes the byte of every vertex of the result the context holds into a library-owned, grow-only buffer;
+ *   *n_vertices (may be NULL) receives n.  Soup: vertex 3*t + v, n = 3*T.  Indexed: n = V.  VTMC_ERR_NO_RESULT without a terrain, without
+ *   a result, or when the result did not come from the resident terrain.  T = 0 is success with 0 vertices.  VTMC_ERR_INVALID_ARG, with
+ *   nothing computed and the previous values kept: null ctx or params; radius not finite or <= 0; radius / voxel_scale >
+ *   VTMC_AO_MAX_RADIUS_CELLS; strength not finite or outside [0, 1]; steps outside 1..VTMC_AO_MAX_STEPS; flags != 0.
+ *   The values belong to one result: after any later extract vtmc_ao_read_vertices / _device_results answer VTMC_ERR_NO_RESULT until
+ *   vtmc_ao_vertices runs again.  The material layer plays no part: neither call needs or disturbs the other's values.
+ * vtmc_ao_read_vertices  copies the n bytes; a capacity below n is VTMC_ERR_INVALID_ARG.
+ * vtmc_ao_device_results  the device pointer of the same (valid until the next vtmc_ao_vertices / destroy).
+ * ------------------------------------------------------------------------------------------ */
+#define VTMC_AO_MAX_STEPS 8
+#define VTMC_AO_MAX_RADIUS_CELLS 6      /* radius / voxel_scale above this: VTMC_ERR_INVALID_ARG */
+
+typedef struct vtmc_ao_params {
+    float radius;      /* world units, > 0 */
+    float strength;    /* [0, 1] */
+    int32_t steps;     /* 1..VTMC_AO_MAX_STEPS */
+    uint32_t flags;    /* reserved, must be 0 */
+} vtmc_ao_params;      /* 16 bytes */
+
+int32_t vtmc_ao_vertices(vtmc_ctx *ctx, const vtmc_ao_params *params, int64_t *n_vertices);
+int32_t vtmc_ao_read_vertices(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity_vertices);
+int32_t vtmc_ao_device_results(vtmc_ctx *ctx, const uint8_t **d_ao, int64_t *n_vertices);
+
+/* ------------------------------------------------------------------------------------------
  * Ray picking -- replaces the Physics.Raycast of the interactive edit (SceneManager.cs:114-131)
  * against the MeshColliders that BatchUpdate cooks from the extracted mesh (VoxelTerrain.cs:448-465),
  * without any mesh on the host.  The surface is the triangle set vtmc_extract_grid emits for every

@@ -56,6 +56,7 @@ SYMBOLS = [
     "vtmc_stamp_from_mesh",
     "vtmc_material_init", "vtmc_material_set_control_map", "vtmc_material_write", "vtmc_material_read", "vtmc_material_paint",
     "vtmc_material_vertices", "vtmc_material_read_vertices", "vtmc_material_device_results",
+    "vtmc_ao_vertices", "vtmc_ao_read_vertices", "vtmc_ao_device_results",
 ]
 COMM_ID_BYTES = 128
 
@@ -67,6 +68,7 @@ MESH_MAX_TRIANGLES, MESH_BAND, MESH_TRUST_CLOSED = 1 << 20, 3.0, 1   # vtmc_stam
 MOD_PATH = 10                     # union of tapered capsules over a segment soup: rivers, tunnels, roads in one pass
 PATH_CHUNK, PATH_MAX_SEGMENTS = 256, 65536   # csrc/terrain_path.h: segments a workgroup prunes at a time; the most a modifier may hold
 MATERIAL_CHANNELS, MATERIAL_MAX_STROKES = 8, 4096   # the material layer: bytes per texel and per vertex; the most strokes of one paint call
+AO_MAX_STEPS, AO_MAX_RADIUS_CELLS = 8, 6   # vtmc_ao_vertices: the most steps of a march; the largest radius in cells (radius / voxel_scale)
 MOD_NOISE = 8                     # fBm / billow / ridged noise (RidgedMultifractalModifier's device form); 6 and 7 are not defined
 
 
@@ -81,6 +83,11 @@ class Modifier(ctypes.Structure):
 class MaterialStroke(ctypes.Structure):
     """vtmc_material_stroke: one paint stroke on the material layer, centre in world space."""
     _fields_ = [("center", ctypes.c_float * 3), ("radius", ctypes.c_float), ("strength", ctypes.c_float), ("channel", ctypes.c_int32)]
+
+
+class AoParams(ctypes.Structure):
+    """vtmc_ao_params: radius in world units, strength in [0, 1], steps 1..AO_MAX_STEPS, flags 0."""
+    _fields_ = [("radius", ctypes.c_float), ("strength", ctypes.c_float), ("steps", ctypes.c_int32), ("flags", ctypes.c_uint32)]
 
 
 class VolumeBatch(ctypes.Structure):
@@ -209,6 +216,12 @@ def load(path=None):
         L.vtmc_material_vertices.argtypes = [vp, P(i64)]
         L.vtmc_material_read_vertices.argtypes = [vp, vp, i64]
         L.vtmc_material_device_results.argtypes = [vp, P(vp), P(i64)]
+    if not explicit or hasattr(L, "vtmc_ao_vertices"):
+        L.vtmc_ao_vertices.argtypes = [vp, P(AoParams), P(i64)]
+        L.vtmc_ao_read_vertices.argtypes = [vp, vp, i64]
+        L.vtmc_ao_device_results.argtypes = [vp, P(vp), P(i64)]
+        L.vtmc_debug_ao_routes.argtypes = [vp, P(u32 * 2), i32]   # not in the header: the route counters of the last vtmc_ao_vertices
+        L.vtmc_debug_ao_routes.restype = i32
     L.vtmc_comm_unique_id.argtypes = [vp]
     L.vtmc_comm_init_rank.argtypes = [vp, vp, i32, i32]
     L.vtmc_comm_destroy.argtypes = [vp]

@@ -11,6 +11,7 @@
 // most 128^3 x 8 B = 16 MB, read-shared by every wave, and lives in L2 and the Infinity Cache.  Traffic that must reach HBM:
 // 76 T read + 24 T written (soup), 24 V + 8 V (indexed).
 #include "terrain_material.h"
+#include "record_tile.h"
 #include "vtmc_ctx.h"
 #include <cmath>
 
@@ -93,25 +94,13 @@ __device__ __forceinline__ uint2 material_weights(const MaterialVertexArgs &a, u
     return make_uint2(out[0], out[1]);
 }
 
-// `nd` consecutive dwords from src (16-byte aligned) into LDS: 16-byte pieces, the last one dword by dword where it is not whole
-__device__ __forceinline__ void material_load_tile(uint32_t *lds, const uint32_t *__restrict__ src, uint32_t nd)
-{
-    for (uint32_t q = threadIdx.x; 4 * q < nd; q += 256) {
-        if (4 * q + 4 <= nd) {
-            *reinterpret_cast<uint4 *>(lds + 4 * q) = *reinterpret_cast<const uint4 *>(src + 4 * q);
-        } else {
-            for (uint32_t d = 4 * q; d < nd; ++d) lds[d] = src[d];
-        }
-    }
-}
-
 // soup: tris = T records of 19 dwords (vtmc_triangle); out[3t + v] = the weights of corner v of triangle t
 __global__ __launch_bounds__(256) void material_soup_kernel(const uint32_t *__restrict__ tris, uint32_t n_tris, uint2 *__restrict__ out, MaterialVertexArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint32_t rec[kMatTile * 19];
     const uint32_t t0 = blockIdx.x * (uint32_t)kMatTile;
     const uint32_t nt = n_tris - t0 < (uint32_t)kMatTile ? n_tris - t0 : (uint32_t)kMatTile;
-    material_load_tile(rec, tris + (size_t)t0 * 19, nt * 19);  // tile base: 256 * 76 bytes per tile, 16-byte aligned
+    load_record_tile(rec, tris + (size_t)t0 * 19, nt * 19);  // tile base: 256 * 76 bytes per tile, 16-byte aligned
     __syncthreads();
     for (uint32_t v = threadIdx.x; v < 3 * nt; v += 256) {
         const uint32_t t = v / 3, c = v - 3 * t;
@@ -141,7 +130,7 @@ __global__ __launch_bounds__(256) void material_indexed_kernel(const uint32_t *_
     __shared__ uint32_t range[2];
     const uint32_t v0 = blockIdx.x * (uint32_t)kMatTile;
     const uint32_t nv = n_verts - v0 < (uint32_t)kMatTile ? n_verts - v0 : (uint32_t)kMatTile;
-    material_load_tile(rec, verts + (size_t)v0 * 6, nv * 6);  // tile base: 256 * 24 bytes per tile, 16-byte aligned
+    load_record_tile(rec, verts + (size_t)v0 * 6, nv * 6);  // tile base: 256 * 24 bytes per tile, 16-byte aligned
     if (threadIdx.x < 2) range[threadIdx.x] = material_block_of(voffsets, 0u, a.n_blocks - 1, threadIdx.x ? v0 + nv - 1 : v0);
     __syncthreads();
     if (threadIdx.x < nv) {

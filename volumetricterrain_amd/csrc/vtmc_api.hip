@@ -301,6 +301,7 @@ int extract_finish(vtmc_ctx *ctx, int64_t *tri_count)
     ++ctx->result_epoch;
     ctx->last_space = pe.sp;
     ctx->last_blocks = pe.sp.n_blocks;
+    ctx->last_active = pe.launched ? ctx->h_totals.p[1] : 0u;   // the scan's count of non-empty blocks: the entries of `active`
     ctx->last_volumes = pe.n_volumes;
     ctx->last_tris = T_found;
     ctx->last_verts = V_found;

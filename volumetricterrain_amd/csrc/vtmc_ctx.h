@@ -1,5 +1,5 @@
 // vtmc_ctx.h -- the context object behind include/vtmc.h and the small host helpers every translation unit of the C-ABI layer shares
-// (context.hip, vtmc_api.hip, terrain.hip, terrain_stamp.hip, stamp_mesh.hip, terrain_path.hip, terrain_material.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
+// (context.hip, vtmc_api.hip, terrain.hip, terrain_stamp.hip, stamp_mesh.hip, terrain_path.hip, terrain_material.hip, terrain_ao.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
 #ifndef VTMC_CTX_H
 #define VTMC_CTX_H
 #include "../../include/vtmc.h"
@@ -117,6 +117,7 @@ struct vtmc_ctx {
     bool has_result = false;
     vtmc::BlockSpace last_space{};
     int last_blocks = 0;
+    uint32_t last_active = 0;           // non-empty blocks of the last result: the BlockDesc records the scan left in `active`, in list order
     int last_volumes = 0;
     int64_t last_tris = 0;
     uint64_t result_epoch = 0;          // counts the finished extracts: names the result the context holds
@@ -150,6 +151,12 @@ struct vtmc_ctx {
     int mat_c = 0;
     int64_t mat_vertices = 0;
     uint64_t mat_weights_epoch = 0;
+    // terrain_ao.hip: the ambient-occlusion byte of every vertex of the result ao_epoch names, and the two route counters of the last call
+    // (workgroups that staged a tile, workgroups that fetched from global memory: vtmc_debug_ao_routes)
+    VtmcDevBuf ao_values, ao_stats;
+    int64_t ao_vertices = 0;
+    uint64_t ao_epoch = 0;
+    int32_t ao_direct_max = -1;         // vertices up to which a block takes the direct route; -1: the library's default
     // raycast.hip, spherequery.hip: the queries and hits of vtmc_terrain_raycast / _spherecast / _closest_point (device, then their pinned staging)
     VtmcDevBuf rays;
     VtmcPinnedBuf<unsigned char> h_rays;

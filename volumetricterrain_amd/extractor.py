@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import COMM_ID_BYTES, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
-from .modifiers import mesh_stamp_args
+from .modifiers import AmbientOcclusion, mesh_stamp_args
 
 
 def _ptr(a):
@@ -451,6 +451,29 @@ class Extractor:
         """(device address of the vertex weights, their number) of the last material_vertices."""
         p, n = ctypes.c_void_p(), ctypes.c_int64()
         self._check(self._L.vtmc_material_device_results(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    # -- ambient occlusion: one byte per vertex of a terrain extract, marched through the resident grid ----------------
+    def ao_vertices(self, params):
+        """Computes the occlusion byte of every vertex of the result the context holds (from terrain_update / undo / redo / load) for an
+        AmbientOcclusion (or a vtmc_ao_params struct) and leaves the bytes on the device.  Returns their number: 3 T (soup) or V (indexed)."""
+        p = params.to_struct() if hasattr(params, "to_struct") else params
+        n = ctypes.c_int64()
+        self._check(self._L.vtmc_ao_vertices(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return n.value
+
+    def vertex_ao(self, radius, strength=1.0, steps=4):
+        """ao_vertices, then the bytes as a uint8 array (255 = open, 0 = fully occluded at strength 1): entry 3 t + v for corner v of soup
+        triangle t, or one per vtmc_vertex of the indexed mesh.  radius in world units, at most AO_MAX_RADIUS_CELLS cells."""
+        n = self.ao_vertices(AmbientOcclusion(radius, strength, steps))
+        out = np.empty(n, np.uint8)
+        self._check(self._L.vtmc_ao_read_vertices(self._h, _ptr(out), n))
+        return out
+
+    def device_ao(self):
+        """(device address of the occlusion bytes, their number) of the last ao_vertices."""
+        p, n = ctypes.c_void_p(), ctypes.c_int64()
+        self._check(self._L.vtmc_ao_device_results(self._h, ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
 
     # -- ray picking: Physics.Raycast of the interactive edit (SceneManager.cs:114-131) on the device ---------------

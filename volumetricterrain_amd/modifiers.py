@@ -9,7 +9,7 @@ order of the C# expressions.
 import numpy as np
 
 from . import _lib
-from ._lib import (MATERIAL_CHANNELS, MESH_MAX_TRIANGLES, MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP,
+from ._lib import (AO_MAX_STEPS, MATERIAL_CHANNELS, MESH_MAX_TRIANGLES, MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP,
                    PATH_MAX_SEGMENTS, STAMP_MAX_DIM, STAMP_MAX_SAMPLES, STAMP_MIN_DIM, Modifier)
 
 _f = np.float32
@@ -222,6 +222,28 @@ class MaterialStroke:
         s = _lib.MaterialStroke()
         s.center[:] = tuple(float(x) for x in self._center)
         s.radius, s.strength, s.channel = float(self._radius), float(self._strength), self._channel
+        return s
+
+
+class AmbientOcclusion:
+    """The parameters of Extractor.vertex_ao (vtmc_ao_params): a march of `steps` samples out to `radius` (world units) along every lattice
+    direction in the normal's half space, the occlusion found scaled by `strength`.  The radius may span at most AO_MAX_RADIUS_CELLS cells
+    of the terrain it is used on; that limit depends on the terrain's voxel scale and is the library's to refuse."""
+
+    def __init__(self, radius, strength=1.0, steps=4):
+        with np.errstate(over="ignore"):
+            self._radius, self._strength = _f(radius), _f(strength)
+        if not np.isfinite(self._radius) or not self._radius > 0:
+            raise ValueError("occlusion radius must be finite and > 0")
+        if not np.isfinite(self._strength) or not 0 <= self._strength <= 1:
+            raise ValueError("occlusion strength must be finite and in [0, 1]")
+        if int(steps) != steps or not 1 <= steps <= AO_MAX_STEPS:
+            raise ValueError("occlusion steps must be an integer in 1..%d" % AO_MAX_STEPS)
+        self._steps = int(steps)
+
+    def to_struct(self):
+        s = _lib.AoParams()
+        s.radius, s.strength, s.steps, s.flags = float(self._radius), float(self._strength), self._steps, 0
         return s
 
 
