@@ -3,6 +3,7 @@
 //   host_selftest --cpu            host logic only (recording backend, no GPU needed)
 //   host_selftest --gpu <out_dir>  real libvtmc.so backend; dumps grid + meshes for the parity test
 //   host_selftest --gpu-resident <out_dir>  the same scene, grid in HBM, Update on the device
+//   host_selftest --gpu-lod <out_dir>  a resident terrain meshed at three levels of detail around a viewer; dumps nodes + per-node counts
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -226,6 +227,58 @@ static int gpu_resident_run(const std::string &out)
     return 0;
 }
 
+// a device-resident terrain of 64 x 32 x 32 cells meshed at mixed levels of detail: the viewer at cell (-1, 3, 5), roots of level 2, split 1
+static int gpu_lod_run(const std::string &out)
+{
+    VoxelTerrain vt;
+    vt._width = 64;
+    vt._elevation = 32;
+    vt._height = 32;
+    vt._voxelScale = 0.5f;
+    vt.TerrainOrigin = Vector3(-3.0f, 1.0f, 2.0f);
+    vt._deviceResident = true;
+    vt._seed = 977;
+    vt.Init();
+    Vector2 lo, up;
+    lo.x = -100; lo.y = -100; up.x = 100; up.y = 100;
+    vt.InsertModifier(std::make_shared<PlaneModifier>(6.3f, lo, up, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(27.5f, 8.0f, 10.0f), 4.25f, true));   // crosses the terrain's upper x face
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(5.0f, 6.0f, 9.0f), 3.0f, false));
+    vt.Update();
+    const int updateTriangles = vt.LastTriangleCount();
+    const size_t blocksBefore = vt.LastUpdateBlocks().size();
+    const int triNum = vt.ExtractLod(Vector3(-3.5f, 2.5f, 4.5f), 2, 1.0f);
+    const std::vector<LodNode> &nodes = vt.LodNodes();
+    std::printf("lod: nodes %zu triangles %d (full resolution %d)\n", nodes.size(), triNum, updateTriangles);
+    if (nodes.empty() || vt.LodMeshes().size() != nodes.size() || triNum <= 0 || triNum >= updateTriangles) return 7;
+    const size_t updateBlocks = vt.LastUpdateBlocks().size();
+    if (vt.LastTriangleCount() != updateTriangles || updateBlocks != blocksBefore || updateBlocks == 0) return 8;   // what Update left stands
+    std::ofstream fnodes(out + "/lod_nodes.i32", std::ios::binary), fc(out + "/lod_counts.i32", std::ios::binary);
+    size_t vertices = 0;
+    for (size_t i = 0; i < nodes.size(); i++) {
+        const int rec[4] = {nodes[i]._origin._x, nodes[i]._origin._y, nodes[i]._origin._z, nodes[i]._level};
+        fnodes.write(reinterpret_cast<const char *>(rec), sizeof rec);
+        const BlockMesh &m = vt.LodMeshes()[i];
+        const int n = (int)m.vertices.size();
+        fc.write(reinterpret_cast<const char *>(&n), sizeof n);
+        vertices += m.vertices.size();
+        const float size = 8.0f * (float)(1 << nodes[i]._level) * vt._voxelScale;   // a node's mesh stays inside its box
+        for (const Vector3 &v : m.vertices)
+            if (!(v.x >= 0 && v.x <= size && v.y >= 0 && v.y <= size && v.z >= 0 && v.z <= size)) return 9;
+    }
+    if (vertices != (size_t)triNum * 3) return 10;
+    bool refused = false;   // a root of level 3 is 64 cells: it does not divide 32
+    try {
+        vt.ExtractLod(Vector3(0, 0, 0), 3);
+    } catch (const UnityException &) {
+        refused = true;
+    }
+    if (!refused || vt.LodNodes().size() != nodes.size()) return 11;
+    vt.Free();
+    std::printf("HOST-LOD-OK\n");
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     try {
@@ -236,10 +289,11 @@ int main(int argc, char **argv)
         }
         if (argc >= 3 && std::string(argv[1]) == "--gpu") return gpu_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-resident") return gpu_resident_run(argv[2]);
+        if (argc >= 3 && std::string(argv[1]) == "--gpu-lod") return gpu_lod_run(argv[2]);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "exception: %s\n", e.what());
         return 3;
     }
-    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir>\n");
+    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir> | --gpu-resident <out_dir> | --gpu-lod <out_dir>\n");
     return 64;
 }

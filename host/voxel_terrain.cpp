@@ -212,6 +212,28 @@ public:
             throw UnityException(std::string("vtmc_material_read_vertices: ") + vtmc_last_error(_ctx));
     }
 
+    void TerrainExtractLod(const Vector3 &viewer, int maxLevel, float split, int maxNodes, std::vector<LodNode> &nodes,
+                           std::vector<CSTriangle> &tris, std::vector<int> &offsets) override
+    {
+        vtmc_lod_params p;
+        p.viewer[0] = viewer.x, p.viewer[1] = viewer.y, p.viewer[2] = viewer.z;
+        p.split = split;
+        p.max_level = maxLevel;
+        p.max_nodes = maxNodes;
+        int32_t nNodes = 0, triNum = 0;
+        if (vtmc_terrain_extract_lod(_ctx, &p, &nNodes, &triNum) != VTMC_OK)
+            throw UnityException(std::string("vtmc_terrain_extract_lod: ") + vtmc_last_error(_ctx));
+        std::vector<vtmc_lod_node> list((size_t)nNodes);
+        if (vtmc_terrain_lod_nodes(_ctx, list.data(), nNodes, nullptr) != VTMC_OK)
+            throw UnityException(std::string("vtmc_terrain_lod_nodes: ") + vtmc_last_error(_ctx));
+        nodes.clear();
+        for (const vtmc_lod_node &nd : list) nodes.push_back(LodNode{MathHelper::Int3(nd.origin[0], nd.origin[1], nd.origin[2]), nd.level});
+        tris.resize((size_t)triNum);
+        offsets.assign((size_t)nNodes + 1, 0);
+        if (vtmc_read_triangles(_ctx, reinterpret_cast<vtmc_triangle *>(tris.data()), triNum, offsets.data()) != VTMC_OK)
+            throw UnityException(std::string("vtmc_read_triangles: ") + vtmc_last_error(_ctx));
+    }
+
 private:
     vtmc_ctx *_ctx = nullptr;
     int _dims[3] = {0, 0, 0};
@@ -283,11 +305,38 @@ const std::vector<uint8_t> &VoxelTerrain::VertexMaterials()
     return _vertexMaterials;
 }
 
+int VoxelTerrain::ExtractLod(const Vector3 &viewer, int maxLevel, float split, int maxNodes)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("ExtractLod needs an initialised device-resident terrain");
+    std::vector<CSTriangle> csTriangles;
+    std::vector<int> offsets;
+    _backend->TerrainExtractLod(viewer, maxLevel, split, maxNodes, _lodNodes, csTriangles, offsets);
+    _lodMeshes.assign(_lodNodes.size(), BlockMesh());
+    for (size_t i = 0; i < _lodNodes.size(); i++) {
+        BlockMesh &mesh = _lodMeshes[i];
+        const float cell = (float)(1 << _lodNodes[i]._level) * _voxelScale;  // a node's cell in world units
+        for (int t = offsets[i]; t < offsets[i + 1]; t++) {
+            const CSTriangle &vt = csTriangles[(size_t)t];
+            mesh.vertices.push_back(Vector3(vt._position0[0], vt._position0[1], vt._position0[2]) * cell);
+            mesh.vertices.push_back(Vector3(vt._position1[0], vt._position1[1], vt._position1[2]) * cell);
+            mesh.vertices.push_back(Vector3(vt._position2[0], vt._position2[1], vt._position2[2]) * cell);
+            mesh.normals.push_back(Vector3(vt._normal0[0], vt._normal0[1], vt._normal0[2]));
+            mesh.normals.push_back(Vector3(vt._normal1[0], vt._normal1[1], vt._normal1[2]));
+            mesh.normals.push_back(Vector3(vt._normal2[0], vt._normal2[1], vt._normal2[2]));
+        }
+        mesh.triangles.resize(mesh.vertices.size());
+        for (size_t k = 0; k < mesh.triangles.size(); k++) mesh.triangles[k] = (int)k;
+    }
+    return (int)csTriangles.size();
+}
+
 // VoxelTerrain.cs:214-245
 void VoxelTerrain::Free()
 {
     for (BlockMesh &b : _blocks) b.Clear();
     _blocks.clear();
+    _lodNodes.clear();
+    _lodMeshes.clear();
     _backend.reset();
     _initialised = false;
 }

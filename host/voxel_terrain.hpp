@@ -291,6 +291,14 @@ struct MaterialStroke {
     }
 };
 
+// New (not in the reference, which meshes every block at full resolution): one node of a level-of-detail extract (vtmc_lod_node of
+// include/vtmc.h).  It covers the cells [_origin, _origin + 8 * 2^_level) per axis and is meshed as one block whose cells are 2^_level
+// fine cells wide.
+struct LodNode {
+    MathHelper::Int3 _origin;
+    int _level;
+};
+
 // What replaces a block's Unity Mesh (VoxelTerrain.cs:448-465): unindexed soup, indices 0..n-1.
 struct BlockMesh {
     std::vector<Vector3> vertices;
@@ -339,6 +347,13 @@ struct ExtractBackend {
     virtual void MaterialPaint(const std::vector<MaterialStroke> &) { throw std::logic_error("MaterialPaint unsupported"); }
     // 8 bytes per vertex of the last TerrainUpdate's result: vertex 3 t + v of triangle t
     virtual void MaterialVertices(std::vector<uint8_t> &) { throw std::logic_error("MaterialVertices unsupported"); }
+
+    // Level-of-detail extract of a device-resident terrain (vtmc_terrain_extract_lod): fills nodes (list order), tris (canonical order,
+    // _block = the node's index) and offsets (nodes + 1).
+    virtual void TerrainExtractLod(const Vector3 &, int, float, int, std::vector<LodNode> &, std::vector<CSTriangle> &, std::vector<int> &)
+    {
+        throw std::logic_error("TerrainExtractLod on a backend without device-resident terrain");
+    }
 };
 
 class VoxelTerrain {
@@ -378,6 +393,15 @@ public:
     // new: the material weights of the last Update's triangles, 8 bytes per vertex in the order of its triangles (3 per triangle)
     const std::vector<uint8_t> &VertexMaterials();
 
+    // New: level of detail (device-resident terrains).  Chooses an octree of nodes around `viewer` (world space) by the rule of
+    // include/vtmc.h -- roots of level maxLevel, a node of 8 * 2^L cells splits when the viewer's Chebyshev distance to it, in cells, is
+    // below split * its size -- and meshes every node as one block.  Returns the triangle count.  The block meshes of Update are left
+    // alone: the nodes' meshes are kept beside them (LodMeshes), mesh i belonging at TerrainOrigin + LodNodes()[i]._origin * _voxelScale
+    // with its vertices already scaled by 2^level * _voxelScale.  Seams between nodes of different levels are not stitched.
+    int ExtractLod(const Vector3 &viewer, int maxLevel, float split = 2.0f, int maxNodes = 1 << 18);
+    const std::vector<LodNode> &LodNodes() const { return _lodNodes; }      // the nodes of the last ExtractLod, in list order
+    const std::vector<BlockMesh> &LodMeshes() const { return _lodMeshes; }  // one mesh per node
+
     // -- inspection (tests, callers that consume the meshes) ----------------------------------
     const BlockMesh &Block(int x, int y, int z) const { return _blocks[((size_t)x * (_elevation / blockSize) + y) * (_height / blockSize) + z]; }
     float Sample(int x, int y, int z) const { return _voxelSamples[((size_t)x * (_elevation + 2) + y) * (_height + 2) + z]; }
@@ -393,6 +417,8 @@ private:
     void EnsureMaterialLayer();
     bool _hasMaterialLayer = false;
     std::vector<uint8_t> _vertexMaterials;
+    std::vector<LodNode> _lodNodes;
+    std::vector<BlockMesh> _lodMeshes;
     std::vector<float> _voxelSamples;  // float[W+2, E+2, H+2], row-major, z fastest (VoxelTerrain.cs:145)
     std::vector<BlockMesh> _blocks;    // GameObject[,,] stand-in (VoxelTerrain.cs:61)
     std::vector<MathHelper::Int3> _nextUpdateblocks, _lastUpdateBlocks;

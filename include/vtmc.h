@@ -742,6 +742,68 @@ int32_t vtmc_ao_read_vertices(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity_vert
 int32_t vtmc_ao_device_results(vtmc_ctx *ctx, const uint8_t **d_ao, int64_t *n_vertices);
 
 /* ------------------------------------------------------------------------------------------
+ * Level of detail -- meshing the resident terrain coarsely far from a viewer (not in the reference, which meshes every block at full
+ * resolution and is capped at 1025 samples per axis for it).  vtmc_terrain_extract_lod chooses an octree of NODES around a viewer on the
+ * host, gathers every node's 10x10x10 tile from the resident grid on the device and runs the ordinary extraction on the packed tiles.
+ *
+ * NODE.  A node of level L has stride s = 2^L and a cell origin o, every component of o a multiple of 8 s.  It covers the cells
+ * [o, o + 8 s) per axis and is meshed as ONE ordinary 8^3-cell block whose cells are s fine cells wide.  Its tile is the point subsample
+ * of the resident grid S (sample counts dim = (W+2, E+2, H+2)) with edge replication:
+ *   T[i, j, k] = S[min(o.x + i s, dim_x - 1), min(o.y + j s, dim_y - 1), min(o.z + k s, dim_z - 1)],   i, j, k in 0..9.
+ * The largest index of a node is o + 9 s <= dim - 2 + s, so only index 9 can ever clamp, and that sample feeds normals only (the forward
+ * difference of the vertices on the node's upper faces).  At L = 0 nothing clamps and the tile is the block's own: a level-0 node is
+ * byte for byte the block the ordinary terrain extract produces.
+ * The mesh of a node is what the extraction makes of T as a tile of vtmc_extract_blocks: cases, counts, 76-byte records or welded
+ * vertices, positions node-local in [0, 8], forward-difference normals of T (in units of the node's own cells).  `block` of a triangle,
+ * and the block of the per-block offsets, is the node's index in the node list.  World position of a node-local position p:
+ *   terrain_origin + (o + p * s) * voxel_scale        (the ordinary extract's mapping for a block at cell origin o, p scaled by s).
+ *
+ * SELECTION, on the host, deterministic, in double arithmetic, no operation fused (no fma):
+ *   c_k = ((double)viewer[k] - (double)terrain_origin[k]) / (double)voxel_scale                  the viewer in cells
+ *   the roots are all nodes of level max_level, x fastest (o = 8 * 2^max_level * (rx, ry, rz), rx running first, then ry, then rz)
+ *   a node of level L > 0 and size n = 8 * 2^L is replaced by its 8 children of level L - 1 when  d < (double)split * n,  where
+ *     d = max over the axes of max(o_k - c_k, 0, c_k - (o_k + n)): the Chebyshev distance from c to the box [o, o + n], 0 inside;
+ *   child k has origin o + (n / 2) * (k & 1, (k >> 1) & 1, (k >> 2) & 1) (bit 0 = x, bit 1 = y, bit 2 = z); children are visited in
+ *   increasing k and tested by the same rule; the node list is the depth-first order of that descent.
+ * The nodes tile the terrain's cells exactly once.  With split >= 1, nodes that share a face differ by at most one level: for boxes A
+ * and P that touch, d(A) <= d(P) + size(P); a node A two or more levels above a face neighbour would have had to stay whole, d(A) >=
+ * split * size(A), beside a box P of at most half its size (the neighbour's ancestor) that split, d(P) < split * size(A) / 2, which
+ * needs split * size(A) / 2 < size(A) / 2, that is split < 1.  (The tests check the 2:1 property and do not assume it.)
+ *
+ * SEAMS BETWEEN LEVELS ARE NOT STITCHED.  Where a level-L node meets a level-(L+1) node the two meshes are built from different samples
+ * and can differ on the shared face by up to the coarse cell's interpolation error: cracks are possible there.  No skirts are added and
+ * no sample is snapped.  The 2:1 property above is what a later transition pass needs.
+ *
+ * vtmc_terrain_extract_lod  works in both output modes and leaves its result for vtmc_read_triangles, vtmc_read_indexed_mesh,
+ *   vtmc_read_cases, vtmc_device_results, vtmc_device_indexed_results and vtmc_last_counts (n_blocks = the number of nodes) exactly as any
+ *   extract does.  It changes nothing in the terrain: not the grid, the dirty list, the history or the event counter.  Its result is NOT a
+ *   result of the dirty list: vtmc_material_vertices and vtmc_ao_vertices answer VTMC_ERR_NO_RESULT after it, until the next
+ *   vtmc_terrain_update / _undo / _redo / _load (per-vertex materials and occlusion on coarse nodes are not defined yet).
+ *   *n_nodes and *tri_count may be NULL.
+ *   VTMC_ERR_NO_RESULT before vtmc_terrain_init.  VTMC_ERR_INVALID_ARG: params null; viewer or split not finite; split < 1; max_level
+ *   outside 0..VTMC_LOD_MAX_LEVEL; max_nodes <= 0.  VTMC_ERR_DIMS: 8 * 2^max_level does not divide W, E and H.  VTMC_ERR_TOO_LARGE: the
+ *   selection holds more than max_nodes nodes.  All of these leave the context as it was, the previous result included.
+ * vtmc_terrain_lod_nodes  the node list of the result the context holds (dst = NULL: only *n_nodes).  VTMC_ERR_NO_RESULT when that result
+ *   is not a level-of-detail extract's (none yet, or another extract since); VTMC_ERR_CAPACITY when capacity_nodes is too small.
+ * ------------------------------------------------------------------------------------------ */
+#define VTMC_LOD_MAX_LEVEL 7
+
+typedef struct vtmc_lod_params {
+    float viewer[3];     /* world space */
+    float split;         /* >= 1: a node splits when the viewer is nearer than split * its size (in cells) */
+    int32_t max_level;   /* 0..VTMC_LOD_MAX_LEVEL: the level of the roots */
+    int32_t max_nodes;   /* > 0 */
+} vtmc_lod_params;       /* 24 bytes */
+
+typedef struct vtmc_lod_node {
+    int32_t origin[3];   /* cells; multiples of 8 * 2^level */
+    int32_t level;
+} vtmc_lod_node;         /* 16 bytes */
+
+int32_t vtmc_terrain_extract_lod(vtmc_ctx *ctx, const vtmc_lod_params *params, int32_t *n_nodes, int32_t *tri_count);
+int32_t vtmc_terrain_lod_nodes(vtmc_ctx *ctx, vtmc_lod_node *dst, int32_t capacity_nodes, int32_t *n_nodes);
+
+/* ------------------------------------------------------------------------------------------
  * Ray picking -- replaces the Physics.Raycast of the interactive edit (SceneManager.cs:114-131)
  * against the MeshColliders that BatchUpdate cooks from the extracted mesh (VoxelTerrain.cs:448-465),
  * without any mesh on the host.  The surface is the triangle set vtmc_extract_grid emits for every

@@ -57,6 +57,7 @@ SYMBOLS = [
     "vtmc_material_init", "vtmc_material_set_control_map", "vtmc_material_write", "vtmc_material_read", "vtmc_material_paint",
     "vtmc_material_vertices", "vtmc_material_read_vertices", "vtmc_material_device_results",
     "vtmc_ao_vertices", "vtmc_ao_read_vertices", "vtmc_ao_device_results",
+    "vtmc_terrain_extract_lod", "vtmc_terrain_lod_nodes",
 ]
 COMM_ID_BYTES = 128
 
@@ -69,6 +70,7 @@ MOD_PATH = 10                     # union of tapered capsules over a segment sou
 PATH_CHUNK, PATH_MAX_SEGMENTS = 256, 65536   # csrc/terrain_path.h: segments a workgroup prunes at a time; the most a modifier may hold
 MATERIAL_CHANNELS, MATERIAL_MAX_STROKES = 8, 4096   # the material layer: bytes per texel and per vertex; the most strokes of one paint call
 AO_MAX_STEPS, AO_MAX_RADIUS_CELLS = 8, 6   # vtmc_ao_vertices: the most steps of a march; the largest radius in cells (radius / voxel_scale)
+LOD_MAX_LEVEL = 7                 # vtmc_terrain_extract_lod: the coarsest level of a node (128 fine cells per node cell)
 MOD_NOISE = 8                     # fBm / billow / ridged noise (RidgedMultifractalModifier's device form); 6 and 7 are not defined
 
 
@@ -88,6 +90,16 @@ class MaterialStroke(ctypes.Structure):
 class AoParams(ctypes.Structure):
     """vtmc_ao_params: radius in world units, strength in [0, 1], steps 1..AO_MAX_STEPS, flags 0."""
     _fields_ = [("radius", ctypes.c_float), ("strength", ctypes.c_float), ("steps", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class LodParams(ctypes.Structure):
+    """vtmc_lod_params: viewer in world space, split >= 1, max_level 0..LOD_MAX_LEVEL, max_nodes > 0."""
+    _fields_ = [("viewer", ctypes.c_float * 3), ("split", ctypes.c_float), ("max_level", ctypes.c_int32), ("max_nodes", ctypes.c_int32)]
+
+
+class LodNode(ctypes.Structure):
+    """vtmc_lod_node: cell origin (multiples of 8 * 2^level) and level of one node of a level-of-detail extract."""
+    _fields_ = [("origin", ctypes.c_int32 * 3), ("level", ctypes.c_int32)]
 
 
 class VolumeBatch(ctypes.Structure):
@@ -222,6 +234,13 @@ def load(path=None):
         L.vtmc_ao_device_results.argtypes = [vp, P(vp), P(i64)]
         L.vtmc_debug_ao_routes.argtypes = [vp, P(u32 * 2), i32]   # not in the header: the route counters of the last vtmc_ao_vertices
         L.vtmc_debug_ao_routes.restype = i32
+    if not explicit or hasattr(L, "vtmc_terrain_extract_lod"):
+        L.vtmc_terrain_extract_lod.argtypes = [vp, P(LodParams), P(i32), P(i32)]
+        L.vtmc_terrain_lod_nodes.argtypes = [vp, vp, i32, P(i32)]
+        L.vtmc_debug_lod_gather_ms.argtypes = [vp, P(ctypes.c_float)]   # not in the header: device time of the last gather launch
+        L.vtmc_debug_lod_gather_ms.restype = i32
+        L.vtmc_debug_lod_tiles.argtypes = [vp, vp, i64]                 # not in the header: the gathered tiles of the last level-of-detail extract
+        L.vtmc_debug_lod_tiles.restype = i32
     L.vtmc_comm_unique_id.argtypes = [vp]
     L.vtmc_comm_init_rank.argtypes = [vp, vp, i32, i32]
     L.vtmc_comm_destroy.argtypes = [vp]

@@ -1,5 +1,5 @@
 // vtmc_ctx.h -- the context object behind include/vtmc.h and the small host helpers every translation unit of the C-ABI layer shares
-// (context.hip, vtmc_api.hip, terrain.hip, terrain_stamp.hip, stamp_mesh.hip, terrain_path.hip, terrain_material.hip, terrain_ao.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
+// (context.hip, vtmc_api.hip, terrain.hip, terrain_stamp.hip, stamp_mesh.hip, terrain_path.hip, terrain_material.hip, terrain_ao.hip, terrain_lod.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
 #ifndef VTMC_CTX_H
 #define VTMC_CTX_H
 #include "../../include/vtmc.h"
@@ -157,6 +157,14 @@ struct vtmc_ctx {
     int64_t ao_vertices = 0;
     uint64_t ao_epoch = 0;
     int32_t ao_direct_max = -1;         // vertices up to which a block takes the direct route; -1: the library's default
+    // terrain_lod.hip: the node list of the level-of-detail result lod_epoch names (host, and the copy the gather kernel reads), the packed
+    // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the events around
+    // the last gather launch (vtmc_debug_lod_gather_ms)
+    std::vector<vtmc_lod_node> lod_nodes;
+    VtmcDevBuf lod_nodes_dev, lod_tiles;
+    uint64_t lod_epoch = 0;
+    hipEvent_t ev_lod[2] = {nullptr, nullptr};
+    bool lod_timed = false;
     // raycast.hip, spherequery.hip: the queries and hits of vtmc_terrain_raycast / _spherecast / _closest_point (device, then their pinned staging)
     VtmcDevBuf rays;
     VtmcPinnedBuf<unsigned char> h_rays;

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import COMM_ID_BYTES, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
-from .modifiers import AmbientOcclusion, mesh_stamp_args
+from .modifiers import AmbientOcclusion, LodParams, mesh_stamp_args
 
 
 def _ptr(a):
@@ -262,6 +262,7 @@ class Extractor:
         o = (ctypes.c_float * 3)(*origin)
         self._check(self._L.vtmc_terrain_init(self._h, width, elevation, height, voxel_scale, ctypes.byref(o), seed))
         self._terrain_dims = (width, elevation, height)
+        self._terrain_placement = (tuple(float(np.float32(v)) for v in origin), float(np.float32(voxel_scale)))   # for lod_world_positions
 
     def terrain_update(self, mods):
         """VoxelTerrain.Update (VoxelTerrain.cs:262-325) for a queue of Modifier structs.
@@ -334,6 +335,9 @@ class Extractor:
         dims = (ctypes.c_int32 * 3)()
         self._check(self._L.vtmc_terrain_device_grid(self._h, None, None, ctypes.byref(dims)))
         self._terrain_dims = tuple(d - 2 for d in dims)   # for terrain_read_samples
+        from .terrainfile import read_header
+        meta = read_header(path)
+        self._terrain_placement = (tuple(float(v) for v in meta["origin"]), float(meta["scale"]))   # for lod_world_positions
         return nd.value, t.value
 
     def terrain_write_samples(self, grid):
@@ -475,6 +479,44 @@ class Extractor:
         p, n = ctypes.c_void_p(), ctypes.c_int64()
         self._check(self._L.vtmc_ao_device_results(self._h, ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
+
+    # -- level of detail: the resident terrain meshed coarsely far from a viewer ---------------------------------------
+    def terrain_extract_lod(self, viewer, max_level, split=2.0, max_nodes=1 << 18):
+        """Chooses an octree of nodes around `viewer` (world space; roots of level max_level, a node of 8 * 2^L cells splits when the viewer
+        is nearer than split times its size), gathers each node's tile from the resident grid at stride 2^L and extracts them as blocks, in
+        the output mode set.  `viewer` may be a LodParams (or a vtmc_lod_params struct) instead; the other arguments are then not read.
+        Returns (number of nodes, T); read the mesh as after any extract, `block` of a triangle indexes terrain_lod_nodes()."""
+        if hasattr(viewer, "to_struct"):
+            p = viewer.to_struct()
+        elif isinstance(viewer, _lib.LodParams):
+            p = viewer
+        else:
+            p = LodParams(viewer, max_level, split, max_nodes).to_struct()
+        n, t = ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._L.vtmc_terrain_extract_lod(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(t)))
+        return n.value, t.value
+
+    def terrain_lod_nodes(self):
+        """The nodes of the level-of-detail result the context holds: an (n, 4) int32 array of (origin x, y, z in cells, level)."""
+        n = ctypes.c_int32()
+        self._check(self._L.vtmc_terrain_lod_nodes(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 4), np.int32)
+        self._check(self._L.vtmc_terrain_lod_nodes(self._h, _ptr(out), n.value, ctypes.byref(n)))
+        return out
+
+    def lod_world_positions(self, nodes, block, local_positions):
+        """World positions (float64) of node-local positions of a level-of-detail mesh: terrain origin + (o + p * 2^level) * voxel scale,
+        with (o, level) = nodes[block].  block: (n,) node indices (a triangle's `block`); local_positions: (n, 3) or (n, m, 3)."""
+        nodes = np.asarray(nodes, np.int64).reshape(-1, 4)
+        block = np.asarray(block, np.int64)
+        p = np.asarray(local_positions, np.float64)
+        o, s = nodes[block, :3].astype(np.float64), np.ldexp(1.0, nodes[block, 3])
+        if p.ndim == 3:
+            o, s = o[:, None, :], s[:, None, None]
+        else:
+            s = s[:, None]
+        origin, scale = self._terrain_placement
+        return np.asarray(origin, np.float64) + (o + p * s) * float(scale)
 
     # -- ray picking: Physics.Raycast of the interactive edit (SceneManager.cs:114-131) on the device ---------------
     def terrain_raycast(self, origins, directions, max_distance=float("inf"), two_sided=False):

@@ -9,7 +9,7 @@ order of the C# expressions.
 import numpy as np
 
 from . import _lib
-from ._lib import (AO_MAX_STEPS, MATERIAL_CHANNELS, MESH_MAX_TRIANGLES, MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP,
+from ._lib import (AO_MAX_STEPS, LOD_MAX_LEVEL, MATERIAL_CHANNELS, MESH_MAX_TRIANGLES, MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP,
                    PATH_MAX_SEGMENTS, STAMP_MAX_DIM, STAMP_MAX_SAMPLES, STAMP_MIN_DIM, Modifier)
 
 _f = np.float32
@@ -244,6 +244,32 @@ class AmbientOcclusion:
     def to_struct(self):
         s = _lib.AoParams()
         s.radius, s.strength, s.steps, s.flags = float(self._radius), float(self._strength), self._steps, 0
+        return s
+
+
+class LodParams:
+    """The parameters of Extractor.terrain_extract_lod (vtmc_lod_params): the viewer in world space, the level of the octree's roots
+    (0..LOD_MAX_LEVEL; a root of 8 * 2^max_level cells must divide the terrain, which is the library's to refuse), `split` >= 1 (a node
+    splits when the viewer's Chebyshev distance to it, in cells, is below split times its size) and the most nodes the call may select."""
+
+    def __init__(self, viewer, max_level, split=2.0, max_nodes=1 << 18):
+        with np.errstate(over="ignore"):
+            self._viewer = tuple(_f(v) for v in viewer)
+            self._split = _f(split)
+        if len(self._viewer) != 3 or not all(np.isfinite(v) for v in self._viewer):
+            raise ValueError("viewer must be three finite coordinates")
+        if not np.isfinite(self._split) or not self._split >= 1:
+            raise ValueError("split must be finite and >= 1")
+        if int(max_level) != max_level or not 0 <= max_level <= LOD_MAX_LEVEL:
+            raise ValueError("max_level must be an integer in 0..%d" % LOD_MAX_LEVEL)
+        if int(max_nodes) != max_nodes or not 0 < max_nodes < 2 ** 31:
+            raise ValueError("max_nodes must be an integer in 1..2^31-1")
+        self._max_level, self._max_nodes = int(max_level), int(max_nodes)
+
+    def to_struct(self):
+        s = _lib.LodParams()
+        s.viewer[:] = [float(v) for v in self._viewer]
+        s.split, s.max_level, s.max_nodes = float(self._split), self._max_level, self._max_nodes
         return s
 
 
