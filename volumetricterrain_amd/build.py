@@ -14,9 +14,9 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvtmc.so")
-SOURCES = ["context.hip", "vtmc_api.hip", "classify_kernels.hip", "emit_kernels.hip", "terrain.hip", "terrain_stamp.hip", "stamp_mesh.hip", "terrain_path.hip", "terrain_material.hip", "terrain_ao.hip", "terrain_lod.hip", "terrain_io.hip", "density.hip",
+SOURCES = ["context.hip", "vtmc_api.hip", "classify_kernels.hip", "emit_kernels.hip", "terrain.hip", "terrain_brush.hip", "terrain_noise.hip", "terrain_stamp.hip", "stamp_mesh.hip", "terrain_path.hip", "terrain_material.hip", "terrain_ao.hip", "terrain_lod.hip", "terrain_io.hip", "density.hip",
            "chunk_io.hip", "comm.hip", "raycast.hip", "spherequery.hip"]
-HEADERS = ["vtmc_internal.h", "vtmc_ctx.h", "mc_device.h", "emit_device.h", "mc_tables_packed.h", "mc_cell.h", "surface_query.h", "perlin_device.h", "terrain_hash.h", "terrain_box.h", "terrain_stamp.h", "mesh_host.h", "terrain_path.h", "terrain_material.h", "terrain_ao.h", "terrain_lod.h", "record_tile.h", os.path.join("..", "..", "include", "vtmc.h")]
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "vtmc.h")]   # for is_stale only
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent FP32 operations into v_pk_fma_f32 / v_pk_add_f32 (+ moves to
 # pair the operands); on gfx950 a packed FP32 op costs more than the two scalar ones it replaces
 # (MI355X_MICROARCH.md, "packed f32 VALU ... an anti-lever"): the sampler runs 30 % faster without it.

@@ -1,5 +1,5 @@
 // perlin_device.h -- the library's one Perlin: Ken Perlin's 2002 improved noise over a 256-entry permutation (density_permutation), as
-// oracle/density_ref.c states it.  Shared by density.hip (the benchmark volumes' per-sample kernel) and terrain.hip (VTMC_MOD_NOISE).
+// oracle/density_ref.c states it.  Shared by density.hip (the benchmark volumes' per-sample kernel) and terrain_noise.hip (VTMC_MOD_NOISE).
 // FP32, one IEEE operation per step (the library is built with -ffp-contract=off), so a sample's bits depend on its position alone.
 //
 // A sample is split where the terrain's box walk splits it: perlin_column is everything that depends on x and z only (lattice cell,

@@ -16,10 +16,7 @@
 // counter-based hash of (seed, event, sample index, draw index) -- same ranges, same number of
 // draws per sample (2 per add, 4 per erode, 1 per Init sample), deterministic; the CPU oracle
 // restates the same hash (oracle/terrain_ref.c).
-#include "vtmc_ctx.h"
-#include "perlin_device.h"
-#include "terrain_box.h"
-#include "terrain_path.h"
+#include "terrain_edit.h"
 #include "terrain_stamp.h"
 #include <algorithm>
 #include <array>
@@ -109,14 +106,7 @@ __global__ __launch_bounds__(256) void terrain_modify_kernel(float *__restrict__
         const float md = clamp_drawn(q, sh.seed, m.event, sample, 0u);
         const float s = grid[sample];
         if (kJournal) image[row + (uint64_t)m.dx * (uint64_t)iy] = s;
-        float r;
-        if (m.add_or_erode) {
-            r = s > md ? s : md;  // Mathf.Max(S, md)
-        } else {
-            const float minus_md = -md;
-            r = clamp_drawn(s < minus_md ? s : minus_md, sh.seed, m.event, sample, 2u);  // Clamp(Min(S, -md), void, full)
-        }
-        grid[sample] = r;
+        grid[sample] = csg_combine(sh, m.event, sample, m.add_or_erode, md, s);
     }
 }
 
@@ -143,48 +133,8 @@ __global__ __launch_bounds__(256) void terrain_swap_kernel(uint32_t *__restrict_
         }
 }
 
-// ---- sculpt brushes (VTMC_MOD_SMOOTH / VTMC_MOD_FLATTEN; not in the reference) ----------------------------------------------------
-// Both blend a sample towards a target T by w = s * clamp01(2 * (1 - |p - c| / r)): full strength inside r/2, linear to 0 at r.  A
-// sample of weight 0 keeps its 32 bits (it is not rewritten); any other becomes S + (T - S) * w (Mathf.Lerp's form, as lerp_unity).
-
-__device__ __forceinline__ float brush_weight(const TerrainModifierArgs &m, float px, float py, float pz)
-{
-    const float dx = px - m.p[0], dy = py - m.p[1], dz = pz - m.p[2];
-    const float d = __builtin_sqrtf(dx * dx + dy * dy + dz * dz);  // as SphereModifier in query_density
-    float t = 1.0f - d / m.p[3];
-    t = t + t;
-    t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-    return m.p[4] * t;
-}
-
-// Flatten: T = clamp((n . (c - p)) / scale, -1, 1), solid below the plane through c, air above it, linear in grid units within one
-// sample of it.  Pointwise; kJournal also stores every sample of the box into its image.
-template <bool kJournal>
-__global__ __launch_bounds__(256) void terrain_flatten_kernel(float *__restrict__ grid, float *__restrict__ image, TerrainShape sh, TerrainModifierArgs m)
-{
-    const BoxThread t;
-    if (!t.inside(m)) return;
-    const int x = m.lx + t.ix, z = m.lz + t.iz;
-    const float px = (float)x * sh.scale + sh.origin[0];
-    const float pz = (float)z * sh.scale + sh.origin[2];
-    const uint64_t row = box_index(m, t.ix, 0, t.iz);  // image index of (ix, 0, iz); sample iy lies iy rows of dx further
-    for (int iy = t.iy0, iy1 = t.iy1(m); iy < iy1; ++iy) {
-        const int y = m.ly + iy;
-        const float py = (float)y * sh.scale + sh.origin[1];
-        const uint64_t sample = grid_index(sh, x, y, z);
-        const float w = brush_weight(m, px, py, pz);
-        if (!kJournal && w == 0.0f) continue;
-        const float s = grid[sample];
-        if (kJournal) image[row + (uint64_t)m.dx * (uint64_t)iy] = s;
-        if (w == 0.0f) continue;
-        float g = (m.p[5] * (m.p[0] - px) + m.p[6] * (m.p[1] - py) + m.p[7] * (m.p[2] - pz)) / sh.scale;
-        g = g < -1.0f ? -1.0f : (g > 1.0f ? 1.0f : g);
-        grid[sample] = s + (g - s) * w;
-    }
-}
-
-// Smooth, pass 1: the brush's box plus a one-sample halo, intersected with the grid (box h), copied to the stage.  Load-before-store
-// order of terrain_swap_kernel.
+// A box h of the grid, copied to `stage`: pass 1 of a smooth (terrain_brush.hip: the brush's box plus a one-sample halo, intersected with
+// the grid) and a stamp's capture.  Load-before-store order of terrain_swap_kernel.
 __global__ __launch_bounds__(256) void terrain_stage_kernel(const float *__restrict__ grid, float *__restrict__ stage, TerrainShape sh, TerrainBox h)
 {
     const BoxThread t;
@@ -200,207 +150,6 @@ __global__ __launch_bounds__(256) void terrain_stage_kernel(const float *__restr
         if (t.iy0 + k < iy1) stage[j0 + (uint64_t)h.dx * k] = v[k];
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// Smooth, pass 2: T = the 27-point box mean of the staged (pre-brush) samples, neighbour indices clamped to the grid, summed as
-//   R(y, z) = (s[x-1] + s[x]) + s[x+1],  P(z) = (R(y-1, z) + R(y, z)) + R(y+1, z),  T = ((P(z-1) + P(z)) + P(z+1)) / 27.
-// A workgroup owns 64 x 4 samples of (x, z) and walks kYRun of y.  Per y-plane of the stage it puts a 66 x 6 tile (the samples and
-// their x / z neighbours) in LDS, and each lane keeps the row sums R of the last two planes in registers, so a staged sample is read
-// from memory (66 * 6) / (64 * 4) * (kYRun + 2) / kYRun = 1.74 times per workgroup, not 27.  Clamping a tile coordinate to the stage
-// is clamping it to the grid: the stage is the box plus whatever of its halo lies in the grid.  Every staged load of the run is
-// issued before the first LDS store.  The old value of each box sample comes from the stage, so kJournal's image costs no grid read.
-constexpr int kTileX = 66, kTileZ = 6, kTile = kTileX * kTileZ;
-template <bool kJournal>
-__global__ __launch_bounds__(256) void terrain_smooth_kernel(float *__restrict__ grid, float *__restrict__ image, const float *__restrict__ stage,
-                                                             TerrainShape sh, TerrainModifierArgs m, TerrainBox h)
-{
-    __shared__ float tile[2][kTile];
-    const BoxThread bt;
-    const int tx = threadIdx.x, tz = threadIdx.y, t = tz * 64 + tx;
-    const int ox = m.lx - h.lx, oy = m.ly - h.ly, oz = m.lz - h.lz;  // the box's first sample in the stage (0 or 1 per axis)
-    const int n_planes = bt.iy1(m) - bt.iy0 + 2;                          // uniform over the workgroup
-    const uint64_t plane = (uint64_t)h.dx * (uint64_t)h.dy;
-    // this lane's tile entries t and t + 256 (the second for t < kTile - 256 only)
-    const bool two = t + 256 < kTile;
-    const uint64_t c0 = (uint64_t)clampi(blockIdx.x * 64 + ox - 1 + t % kTileX, 0, h.dx - 1) +
-                        plane * (uint64_t)clampi(blockIdx.y * 4 + oz - 1 + t / kTileX, 0, h.dz - 1);
-    const uint64_t c1 = two ? (uint64_t)clampi(blockIdx.x * 64 + ox - 1 + (t + 256) % kTileX, 0, h.dx - 1) +
-                                  plane * (uint64_t)clampi(blockIdx.y * 4 + oz - 1 + (t + 256) / kTileX, 0, h.dz - 1)
-                            : 0;
-    float v0[kYRun + 2], v1[kYRun + 2];
-#pragma unroll
-    for (int k = 0; k < kYRun + 2; ++k)
-        if (k < n_planes) {
-            const uint64_t sy = (uint64_t)h.dx * (uint64_t)clampi(bt.iy0 + oy - 1 + k, 0, h.dy - 1);
-            v0[k] = stage[c0 + sy];
-            if (two) v1[k] = stage[c1 + sy];
-        }
-    // BoxThread::inside, written out: through the call the compiler nests the 15 unrolled write-backs in two branches instead of one mask
-    const bool live = bt.ix < m.dx && bt.iz < m.dz;
-    const int x = m.lx + bt.ix, z = m.lz + bt.iz;
-    const float px = (float)x * sh.scale + sh.origin[0];
-    const float pz = (float)z * sh.scale + sh.origin[2];
-    const uint64_t row = box_index(m, bt.ix, 0, bt.iz);
-    float ra[3] = {0.0f, 0.0f, 0.0f}, rb[3] = {0.0f, 0.0f, 0.0f}, sb = 0.0f;  // R of planes k-2 and k-1 at z-1, z, z+1; S of plane k-1
-#pragma unroll
-    for (int k = 0; k < kYRun + 2; ++k) {
-        if (k < n_planes) {  // uniform over the workgroup, as the barrier needs
-            // double-buffered: the buffer written here was last read before the previous iteration's barrier
-            float *tl = tile[k & 1];
-            tl[t] = v0[k];
-            if (two) tl[t + 256] = v1[k];
-            __syncthreads();
-            float r[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const float *q = tl + (tz + j) * kTileX + tx;
-                r[j] = (q[0] + q[1]) + q[2];
-            }
-            const float sc = tl[(tz + 1) * kTileX + tx + 1];
-            if (k >= 2 && live) {
-                const int iy = bt.iy0 + k - 2, y = m.ly + iy;
-                const float py = (float)y * sh.scale + sh.origin[1];
-                const uint64_t sample = grid_index(sh, x, y, z);
-                if (kJournal) image[row + (uint64_t)m.dx * (uint64_t)iy] = sb;
-                const float w = brush_weight(m, px, py, pz);
-                if (w != 0.0f) {
-                    const float p0 = (ra[0] + rb[0]) + r[0], p1 = (ra[1] + rb[1]) + r[1], p2 = (ra[2] + rb[2]) + r[2];
-                    const float target = ((p0 + p1) + p2) / 27.0f;
-                    grid[sample] = sb + (target - sb) * w;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                ra[j] = rb[j];
-                rb[j] = r[j];
-            }
-            sb = sc;
-        }
-    }
-}
-
-// ---- noise modifier (VTMC_MOD_NOISE: fBm, billow, ridged multifractal; the reference's RidgedMultifractalModifier wraps LibNoise, which
-// it does not vendor: the values here are the library's own Perlin, perlin_device.h) ---------------------------------------------------
-// Its own kernel arguments, not TerrainModifierArgs (which every other kernel carries): the 256-byte permutation travels by value, so an
-// edit needs no device allocation, no upload and no host wait.
-struct TerrainNoiseArgs {
-    int add_or_erode;
-    float frequency, lacunarity, gain, amplitude, bias, ramp_scale, ramp_center, ridge_offset;  // vtmc_modifier.p[0..7]
-    int octaves;
-    int lx, ly, lz, dx, dy, dz;  // the clamped sample box, as TerrainModifierArgs
-    uint32_t event;
-    unsigned char perm[256];     // density_permutation((uint64_t)(uint32_t)seed)
-};
-
-// one octave's contribution: sum and the ridged basis' running weight w, from the octave's noise value n
-template <int kBasis>
-__device__ __forceinline__ void noise_octave(float n, float amp, float ridge_offset, float &sum, float &w)
-{
-    if (kBasis == 0) {          // fBm
-        sum = sum + amp * n;
-    } else if (kBasis == 1) {   // billow
-        float t = fabsf(n);
-        t = t + t;
-        t = t - 1.0f;
-        sum = sum + amp * t;
-    } else {                    // ridged multifractal
-        float r = ridge_offset - fabsf(n);
-        r = r * r;
-        r = r * w;
-        w = r + r;
-        w = w < 0.0f ? 0.0f : (w > 1.0f ? 1.0f : w);
-        sum = sum + amp * r;
-    }
-}
-
-// what a sample becomes: q from its octave sum, the clamp draws, then the add / erode rule of terrain_modify_kernel
-__device__ __forceinline__ float noise_write(const TerrainShape &sh, const TerrainNoiseArgs &m, float sum, float py, uint64_t sample, float s)
-{
-    float q = m.amplitude * sum;
-    q = q + m.bias;
-    q = q - (py - m.ramp_center) * m.ramp_scale;
-    const float md = clamp_drawn(q, sh.seed, m.event, sample, 0u);
-    if (m.add_or_erode) return s > md ? s : md;
-    const float minus_md = -md;
-    return clamp_drawn(s < minus_md ? s : minus_md, sh.seed, m.event, sample, 2u);
-}
-
-// VALU-bound (octaves x ~100 FP32 operations against 8-12 bytes per sample), unlike the kernels above.  The octave loop is the OUTER one:
-// what an octave needs of x and z (perlin_column) is evaluated once and serves the kYRun samples of the thread's run, whose octave
-// coordinates, sums and ridge weights stay in registers (3 x kYRun).  Every sample still sees its own operations in the header's order,
-// so the interchange keeps the bits.  A run's tail past the box is evaluated and never loaded or stored.
-// VTMC_NOISE_PER_SAMPLE builds the plain form (noise3 per sample and octave) for the comparison in profiles/r11/noise/README.md.
-template <bool kJournal, int kBasis>
-__global__ __launch_bounds__(256) void terrain_noise_kernel(float *__restrict__ grid, float *__restrict__ image, TerrainShape sh, TerrainNoiseArgs m)
-{
-    __shared__ unsigned s_perm[512];  // 32-bit entries, the table twice: a lookup is one ds_read_b32 with no index wrap
-    {
-        const int t = threadIdx.y * 64 + threadIdx.x;
-        const unsigned v = m.perm[t];
-        s_perm[t] = v;
-        s_perm[t + 256] = v;
-    }
-    __syncthreads();
-    const PermWords P{s_perm};
-    const BoxThread t;
-    if (!t.inside(m)) return;
-    const int x = m.lx + t.ix, z = m.lz + t.iz;
-    const float px = (float)x * sh.scale + sh.origin[0];
-    const float pz = (float)z * sh.scale + sh.origin[2];
-    const int iy1 = t.iy1(m);
-    const uint64_t s0 = grid_index(sh, x, m.ly + t.iy0, z), j0 = box_index(m, t.ix, t.iy0, t.iz);  // sample k of the run: k rows further
-#ifndef VTMC_NOISE_PER_SAMPLE
-    float yo[kYRun], sum[kYRun], w[kYRun];
-#pragma unroll
-    for (int k = 0; k < kYRun; ++k) {
-        const float py = (float)(m.ly + t.iy0 + k) * sh.scale + sh.origin[1];
-        yo[k] = py * m.frequency;
-        sum[k] = 0.0f;
-        w[k] = 1.0f;
-    }
-    float xo = px * m.frequency, zo = pz * m.frequency, amp = 1.0f;
-    for (int o = 0; o < m.octaves; ++o) {
-        const PerlinColumn c = perlin_column(P, xo, zo);
-#pragma unroll
-        for (int k = 0; k < kYRun; ++k) {
-            noise_octave<kBasis>(perlin_at(P, c, yo[k]), amp, m.ridge_offset, sum[k], w[k]);
-            yo[k] = yo[k] * m.lacunarity;
-        }
-        xo = xo * m.lacunarity;
-        zo = zo * m.lacunarity;
-        amp = amp * m.gain;
-    }
-    float old[kYRun];  // every load of the run is issued before the first store, as terrain_swap_kernel
-#pragma unroll
-    for (int k = 0; k < kYRun; ++k)
-        if (t.iy0 + k < iy1) old[k] = grid[s0 + (uint64_t)sh.dim_x * k];
-#pragma unroll
-    for (int k = 0; k < kYRun; ++k)
-        if (t.iy0 + k < iy1) {
-            const float py = (float)(m.ly + t.iy0 + k) * sh.scale + sh.origin[1];  // again rather than kept: kYRun registers
-            const uint64_t sample = s0 + (uint64_t)sh.dim_x * k;
-            if (kJournal) image[j0 + (uint64_t)m.dx * k] = old[k];
-            grid[sample] = noise_write(sh, m, sum[k], py, sample, old[k]);
-        }
-#else
-    for (int k = 0; t.iy0 + k < iy1; ++k) {
-        const float py = (float)(m.ly + t.iy0 + k) * sh.scale + sh.origin[1];
-        float xo = px * m.frequency, yo = py * m.frequency, zo = pz * m.frequency, amp = 1.0f, sum = 0.0f, w = 1.0f;
-        for (int o = 0; o < m.octaves; ++o) {
-            noise_octave<kBasis>(noise3(P, xo, yo, zo), amp, m.ridge_offset, sum, w);
-            xo = xo * m.lacunarity;
-            yo = yo * m.lacunarity;
-            zo = zo * m.lacunarity;
-            amp = amp * m.gain;
-        }
-        const uint64_t sample = s0 + (uint64_t)sh.dim_x * k;
-        const float s = grid[sample];
-        if (kJournal) image[j0 + (uint64_t)m.dx * k] = s;
-        grid[sample] = noise_write(sh, m, sum, py, sample, s);
-    }
-#endif
-}
-
 hipError_t launch_terrain_fill(float *grid, long long n, uint64_t seed, int n_cus, hipStream_t stream)
 {
     long long wgs = (n + 255) / 256;
@@ -411,8 +160,6 @@ hipError_t launch_terrain_fill(float *grid, long long n, uint64_t seed, int n_cu
     return launch_end();
 }
 
-static TerrainBox box_of(const TerrainModifierArgs &m) { return TerrainBox{m.lx, m.ly, m.lz, m.dx, m.dy, m.dz}; }
-
 // declared by vtmc_internal.h, whose text the traffic constant of the extract path is tied to: kept for that declaration, vtmc_terrain_update
 // goes through launch_box itself
 hipError_t launch_terrain_modify(float *grid, const TerrainShape &sh, const TerrainModifierArgs &m, hipStream_t stream)
@@ -420,18 +167,10 @@ hipError_t launch_terrain_modify(float *grid, const TerrainShape &sh, const Terr
     return box_empty(box_of(m)) ? hipSuccess : launch_box(terrain_modify_kernel<false>, box_of(m), stream, grid, (float *)nullptr, sh, m);
 }
 
-// vtmc_stamp_capture (terrain_stamp.h): a box of the grid as 32-bit copies, the copy a smooth stages its box with
+// terrain_stamp.h: a box of the grid as 32-bit copies, for vtmc_stamp_capture and the stage of a smooth (terrain_brush.hip)
 hipError_t launch_terrain_copy_box(const float *grid, float *dst, const TerrainShape &sh, const TerrainBox &b, hipStream_t stream)
 {
     return launch_box(terrain_stage_kernel, b, stream, grid, dst, sh, b);
-}
-
-// the stage box of a smooth: its (non-empty) box grown by one sample per side, intersected with the grid
-static TerrainBox smooth_stage_box(const TerrainShape &sh, const TerrainModifierArgs &m)
-{
-    const int lx = std::max(m.lx - 1, 0), ly = std::max(m.ly - 1, 0), lz = std::max(m.lz - 1, 0);
-    const int ux = std::min(m.lx + m.dx, sh.dim_x - 1), uy = std::min(m.ly + m.dy, sh.dim_y - 1), uz = std::min(m.lz + m.dz, sh.dim_z - 1);
-    return TerrainBox{lx, ly, lz, ux - lx + 1, uy - ly + 1, uz - lz + 1};
 }
 
 static int saturating_int(float f)   // of a floor / ceil: Mathf.FloorToInt / CeilToInt, saturating
@@ -449,8 +188,7 @@ static void for_each_block(const std::array<int, 3> &nb, F f)
             for (int bx = 0; bx < nb[0]; ++bx) f(bx, by, bz);
 }
 
-// a modifier's kernel arguments: its AABB in sample indices, [low, up] clamped to the grid (up[] is also what the dirty blocks are found from)
-static TerrainModifierArgs sample_range(const TerrainShape &sh, const vtmc_modifier &md, int low[3], int up[3])
+TerrainModifierArgs sample_range(const TerrainShape &sh, const vtmc_modifier &md, int low[3], int up[3])
 {
     TerrainModifierArgs a{};
     a.kind = md.kind;
@@ -499,76 +237,60 @@ static size_t mark_dirty_blocks(const int low[3], const int up[3], const std::ar
     return n_new;
 }
 
-// VTMC_MOD_NOISE: data_dims[1] = octaves | basis << 8
-static int noise_octaves(const vtmc_modifier &md) { return md.data_dims[1] & 255; }
-static int noise_basis(const vtmc_modifier &md) { return md.data_dims[1] >> 8; }
-
-// The largest magnitude a lattice coordinate of a (checked: finite parameters, octaves 1..16) noise modifier can take inside its clamped
-// sample box: the box's world corners (positions are monotonic in the index) times |f| * max(1, |L|)^(octaves - 1).  From 2^24 on the
-// lattice fraction carries no information, and further out the float -> int conversion differs between targets.
-static double noise_lattice_reach(const TerrainShape &sh, const vtmc_modifier &md)
+// An earlier modifier of the same queue may still be reading what the buffer held, hence the drain before the buffer is grown or written.
+int stage_for_queue(vtmc_ctx *ctx, VtmcDevBuf &buf, const void *host, size_t bytes)
 {
-    int low[3], up[3];
-    const TerrainModifierArgs a = sample_range(sh, md, low, up);
-    if (box_empty(box_of(a))) return 0.0;  // no sample is evaluated
-    const int first[3] = {a.lx, a.ly, a.lz}, ext[3] = {a.dx, a.dy, a.dz};
-    double reach = 0.0;
-    for (int k = 0; k < 3; ++k)
-        for (int idx : {first[k], first[k] + ext[k] - 1}) reach = std::max(reach, (double)std::fabs((float)idx * sh.scale + sh.origin[k]));
-    return reach * std::fabs((double)md.p[0]) * std::pow(std::max(1.0, std::fabs((double)md.p[1])), noise_octaves(md) - 1);
+    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = ensure(ctx, buf, bytes)) return rc;
+    VTMC_HIP(ctx, hipMemcpy(buf.p, host, bytes, hipMemcpyHostToDevice));
+    return VTMC_OK;
 }
 
-static TerrainNoiseArgs noise_args(const vtmc_modifier &md, const TerrainModifierArgs &a)
+// the reference's modifiers, kinds 0-3
+static int check_reference(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i)
 {
-    TerrainNoiseArgs n{};
-    n.add_or_erode = a.add_or_erode;
-    n.frequency = md.p[0], n.lacunarity = md.p[1], n.gain = md.p[2], n.amplitude = md.p[3], n.bias = md.p[4];
-    n.ramp_scale = md.p[5], n.ramp_center = md.p[6], n.ridge_offset = md.p[7];
-    n.octaves = noise_octaves(md);
-    n.lx = a.lx, n.ly = a.ly, n.lz = a.lz, n.dx = a.dx, n.dy = a.dy, n.dz = a.dz;
-    n.event = a.event;
-    density_permutation((uint64_t)(uint32_t)md.data_dims[0], n.perm);  // the C# int _seed
-    return n;
+    if (md.kind == VTMC_MOD_HEIGHTMAP && (!md.data || md.data_dims[0] < 1 || md.data_dims[1] < 1))
+        return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: heightmap data / dims missing", i);
+    return VTMC_OK;
 }
 
-using NoiseKernel = void (*)(float *, float *, TerrainShape, TerrainNoiseArgs);
-static NoiseKernel noise_kernel(bool journal, int basis)
+static int apply_reference(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &args, float *grid, float *image)
 {
-    static const NoiseKernel k[2][3] = {{terrain_noise_kernel<false, 0>, terrain_noise_kernel<false, 1>, terrain_noise_kernel<false, 2>},
-                                        {terrain_noise_kernel<true, 0>, terrain_noise_kernel<true, 1>, terrain_noise_kernel<true, 2>}};
-    return k[journal][basis];
+    TerrainModifierArgs a = args;
+    if (md.kind == VTMC_MOD_HEIGHTMAP) {  // _heightmap (IslandModifier.cs:36) goes to the device
+        if (int rc = stage_for_queue(ctx, ctx->heightmap, md.data, sizeof(float) * (size_t)md.data_dims[0] * (size_t)md.data_dims[1])) return rc;
+        a.data = (const float *)ctx->heightmap.p;
+        a.dims0 = md.data_dims[0];
+        a.dims1 = md.data_dims[1];
+    }
+    VTMC_HIP(ctx, launch_box(image ? terrain_modify_kernel<true> : terrain_modify_kernel<false>, box_of(a), ctx->stream, grid, image, ctx->tshape, a));
+    return VTMC_OK;
+}
+
+// every kind of vtmc_modifier (terrain_edit.h)
+static const ModifierKind kModifierKinds[] = {
+    {VTMC_MOD_PLANE, check_reference, apply_reference},
+    {VTMC_MOD_SPHERE, check_reference, apply_reference},
+    {VTMC_MOD_CYLINDER, check_reference, apply_reference},
+    {VTMC_MOD_HEIGHTMAP, check_reference, apply_reference},
+    {VTMC_MOD_SMOOTH, check_brush, apply_smooth},
+    {VTMC_MOD_FLATTEN, check_brush, apply_flatten},
+    {VTMC_MOD_NOISE, check_noise, apply_noise},
+    {VTMC_MOD_STAMP, check_stamp, apply_stamp},
+    {VTMC_MOD_PATH, check_path, apply_path},
+};
+
+const ModifierKind *find_modifier_kind(int32_t kind)
+{
+    for (const ModifierKind &k : kModifierKinds)
+        if (k.kind == kind) return &k;
+    return nullptr;
 }
 
 static int check_modifier(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i)
 {
-    if ((md.kind < VTMC_MOD_PLANE || md.kind > VTMC_MOD_FLATTEN) && md.kind != VTMC_MOD_NOISE && md.kind != VTMC_MOD_STAMP && md.kind != VTMC_MOD_PATH)
-        return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: unknown kind %d", i, md.kind);
-    if (md.kind == VTMC_MOD_STAMP) return check_stamp_modifier(ctx, md, i);
-    if (md.kind == VTMC_MOD_PATH) return check_path_modifier(ctx, md, i);
-    if (md.kind == VTMC_MOD_NOISE) {
-        for (int k = 0; k < 8; ++k)
-            if (!std::isfinite(md.p[k])) return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: noise parameter p[%d] not finite", i, k);
-        const int octaves = noise_octaves(md), basis = noise_basis(md);
-        if (octaves < 1 || octaves > 16) return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: noise octaves %d not in 1..16", i, octaves);
-        if (basis < 0 || basis > 2) return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: noise basis %d not in 0..2", i, basis);
-        const double reach = noise_lattice_reach(ctx->tshape, md);
-        if (!(reach < 16777216.0))
-            return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: noise lattice coordinates reach %g in its box (limit 2^24)", i, reach);
-    }
-    if (md.kind == VTMC_MOD_HEIGHTMAP && (!md.data || md.data_dims[0] < 1 || md.data_dims[1] < 1))
-        return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: heightmap data / dims missing", i);
-    if (md.kind == VTMC_MOD_SMOOTH || md.kind == VTMC_MOD_FLATTEN) {
-        const float *p = md.p;
-        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]))
-            return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: brush centre not finite", i);
-        if (!std::isfinite(p[3]) || !(p[3] > 0.0f)) return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: brush radius %g not finite and > 0", i, p[3]);
-        if (!std::isfinite(p[4]) || !(p[4] >= 0.0f && p[4] <= 1.0f))
-            return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: brush strength %g not in [0, 1]", i, p[4]);
-        if (md.kind == VTMC_MOD_FLATTEN &&
-            (!std::isfinite(p[5]) || !std::isfinite(p[6]) || !std::isfinite(p[7]) || p[5] * p[5] + p[6] * p[6] + p[7] * p[7] == 0.0f))
-            return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: flatten normal not finite or zero", i);
-    }
-    return VTMC_OK;
+    const ModifierKind *k = find_modifier_kind(md.kind);
+    return k ? k->check(ctx, md, i) : fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: unknown kind %d", i, md.kind);
 }
 
 // _nextUpdateblocks (VoxelTerrain.cs:321) from the marks, ordered by block id (a full rebuild needs no list), then BatchUpdate
@@ -748,43 +470,9 @@ int32_t vtmc_terrain_update(vtmc_ctx *ctx, const vtmc_modifier *mods, int32_t n_
         int low[3], up[3];
         TerrainModifierArgs a = sample_range(sh, md, low, up);
         a.event = ++ctx->terrain_events;
-        const TerrainBox b = box_of(a);
-        if (md.kind == VTMC_MOD_HEIGHTMAP && !box_empty(b)) {
-            // _heightmap (IslandModifier.cs:36) goes to the device; an earlier modifier of this queue may
-            // still be reading the previous one, hence the drain before the buffer is touched
-            const size_t bytes = sizeof(float) * (size_t)md.data_dims[0] * (size_t)md.data_dims[1];
-            VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (int rc = ensure(ctx, ctx->heightmap, bytes)) return rc;
-            VTMC_HIP(ctx, hipMemcpy(ctx->heightmap.p, md.data, bytes, hipMemcpyHostToDevice));
-            a.data = (const float *)ctx->heightmap.p;
-            a.dims0 = md.data_dims[0];
-            a.dims1 = md.data_dims[1];
-        }
-        if (!box_empty(b)) {
-            float *grid = (float *)ctx->terrain.p, *image = journaled ? (float *)((char *)ctx->journal.p + step.boxes[i].off) : nullptr;
-            if (md.kind == VTMC_MOD_SMOOTH) {
-                const TerrainBox h = smooth_stage_box(sh, a);
-                const size_t bytes = sizeof(float) * (size_t)h.dx * (size_t)h.dy * (size_t)h.dz;
-                if (ctx->brush.bytes < bytes) {  // an earlier smooth of this queue may still be reading the stage
-                    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    if (int rc = ensure(ctx, ctx->brush, bytes)) return rc;
-                }
-                // h contains b (sample_range clips b to the grid, smooth_stage_box only grows it), so a box too large to launch fails
-                // here, before anything is written
-                float *stage = (float *)ctx->brush.p;
-                VTMC_HIP(ctx, launch_box(terrain_stage_kernel, h, ctx->stream, grid, stage, sh, h));
-                VTMC_HIP(ctx, launch_box(image ? terrain_smooth_kernel<true> : terrain_smooth_kernel<false>, b, ctx->stream, grid, image, stage, sh, a, h));
-            } else if (md.kind == VTMC_MOD_FLATTEN) {
-                VTMC_HIP(ctx, launch_box(image ? terrain_flatten_kernel<true> : terrain_flatten_kernel<false>, b, ctx->stream, grid, image, sh, a));
-            } else if (md.kind == VTMC_MOD_NOISE) {
-                VTMC_HIP(ctx, launch_box(noise_kernel(image != nullptr, noise_basis(md)), b, ctx->stream, grid, image, sh, noise_args(md, a)));
-            } else if (md.kind == VTMC_MOD_STAMP) {
-                VTMC_HIP(ctx, launch_stamp_paste(ctx, md, a, grid, image, ctx->stream));
-            } else if (md.kind == VTMC_MOD_PATH) {  // stages its segments in the context's buffer, as the heightmap above
-                if (int rc = launch_path(ctx, md, a, grid, image, ctx->stream)) return rc;
-            } else {  // the reference's modifiers, kinds 0-3
-                VTMC_HIP(ctx, launch_box(image ? terrain_modify_kernel<true> : terrain_modify_kernel<false>, b, ctx->stream, grid, image, sh, a));
-            }
+        if (!box_empty(box_of(a))) {
+            float *image = journaled ? (float *)((char *)ctx->journal.p + step.boxes[i].off) : nullptr;
+            if (int rc = find_modifier_kind(md.kind)->apply(ctx, md, a, (float *)ctx->terrain.p, image)) return rc;
         }
         if (n_marked < mark.size()) n_marked += mark_dirty_blocks(low, up, nb, mark);
     }

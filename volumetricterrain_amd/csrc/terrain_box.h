@@ -1,6 +1,6 @@
-// terrain_box.h -- the box walk and the clamp draws every edit kernel of the resident terrain shares (terrain.hip, terrain_stamp.hip): a
-// thread's place in a modifier's sample box, the grid and image indices, Mathf.Clamp against the drawn void / full values, and the one launch
-// of a box kernel.
+// terrain_box.h -- the box walk and the clamp draws every edit kernel of the resident terrain shares: a thread's place in a modifier's
+// sample box, the grid and image indices, Mathf.Clamp against the drawn void / full values, the CSG write rule, and the one launch of a
+// box kernel.
 #ifndef VTMC_TERRAIN_BOX_H
 #define VTMC_TERRAIN_BOX_H
 #include "vtmc_ctx.h"
@@ -21,6 +21,14 @@ __device__ __forceinline__ float clamp_drawn(float v, uint64_t seed, uint32_t ev
         if (v > hi) v = hi;
     }
     return v;
+}
+
+// what a sample s becomes under the clamped density md: Mathf.Max(S, md) (add) or Clamp(Min(S, -md), void, full) (erode)
+__device__ __forceinline__ float csg_combine(const TerrainShape &sh, uint32_t event, uint64_t sample, int add_or_erode, float md, float s)
+{
+    if (add_or_erode) return s > md ? s : md;
+    const float minus_md = -md;
+    return clamp_drawn(s < minus_md ? s : minus_md, sh.seed, event, sample, 2u);
 }
 
 constexpr int kYRun = 16;  // samples along y per thread

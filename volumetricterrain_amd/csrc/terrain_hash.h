@@ -1,5 +1,5 @@
 // terrain_hash.h -- the counter hash behind voidDensity / fullDensity (terrain.hip's header comment): a pure function of (seed, event,
-// sample index, draw index), shared by the edit kernels (terrain.hip) and the redraw of elided bricks on load (terrain_io.hip).  The CPU
+// sample index, draw index), shared by the edit kernels (terrain_box.h) and the redraw of elided bricks on load (terrain_io.hip).  The CPU
 // oracle (oracle/terrain_ref.c) and volumetricterrain_amd/terrainfile.py restate it.
 #ifndef VTMC_TERRAIN_HASH_H
 #define VTMC_TERRAIN_HASH_H

@@ -12,7 +12,7 @@
 //
 // Pruning is exact, not approximate: a segment whose f stays below -2 on every sample of a tile cannot change md there, since any
 // q < -2 -- the initial -inf included -- clamps to the same drawn void value.  A tile with no surviving segment still writes.
-#include "terrain_box.h"
+#include "terrain_edit.h"
 #include "terrain_path.h"
 #include <algorithm>
 #include <cmath>
@@ -132,18 +132,11 @@ __global__ __launch_bounds__(256) void terrain_path_kernel(float *__restrict__ g
             const uint64_t sample = s0 + (uint64_t)sh.dim_x * k;
             if (kJournal) image[j0 + (uint64_t)m.dx * k] = old[k];
             const float md = clamp_drawn(q[k], sh.seed, m.event, sample, 0u);
-            float r;
-            if (m.add_or_erode) {
-                r = old[k] > md ? old[k] : md;  // Mathf.Max(S, md)
-            } else {
-                const float minus_md = -md;
-                r = clamp_drawn(old[k] < minus_md ? old[k] : minus_md, sh.seed, m.event, sample, 2u);  // Clamp(Min(S, -md), void, full)
-            }
-            grid[sample] = r;
+            grid[sample] = csg_combine(sh, m.event, sample, m.add_or_erode, md, old[k]);
         }
 }
 
-int check_path_modifier(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i)
+int check_path(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i)
 {
     if (!md.data) return fail(ctx, VTMC_ERR_INVALID_ARG, "modifier %d: path data is null", i);
     const int n = md.data_dims[0];
@@ -193,14 +186,11 @@ static std::vector<float> path_records(const TerrainShape &sh, const vtmc_modifi
     return rec;
 }
 
-int launch_path(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &a, float *grid, float *image, hipStream_t stream)
+int apply_path(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &a, float *grid, float *image)
 {
     const std::vector<float> rec = path_records(ctx->tshape, md);
     const int n = md.data_dims[0];
-    // an earlier path modifier of this queue may still be reading the buffer (the heightmap's hazard, terrain.hip): drain before it is touched
-    VTMC_HIP(ctx, hipStreamSynchronize(stream));
-    if (int rc = ensure(ctx, ctx->path, rec.size() * sizeof(float))) return rc;
-    VTMC_HIP(ctx, hipMemcpy(ctx->path.p, rec.data(), rec.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = stage_for_queue(ctx, ctx->path, rec.data(), rec.size() * sizeof(float))) return rc;
     TerrainPathArgs p{};
     p.seg = (const float4 *)ctx->path.p;
     p.bound = p.seg + (size_t)2 * n;
@@ -209,8 +199,7 @@ int launch_path(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArg
     p.add_or_erode = a.add_or_erode;
     p.lx = a.lx, p.ly = a.ly, p.lz = a.lz, p.dx = a.dx, p.dy = a.dy, p.dz = a.dz;
     p.event = a.event;
-    VTMC_HIP(ctx, launch_box(image ? terrain_path_kernel<true> : terrain_path_kernel<false>, TerrainBox{a.lx, a.ly, a.lz, a.dx, a.dy, a.dz}, stream, grid, image,
-                             ctx->tshape, p));
+    VTMC_HIP(ctx, launch_box(image ? terrain_path_kernel<true> : terrain_path_kernel<false>, box_of(a), ctx->stream, grid, image, ctx->tshape, p));
     return VTMC_OK;
 }
 

@@ -8,7 +8,7 @@
 // stamp samples, reads the grid sample and writes it: the 8 reads are gathers whose coalescing depends on the rotation (with the identity a
 // wave reads rows of the stamp, x fastest in both), served by L2 for stamps of the sizes an editor pastes (64^3 is 1 MB).  Plain global
 // loads, no LDS stage: a workgroup's footprint in the stamp under a free rotation is a slanted slab, not a tile (profiles/r13/stamp).
-#include "terrain_box.h"
+#include "terrain_edit.h"
 #include "terrain_stamp.h"
 #include <cmath>
 #include <vector>
@@ -90,12 +90,7 @@ __global__ __launch_bounds__(256) void terrain_stamp_kernel(float *__restrict__ 
             r = fabsf(q) <= 2.0f ? q : clamp_drawn(q, sh.seed, m.event, sample, 0u);
         } else {
             const float md = clamp_drawn(q, sh.seed, m.event, sample, 0u);
-            if (kMode == kStampAdd) {
-                r = old > md ? old : md;  // Mathf.Max(S, md)
-            } else {
-                const float minus_md = -md;
-                r = clamp_drawn(old < minus_md ? old : minus_md, sh.seed, m.event, sample, 2u);  // Clamp(Min(S, -md), void, full)
-            }
+            r = csg_combine(sh, m.event, sample, kMode == kStampAdd, md, old);
         }
         grid[sample] = r;
     }
@@ -136,7 +131,7 @@ static void stamp_map(const float p[8], const VtmcStamp &st, TerrainStampArgs &a
     }
 }
 
-int check_stamp_modifier(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i)
+int check_stamp(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i)
 {
     const float *p = md.p;
     for (int k = 0; k < 8; ++k)
@@ -149,10 +144,10 @@ int check_stamp_modifier(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i)
     return VTMC_OK;
 }
 
-hipError_t launch_stamp_paste(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &a, float *grid, float *image, hipStream_t stream)
+int apply_stamp(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &a, float *grid, float *image)
 {
     const VtmcStamp *st = find_stamp(ctx, md.data_dims[0]);
-    if (!st) return hipErrorInvalidValue;  // check_stamp_modifier has run: not reached
+    if (!st) return fail(ctx, VTMC_ERR_INVALID_ARG, "unknown stamp id %d", md.data_dims[0]);  // check_stamp has run: not reached
     TerrainStampArgs s{};
     s.s = (const float *)st->samples.p;
     s.nx = st->nx, s.ny = st->ny, s.nz = st->nz;
@@ -160,7 +155,8 @@ hipError_t launch_stamp_paste(vtmc_ctx *ctx, const vtmc_modifier &md, const Terr
     s.lx = a.lx, s.ly = a.ly, s.lz = a.lz, s.dx = a.dx, s.dy = a.dy, s.dz = a.dz;
     s.event = a.event;
     const int mode = md.data_dims[1] == 1 ? kStampReplace : (a.add_or_erode ? kStampAdd : kStampErode);
-    return launch_box(stamp_kernel(image != nullptr, mode), TerrainBox{a.lx, a.ly, a.lz, a.dx, a.dy, a.dz}, stream, grid, image, ctx->tshape, s);
+    VTMC_HIP(ctx, launch_box(stamp_kernel(image != nullptr, mode), box_of(a), ctx->stream, grid, image, ctx->tshape, s));
+    return VTMC_OK;
 }
 
 int check_stamp_dims(vtmc_ctx *ctx, int32_t nx, int32_t ny, int32_t nz)

@@ -1,5 +1,5 @@
 // vtmc_ctx.h -- the context object behind include/vtmc.h and the small host helpers every translation unit of the C-ABI layer shares
-// (context.hip, vtmc_api.hip, terrain.hip, terrain_stamp.hip, stamp_mesh.hip, terrain_path.hip, terrain_material.hip, terrain_ao.hip, terrain_lod.hip, terrain_io.hip, density.hip, chunk_io.hip, comm.hip, raycast.hip, spherequery.hip).  Not installed.
+// (every .hip file but the two of extract kernels).  Not installed.
 #ifndef VTMC_CTX_H
 #define VTMC_CTX_H
 #include "../../include/vtmc.h"
@@ -135,7 +135,7 @@ struct vtmc_ctx {
     VtmcDevBuf journal;
     std::deque<VtmcHistoryStep> hist;
     size_t hist_done = 0;
-    // terrain.hip: the stage of a VTMC_MOD_SMOOTH brush (its box plus a one-sample halo, before the brush), grow-only; grown only after
+    // terrain_brush.hip: the stage of a VTMC_MOD_SMOOTH brush (its box plus a one-sample halo, before the brush), grow-only; grown only after
     // the stream has drained, since an earlier smooth of the same queue may still be reading it
     VtmcDevBuf brush;
     // terrain_stamp.hip: the stamps by id; ids count up from 1 and are never reused.  No part of the terrain: vtmc_terrain_init / _load and the
