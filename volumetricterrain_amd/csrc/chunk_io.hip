@@ -104,10 +104,10 @@ int32_t vtmc_chunk_write(vtmc_ctx *ctx, const char *path, int32_t volume, const 
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
     if (!path || !origin) return fail(ctx, VTMC_ERR_INVALID_ARG, "path or origin is null");
-    if (!ctx->has_result) return fail(ctx, VTMC_ERR_NO_RESULT, "chunk_write before any extract");
-    const BlockSpace &sp = ctx->last_space;
-    if (sp.list || ctx->last_volumes <= 0) return fail(ctx, VTMC_ERR_NO_RESULT, "chunk_write needs an extract over whole volumes (not a block list)");
-    if (volume < 0 || volume >= ctx->last_volumes) return fail(ctx, VTMC_ERR_INVALID_ARG, "volume %d outside [0,%d)", volume, ctx->last_volumes);
+    if (!ctx->result.valid) return fail(ctx, VTMC_ERR_NO_RESULT, "chunk_write before any extract");
+    const BlockSpace &sp = ctx->result.space;
+    if (sp.list || ctx->result.volumes <= 0) return fail(ctx, VTMC_ERR_NO_RESULT, "chunk_write needs an extract over whole volumes (not a block list)");
+    if (volume < 0 || volume >= ctx->result.volumes) return fail(ctx, VTMC_ERR_INVALID_ARG, "volume %d outside [0,%d)", volume, ctx->result.volumes);
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const int bpv = sp.bpv;
@@ -116,7 +116,7 @@ int32_t vtmc_chunk_write(vtmc_ctx *ctx, const char *path, int32_t volume, const 
     uint32_t span[4] = {0, 0, 0, 0};
     VTMC_HIP(ctx, hipMemcpyAsync(&span[0], (const uint32_t *)ctx->offsets.p + b0, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     VTMC_HIP(ctx, hipMemcpyAsync(&span[1], (const uint32_t *)ctx->offsets.p + b0 + bpv, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (ctx->last_indexed) {
+    if (ctx->result.indexed) {
         VTMC_HIP(ctx, hipMemcpyAsync(&span[2], (const uint32_t *)ctx->voffsets.p + b0, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         VTMC_HIP(ctx, hipMemcpyAsync(&span[3], (const uint32_t *)ctx->voffsets.p + b0 + bpv, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
@@ -125,14 +125,14 @@ int32_t vtmc_chunk_write(vtmc_ctx *ctx, const char *path, int32_t volume, const 
     ChunkHeader h{};
     memcpy(h.magic, "VTCHUNK1", 8);
     h.version = 1;
-    h.flags = (with_samples ? kFlagSamples : 0u) | (ctx->last_indexed ? kFlagIndexed : kFlagSoup);
+    h.flags = (with_samples ? kFlagSamples : 0u) | (ctx->result.indexed ? kFlagIndexed : kFlagSoup);
     for (int k = 0; k < 3; ++k) h.origin[k] = origin[k];
     h.cells[0] = sp.nbx * 8;
     h.cells[1] = sp.nby * 8;
     h.cells[2] = sp.nbz * 8;
     h.n_blocks = (uint32_t)bpv;
     h.n_triangles = span[1] - span[0];
-    h.n_vertices = ctx->last_indexed ? span[3] - span[2] : 0u;
+    h.n_vertices = ctx->result.indexed ? span[3] - span[2] : 0u;
     const ChunkLayout l = layout_of(h);
     if (int rc = ensure(ctx, ctx->chunk_image, l.total)) return rc;
     char *img = (char *)ctx->chunk_image.p;
@@ -147,7 +147,7 @@ int32_t vtmc_chunk_write(vtmc_ctx *ctx, const char *path, int32_t volume, const 
     }
     hipLaunchKernelGGL(pack_offsets_kernel, dim3(grid_for(bpv + 1)), dim3(256), 0, st, (const uint32_t *)ctx->offsets.p + b0, bpv + 1,
                        (uint32_t *)(img + l.tri_offsets));
-    if (ctx->last_indexed) {
+    if (ctx->result.indexed) {
         hipLaunchKernelGGL(pack_offsets_kernel, dim3(grid_for(bpv + 1)), dim3(256), 0, st, (const uint32_t *)ctx->voffsets.p + b0, bpv + 1,
                            (uint32_t *)(img + l.vert_offsets));
         if (h.n_vertices)

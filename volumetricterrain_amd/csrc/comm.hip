@@ -210,9 +210,9 @@ int32_t vtmc_allgather_volume_counts(vtmc_ctx *ctx, uint32_t *d_all_counts, int3
     if (!ctx->comm) return fail(ctx, VTMC_ERR_NO_RESULT, "allgather_volume_counts before vtmc_comm_init_rank");
     // the counts are final once the scan has run: valid for a finished extract and for a queued one
     // (vtmc_extract_volumes_device_async), which is how a rank keeps its host out of the step
-    if (!ctx->has_result && !ctx->pending.active) return fail(ctx, VTMC_ERR_NO_RESULT, "allgather_volume_counts before any extract");
-    const int n_vol = ctx->pending.active ? ctx->pending.n_volumes : ctx->last_volumes;
-    const int n_blk = ctx->pending.active ? ctx->pending.sp.n_blocks : ctx->last_blocks;
+    if (!ctx->result.valid && !ctx->pending.active) return fail(ctx, VTMC_ERR_NO_RESULT, "allgather_volume_counts before any extract");
+    const int n_vol = ctx->pending.active ? ctx->pending.n_volumes : ctx->result.volumes;
+    const int n_blk = ctx->pending.active ? ctx->pending.sp.n_blocks : ctx->result.blocks;
     if (!d_all_counts) return fail(ctx, VTMC_ERR_INVALID_ARG, "d_all_counts is null");
     if (volumes_per_rank < n_vol || volumes_per_rank <= 0)
         return fail(ctx, VTMC_ERR_CAPACITY, "volumes_per_rank %d < %d volumes of the last extract", volumes_per_rank, n_vol);

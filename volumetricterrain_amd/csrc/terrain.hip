@@ -315,9 +315,7 @@ static int extract_dirty(vtmc_ctx *ctx, const std::vector<uint8_t> &mark, size_t
         if (int rc = upload_block_list(ctx, ctx->dirty.data(), (int)n_marked, sp)) return rc;
         n_volumes = 0;
     }
-    const int rc = extract_core(ctx, sp, n_volumes, tri_count);
-    if (rc == VTMC_OK) ctx->terrain_result_epoch = ctx->result_epoch;   // this result's blocks are the dirty list's (terrain_material.hip)
-    return rc;
+    return extract_core(ctx, sp, n_volumes, ResultSource::TerrainDirty, tri_count);
 }
 
 void history_clear(vtmc_ctx *ctx)   // vtmc_ctx.h: terrain_io.hip clears the history too
@@ -416,7 +414,7 @@ int32_t vtmc_terrain_init(vtmc_ctx *ctx, int32_t width, int32_t elevation, int32
     if (!(voxel_scale > 0.0f)) return fail(ctx, VTMC_ERR_INVALID_ARG, "voxel_scale must be positive");
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     ctx->has_terrain = false;
-    ctx->has_result = false;
+    ctx->result.valid = false;
     history_clear(ctx);
     material_drop(ctx);
     TerrainShape sh{};

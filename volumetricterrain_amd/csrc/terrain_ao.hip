@@ -234,8 +234,6 @@ __global__ __launch_bounds__(256) void ao_kernel(const uint32_t *__restrict__ re
     }
 }
 
-static bool ao_current(const vtmc_ctx *ctx) { return ctx->has_result && ctx->ao_epoch != 0 && ctx->ao_epoch == ctx->result_epoch; }
-
 }  // namespace vtmc
 
 using namespace vtmc;
@@ -246,23 +244,21 @@ int32_t vtmc_ao_vertices(vtmc_ctx *ctx, const vtmc_ao_params *params, int64_t *n
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
     if (!params) return fail(ctx, VTMC_ERR_INVALID_ARG, "params is null");
-    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "ao_vertices before terrain_init");
-    if (!ctx->has_result) return fail(ctx, VTMC_ERR_NO_RESULT, "ao_vertices before any extract");
-    if (ctx->terrain_result_epoch != ctx->result_epoch)
-        return fail(ctx, VTMC_ERR_NO_RESULT, "ao_vertices: the last result did not come from the resident terrain");
+    if (int rc = attr_gate(ctx, "ao_vertices")) return rc;
     if (const char *fault = ao_params_fault(*params, ctx->tshape.scale)) return fail(ctx, VTMC_ERR_INVALID_ARG, "ao_vertices: %s", fault);
-    const int64_t n = ctx->last_indexed ? ctx->last_verts : 3 * ctx->last_tris;
+    const VtmcResult &res = ctx->result;
+    const int64_t n = res.vertices();
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = ensure(ctx, ctx->ao_stats, 2 * sizeof(uint32_t))) return rc;
     VTMC_HIP(ctx, hipMemsetAsync(ctx->ao_stats.p, 0, 2 * sizeof(uint32_t), ctx->stream));
-    if (n > 0 && ctx->last_active > 0) {
-        if (int rc = ensure(ctx, ctx->ao_values, ((size_t)n + 3) & ~(size_t)3)) return rc;
+    if (n > 0 && res.active > 0) {
+        if (int rc = ensure(ctx, ctx->ao.values, ((size_t)n + 3) & ~(size_t)3)) return rc;
         const AoTables tb = ao_tables(*params, ctx->tshape.scale);
         AoArgs a{};
         a.grid = (const float *)ctx->terrain.p;
         a.n[0] = ctx->tshape.dim_x, a.n[1] = ctx->tshape.dim_y, a.n[2] = ctx->tshape.dim_z;
         a.active = (const BlockDesc *)ctx->active.p;
-        const BlockSpace &sp = ctx->last_space;
+        const BlockSpace &sp = res.space;
         a.list = sp.list;
         a.nbx = sp.nbx, a.nby = sp.nby;
         a.d_nbx = sp.d_nbx, a.d_nby = sp.d_nby;
@@ -276,18 +272,18 @@ int32_t vtmc_ao_vertices(vtmc_ctx *ctx, const vtmc_ao_params *params, int64_t *n
         }
         a.direct_max = (uint32_t)(ctx->ao_direct_max >= 0 ? ctx->ao_direct_max : kAoDirectMax);
         a.stats = (uint32_t *)ctx->ao_stats.p;
-        a.out = (uint8_t *)ctx->ao_values.p;
+        a.out = (uint8_t *)ctx->ao.values.p;
         const size_t lds = ao_tile_bytes(tb.extent);
         launch_begin();
-        if (ctx->last_indexed)
-            hipLaunchKernelGGL(ao_kernel<true>, dim3(ctx->last_active), dim3(256), lds, ctx->stream, (const uint32_t *)ctx->verts.p, a);
+        if (res.indexed)
+            hipLaunchKernelGGL(ao_kernel<true>, dim3(res.active), dim3(256), lds, ctx->stream, (const uint32_t *)ctx->verts.p, a);
         else
-            hipLaunchKernelGGL(ao_kernel<false>, dim3(ctx->last_active), dim3(256), lds, ctx->stream, (const uint32_t *)ctx->tris.p, a);
+            hipLaunchKernelGGL(ao_kernel<false>, dim3(res.active), dim3(256), lds, ctx->stream, (const uint32_t *)ctx->tris.p, a);
         VTMC_HIP(ctx, launch_end());
     }
     VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->ao_vertices = n;
-    ctx->ao_epoch = ctx->result_epoch;
+    ctx->ao.n = n;
+    ctx->ao.epoch = res.epoch;
     if (n_vertices) *n_vertices = n;
     return VTMC_OK;
 }
@@ -295,23 +291,13 @@ int32_t vtmc_ao_vertices(vtmc_ctx *ctx, const vtmc_ao_params *params, int64_t *n
 int32_t vtmc_ao_read_vertices(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity_vertices)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ao_current(ctx)) return fail(ctx, VTMC_ERR_NO_RESULT, "ao_read_vertices: no occlusion values of the current result (call vtmc_ao_vertices)");
-    if (capacity_vertices < ctx->ao_vertices)
-        return fail(ctx, VTMC_ERR_INVALID_ARG, "capacity %lld < %lld vertices", (long long)capacity_vertices, (long long)ctx->ao_vertices);
-    if (ctx->ao_vertices == 0) return VTMC_OK;
-    if (!dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "dst is null");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    VTMC_HIP(ctx, hipMemcpy(dst, ctx->ao_values.p, (size_t)ctx->ao_vertices, hipMemcpyDeviceToHost));
-    return VTMC_OK;
+    return attr_read(ctx, ctx->ao, "ao_read_vertices: no occlusion values of the current result (call vtmc_ao_vertices)", 1, dst, capacity_vertices);
 }
 
 int32_t vtmc_ao_device_results(vtmc_ctx *ctx, const uint8_t **d_ao, int64_t *n_vertices)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ao_current(ctx)) return fail(ctx, VTMC_ERR_NO_RESULT, "ao_device_results: no occlusion values of the current result (call vtmc_ao_vertices)");
-    if (d_ao) *d_ao = (const uint8_t *)ctx->ao_values.p;
-    if (n_vertices) *n_vertices = ctx->ao_vertices;
-    return VTMC_OK;
+    return attr_device_results(ctx, ctx->ao, "ao_device_results: no occlusion values of the current result (call vtmc_ao_vertices)", d_ao, n_vertices);
 }
 
 // Not part of the ABI (tests, tools/ao_bench.py): counts[0] = workgroups of the last vtmc_ao_vertices that staged a tile, counts[1] = those

@@ -486,7 +486,7 @@ int32_t vtmc_terrain_load(vtmc_ctx *ctx, const char *path, uint32_t flags, int32
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->has_terrain = false;
-    ctx->has_result = false;
+    ctx->result.valid = false;
     history_clear(ctx);
     material_drop(ctx);
     ctx->dirty.clear();

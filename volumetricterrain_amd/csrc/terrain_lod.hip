@@ -51,7 +51,7 @@ __global__ __launch_bounds__(kLodThreads) void lod_gather_kernel(const float *__
     }
 }
 
-static bool lod_current(const vtmc_ctx *ctx) { return ctx->has_result && ctx->lod_epoch != 0 && ctx->lod_epoch == ctx->result_epoch; }
+static bool lod_current(const vtmc_ctx *ctx) { return ctx->result.valid && ctx->result.source == ResultSource::TerrainLod; }
 
 }  // namespace vtmc
 
@@ -80,7 +80,7 @@ int32_t vtmc_terrain_extract_lod(vtmc_ctx *ctx, const vtmc_lod_params *params, i
     }
     const size_t n = nodes.size();
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->has_result = false;   // from here on the tiles of an earlier level-of-detail result are overwritten
+    ctx->result.valid = false;   // from here on the tiles of an earlier level-of-detail result are overwritten
     if (int rc = ensure(ctx, ctx->lod_nodes_dev, n * sizeof(vtmc_lod_node))) return rc;
     if (int rc = ensure(ctx, ctx->lod_tiles, n * VTMC_TILE_SAMPLES * sizeof(float))) return rc;
     int rc = VTMC_OK;
@@ -99,15 +99,13 @@ int32_t vtmc_terrain_extract_lod(vtmc_ctx *ctx, const vtmc_lod_params *params, i
     if (rc == VTMC_OK) {
         // the tile buffer is a batch of n volumes of one 8^3 block each, as vtmc_extract_blocks submits it
         const BlockSpace sp = dense_space((const float *)ctx->lod_tiles.p, 8, 8, 8, 1, 10, 100, (int)n, VTMC_TILE_SAMPLES);
-        rc = extract_core(ctx, sp, 0, tri_count);
+        rc = extract_core(ctx, sp, 0, ResultSource::TerrainLod, tri_count);
     }
     if (rc) {   // `nodes` is only borrowed by the upload: a failure must not return while the copy may still read it
         quiet(hipStreamSynchronize(ctx->stream));
         return rc;
     }
-    // terrain_result_epoch stays behind: this result's blocks are nodes, not the dirty list's (terrain_material.hip, terrain_ao.hip)
     ctx->lod_nodes.swap(nodes);
-    ctx->lod_epoch = ctx->result_epoch;
     ctx->lod_timed = true;
     if (n_nodes) *n_nodes = (int32_t)n;
     return VTMC_OK;

@@ -206,8 +206,8 @@ __global__ __launch_bounds__(256) void material_paint_kernel(uint2 *__restrict__
 void material_drop(vtmc_ctx *ctx)
 {
     ctx->mat_c = 0;
-    ctx->mat_vertices = 0;
-    ctx->mat_weights_epoch = 0;
+    ctx->mat_weights.n = 0;
+    ctx->mat_weights.epoch = 0;
     release(ctx->material);
     release(ctx->mat_image);
 }
@@ -224,8 +224,6 @@ static void terrain_cells(const vtmc_ctx *ctx, int cells[3])
 {
     cells[0] = ctx->tshape.dim_x - 2, cells[1] = ctx->tshape.dim_y - 2, cells[2] = ctx->tshape.dim_z - 2;
 }
-
-static bool weights_current(const vtmc_ctx *ctx) { return ctx->mat_c && ctx->has_result && ctx->mat_weights_epoch == ctx->result_epoch; }
 
 }  // namespace vtmc
 
@@ -334,39 +332,38 @@ int32_t vtmc_material_vertices(vtmc_ctx *ctx, int64_t *n_vertices)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
     if (int rc = need_layer(ctx, "material_vertices")) return rc;
-    if (!ctx->has_result) return fail(ctx, VTMC_ERR_NO_RESULT, "material_vertices before any extract");
-    if (!ctx->has_terrain || ctx->terrain_result_epoch != ctx->result_epoch)
-        return fail(ctx, VTMC_ERR_NO_RESULT, "material_vertices: the last result did not come from the resident terrain");
-    const int64_t n = ctx->last_indexed ? ctx->last_verts : 3 * ctx->last_tris;
+    if (int rc = attr_gate(ctx, "material_vertices")) return rc;
+    const VtmcResult &res = ctx->result;
+    const int64_t n = res.vertices();
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     if (n > 0) {
-        if (int rc = ensure(ctx, ctx->mat_weights, (size_t)n * VTMC_MATERIAL_CHANNELS)) return rc;
+        if (int rc = ensure(ctx, ctx->mat_weights.values, (size_t)n * VTMC_MATERIAL_CHANNELS)) return rc;
         MaterialVertexArgs a{};
         int cells[3];
         terrain_cells(ctx, cells);
         a.layer = (const uint2 *)ctx->material.p;
         a.C = ctx->mat_c;
         material_vertex_scale(cells, a.C, a.s);
-        const BlockSpace &sp = ctx->last_space;
+        const BlockSpace &sp = res.space;
         a.list = sp.list;
-        a.n_blocks = (uint32_t)ctx->last_blocks;
+        a.n_blocks = (uint32_t)res.blocks;
         a.nbx = sp.nbx, a.nby = sp.nby;
         a.d_nbx = sp.d_nbx, a.d_nby = sp.d_nby;
         launch_begin();
-        if (ctx->last_indexed) {
-            const uint32_t V = (uint32_t)ctx->last_verts;
+        if (res.indexed) {
+            const uint32_t V = (uint32_t)res.verts;
             hipLaunchKernelGGL(material_indexed_kernel, dim3((V + kMatTile - 1) / kMatTile), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->verts.p, V,
-                               (const uint32_t *)ctx->voffsets.p, (uint2 *)ctx->mat_weights.p, a);
+                               (const uint32_t *)ctx->voffsets.p, (uint2 *)ctx->mat_weights.values.p, a);
         } else {
-            const uint32_t T = (uint32_t)ctx->last_tris;
+            const uint32_t T = (uint32_t)res.tris;
             hipLaunchKernelGGL(material_soup_kernel, dim3((T + kMatTile - 1) / kMatTile), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->tris.p, T,
-                               (uint2 *)ctx->mat_weights.p, a);
+                               (uint2 *)ctx->mat_weights.values.p, a);
         }
         VTMC_HIP(ctx, launch_end());
         VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    ctx->mat_vertices = n;
-    ctx->mat_weights_epoch = ctx->result_epoch;
+    ctx->mat_weights.n = n;
+    ctx->mat_weights.epoch = res.epoch;
     if (n_vertices) *n_vertices = n;
     return VTMC_OK;
 }
@@ -374,23 +371,15 @@ int32_t vtmc_material_vertices(vtmc_ctx *ctx, int64_t *n_vertices)
 int32_t vtmc_material_read_vertices(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity_vertices)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!weights_current(ctx)) return fail(ctx, VTMC_ERR_NO_RESULT, "material_read_vertices: no vertex weights of the current result (call vtmc_material_vertices)");
-    if (capacity_vertices < ctx->mat_vertices)
-        return fail(ctx, VTMC_ERR_INVALID_ARG, "capacity %lld < %lld vertices", (long long)capacity_vertices, (long long)ctx->mat_vertices);
-    if (ctx->mat_vertices == 0) return VTMC_OK;
-    if (!dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "dst is null");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    VTMC_HIP(ctx, hipMemcpy(dst, ctx->mat_weights.p, (size_t)ctx->mat_vertices * VTMC_MATERIAL_CHANNELS, hipMemcpyDeviceToHost));
-    return VTMC_OK;
+    return attr_read(ctx, ctx->mat_weights, "material_read_vertices: no vertex weights of the current result (call vtmc_material_vertices)",
+                     VTMC_MATERIAL_CHANNELS, dst, capacity_vertices);
 }
 
 int32_t vtmc_material_device_results(vtmc_ctx *ctx, const uint8_t **d_weights, int64_t *n_vertices)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!weights_current(ctx)) return fail(ctx, VTMC_ERR_NO_RESULT, "material_device_results: no vertex weights of the current result (call vtmc_material_vertices)");
-    if (d_weights) *d_weights = (const uint8_t *)ctx->mat_weights.p;
-    if (n_vertices) *n_vertices = ctx->mat_vertices;
-    return VTMC_OK;
+    return attr_device_results(ctx, ctx->mat_weights, "material_device_results: no vertex weights of the current result (call vtmc_material_vertices)",
+                               d_weights, n_vertices);
 }
 
 }  // extern "C"

@@ -54,16 +54,17 @@ int queue_emit(vtmc_ctx *ctx, bool retry)
 // Queues the device side of BatchUpdate (VoxelTerrain.cs:365-427) -- classify -> scan -> emit -- on
 // `stream` and returns without waiting: {T, nActive} (and V) stay in device memory, there is no
 // mid-pipeline read-back (VoxelTerrain.cs:394-395).  extract_finish() completes the call.
-int extract_queue(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, uint32_t flags, hipStream_t stream)
+int extract_queue(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, ResultSource source, uint32_t flags, hipStream_t stream)
 {
     const int B = sp.n_blocks;
     const bool indexed = ctx->output_mode == VTMC_OUTPUT_INDEXED;
-    ctx->has_result = false;
+    ctx->result.valid = false;
     ctx->pending = VtmcPending{};
     VtmcPending pe;
     pe.sp = sp;
     pe.n_volumes = n_volumes;
     pe.indexed = indexed;
+    pe.source = source;
     pe.stream = stream;
     if (B == 0) {  // the reference's early exit (VoxelTerrain.cs:396-405): empty offsets, nothing launched
         if (int rc = ensure(ctx, ctx->offsets, sizeof(uint32_t))) return rc;
@@ -297,15 +298,8 @@ int extract_finish(vtmc_ctx *ctx, int64_t *tri_count)
         if (int rc = record_stage_ms(ctx, placed)) return rc;
     }
     ctx->pending.active = false;
-    ctx->has_result = true;
-    ++ctx->result_epoch;
-    ctx->last_space = pe.sp;
-    ctx->last_blocks = pe.sp.n_blocks;
-    ctx->last_active = pe.launched ? ctx->h_totals.p[1] : 0u;   // the scan's count of non-empty blocks: the entries of `active`
-    ctx->last_volumes = pe.n_volumes;
-    ctx->last_tris = T_found;
-    ctx->last_verts = V_found;
-    ctx->last_indexed = pe.indexed;
+    const uint32_t n_active = pe.launched ? ctx->h_totals.p[1] : 0u;   // the scan's count of non-empty blocks: the entries of `active`
+    ctx->result = VtmcResult{true, ctx->result.epoch + 1, pe.source, pe.sp, pe.sp.n_blocks, n_active, pe.n_volumes, T_found, V_found, pe.indexed};
     if (tri_count) *tri_count = T_found;
     return VTMC_OK;
 }
@@ -324,7 +318,7 @@ int upload_grid(vtmc_ctx *ctx, const float *grid, int nx, int ny, int nz, int64_
 int copy_offsets(vtmc_ctx *ctx, int32_t *dst, const DevBuf &offsets)
 {
     if (!dst) return VTMC_OK;
-    if (ctx->last_blocks > 0) VTMC_HIP(ctx, hipMemcpy(dst, offsets.p, sizeof(uint32_t) * ((size_t)ctx->last_blocks + 1), hipMemcpyDeviceToHost));
+    if (ctx->result.blocks > 0) VTMC_HIP(ctx, hipMemcpy(dst, offsets.p, sizeof(uint32_t) * ((size_t)ctx->result.blocks + 1), hipMemcpyDeviceToHost));
     else dst[0] = 0;
     return VTMC_OK;
 }
@@ -382,12 +376,43 @@ const float *gather_tiles(vtmc_ctx *ctx, const float *grid, int64_t sx, int64_t 
 
 namespace vtmc {
 
-int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, int32_t *tri_count)
+int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, ResultSource source, int32_t *tri_count)
 {
     int64_t T = 0;
-    if (int rc = extract_queue(ctx, sp, n_volumes, 0, ctx->stream)) return rc;
+    if (int rc = extract_queue(ctx, sp, n_volumes, source, 0, ctx->stream)) return rc;
     if (int rc = extract_finish(ctx, &T)) return rc;
     if (tri_count) *tri_count = (int32_t)T;
+    return VTMC_OK;
+}
+
+int attr_gate(vtmc_ctx *ctx, const char *who)
+{
+    if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "%s before terrain_init", who);
+    if (!ctx->result.valid) return fail(ctx, VTMC_ERR_NO_RESULT, "%s before any extract", who);
+    if (ctx->result.source != ResultSource::TerrainDirty)
+        return fail(ctx, VTMC_ERR_NO_RESULT, "%s: the last result did not come from the resident terrain", who);
+    return VTMC_OK;
+}
+
+// an attribute is the current result's when it was computed at the epoch of a result that still stands (a standing result's epoch is >= 1)
+static bool attr_current(const vtmc_ctx *ctx, const VertexAttr &a) { return ctx->result.valid && a.epoch == ctx->result.epoch; }
+
+int attr_read(vtmc_ctx *ctx, const VertexAttr &a, const char *stale, size_t bytes_per_vertex, uint8_t *dst, int64_t capacity_vertices)
+{
+    if (!attr_current(ctx, a)) return fail(ctx, VTMC_ERR_NO_RESULT, "%s", stale);
+    if (capacity_vertices < a.n) return fail(ctx, VTMC_ERR_INVALID_ARG, "capacity %lld < %lld vertices", (long long)capacity_vertices, (long long)a.n);
+    if (a.n == 0) return VTMC_OK;
+    if (!dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "dst is null");
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    VTMC_HIP(ctx, hipMemcpy(dst, a.values.p, (size_t)a.n * bytes_per_vertex, hipMemcpyDeviceToHost));
+    return VTMC_OK;
+}
+
+int attr_device_results(vtmc_ctx *ctx, const VertexAttr &a, const char *stale, const uint8_t **d_values, int64_t *n_vertices)
+{
+    if (!attr_current(ctx, a)) return fail(ctx, VTMC_ERR_NO_RESULT, "%s", stale);
+    if (d_values) *d_values = (const uint8_t *)a.values.p;
+    if (n_vertices) *n_vertices = a.n;
     return VTMC_OK;
 }
 
@@ -450,7 +475,7 @@ int32_t vtmc_extract_blocks(vtmc_ctx *ctx, const float *samples, int32_t n_block
     }
     // the tile buffer is a batch of n_blocks volumes of one 8^3 block each
     BlockSpace sp = dense_space((const float *)ctx->input.p, 8, 8, 8, 1, 10, 100, n_blocks, VTMC_TILE_SAMPLES);
-    const int rc = extract_core(ctx, sp, 0, tri_count);
+    const int rc = extract_core(ctx, sp, 0, ResultSource::Caller, tri_count);
     // the caller's `samples` are only borrowed for this call: a failure behind the asynchronous upload must not return while the DMA still reads them
     if (rc && n_blocks > 0) quiet(hipStreamSynchronize(ctx->stream));
     return rc;
@@ -487,7 +512,7 @@ int32_t vtmc_extract_grid(vtmc_ctx *ctx, const float *grid, int32_t nx, int32_t 
     if (block_list)
         if (int rc = upload_block_list(ctx, block_list, n_blocks, sp)) return rc;
     sp.base = (const float *)ctx->input.p;
-    const int rc = extract_core(ctx, sp, block_list ? 0 : 1, tri_count);
+    const int rc = extract_core(ctx, sp, block_list ? 0 : 1, ResultSource::Caller, tri_count);
     if (rc) quiet(hipStreamSynchronize(ctx->stream));   // the uploads above borrow the caller's arrays: nothing of them is in flight when an error returns
     return rc;
 }
@@ -525,7 +550,7 @@ int32_t vtmc_extract_grid_sharded(vtmc_ctx *ctx, const float *grid, int32_t nx, 
     if (int rc = upload_block_list(ctx, list.data(), n_blocks, sp)) return rc;
     sp.bpv = bpc;  // chunk-major list: each local chunk is a contiguous run of bpc blocks
     int32_t T = 0;
-    if (int rc = extract_core(ctx, sp, n_local, &T)) return rc;
+    if (int rc = extract_core(ctx, sp, n_local, ResultSource::Caller, &T)) return rc;
     if (chunk_counts && n_local > 0 && n_blocks > 0)
         VTMC_HIP(ctx, hipMemcpy(chunk_counts, ctx->volcounts.p, sizeof(uint32_t) * 2 * (size_t)n_local, hipMemcpyDeviceToHost));
     if (tri_count) *tri_count = T;
@@ -543,8 +568,8 @@ int32_t vtmc_set_output_mode(vtmc_ctx *ctx, int32_t mode)
 int32_t vtmc_last_vertex_count(const vtmc_ctx *ctx, int32_t *vertex_count)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_result || !ctx->last_indexed) return VTMC_ERR_NO_RESULT;
-    if (vertex_count) *vertex_count = (int32_t)ctx->last_verts;
+    if (!ctx->result.valid || !ctx->result.indexed) return VTMC_ERR_NO_RESULT;
+    if (vertex_count) *vertex_count = (int32_t)ctx->result.verts;
     return VTMC_OK;
 }
 
@@ -552,14 +577,14 @@ int32_t vtmc_read_indexed_mesh(vtmc_ctx *ctx, vtmc_vertex *vertices, int64_t ver
                                int32_t *block_vertex_offsets, int32_t *block_tri_offsets)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_result || !ctx->last_indexed) return fail(ctx, VTMC_ERR_NO_RESULT, "read_indexed_mesh: the last extract did not run in indexed mode");
-    if (vertex_capacity < ctx->last_verts || tri_capacity < ctx->last_tris)
+    if (!ctx->result.valid || !ctx->result.indexed) return fail(ctx, VTMC_ERR_NO_RESULT, "read_indexed_mesh: the last extract did not run in indexed mode");
+    if (vertex_capacity < ctx->result.verts || tri_capacity < ctx->result.tris)
         return fail(ctx, VTMC_ERR_CAPACITY, "capacity (%lld vertices, %lld triangles) < (%lld, %lld)", (long long)vertex_capacity,
-                    (long long)tri_capacity, (long long)ctx->last_verts, (long long)ctx->last_tris);
-    if ((ctx->last_verts > 0 && !vertices) || (ctx->last_tris > 0 && !indices)) return fail(ctx, VTMC_ERR_INVALID_ARG, "destination is null");
+                    (long long)tri_capacity, (long long)ctx->result.verts, (long long)ctx->result.tris);
+    if ((ctx->result.verts > 0 && !vertices) || (ctx->result.tris > 0 && !indices)) return fail(ctx, VTMC_ERR_INVALID_ARG, "destination is null");
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->last_verts > 0) VTMC_HIP(ctx, hipMemcpy(vertices, ctx->verts.p, sizeof(vtmc_vertex) * (size_t)ctx->last_verts, hipMemcpyDeviceToHost));
-    if (ctx->last_tris > 0) VTMC_HIP(ctx, hipMemcpy(indices, ctx->indices.p, sizeof(int32_t) * 3 * (size_t)ctx->last_tris, hipMemcpyDeviceToHost));
+    if (ctx->result.verts > 0) VTMC_HIP(ctx, hipMemcpy(vertices, ctx->verts.p, sizeof(vtmc_vertex) * (size_t)ctx->result.verts, hipMemcpyDeviceToHost));
+    if (ctx->result.tris > 0) VTMC_HIP(ctx, hipMemcpy(indices, ctx->indices.p, sizeof(int32_t) * 3 * (size_t)ctx->result.tris, hipMemcpyDeviceToHost));
     if (int rc = copy_offsets(ctx, block_vertex_offsets, ctx->voffsets)) return rc;
     return copy_offsets(ctx, block_tri_offsets, ctx->offsets);
 }
@@ -568,7 +593,7 @@ int32_t vtmc_device_indexed_results(vtmc_ctx *ctx, const vtmc_vertex **d_vertice
                                     const uint32_t **d_block_vertex_offsets, const uint32_t **d_block_tri_offsets)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_result || !ctx->last_indexed) return fail(ctx, VTMC_ERR_NO_RESULT, "device_indexed_results: the last extract did not run in indexed mode");
+    if (!ctx->result.valid || !ctx->result.indexed) return fail(ctx, VTMC_ERR_NO_RESULT, "device_indexed_results: the last extract did not run in indexed mode");
     if (d_vertices) *d_vertices = (const vtmc_vertex *)ctx->verts.p;
     if (d_indices) *d_indices = (const int32_t *)ctx->indices.p;
     if (d_block_vertex_offsets) *d_block_vertex_offsets = (const uint32_t *)ctx->voffsets.p;
@@ -579,21 +604,21 @@ int32_t vtmc_device_indexed_results(vtmc_ctx *ctx, const vtmc_vertex **d_vertice
 int32_t vtmc_read_triangles(vtmc_ctx *ctx, vtmc_triangle *dst, int64_t capacity, int32_t *block_tri_offsets)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_result) return fail(ctx, VTMC_ERR_NO_RESULT, "read_triangles before any extract");
-    if (ctx->last_indexed) return fail(ctx, VTMC_ERR_NO_RESULT, "read_triangles: the last extract ran in indexed mode (use vtmc_read_indexed_mesh)");
-    if (capacity < ctx->last_tris) return fail(ctx, VTMC_ERR_CAPACITY, "capacity %lld < %lld triangles", (long long)capacity, (long long)ctx->last_tris);
-    if (ctx->last_tris > 0 && !dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "dst is null");
+    if (!ctx->result.valid) return fail(ctx, VTMC_ERR_NO_RESULT, "read_triangles before any extract");
+    if (ctx->result.indexed) return fail(ctx, VTMC_ERR_NO_RESULT, "read_triangles: the last extract ran in indexed mode (use vtmc_read_indexed_mesh)");
+    if (capacity < ctx->result.tris) return fail(ctx, VTMC_ERR_CAPACITY, "capacity %lld < %lld triangles", (long long)capacity, (long long)ctx->result.tris);
+    if (ctx->result.tris > 0 && !dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "dst is null");
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->last_tris > 0)
-        VTMC_HIP(ctx, hipMemcpy(dst, ctx->tris.p, sizeof(vtmc_triangle) * (size_t)ctx->last_tris, hipMemcpyDeviceToHost));
+    if (ctx->result.tris > 0)
+        VTMC_HIP(ctx, hipMemcpy(dst, ctx->tris.p, sizeof(vtmc_triangle) * (size_t)ctx->result.tris, hipMemcpyDeviceToHost));
     return copy_offsets(ctx, block_tri_offsets, ctx->offsets);
 }
 
 int32_t vtmc_read_cases(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_result) return fail(ctx, VTMC_ERR_NO_RESULT, "read_cases before any extract");
-    const int64_t need = (int64_t)ctx->last_blocks * 512;
+    if (!ctx->result.valid) return fail(ctx, VTMC_ERR_NO_RESULT, "read_cases before any extract");
+    const int64_t need = (int64_t)ctx->result.blocks * 512;
     if (capacity < need) return fail(ctx, VTMC_ERR_CAPACITY, "capacity %lld < %lld bytes", (long long)capacity, (long long)need);
     if (need == 0) return VTMC_OK;
     if (!dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "dst is null");
@@ -602,8 +627,8 @@ int32_t vtmc_read_cases(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity)
     // extract is still resident: ctx-owned for host entry points, caller-owned for device ones)
     if (int rc = ensure(ctx, ctx->cases, (size_t)need)) return rc;
     DevBuf tmp;   // freed on every path out
-    if (int rc = ensure(ctx, tmp, sizeof(uint32_t) * (size_t)ctx->last_blocks)) return rc;
-    hipError_t e = launch_classify_blocks(ctx->last_space, ctx->tables, (uint32_t *)tmp.p, (uint8_t *)ctx->cases.p, nullptr, ctx->n_cus, nullptr, 0, ctx->stream);
+    if (int rc = ensure(ctx, tmp, sizeof(uint32_t) * (size_t)ctx->result.blocks)) return rc;
+    hipError_t e = launch_classify_blocks(ctx->result.space, ctx->tables, (uint32_t *)tmp.p, (uint8_t *)ctx->cases.p, nullptr, ctx->n_cus, nullptr, 0, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(dst, ctx->cases.p, (size_t)need, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(ctx, VTMC_ERR_DEVICE, "read_cases: %s", hipGetErrorString(e));
@@ -613,9 +638,9 @@ int32_t vtmc_read_cases(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity)
 int32_t vtmc_last_counts(const vtmc_ctx *ctx, int32_t *n_blocks, int32_t *tri_count)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_result) return VTMC_ERR_NO_RESULT;
-    if (n_blocks) *n_blocks = ctx->last_blocks;
-    if (tri_count) *tri_count = (int32_t)ctx->last_tris;
+    if (!ctx->result.valid) return VTMC_ERR_NO_RESULT;
+    if (n_blocks) *n_blocks = ctx->result.blocks;
+    if (tri_count) *tri_count = (int32_t)ctx->result.tris;
     return VTMC_OK;
 }
 
@@ -639,7 +664,7 @@ int32_t vtmc_extract_volumes_device_async(vtmc_ctx *ctx, const vtmc_volume_batch
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     BlockSpace sp = dense_space(batch->d_samples, batch->nx, batch->ny, batch->nz, batch->stride_x, batch->stride_y,
                                 batch->stride_z, batch->n_volumes, batch->volume_stride);
-    return extract_queue(ctx, sp, batch->n_volumes, flags, stream ? (hipStream_t)stream : ctx->stream);
+    return extract_queue(ctx, sp, batch->n_volumes, ResultSource::Caller, flags, stream ? (hipStream_t)stream : ctx->stream);
 }
 
 int32_t vtmc_extract_finish(vtmc_ctx *ctx, int64_t *tri_count)
@@ -653,7 +678,7 @@ int32_t vtmc_device_results(vtmc_ctx *ctx, const vtmc_triangle **d_triangles, co
                             const uint32_t **d_volume_counts)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_result) return fail(ctx, VTMC_ERR_NO_RESULT, "device_results before any extract");
+    if (!ctx->result.valid) return fail(ctx, VTMC_ERR_NO_RESULT, "device_results before any extract");
     if (d_triangles) *d_triangles = (const vtmc_triangle *)ctx->tris.p;
     if (d_block_tri_offsets) *d_block_tri_offsets = (const uint32_t *)ctx->offsets.p;
     if (d_volume_counts) *d_volume_counts = (const uint32_t *)ctx->volcounts.p;
@@ -664,9 +689,9 @@ int32_t vtmc_copy_volume_counts_device(vtmc_ctx *ctx, uint32_t *d_dst, int32_t c
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
     // the counts are final once the scan has run: valid for a finished extract and for a queued one
-    if (!ctx->has_result && !ctx->pending.active) return fail(ctx, VTMC_ERR_NO_RESULT, "copy_volume_counts before any extract");
-    const int n_vol = ctx->pending.active ? ctx->pending.n_volumes : ctx->last_volumes;
-    const int n_blk = ctx->pending.active ? ctx->pending.sp.n_blocks : ctx->last_blocks;
+    if (!ctx->result.valid && !ctx->pending.active) return fail(ctx, VTMC_ERR_NO_RESULT, "copy_volume_counts before any extract");
+    const int n_vol = ctx->pending.active ? ctx->pending.n_volumes : ctx->result.volumes;
+    const int n_blk = ctx->pending.active ? ctx->pending.sp.n_blocks : ctx->result.blocks;
     if (capacity_volumes < n_vol) return fail(ctx, VTMC_ERR_CAPACITY, "capacity %d < %d volumes", capacity_volumes, n_vol);
     if (n_vol == 0 || n_blk == 0) return VTMC_OK;
     if (!d_dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "d_dst is null");
@@ -683,7 +708,7 @@ int32_t vtmc_reserve_triangles(vtmc_ctx *ctx, int64_t capacity)
     if (!ctx) return VTMC_ERR_INVALID_ARG;
     if (capacity < 0 || capacity > 0x7fffffffll) return fail(ctx, VTMC_ERR_INVALID_ARG, "capacity out of range");
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->has_result = false;  // the old triangle buffer may be released
+    ctx->result.valid = false;  // the old triangle buffer may be released
     const size_t bytes = sizeof(vtmc_triangle) * (size_t)std::max<int64_t>(capacity, 1);
     if (ctx->tris.p && ctx->tris.bytes > std::max<size_t>(bytes, 256)) release(ctx->tris);  // exact size: shrinking is allowed
     const void *before = ctx->tris.p;
@@ -704,7 +729,7 @@ int32_t vtmc_last_placement(const vtmc_ctx *ctx, float ms[16], int32_t *n_candid
 int32_t vtmc_last_stage_ms(vtmc_ctx *ctx, float ms[4])
 {
     if (!ctx || !ms) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->has_result) return fail(ctx, VTMC_ERR_NO_RESULT, "last_stage_ms before any extract");
+    if (!ctx->result.valid) return fail(ctx, VTMC_ERR_NO_RESULT, "last_stage_ms before any extract");
     memcpy(ms, ctx->stage_ms, sizeof ctx->stage_ms);
     return VTMC_OK;
 }

@@ -65,6 +65,33 @@ struct VtmcStamp {
     int nx = 0, ny = 0, nz = 0;
 };
 
+// Who produced an extract's blocks: the caller's own samples, the resident terrain's dirty list (terrain.hip) or a level-of-detail
+// selection of the terrain (terrain_lod.hip: the blocks are nodes, tiles in lod_tiles, node list in lod_nodes)
+enum class ResultSource { Caller, TerrainDirty, TerrainLod };
+
+// The result the context holds.  extract_finish() writes it whole and is the only writer of a valid one; everything that overwrites or
+// may release what it names clears `valid` and leaves `epoch` alone, so no epoch ever names two results.
+struct VtmcResult {
+    bool valid = false;
+    uint64_t epoch = 0;          // counts the finished extracts
+    ResultSource source = ResultSource::Caller;
+    vtmc::BlockSpace space{};
+    int blocks = 0;
+    uint32_t active = 0;         // non-empty blocks: the BlockDesc records the scan left in `active`, in list order
+    int volumes = 0;
+    int64_t tris = 0, verts = 0;
+    bool indexed = false;
+    int64_t vertices() const { return indexed ? verts : 3 * tris; }
+};
+
+// One value per vertex of the result `epoch` names (material weights, occlusion): library-owned, computed on demand, stale after the
+// next extract
+struct VertexAttr {
+    VtmcDevBuf values;
+    int64_t n = 0;
+    uint64_t epoch = 0;
+};
+
 // An extract that has been queued on a stream and not yet completed by extract_finish().
 struct VtmcPending {
     bool active = false;    // queued, extract_finish() not yet called
@@ -72,6 +99,7 @@ struct VtmcPending {
     vtmc::BlockSpace sp{};
     int n_volumes = 0;
     bool indexed = false;
+    ResultSource source = ResultSource::Caller;
     hipStream_t stream = nullptr;
     size_t tcap = 0, vcap = 0;  // capacities the last emit launch was given
     bool scan_event = false;    // ev[2] was recorded behind this extract's scan
@@ -89,8 +117,6 @@ struct vtmc_ctx {
     VtmcDevBuf counts, offsets, active, partials, totals, volcounts, cases, tris, input, list, perm, origins, yrows;
     VtmcDevBuf vcounts, voffsets, vtotals, verts, indices;  // indexed output
     int output_mode = VTMC_OUTPUT_SOUP;
-    bool last_indexed = false;
-    int64_t last_verts = 0;
     uint32_t *h_totals_dev = nullptr;  // the same pinned words as the device sees them (the fused scan writes its totals there)
     VtmcPinnedBuf<uint32_t> h_totals;  // pinned: the scan's totals ({T sat, nActive, T lo, T hi}, then the vertex scan's), 64 words
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // [0..3] stage timing, [4] staging copies
@@ -113,15 +139,7 @@ struct vtmc_ctx {
     hipEvent_t ev_fill[2] = {nullptr, nullptr};  // around the last density kernel (vtmc_last_fill_ms)
     bool fill_timed = false;
     VtmcPending pending;
-    // last result
-    bool has_result = false;
-    vtmc::BlockSpace last_space{};
-    int last_blocks = 0;
-    uint32_t last_active = 0;           // non-empty blocks of the last result: the BlockDesc records the scan left in `active`, in list order
-    int last_volumes = 0;
-    int64_t last_tris = 0;
-    uint64_t result_epoch = 0;          // counts the finished extracts: names the result the context holds
-    uint64_t terrain_result_epoch = 0;  // the result_epoch of the last extract of the resident terrain's dirty set (terrain.hip)
+    VtmcResult result;
     vtmc::Tuning tune;
     // device-resident terrain (vtmc_terrain_*)
     VtmcDevBuf terrain, heightmap;
@@ -146,23 +164,20 @@ struct vtmc_ctx {
     // drained, since an earlier path modifier of the same queue may still be reading it
     VtmcDevBuf path;
     // terrain_material.hip: the material layer (mat_c^3 texels of 8 bytes; mat_c = 0: none), the float image of a set_control_map on its way
-    // to the quantising kernel, the strokes of a paint call, and the vertex weights (8 bytes per vertex) of the result mat_weights_epoch names
-    VtmcDevBuf material, mat_image, mat_strokes, mat_weights;
+    // to the quantising kernel, the strokes of a paint call, and the vertex weights (8 bytes per vertex)
+    VtmcDevBuf material, mat_image, mat_strokes;
     int mat_c = 0;
-    int64_t mat_vertices = 0;
-    uint64_t mat_weights_epoch = 0;
-    // terrain_ao.hip: the ambient-occlusion byte of every vertex of the result ao_epoch names, and the two route counters of the last call
-    // (workgroups that staged a tile, workgroups that fetched from global memory: vtmc_debug_ao_routes)
-    VtmcDevBuf ao_values, ao_stats;
-    int64_t ao_vertices = 0;
-    uint64_t ao_epoch = 0;
+    VertexAttr mat_weights;
+    // terrain_ao.hip: the ambient-occlusion byte of every vertex, and the two route counters of the last call (workgroups that staged a
+    // tile, workgroups that fetched from global memory: vtmc_debug_ao_routes)
+    VertexAttr ao;
+    VtmcDevBuf ao_stats;
     int32_t ao_direct_max = -1;         // vertices up to which a block takes the direct route; -1: the library's default
-    // terrain_lod.hip: the node list of the level-of-detail result lod_epoch names (host, and the copy the gather kernel reads), the packed
+    // terrain_lod.hip: the node list of the last level-of-detail result (host, and the copy the gather kernel reads), the packed
     // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the events around
     // the last gather launch (vtmc_debug_lod_gather_ms)
     std::vector<vtmc_lod_node> lod_nodes;
     VtmcDevBuf lod_nodes_dev, lod_tiles;
-    uint64_t lod_epoch = 0;
     hipEvent_t ev_lod[2] = {nullptr, nullptr};
     bool lod_timed = false;
     // raycast.hip, spherequery.hip: the queries and hits of vtmc_terrain_raycast / _spherecast / _closest_point (device, then their pinned staging)
@@ -215,7 +230,13 @@ BlockSpace dense_space(const float *d_base, int nx, int ny, int nz, int64_t sx, 
 float *pinned_stage(vtmc_ctx *ctx, size_t bytes);   // the pinned stage of host-gathered data (vtmc_api.hip), grown to `bytes`; null: none to be had, go pageable
 void material_drop(vtmc_ctx *ctx);   // terrain_material.hip: vtmc_terrain_init / _load drop the layer
 int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp);   // sp then walks the (bx,by,bz) list
-int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, int32_t *tri_count);   // queued on the context's stream and finished
+int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, ResultSource source, int32_t *tri_count);   // queued on the context's stream and finished
+// The vertex attributes of a terrain result (terrain_material.hip, terrain_ao.hip), in vtmc_api.hip.  attr_gate: may `who` compute one for
+// the result the context holds (terrain, then result, then its blocks are the dirty list's)?  attr_read / attr_device_results: the
+// attribute of the current result to the host / as it lies in device memory; `stale` is the refusal when it is not the current result's.
+int attr_gate(vtmc_ctx *ctx, const char *who);
+int attr_read(vtmc_ctx *ctx, const VertexAttr &a, const char *stale, size_t bytes_per_vertex, uint8_t *dst, int64_t capacity_vertices);
+int attr_device_results(vtmc_ctx *ctx, const VertexAttr &a, const char *stale, const uint8_t **d_values, int64_t *n_vertices);
 // terrain.hip, for terrain_io.hip
 void history_clear(vtmc_ctx *ctx);
 int terrain_extract_all(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_count);   // extracts every block of the resident terrain, as an update that dirtied all of them
