@@ -8,13 +8,31 @@ the library's code -- and every step keeps a copy of the grid before and after i
 generate(seed, world, n_ops) returns a list of operations, the same list for the same arguments.  An operation is a tuple:
   ("set_history", bytes)              ("update", [spec, ...])       ("reject", [spec, ...], reason)   ("undo",)   ("redo",)
   ("stamp_create", seed, dims, amp)   ("stamp_capture", first, dims)   ("stamp_destroy", id)   ("save_load",)
-A spec is terrain_twin's (kind, args) or (kind, args, (lower, upper)): the third entry is the AABB the struct gets after to_struct().
-Stamp ids count up from 1 in the model as in a fresh context, so the generator can name them before any exists."""
+and, in the second generation (generation=2: worlds b and c, SEEDS2, N_OPS2),
+  ("stamp_from_mesh", mesh, first, pitch, dims)      a stamp voxelized from mesh_twin's icosphere, torus or box (mesh_of)
+  ("material_init", fineness)   ("paint", [stroke, ...])   ("control_map", seed, group)      the material layer
+  ("attributes", radius, strength, steps)            vtmc_material_vertices and vtmc_ao_vertices on the result the context holds
+  ("lod", viewer in cells, max_level, split)         vtmc_terrain_extract_lod (world c)
+  ("probe", seed)                                    a fixed small batch of rays, sphere casts and closest points (probe_queries)
+  ("chunk_write",)                                   the chunk file of the result over every block, directly after a save_load
+A spec is terrain_twin's (kind, args) or (kind, args, (lower, upper)): the third entry is the AABB the struct gets after to_struct();
+path_twin's ("path", ...) and stamp_twin's ("stamp", ...) among them.
+Stamp ids count up from 1 in the model as in a fresh context, so the generator can name them before any exists.
+
+Beside the grid the model holds: which stamps came from a mesh (their pastes are the categories "mesh:<mode>"); the material layer, a
+material_twin array or None -- undo and redo leave it alone, a load drops it, material_init brings it back, and paint or control_map
+without one answer VTMC_ERR_NO_RESULT; and which result the context holds (a terrain result with its dirty list, a level-of-detail
+result, or none) and by which operation, since attributes accepts a terrain result only and every new result makes the attributes stale."""
 import os
 
 import numpy as np
 
 from volumetricterrain_amd import _lib, terrainfile as tf
+import ao_twin
+import lod_twin
+import material_twin
+import mesh_twin
+import path_twin
 import stamp_twin
 from terrain_twin import block_list, box_of, image_bytes
 
@@ -23,6 +41,7 @@ f32 = np.float32
 WORLDS = {
     "a": dict(dims=(64, 24, 48), scale=1.0, origin=(0.0, 0.0, 0.0), seed=1234),   # the world of the other terrain tests
     "b": dict(dims=(48, 32, 40), scale=0.3, origin=(-3.1, 1.7, 2.3), seed=8642),
+    "c": dict(dims=(64, 32, 32), scale=0.5, origin=(-3.0, 1.0, 2.0), seed=7531),   # the smallest world on which level-of-detail roots of level 2 are legal
 }
 SEEDS = {"a": (30, 31, 39, 52), "b": (4, 22, 24, 42)}   # chosen so that test_terrain_session.py's generator conditions hold
 N_OPS = 80
@@ -32,6 +51,15 @@ FACES = ("x0", "x1", "y0", "y1", "z0", "z1")
 FAMILIES = ("modify", "flatten", "smooth", "noise", "stamp", "swap", "copy")
 HEIGHTMAPS = ((1, 7), (7, 1), (48, 40))
 REJECTS = ("kind", "radius", "octaves", "stamp")   # an unknown kind, a brush radius of 0, 0 octaves, a stamp id that never existed
+# the second generation (generate(..., generation=2)): the first one's deck plus paths and pastes of mesh stamps, and the consumers of the
+# resident terrain between the queues.  Per world (the seed of the soup session, the seed of the indexed one).
+SEEDS2 = {"b": (3, 4), "c": (1, 3)}             # chosen so that the second generation's conditions hold
+N_OPS2 = 128
+KINDS2 = KINDS + ("path:add", "path:erode", "mesh:add", "mesh:erode", "mesh:replace")
+FAMILIES2 = FAMILIES + ("path",)
+REJECTS2 = REJECTS + ("path",)                     # ... and a path of 0 segments
+LOD_MAX_LEVEL = 2
+CORNER_VIEWER = (-1.0, 3.0, 5.0)                   # in cells; with split 1 on world c: 37 nodes of levels 0, 1 and 2
 
 
 # -- the history ------------------------------------------------------------------------------------------------------------------------
@@ -45,7 +73,7 @@ class History:
     journal of `budget` bytes; steps[:done] can be undone, steps[done:] redone."""
 
     def __init__(self):
-        self.budget, self.steps, self.done = 0, [], 0
+        self.budget, self.steps, self.done, self.evicted = 0, [], 0, []
         self.wraps = self.over_budget = self.after_undo = self.evictions_with_redo = 0
 
     def set_budget(self, nbytes):
@@ -84,6 +112,7 @@ class History:
         while not self._fits(self.steps[k:], st.off, nbytes):   # the oldest steps go
             k += 1
         self.evictions_with_redo += bool(k and had_redo)
+        self.evicted = self.steps[:k]         # the steps this one cost: the ring has come round to them
         self.steps = self.steps[k:] + [st]
         self.done = len(self.steps)
         return st
@@ -102,16 +131,24 @@ class History:
 
 
 # -- the session ------------------------------------------------------------------------------------------------------------------------
-def category(spec):
+def category(spec, mesh_ids=()):
+    """The deck's name of a spec; mesh_ids: the ids of the stamps that came from stamp_from_mesh (their pastes are "mesh:<mode>")."""
     if spec[0] == "noise":
         return "noise:" + spec[1].get("basis", "fbm")
     if spec[0] == "stamp":
-        return "stamp:" + spec[1]["mode"]
+        return ("mesh:" if spec[1]["stamp_id"] in mesh_ids else "stamp:") + spec[1]["mode"]
+    if spec[0] == "path":
+        return "path:" + ("add" if spec[1]["addOrErode"] else "erode")
     return spec[0]
 
 
 def family(spec):
-    return spec[0] if spec[0] in ("flatten", "smooth", "noise", "stamp") else "modify"
+    return spec[0] if spec[0] in ("flatten", "smooth", "noise", "stamp", "path") else "modify"
+
+
+def gpu_struct(spec):
+    """The vtmc_modifier of any spec of a session: path_twin's for a path, stamp_twin's (and through it terrain_twin's) for the rest."""
+    return path_twin.gpu_struct(spec) if spec[0] == "path" else stamp_twin.gpu_struct(spec)
 
 
 def faces_of(first, ext, dims):
@@ -139,7 +176,7 @@ def stamp_field(seed, dims, amplitude):
 
 def bad_modifier(reason):
     """A vtmc_modifier include/vtmc.h says is refused with VTMC_ERR_INVALID_ARG; its box lies inside every world."""
-    m = _lib.Modifier({"kind": 6, "radius": _lib.MOD_SMOOTH, "octaves": _lib.MOD_NOISE, "stamp": _lib.MOD_STAMP}[reason], 1)
+    m = _lib.Modifier({"kind": 6, "radius": _lib.MOD_SMOOTH, "octaves": _lib.MOD_NOISE, "stamp": _lib.MOD_STAMP, "path": _lib.MOD_PATH}[reason], 1)
     m.lower[:], m.upper[:] = (1.0, 3.0, 4.0), (3.0, 5.0, 6.0)
     if reason == "radius":
         m.p[0:5] = (2.0, 4.0, 5.0, 0.0, 0.5)
@@ -149,51 +186,81 @@ def bad_modifier(reason):
     elif reason == "stamp":
         m.p[0:8] = (2.0, 4.0, 5.0, 0.0, 0.0, 0.0, 1.0, 1.0)
         m.data_dims[:] = (1 << 20, 0)
+    elif reason == "path":   # well-formed data, 0 segments of it
+        m._keep = np.array([[2.0, 4.0, 5.0, 1.0, 3.0, 4.0, 5.0, 1.0]], f32)
+        m.data = m._keep.ctypes.data
+        m.data_dims[:] = (0, 8)
     return m
 
 
 class Session:
-    def __init__(self, oracle_mod, world):
+    def __init__(self, oracle_mod, world, indexed=False):
         w = WORLDS[world]
-        self.oracle, self.world = oracle_mod, w
+        self.oracle, self.world, self.indexed = oracle_mod, w, indexed
         self.ref = oracle_mod.Terrain(*w["dims"], w["scale"], w["origin"], w["seed"])
         self.nb = tuple(d // 8 for d in w["dims"])
-        self.stamps, self.next_stamp = {}, 1
+        self.stamps, self.next_stamp, self.mesh_ids = {}, 1, set()
         self.hist = History()
+        self.layer = None            # the material layer (material_twin's array), None while the device has none
+        # the result the context holds: None, "terrain" (an update, undo, redo or load, with its dirty list) or "lod"; attributes_current:
+        # the vertex weights and occlusion bytes were computed for it
+        self.result, self.result_source, self.result_dirty, self.attributes_current = None, None, None, False
         # what the generator conditions read
-        self.kinds = dict.fromkeys(KINDS, 0)
+        self.kinds = dict.fromkeys(KINDS2, 0)
         self.taken = {True: {"low": 0, "high": 0}, False: {"low": 0, "high": 0}}   # csg_write's clamp branches, by add_or_erode
+        self.path_taken = {True: {"low": 0, "high": 0}, False: {"low": 0, "high": 0}}   # the same of the paths alone
         self.footprints = []
-        self.faces = {f: set() for f in FAMILIES}
+        self.mesh_footprints = {"add": [], "erode": [], "replace": []}
+        self.faces = {f: set() for f in FAMILIES2}
         self.loads, self.loads_edited = 0, 0
+        self.paths = dict(undone=0, redone=0, evicted=0, after_undo=0, after_load=0)
+        self.last = None             # the name of the last operation that ran, with "!" behind an undo or redo that was refused
 
     # -- updates --------------------------------------------------------------------------------------------------------------------
     def _apply(self, specs):
         ids = set()
         for spec in specs:
-            taken = {"low": 0, "high": 0}
-            for bx, by, bz in stamp_twin.twin_update(self.ref, self.oracle, [spec], self.stamps, self.footprints, taken):
+            taken, counts = {"low": 0, "high": 0}, []
+            if spec[0] == "path":
+                hit = path_twin.twin_update(self.ref, self.oracle, [spec], taken)
+            else:
+                hit = stamp_twin.twin_update(self.ref, self.oracle, [spec], self.stamps, counts, taken)
+            for bx, by, bz in hit:
                 ids.add(int(bx + self.nb[0] * (by + self.nb[1] * bz)))
-            if spec[0] == "noise":
+            self.footprints += counts
+            if spec[0] == "stamp" and spec[1]["stamp_id"] in self.mesh_ids:
+                self.mesh_footprints[spec[1]["mode"]] += counts
+            if spec[0] in ("noise", "path"):
+                into = self.taken if spec[0] == "noise" else self.path_taken
                 for k in taken:
-                    self.taken[bool(spec[1].get("add_or_erode", True))][k] += taken[k]
+                    into[bool(spec[1].get("add_or_erode", True) if spec[0] == "noise" else spec[1]["addOrErode"])][k] += taken[k]
         return block_list(ids, self.nb)
 
     def boxes(self, specs):
-        return [box_of(self.ref, stamp_twin.gpu_struct(s))[:2] for s in specs]
+        return [box_of(self.ref, gpu_struct(s))[:2] for s in specs]
+
+    def _produced(self, kind, source, dirty=None):
+        self.result, self.result_source, self.result_dirty, self.attributes_current = kind, source, dirty, False
 
     def update(self, specs):
         """One vtmc_terrain_update of the whole queue.  Returns its dirty list."""
         boxes = self.boxes(specs)
         for spec, (first, ext) in zip(specs, boxes):
-            self.kinds[category(spec)] += 1
+            self.kinds[category(spec, self.mesh_ids)] += 1
             self.faces[family(spec)] |= faces_of(first, ext, self.ref.dims)
         nbytes = sum(image_bytes(ext) for _, ext in boxes)
+        has_path = any(sp[0] == "path" and min(ext) > 0 for sp, (_, ext) in zip(specs, boxes))
+        had_redo = self.hist.done < len(self.hist.steps)
         before = self.ref._mem.copy()
         dirty = self._apply(specs)
-        self.hist.record(nbytes, dict(before=before, after=self.ref._mem.copy(), dirty=dirty, boxes=boxes))
+        step = self.hist.record(nbytes, dict(before=before, after=self.ref._mem.copy(), dirty=dirty, boxes=boxes, has_path=has_path))
+        if step is not None:
+            self.paths["evicted"] += sum(bool(e.payload["has_path"]) for e in self.hist.evicted)
+            self.paths["after_undo"] += bool(has_path and had_redo)
         if self.loads and nbytes:
             self.loads_edited = max(self.loads_edited, self.loads)
+            self.paths["after_load"] += has_path
+        self._produced("terrain", "update", dirty)
         return dirty
 
     def reject(self, prefix):
@@ -209,6 +276,8 @@ class Session:
         self.ref._mem[...] = step.payload[which]
         for first, ext in step.payload["boxes"]:
             self.faces["swap"] |= faces_of(first, ext, self.ref.dims)
+        self.paths["undone" if which == "before" else "redone"] += bool(step.payload.get("has_path"))
+        self._produced("terrain", "undo" if which == "before" else "redo", step.payload["dirty"])
         return step.payload["dirty"]
 
     def undo(self):
@@ -236,6 +305,13 @@ class Session:
         self.faces["copy"] |= faces_of(first, dims, self.ref.dims)
         return self._new_stamp(np.array(self.ref.grid[x:x + nx, y:y + ny, z:z + nz], f32))
 
+    def stamp_from_mesh(self, mesh, first, pitch, dims):
+        """mesh_twin.voxelize's samples of the named mesh (mesh_of); the stamp's pastes count as "mesh:<mode>"."""
+        v, t = mesh_of(mesh)
+        sid = self._new_stamp(mesh_twin.voxelize(v, t, first, pitch, dims))
+        self.mesh_ids.add(sid)
+        return sid
+
     def stamp_destroy(self, sid):
         del self.stamps[sid]
 
@@ -245,38 +321,131 @@ class Session:
 
     def save_load(self, path):
         """vtmc_terrain_save then vtmc_terrain_load through the format's mirror.  The loaded grid becomes the grid, elided bricks redrawn;
-        the events come from the file; the history is cleared and keeps its budget.  Returns the dirty list: every block."""
+        the events come from the file; the history is cleared and keeps its budget; the material layer is dropped.  Returns the dirty
+        list: every block."""
         tf.write_terrain(path, self.ref.grid, self.meta())
         meta, _, grid = tf.read_terrain(path)
         self.ref._mem[...] = grid.transpose(2, 1, 0)
         self.ref.events = meta["event"]
         self.hist.clear()
         self.loads += 1
-        return block_list(range(self.nb[0] * self.nb[1] * self.nb[2]), self.nb)
+        self.layer = None
+        dirty = block_list(range(self.nb[0] * self.nb[1] * self.nb[2]), self.nb)
+        self._produced("terrain", "save_load", dirty)
+        return dirty
+
+    # -- the material layer (include/vtmc.h: undo and redo leave it alone, a load drops it) ------------------------------------------
+    def material_init(self, fineness):
+        self.layer = material_twin.initial(16 * fineness)
+        return self.layer
+
+    def paint(self, strokes):
+        """The layer after the strokes; None where the device answers VTMC_ERR_NO_RESULT (no layer)."""
+        if self.layer is None:
+            return None
+        w = self.world
+        self.layer = material_twin.paint(self.layer, strokes, w["dims"], w["scale"], w["origin"])
+        return self.layer
+
+    def control_map(self, seed, group):
+        if self.layer is None:
+            return None
+        self.layer = material_twin.set_control_map(self.layer, control_image(seed, self.layer.shape[0]), group)
+        return self.layer
+
+    # -- the consumers ---------------------------------------------------------------------------------------------------------------
+    def geometry(self):
+        """(blocks, positions, normals, vertices per block) of the result the model holds, from the oracle's extract of the model's grid:
+        what the generator conditions use in place of the device's records."""
+        dirty = self.result_dirty
+        grid = np.ascontiguousarray(self.ref.grid)
+        if self.indexed:
+            verts, _, voffs, _ = self.oracle.extract_grid_indexed(grid, dirty)
+            return ao_twin.indexed_vertices(verts, voffs, dirty) + (np.diff(voffs),)
+        tris, offs, _ = self.oracle.extract_grid(grid, dirty, threads=8)
+        return ao_twin.soup_vertices(tris, dirty) + (3 * np.diff(offs),)
+
+    def attributes(self, radius, strength, steps, geo=None):
+        """vtmc_material_vertices and vtmc_ao_vertices on the result held.  Returns (weights, occlusion): an array each, or None where the
+        device answers VTMC_ERR_NO_RESULT -- both without a terrain result, the weights also without a layer.  geo: the vertices as the
+        device returned them (blocks, positions, normals, ...); the model's own where None."""
+        if self.result != "terrain":
+            return None, None
+        geo = self.geometry() if geo is None else geo
+        self.attributes_current = True
+        weights = None if self.layer is None else material_twin.vertex_weights(self.layer, self.world["dims"], geo[0], geo[1])
+        return weights, ao_twin.vertex_ao(self.ref.grid, geo[0], geo[1], geo[2], radius, self.world["scale"], strength, steps)
+
+    def lod(self, viewer, max_level, split):
+        """vtmc_terrain_extract_lod for a viewer given in cells.  Returns (nodes, tiles): lod_twin's selection and its tiles of the grid."""
+        w = self.world
+        nodes = lod_twin.select_nodes(w["dims"], w["origin"], w["scale"], viewer_world(w, viewer), max_level, split)
+        self._produced("lod", "lod")
+        return nodes, lod_twin.node_tiles(self.ref.grid, nodes)
 
     # -- driving ----------------------------------------------------------------------------------------------------------------------
     def run(self, op, tmp_dir):
         """One operation of generate() on the model alone; returns what the method returns."""
         name = op[0]
         if name == "update":
-            return self.update(op[1])
-        if name == "reject":
-            return self.reject(op[1])
-        if name == "save_load":
-            return self.save_load(os.path.join(str(tmp_dir), "twin.vtmt"))
-        return getattr(self, name)(*op[1:])
+            out = self.update(op[1])
+        elif name == "reject":
+            out = self.reject(op[1])
+        elif name == "save_load":
+            out = self.save_load(os.path.join(str(tmp_dir), "twin.vtmt"))
+        elif name in ("probe", "chunk_write"):   # they read the grid and change nothing
+            out = None
+        else:
+            out = getattr(self, name)(*op[1:])
+        self.last = name + ("!" if name in ("undo", "redo") and out is None else "")
+        return out
+
+
+def mesh_of(mesh):
+    """(vertices, triangles) of a mesh an operation names: ("icosphere", subdivisions, radius, centre), ("torus", major, minor, n_major,
+    n_minor, centre) or ("box", lo, hi), mesh_twin's builders."""
+    return getattr(mesh_twin, mesh[0])(*mesh[1:])
+
+
+def control_image(seed, C):
+    """The C^3 x 4 floats of a control_map operation: uniform in [-0.25, 1.25], so both clamps of the quantisation are taken."""
+    return np.random.default_rng(seed).uniform(-0.25, 1.25, (C, C, C, 4)).astype(f32)
+
+
+def viewer_world(w, cells):
+    """The world position of a viewer given in cells; exact in float32 for world c's dyadic scale and origin and viewers on quarter cells."""
+    return tuple(float(f32(w["origin"][k]) + f32(cells[k]) * f32(w["scale"])) for k in range(3))
+
+
+def probe_queries(w, seed, n_rays=32, n_spheres=16):
+    """The fixed small batch of a probe operation: rays from above the grid downwards at a slant (most of them hit ground), sphere casts
+    of the same shape, and closest-point balls inside the grid.  World space, float32."""
+    rng = np.random.default_rng([seed, 77])
+    dims, s, o = np.array(w["dims"], float), w["scale"], np.array(w["origin"], float)
+
+    def down(n):
+        org = o + np.stack([rng.uniform(2, dims[0] - 2, n), np.full(n, dims[1] + 3.0), rng.uniform(2, dims[2] - 2, n)], 1) * s
+        return org.astype(f32), np.stack([rng.uniform(-0.3, 0.3, n), -np.ones(n), rng.uniform(-0.3, 0.3, n)], 1).astype(f32)
+    ray_o, ray_d = down(n_rays)
+    half = n_spheres // 2
+    cast_o, cast_d = down(half)
+    cast_r = (rng.uniform(0.2, 2.5, half) * s).astype(f32)
+    ball_c = (o + rng.uniform(0.15, 0.85, (n_spheres - half, 3)) * dims * s).astype(f32)
+    ball_r = (rng.uniform(2.0, 5.0, n_spheres - half) * s).astype(f32)
+    return dict(ray_o=ray_o, ray_d=ray_d, cast_o=cast_o, cast_d=cast_d, cast_r=cast_r, ball_c=ball_c, ball_r=ball_r)
 
 
 # -- the generator ----------------------------------------------------------------------------------------------------------------------
 class _Draw:
     """The generator's state: the random stream, the world's geometry and the stamps that exist at the point the list has reached."""
 
-    def __init__(self, seed, world):
+    def __init__(self, seed, world, generation=1):
         w = WORLDS[world]
-        self.rng = np.random.default_rng([seed, ord(world)])
+        self.rng = np.random.default_rng([seed, ord(world)] + ([generation] if generation > 1 else []))
         self.dims, self.scale, self.origin = w["dims"], w["scale"], w["origin"]
         self.top = [d + 1 for d in self.dims]
         self.live, self.next_stamp, self.islands = {}, 1, 0   # live: id -> dims
+        self.mesh = set()                                     # the ids among them that came from a mesh
 
     def pos(self, i, k):
         return float(f32(i) * f32(self.scale) + f32(self.origin[k]))
@@ -314,7 +483,9 @@ class _Draw:
     def modifier(self, cat, mode):
         """One spec of category cat whose box is drawn by mode."""
         r, s = self.rng, self.scale
-        spans, aabb = self.box(mode)
+        if mode == "long":
+            return self.long_path(cat.endswith("add"))
+        spans, aabb = self.box("free" if mode in ("single", "zero") else mode)
         mid = tuple(self.pos(0.5 * (lo + hi), k) for k, (lo, hi) in enumerate(spans))
         half = [0.5 * (hi - lo) * s for lo, hi in spans]
         add = bool(r.integers(0, 2))
@@ -350,13 +521,94 @@ class _Draw:
                                   basis=cat.split(":")[1], amplitude=float(r.uniform(0.8, 2.0)), ramp_scale=float(r.uniform(0.4, 0.8)) / s,
                                   ramp_center=mid[1], lower=aabb[0], upper=aabb[1], add_or_erode=add))
             own_box = True
-        else:
-            sid = sorted(self.live)[int(r.integers(0, len(self.live)))]
+        elif kind == "path":
+            spec = ("path", dict(segments=self.path_segments(mode, spans), addOrErode=cat.endswith("add")))
+            own_box = own_box and mode in ("free", "single", "zero")   # on the faces the exact AABB: the path family must touch all six
+        else:   # a paste of a stamp, or ("mesh") of one that came from a mesh
+            pool = sorted(i for i in self.live if (i in self.mesh) == (kind == "mesh"))
+            sid = pool[int(r.integers(0, len(pool)))]
             inside = tuple(min(max(mid[k], self.pos(1, k)), self.pos(self.top[k] - 1, k)) for k in range(3))
             spec = ("stamp", dict(stamp_id=sid, dims=self.live[sid], position=inside, rotation=self.quaternion(),
                                   pitch=float(r.uniform(0.7, 1.4)) * s, mode=cat.split(":")[1]))
             own_box = True   # the world AABB of the turned stamp box: the footprint must lie inside the box
         return spec if own_box else spec + (aabb,)
+
+    def path_segments(self, mode, spans):
+        """A polyline or a tree through the box, as (n, 8) segments: nodes anywhere in the box, radii from thin (every sample far outside:
+        the low clamp branch) to wider than the box (the high one).  "single": one segment; "zero": a polyline with a segment of length 0
+        whose radii differ."""
+        r, s = self.rng, self.scale
+        lo = np.array([self.pos(a, k) for k, (a, _) in enumerate(spans)])
+        hi = np.array([self.pos(b, k) for k, (_, b) in enumerate(spans)])
+        n = 2 if mode == "single" else int(r.integers(3, 8))
+        pts = lo + r.uniform(0.0, 1.0, (n, 3)) * (hi - lo)
+        rad = r.uniform(0.2, 2.8, n) * (1.0 if s < 0.4 else 1.5)
+        if mode != "single" and r.random() < 0.5:
+            parent = [-1] + [int(r.integers(0, k)) for k in range(1, n)]
+            seg = np.array([[*pts[parent[k]], rad[parent[k]], *pts[k], rad[k]] for k in range(1, n)])
+        else:
+            seg = np.array([[*pts[k], rad[k], *pts[k + 1], rad[k + 1]] for k in range(n - 1)])
+        if mode == "zero":
+            seg = np.insert(seg, 1, [*pts[1], 0.5 * rad[1], *pts[1], 1.5 * rad[1]], axis=0)
+        return seg
+
+    def long_path(self, add):
+        """More than kPathChunk segments in two clusters at the two z ends of the grid, the first chunk's all in the first one, in a box of
+        10 x 20 samples over the whole of z: the tiles near one end are farther than radius + 2 from every segment of the other chunk."""
+        r, s = self.rng, self.scale
+        x0 = int(r.integers(2, self.top[0] - 12))
+        spans = [(x0, x0 + 9), (2, 21), (-1, self.top[2] + 2)]
+        lower = tuple(self.pos(a, k) + 0.25 * s for k, (a, _) in enumerate(spans))
+        upper = tuple(self.pos(b, k) - 0.25 * s for k, (_, b) in enumerate(spans))
+        C = _lib.PATH_CHUNK
+
+        def cluster(n, z):
+            a = np.stack([r.uniform(lower[0], upper[0], n), r.uniform(lower[1], upper[1], n), self.pos(z, 2) + r.uniform(-0.5, 0.5, n)], 1)
+            b = a + r.uniform(-0.6, 0.6, (n, 3))
+            return np.column_stack([a, r.uniform(0.2, 0.7, n), b, r.uniform(0.2, 0.7, n)])
+        seg = np.concatenate([cluster(C, 2), cluster(C // 4 + 3, self.top[2] - 2)])
+        return ("path", dict(segments=seg, addOrErode=add), (lower, upper))
+
+    def surface_edit(self):
+        """A small queue where the first update's plane lies, for the undo that an attributes, probe or lod operation follows: a ball
+        added and a path of one segment carved through it, so it changes solid ground and empty air alike.  Returns (specs, centre)."""
+        r, s = self.rng, self.scale
+        c = (self.pos(int(r.integers(6, self.top[0] - 6)), 0), self.pos(self.top[1] // 2, 1) + 0.375 * s, self.pos(int(r.integers(6, self.top[2] - 6)), 2))
+        rad = float(r.uniform(3.0, 4.5)) * s
+        seg = [[c[0] - 1.5 * rad, c[1] + 0.3 * rad, c[2] - 0.5 * rad, 0.5 * rad, c[0] + 1.5 * rad, c[1] - 0.2 * rad, c[2] + 0.5 * rad, 0.4 * rad]]
+        return [("sphere", (c, rad, True)), ("path", dict(segments=np.array(seg), addOrErode=False))], c
+
+    def strokes(self, n, at=None):
+        """n paint strokes (center, radius, channel, strength), radii of one to three texels of a 16^3 layer; the first one at `at`."""
+        r, s = self.rng, self.scale
+        texel = max(self.dims) * s / 16.0
+        out = []
+        for i in range(n):
+            c = at if at is not None and i == 0 else tuple(self.pos(float(r.uniform(0, self.dims[k])), k) for k in range(3))
+            out.append((tuple(float(v) for v in c), float(r.uniform(1.0, 3.0)) * texel, int(r.integers(1, 8)), float(r.uniform(0.5, 1.0))))
+        return out
+
+    def attributes(self):
+        return ("attributes", float(self.rng.uniform(1.5, 5.9)) * self.scale, float(self.rng.uniform(0.5, 1.0)), int(self.rng.integers(3, 9)))
+
+    def mesh_stamp(self, shape):
+        """("stamp_from_mesh", mesh, first, pitch, dims): the mesh in the middle of a stamp of 6..12 samples per axis."""
+        r = self.rng
+        dims = tuple(int(v) for v in r.integers(6, 13, 3))
+        h = float((0.75, 1.0, 1.25)[int(r.integers(0, 3))])
+        first = (0.125, -0.25, 0.0625)
+        c = tuple(first[k] + h * (0.5 * (dims[k] - 1) + float(r.uniform(-0.4, 0.4))) for k in range(3))
+        if shape == "icosphere":
+            mesh = ("icosphere", 1, h * (0.5 * min(dims) - 1.2), c)
+        elif shape == "torus":
+            m = min(dims[0], dims[2])
+            mesh = ("torus", h * 0.28 * m, h * min(0.14 * m, 0.5 * dims[1] - 1.0), 8, 6, c)
+        else:
+            mesh = ("box", tuple(c[k] - h * (0.5 * dims[k] - 1.6) for k in range(3)), tuple(c[k] + h * (0.5 * dims[k] - 1.6) for k in range(3)))
+        self.live[self.next_stamp] = dims
+        self.mesh.add(self.next_stamp)
+        self.next_stamp += 1
+        return ("stamp_from_mesh", mesh, first, h, dims)
 
     def create(self):
         dims = tuple(int(v) for v in self.rng.integers(6, 13, 3))
@@ -382,10 +634,8 @@ class _Draw:
         return ("stamp_destroy", sid)
 
 
-def generate(seed, world, n_ops=N_OPS, history_from_start=True):
-    """The session (seed, world) as a list of n_ops operations.  history_from_start False: the same list with the history switched on a
-    third of the way in instead of before the first update (budget changes before that point switch it off again)."""
-    d = _Draw(seed, world)
+def _operations1(d, n_ops):
+    """The first generation's operations, without the first set_history."""
     r, s = d.rng, d.scale
     # the modifiers every session holds: each category with a box on the three low faces, one on the three high faces, one ending on
     # block faces and one anywhere; whole-world planes and islands; one sphere wholly outside
@@ -443,9 +693,133 @@ def generate(seed, world, n_ops=N_OPS, history_from_start=True):
         ops.append(("undo",) if k == 0 else ("redo",) if k == 1 else ("update", queue_of([(KINDS[int(r.integers(4, 9))], "free")])))
     assert len(ops) == n_ops - 1, "n_ops is too small for what every session holds: %d" % (len(ops) + 1)
 
+    return ops
+
+
+def _operations2(d, world, n_ops):
+    """The second generation: the first one's deck with paths and pastes of mesh stamps beside every old category, and between the
+    queues the operations on the material layer, the vertex attributes, the level-of-detail extract (world c), the queries and the
+    chunk file, in the sequences the conditions of test_terrain_session.py ask for."""
+    r, s = d.rng, d.scale
+    modes = ("low", "high", "block", "free")
+    deck = [(cat, mode) for cat in KINDS2 for mode in modes if cat not in ("plane", "island") or mode != "free"]
+    deck += [("plane", "world"), ("island", "world"), ("island", "world"), ("sphere", "outside")]
+    deck += [("path:erode", "single"), ("path:add", "long"), ("path:erode", "zero")]
+    deck = [deck[i] for i in r.permutation(len(deck))]
+    extras = ["capture:low", "capture:high", "capture:free", "destroy", "create", "load:chunk", "load:probe", "load:layer",
+              "budget", "budget", "material_init", "material_init", "paint", "paint", "paint", "control_map", "control_map"]
+    extras += ["reject"] * 5 + ["undo+"] * 6 + ["undo2"] * 2 + ["redo"] * 3
+    extras += ["undo,attributes", "undo,attributes", "paint,undo,attributes", "undo,redo,attributes", "attributes", "attributes", "attributes"]
+    extras += ["undo,probe", "probe", "probe"]
+    if world == "c":
+        extras += ["undo,lod", "lod,attributes", "lod"]
+    queues = []
+    while deck:
+        n = min(int(r.integers(1, 5)), len(deck))
+        queues.append([deck.pop() for _ in range(n)])
+    slots = [("queue", q) for q in queues] + [("extra", e) for e in extras]
+    slots = [slots[i] for i in r.permutation(len(slots))]
+
+    ops = [("update", [("plane", (d.pos(d.top[1] // 2, 1) + 0.375 * s, (d.pos(-2, 0), d.pos(-2, 2)), (d.pos(d.top[0] + 2, 0), d.pos(d.top[2] + 2, 2)), True))]),
+           d.create(), d.create(), d.mesh_stamp("icosphere"), d.mesh_stamp("torus"), d.mesh_stamp("box"), ("material_init", 1)]
+    count = dict(reject=0, lod=0, path_on_undo=0)
+
+    def queue_of(items):
+        return [d.modifier(cat, "free")[:2] if mode == "world" else d.modifier(cat, mode) for cat, mode in items]
+
+    def small(lo, hi):   # a queue of free boxes of the categories KINDS2[lo:hi]
+        return queue_of([(KINDS2[int(r.integers(lo, hi))], "free") for _ in range(int(r.integers(1, 4)))])
+
+    def edit_undo():   # an edit at the surface and its undo; returns the edit's centre
+        specs, c = d.surface_edit()
+        ops.append(("update", specs))
+        return c
+
+    def lod():   # the operation after it: an undo, a redo and an update in turn
+        viewer = CORNER_VIEWER if count["lod"] < 2 else tuple(float(v) for v in np.round(r.uniform(-8, 72, 3) * 4) / 4)
+        ops.append(("lod", viewer, LOD_MAX_LEVEL, 1.0 if count["lod"] < 2 else float((1.0, 1.5, 2.0)[int(r.integers(0, 3))])))
+        count["lod"] += 1
+        return [("undo",), ("redo",), ("update", small(0, 9))][count["lod"] % 3]
+
+    for what, arg in slots:
+        if what == "queue":
+            ops.append(("update", queue_of(arg)))
+        elif arg.startswith("capture"):
+            ops.append(d.capture(arg.split(":")[1]))
+        elif arg == "destroy":
+            ops.append(d.destroy())
+        elif arg == "create":
+            ops.append(d.create())
+        elif arg == "load:chunk":    # the file of the result over every block; the attributes of that result, with no layer
+            ops += [("save_load",), ("chunk_write",), d.attributes()]
+        elif arg == "load:probe":
+            ops += [("save_load",), ("probe", int(r.integers(0, 1 << 30))), ("material_init", 1)]
+        elif arg == "load:layer":    # the layer brought back and painted before the attributes of the load's result
+            ops += [("save_load",), ("material_init", 1), ("paint", d.strokes(3)), d.attributes()]
+        elif arg == "budget":
+            ops.append(("set_history", float(r.uniform(2.6, 3.6))))
+        elif arg == "material_init":
+            ops.append(("material_init", 1))
+        elif arg == "paint":
+            ops.append(("paint", d.strokes(int(r.integers(1, 5)))))
+        elif arg == "control_map":
+            ops.append(("control_map", int(r.integers(0, 1 << 30)), int(r.integers(1, 3))))
+        elif arg == "reject":
+            ops.append(("reject", small(0, 9)[:int(r.integers(0, 3))], REJECTS2[count["reject"] % len(REJECTS2)]))
+            count["reject"] += 1
+        elif arg == "undo+":   # an undo and an edit on top of it: the redo is discarded; every other one holds a path
+            top = small(4, 9) + ([d.modifier(("path:add", "path:erode")[count["path_on_undo"] // 2 % 2], "free")] if count["path_on_undo"] % 2 == 0 else [])
+            count["path_on_undo"] += 1
+            ops += [("undo",), ("update", top)]
+        elif arg == "undo2":
+            ops += [("undo",), ("undo",), ("redo",)]
+        elif arg == "redo":
+            ops.append(("redo",))
+        elif arg == "undo,attributes":
+            edit_undo()
+            ops += [("undo",), d.attributes()]
+        elif arg == "paint,undo,attributes":   # the edit is painted over, then undone: the layer keeps the paint
+            c = edit_undo()
+            ops += [("paint", d.strokes(2, at=c)), ("undo",), d.attributes()]
+        elif arg == "undo,redo,attributes":
+            edit_undo()
+            ops += [("undo",), ("redo",), d.attributes()]
+        elif arg == "attributes":
+            ops.append(d.attributes())
+        elif arg == "undo,probe":
+            edit_undo()
+            ops += [("undo",), ("probe", int(r.integers(0, 1 << 30)))]
+        elif arg == "probe":
+            ops.append(("probe", int(r.integers(0, 1 << 30))))
+        elif arg == "undo,lod":
+            edit_undo()
+            ops.append(("undo",))
+            ops.append(lod())
+        elif arg == "lod,attributes":
+            after = lod()
+            ops += [d.attributes(), after]
+        elif arg == "lod":
+            ops.append(lod())
+        else:
+            raise AssertionError(arg)
+    while len(ops) < n_ops - 1:
+        k = int(r.integers(0, 4))
+        ops.append(("undo",) if k == 0 else ("redo",) if k == 1 else ("update", small(4, 9)[:1]))
+    assert len(ops) == n_ops - 1, "n_ops is too small for what every session holds: %d" % (len(ops) + 1)
+    return ops
+
+
+def generate(seed, world, n_ops=None, history_from_start=True, generation=1):
+    """The session (seed, world) as a list of n_ops operations (N_OPS, or N_OPS2 for generation 2).  history_from_start False: the same
+    list with the history switched on a third of the way in instead of before the first update (budget changes before that point switch
+    it off again).  generation 2: its own deck, seeds and length (_operations2)."""
+    n_ops = n_ops or (N_OPS if generation == 1 else N_OPS2)
+    d = _Draw(seed, world, generation)
+    s = d.scale
+    ops = _operations1(d, n_ops) if generation == 1 else _operations2(d, world, n_ops)
     # budgets relative to the session's own median step size
     ref = type("Shape", (), dict(dims=d.dims, scale=s, origin=np.asarray(d.origin, f32)))
-    sizes = [sum(image_bytes(box_of(ref, stamp_twin.gpu_struct(sp))[1]) for sp in op[1]) for op in ops if op[0] == "update"]
+    sizes = [sum(image_bytes(box_of(ref, gpu_struct(sp))[1]) for sp in op[1]) for op in ops if op[0] == "update"]
     median = float(np.median([b for b in sizes if b]))
     first = 0 if history_from_start else n_ops // 3
     ops.insert(first, ("set_history", 3.1))

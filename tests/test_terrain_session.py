@@ -1,5 +1,12 @@
 """The resident terrain as one randomized edit session against its twins (session_twin.py), a directed matrix of box extents on the seams
-of the shared box walk (64 lanes along x, 4 z-planes, runs of 16 along y), and the inclusive dirty rule on the device.
+of the shared box walk (64 lanes along x, 4 z-planes, runs of 16 along y) for every kernel that runs on it, the path kernel included, and
+the inclusive dirty rule on the device.
+
+Two generations of sessions.  The first (worlds a and b, soup output) is pinned by digests of its operation lists.  The second (worlds b
+and c, one soup and one indexed session each) adds paths and pastes of mesh stamps to the deck and, between the queues, the consumers
+of the resident terrain: the material layer (init, paint, control map), the vertex weights and occlusion bytes of whatever result the
+context holds, the level-of-detail extract, ray and sphere queries and the chunk file -- each against its own twin (material_twin,
+ao_twin, lod_twin, surface_twin, chunkfile) on the MODEL's grid, after undos, redos, ring wraps and loads.
 
 CPU: the generator is deterministic and every committed seed meets the coverage conditions (conditions, not measurements: a seed that
 misses one is replaced, the condition stays); the history model gives the answers worked by hand below; the model's snapshots are
@@ -9,6 +16,7 @@ the history model, every undo or redo the device grants must put back the snapsh
 
 "Eviction while the redo stack is non-empty" is read as: an update that arrives with steps to redo and, after discarding them, still
 costs at least one older step (the library discards the redo before it places the step)."""
+import hashlib
 import os
 
 import numpy as np
@@ -16,10 +24,16 @@ import pytest
 
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib, terrainfile as tf
+import ao_twin
+import material_twin
+import path_twin
 import session_twin as st
 import stamp_twin
+from extract_checks import ATOL, assert_tris_match
 from session_twin import FACES, FAMILIES, KINDS, SEEDS, History, Session, generate
-from terrain_twin import assert_triangles, bits, box_of, gpu_struct, oracle_mod_of
+from surface_twin import Surface, check_tight, compare as compare_rays, reference as ray_reference
+from terrain_twin import assert_triangles, bits, block_list, box_of, csg_write, gpu_struct, oracle_mod_of
+from test_sphere_queries import SphereSurface, check as check_spheres
 
 f32 = np.float32
 CASES = [(w, s) for w in sorted(SEEDS) for s in SEEDS[w]]
@@ -96,6 +110,217 @@ def test_generator_conditions(oracle_mod, tmp_path_factory, world, seed):
     names = [op[0] for op in ops]
     assert names.count("reject") >= 3 and names.count("stamp_create") >= 2 and names.count("stamp_capture") >= 3 and "stamp_destroy" in names
     assert names.count("set_history") >= 3 and names.count("redo") >= 4
+
+
+# the first generation, pinned: sha256 of repr(plain(ops)), history from the start and mid-session, computed before the generator learnt
+# its second generation.  A change of the generator that moves one draw of an old session shows here.
+DIGESTS = {("a", 30): ("9873e549f506e40d", "aba98020f443dde0"), ("a", 31): ("719dc96fed38158f", "c94f0e042dbdc0f2"),
+           ("a", 39): ("c3a8e58001919b78", "04a4578ebfb0b434"), ("a", 52): ("6264918e33e639fe", "83bff65398cbb3ab"),
+           ("b", 4): ("85fa0fb1f1e4916e", "36a3af88b973d4d4"), ("b", 22): ("4bda2bd56452bcb4", "d1441217d5868fb5"),
+           ("b", 24): ("cf4081cf3cc4d39e", "de149032a0d67fdb"), ("b", 42): ("d2d94c2af003d83b", "61cfa8c910795ea6")}
+
+
+def digest(ops):
+    return hashlib.sha256(repr(plain(ops)).encode()).hexdigest()[:16]
+
+
+@pytest.mark.parametrize("world,seed", CASES)
+def test_first_generation_sessions_are_unchanged(world, seed):
+    assert set(DIGESTS) == set(CASES)
+    assert (digest(generate(seed, world)), digest(generate(seed, world, history_from_start=False))) == DIGESTS[world, seed]
+    assert digest(generate(seed, world, generation=1)) == DIGESTS[world, seed][0]
+
+
+# -- CPU: the second generation ------------------------------------------------------------------------------------------------------------
+CASES2 = [(w, seed, indexed) for w in sorted(st.SEEDS2) for seed, indexed in zip(st.SEEDS2[w], (False, True))]
+IDS2 = ["%s-%d-%s" % (w, seed, "indexed" if indexed else "soup") for w, seed, indexed in CASES2]
+_runs2 = {}
+
+
+def world_f32(w):
+    """(origin, scale) as the device holds them: the float32 values, as Python floats."""
+    return tuple(float(f32(v)) for v in w["origin"]), float(f32(w["scale"]))
+
+
+def probe_reference(s, seed):
+    """surface_twin's and test_sphere_queries' references of a probe's queries on the model's grid."""
+    q = st.probe_queries(s.world, seed)
+    origin, scale = world_f32(s.world)
+    grid = np.ascontiguousarray(s.ref.grid)
+    surf = Surface.of_grid(s.oracle, grid, origin, scale)
+    spheres = SphereSurface(s.oracle, grid, origin, scale)
+    return dict(q=q, surf=surf, scale=scale, rays=ray_reference(surf, q["ray_o"], q["ray_d"]),
+                casts=[spheres.cast(o, d, float(r)) for o, d, r in zip(q["cast_o"].astype(np.float64), q["cast_d"], q["cast_r"])],
+                balls=[spheres.closest(c, float(r)) for c, r in zip(q["ball_c"].astype(np.float64), q["ball_r"])])
+
+
+def unpainted(layer_ops):
+    """The layer the model would hold had no stroke been painted: the material_init and control_map operations alone."""
+    layer = None
+    for op in layer_ops:
+        if op[0] == "material_init":
+            layer = material_twin.initial(16 * op[1])
+        elif op[0] == "save_load":
+            layer = None
+        elif op[0] == "control_map" and layer is not None:
+            layer = material_twin.set_control_map(layer, st.control_image(op[1], layer.shape[0]), op[2])
+    return layer
+
+
+def twin_run2(oracle_mod, tmp_path_factory, world, seed, indexed):
+    """A second-generation session on the model alone, once per case: the model after the last operation and, per attributes, lod and
+    probe operation, what the generator conditions read."""
+    key = (world, seed, indexed)
+    if key not in _runs2:
+        tmp = tmp_path_factory.mktemp("session2_%s%d" % (world, seed))
+        s = Session(oracle_mod, world, indexed)
+        ops = generate(seed, world, generation=2)
+        notes = dict(attributes=[], lod=[], probe=[], chunk=[])
+        grids = [s.ref.grid.copy(), s.ref.grid.copy()]          # the grid before the last two operations
+        for i, op in enumerate(ops):
+            prev, loads = s.last, s.loads
+            grids = [grids[1], s.ref.grid.copy()]
+            if op[0] == "attributes":
+                geo = s.geometry() if s.result == "terrain" else None
+                layer = s.layer
+                weights, ao = s.attributes(*op[1:], geo=geo)
+                n = dict(i=i, prev=prev, result=s.result, source=s.result_source, loads=loads, layer=layer is not None, weights=weights, ao=ao,
+                         per_block=None if geo is None else geo[3])
+                if geo is not None and prev == "undo":          # the same vertices on the grid the undo replaced
+                    n["ao_before_undo"] = ao_twin.vertex_ao(grids[0], geo[0], geo[1], geo[2], op[1], s.world["scale"], op[2], op[3])
+                if weights is not None:
+                    plain_layer = unpainted(ops[:i])
+                    n["weights_unpainted"] = material_twin.vertex_weights(plain_layer, s.world["dims"], geo[0], geo[1])
+                notes["attributes"].append(n)
+                s.last = "attributes"
+            elif op[0] == "lod":
+                nodes, tiles = s.lod(*op[1:])
+                _, offs, _ = oracle_mod.extract_tiles(tiles)
+                per_level = [int(np.diff(offs)[nodes[:, 3] == lv].sum()) for lv in range(3)]
+                notes["lod"].append(dict(i=i, prev=prev, nodes=nodes, per_level=per_level))
+                s.last = "lod"
+            elif op[0] == "probe":
+                ref = probe_reference(s, op[1])
+                notes["probe"].append(dict(i=i, prev=prev, hits=sum(r["hit"] for r in ref["rays"]), n=len(ref["rays"]),
+                                           ambiguous=sum(r["ambiguous"] for r in ref["rays"]),
+                                           sphere_ambiguous=sum(r["kind"] == "ambiguous" for r in ref["casts"] + ref["balls"]),
+                                           sphere_hits=sum(r["hit"] for r in ref["casts"] + ref["balls"])))
+                s.last = "probe"
+            else:
+                if op[0] == "chunk_write":
+                    notes["chunk"].append(dict(i=i, prev=prev, all_blocks=len(s.result_dirty) == s.nb[0] * s.nb[1] * s.nb[2]))
+                s.run(op, tmp)
+        _runs2[key] = (s, ops, notes)
+    return _runs2[key]
+
+
+@pytest.mark.parametrize("world,seed,indexed", CASES2, ids=IDS2)
+def test_second_generation_is_deterministic_and_holds_its_deck(world, seed, indexed):
+    ops = generate(seed, world, generation=2)
+    assert len(ops) == st.N_OPS2 and plain(ops) == plain(generate(seed, world, generation=2))
+    assert plain(ops) != plain(generate(seed + 1000, world, generation=2))
+    assert ops[0][0] == "set_history" and ops[0][1] > 0 and ops[1][0] == "update"
+    assert all(op[1] > 0 for op in ops if op[0] == "set_history")        # the history is on from the start and stays on
+    names = [op[0] for op in ops]
+    assert names.count("stamp_from_mesh") == 3 and {op[1][0] for op in ops if op[0] == "stamp_from_mesh"} == {"icosphere", "torus", "box"}
+    assert all(6 <= n <= 12 for op in ops if op[0] == "stamp_from_mesh" for n in op[4])
+    paths = [sp for op in ops if op[0] == "update" for sp in op[1] if sp[0] == "path"]
+    n_seg = [len(sp[1]["segments"]) for sp in paths]
+    assert 1 in n_seg and max(n_seg) > _lib.PATH_CHUNK
+    assert any((np.asarray(sp[1]["segments"])[:, 0:3] == np.asarray(sp[1]["segments"])[:, 4:7]).all(axis=1).any() for sp in paths)   # a segment of length 0
+    reasons = [op[2] for op in ops if op[0] == "reject"]
+    assert set(reasons) == set(st.REJECTS2)
+    for i, op in enumerate(ops):
+        if op[0] == "chunk_write":
+            assert ops[i - 1][0] == "save_load"
+        if op[0] == "lod":
+            assert world == "c" and ops[i + 1][0] in ("undo", "redo", "update", "attributes")
+    if world == "c":
+        after = [ops[i + (2 if ops[i + 1][0] == "attributes" else 1)][0] for i, op in enumerate(ops) if op[0] == "lod"]
+        assert set(after) == {"undo", "redo", "update"}, after
+
+
+def test_long_path_has_chunks_that_most_tiles_skip(oracle_mod):
+    """csrc/terrain_path.hip skips a chunk of kPathChunk segments for a tile when their bounds, grown by max(ra, rb) + 2 and a slack, miss
+    the tile.  In every session's long path, by the same arithmetic without the slack: some (tile, chunk) pairs are apart, and every
+    chunk is near some tile."""
+    for world, seed, _ in CASES2:
+        ops = generate(seed, world, generation=2)
+        (spec,) = [sp for op in ops if op[0] == "update" for sp in op[1] if sp[0] == "path" and len(sp[1]["segments"]) > _lib.PATH_CHUNK]
+        ref = oracle_mod.Terrain(*st.WORLDS[world]["dims"], st.WORLDS[world]["scale"], st.WORLDS[world]["origin"], 1)
+        m = st.gpu_struct(spec)
+        first, ext, _ = box_of(ref, m)
+        seg = path_twin.struct_segments(m)
+        assert ext[1] > 16 and ext[2] > 4 * 4 and len(seg) > _lib.PATH_CHUNK
+        pos = lambda i, k: float(f32(i) * f32(ref.scale) + f32(ref.origin[k]))   # noqa: E731
+        apart = near = 0
+        for c0 in range(0, len(seg), _lib.PATH_CHUNK):
+            chunk = seg[c0:c0 + _lib.PATH_CHUNK]
+            grow = np.maximum(chunk[:, 3], chunk[:, 7]) + 2.5
+            lo = (np.minimum(chunk[:, 0:3], chunk[:, 4:7]) - grow[:, None]).min(axis=0)
+            hi = (np.maximum(chunk[:, 0:3], chunk[:, 4:7]) + grow[:, None]).max(axis=0)
+            near_here = 0
+            for ty in range(first[1], first[1] + ext[1], 16):
+                for tz in range(first[2], first[2] + ext[2], 4):
+                    tlo = [pos(first[0], 0), pos(ty, 1), pos(tz, 2)]
+                    thi = [pos(first[0] + ext[0] - 1, 0), pos(min(ty + 15, first[1] + ext[1] - 1), 1), pos(min(tz + 3, first[2] + ext[2] - 1), 2)]
+                    is_apart = any(thi[k] < lo[k] or tlo[k] > hi[k] for k in range(3))
+                    apart += is_apart
+                    near_here += not is_apart
+            assert near_here > 0
+            near += near_here
+        assert apart > 0 and near > 0, (world, seed, apart, near)
+
+
+@pytest.mark.parametrize("world,seed,indexed", CASES2, ids=IDS2)
+def test_generator_conditions_of_the_second_generation(oracle_mod, tmp_path_factory, world, seed, indexed):
+    s, ops, notes = twin_run2(oracle_mod, tmp_path_factory, world, seed, indexed)
+    for k in st.KINDS2:   # every old and new category
+        assert s.kinds[k] >= 3, (k, s.kinds)
+    assert s.faces["path"] == set(FACES), sorted(set(FACES) - s.faces["path"])
+    for add in (True, False):   # both clamp branches of the CSG write, for paths that add and paths that erode
+        assert s.path_taken[add]["low"] > 0 and s.path_taken[add]["high"] > 0, (add, s.path_taken)
+    for mode, counts in s.mesh_footprints.items():
+        assert counts and max(counts) > 0, (mode, counts)
+    # the history with paths in it: undone and redone, evicted by the ring, arriving on top of undone steps, after a load
+    assert all(v >= 1 for v in s.paths.values()), s.paths
+    assert s.hist.wraps >= 1 and s.hist.after_undo >= 1
+    assert all(c["prev"] == "save_load" and c["all_blocks"] for c in notes["chunk"]) and notes["chunk"]
+    # attributes
+    A = notes["attributes"]
+    print("%s %d %s: kinds %s" % (world, seed, "indexed" if indexed else "soup", s.kinds))
+    print("attributes by predecessor: %s; paths %s" % ({p: sum(a["prev"] == p for a in A) for p in sorted({a["prev"] for a in A})}, s.paths))
+    assert len(A) >= 8
+    after_undo = [a for a in A if a["prev"] == "undo"]
+    assert len(after_undo) >= 2 and sum(a["prev"] == "redo" for a in A) >= 1
+    assert any(a["source"] == "save_load" and not a["layer"] and a["ao"] is not None and a["weights"] is None for a in A)   # a load, the layer gone
+    assert any(a["source"] == "save_load" and a["layer"] and a["weights"] is not None for a in A)                           # a load, the layer back
+    if world == "c":
+        assert any(a["prev"] == "lod" and a["result"] == "lod" and a["ao"] is None and a["weights"] is None for a in A)
+    assert all(a["per_block"] is None or len(a["per_block"]) > 0 for a in A)       # no attributes of a result without a dirty block
+    ao = np.concatenate([a["ao"] for a in A if a["ao"] is not None])
+    assert (ao == 255).any() and (ao < 128).any(), (len(ao), int(ao.min()))
+    assert any(a["weights"] is not None and (a["weights"] != a["weights_unpainted"]).any() for a in A)      # vertices a paint stroke changed
+    assert any(a["per_block"] is not None and ((a["per_block"] > 0) & (a["per_block"] <= 12)).any() and (a["per_block"] > 12).any() for a in A)
+    for a in after_undo:    # a consumer that reads the grid of before the undo cannot pass
+        assert len(a["ao"]) > 0 and not np.array_equal(a["ao"], a["ao_before_undo"]), a["i"]
+    # ... nor one that reads a layer the undo reverted: the edit was painted over, then undone
+    assert any(a["weights"] is not None and ops[a["i"] - 2][0] == "paint" and (a["weights"] != a["weights_unpainted"]).any() for a in after_undo)
+    # lod
+    L = notes["lod"]
+    if world == "c":
+        print("lod levels: %s" % [np.bincount(n["nodes"][:, 3], minlength=3).tolist() for n in L])
+        assert len(L) >= 3 and any(n["prev"] == "undo" for n in L)
+        assert any(sorted(set(n["nodes"][:, 3].tolist())) == [0, 1, 2] and min(n["per_level"]) > 0 for n in L), [n["per_level"] for n in L]
+    else:
+        assert not L
+    # probe: the rule of surface_twin allows ambiguous queries below 1 % of a test's; with 32 and 16 that is none, so none is drawn
+    P = notes["probe"]
+    assert len(P) >= 4 and any(p["prev"] == "undo" for p in P) and any(p["prev"] == "save_load" for p in P)
+    for p in P:
+        assert 3 * p["hits"] >= p["n"] and p["sphere_hits"] >= 4, p
+        assert p["ambiguous"] == 0 and p["sphere_ambiguous"] == 0, p
+
 
 
 def test_twins_take_an_overridden_box(oracle_mod):
@@ -195,18 +420,80 @@ def assert_state(ex, s, tag):
     assert ex.terrain_history() == s.hist.state(), tag
 
 
+def assert_indexed(ex, oracle_mod, grid, dirty, T, tag):
+    """An indexed result as extract_checks.check_against_oracle compares one: indices and offsets exact, floats within 1e-5, and its
+    de-indexed form against the oracle's soup."""
+    grid = np.ascontiguousarray(grid)
+    want_v, want_i, want_vo, want_to = oracle_mod.extract_grid_indexed(grid, dirty)
+    soup, _, _ = oracle_mod.extract_grid(grid, dirty, threads=8)
+    assert T == len(want_i), tag
+    verts, idx, voffs, toffs = ex.read_indexed_mesh()
+    assert np.array_equal(voffs, want_vo) and np.array_equal(toffs, want_to) and np.array_equal(idx, want_i), tag
+    for f in ("position", "normal"):
+        assert np.array_equal(np.isnan(verts[f]), np.isnan(want_v[f])), tag
+        assert np.abs(np.nan_to_num(verts[f]) - np.nan_to_num(want_v[f])).max(initial=0.0) <= ATOL, (tag, f)
+    back = oracle_mod.deindex(verts, idx, voffs, toffs)
+    assert_tris_match(back, soup)
+
+
 def assert_result(ex, s, got, dirty, tag):
     n_dirty, T = got
     assert n_dirty == len(dirty) and np.array_equal(ex.terrain_dirty_blocks(), dirty), tag
-    if len(dirty):
-        assert_triangles(ex, s.oracle, s.ref.grid, dirty, T)
-    else:
+    if not len(dirty):
         assert T == 0, tag
+    elif s.indexed:
+        assert_indexed(ex, s.oracle, s.ref.grid, dirty, T, tag)
+    else:
+        assert_triangles(ex, s.oracle, s.ref.grid, dirty, T)
+    # a new result: what was computed for the one before is stale
+    assert reader_codes(ex) == (_lib.ERR_NO_RESULT, _lib.ERR_NO_RESULT), tag
+
+
+_READ = np.zeros((1 << 18, 8), np.uint8)
+
+
+def reader_codes(ex):
+    """What vtmc_material_read_vertices and vtmc_ao_read_vertices answer now."""
+    return (ex._L.vtmc_material_read_vertices(ex._h, _READ.ctypes.data, len(_READ)), ex._L.vtmc_ao_read_vertices(ex._h, _READ.ctypes.data, _READ.size))
+
+
+def code_of(fn):
+    try:
+        fn()
+    except vt.VtmcError as e:
+        return e.code
+    return _lib.OK
+
+
+def device_geometry(ex, indexed):
+    """(blocks, positions, normals, vertices per block) of the result the context holds, from the device's own records."""
+    dirty = ex.terrain_dirty_blocks()
+    if indexed:
+        verts, _, voffs, _ = ex.read_indexed_mesh()
+        return ao_twin.indexed_vertices(verts, voffs, dirty) + (np.diff(voffs),)
+    tris, offs = ex.read_triangles()
+    return ao_twin.soup_vertices(tris, dirty) + (3 * np.diff(offs),)
+
+
+def assert_bytes(got, want, tag):
+    assert got.shape == want.shape and got.dtype == np.uint8, (tag, got.shape, want.shape)
+    bad = np.argwhere(got != want)
+    assert not len(bad), "%s: %d of %d bytes differ, first at %s: %s != %s" % (tag, len(bad), got.size, bad[0], got[tuple(bad[0])], want[tuple(bad[0])])
+
+
+def assert_stamps(ex, s, tag):
+    for sid, want in s.stamps.items():
+        assert np.array_equal(bits(ex.stamp_read(sid)), bits(want)), (tag, sid)
 
 
 def describe(s, i, op):
     if op[0] in ("update", "reject"):
-        return "op %d %s %s" % (i, op[0], [(st.category(sp), "box" if len(sp) > 2 else "own", *box_of(s.ref, stamp_twin.gpu_struct(sp))[:2]) for sp in op[1]])
+        return "op %d %s %s" % (i, op[0], [(st.category(sp, s.mesh_ids), "box" if len(sp) > 2 else "own", *box_of(s.ref, st.gpu_struct(sp))[:2]) for sp in op[1]])
+    if op[0] == "paint":
+        return "op %d paint %s (layer %s)" % (i, [(tuple(round(v, 3) for v in c), round(r, 3), ch) for c, r, ch, _ in op[1]], "present" if s.layer is not None else "missing")
+    if op[0] in ("attributes", "lod", "probe", "chunk_write", "control_map", "material_init", "stamp_from_mesh"):
+        return "op %d %r on the result of %s (%s), layer %s" % (i, op, s.result_source, "%d dirty blocks" % len(s.result_dirty) if s.result == "terrain" else s.result,
+                                                                 "present" if s.layer is not None else "missing")
     return "op %d %r" % (i, op[:1] + tuple(op[1:])[:3])
 
 
@@ -216,7 +503,7 @@ def step_session(ex, s, op, tmp, tag, mine):
     name = op[0]
     if name == "update":
         before = s.ref._mem.copy()
-        got = ex.terrain_update([stamp_twin.gpu_struct(sp) for sp in op[1]])
+        got = ex.terrain_update([st.gpu_struct(sp) for sp in op[1]])
         dirty = s.update(op[1])
         assert_state(ex, s, tag)
         assert_result(ex, s, got, dirty, tag)
@@ -275,15 +562,127 @@ def step_session(ex, s, op, tmp, tag, mine):
         mine["undo"].clear(), mine["redo"].clear()
         assert_state(ex, s, tag)
         assert_result(ex, s, got, dirty, tag)
+        assert code_of(ex.material_read) == _lib.ERR_NO_RESULT, tag + ": a load drops the material layer"
     elif name == "reject":
-        mods = [stamp_twin.gpu_struct(sp) for sp in op[1]] + [st.bad_modifier(op[2])]
+        mods = [st.gpu_struct(sp) for sp in op[1]] + [st.bad_modifier(op[2])]
         with pytest.raises(vt.VtmcError) as e:
             ex.terrain_update(mods)
         assert e.value.code == _lib.ERR_INVALID_ARG and "modifier %d" % len(op[1]) in str(e.value), (tag, str(e.value))
         s.reject(op[1])
         assert_state(ex, s, tag)   # history on: nothing changed; off: the prefix, and its event numbers (the next draws hash them)
+    elif name == "stamp_from_mesh":
+        want = s.stamp_from_mesh(*op[1:])
+        v, t = st.mesh_of(op[1])
+        sid = ex.stamp_from_mesh(v, t, *op[2:])
+        assert sid == want and ex.stamp_dims(sid) == tuple(op[4]), tag
+        got = ex.stamp_read(sid)
+        diff = np.argwhere(bits(got) != bits(s.stamps[want]))
+        assert not len(diff), "%s: %d samples differ, first at %s" % (tag, len(diff), diff[0])
+        assert_state(ex, s, tag)
+    elif name == "material_init":
+        want = s.material_init(op[1])
+        assert ex.material_init(op[1]) == want.shape[0], tag
+        assert_bytes(ex.material_read(), want, tag)
+        assert reader_codes(ex)[0] == _lib.ERR_NO_RESULT, tag        # the weights of the layer before are gone
+    elif name in ("paint", "control_map"):
+        had = s.layer is not None
+        call = (lambda: ex.paint([vt.MaterialStroke(*k) for k in op[1]])) if name == "paint" else \
+            (lambda: ex.set_control_map(st.control_image(op[1], s.layer.shape[0] if had else 16), op[2]))
+        want = s.paint(op[1]) if name == "paint" else s.control_map(*op[1:])
+        if want is None:   # no layer since the last load
+            assert code_of(call) == _lib.ERR_NO_RESULT and code_of(ex.material_read) == _lib.ERR_NO_RESULT, tag
+        else:
+            before = reader_codes(ex)
+            call()
+            assert_bytes(ex.material_read(), want, tag)
+            assert reader_codes(ex) == before, tag                   # paint leaves the result and its weights alone
+        assert_state(ex, s, tag)
+    elif name == "attributes":
+        radius, strength, steps = op[1:]
+        if s.result != "terrain":   # a level-of-detail result, or none: both passes and both readers refuse
+            assert s.attributes(*op[1:]) == (None, None)
+            assert code_of(ex.material_vertices) == _lib.ERR_NO_RESULT and code_of(lambda: ex.vertex_ao(radius, strength, steps)) == _lib.ERR_NO_RESULT, tag
+            assert reader_codes(ex) == (_lib.ERR_NO_RESULT, _lib.ERR_NO_RESULT), tag
+        else:
+            geo = device_geometry(ex, s.indexed)
+            want_w, want_ao = s.attributes(radius, strength, steps, geo)
+            if want_w is None:      # no layer: VTMC_ERR_NO_RESULT, and the occlusion does not need one
+                assert code_of(ex.material_vertices) == _lib.ERR_NO_RESULT, tag
+            else:
+                assert_bytes(ex.vertex_materials(), want_w, tag + " weights")
+            assert_bytes(ex.vertex_ao(radius, strength, steps), want_ao, tag + " occlusion")
+            assert reader_codes(ex) == (_lib.OK if want_w is not None else _lib.ERR_NO_RESULT, _lib.OK), tag
+        assert_state(ex, s, tag)
+    elif name == "lod":
+        w = s.world
+        n, T = ex.terrain_extract_lod(st.viewer_world(w, op[1]), op[2], op[3])
+        nodes, tiles = s.lod(*op[1:])
+        assert n == len(nodes) and np.array_equal(ex.terrain_lod_nodes(), nodes), tag
+        got_tiles = np.zeros((n, 1000), f32)
+        assert ex._L.vtmc_debug_lod_tiles(ex._h, got_tiles.ctypes.data, got_tiles.size) == _lib.OK
+        assert np.array_equal(bits(got_tiles), bits(tiles)), tag + ": the gathered tiles"
+        want, offs, cases = s.oracle.extract_tiles(tiles)
+        assert T == len(want) and ex.last_counts() == (n, T) and np.array_equal(ex.read_cases(), cases), tag
+        if s.indexed:
+            verts, idx, voffs, toffs = ex.read_indexed_mesh()
+            assert np.array_equal(toffs, offs), tag
+            assert_tris_match(s.oracle.deindex(verts, idx, voffs, toffs), want)
+        else:
+            got, goffs = ex.read_triangles()
+            assert np.array_equal(goffs, offs), tag
+            assert_tris_match(got, want)
+        assert reader_codes(ex) == (_lib.ERR_NO_RESULT, _lib.ERR_NO_RESULT), tag
+        assert_state(ex, s, tag)        # the grid and the history are as they were
+        assert_stamps(ex, s, tag)
+    elif name == "probe":
+        ref = probe_reference(s, op[1])
+        q, scale = ref["q"], ref["scale"]
+        hits = ex.terrain_raycast(q["ray_o"], q["ray_d"])
+        n_amb = compare_rays(hits, ref["rays"], scale, tag)
+        check_tight(hits, ref["rays"], ref["surf"], tag)
+        assert n_amb < 0.01 * len(hits), (tag, n_amb)
+        check_spheres(ex.terrain_spherecast(q["cast_o"], q["cast_d"], q["cast_r"]), ref["casts"], scale, tag + " sphere casts")
+        check_spheres(ex.terrain_closest_point(q["ball_c"], q["ball_r"]), ref["balls"], scale, tag + " closest points")
+        assert_state(ex, s, tag)
+    elif name == "chunk_write":
+        from volumetricterrain_amd import chunkfile
+        path = os.path.join(tmp, "chunk.vtchunk")
+        ex.chunk_write(path, 0, (0, 0, 0), with_samples=True)
+        f = chunkfile.read_chunk(path)
+        grid = np.ascontiguousarray(s.ref.grid)
+        assert f["origin"] == (0, 0, 0) and f["cells"] == tuple(s.world["dims"]) and f["flags"] == (1 | (4 if s.indexed else 2)), tag
+        assert np.array_equal(bits(f["samples"]), bits(np.ascontiguousarray(grid.transpose(2, 1, 0)).ravel())), tag
+        if s.indexed:
+            verts, idx, voffs, toffs = s.oracle.extract_grid_indexed(grid)
+            assert np.array_equal(f["tri_offsets"], toffs.astype(np.uint32)) and np.array_equal(f["vert_offsets"], voffs.astype(np.uint32)), tag
+            assert np.array_equal(f["indices"], idx), tag
+            assert np.abs(f["vertices"]["position"] - verts["position"]).max() <= ATOL and np.abs(f["vertices"]["normal"] - verts["normal"]).max() <= ATOL, tag
+        else:
+            want, want_offs, _ = s.oracle.extract_grid(grid, threads=8)
+            assert np.array_equal(f["tri_offsets"], want_offs.astype(np.uint32)), tag
+            assert_tris_match(f["triangles"], want)
+        assert_state(ex, s, tag)
     else:
         raise AssertionError(name)
+    s.last = name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("world,seed,indexed", CASES2, ids=IDS2)
+def test_gpu_session_second_generation(oracle_mod, tmp_path, world, seed, indexed):
+    """Worlds b and c, one soup and one indexed session each, the history on from the start: paths and mesh stamps in the queues, the
+    material layer, vertex attributes, level of detail, queries and the chunk file between them."""
+    w = st.WORLDS[world]
+    ops = generate(seed, world, generation=2)
+    s = Session(oracle_mod, world, indexed)
+    mine = {"undo": [], "redo": []}
+    with vt.Extractor(0) as ex:
+        ex.set_output_mode(indexed)
+        ex.terrain_init(*w["dims"], w["scale"], w["origin"], w["seed"])
+        assert_state(ex, s, "init")
+        for i, op in enumerate(ops):
+            step_session(ex, s, op, str(tmp_path), describe(s, i, op), mine)
+        assert_stamps(ex, s, "the end")
 
 
 @pytest.mark.gpu
@@ -331,12 +730,79 @@ def matrix_specs(first, ext, stamp_id, stamp_dims):
     box = (tuple(float(v) for v in first), tuple(float(first[k] + ext[k] - 1) for k in range(3)))
     hm = (12.0 + 8.0 * np.sin(np.linspace(0, 3, 48))[:, None] * np.cos(np.linspace(0, 2, 40))[None, :]).astype(f32)
     noise = dict(seed=7, octaves=2, frequency=0.21, amplitude=1.5, ramp_scale=0.3, ramp_center=20.0, lower=box[0], upper=box[1])
-    return [("plane", (20.375, (0, 0), (80, 80), True), box), ("sphere", ((37.0, 20.0, 13.0), 30.0, False), box),
+    path = dict(segments=matrix_segments())
+    return [("path", dict(path, addOrErode=True), box), ("path", dict(path, addOrErode=False), box),
+            ("plane", (20.375, (0, 0), (80, 80), True), box), ("sphere", ((37.0, 20.0, 13.0), 30.0, False), box),
             ("cylinder", ((0.0, 20.0, 12.0), (1.0, 0.1, 0.05), 80.0, 9.0, True), box), ("island", (hm, 74.0, 26.0, 60.0, True), box),
             ("flatten", ((37.0, 21.0, 13.0), (0.2, 1.0, 0.1), 200.0, 0.75), box), ("smooth", ((37.0, 21.0, 13.0), 200.0, 0.5), box),
             ("noise", dict(noise, basis="fbm", add_or_erode=True)), ("noise", dict(noise, basis="billow", add_or_erode=False)),
             ("noise", dict(noise, basis="ridged", add_or_erode=True)),
             ("stamp", dict(stamp_id=stamp_id, dims=stamp_dims, position=(36.8, 20.7, 12.9), pitch=2.0, mode="replace"), box)]
+
+
+N_CLUSTER = _lib.PATH_CHUNK + 4
+
+
+def matrix_segments():
+    """The path of the matrix: more than kPathChunk short segments clustered about sample (64, 30, 20), where the walk's second x-segment
+    begins, and behind them three long ones through the grid.  The first chunk is the cluster alone: a tile farther than radius + 2 from
+    it skips it whole, and the second chunk -- the cluster's last four and the long segments -- survives in most tiles."""
+    rng = np.random.default_rng(77)
+    a = np.array([64.0, 30.0, 20.0]) + rng.uniform(-3.0, 3.0, (N_CLUSTER, 3))
+    b = a + rng.uniform(-1.5, 1.5, (N_CLUSTER, 3))
+    cluster = np.column_stack([a, rng.uniform(0.3, 1.0, N_CLUSTER), b, rng.uniform(0.3, 1.0, N_CLUSTER)])
+    long_ones = [[2.0, 20.0, 3.0, 2.5, 70.0, 24.0, 22.0, 1.5], [5.0, 38.0, 20.0, 2.0, 68.0, 4.0, 6.0, 3.0], [36.0, 0.0, 13.0, 1.5, 38.0, 41.0, 12.0, 2.5]]
+    return np.concatenate([cluster, long_ones])
+
+
+_matrix_q = {}
+
+
+def matrix_density(cluster=True):
+    """q of the matrix's path on every sample of the 74 x 42 x 26 grid, [z, y, x], by path_twin.path_density, once per process.  The rule
+    is pointwise and a sample's position depends on its own index alone, so the density of any box is this array's slice."""
+    if cluster not in _matrix_q:
+        seg = vt.PathModifier(matrix_segments()[0 if cluster else N_CLUSTER:]).segments
+        px, py, pz = (np.arange(d + 2).astype(f32) * f32(1.0) + f32(0.0) for d in M_DIMS)
+        _matrix_q[cluster] = path_twin.path_density(seg, px[None, None, :], py[None, :, None], pz[:, None, None])
+    return _matrix_q[cluster]
+
+
+def matrix_twin_update(ref, oracle_mod, spec, stamps, counts, cluster=True):
+    """stamp_twin.twin_update for one spec of the matrix; a path takes its density from matrix_density's slice."""
+    if spec[0] != "path":
+        return stamp_twin.twin_update(ref, oracle_mod, [spec], stamps, counts)
+    first, ext, ids = box_of(ref, st.gpu_struct(spec))
+    (lx, ly, lz), (dx, dy, dz) = first, ext
+    csg_write(ref, first, ext, matrix_density(cluster)[lz:lz + dz, ly:ly + dy, lx:lx + dx], spec[1]["addOrErode"])
+    return block_list(ids, tuple(d // 8 for d in ref.dims))
+
+
+def ground(oracle_mod):
+    """The matrix's terrain under a plane at height 30.375, through the middle of the cluster: an adding path shows above it, an eroding one below."""
+    ref = oracle_mod.Terrain(*M_DIMS, 1.0, (0.0, 0.0, 0.0), M_SEED)
+    stamp_twin.twin_update(ref, oracle_mod, [("plane", (30.375, (-1, -1), (80, 80), True))], {})
+    return ref
+
+
+def test_matrix_path_twin_and_its_pruned_chunk(oracle_mod):
+    """The sliced density is path_twin's own on a box, and on the whole grid the clustered segments matter on both x-segments of the walk:
+    a kernel that drops the cluster's chunk where it must keep it cannot pass."""
+    whole = ((0.0, 0.0, 0.0), tuple(float(d + 1) for d in M_DIMS))
+    box = ((59.0, 19.0, 11.0), (70.0, 37.0, 24.0))
+    for add in (True, False):
+        for b in (box, whole):
+            spec = ("path", dict(segments=matrix_segments(), addOrErode=add), b)
+            one, two = (ground(oracle_mod) for _ in range(2))
+            d1 = path_twin.twin_update(one, oracle_mod, [spec])
+            d2 = matrix_twin_update(two, oracle_mod, spec, {}, [])
+            assert np.array_equal(bits(one.grid), bits(two.grid)) and np.array_equal(d1, d2) and one.events == two.events == 2
+        without = ground(oracle_mod)
+        matrix_twin_update(without, oracle_mod, spec, {}, [], cluster=False)
+        differ = np.argwhere(bits(one.grid) != bits(without.grid))
+        assert (differ[:, 0] < 64).any() and (differ[:, 0] >= 64).any(), (add, len(differ))
+    seg = matrix_segments()
+    assert len(seg) > _lib.PATH_CHUNK + 3 and M_DIMS[0] + 2 == 74
 
 
 def test_matrix_covers_the_seams():
@@ -369,11 +835,11 @@ def test_gpu_box_matrix(oracle_mod, ext, history):
         for first in placements(ext):
             for spec in matrix_specs(first, ext, 1, (40, 24, 16)):
                 tag = "%s box %s + %s" % (st.category(spec), first, ext)
-                assert box_of(ref, stamp_twin.gpu_struct(spec))[:2] == (list(first), list(ext)), tag
+                assert box_of(ref, st.gpu_struct(spec))[:2] == (list(first), list(ext)), tag
                 before = ref._mem.copy()
-                n_dirty, _ = ex.terrain_update([stamp_twin.gpu_struct(spec)])
+                n_dirty, _ = ex.terrain_update([st.gpu_struct(spec)])
                 counts = []
-                dirty = stamp_twin.twin_update(ref, oracle_mod, [spec], stamps, counts)
+                dirty = matrix_twin_update(ref, oracle_mod, spec, stamps, counts)
                 assert not counts or counts[0] == ext[0] * ext[1] * ext[2], tag
                 got = bits(ex.terrain_read_samples())
                 assert np.array_equal(got, bits(ref.grid)), (tag, np.argwhere(got != bits(ref.grid))[:4])
