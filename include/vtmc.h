@@ -742,6 +742,79 @@ int32_t vtmc_ao_read_vertices(vtmc_ctx *ctx, uint8_t *dst, int64_t capacity_vert
 int32_t vtmc_ao_device_results(vtmc_ctx *ctx, const uint8_t **d_ao, int64_t *n_vertices);
 
 /* ------------------------------------------------------------------------------------------
+ * Surface scatter -- the third consumer of a terrain extract (not in the reference): instances (grass, rocks, trees) distributed over the
+ * triangles of the result by area, filtered by slope, world height and one channel of the material layer, on the device, in either
+ * output mode.  It is STABLE UNDER EDITS: every random draw is keyed on the triangle's own vertex coordinates in the grid, not on its
+ * index in the result, so a block whose triangles an edit left as they were gets exactly the instances it had; a host replaces the
+ * instances of the dirty blocks only.  The life cycle is that of the vertex attributes: computed on demand for the result the context
+ * holds, library-owned, stale after the next extract.
+ *
+ * All arithmetic is FP32, one IEEE operation per step in the order written (library built with -ffp-contract=off); / and sqrtf are
+ * correctly rounded; 64-bit integer arithmetic wraps.
+ *
+ * Hash:  fin(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31   (the finaliser of
+ *   the terrain's own counter hash);  G = 0x9E3779B97F4A7C15;  step(k, w) = fin((k ^ (uint64)w) + G).
+ * Triangle key:  per corner c and axis a:  g[c][a] = ((float)(8*b_a) + p[c][a]) + 0.0f, with (bx, by, bz) the block as
+ *   vtmc_material_vertices finds it and p the block-local position in the record (indexed: of the vtmc_vertex the index names; the
+ *   + 0.0f turns -0 into +0);  k = fin((uint64)seed + G);  then for c = 0..2, a = 0..2 in that order:  k = step(k, bits(g[c][a])).
+ * Draws:  word(k, i, d) = step(k, ((uint64)i << 8) | d);  U(k, i, d) = (float)(uint32)(word >> 40) * 2^-24;
+ *   rnd = (uint32)(word(k, i, 4) >> 32).
+ * Per triangle, from the block-local positions p0, p1, p2 and normals n0, n1, n2:
+ *     e1 = p1 - p0;  e2 = p2 - p0
+ *     cx = e1.y*e2.z - e1.z*e2.y;  cy = e1.z*e2.x - e1.x*e2.z;  cz = e1.x*e2.y - e1.y*e2.x
+ *     L = sqrtf((cx*cx + cy*cy) + cz*cz);   if (!(L > 0) || !(L < INFINITY)):  no instances      (degenerate triangles exist in every terrain)
+ *     up = cy / L;   if (!(min_up <= up && up <= max_up)):  no instances
+ *       (cross(p1 - p0, p2 - p0) points out of the solid, as the record normals do: flat ground under a plane modifier has up = 1)
+ *     dc = density * (voxel_scale * voxel_scale), computed on the host;   lam = (0.5f * L) * dc;   fl = floorf(lam)
+ *     n = (int)fl + (U(k, 0, 0) < lam - fl ? 1 : 0);   n = min(n, VTMC_SCATTER_MAX_PER_TRIANGLE)
+ *       (a triangle inside a unit cell has area at most sqrt(3)/2, so with dc <= 8 the cap never binds)
+ * Per candidate i = 0..n-1:
+ *     u = U(k, i, 1);  v = U(k, i, 2);   if (u + v > 1.0f):  u = 1.0f - u;  v = 1.0f - v
+ *     q = (p0 + e1*u) + e2*v per component;   nrm = (n0 + (n1 - n0)*u) + (n2 - n0)*v per component
+ *     world_a = origin_a + ((float)(8*b_a) + q_a) * voxel_scale;   keep iff min_y <= world_y && world_y <= max_y
+ *     if material_channel >= 0:  w = the byte vtmc_material_vertices would give a vertex of this block at block-local position q, in that
+ *       channel;  keep iff U(k, i, 3) * 255.0f < (float)w
+ * Output: the survivors in triangle order, then by ascending i.  block_instance_offsets[b] = the number of instances on blocks before b of
+ *   the result's block list; entry B is the total.
+ *
+ * vtmc_scatter_surface  computes the instances of the result the context holds into library-owned, grow-only buffers; *n_instances (may
+ *   be NULL) receives their number.  VTMC_ERR_NO_RESULT without a terrain, without a result, when the result did not come from the
+ *   terrain's dirty list (vtmc_extract_*, vtmc_terrain_extract_lod), or with material_channel >= 0 and no material layer.
+ *   VTMC_ERR_INVALID_ARG, with nothing computed and the previous instances kept: null ctx or params; density not finite or <= 0;
+ *   dc > VTMC_SCATTER_MAX_DENSITY_CELLS; a NaN in, or min > max of, either band; material_channel outside -1..7; max_instances <= 0;
+ *   flags != 0.  VTMC_ERR_TOO_LARGE when the total exceeds max_instances: nothing is emitted, the context then holds no scatter, and
+ *   vtmc_last_error carries the total, so a host can retry.  T = 0 is success with 0 instances and an all-zero offsets array.
+ *   The instances belong to one result: after any later extract vtmc_scatter_read / _device_results answer VTMC_ERR_NO_RESULT until
+ *   vtmc_scatter_surface runs again.  Painting or editing afterwards does not change instances already made; the vertex weights and
+ *   occlusion bytes of the same result are not disturbed, nor do they disturb the instances.
+ * vtmc_scatter_read  copies the instances and (when not NULL) the B + 1 offsets; a capacity below the total is VTMC_ERR_INVALID_ARG.
+ * vtmc_scatter_device_results  the device pointers of the same (valid until the next vtmc_scatter_surface / destroy); each may be NULL.
+ * ------------------------------------------------------------------------------------------ */
+#define VTMC_SCATTER_MAX_DENSITY_CELLS 8.0f   /* density * voxel_scale^2 above this: VTMC_ERR_INVALID_ARG */
+#define VTMC_SCATTER_MAX_PER_TRIANGLE 8
+
+typedef struct vtmc_scatter_params {
+    float density;            /* instances per world unit^2, finite, > 0 */
+    float min_up, max_up;     /* keep a triangle when min_up <= up <= max_up (up: y of its unit face normal); not NaN, min <= max */
+    float min_y, max_y;       /* world height band of an instance; not NaN (infinities = no bound), min <= max */
+    int32_t material_channel; /* -1: no material filter; 0..7: keep with probability weight/255 of that channel */
+    uint32_t seed;
+    int32_t max_instances;    /* > 0 */
+    uint32_t flags;           /* reserved, 0 */
+} vtmc_scatter_params;        /* 36 bytes */
+
+typedef struct vtmc_instance {
+    float position[3];        /* world */
+    float normal[3];          /* the record normals interpolated, un-normalised */
+    uint32_t triangle;        /* index of the triangle in the result (soup record / index triple) */
+    uint32_t rnd;             /* 32 random bits of the instance (rotation, scale, variant are the host's to derive) */
+} vtmc_instance;              /* 32 bytes */
+
+int32_t vtmc_scatter_surface(vtmc_ctx *ctx, const vtmc_scatter_params *params, int64_t *n_instances);
+int32_t vtmc_scatter_read(vtmc_ctx *ctx, vtmc_instance *dst, int64_t capacity, int32_t *block_instance_offsets /* B+1, may be NULL */);
+int32_t vtmc_scatter_device_results(vtmc_ctx *ctx, const vtmc_instance **d_instances, const int32_t **d_block_offsets, int64_t *n_instances);
+
+/* ------------------------------------------------------------------------------------------
  * Level of detail -- meshing the resident terrain coarsely far from a viewer (not in the reference, which meshes every block at full
  * resolution and is capped at 1025 samples per axis for it).  vtmc_terrain_extract_lod chooses an octree of NODES around a viewer on the
  * host, gathers every node's 10x10x10 tile from the resident grid on the device and runs the ordinary extraction on the packed tiles.

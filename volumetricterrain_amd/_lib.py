@@ -30,6 +30,9 @@ SPHERE_HIT_DTYPE = np.dtype([("distance", "<f4"), ("point", "<f4", 3), ("normal"
                              ("triangle", "<i4")])
 assert SPHERE_HIT_DTYPE.itemsize == 48
 SPHERE_MAX_RADIUS_CELLS = 16
+# vtmc_instance: one instance of vtmc_scatter_surface
+INSTANCE_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("triangle", "<u4"), ("rnd", "<u4")])
+assert INSTANCE_DTYPE.itemsize == 32
 OUTPUT_SOUP, OUTPUT_INDEXED = 0, 1
 
 OK = 0
@@ -57,6 +60,7 @@ SYMBOLS = [
     "vtmc_material_init", "vtmc_material_set_control_map", "vtmc_material_write", "vtmc_material_read", "vtmc_material_paint",
     "vtmc_material_vertices", "vtmc_material_read_vertices", "vtmc_material_device_results",
     "vtmc_ao_vertices", "vtmc_ao_read_vertices", "vtmc_ao_device_results",
+    "vtmc_scatter_surface", "vtmc_scatter_read", "vtmc_scatter_device_results",
     "vtmc_terrain_extract_lod", "vtmc_terrain_lod_nodes",
 ]
 COMM_ID_BYTES = 128
@@ -70,6 +74,7 @@ MOD_PATH = 10                     # union of tapered capsules over a segment sou
 PATH_CHUNK, PATH_MAX_SEGMENTS = 256, 65536   # csrc/terrain_path.h: segments a workgroup prunes at a time; the most a modifier may hold
 MATERIAL_CHANNELS, MATERIAL_MAX_STROKES = 8, 4096   # the material layer: bytes per texel and per vertex; the most strokes of one paint call
 AO_MAX_STEPS, AO_MAX_RADIUS_CELLS = 8, 6   # vtmc_ao_vertices: the most steps of a march; the largest radius in cells (radius / voxel_scale)
+SCATTER_MAX_DENSITY_CELLS, SCATTER_MAX_PER_TRIANGLE = 8.0, 8   # vtmc_scatter_surface: the largest density * voxel_scale^2; the most instances of a triangle
 LOD_MAX_LEVEL = 7                 # vtmc_terrain_extract_lod: the coarsest level of a node (128 fine cells per node cell)
 MOD_NOISE = 8                     # fBm / billow / ridged noise (RidgedMultifractalModifier's device form); 6 and 7 are not defined
 
@@ -90,6 +95,19 @@ class MaterialStroke(ctypes.Structure):
 class AoParams(ctypes.Structure):
     """vtmc_ao_params: radius in world units, strength in [0, 1], steps 1..AO_MAX_STEPS, flags 0."""
     _fields_ = [("radius", ctypes.c_float), ("strength", ctypes.c_float), ("steps", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class ScatterParams(ctypes.Structure):
+    """vtmc_scatter_params: density per world unit^2, the slope band on the face normal's y, the world height band, the material channel
+    (-1: none), the seed, the most instances the call may make, flags 0."""
+    _fields_ = [("density", ctypes.c_float), ("min_up", ctypes.c_float), ("max_up", ctypes.c_float), ("min_y", ctypes.c_float),
+                ("max_y", ctypes.c_float), ("material_channel", ctypes.c_int32), ("seed", ctypes.c_uint32), ("max_instances", ctypes.c_int32),
+                ("flags", ctypes.c_uint32)]
+
+
+class Instance(ctypes.Structure):
+    """vtmc_instance: world position, interpolated record normal, the triangle's index in the result, 32 random bits."""
+    _fields_ = [("position", ctypes.c_float * 3), ("normal", ctypes.c_float * 3), ("triangle", ctypes.c_uint32), ("rnd", ctypes.c_uint32)]
 
 
 class LodParams(ctypes.Structure):
@@ -234,6 +252,12 @@ def load(path=None):
         L.vtmc_ao_device_results.argtypes = [vp, P(vp), P(i64)]
         L.vtmc_debug_ao_routes.argtypes = [vp, P(u32 * 2), i32]   # not in the header: the route counters of the last vtmc_ao_vertices
         L.vtmc_debug_ao_routes.restype = i32
+    if not explicit or hasattr(L, "vtmc_scatter_surface"):
+        L.vtmc_scatter_surface.argtypes = [vp, P(ScatterParams), P(i64)]
+        L.vtmc_scatter_read.argtypes = [vp, vp, i64, vp]
+        L.vtmc_scatter_device_results.argtypes = [vp, P(vp), P(vp), P(i64)]
+        L.vtmc_debug_scatter_ms.argtypes = [vp, P(ctypes.c_float * 4)]   # not in the header: device time of the last scatter's four kernels
+        L.vtmc_debug_scatter_ms.restype = i32
     if not explicit or hasattr(L, "vtmc_terrain_extract_lod"):
         L.vtmc_terrain_extract_lod.argtypes = [vp, P(LodParams), P(i32), P(i32)]
         L.vtmc_terrain_lod_nodes.argtypes = [vp, vp, i32, P(i32)]

@@ -145,6 +145,8 @@ int32_t vtmc_create(int32_t device, vtmc_ctx **out_ctx)
         if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
     for (auto &ev : ctx->ev_lod)
         if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
+    for (auto &ev : ctx->ev_scatter)
+        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreateWithFlags(&ctx->ev_origins, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = pin(ctx->h_totals, 64 * sizeof(uint32_t))) != hipSuccess) return bail("hipHostMalloc", e);
     memset(ctx->h_totals.p, 0, 64 * sizeof(uint32_t));
@@ -193,6 +195,8 @@ int32_t vtmc_destroy(vtmc_ctx *ctx)
     for (auto &ev : ctx->ev_fill)
         if (ev) quiet(hipEventDestroy(ev));
     for (auto &ev : ctx->ev_lod)
+        if (ev) quiet(hipEventDestroy(ev));
+    for (auto &ev : ctx->ev_scatter)
         if (ev) quiet(hipEventDestroy(ev));
     if (ctx->ev_gather) quiet(hipEventDestroy(ctx->ev_gather));
     if (ctx->ev_last_gather) quiet(hipEventDestroy(ctx->ev_last_gather));

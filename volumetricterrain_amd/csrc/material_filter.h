@@ -1,0 +1,114 @@
+// material_filter.h -- the material layer's trilinear filter and the block mapping of a terrain result, shared by the passes that read the
+// layer at points of the surface: the vertex weights (terrain_material.hip) and the material filter of the scatter (terrain_scatter.hip).
+// One piece of code, so both follow the rule of include/vtmc.h (vtmc_material_vertices) operation by operation.  Device code only.
+#ifndef VTMC_MATERIAL_FILTER_H
+#define VTMC_MATERIAL_FILTER_H
+#include "vtmc_internal.h"
+#include <cmath>
+
+namespace vtmc {
+
+struct MaterialVertexArgs {
+    const uint2 *layer;  // C^3 texels, x fastest
+    int C;
+    float s[3];       // texels per cell, per axis
+    const int *list;  // device (bx, by, bz) triples of the dirty list, or null: every block, b = bx + nbx * (by + nby * bz)
+    uint32_t n_blocks;
+    int nbx, nby;
+    FastDiv d_nbx, d_nby;
+};
+
+// (bx, by, bz) of block b, an index into the dirty list
+__device__ __forceinline__ void material_block(const MaterialVertexArgs &a, uint32_t b, int &bx, int &by, int &bz)
+{
+    if (b >= a.n_blocks) b = a.n_blocks - 1;  // never taken for a result of the library; keeps a foreign record inside the list
+    if (a.list) {
+        bx = a.list[3 * (size_t)b], by = a.list[3 * (size_t)b + 1], bz = a.list[3 * (size_t)b + 2];
+    } else {
+        const unsigned q = a.d_nbx.quot(b);
+        bx = (int)(b - q * (unsigned)a.nbx);
+        bz = (int)a.d_nby.quot(q);
+        by = (int)(q - (unsigned)bz * (unsigned)a.nby);
+    }
+}
+
+// the largest b in [lo, hi] with off[b] <= v (off[lo] <= v holds): the block whose range of the offsets holds v, empty blocks skipped
+__device__ __forceinline__ uint32_t material_block_of(const uint32_t *__restrict__ off, uint32_t lo, uint32_t hi, uint32_t v)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (off[mid] <= v) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// tx = g * s - 0.5 cut into the texel below it, wrapped as a Repeat texture, the one after it, and the weight
+__device__ __forceinline__ void material_axis(float g, float s, int C, int &i0, int &i1, float &f)
+{
+    float t = g * s;
+    t = t - 0.5f;
+    i0 = (int)floorf(t);
+    f = t - (float)i0;
+    // ((i0 % C) + C) % C; a vertex of the terrain gives i0 in -1..C-1, which needs no division
+    if (i0 == -1) i0 = C - 1;
+    else if ((unsigned)i0 >= (unsigned)C) i0 = ((i0 % C) + C) % C;
+    i1 = i0 + 1 == C ? 0 : i0 + 1;
+}
+
+__device__ __forceinline__ float material_channel(uint2 w, int k) { return (float)(((k < 4 ? w.x : w.y) >> (8 * (k & 3))) & 0xffu); }
+
+// a + (b - a) * f per channel k of two texels
+__device__ __forceinline__ float material_lerp(uint2 a, uint2 b, int k, float f)
+{
+    const float x = material_channel(a, k), y = material_channel(b, k);
+    return x + (y - x) * f;
+}
+
+// the eight texels around a point and its three weights
+struct MaterialTaps {
+    uint2 m000, m100, m010, m110, m001, m101, m011, m111;
+    float fx, fy, fz;
+};
+
+// the taps of block-local position p of block (bx, by, bz)
+__device__ __forceinline__ MaterialTaps material_taps(const MaterialVertexArgs &a, int bx, int by, int bz, float p0, float p1, float p2)
+{
+    const float gx = (float)(8 * bx) + p0, gy = (float)(8 * by) + p1, gz = (float)(8 * bz) + p2;
+    int i0, i1, j0, j1, k0, k1;
+    MaterialTaps t;
+    material_axis(gx, a.s[0], a.C, i0, i1, t.fx);
+    material_axis(gy, a.s[1], a.C, j0, j1, t.fy);
+    material_axis(gz, a.s[2], a.C, k0, k1, t.fz);
+    const int C = a.C;
+    const int r00 = C * (j0 + C * k0), r10 = C * (j1 + C * k0), r01 = C * (j0 + C * k1), r11 = C * (j1 + C * k1);
+    const uint2 *__restrict__ m = a.layer;
+    t.m000 = m[r00 + i0], t.m100 = m[r00 + i1], t.m010 = m[r10 + i0], t.m110 = m[r10 + i1];
+    t.m001 = m[r01 + i0], t.m101 = m[r01 + i1], t.m011 = m[r11 + i0], t.m111 = m[r11 + i1];
+    return t;
+}
+
+// the byte of channel k: along x, then y, then z, rounded ties to even
+__device__ __forceinline__ uint32_t material_filter_channel(const MaterialTaps &t, int k)
+{
+    const float a00 = material_lerp(t.m000, t.m100, k, t.fx), a10 = material_lerp(t.m010, t.m110, k, t.fx);
+    const float a01 = material_lerp(t.m001, t.m101, k, t.fx), a11 = material_lerp(t.m011, t.m111, k, t.fx);
+    const float b0 = a00 + (a10 - a00) * t.fy, b1 = a01 + (a11 - a01) * t.fy;
+    const float q = b0 + (b1 - b0) * t.fz;
+    return (uint32_t)rintf(q) & 0xffu;
+}
+
+// the 8 weights of a vertex at block-local position p of block b (an index into the dirty list)
+__device__ __forceinline__ uint2 material_weights(const MaterialVertexArgs &a, uint32_t b, float p0, float p1, float p2)
+{
+    int bx, by, bz;
+    material_block(a, b, bx, by, bz);
+    const MaterialTaps t = material_taps(a, bx, by, bz, p0, p1, p2);
+    uint32_t out[2] = {0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) out[k >> 2] |= material_filter_channel(t, k) << (8 * (k & 3));
+    return make_uint2(out[0], out[1]);
+}
+
+}  // namespace vtmc
+#endif

@@ -11,6 +11,7 @@
 // most 128^3 x 8 B = 16 MB, read-shared by every wave, and lives in L2 and the Infinity Cache.  Traffic that must reach HBM:
 // 76 T read + 24 T written (soup), 24 V + 8 V (indexed).
 #include "terrain_material.h"
+#include "material_filter.h"
 #include "record_tile.h"
 #include "vtmc_ctx.h"
 #include <cmath>
@@ -19,80 +20,12 @@ namespace vtmc {
 
 constexpr int kMatTile = 256;  // records (triangles or vertices) per workgroup, one workgroup of 256 threads per tile
 
-struct MaterialVertexArgs {
-    const uint2 *layer;  // C^3 texels, x fastest
-    int C;
-    float s[3];       // texels per cell, per axis
-    const int *list;  // device (bx, by, bz) triples of the dirty list, or null: every block, b = bx + nbx * (by + nby * bz)
-    uint32_t n_blocks;
-    int nbx, nby;
-    FastDiv d_nbx, d_nby;
-};
-
 struct MaterialPaintArgs {
     float ts[3], origin[3];
     int C;
     int lo[3], n[3];  // the texel box the launch walks
     int n_strokes;
 };
-
-// tx = g * s - 0.5 cut into the texel below it, wrapped as a Repeat texture, the one after it, and the weight
-__device__ __forceinline__ void material_axis(float g, float s, int C, int &i0, int &i1, float &f)
-{
-    float t = g * s;
-    t = t - 0.5f;
-    i0 = (int)floorf(t);
-    f = t - (float)i0;
-    // ((i0 % C) + C) % C; a vertex of the terrain gives i0 in -1..C-1, which needs no division
-    if (i0 == -1) i0 = C - 1;
-    else if ((unsigned)i0 >= (unsigned)C) i0 = ((i0 % C) + C) % C;
-    i1 = i0 + 1 == C ? 0 : i0 + 1;
-}
-
-__device__ __forceinline__ float material_channel(uint2 w, int k) { return (float)(((k < 4 ? w.x : w.y) >> (8 * (k & 3))) & 0xffu); }
-
-// a + (b - a) * f per channel k of two texels
-__device__ __forceinline__ float material_lerp(uint2 a, uint2 b, int k, float f)
-{
-    const float x = material_channel(a, k), y = material_channel(b, k);
-    return x + (y - x) * f;
-}
-
-// the 8 weights of a vertex at block-local position p of block b (an index into the dirty list)
-__device__ __forceinline__ uint2 material_weights(const MaterialVertexArgs &a, uint32_t b, float p0, float p1, float p2)
-{
-    if (b >= a.n_blocks) b = a.n_blocks - 1;  // never taken for a result of the library; keeps a foreign record inside the list
-    int bx, by, bz;
-    if (a.list) {
-        bx = a.list[3 * (size_t)b], by = a.list[3 * (size_t)b + 1], bz = a.list[3 * (size_t)b + 2];
-    } else {
-        const unsigned q = a.d_nbx.quot(b);
-        bx = (int)(b - q * (unsigned)a.nbx);
-        bz = (int)a.d_nby.quot(q);
-        by = (int)(q - (unsigned)bz * (unsigned)a.nby);
-    }
-    const float gx = (float)(8 * bx) + p0, gy = (float)(8 * by) + p1, gz = (float)(8 * bz) + p2;
-    int i0, i1, j0, j1, k0, k1;
-    float fx, fy, fz;
-    material_axis(gx, a.s[0], a.C, i0, i1, fx);
-    material_axis(gy, a.s[1], a.C, j0, j1, fy);
-    material_axis(gz, a.s[2], a.C, k0, k1, fz);
-    const int C = a.C;
-    const int r00 = C * (j0 + C * k0), r10 = C * (j1 + C * k0), r01 = C * (j0 + C * k1), r11 = C * (j1 + C * k1);
-    const uint2 *__restrict__ m = a.layer;
-    const uint2 m000 = m[r00 + i0], m100 = m[r00 + i1], m010 = m[r10 + i0], m110 = m[r10 + i1];
-    const uint2 m001 = m[r01 + i0], m101 = m[r01 + i1], m011 = m[r11 + i0], m111 = m[r11 + i1];
-    uint32_t out[2] = {0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float a00 = material_lerp(m000, m100, k, fx), a10 = material_lerp(m010, m110, k, fx);
-        const float a01 = material_lerp(m001, m101, k, fx), a11 = material_lerp(m011, m111, k, fx);
-        const float b0 = a00 + (a10 - a00) * fy, b1 = a01 + (a11 - a01) * fy;
-        const float q = b0 + (b1 - b0) * fz;
-        out[k >> 2] |= ((uint32_t)rintf(q) & 0xffu) << (8 * (k & 3));
-    }
-    return make_uint2(out[0], out[1]);
-}
 
 // soup: tris = T records of 19 dwords (vtmc_triangle); out[3t + v] = the weights of corner v of triangle t
 __global__ __launch_bounds__(256) void material_soup_kernel(const uint32_t *__restrict__ tris, uint32_t n_tris, uint2 *__restrict__ out, MaterialVertexArgs a)
@@ -108,17 +41,6 @@ __global__ __launch_bounds__(256) void material_soup_kernel(const uint32_t *__re
         const uint2 w = material_weights(a, r[18], __uint_as_float(r[3 * c]), __uint_as_float(r[3 * c + 1]), __uint_as_float(r[3 * c + 2]));
         out[(size_t)t0 * 3 + v] = w;
     }
-}
-
-// the largest b in [lo, hi] with off[b] <= v (off[lo] <= v holds): the block whose vertex range holds v, empty blocks skipped
-__device__ __forceinline__ uint32_t material_block_of(const uint32_t *__restrict__ off, uint32_t lo, uint32_t hi, uint32_t v)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (off[mid] <= v) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
 }
 
 // indexed: verts = V records of 6 dwords (vtmc_vertex), voffsets = the n_blocks + 1 per-block vertex offsets; out[v] = the weights of

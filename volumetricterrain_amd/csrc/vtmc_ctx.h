@@ -92,6 +92,17 @@ struct VertexAttr {
     uint64_t epoch = 0;
 };
 
+// The instances scattered over the result `epoch` names (terrain_scatter.hip): library-owned, grow-only, stale after the next extract.
+// masks: one survivor byte per triangle, whole tiles; tiles: the grand total (64 bits), the tile totals and their prefixes inside a
+// group of tiles, the group totals and their prefixes.
+struct VtmcScatter {
+    VtmcDevBuf instances, block_offsets, masks, tiles;
+    int64_t n = 0;
+    int blocks = 0;        // block_offsets holds blocks + 1 entries
+    uint64_t epoch = 0;
+    bool timed = false;    // the events around the last call's kernels were recorded (vtmc_debug_scatter_ms)
+};
+
 // An extract that has been queued on a stream and not yet completed by extract_finish().
 struct VtmcPending {
     bool active = false;    // queued, extract_finish() not yet called
@@ -173,6 +184,9 @@ struct vtmc_ctx {
     VertexAttr ao;
     VtmcDevBuf ao_stats;
     int32_t ao_direct_max = -1;         // vertices up to which a block takes the direct route; -1: the library's default
+    // terrain_scatter.hip: the instances of the last vtmc_scatter_surface and the events around its kernels
+    VtmcScatter scatter;
+    hipEvent_t ev_scatter[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // terrain_lod.hip: the node list of the last level-of-detail result (host, and the copy the gather kernel reads), the packed
     // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the events around
     // the last gather launch (vtmc_debug_lod_gather_ms)

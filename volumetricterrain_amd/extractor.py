@@ -10,8 +10,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
-from .modifiers import AmbientOcclusion, LodParams, mesh_stamp_args
+from ._lib import COMM_ID_BYTES, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from .modifiers import AmbientOcclusion, LodParams, ScatterParams, mesh_stamp_args
 
 
 def _ptr(a):
@@ -479,6 +479,26 @@ class Extractor:
         p, n = ctypes.c_void_p(), ctypes.c_int64()
         self._check(self._L.vtmc_ao_device_results(self._h, ctypes.byref(p), ctypes.byref(n)))
         return p.value, n.value
+
+    # -- surface scatter: instances over the triangles of a terrain extract, stable under edits ------------------------
+    def scatter_surface(self, params):
+        """Scatters instances over the result the context holds (from terrain_update / undo / redo / load) for a ScatterParams (or a
+        vtmc_scatter_params struct).  Returns (instances, block_offsets): a structured INSTANCE_DTYPE array in triangle order, and the
+        B + 1 instance offsets of the blocks of the result's list, so block b owns instances[block_offsets[b]:block_offsets[b + 1]]."""
+        p = params.to_struct() if hasattr(params, "to_struct") else params
+        n = ctypes.c_int64()
+        self._check(self._L.vtmc_scatter_surface(self._h, ctypes.byref(p), ctypes.byref(n)))
+        out = np.zeros(n.value, INSTANCE_DTYPE)
+        offs = np.zeros(self.last_counts()[0] + 1, np.int32)
+        self._check(self._L.vtmc_scatter_read(self._h, _ptr(out), n.value, _ptr(offs)))
+        return out, offs
+
+    def device_scatter(self):
+        """(device address of the instances, device address of the B + 1 block offsets, the number of instances) of the last
+        scatter_surface."""
+        p, o, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        self._check(self._L.vtmc_scatter_device_results(self._h, ctypes.byref(p), ctypes.byref(o), ctypes.byref(n)))
+        return p.value, o.value, n.value
 
     # -- level of detail: the resident terrain meshed coarsely far from a viewer ---------------------------------------
     def terrain_extract_lod(self, viewer, max_level, split=2.0, max_nodes=1 << 18):

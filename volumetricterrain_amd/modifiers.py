@@ -247,6 +247,39 @@ class AmbientOcclusion:
         return s
 
 
+class ScatterParams:
+    """The parameters of Extractor.scatter_surface (vtmc_scatter_params): `density` instances per world unit^2 of surface; a triangle is
+    kept when min_up <= up <= max_up, up the y of its unit face normal (1: flat ground, 0: a wall, -1: a ceiling); an instance when
+    min_y <= its world height <= max_y (infinities: no bound) and, with material_channel 0..7, with probability weight / 255 of that
+    channel of the material layer (-1: no material filter).  density * voxel_scale^2 may be at most SCATTER_MAX_DENSITY_CELLS; that limit
+    depends on the terrain's voxel scale and is the library's to refuse."""
+
+    def __init__(self, density, min_up=-1.0, max_up=1.0, min_y=-np.inf, max_y=np.inf, material_channel=-1, seed=0, max_instances=1 << 24):
+        with np.errstate(over="ignore"):
+            self._density = _f(density)
+            self._up = (_f(min_up), _f(max_up))
+            self._y = (_f(min_y), _f(max_y))
+        if not np.isfinite(self._density) or not self._density > 0:
+            raise ValueError("scatter density must be finite and > 0")
+        for name, (lo, hi) in (("up", self._up), ("y", self._y)):
+            if np.isnan(lo) or np.isnan(hi) or not lo <= hi:
+                raise ValueError("scatter min_%s / max_%s must not be NaN and min <= max" % (name, name))
+        if int(material_channel) != material_channel or not -1 <= material_channel < MATERIAL_CHANNELS:
+            raise ValueError("scatter material_channel must be an integer in -1..%d" % (MATERIAL_CHANNELS - 1))
+        if int(seed) != seed or not 0 <= seed < 1 << 32:
+            raise ValueError("scatter seed must be an integer in 0..2^32-1")
+        if int(max_instances) != max_instances or not 0 < max_instances < 1 << 31:
+            raise ValueError("scatter max_instances must be an integer in 1..2^31-1")
+        self._channel, self._seed, self._max = int(material_channel), int(seed), int(max_instances)
+
+    def to_struct(self):
+        s = _lib.ScatterParams()
+        s.density, s.min_up, s.max_up = float(self._density), float(self._up[0]), float(self._up[1])
+        s.min_y, s.max_y = float(self._y[0]), float(self._y[1])
+        s.material_channel, s.seed, s.max_instances, s.flags = self._channel, self._seed, self._max, 0
+        return s
+
+
 class LodParams:
     """The parameters of Extractor.terrain_extract_lod (vtmc_lod_params): the viewer in world space, the level of the octree's roots
     (0..LOD_MAX_LEVEL; a root of 8 * 2^max_level cells must divide the terrain, which is the library's to refuse), `split` >= 1 (a node
