@@ -181,6 +181,21 @@ public:
             throw UnityException(std::string("vtmc_terrain_read_samples: ") + vtmc_last_error(_ctx));
     }
 
+    void TerrainFragments(const Vector3 &lower, const Vector3 &upper, int maxSamples, int captureMinSamples, std::vector<Fragment> &out) override
+    {
+        const float lo[3] = {lower.x, lower.y, lower.z}, up[3] = {upper.x, upper.y, upper.z};
+        int32_t n = 0;
+        if (vtmc_terrain_fragments(_ctx, lo, up, maxSamples, 0, nullptr, 0, &n) != VTMC_OK)
+            throw UnityException(std::string("vtmc_terrain_fragments: ") + vtmc_last_error(_ctx));
+        std::vector<vtmc_fragment> list((size_t)n);
+        if (n > 0 && vtmc_terrain_fragments(_ctx, lo, up, maxSamples, captureMinSamples, list.data(), n, &n) != VTMC_OK)
+            throw UnityException(std::string("vtmc_terrain_fragments: ") + vtmc_last_error(_ctx));
+        out.clear();
+        for (const vtmc_fragment &f : list)
+            out.push_back(Fragment{Int3(f.seed[0], f.seed[1], f.seed[2]), Int3(f.lo[0], f.lo[1], f.lo[2]), Int3(f.hi[0], f.hi[1], f.hi[2]), f.n_samples,
+                                   f.stamp_id});
+    }
+
     int MaterialInit(int fineness) override
     {
         if (vtmc_material_init(_ctx, fineness) != VTMC_OK) throw UnityException(std::string("vtmc_material_init: ") + vtmc_last_error(_ctx));
@@ -303,6 +318,14 @@ const std::vector<uint8_t> &VoxelTerrain::VertexMaterials()
     EnsureMaterialLayer();
     _backend->MaterialVertices(_vertexMaterials);
     return _vertexMaterials;
+}
+
+std::vector<Fragment> VoxelTerrain::Fragments(const Vector3 &lower, const Vector3 &upper, int maxSamples, int captureMinSamples)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("Fragments needs an initialised device-resident terrain");
+    std::vector<Fragment> out;
+    _backend->TerrainFragments(lower, upper, maxSamples, captureMinSamples, out);
+    return out;
 }
 
 int VoxelTerrain::ExtractLod(const Vector3 &viewer, int maxLevel, float split, int maxNodes)

@@ -274,6 +274,40 @@ private:
     float _low[3], _up[3];
 };
 
+// New (not in the reference): removes every floating fragment of the box _lower.._upper (VTMC_MOD_DETACH of include/vtmc.h): the components of
+// solid samples, joined along x, y and z inside the box, that touch no face of the box.  _maxSamples > 0 leaves larger fragments alone.
+// Queued after a dig in the same Update, the dig and what falls off are one step.  Device-resident terrains only: QueryDensity throws.
+class DetachModifier : public TerrainModifier {
+public:
+    Vector3 _lower, _upper;
+    int _maxSamples;
+    DetachModifier(Vector3 lower, Vector3 upper, int maxSamples = 0) : _lower(lower), _upper(upper), _maxSamples(maxSamples)
+    {
+        if (std::isnan(lower.x) || std::isnan(lower.y) || std::isnan(lower.z) || std::isnan(upper.x) || std::isnan(upper.y) || std::isnan(upper.z) ||
+            maxSamples < 0)
+            throw std::invalid_argument("DetachModifier: a bound is NaN or maxSamples is negative");
+        AddOrErode = false;
+    }
+    Vector3 LowerBound() const override { return _lower; }
+    Vector3 UpperBound() const override { return _upper; }
+    float QueryDensity(const Vector3 &) const override { throw std::logic_error("DetachModifier has no host density: it is evaluated on the device"); }
+    bool Describe(ModifierDesc &d) const override
+    {
+        d.kind = 11;
+        d.dims[0] = _maxSamples;
+        d.dims[1] = 0;
+        return true;
+    }
+};
+
+// New (not in the reference): one floating fragment of VoxelTerrain::Fragments (vtmc_fragment of include/vtmc.h): the sample of smallest
+// grid index, the tight inclusive sample bounds, the solid sample count, and the id of the stamp it was captured into (0: none).
+struct Fragment {
+    MathHelper::Int3 _seed, _lo, _hi;
+    int _samples;
+    int _stampId;
+};
+
 // New (not in the reference, which can only replace a control map whole): one paint stroke on the material layer (vtmc_material_stroke
 // of include/vtmc.h).  Every texel within _radius of _center (world space) is blended towards the one-hot of _channel (0..3: control map
 // 1's r, g, b, a; 4..7: control map 2's) by _strength * clamp01(2 (1 - d / _radius)).
@@ -340,6 +374,11 @@ struct ExtractBackend {
         throw std::logic_error("TerrainUpdate on a backend without device-resident terrain");
     }
     virtual void TerrainReadSamples(std::vector<float> &) { throw std::logic_error("TerrainReadSamples unsupported"); }
+    // The floating fragments of a box of a device-resident terrain (vtmc_terrain_fragments), in increasing grid index of the seed.
+    virtual void TerrainFragments(const Vector3 &, const Vector3 &, int, int, std::vector<Fragment> &)
+    {
+        throw std::logic_error("TerrainFragments on a backend without device-resident terrain");
+    }
 
     // Material layer of a device-resident terrain (vtmc_material_*).  MaterialInit returns the layer's size C = 16 * fineness.
     virtual int MaterialInit(int) { throw std::logic_error("MaterialInit on a backend without a material layer"); }
@@ -401,6 +440,11 @@ public:
     int ExtractLod(const Vector3 &viewer, int maxLevel, float split = 2.0f, int maxNodes = 1 << 18);
     const std::vector<LodNode> &LodNodes() const { return _lodNodes; }      // the nodes of the last ExtractLod, in list order
     const std::vector<BlockMesh> &LodMeshes() const { return _lodMeshes; }  // one mesh per node
+
+    // New: what no longer hangs on anything (device-resident terrains).  Lists the fragments a DetachModifier with the same bounds and
+    // maxSamples would remove now and changes nothing; captureMinSamples > 0 also captures every fragment of at least that many samples
+    // as a stamp (Fragment::_stampId) for debris.  A dig: Update [erode]; Fragments with capture; spawn the debris; Update [detach].
+    std::vector<Fragment> Fragments(const Vector3 &lower, const Vector3 &upper, int maxSamples = 0, int captureMinSamples = 0);
 
     // -- inspection (tests, callers that consume the meshes) ----------------------------------
     const BlockMesh &Block(int x, int y, int z) const { return _blocks[((size_t)x * (_elevation / blockSize) + y) * (_height / blockSize) + z]; }

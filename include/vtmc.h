@@ -409,6 +409,37 @@ int32_t vtmc_device_indexed_results(vtmc_ctx *ctx, const vtmc_vertex **d_vertice
  * data_dims[1] != 8; any of a segment's 8 floats not finite; a radius below 0; a coordinate or radius above 2^20 in magnitude (so every
  * product above stays finite for sample positions of that size). */
 
+#define VTMC_MOD_DETACH 11   /* removes what no longer hangs on anything: every floating fragment of the box (not in the reference).
+                                                           data_dims[0] = max_samples (>= 0; 0: no limit), an integer in data_dims
+                                                           as VTMC_MOD_STAMP's id is.  add_or_erode must be 0, data NULL,
+                                                           data_dims[1] 0; p[0..7] are not read. */
+/* FRAGMENTS: the one question about the terrain that is not local -- after this dig, what is still attached to the ground?  The rule below
+ * is shared by VTMC_MOD_DETACH and vtmc_terrain_fragments (further down); it is integers and 32-bit copies only, there is no tolerance in
+ * it, and nothing in it depends on how the labelling is done.
+ *   Box        the clamped sample box of lower / upper: world bounds, floor / ceil, clamped to [0, dim + 1], exactly as for every modifier.
+ *              An empty box: nothing to do.
+ *   Solid      a sample is solid when s > 0: strict, and NaN is not solid -- the classify kernel's test.
+ *   Component  two solid samples of the box are joined when they are neighbours along x, y or z (6-connectivity); a component is a class
+ *              of that relation, taken inside the box only.  Diagonal contact does not join.  This is THE LIBRARY'S OWN rule and the safe
+ *              side: two solid samples across an edge of the lattice are always one piece of the mesh, whatever the case tables choose,
+ *              while what the tables do with two solid samples that touch only diagonally depends on the case (the ambiguous faces).  A
+ *              piece that hangs on by a diagonal alone is therefore treated as loose, never the other way round.
+ *   Anchored   a component that holds at least one sample on any of the six faces of the box.  What reaches the edge of the box may go on
+ *              outside it; where a face of the box is a face of the grid, the world's border holds it.
+ *   Fragment   every other component.  Its seed is its sample of smallest grid index x + dim_x * (y + dim_y * z); lo / hi are its tight
+ *              inclusive sample bounds; n_samples is its solid sample count.
+ *   Size limit with max_samples > 0 a fragment of n_samples > max_samples is left alone and not listed (a sky island that is meant to
+ *              float); 0: no limit.
+ *   Order      fragments are listed in increasing grid index of the seed.
+ * VTMC_MOD_DETACH writes every sample of every fragment as an erode whose clamped density is 2 does: with the event number e the modifier
+ * takes and the sample's grid index i, s becomes Clamp(min(s, -2), void, full) = uniform(seed, e, i, 2) - 2, a void value in [-2, -1).
+ * Every other sample keeps its bits.  The modifier takes its box from lower / upper, marks the dirty blocks of that box (also when nothing
+ * was removed), is journaled (its box: undo restores it bit for bit, redo puts the values back without labelling again) and takes one event
+ * number exactly as kinds 0-3, in queue order with every other kind, and sees what the earlier modifiers of its queue wrote: in a queue
+ * [erode sphere, detach(box around it)] the dig and what falls off are ONE undo step.
+ * VTMC_ERR_INVALID_ARG (the modifier's index in vtmc_last_error, nothing written by it): add_or_erode != 0; data not NULL;
+ * data_dims[0] < 0; data_dims[1] != 0. */
+
 /* One queued TerrainModifier (TerrainModifier.cs:19-33).  lower / upper are the values the C#
  * LowerBound / UpperBound properties return (world space): the shim copies them, so Unity's
  * Vector3.ProjectOnPlane stays on the C# side. */
@@ -541,6 +572,37 @@ int32_t vtmc_stamp_capture(vtmc_ctx *ctx, const int32_t first_sample[3], int32_t
 int32_t vtmc_stamp_info(const vtmc_ctx *ctx, int32_t stamp_id, int32_t dims[3]);
 int32_t vtmc_stamp_read(vtmc_ctx *ctx, int32_t stamp_id, float *dst, int64_t stride_x, int64_t stride_y, int64_t stride_z);
 int32_t vtmc_stamp_destroy(vtmc_ctx *ctx, int32_t stamp_id);
+
+/* The fragment query (not in the reference): lists, and optionally captures as stamps, exactly the fragments a VTMC_MOD_DETACH with the same
+ * lower / upper and max_samples would remove now (the rule: FRAGMENTS, at VTMC_MOD_DETACH above), in the rule's order.  It changes nothing:
+ * not the grid, the history, the event counter, the dirty list or the result the context holds; it waits for work queued on the context's
+ * stream as vtmc_terrain_read_samples does.  Labelling, counting, bounds and capture run on the device; only the records cross PCIe.
+ *   dst = NULL            count only: *n_fragments is set, nothing is captured.
+ *   capacity < n          VTMC_ERR_CAPACITY with *n_fragments set and nothing captured.
+ *   capture_min_samples   > 0: every listed fragment with n_samples >= capture_min_samples also becomes a stamp, its id in stamp_id.  The
+ *                         stamp box is [max(lo - 2, box lo), min(hi + 2, box hi)] per axis: it never leaves the query box, and since a
+ *                         fragment touches no face of that box the margin is at least 1 on every side and every dim at least 3.  A stamp
+ *                         sample is the grid's 32-bit value where the grid sample is not solid or belongs to this fragment, and -s where
+ *                         it is solid but belongs to something else: another piece in the box becomes equally deep air, so the stamp
+ *                         meshes to this fragment alone.  A fragment whose stamp box breaks the stamp limits (2^27 samples) keeps
+ *                         stamp_id 0.  If an allocation fails, the stamps this call made are destroyed and the call returns
+ *                         VTMC_ERR_DEVICE.  The stamps are ordinary stamps: vtmc_stamp_info / _read / _destroy and VTMC_MOD_STAMP work
+ *                         on them (pasted unturned in replace mode at its own box, one puts its fragment back bit for bit).
+ * VTMC_ERR_NO_RESULT without a terrain; VTMC_ERR_INVALID_ARG for null bounds, a bound that is NaN, or a negative max_samples or
+ * capture_min_samples; VTMC_ERR_DEVICE ("labelling did not converge") should the labelling ever break its own bounds.
+ * A host's flow for a dig: vtmc_terrain_update [erode]; vtmc_terrain_fragments with capture; spawn the debris from the stamps;
+ * vtmc_terrain_update [detach]. */
+typedef struct vtmc_fragment {
+    int32_t seed[3];     /* sample of smallest grid index */
+    int32_t lo[3];       /* tight bounds, inclusive */
+    int32_t hi[3];
+    int32_t n_samples;   /* solid samples */
+    int32_t stamp_id;    /* 0: not captured */
+    int32_t reserved;    /* 0 */
+} vtmc_fragment;         /* 48 bytes */
+
+int32_t vtmc_terrain_fragments(vtmc_ctx *ctx, const float lower[3], const float upper[3], int32_t max_samples, int32_t capture_min_samples,
+                               vtmc_fragment *dst, int32_t capacity, int32_t *n_fragments);
 
 /* Mesh stamps: a closed triangle mesh -- a rock, an arch, a prefab tunnel mouth -- voxelized on the device into an ordinary stamp (not in
  * the reference).  positions = n_vertices x 3 floats, indices = n_triangles x 3 vertex numbers; both are host pointers, borrowed for the

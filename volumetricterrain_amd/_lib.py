@@ -33,6 +33,9 @@ SPHERE_MAX_RADIUS_CELLS = 16
 # vtmc_instance: one instance of vtmc_scatter_surface
 INSTANCE_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("triangle", "<u4"), ("rnd", "<u4")])
 assert INSTANCE_DTYPE.itemsize == 32
+# vtmc_fragment: one record of vtmc_terrain_fragments
+FRAGMENT_DTYPE = np.dtype([("seed", "<i4", 3), ("lo", "<i4", 3), ("hi", "<i4", 3), ("n_samples", "<i4"), ("stamp_id", "<i4"), ("reserved", "<i4")])
+assert FRAGMENT_DTYPE.itemsize == 48
 OUTPUT_SOUP, OUTPUT_INDEXED = 0, 1
 
 OK = 0
@@ -62,6 +65,7 @@ SYMBOLS = [
     "vtmc_ao_vertices", "vtmc_ao_read_vertices", "vtmc_ao_device_results",
     "vtmc_scatter_surface", "vtmc_scatter_read", "vtmc_scatter_device_results",
     "vtmc_terrain_extract_lod", "vtmc_terrain_lod_nodes",
+    "vtmc_terrain_fragments",
 ]
 COMM_ID_BYTES = 128
 
@@ -76,6 +80,7 @@ MATERIAL_CHANNELS, MATERIAL_MAX_STROKES = 8, 4096   # the material layer: bytes 
 AO_MAX_STEPS, AO_MAX_RADIUS_CELLS = 8, 6   # vtmc_ao_vertices: the most steps of a march; the largest radius in cells (radius / voxel_scale)
 SCATTER_MAX_DENSITY_CELLS, SCATTER_MAX_PER_TRIANGLE = 8.0, 8   # vtmc_scatter_surface: the largest density * voxel_scale^2; the most instances of a triangle
 LOD_MAX_LEVEL = 7                 # vtmc_terrain_extract_lod: the coarsest level of a node (128 fine cells per node cell)
+MOD_DETACH = 11                   # removes the floating fragments of its box; data_dims[0] = max_samples (0: no limit)
 MOD_NOISE = 8                     # fBm / billow / ridged noise (RidgedMultifractalModifier's device form); 6 and 7 are not defined
 
 
@@ -113,6 +118,12 @@ class Instance(ctypes.Structure):
 class LodParams(ctypes.Structure):
     """vtmc_lod_params: viewer in world space, split >= 1, max_level 0..LOD_MAX_LEVEL, max_nodes > 0."""
     _fields_ = [("viewer", ctypes.c_float * 3), ("split", ctypes.c_float), ("max_level", ctypes.c_int32), ("max_nodes", ctypes.c_int32)]
+
+
+class Fragment(ctypes.Structure):
+    """vtmc_fragment: seed (the sample of smallest grid index), tight inclusive bounds, solid sample count, the stamp's id (0: not captured)."""
+    _fields_ = [("seed", ctypes.c_int32 * 3), ("lo", ctypes.c_int32 * 3), ("hi", ctypes.c_int32 * 3), ("n_samples", ctypes.c_int32),
+                ("stamp_id", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class LodNode(ctypes.Structure):
@@ -265,6 +276,8 @@ def load(path=None):
         L.vtmc_debug_lod_gather_ms.restype = i32
         L.vtmc_debug_lod_tiles.argtypes = [vp, vp, i64]                 # not in the header: the gathered tiles of the last level-of-detail extract
         L.vtmc_debug_lod_tiles.restype = i32
+    if not explicit or hasattr(L, "vtmc_terrain_fragments"):
+        L.vtmc_terrain_fragments.argtypes = [vp, P(ctypes.c_float * 3), P(ctypes.c_float * 3), i32, i32, vp, i32, P(i32)]
     L.vtmc_comm_unique_id.argtypes = [vp]
     L.vtmc_comm_init_rank.argtypes = [vp, vp, i32, i32]
     L.vtmc_comm_destroy.argtypes = [vp]

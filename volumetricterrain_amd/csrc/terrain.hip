@@ -278,6 +278,7 @@ static const ModifierKind kModifierKinds[] = {
     {VTMC_MOD_NOISE, check_noise, apply_noise},
     {VTMC_MOD_STAMP, check_stamp, apply_stamp},
     {VTMC_MOD_PATH, check_path, apply_path},
+    {VTMC_MOD_DETACH, check_detach, apply_detach},
 };
 
 const ModifierKind *find_modifier_kind(int32_t kind)

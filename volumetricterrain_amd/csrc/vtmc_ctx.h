@@ -174,6 +174,10 @@ struct vtmc_ctx {
     // terrain_path.hip: the segment records of the VTMC_MOD_PATH modifier being applied, grow-only; written only after the stream has
     // drained, since an earlier path modifier of the same queue may still be reading it
     VtmcDevBuf path;
+    // terrain_fragments.hip: the scratch of a labelling pass (a parent word and an auxiliary word per sample of the box: 8 bytes per sample), its
+    // control words (the convergence flag, the fragment count, the slot counter) and the query's fragment records; all grow-only, grown only
+    // after the stream has drained
+    VtmcDevBuf frag_labels, frag_ctl, frag_records;
     // terrain_material.hip: the material layer (mat_c^3 texels of 8 bytes; mat_c = 0: none), the float image of a set_control_map on its way
     // to the quantising kernel, the strokes of a paint call, and the vertex weights (8 bytes per vertex)
     VtmcDevBuf material, mat_image, mat_strokes;

@@ -10,8 +10,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
-from .modifiers import AmbientOcclusion, LodParams, ScatterParams, mesh_stamp_args
+from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from .modifiers import AmbientOcclusion, LodParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
 
 
 def _ptr(a):
@@ -391,6 +391,46 @@ class Extractor:
 
     def stamp_destroy(self, stamp_id):
         self._check(self._L.vtmc_stamp_destroy(self._h, int(stamp_id)))
+
+    # -- fragments: what no longer hangs on anything, listed (and captured as stamps) without touching the terrain --------
+    def terrain_fragments(self, lower=None, upper=None, max_samples=0, capture_min_samples=0):
+        """The floating fragments of the box lower..upper (world bounds; None: the whole terrain) that DetachModifier with the same bounds
+        and max_samples would remove now: a FRAGMENT_DTYPE array in increasing grid index of the seed.  capture_min_samples > 0: every
+        fragment of at least that many samples also becomes a stamp (its id in stamp_id; its place: fragment_stamp_box).  Changes nothing
+        in the terrain."""
+        lo, up = fragment_bounds(lower, upper)
+        most, least = fragment_count(max_samples, "max_samples"), fragment_count(capture_min_samples, "capture_min_samples")
+        lo_c, up_c = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*up)
+        n = ctypes.c_int32()
+        self._check(self._L.vtmc_terrain_fragments(self._h, ctypes.byref(lo_c), ctypes.byref(up_c), most, 0, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, FRAGMENT_DTYPE)
+        if n.value:
+            self._check(self._L.vtmc_terrain_fragments(self._h, ctypes.byref(lo_c), ctypes.byref(up_c), most, least, _ptr(out), n.value, ctypes.byref(n)))
+        return out
+
+    def terrain_sample_box(self, lower=None, upper=None):
+        """The clamped sample box of world bounds, (first sample, samples per axis), as the library finds it for a modifier or a fragment
+        query: floor / ceil of (bound - origin) / scale in float32, clamped to the grid; an axis of 0 samples: empty."""
+        lo, up = fragment_bounds(lower, upper)
+        origin, scale = self._terrain_placement
+        first, dims = [], []
+        with np.errstate(over="ignore", invalid="ignore"):
+            for k in range(3):
+                top = self._terrain_dims[k] + 1
+                a = float(np.floor((lo[k] - np.float32(origin[k])) / np.float32(scale)))
+                b = float(np.ceil((up[k] - np.float32(origin[k])) / np.float32(scale)))
+                a, b = int(max(min(a, 2.0 ** 31 - 1), 0.0)), int(min(max(b, -2.0 ** 31), float(top)))
+                first.append(a)
+                dims.append(max(0, b - a + 1) if a <= top else 0)
+        return tuple(first), tuple(dims)
+
+    def fragment_stamp_box(self, fragment, lower=None, upper=None):
+        """(first sample, dims) of the stamp a fragment record of terrain_fragments(lower, upper, ...) was captured into: its bounds grown
+        by 2 samples, cut to the query box.  StampModifier(stamp_id, dims, world centre of that box, mode="replace") pastes it back."""
+        first, dims = self.terrain_sample_box(lower, upper)
+        a = [max(int(fragment["lo"][k]) - 2, first[k]) for k in range(3)]
+        b = [min(int(fragment["hi"][k]) + 2, first[k] + dims[k] - 1) for k in range(3)]
+        return tuple(a), tuple(b[k] - a[k] + 1 for k in range(3))
 
     # -- material layer: VoxelTerrain.SetControlMap's splat volumes in HBM, paint, and per-vertex weights -------------
     def material_init(self, fineness):

@@ -9,7 +9,7 @@ order of the C# expressions.
 import numpy as np
 
 from . import _lib
-from ._lib import (AO_MAX_STEPS, LOD_MAX_LEVEL, MATERIAL_CHANNELS, MESH_MAX_TRIANGLES, MOD_CYLINDER, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP,
+from ._lib import (AO_MAX_STEPS, LOD_MAX_LEVEL, MATERIAL_CHANNELS, MESH_MAX_TRIANGLES, MOD_CYLINDER, MOD_DETACH, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP,
                    PATH_MAX_SEGMENTS, STAMP_MAX_DIM, STAMP_MAX_SAMPLES, STAMP_MIN_DIM, Modifier)
 
 _f = np.float32
@@ -410,6 +410,49 @@ class StampModifier(TerrainModifier):
 
     def attach(self, m):
         m.data_dims[:] = (self._id, 1 if self._mode == "replace" else 0)
+
+
+# -- fragments (include/vtmc.h VTMC_MOD_DETACH) ------------------------------------------------------------------------------------------
+def fragment_bounds(lower, upper):
+    """World bounds of a fragment box as float32 triples; None: without limit on that side (the whole terrain).  NaN is refused."""
+    with np.errstate(over="ignore"):
+        lo = np.full(3, -np.inf, _f) if lower is None else np.asarray(lower, np.float64).astype(_f).reshape(-1)
+        up = np.full(3, np.inf, _f) if upper is None else np.asarray(upper, np.float64).astype(_f).reshape(-1)
+    if lo.shape != (3,) or up.shape != (3,) or np.isnan(lo).any() or np.isnan(up).any():
+        raise ValueError("fragment bounds must be three numbers each, none of them NaN")
+    return lo, up
+
+
+def fragment_count(n, name):
+    if isinstance(n, bool) or int(n) != n or not 0 <= n < 2 ** 31:
+        raise ValueError("%s must be an integer in 0..2^31-1" % name)
+    return int(n)
+
+
+class DetachModifier(TerrainModifier):
+    """Removes every floating fragment of the box lower..upper (world bounds; None: the whole terrain): the components of solid samples
+    (s > 0, joined along x, y, z inside the box) that touch no face of the box.  max_samples > 0 leaves larger fragments alone.  What it
+    removes is what Extractor.terrain_fragments with the same arguments lists."""
+    kind = MOD_DETACH
+    AddOrErode = False
+
+    def __init__(self, lower=None, upper=None, max_samples=0):
+        self._low, self._up = fragment_bounds(lower, upper)
+        self._max = fragment_count(max_samples, "max_samples")
+
+    @property
+    def LowerBound(self):
+        return self._low
+
+    @property
+    def UpperBound(self):
+        return self._up
+
+    def params(self):
+        return []
+
+    def attach(self, m):
+        m.data_dims[:] = (self._max, 0)
 
 
 # -- mesh stamps (include/vtmc.h vtmc_stamp_from_mesh) ------------------------------------------------------------------------------------
