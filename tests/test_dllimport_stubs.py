@@ -9,14 +9,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def c_prototypes():
-    text = open(os.path.join(ROOT, "include", "vtmc.h")).read()
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    protos = {}
-    for m in re.finditer(r"\b(int32_t|const char \*|void)\s*(vtmc_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        ret, name, args = m.group(1).strip(), m.group(2), " ".join(m.group(3).split())
-        params = [] if args in ("", "void") else [a.strip() for a in args.split(",")]
-        protos[name] = (ret, params)
-    return protos
+    """{name: (return type, parameter declarations)} as the package's own reader of include/vtmc.h finds them"""
+    from volumetricterrain_amd import _header
+    return {name: (p.ret, p.params) for name, p in _header.HEADER.prototypes.items()}
 
 
 def cs_stubs():

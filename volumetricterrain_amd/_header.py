@@ -1,0 +1,124 @@
+"""Reader of include/vtmc.h, the project's contract: its constants, structs and prototypes as Python values, so that the ctypes binding
+(_lib.py) is the header's by construction.  It knows the forms the header uses and nothing else, and it never skips: whatever it cannot
+read raises HeaderError with the line, so a new form is taught to the reader in the pull request that first writes it."""
+import collections
+import ctypes
+import os
+import re
+
+import numpy as np
+
+from . import build as _build
+
+PATH = os.path.normpath(os.path.join(_build.CSRC, _build.HEADERS[-1]))
+
+SCALARS = {"float": (ctypes.c_float, "<f4"), "int32_t": (ctypes.c_int32, "<i4"), "uint32_t": (ctypes.c_uint32, "<u4"),
+           "int64_t": (ctypes.c_int64, "<i8"), "uint64_t": (ctypes.c_uint64, "<u8")}
+RETURNS = {"int32_t": ctypes.c_int32, "const char *": ctypes.c_char_p, "void": None}
+
+# name; return type and parameter declarations as written (one space between words); what ctypes is given
+Prototype = collections.namedtuple("Prototype", "name ret params restype argtypes")
+Field = collections.namedtuple("Field", "name ctype format shape")   # format / shape: numpy's; None / () for a pointer
+
+
+class HeaderError(ValueError):
+    pass
+
+
+class Header:
+    def __init__(self, path=PATH):
+        self.path = path
+        with open(path) as f:
+            self.text = re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group()), f.read(), flags=re.S)   # comments blanked, lines kept
+        self.constants, self.structs, self.prototypes = {}, {}, {}
+        self.pointees = set(SCALARS) | {"void", "char", "uint8_t"}   # what a pointer may point to; structs and opaque types join below
+        for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(VTMC_\w+)(.*)$", self.text, flags=re.M):
+            if not (m.group(1) == "VTMC_H" and not m.group(2).strip()):   # the include guard
+                self.constants[m.group(1)] = self._value(m.group(2), m.start())
+        for m in re.finditer(r"\btypedef\s+struct\b", self.text):
+            self._struct(m.start())
+        for m in re.finditer(r"\b(vtmc_\w+)\s*\(", self.text):
+            self._prototype(m)
+
+    def _fail(self, pos, what):
+        raise HeaderError("%s:%d: %s" % (self.path, self.text.count("\n", 0, pos) + 1, what))
+
+    def _value(self, text, pos):
+        v = text.strip()
+        if v.startswith("(") and v.endswith(")"):
+            v = v[1:-1].strip()
+        if re.fullmatch(r"-?\d+[uU]?", v):
+            return int(v.rstrip("uU"))
+        m = re.fullmatch(r"(\d+)\s*<<\s*(\d+)", v)
+        if m:
+            return int(m.group(1)) << int(m.group(2))
+        if re.fullmatch(r"-?(\d+\.\d*|\.\d+)([eE][-+]?\d+)?[fF]?", v):
+            return float(v.rstrip("fF"))
+        self._fail(pos, "cannot evaluate #define value %r" % text.strip())
+
+    def _struct(self, pos):
+        m = re.compile(r"typedef\s+struct\s+(\w+)\s+(\w+)\s*;").match(self.text, pos)
+        if m and m.group(1) == m.group(2):   # an opaque handle: typedef struct vtmc_ctx vtmc_ctx;
+            self.pointees.add(m.group(1))
+            return
+        m = re.compile(r"typedef\s+struct\s+(vtmc_\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;").match(self.text, pos)
+        if not m or m.group(1) != m.group(3) or m.group(1) in self.structs:
+            self._fail(pos, "cannot parse this typedef struct")
+        fields, at = [], m.start(2)
+        for decl in m.group(2).split(";")[:-1]:
+            d = re.fullmatch(r"\s*(?:const\s+)?(\w+)\b(.*)", decl, flags=re.S)
+            if not d:
+                self._fail(at, "cannot parse field declaration %r" % decl.strip())
+            for one in d.group(2).split(","):
+                f = re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[(\d+)\])?\s*", one)
+                if not f or d.group(1) not in (self.pointees if f.group(1) else SCALARS) or (f.group(1) and f.group(3)):
+                    self._fail(at + len(decl) - len(decl.lstrip()), "field %r: a form or base type this reader does not know" % " ".join(decl.split()))
+                if f.group(1):
+                    fields.append(Field(f.group(2), ctypes.c_void_p, None, ()))
+                else:
+                    ctype, fmt = SCALARS[d.group(1)]
+                    n = int(f.group(3)) if f.group(3) else 0
+                    fields.append(Field(f.group(2), ctype * n if n else ctype, fmt, (n,) if n else ()))
+            at += len(decl) + 1
+        if m.group(2).split(";")[-1].strip() or not fields:
+            self._fail(pos, "cannot parse this typedef struct")
+        self.structs[m.group(1)] = fields
+        self.pointees.add(m.group(1))
+
+    def _prototype(self, m):
+        name, at = m.group(1), m.start()
+        ret = self.text[max(self.text.rfind(";", 0, at), self.text.rfind("}", 0, at)) + 1:at].split("\n")   # before the name, back to the last declaration,
+        ret = re.sub(r"\s*\*\s*", " *", " ".join(" ".join(l for l in ret if not l.lstrip().startswith("#")).split()))   # less preprocessor lines
+        tail = re.compile(r"\(([^;{}()]*)\)\s*;").match(self.text, m.end() - 1)
+        if ret not in RETURNS or not tail or name in self.prototypes:
+            self._fail(at, "%s( is not a prototype this reader knows (return type %r)" % (name, ret))
+        args = " ".join(tail.group(1).split())
+        params = [] if args in ("", "void") else [a.strip() for a in args.split(",")]
+        self.prototypes[name] = Prototype(name, ret, params, RETURNS[ret], [self._parameter(p, at, name) for p in params])
+
+    def _parameter(self, decl, pos, name):
+        d = re.fullmatch(r"(?:const )?(\w+) ?((?:\* ?(?:const ?)?)*)(\w+)? ?(\[\w*\])?", decl)
+        if d and (d.group(2) or d.group(4)):   # a pointer, or an array parameter, which is one
+            if d.group(1) == "char" and d.group(2).count("*") == 1 and not d.group(4):
+                return ctypes.c_char_p
+            if d.group(1) in self.pointees:
+                return ctypes.c_void_p   # accepts byref(...), array.ctypes.data_as(c_void_p) and a bare address alike
+        elif d and d.group(1) in SCALARS and d.group(3):
+            return SCALARS[d.group(1)][0]
+        self._fail(pos, "%s: parameter %r: a form or base type this reader does not know" % (name, decl))
+
+    def structure(self, c_name, py_name, doc=None):
+        """A ctypes.Structure class of a struct of the header: natural alignment, fields in the header's order."""
+        return type(py_name, (ctypes.Structure,), {"_fields_": [(f.name, f.ctype) for f in self.structs[c_name]], "__doc__": doc})
+
+    def dtype(self, c_name, names=None):
+        """The little-endian numpy dtype of a struct without pointers, offsets and size as the C compiler's; names: other field names,
+        by position."""
+        fields, layout = self.structs[c_name], self.structure(c_name, c_name)
+        if any(f.format is None for f in fields):
+            raise HeaderError("%s holds a pointer: it has no numpy dtype" % c_name)
+        return np.dtype({"names": list(names or [f.name for f in fields]), "formats": [(f.format, f.shape) for f in fields],
+                         "offsets": [getattr(layout, f.name).offset for f in fields], "itemsize": ctypes.sizeof(layout)})
+
+
+HEADER = Header()

@@ -18,6 +18,21 @@ def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
 
 
+def _struct(x):
+    """The ctypes struct of a mirror object of modifiers.py (anything with to_struct); a struct is passed through."""
+    return x.to_struct() if hasattr(x, "to_struct") else x
+
+
+def _struct_array(items, kind):
+    """(a ctypes array of `kind` with the items' structs copied into it -- one element when there are none --, their number)"""
+    structs = [_struct(x) for x in items]
+    arr = (kind * max(len(structs), 1))()
+    for i, s in enumerate(structs):
+        ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(s), ctypes.sizeof(kind))
+    arr._structs = structs   # what a struct keeps alive (a path's segments) lives as long as the array
+    return arr, len(structs)
+
+
 def elem_strides(grid):
     if grid.dtype != np.float32 or grid.ndim != 3:
         raise ValueError("grid must be a 3-D float32 array indexed [x, y, z]")
@@ -267,13 +282,8 @@ class Extractor:
     def terrain_update(self, mods):
         """VoxelTerrain.Update (VoxelTerrain.cs:262-325) for a queue of Modifier structs.
         Returns (number of dirty blocks, T)."""
-        mods = [m.to_struct() if hasattr(m, "to_struct") else m for m in mods]
-        arr = (Modifier * max(len(mods), 1))()
-        for i, m in enumerate(mods):
-            ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(m), ctypes.sizeof(Modifier))
         nd, t = ctypes.c_int32(), ctypes.c_int32()
-        self._check(self._L.vtmc_terrain_update(self._h, ctypes.cast(arr, ctypes.c_void_p), len(mods),
-                                                ctypes.byref(nd), ctypes.byref(t)))
+        self._check(self._L.vtmc_terrain_update(self._h, *_struct_array(mods, Modifier), ctypes.byref(nd), ctypes.byref(t)))
         return nd.value, t.value
 
     def terrain_set_history(self, max_bytes):
@@ -470,11 +480,7 @@ class Extractor:
 
     def paint(self, strokes):
         """Applies MaterialStroke objects (or vtmc_material_stroke structs) in order, in one pass over the texels they reach."""
-        strokes = [s.to_struct() if hasattr(s, "to_struct") else s for s in strokes]
-        arr = (_lib.MaterialStroke * max(len(strokes), 1))()
-        for i, s in enumerate(strokes):
-            ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(s), ctypes.sizeof(_lib.MaterialStroke))
-        self._check(self._L.vtmc_material_paint(self._h, ctypes.cast(arr, ctypes.c_void_p), len(strokes)))
+        self._check(self._L.vtmc_material_paint(self._h, *_struct_array(strokes, _lib.MaterialStroke)))
 
     def material_vertices(self):
         """Computes the material weights of every vertex of the result the context holds (from terrain_update / undo / redo / load) and
@@ -501,7 +507,7 @@ class Extractor:
     def ao_vertices(self, params):
         """Computes the occlusion byte of every vertex of the result the context holds (from terrain_update / undo / redo / load) for an
         AmbientOcclusion (or a vtmc_ao_params struct) and leaves the bytes on the device.  Returns their number: 3 T (soup) or V (indexed)."""
-        p = params.to_struct() if hasattr(params, "to_struct") else params
+        p = _struct(params)
         n = ctypes.c_int64()
         self._check(self._L.vtmc_ao_vertices(self._h, ctypes.byref(p), ctypes.byref(n)))
         return n.value
@@ -525,7 +531,7 @@ class Extractor:
         """Scatters instances over the result the context holds (from terrain_update / undo / redo / load) for a ScatterParams (or a
         vtmc_scatter_params struct).  Returns (instances, block_offsets): a structured INSTANCE_DTYPE array in triangle order, and the
         B + 1 instance offsets of the blocks of the result's list, so block b owns instances[block_offsets[b]:block_offsets[b + 1]]."""
-        p = params.to_struct() if hasattr(params, "to_struct") else params
+        p = _struct(params)
         n = ctypes.c_int64()
         self._check(self._L.vtmc_scatter_surface(self._h, ctypes.byref(p), ctypes.byref(n)))
         out = np.zeros(n.value, INSTANCE_DTYPE)
@@ -546,12 +552,7 @@ class Extractor:
         is nearer than split times its size), gathers each node's tile from the resident grid at stride 2^L and extracts them as blocks, in
         the output mode set.  `viewer` may be a LodParams (or a vtmc_lod_params struct) instead; the other arguments are then not read.
         Returns (number of nodes, T); read the mesh as after any extract, `block` of a triangle indexes terrain_lod_nodes()."""
-        if hasattr(viewer, "to_struct"):
-            p = viewer.to_struct()
-        elif isinstance(viewer, _lib.LodParams):
-            p = viewer
-        else:
-            p = LodParams(viewer, max_level, split, max_nodes).to_struct()
+        p = _struct(viewer if hasattr(viewer, "to_struct") or isinstance(viewer, _lib.LodParams) else LodParams(viewer, max_level, split, max_nodes))
         n, t = ctypes.c_int32(), ctypes.c_int32()
         self._check(self._L.vtmc_terrain_extract_lod(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(t)))
         return n.value, t.value
