@@ -4,6 +4,7 @@
 //   host_selftest --gpu <out_dir>  real libvtmc.so backend; dumps grid + meshes for the parity test
 //   host_selftest --gpu-resident <out_dir>  the same scene, grid in HBM, Update on the device
 //   host_selftest --gpu-lod <out_dir>  a resident terrain meshed at three levels of detail around a viewer; dumps nodes + per-node counts
+//   host_selftest --gpu-nav <out_dir>  the navigation layer of a box of a resident terrain; dumps the spans, the column offsets and the box
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -228,6 +229,47 @@ static int gpu_resident_run(const std::string &out)
 }
 
 // a device-resident terrain of 64 x 32 x 32 cells meshed at mixed levels of detail: the viewer at cell (-1, 3, 5), roots of level 2, split 1
+static int gpu_nav_run(const std::string &out)
+{
+    VoxelTerrain vt;
+    vt._width = 64;
+    vt._elevation = 32;
+    vt._height = 32;
+    vt._voxelScale = 0.5f;
+    vt.TerrainOrigin = Vector3(-3.0f, 1.0f, 2.0f);
+    vt._deviceResident = true;
+    vt._seed = 977;
+    vt.Init();
+    Vector2 lo, up;
+    lo.x = -100; lo.y = -100; up.x = 100; up.y = 100;
+    vt.InsertModifier(std::make_shared<PlaneModifier>(6.3f, lo, up, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(27.5f, 8.0f, 10.0f), 4.25f, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(5.0f, 6.0f, 9.0f), 3.0f, false));
+    vt.Update();
+    const int updateTriangles = vt.LastTriangleCount();
+    // an agent 0.9 world units high (2 samples) that steps 0.4 (0.8 grid units), in a box around the dig
+    const NavResult nav = vt.BuildNav(Vector3(-1.0f, 1.0f, 3.0f), Vector3(14.0f, 15.0f, 16.5f), 0.9f, 0.4f);
+    std::printf("nav: spans %zu columns %zu box %d %d %d + %d %d %d\n", nav._spans.size(), nav._columnOffsets.size() - 1, nav._boxLo._x, nav._boxLo._y,
+                nav._boxLo._z, nav._boxDims._x, nav._boxDims._y, nav._boxDims._z);
+    if (nav._spans.empty() || nav._columnOffsets.size() != (size_t)nav._boxDims._x * nav._boxDims._z + 1) return 7;
+    if (nav._columnOffsets.back() != (int)nav._spans.size() || vt.LastTriangleCount() != updateTriangles) return 8;   // what Update left stands
+    static_assert(sizeof(NavSpan) == 32, "dumped as it lies");
+    std::ofstream fs(out + "/nav_spans.bin", std::ios::binary), fo(out + "/nav_offsets.i32", std::ios::binary), fb(out + "/nav_box.i32", std::ios::binary);
+    fs.write(reinterpret_cast<const char *>(nav._spans.data()), (std::streamsize)(nav._spans.size() * sizeof(NavSpan)));
+    fo.write(reinterpret_cast<const char *>(nav._columnOffsets.data()), (std::streamsize)(nav._columnOffsets.size() * sizeof(int)));
+    const int box[6] = {nav._boxLo._x, nav._boxLo._y, nav._boxLo._z, nav._boxDims._x, nav._boxDims._y, nav._boxDims._z};
+    fb.write(reinterpret_cast<const char *>(box), sizeof box);
+    bool refused = false;   // 200 world units of headroom are 400 samples: more than the layer takes
+    try {
+        vt.BuildNav(Vector3(0, 0, 0), Vector3(1, 1, 1), 200.0f, 0.4f);
+    } catch (const UnityException &) {
+        refused = true;
+    }
+    if (!refused) return 9;
+    std::printf("HOST-NAV-OK\n");
+    return 0;
+}
+
 static int gpu_lod_run(const std::string &out)
 {
     VoxelTerrain vt;
@@ -290,10 +332,11 @@ int main(int argc, char **argv)
         if (argc >= 3 && std::string(argv[1]) == "--gpu") return gpu_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-resident") return gpu_resident_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-lod") return gpu_lod_run(argv[2]);
+        if (argc >= 3 && std::string(argv[1]) == "--gpu-nav") return gpu_nav_run(argv[2]);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "exception: %s\n", e.what());
         return 3;
     }
-    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir> | --gpu-resident <out_dir> | --gpu-lod <out_dir>\n");
+    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir> | --gpu-resident <out_dir> | --gpu-lod <out_dir> | --gpu-nav <out_dir>\n");
     return 64;
 }

@@ -7,7 +7,7 @@
 #include <cstring>
 #include <unordered_set>
 
-#include "../include/vtmc.h"
+#include "../include/vtmc_nav.h"   // includes vtmc.h
 
 namespace PGRTerrain {
 
@@ -196,6 +196,25 @@ public:
                                    f.stamp_id});
     }
 
+    void TerrainNav(const Vector3 &lower, const Vector3 &upper, int agentHeight, float maxStep, int maxSpans, NavResult &out) override
+    {
+        const float lo[3] = {lower.x, lower.y, lower.z}, up[3] = {upper.x, upper.y, upper.z};
+        vtmc_nav_params p;
+        p.agent_height = agentHeight, p.max_step = maxStep, p.max_spans = maxSpans, p.flags = 0;
+        int32_t n = 0, first[3], dims[3];
+        if (vtmc_terrain_nav_build(_ctx, lo, up, &p, &n) != VTMC_OK || vtmc_nav_info(_ctx, first, dims, &n) != VTMC_OK)
+            throw UnityException(std::string("vtmc_terrain_nav_build: ") + vtmc_last_error(_ctx));
+        std::vector<vtmc_nav_span> list((size_t)n);
+        out._columnOffsets.assign((size_t)dims[0] * (size_t)dims[2] + 1, 0);
+        static_assert(sizeof(int) == sizeof(int32_t), "column offsets are read in place");
+        if (vtmc_nav_read(_ctx, list.data(), n, out._columnOffsets.data()) != VTMC_OK)
+            throw UnityException(std::string("vtmc_nav_read: ") + vtmc_last_error(_ctx));
+        out._boxLo = Int3(first[0], first[1], first[2]);
+        out._boxDims = Int3(dims[0], dims[1], dims[2]);
+        out._spans.clear();
+        for (const vtmc_nav_span &s : list) out._spans.push_back(NavSpan{s.height, s.y, s.clearance, {s.link[0], s.link[1], s.link[2], s.link[3]}, s.region});
+    }
+
     int MaterialInit(int fineness) override
     {
         if (vtmc_material_init(_ctx, fineness) != VTMC_OK) throw UnityException(std::string("vtmc_material_init: ") + vtmc_last_error(_ctx));
@@ -325,6 +344,16 @@ std::vector<Fragment> VoxelTerrain::Fragments(const Vector3 &lower, const Vector
     if (!_initialised || !_deviceResident) throw UnityException("Fragments needs an initialised device-resident terrain");
     std::vector<Fragment> out;
     _backend->TerrainFragments(lower, upper, maxSamples, captureMinSamples, out);
+    return out;
+}
+
+NavResult VoxelTerrain::BuildNav(const Vector3 &lower, const Vector3 &upper, float agentHeight, float maxStep, int maxSpans)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("BuildNav needs an initialised device-resident terrain");
+    const float samples = std::ceil(agentHeight / _voxelScale);
+    if (!(samples >= 1.0f && samples <= (float)VTMC_NAV_MAX_AGENT_HEIGHT)) throw UnityException("BuildNav: agentHeight outside 1..256 samples");
+    NavResult out;
+    _backend->TerrainNav(lower, upper, (int)samples, maxStep / _voxelScale, maxSpans, out);
     return out;
 }
 

@@ -308,6 +308,22 @@ struct Fragment {
     int _stampId;
 };
 
+// New (not in the reference): the navigation layer of a box of the terrain, as VoxelTerrain::BuildNav returns it (vtmc_nav_span of
+// include/vtmc_nav.h, where the rule is): the spans ordered by column (ix + dx * iz of the box) and bottom-up inside a column, the
+// dx * dz + 1 span offsets of the columns, and the box in grid samples.  A span's height is in grid units; a link is the index of a span
+// in the column at -x, +x, -z, +z or -1; _region is the smallest span index of its component.
+struct NavSpan {
+    float _height;
+    int _y, _clearance;
+    int _link[4];
+    int _region;
+};
+struct NavResult {
+    std::vector<NavSpan> _spans;
+    std::vector<int> _columnOffsets;
+    MathHelper::Int3 _boxLo, _boxDims;
+};
+
 // New (not in the reference, which can only replace a control map whole): one paint stroke on the material layer (vtmc_material_stroke
 // of include/vtmc.h).  Every texel within _radius of _center (world space) is blended towards the one-hot of _channel (0..3: control map
 // 1's r, g, b, a; 4..7: control map 2's) by _strength * clamp01(2 (1 - d / _radius)).
@@ -379,6 +395,11 @@ struct ExtractBackend {
     {
         throw std::logic_error("TerrainFragments on a backend without device-resident terrain");
     }
+    // The navigation build of a box of a device-resident terrain (vtmc_terrain_nav_build, vtmc_nav_read); agent height in samples, step in grid units.
+    virtual void TerrainNav(const Vector3 &, const Vector3 &, int, float, int, NavResult &)
+    {
+        throw std::logic_error("TerrainNav on a backend without device-resident terrain");
+    }
 
     // Material layer of a device-resident terrain (vtmc_material_*).  MaterialInit returns the layer's size C = 16 * fineness.
     virtual int MaterialInit(int) { throw std::logic_error("MaterialInit on a backend without a material layer"); }
@@ -445,6 +466,12 @@ public:
     // maxSamples would remove now and changes nothing; captureMinSamples > 0 also captures every fragment of at least that many samples
     // as a stamp (Fragment::_stampId) for debris.  A dig: Update [erode]; Fragments with capture; spawn the debris; Update [detach].
     std::vector<Fragment> Fragments(const Vector3 &lower, const Vector3 &upper, int maxSamples = 0, int captureMinSamples = 0);
+
+    // New: where something can walk, and which places are connected (device-resident terrains).  Builds the walkable spans, their links
+    // and regions for the box and changes nothing; agentHeight and maxStep are in world units (ceil(agentHeight / _voxelScale) samples of
+    // headroom, maxStep / _voxelScale grid units between neighbour columns).  The result is a snapshot: after an edit, build the edit's
+    // box plus a margin again.  No agent radius, no slope by normal, no stitching across boxes, no path search.
+    NavResult BuildNav(const Vector3 &lower, const Vector3 &upper, float agentHeight, float maxStep, int maxSpans = 1 << 24);
 
     // -- inspection (tests, callers that consume the meshes) ----------------------------------
     const BlockMesh &Block(int x, int y, int z) const { return _blocks[((size_t)x * (_elevation / blockSize) + y) * (_height / blockSize) + z]; }

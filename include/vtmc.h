@@ -604,6 +604,10 @@ typedef struct vtmc_fragment {
 int32_t vtmc_terrain_fragments(vtmc_ctx *ctx, const float lower[3], const float upper[3], int32_t max_samples, int32_t capture_min_samples,
                                vtmc_fragment *dst, int32_t capacity, int32_t *n_fragments);
 
+/* NAVIGATION: the other non-local question -- where can something walk, and which places are connected? -- is answered by a layer with a
+ * header of its own, include/vtmc_nav.h (walkable spans, links and regions of a box of the resident terrain; same library, same context).
+ * It includes this header and adds nothing to it. */
+
 /* Mesh stamps: a closed triangle mesh -- a rock, an arch, a prefab tunnel mouth -- voxelized on the device into an ordinary stamp (not in
  * the reference).  positions = n_vertices x 3 floats, indices = n_triangles x 3 vertex numbers; both are host pointers, borrowed for the
  * call and copied to the device.  Stamp sample (i, j, k) lies at px = (float)i * h + first[0], py = (float)j * h + first[1],

@@ -1,0 +1,93 @@
+// nav_host_check.cpp -- a stand-alone run of the host half of the navigation build (csrc/terrain_nav.h: the argument checks, the box as
+// the result reports it, the buffer sizes and the max_spans check), for the host sanitizers:
+//   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -ffp-contract=off tools/nav_host_check.cpp -o nav_host_check && ./nav_host_check
+// It checks known answers and exits 0 when every one is the expected one.
+#include "../volumetricterrain_amd/csrc/terrain_nav.h"
+#include <cstdio>
+#include <limits>
+
+using namespace vtmc;
+
+static int failures = 0;
+#define EXPECT(c) \
+    do { \
+        if (!(c)) { \
+            std::printf("line %d: %s\n", __LINE__, #c); \
+            ++failures; \
+        } \
+    } while (0)
+
+static vtmc_nav_params params(int32_t agent_height, float max_step, int32_t max_spans, uint32_t flags)
+{
+    vtmc_nav_params p;
+    p.agent_height = agent_height, p.max_step = max_step, p.max_spans = max_spans, p.flags = flags;
+    return p;
+}
+
+int main()
+{
+    const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
+    static_assert(sizeof(vtmc_nav_params) == 16 && sizeof(vtmc_nav_span) == 32 && VTMC_NAV_OPEN == 2147483647 && VTMC_NAV_MAX_AGENT_HEIGHT == 256,
+                  "include/vtmc_nav.h");
+
+    // the argument checks: every fault of include/vtmc_nav.h
+    const float lo[3] = {-inf, 0.0f, -1e30f}, up[3] = {inf, 5.0f, 1e30f};
+    const vtmc_nav_params good = params(2, 0.5f, 1000, 0u);
+    EXPECT(nav_args_fault(lo, up, &good) == nullptr);
+    EXPECT(nav_args_fault(nullptr, up, &good) != nullptr && nav_args_fault(lo, nullptr, &good) != nullptr && nav_args_fault(lo, up, nullptr) != nullptr);
+    for (int k = 0; k < 3; ++k) {
+        float bad[3] = {0.0f, 0.0f, 0.0f};
+        bad[k] = nan;
+        EXPECT(nav_args_fault(bad, up, &good) != nullptr && nav_args_fault(lo, bad, &good) != nullptr);
+    }
+    const vtmc_nav_params cases[] = {params(1, 0.0f, 1, 0u), params(256, 3.0e38f, 2147483647, 0u)};
+    for (const vtmc_nav_params &p : cases) EXPECT(nav_args_fault(lo, up, &p) == nullptr);
+    const vtmc_nav_params faults[] = {params(0, 0.5f, 1000, 0u),  params(257, 0.5f, 1000, 0u), params(-2147483647 - 1, 0.5f, 1000, 0u),
+                                      params(2, -0.5f, 1000, 0u), params(2, nan, 1000, 0u),    params(2, inf, 1000, 0u),
+                                      params(2, -inf, 1000, 0u),  params(2, 0.5f, 0, 0u),      params(2, 0.5f, -1, 0u),
+                                      params(2, 0.5f, 1000, 1u),  params(2, 0.5f, 1000, 0x80000000u)};
+    for (const vtmc_nav_params &p : faults) EXPECT(nav_args_fault(lo, up, &p) != nullptr);
+    const vtmc_nav_params minus_zero = params(2, -0.0f, 1000, 0u);   // -0 is not below 0
+    EXPECT(nav_args_fault(lo, up, &minus_zero) == nullptr);
+
+    // the box as reported: an empty box has no samples on any axis
+    const int32_t first[3] = {5, 1, 3}, dims[3] = {67, 13, 23};
+    NavBox b = nav_box(first, dims);
+    EXPECT(b.lo[0] == 5 && b.lo[1] == 1 && b.lo[2] == 3 && b.d[0] == 67 && b.d[1] == 13 && b.d[2] == 23 && !nav_box_empty(b));
+    for (int k = 0; k < 3; ++k) {
+        int32_t d[3] = {67, 13, 23};
+        d[k] = 0;
+        b = nav_box(first, d);
+        EXPECT(nav_box_empty(b) && b.d[0] == 0 && b.d[1] == 0 && b.d[2] == 0 && b.lo[k] == first[k]);
+    }
+    NavSizes s = nav_sizes(b);   // empty: one offset, the total
+    EXPECT(s.columns == 0 && s.groups == 0 && s.offsets_bytes == 4 && s.launchable);
+
+    // the sizes: 64-bit columns times 4
+    b = nav_box(first, dims);
+    s = nav_sizes(b);
+    EXPECT(s.columns == 67 * 23 && s.groups == 2 && s.offsets_bytes == 4u * (67 * 23 + 1) && s.scan_bytes == 8u + 8u * (67 * 23 + 2) && s.launchable);
+    const int32_t zero[3] = {0, 0, 0}, one_group[3] = {32, 2, 32}, just_over[3] = {1025, 2, 1}, largest[3] = {1026, 1026, 1026};
+    s = nav_sizes(nav_box(zero, one_group));
+    EXPECT(s.columns == 1024 && s.groups == 1);
+    s = nav_sizes(nav_box(zero, just_over));
+    EXPECT(s.columns == 1025 && s.groups == 2);
+    s = nav_sizes(nav_box(zero, largest));
+    EXPECT(s.columns == 1052676 && s.groups == 1029 && s.offsets_bytes == 4210708u && s.launchable);
+    const int32_t huge[3] = {2147483647, 2, 2147483647};   // no grid has it: the arithmetic must still not wrap
+    s = nav_sizes(nav_box(zero, huge));
+    EXPECT(s.columns == 4611686014132420609ll && !s.launchable);
+    const int32_t deep[3] = {4, 2, 262144};   // more z quads than a kernel grid holds
+    EXPECT(!nav_sizes(nav_box(zero, deep)).launchable);
+    EXPECT(nav_span_bytes(0) == 0 && nav_span_bytes(3) == 96 && nav_span_bytes(2147483647) == 68719476704ull);
+    EXPECT(nav_scratch_bytes(3) == 24 && nav_scratch_bytes(2147483647) == 17179869176ull);
+
+    // the max_spans check
+    EXPECT(nav_total_fits(0, 1) && nav_total_fits(1000, 1000) && !nav_total_fits(1001, 1000));
+    EXPECT(nav_total_fits(2147483647ull, 2147483647) && !nav_total_fits(2147483648ull, 2147483647));
+    EXPECT(!nav_total_fits(18446744073709551615ull, 2147483647) && !nav_total_fits(0, 0) && !nav_total_fits(0, -1));
+
+    if (failures) std::printf("%d check(s) failed\n", failures);
+    else std::printf("nav_host_check: ok\n");
+    return failures ? 1 : 0;
+}

@@ -1,5 +1,5 @@
-"""Reader of include/vtmc.h, the project's contract: its constants, structs and prototypes as Python values, so that the ctypes binding
-(_lib.py) is the header's by construction.  It knows the forms the header uses and nothing else, and it never skips: whatever it cannot
+"""Reader of include/vtmc.h, the project's contract, and of the headers of its optional layers (include/vtmc_nav.h): their constants,
+structs and prototypes as Python values, so that the ctypes binding (_lib.py) is the headers' by construction.  It knows the forms the header uses and nothing else, and it never skips: whatever it cannot
 read raises HeaderError with the line, so a new form is taught to the reader in the pull request that first writes it."""
 import collections
 import ctypes
@@ -11,6 +11,7 @@ import numpy as np
 from . import build as _build
 
 PATH = os.path.normpath(os.path.join(_build.CSRC, _build.HEADERS[-1]))
+NAV_PATH = os.path.join(os.path.dirname(PATH), "vtmc_nav.h")   # the navigation layer; includes vtmc.h
 
 SCALARS = {"float": (ctypes.c_float, "<f4"), "int32_t": (ctypes.c_int32, "<i4"), "uint32_t": (ctypes.c_uint32, "<u4"),
            "int64_t": (ctypes.c_int64, "<i8"), "uint64_t": (ctypes.c_uint64, "<u8")}
@@ -26,14 +27,17 @@ class HeaderError(ValueError):
 
 
 class Header:
-    def __init__(self, path=PATH):
+    def __init__(self, path=PATH, base=None):
+        """base: the Header of the file this one includes; its types may be pointed to here."""
         self.path = path
         with open(path) as f:
             self.text = re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group()), f.read(), flags=re.S)   # comments blanked, lines kept
         self.constants, self.structs, self.prototypes = {}, {}, {}
         self.pointees = set(SCALARS) | {"void", "char", "uint8_t"}   # what a pointer may point to; structs and opaque types join below
+        if base is not None:
+            self.pointees |= base.pointees
         for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(VTMC_\w+)(.*)$", self.text, flags=re.M):
-            if not (m.group(1) == "VTMC_H" and not m.group(2).strip()):   # the include guard
+            if not (m.group(1).endswith("_H") and not m.group(2).strip()):   # the include guard
                 self.constants[m.group(1)] = self._value(m.group(2), m.start())
         for m in re.finditer(r"\btypedef\s+struct\b", self.text):
             self._struct(m.start())
@@ -49,6 +53,8 @@ class Header:
             v = v[1:-1].strip()
         if re.fullmatch(r"-?\d+[uU]?", v):
             return int(v.rstrip("uU"))
+        if re.fullmatch(r"0[xX][0-9a-fA-F]+[uU]?", v):
+            return int(v.rstrip("uU"), 16)
         m = re.fullmatch(r"(\d+)\s*<<\s*(\d+)", v)
         if m:
             return int(m.group(1)) << int(m.group(2))
@@ -122,3 +128,4 @@ class Header:
 
 
 HEADER = Header()
+NAV_HEADER = Header(NAV_PATH, base=HEADER)

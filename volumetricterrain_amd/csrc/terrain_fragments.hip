@@ -14,12 +14,12 @@
 //   3. frag_flatten_kernel every sample to its root; fused with the per-root sample counts (reduced per run of a wave before the atomic).
 // Between 2 and 3, frag_anchor_kernel walks the six faces of the box and marks the roots it meets.
 //
-// VISIBILITY inside the merge kernel: the parent array is written by workgroups on other XCDs while it is read.  The union is written so
-// that ONLY THE VALUE AN atomicMin RETURNS DECIDES whether it is done: a root a is attached under a smaller root b by
-// old = atomicMin(&parent[a], b), and the union is complete only if old == a (a was still a root at that moment); otherwise it goes on
-// with (old, b), which must still meet.  Every parent value ever written is a smaller index of the same component, so a stale read names
-// an older ancestor: it can cost a retry, never a wrong answer.  The reads are relaxed agent-scope atomic loads all the same, which keeps
-// the retries few.  Path compression is an atomicMin as well, on nodes that are no roots.
+// VISIBILITY inside the merge kernel: the parent array is written by workgroups on other XCDs while it is read.  The union (union_find.h)
+// is written so that ONLY THE VALUE THE ATTACHING ATOMIC RETURNS DECIDES whether it is done: a root a is attached under a smaller root b by
+// a compare-and-swap of parent[a] from a to b, and the union is complete only if that succeeds (a was still a root at that moment);
+// otherwise it goes on with (old, b), which must still meet.  Every parent value ever written is a smaller index of the same tree, so a
+// stale read names an older ancestor: it can cost a retry, never a wrong answer.  The reads are relaxed agent-scope atomic loads all the
+// same, which keeps the retries few.  Path compression is an atomicMin, on nodes that are no roots.
 //
 // EVERY LOOP IS BOUNDED, twice: a walk up the parents must strictly decrease the index and a union's retry must strictly decrease its
 // larger root (both hold on any valid input), and each loop also counts against the number of samples.  A violation sets a
@@ -27,6 +27,7 @@
 #include "terrain_edit.h"
 #include "terrain_fragments.h"
 #include "terrain_stamp.h"
+#include "union_find.h"
 #include <climits>
 #include <cstring>
 #include <vector>
@@ -36,63 +37,6 @@ namespace vtmc {
 constexpr int kTileX = 64, kTileY = 8, kTileZ = 8, kTileSamples = kTileX * kTileY * kTileZ;
 constexpr uint32_t kAnchoredBit = 0x80000000u;   // aux[root]: anchored; the bits below it count the samples of an unanchored root (<= 2^30)
 enum { kCtlFlag = 0, kCtlCount = 1, kCtlSlots = 2, kCtlWords = 16 };
-
-template <int kScope>
-__device__ __forceinline__ int uf_load(const int *P, int i) { return __hip_atomic_load(P + i, __ATOMIC_RELAXED, kScope); }
-
-// the root above i, or -1 with the flag set; i is solid.  Every hop goes to a strictly smaller index.
-template <int kScope>
-__device__ __forceinline__ int uf_find(const int *P, int i, int bound, int *flag)
-{
-    for (int hops = 0; hops <= bound; ++hops) {
-        const int p = uf_load<kScope>(P, i);
-        if (p == i) return i;
-        if (p > i || p < 0) break;
-        i = p;
-    }
-    atomicOr(flag, 1);
-    return -1;
-}
-
-// every node from i up to (not including) anything <= r gets r, an ancestor of it, as its parent at the least
-template <int kScope>
-__device__ __forceinline__ void uf_compress(int *P, int i, int r, int bound, int *flag)
-{
-    for (int hops = 0; i > r && hops <= bound; ++hops) {
-        const int p = __hip_atomic_fetch_min(P + i, r, __ATOMIC_RELAXED, kScope);
-        if (p > i || p < 0) {
-            atomicOr(flag, 1);
-            return;
-        }
-        if (p == i) return;
-        i = p;
-    }
-}
-
-// joins the components of the solid samples a and b: the larger root goes under the smaller
-template <int kScope, bool kCompress>
-__device__ __forceinline__ void uf_union(int *P, int a, int b, int bound, int *flag)
-{
-    int larger = INT_MAX;
-    for (int tries = 0; tries <= bound; ++tries) {
-        const int ra = uf_find<kScope>(P, a, bound, flag), rb = uf_find<kScope>(P, b, bound, flag);
-        if (ra < 0 || rb < 0) return;
-        if (kCompress) {
-            uf_compress<kScope>(P, a, ra, bound, flag);
-            uf_compress<kScope>(P, b, rb, bound, flag);
-        }
-        if (ra == rb) return;
-        a = ra > rb ? ra : rb;
-        b = ra > rb ? rb : ra;
-        if (a >= larger) break;   // a retry's larger root lies strictly below the last one's
-        larger = a;
-        const int old = __hip_atomic_fetch_min(P + a, b, __ATOMIC_RELAXED, kScope);
-        if (old == a) return;     // a was still a root when it went under b
-        if (old > a || old < 0) break;
-        a = old;                  // somebody attached a first: old and b have yet to meet
-    }
-    atomicOr(flag, 2);
-}
 
 // box-linear index of sample (ix, iy, iz) of the box; below 2^31 for every box of a grid
 __device__ __forceinline__ int frag_index(const TerrainBox &b, int ix, int iy, int iz) { return ix + b.dx * (iy + b.dy * iz); }

@@ -8,8 +8,8 @@
 // instance goes: the order is a function of the result alone.
 //   1. scatter_count_kernel  evaluates every candidate of its triangle and writes one SURVIVOR MASK byte per triangle (bit i: candidate i
 //      survives; n <= 8) and the tile's survivor total.
-//   2. the scan of the tile totals, in two levels: scatter_scan_tiles_kernel gives every tile its prefix inside its group of 1024 tiles
-//      and every group its total; scatter_scan_groups_kernel, one workgroup, scans the group totals (at most 8192 of them) and leaves the
+//   2. the scan of the tile totals, in two levels: scan_tiles_kernel gives every tile its prefix inside its group of 1024 tiles
+//      and every group its total; scan_groups_kernel, one workgroup, scans the group totals (at most 8192 of them) and leaves the
 //      grand total, which goes to the host for the max_instances check and the growth of the instance buffer.  A tile's offset is the sum
 //      of the two prefixes.  (One workgroup over all the tile totals took 0.19 ms of the pass's 0.88 at 1024^3: profiles/r19/scatter.)
 //   3. scatter_emit_kernel   the same tiling; a workgroup scan of the masks' popcounts gives every lane its slot; only triangles with a
@@ -26,13 +26,12 @@
 #include "terrain_scatter.h"
 #include "material_filter.h"
 #include "record_tile.h"
+#include "scan_kernels.h"
 #include "terrain_material.h"
 #include "vtmc_ctx.h"
 #include <cmath>
 
 namespace vtmc {
-
-constexpr int kScatterScanThreads = 1024;   // threads of a scan workgroup = tiles of a group
 
 struct ScatterArgs {
     const uint32_t *recs;      // soup: T records of 19 dwords (vtmc_triangle); indexed: V records of 6 dwords (vtmc_vertex)
@@ -142,30 +141,6 @@ __device__ __forceinline__ bool scatter_candidate(const ScatterArgs &a, const Sc
     return true;
 }
 
-// exclusive prefix of v over the 64 * WAVES threads of the workgroup, wave by wave and then across the waves; total = the sum
-template <int WAVES>
-__device__ __forceinline__ uint32_t scatter_block_scan(uint32_t v, uint32_t *wave_sums, uint32_t &total)
-{
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63u) wave_sums[w] = x;
-    __syncthreads();
-    uint32_t base = 0;
-    total = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < (uint32_t)WAVES; ++j) {
-        const uint32_t s = wave_sums[j];
-        if (j < w) base += s;
-        total += s;
-    }
-    return base + x - v;
-}
-
 // the tile of a workgroup: soup records into LDS; indexed, the blocks of the tile's first and last triangle
 template <bool INDEXED>
 __device__ __forceinline__ void scatter_stage(const ScatterArgs &a, uint32_t *rec, uint32_t *range, uint32_t t0, uint32_t nt)
@@ -198,48 +173,8 @@ __global__ __launch_bounds__(256) void scatter_count_kernel(ScatterArgs a, uint8
     }
     masks[(size_t)t0 + threadIdx.x] = (uint8_t)mask;   // the buffer holds whole tiles: the ragged tile's tail is written as zeros
     uint32_t total;
-    scatter_block_scan<4>((uint32_t)__popc(mask), wave_sums, total);
+    block_scan<4>((uint32_t)__popc(mask), wave_sums, total);
     if (threadIdx.x == 0) tile_totals[blockIdx.x] = total;
-}
-
-// A workgroup per group of 1024 tiles, a thread per tile: the tile's prefix inside its group, and the group's total (at most 1024 * 256 * 8)
-__global__ __launch_bounds__(kScatterScanThreads) void scatter_scan_tiles_kernel(const uint32_t *__restrict__ tile_totals, uint32_t n_tiles,
-                                                                                 uint32_t *__restrict__ tile_offsets, uint32_t *__restrict__ group_totals)
-{
-    __shared__ uint32_t wave_sums[kScatterScanThreads / 64];
-    const uint32_t tile = blockIdx.x * (uint32_t)kScatterScanThreads + threadIdx.x;
-    const uint32_t v = tile < n_tiles ? tile_totals[tile] : 0u;
-    uint32_t total;
-    const uint32_t before = scatter_block_scan<kScatterScanThreads / 64>(v, wave_sums, total);
-    if (tile < n_tiles) tile_offsets[tile] = before;
-    if (threadIdx.x == 0) group_totals[blockIdx.x] = total;
-}
-
-// One workgroup.  Thread i owns a contiguous run of the groups (8 at the most): it sums the run, the sums are scanned across the
-// workgroup, and the run is walked again to write the prefixes.  The total is kept in 64 bits (T * 8 can pass 2^32).
-__global__ __launch_bounds__(kScatterScanThreads) void scatter_scan_groups_kernel(const uint32_t *__restrict__ group_totals, uint32_t n_groups,
-                                                                                  uint32_t *__restrict__ group_offsets, unsigned long long *__restrict__ total)
-{
-    __shared__ unsigned long long part[kScatterScanThreads];
-    const uint32_t run = (n_groups + kScatterScanThreads - 1) / kScatterScanThreads;
-    const uint32_t lo = threadIdx.x * run < n_groups ? threadIdx.x * run : n_groups;
-    const uint32_t hi = lo + run < n_groups ? lo + run : n_groups;
-    unsigned long long s = 0;
-    for (uint32_t i = lo; i < hi; ++i) s += group_totals[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t d = 1; d < (uint32_t)kScatterScanThreads; d <<= 1) {
-        const unsigned long long y = threadIdx.x >= d ? part[threadIdx.x - d] : 0ull;
-        __syncthreads();
-        part[threadIdx.x] += y;
-        __syncthreads();
-    }
-    unsigned long long at = part[threadIdx.x] - s;
-    for (uint32_t i = lo; i < hi; ++i) {
-        group_offsets[i] = (uint32_t)at;   // the host goes on only when the total fits an int32
-        at += group_totals[i];
-    }
-    if (threadIdx.x == kScatterScanThreads - 1) *total = part[threadIdx.x];
 }
 
 template <bool INDEXED>
@@ -252,14 +187,14 @@ __global__ __launch_bounds__(256) void scatter_emit_kernel(ScatterArgs a, const 
     const uint32_t nt = a.n_tris - t0 < (uint32_t)kScatterTile ? a.n_tris - t0 : (uint32_t)kScatterTile;
     uint32_t mask = masks[(size_t)t0 + threadIdx.x];
     uint32_t total;
-    const uint32_t before = scatter_block_scan<4>((uint32_t)__popc(mask), wave_sums, total);
+    const uint32_t before = block_scan<4>((uint32_t)__popc(mask), wave_sums, total);
     if (total == 0u) return;   // a tile without survivors reads no record (uniform across the workgroup)
     scatter_stage<INDEXED>(a, rec, range, t0, nt);
     if (mask == 0u || threadIdx.x >= nt) return;
     ScatterTri tri;
     scatter_load<INDEXED>(a, rec, range, t0 + threadIdx.x, tri);
     const uint64_t k = scatter_key(a, tri);
-    uint32_t slot = group_offsets[blockIdx.x / (uint32_t)kScatterScanThreads] + tile_offsets[blockIdx.x] + before;
+    uint32_t slot = group_offsets[blockIdx.x / (uint32_t)kScanThreads] + tile_offsets[blockIdx.x] + before;
     while (mask) {
         const uint32_t i = (uint32_t)__ffs(mask) - 1u;
         mask &= mask - 1u;
@@ -288,7 +223,7 @@ __global__ __launch_bounds__(256) void scatter_block_offsets_kernel(const uint32
     }
     const uint32_t tile = t / (uint32_t)kScatterTile, r = t % (uint32_t)kScatterTile;
     const uint32_t *w = mask_words + (size_t)tile * (kScatterTile / 4);
-    uint32_t sum = group_offsets[tile / (uint32_t)kScatterScanThreads] + tile_offsets[tile];
+    uint32_t sum = group_offsets[tile / (uint32_t)kScanThreads] + tile_offsets[tile];
     for (uint32_t j = 0; j < r / 4u; ++j) sum += (uint32_t)__popc(w[j]);
     if (r & 3u) sum += (uint32_t)__popc(w[r / 4u] & ((1u << (8u * (r & 3u))) - 1u));
     out[b] = (int32_t)sum;
@@ -324,7 +259,7 @@ int32_t vtmc_scatter_surface(vtmc_ctx *ctx, const vtmc_scatter_params *params, i
     } else {
         const uint32_t tiles = scatter_tiles(T);
         if (int rc = ensure(ctx, sc.masks, scatter_mask_bytes(T))) return rc;
-        const uint32_t groups = (tiles + kScatterScanThreads - 1) / kScatterScanThreads;
+        const uint32_t groups = (tiles + kScanThreads - 1) / kScanThreads;
         if (int rc = ensure(ctx, sc.tiles, sizeof(unsigned long long) + 2 * sizeof(uint32_t) * ((size_t)tiles + groups))) return rc;
         unsigned long long *d_total = (unsigned long long *)sc.tiles.p;   // then the tile totals, their prefixes, the group totals, their prefixes
         uint32_t *tile_totals = (uint32_t *)(d_total + 1), *tile_offsets = tile_totals + tiles;
@@ -361,10 +296,10 @@ int32_t vtmc_scatter_surface(vtmc_ctx *ctx, const vtmc_scatter_params *params, i
         VTMC_HIP(ctx, launch_end());
         VTMC_HIP(ctx, hipEventRecord(ctx->ev_scatter[1], ctx->stream));
         launch_begin();
-        hipLaunchKernelGGL(scatter_scan_tiles_kernel, dim3(groups), dim3(kScatterScanThreads), 0, ctx->stream, tile_totals, tiles, tile_offsets, group_totals);
+        hipLaunchKernelGGL(scan_tiles_kernel, dim3(groups), dim3(kScanThreads), 0, ctx->stream, tile_totals, tiles, tile_offsets, group_totals);
         VTMC_HIP(ctx, launch_end());
         launch_begin();
-        hipLaunchKernelGGL(scatter_scan_groups_kernel, dim3(1), dim3(kScatterScanThreads), 0, ctx->stream, group_totals, groups, group_offsets, d_total);
+        hipLaunchKernelGGL(scan_groups_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, group_totals, groups, group_offsets, d_total);
         VTMC_HIP(ctx, launch_end());
         VTMC_HIP(ctx, hipEventRecord(ctx->ev_scatter[2], ctx->stream));
         VTMC_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));

@@ -103,6 +103,19 @@ struct VtmcScatter {
     bool timed = false;    // the events around the last call's kernels were recorded (vtmc_debug_scatter_ms)
 };
 
+// The navigation build the context holds (terrain_nav.hip): library-owned, grow-only; a snapshot of the grid at build time, dropped by
+// vtmc_terrain_init / _load.  offsets: the columns + 1 span offsets; scan: the grand total (64 bits), the column counts and their prefixes
+// inside a group of columns, the group totals and their prefixes; scratch: a column word and a parent word per span; ctl: the flag word
+// and the verify pass's count.
+struct VtmcNav {
+    VtmcDevBuf spans, offsets, scan, scratch, ctl;
+    bool valid = false;
+    int32_t n = 0;
+    int32_t lo[3] = {0, 0, 0}, d[3] = {0, 0, 0};   // the box as reported: first sample, samples per axis
+    bool timed = false;                            // the events around the last build's kernels were recorded (vtmc_debug_nav_ms)
+    int rounds = 0;                                // union / flatten / verify rounds of the last build
+};
+
 // An extract that has been queued on a stream and not yet completed by extract_finish().
 struct VtmcPending {
     bool active = false;    // queued, extract_finish() not yet called
@@ -191,6 +204,9 @@ struct vtmc_ctx {
     // terrain_scatter.hip: the instances of the last vtmc_scatter_surface and the events around its kernels
     VtmcScatter scatter;
     hipEvent_t ev_scatter[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // terrain_nav.hip: the last navigation build and the events around its kernels (created by the first build)
+    VtmcNav nav;
+    hipEvent_t ev_nav[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // terrain_lod.hip: the node list of the last level-of-detail result (host, and the copy the gather kernel reads), the packed
     // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the events around
     // the last gather launch (vtmc_debug_lod_gather_ms)

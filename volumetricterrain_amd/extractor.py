@@ -10,8 +10,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
-from .modifiers import AmbientOcclusion, LodParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
+from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from .modifiers import AmbientOcclusion, LodParams, NavParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
 
 
 def _ptr(a):
@@ -39,6 +39,16 @@ def elem_strides(grid):
     if any(s % 4 for s in grid.strides):
         raise ValueError("grid strides must be multiples of 4 bytes")
     return tuple(int(s) // 4 for s in grid.strides)
+
+
+def nav_world_positions(spans, column_offsets, box_lo, dims, origin, scale):
+    """World positions (float64, (n, 3)) of the spans of Extractor.terrain_nav: origin + (x, height, z) * scale, with (x, z) the grid
+    column of each span, found from column_offsets (column c = ix + dx * iz of the box at box_lo with dims samples per axis)."""
+    counts = np.diff(np.asarray(column_offsets, np.int64))
+    col = np.repeat(np.arange(len(counts), dtype=np.int64), counts)
+    dx = max(int(dims[0]), 1)
+    g = np.stack([box_lo[0] + col % dx, np.asarray(spans["height"], np.float64), box_lo[2] + col // dx], axis=1)
+    return np.asarray(origin, np.float64) + g * float(scale)
 
 
 def density_params(kind, n, seed=1337):
@@ -441,6 +451,37 @@ class Extractor:
         a = [max(int(fragment["lo"][k]) - 2, first[k]) for k in range(3)]
         b = [min(int(fragment["hi"][k]) + 2, first[k] + dims[k] - 1) for k in range(3)]
         return tuple(a), tuple(b[k] - a[k] + 1 for k in range(3))
+
+    # -- navigation: walkable spans, links and regions of a box of the resident terrain (include/vtmc_nav.h) ----------
+    def terrain_nav(self, lower=None, upper=None, params=None):
+        """Builds the navigation layer of the box lower..upper (world bounds; None: the whole terrain) for a NavParams (world units; or a
+        vtmc_nav_params struct, in samples and grid units).  Returns (spans, column_offsets, box_lo, box_dims): a NAV_SPAN_DTYPE array
+        ordered by column (ix + dx * iz) and bottom-up inside a column, the dx * dz + 1 span offsets of the columns, and the box's first
+        grid sample and samples per axis ((0, 0, 0) samples for an empty box).  Changes nothing in the terrain; the result is a snapshot."""
+        lo, up = fragment_bounds(lower, upper)
+        if params is None:
+            raise ValueError("terrain_nav needs a NavParams")
+        p = params.to_struct(self._terrain_placement[1]) if isinstance(params, NavParams) else _struct(params)
+        lo_c, up_c = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*up)
+        n = ctypes.c_int32()
+        self._check(self._L.vtmc_terrain_nav_build(self._h, ctypes.byref(lo_c), ctypes.byref(up_c), ctypes.byref(p), ctypes.byref(n)))
+        return self.nav_read()
+
+    def nav_read(self):
+        """(spans, column_offsets, box_lo, box_dims) of the navigation build the context holds."""
+        first, dims, n = (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)(), ctypes.c_int32()
+        self._check(self._L.vtmc_nav_info(self._h, ctypes.byref(first), ctypes.byref(dims), ctypes.byref(n)))
+        spans = np.zeros(n.value, NAV_SPAN_DTYPE)
+        offsets = np.zeros(dims[0] * dims[2] + 1, np.int32)
+        self._check(self._L.vtmc_nav_read(self._h, _ptr(spans), n.value, _ptr(offsets)))
+        return spans, offsets, tuple(first), tuple(dims)
+
+    def device_nav(self):
+        """(device address of the spans, device address of the dx * dz + 1 column offsets, the number of spans) of the last terrain_nav;
+        valid until the next one, terrain_init, terrain_load or close."""
+        p, o, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int32()
+        self._check(self._L.vtmc_nav_device_results(self._h, ctypes.byref(p), ctypes.byref(o), ctypes.byref(n)))
+        return p.value, o.value, n.value
 
     # -- material layer: VoxelTerrain.SetControlMap's splat volumes in HBM, paint, and per-vertex weights -------------
     def material_init(self, fineness):

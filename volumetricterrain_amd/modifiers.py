@@ -455,6 +455,36 @@ class DetachModifier(TerrainModifier):
         m.data_dims[:] = (self._max, 0)
 
 
+# -- navigation (include/vtmc_nav.h) ----------------------------------------------------------------------------------------------------
+class NavParams:
+    """The parameters of Extractor.terrain_nav in WORLD units: the agent's height (the headroom a floor needs) and the largest step between
+    neighbour columns, and the most spans the call may make.  to_struct(voxel_scale) gives the vtmc_nav_params of a terrain of that scale:
+    agent_height = ceil(height / voxel_scale) samples (1..NAV_MAX_AGENT_HEIGHT is the library's to refuse), max_step / voxel_scale grid
+    units, both in float32."""
+
+    def __init__(self, agent_height, max_step, max_spans=1 << 24):
+        with np.errstate(over="ignore"):
+            self._height, self._step = _f(agent_height), _f(max_step)
+        if not np.isfinite(self._height) or not self._height > 0:
+            raise ValueError("nav agent_height must be finite and > 0")
+        if not np.isfinite(self._step) or not self._step >= 0:
+            raise ValueError("nav max_step must be finite and >= 0")
+        if isinstance(max_spans, bool) or int(max_spans) != max_spans or not 0 < max_spans < 2 ** 31:
+            raise ValueError("nav max_spans must be an integer in 1..2^31-1")
+        self._max = int(max_spans)
+
+    def to_struct(self, voxel_scale):
+        scale = _f(voxel_scale)
+        with np.errstate(over="ignore"):
+            samples = float(np.ceil(self._height / scale))
+            step = self._step / scale
+        if not samples < 2.0 ** 31 or not np.isfinite(step):
+            raise ValueError("nav parameters overflow at voxel scale %r" % (voxel_scale,))
+        s = _lib.NavParamsStruct()
+        s.agent_height, s.max_step, s.max_spans, s.flags = int(samples), float(step), self._max, 0
+        return s
+
+
 # -- mesh stamps (include/vtmc.h vtmc_stamp_from_mesh) ------------------------------------------------------------------------------------
 MESH_MAX_COORDINATE = 2.0 ** 20
 
