@@ -5,6 +5,7 @@
 //   host_selftest --gpu-resident <out_dir>  the same scene, grid in HBM, Update on the device
 //   host_selftest --gpu-lod <out_dir>  a resident terrain meshed at three levels of detail around a viewer; dumps nodes + per-node counts
 //   host_selftest --gpu-nav <out_dir>  the navigation layer of a box of a resident terrain; dumps the spans, the column offsets and the box
+//   host_selftest --gpu-navfield <out_dir>  a flow field on that build: dumps the cells, every span's path and the located goal spans
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -270,6 +271,56 @@ static int gpu_nav_run(const std::string &out)
     return 0;
 }
 
+// the world of --gpu-nav and its box; a field towards two goals found by position, then every span's path
+static int gpu_navfield_run(const std::string &out)
+{
+    VoxelTerrain vt;
+    vt._width = 64;
+    vt._elevation = 32;
+    vt._height = 32;
+    vt._voxelScale = 0.5f;
+    vt.TerrainOrigin = Vector3(-3.0f, 1.0f, 2.0f);
+    vt._deviceResident = true;
+    vt._seed = 977;
+    vt.Init();
+    Vector2 lo, up;
+    lo.x = -100; lo.y = -100; up.x = 100; up.y = 100;
+    vt.InsertModifier(std::make_shared<PlaneModifier>(6.3f, lo, up, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(27.5f, 8.0f, 10.0f), 4.25f, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(5.0f, 6.0f, 9.0f), 3.0f, false));
+    vt.Update();
+    const int updateTriangles = vt.LastTriangleCount();
+    const NavResult nav = vt.BuildNav(Vector3(-1.0f, 1.0f, 3.0f), Vector3(14.0f, 15.0f, 16.5f), 0.9f, 0.4f);
+    // two agents' worth of goals by position: on the plane (height 6.3) near a corner of the box, and further along it; 1 world unit either way
+    const std::vector<int> at = vt.LocateOnNav({Vector3(0.0f, 6.3f, 4.0f), Vector3(12.0f, 6.3f, 15.0f), Vector3(500.0f, 6.3f, 4.0f)}, 1.0f, 1.0f);
+    if (at.size() != 3 || at[0] < 0 || at[1] < 0 || at[2] != -1) return 7;
+    const std::vector<NavFieldCell> cells = vt.BuildNavField({NavGoal{at[0], 0u}, NavGoal{at[1], 3000u}}, 2.0f, 0.5f);
+    if (cells.size() != nav._spans.size() || cells[(size_t)at[0]]._cost != 0u || cells[(size_t)at[0]]._next != -1) return 8;
+    std::vector<int> starts(nav._spans.size());
+    for (size_t i = 0; i < starts.size(); i++) starts[i] = (int)i;
+    starts.push_back(-1);
+    const NavPaths paths = vt.TracePaths(starts, 64);
+    if (paths._lengths.size() != starts.size() || paths._paths.size() != starts.size() * 64 || paths._lengths.back() != 0) return 9;
+    if (vt.LastTriangleCount() != updateTriangles) return 10;   // what Update left stands
+    std::printf("navfield: spans %zu goals %d %d\n", cells.size(), at[0], at[1]);
+    static_assert(sizeof(NavFieldCell) == 8, "dumped as it lies");
+    std::ofstream fc(out + "/navfield_cells.bin", std::ios::binary), fp(out + "/navfield_paths.i32", std::ios::binary),
+        fl(out + "/navfield_lengths.i32", std::ios::binary), fa(out + "/navfield_located.i32", std::ios::binary);
+    fc.write(reinterpret_cast<const char *>(cells.data()), (std::streamsize)(cells.size() * sizeof(NavFieldCell)));
+    fp.write(reinterpret_cast<const char *>(paths._paths.data()), (std::streamsize)(paths._paths.size() * sizeof(int)));
+    fl.write(reinterpret_cast<const char *>(paths._lengths.data()), (std::streamsize)(paths._lengths.size() * sizeof(int)));
+    fa.write(reinterpret_cast<const char *>(at.data()), (std::streamsize)(at.size() * sizeof(int)));
+    bool refused = false;   // a start beyond the spans refuses the whole call
+    try {
+        vt.TracePaths({(int)cells.size()}, 4);
+    } catch (const UnityException &) {
+        refused = true;
+    }
+    if (!refused) return 11;
+    std::printf("HOST-NAVFIELD-OK\n");
+    return 0;
+}
+
 static int gpu_lod_run(const std::string &out)
 {
     VoxelTerrain vt;
@@ -333,10 +384,11 @@ int main(int argc, char **argv)
         if (argc >= 3 && std::string(argv[1]) == "--gpu-resident") return gpu_resident_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-lod") return gpu_lod_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-nav") return gpu_nav_run(argv[2]);
+        if (argc >= 3 && std::string(argv[1]) == "--gpu-navfield") return gpu_navfield_run(argv[2]);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "exception: %s\n", e.what());
         return 3;
     }
-    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir> | --gpu-resident <out_dir> | --gpu-lod <out_dir> | --gpu-nav <out_dir>\n");
+    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir> | --gpu-resident <out_dir> | --gpu-lod <out_dir> | --gpu-nav <out_dir> | --gpu-navfield <out_dir>\n");
     return 64;
 }

@@ -7,7 +7,7 @@
 #include <cstring>
 #include <unordered_set>
 
-#include "../include/vtmc_nav.h"   // includes vtmc.h
+#include "../include/vtmc_navfield.h"   // includes vtmc_nav.h, which includes vtmc.h
 
 namespace PGRTerrain {
 
@@ -215,6 +215,38 @@ public:
         for (const vtmc_nav_span &s : list) out._spans.push_back(NavSpan{s.height, s.y, s.clearance, {s.link[0], s.link[1], s.link[2], s.link[3]}, s.region});
     }
 
+    void NavLocate(const std::vector<Vector3> &positions, float below, float above, std::vector<int> &out) override
+    {
+        std::vector<float> p;
+        for (const Vector3 &v : positions) p.insert(p.end(), {v.x, v.y, v.z});
+        out.assign(positions.size(), -1);
+        static_assert(sizeof(int) == sizeof(int32_t), "spans are read in place");
+        if (vtmc_nav_locate(_ctx, p.data(), (int32_t)positions.size(), below, above, out.data()) != VTMC_OK)
+            throw UnityException(std::string("vtmc_nav_locate: ") + vtmc_last_error(_ctx));
+    }
+    void NavField(const std::vector<NavGoal> &goals, float climbCost, float dropCost, unsigned maxCost, std::vector<NavFieldCell> &out) override
+    {
+        std::vector<vtmc_navfield_goal> g;
+        for (const NavGoal &goal : goals) g.push_back(vtmc_navfield_goal{goal._span, goal._cost});
+        vtmc_navfield_params p;
+        p.climb_cost = climbCost, p.drop_cost = dropCost, p.max_cost = maxCost, p.flags = 0;
+        int32_t n = 0;
+        if (vtmc_navfield_build(_ctx, g.data(), (int32_t)g.size(), &p, nullptr) != VTMC_OK || vtmc_navfield_info(_ctx, &n, nullptr, nullptr) != VTMC_OK)
+            throw UnityException(std::string("vtmc_navfield_build: ") + vtmc_last_error(_ctx));
+        std::vector<vtmc_navfield_cell> cells((size_t)n);
+        if (vtmc_navfield_read(_ctx, cells.data(), n) != VTMC_OK) throw UnityException(std::string("vtmc_navfield_read: ") + vtmc_last_error(_ctx));
+        out.clear();
+        for (const vtmc_navfield_cell &c : cells) out.push_back(NavFieldCell{c.cost, c.next});
+    }
+    void NavTrace(const std::vector<int> &starts, int maxLen, NavPaths &out) override
+    {
+        out._maxLen = maxLen;
+        out._paths.assign(starts.size() * (size_t)(maxLen > 0 ? maxLen : 0), -1);
+        out._lengths.assign(starts.size(), 0);
+        if (vtmc_navfield_trace(_ctx, starts.data(), (int32_t)starts.size(), maxLen, out._paths.data(), out._lengths.data()) != VTMC_OK)
+            throw UnityException(std::string("vtmc_navfield_trace: ") + vtmc_last_error(_ctx));
+    }
+
     int MaterialInit(int fineness) override
     {
         if (vtmc_material_init(_ctx, fineness) != VTMC_OK) throw UnityException(std::string("vtmc_material_init: ") + vtmc_last_error(_ctx));
@@ -354,6 +386,30 @@ NavResult VoxelTerrain::BuildNav(const Vector3 &lower, const Vector3 &upper, flo
     if (!(samples >= 1.0f && samples <= (float)VTMC_NAV_MAX_AGENT_HEIGHT)) throw UnityException("BuildNav: agentHeight outside 1..256 samples");
     NavResult out;
     _backend->TerrainNav(lower, upper, (int)samples, maxStep / _voxelScale, maxSpans, out);
+    return out;
+}
+
+std::vector<int> VoxelTerrain::LocateOnNav(const std::vector<Vector3> &positions, float below, float above)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("LocateOnNav needs an initialised device-resident terrain");
+    std::vector<int> out;
+    _backend->NavLocate(positions, below / _voxelScale, above / _voxelScale, out);
+    return out;
+}
+
+std::vector<NavFieldCell> VoxelTerrain::BuildNavField(const std::vector<NavGoal> &goals, float climbCost, float dropCost, unsigned maxCost)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("BuildNavField needs an initialised device-resident terrain");
+    std::vector<NavFieldCell> out;
+    _backend->NavField(goals, climbCost, dropCost, maxCost, out);
+    return out;
+}
+
+NavPaths VoxelTerrain::TracePaths(const std::vector<int> &starts, int maxLen)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("TracePaths needs an initialised device-resident terrain");
+    NavPaths out;
+    _backend->NavTrace(starts, maxLen, out);
     return out;
 }
 

@@ -324,6 +324,23 @@ struct NavResult {
     MathHelper::Int3 _boxLo, _boxDims;
 };
 
+// New (not in the reference): a flow field on the last BuildNav (include/vtmc_navfield.h, where the rule is).  A goal is a span and the
+// cost of standing on it; a cell is a span's cheapest cost to the nearest goal (kNavFieldUnreached: none within the limit) and the span to
+// step to next (-1: arrived, or unreached); NavPaths holds, for every start, a row of _maxLen spans padded with -1 and its length.
+constexpr unsigned kNavFieldUnreached = 0xffffffffu;
+struct NavGoal {
+    int _span;
+    unsigned _cost;
+};
+struct NavFieldCell {
+    unsigned _cost;
+    int _next;
+};
+struct NavPaths {
+    std::vector<int> _paths, _lengths;
+    int _maxLen = 0;
+};
+
 // New (not in the reference, which can only replace a control map whole): one paint stroke on the material layer (vtmc_material_stroke
 // of include/vtmc.h).  Every texel within _radius of _center (world space) is blended towards the one-hot of _channel (0..3: control map
 // 1's r, g, b, a; 4..7: control map 2's) by _strength * clamp01(2 (1 - d / _radius)).
@@ -400,6 +417,10 @@ struct ExtractBackend {
     {
         throw std::logic_error("TerrainNav on a backend without device-resident terrain");
     }
+    // Flow fields on that build (vtmc_nav_locate, vtmc_navfield_build with _read, vtmc_navfield_trace); below / above in grid units.
+    virtual void NavLocate(const std::vector<Vector3> &, float, float, std::vector<int> &) { throw std::logic_error("NavLocate unsupported"); }
+    virtual void NavField(const std::vector<NavGoal> &, float, float, unsigned, std::vector<NavFieldCell> &) { throw std::logic_error("NavField unsupported"); }
+    virtual void NavTrace(const std::vector<int> &, int, NavPaths &) { throw std::logic_error("NavTrace unsupported"); }
 
     // Material layer of a device-resident terrain (vtmc_material_*).  MaterialInit returns the layer's size C = 16 * fineness.
     virtual int MaterialInit(int) { throw std::logic_error("MaterialInit on a backend without a material layer"); }
@@ -470,8 +491,18 @@ public:
     // New: where something can walk, and which places are connected (device-resident terrains).  Builds the walkable spans, their links
     // and regions for the box and changes nothing; agentHeight and maxStep are in world units (ceil(agentHeight / _voxelScale) samples of
     // headroom, maxStep / _voxelScale grid units between neighbour columns).  The result is a snapshot: after an edit, build the edit's
-    // box plus a margin again.  No agent radius, no slope by normal, no stitching across boxes, no path search.
+    // box plus a margin again.  No agent radius, no slope by normal, no stitching across boxes; the path search is BuildNavField below.
     NavResult BuildNav(const Vector3 &lower, const Vector3 &upper, float agentHeight, float maxStep, int maxSpans = 1 << 24);
+
+    // New: how to get there.  On the last BuildNav: LocateOnNav gives the span each world position stands on (the nearest span of its
+    // column within `below` under and `above` over it, world units; -1: none); BuildNavField every span's cheapest cost to the nearest
+    // goal and the span to step to next (a level step costs 1024; climbCost / dropCost, 0..1024, are added per grid unit of height
+    // climbed / dropped; a span beyond maxCost is unreached); TracePaths the spans an agent visits from each start by following next, at
+    // most maxLen of them.  One field serves any number of agents.  The next BuildNav drops the field; an edit does not.  No agent
+    // radius, no any-angle smoothing, no field across two boxes.
+    std::vector<int> LocateOnNav(const std::vector<Vector3> &positions, float below, float above);
+    std::vector<NavFieldCell> BuildNavField(const std::vector<NavGoal> &goals, float climbCost, float dropCost, unsigned maxCost = 0x7fffffffu);
+    NavPaths TracePaths(const std::vector<int> &starts, int maxLen);
 
     // -- inspection (tests, callers that consume the meshes) ----------------------------------
     const BlockMesh &Block(int x, int y, int z) const { return _blocks[((size_t)x * (_elevation / blockSize) + y) * (_height / blockSize) + z]; }

@@ -36,7 +36,8 @@
  *   Region     the components of the undirected graph whose edges are the links, taken in either direction.  region is the smallest span
  *              index of the component.
  * OUT OF SCOPE, deliberately, and left to the host: no agent-radius erosion; no slope test by normal (slope is limited through max_step,
- * the largest height difference between neighbour columns); no stitching of the results of two boxes; no path search.
+ * the largest height difference between neighbour columns); no stitching of the results of two boxes.  Path search is not here either but
+ * in a layer of its own on top of this one: vtmc_navfield.h (locate, cost field, traced paths; PATHFINDING.md).
  *
  * Life cycle.  The buffers are library-owned and grow-only, valid until the next vtmc_terrain_nav_build, vtmc_terrain_init,
  * vtmc_terrain_load or vtmc_destroy.  The result is a snapshot of the grid at build time: later edits do not invalidate it (rebuild the

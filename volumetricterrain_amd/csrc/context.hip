@@ -200,6 +200,8 @@ int32_t vtmc_destroy(vtmc_ctx *ctx)
         if (ev) quiet(hipEventDestroy(ev));
     for (auto &ev : ctx->ev_nav)
         if (ev) quiet(hipEventDestroy(ev));
+    for (auto &ev : ctx->ev_navfield)
+        if (ev) quiet(hipEventDestroy(ev));
     if (ctx->ev_gather) quiet(hipEventDestroy(ctx->ev_gather));
     if (ctx->ev_last_gather) quiet(hipEventDestroy(ctx->ev_last_gather));
     if (ctx->ev_comm_chain) quiet(hipEventDestroy(ctx->ev_comm_chain));

@@ -249,7 +249,7 @@ int32_t vtmc_terrain_nav_build(vtmc_ctx *ctx, const float lower[3], const float 
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     VTMC_HIP(ctx, hipStreamSynchronize(s));
-    nav.valid = false;   // from here on the buffers no longer hold the previous build
+    nav_drop(ctx);   // from here on the buffers no longer hold the previous build, nor does the flow field on it stand
     nav.timed = false;
     if (int rc = ensure(ctx, nav.offsets, sz.offsets_bytes)) return rc;
     int32_t *offsets = (int32_t *)nav.offsets.p;

@@ -116,6 +116,16 @@ struct VtmcNav {
     int rounds = 0;                                // union / flatten / verify rounds of the last build
 };
 
+// The flow field the context holds (terrain_navfield.hip), built on the nav result above and dropped with it: library-owned, grow-only.
+// cells: the result; work: per span the four edge costs (16 bytes), then the cost D and the cheapest goal cost (4 bytes each); ctl: the
+// flag word of every round of a batch, then the reached count.
+struct VtmcNavField {
+    VtmcDevBuf cells, work, ctl;
+    bool valid = false;
+    int32_t n = 0, reached = 0, rounds = 0;
+    bool timed = false;   // the events around the last build's kernels were recorded (vtmc_debug_navfield_ms)
+};
+
 // An extract that has been queued on a stream and not yet completed by extract_finish().
 struct VtmcPending {
     bool active = false;    // queued, extract_finish() not yet called
@@ -207,6 +217,9 @@ struct vtmc_ctx {
     // terrain_nav.hip: the last navigation build and the events around its kernels (created by the first build)
     VtmcNav nav;
     hipEvent_t ev_nav[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // terrain_navfield.hip: the flow field on that build and the events around its kernels (edge costs and goals, relaxation, next)
+    VtmcNavField navfield;
+    hipEvent_t ev_navfield[4] = {nullptr, nullptr, nullptr, nullptr};
     // terrain_lod.hip: the node list of the last level-of-detail result (host, and the copy the gather kernel reads), the packed
     // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the events around
     // the last gather launch (vtmc_debug_lod_gather_ms)
@@ -263,6 +276,8 @@ int check_dims(vtmc_ctx *ctx, int nx, int ny, int nz);
 BlockSpace dense_space(const float *d_base, int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz, int n_volumes, int64_t sv);
 float *pinned_stage(vtmc_ctx *ctx, size_t bytes);   // the pinned stage of host-gathered data (vtmc_api.hip), grown to `bytes`; null: none to be had, go pageable
 void material_drop(vtmc_ctx *ctx);   // terrain_material.hip: vtmc_terrain_init / _load drop the layer
+// whatever invalidates the nav result drops the flow field built on it: vtmc_terrain_init / _load and every vtmc_terrain_nav_build
+inline void nav_drop(vtmc_ctx *ctx) { ctx->nav.valid = false, ctx->navfield.valid = false; }
 int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp);   // sp then walks the (bx,by,bz) list
 int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, ResultSource source, int32_t *tri_count);   // queued on the context's stream and finished
 // The vertex attributes of a terrain result (terrain_material.hip, terrain_ao.hip), in vtmc_api.hip.  attr_gate: may `who` compute one for

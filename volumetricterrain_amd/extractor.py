@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, NAVFIELD_CELL_DTYPE, NAVFIELD_GOAL_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
 from .modifiers import AmbientOcclusion, LodParams, NavParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
 
 
@@ -482,6 +482,61 @@ class Extractor:
         p, o, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int32()
         self._check(self._L.vtmc_nav_device_results(self._h, ctypes.byref(p), ctypes.byref(o), ctypes.byref(n)))
         return p.value, o.value, n.value
+
+    # -- flow fields on the navigation build the context holds (include/vtmc_navfield.h) ------------------------------
+    def nav_locate(self, positions, below, above):
+        """The span each world position (n, 3) stands on, or -1: the nearest span of its column within `below` under and `above` over it
+        (world units, divided by the voxel scale in float32)."""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        scale = np.float32(self._terrain_placement[1])
+        out = np.full(len(p), -1, np.int32)
+        self._check(self._L.vtmc_nav_locate(self._h, _ptr(p), len(p), float(np.float32(below) / scale), float(np.float32(above) / scale), _ptr(out)))
+        return out
+
+    def nav_field(self, goals, params):
+        """Builds the flow field of the goals on the nav result held: `goals` is an int array of spans (cost 0), (span, cost) pairs or a
+        NAVFIELD_GOAL_DTYPE array; `params` a NavFieldParams (or a vtmc_navfield_params struct).  Returns the cells (NAVFIELD_CELL_DTYPE,
+        one per span: cost, or NAVFIELD_UNREACHED, and the span to step to next, or -1)."""
+        g = np.asarray(goals)
+        if g.dtype != NAVFIELD_GOAL_DTYPE:
+            pairs = np.asarray(goals, np.int64)
+            if pairs.ndim == 1:
+                pairs = np.stack([pairs, np.zeros_like(pairs)], axis=1)
+            if pairs.ndim != 2 or pairs.shape[1] != 2 or (pairs[:, 1] < 0).any() or (pairs[:, 1] > 0xffffffff).any() or (abs(pairs[:, 0]) >= 2 ** 31).any():
+                raise ValueError("goals must be spans, (span, cost) pairs or a NAVFIELD_GOAL_DTYPE array")
+            g = np.zeros(len(pairs), NAVFIELD_GOAL_DTYPE)
+            g["span"], g["cost"] = pairs[:, 0], pairs[:, 1]
+        g = np.ascontiguousarray(g)
+        p, n = _struct(params), ctypes.c_int32()
+        self._check(self._L.vtmc_navfield_build(self._h, _ptr(g), len(g), ctypes.byref(p), ctypes.byref(n)))
+        return self.navfield_read()
+
+    def navfield_info(self):
+        """(spans, reached spans, relaxation rounds) of the flow field the context holds."""
+        n, r, k = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._L.vtmc_navfield_info(self._h, ctypes.byref(n), ctypes.byref(r), ctypes.byref(k)))
+        return n.value, r.value, k.value
+
+    def navfield_read(self):
+        """The cells of the flow field the context holds."""
+        cells = np.zeros(self.navfield_info()[0], NAVFIELD_CELL_DTYPE)
+        self._check(self._L.vtmc_navfield_read(self._h, _ptr(cells), len(cells)))
+        return cells
+
+    def device_navfield(self):
+        """(device address of the cells, the number of spans) of the last nav_field; valid until the next one, the next terrain_nav,
+        terrain_init, terrain_load or close."""
+        p, n = ctypes.c_void_p(), ctypes.c_int32()
+        self._check(self._L.vtmc_navfield_device_results(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def nav_trace(self, starts, max_len):
+        """(paths, lengths): for every start (a span, or -1) the spans that following `next` visits, at most max_len of them, in a row of
+        paths (len(starts), max_len) padded with -1, and the number of them."""
+        s = np.ascontiguousarray(starts, np.int32).reshape(-1)
+        paths, lengths = np.full((len(s), max(int(max_len), 0)), -1, np.int32), np.zeros(len(s), np.int32)
+        self._check(self._L.vtmc_navfield_trace(self._h, _ptr(s), len(s), int(max_len), _ptr(paths), _ptr(lengths)))
+        return paths, lengths
 
     # -- material layer: VoxelTerrain.SetControlMap's splat volumes in HBM, paint, and per-vertex weights -------------
     def material_init(self, fineness):

@@ -485,6 +485,27 @@ class NavParams:
         return s
 
 
+class NavFieldParams:
+    """The parameters of Extractor.nav_field: what a unit of height climbed and a unit dropped add to a step's cost, in level steps (a
+    level step costs NAVFIELD_UNIT), both in [0, 1024], and the cost beyond which a span counts as unreached.  The costs are dimensionless
+    per GRID unit, so to_struct needs no voxel scale."""
+
+    def __init__(self, climb_cost, drop_cost, max_cost=0x7fffffff):
+        with np.errstate(over="ignore"):
+            self._climb, self._drop = _f(climb_cost), _f(drop_cost)
+        for name, v in (("climb_cost", self._climb), ("drop_cost", self._drop)):
+            if not np.isfinite(v) or not 0 <= v <= 1024:
+                raise ValueError("navfield %s must be finite and in [0, 1024]" % name)
+        if isinstance(max_cost, bool) or int(max_cost) != max_cost or not 1 <= max_cost <= 0x7fffffff:
+            raise ValueError("navfield max_cost must be an integer in 1..2^31-1")
+        self._max = int(max_cost)
+
+    def to_struct(self):
+        s = _lib.NavFieldParamsStruct()
+        s.climb_cost, s.drop_cost, s.max_cost, s.flags = float(self._climb), float(self._drop), self._max, 0
+        return s
+
+
 # -- mesh stamps (include/vtmc.h vtmc_stamp_from_mesh) ------------------------------------------------------------------------------------
 MESH_MAX_COORDINATE = 2.0 ** 20
 
