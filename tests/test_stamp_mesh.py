@@ -18,6 +18,7 @@ import terrain_twin
 from terrain_twin import assert_grid, bits
 import stamp_twin
 import mesh_twin
+from host_check import run_host_check
 from mesh_twin import box, concat, icosphere, torus, voxelize
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -194,6 +195,11 @@ def test_twin_does_not_depend_on_vertex_or_triangle_order(name):
 
 def test_twin_far_mesh_saturates():
     assert (twin_stamp("deep_inside") == 3).all() and (twin_stamp("far_outside") == -3).all() and (twin_stamp("far_behind") == -3).all()
+
+
+def test_host_check_runs_clean_under_the_host_sanitizers(tmp_path):
+    """tools/mesh_host_check.cpp: the host half (csrc/mesh_host.h) as a stand-alone program under ASan and UBSan, on the CPU."""
+    run_host_check("mesh_host_check", tmp_path)
 
 
 # -- GPU --------------------------------------------------------------------------------------------------------------------------------

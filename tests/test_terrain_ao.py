@@ -9,8 +9,6 @@ On the CPU twin of that world (the oracle's extract) the 6-cell result holds 132
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +16,7 @@ import pytest
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib
 import ao_twin as twin
+from host_check import run_host_check
 import path_twin
 from terrain_twin import gpu_struct, no_result
 from test_terrain_brushes import WORLD
@@ -77,17 +76,7 @@ def test_null_context_is_an_error_not_a_crash():
 
 def test_host_check_runs_clean_under_the_host_sanitizers(tmp_path):
     """tools/ao_host_check.cpp: the host half (csrc/terrain_ao.h) as a stand-alone program under ASan and UBSan, on the CPU."""
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no host C++ compiler")
-    exe = tmp_path / "ao_host_check"
-    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
-                            os.path.join(ROOT, "tools", "ao_host_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    if build.returncode != 0 and re.search(r"cannot find .*(asan|ubsan)|unsupported option .*-fsanitize|libasan|libubsan", build.stderr):
-        pytest.skip("the sanitizer runtime is not installed")
-    assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0 and "ao_host_check: ok" in run.stdout, (run.returncode, run.stdout[-1000:], run.stderr[-2000:])
+    run_host_check("ao_host_check", tmp_path)
 
 
 # -- CPU: known answers of the twin -----------------------------------------------------------------------------------------------------

@@ -15,8 +15,6 @@ import ctypes
 import functools
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,6 +23,7 @@ import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib
 from volumetricterrain_amd.terrainfile import terrain_uniform
 import fragment_twin as twin
+from host_check import run_host_check
 from extract_checks import assert_tris_match
 from terrain_twin import bits, block_list, dirty_ids, image_bytes, invalid, no_result
 
@@ -208,17 +207,7 @@ def test_null_pointers_are_errors_not_crashes():
 
 def test_host_check_runs_clean_under_the_host_sanitizers(tmp_path):
     """tools/fragments_host_check.cpp: the host half (csrc/terrain_fragments.h) as a stand-alone program under ASan and UBSan, on the CPU."""
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no host C++ compiler")
-    exe = tmp_path / "fragments_host_check"
-    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
-                            os.path.join(ROOT, "tools", "fragments_host_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    if build.returncode != 0 and re.search(r"cannot find .*(asan|ubsan)|unsupported option .*-fsanitize|libasan|libubsan", build.stderr):
-        pytest.skip("the sanitizer runtime is not installed")
-    assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0 and "fragments_host_check: ok" in run.stdout, (run.returncode, run.stdout[-1000:], run.stderr[-2000:])
+    run_host_check("fragments_host_check", tmp_path)
 
 
 # -- CPU: the twin ----------------------------------------------------------------------------------------------------------------------

@@ -10,7 +10,6 @@ each comparison of the selection is exact in double and the node lists must be E
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -19,6 +18,7 @@ import pytest
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib
 import lod_twin as twin
+from host_check import run_host_check
 from extract_checks import FLOATS, assert_tris_match
 from terrain_twin import assert_triangles, no_result
 
@@ -174,17 +174,6 @@ def test_twin_world_positions():
 def test_host_check_runs_clean_under_the_host_sanitizers_and_agrees_with_the_twin(tmp_path):
     """tools/lod_host_check.cpp: the host half (csrc/terrain_lod.h) as a stand-alone program under ASan and UBSan, on the CPU: its own
     known answers, then the node lists of every case above, which must equal the twin's."""
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no host C++ compiler")
-    exe = tmp_path / "lod_host_check"
-    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
-                            os.path.join(ROOT, "tools", "lod_host_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    if build.returncode != 0 and re.search(r"cannot find .*(asan|ubsan)|unsupported option .*-fsanitize|libasan|libubsan", build.stderr):
-        pytest.skip("the sanitizer runtime is not installed")
-    assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0 and "lod_host_check: ok" in run.stdout, (run.returncode, run.stdout[-1000:], run.stderr[-2000:])
     cases = [(name, split, MAX_LEVEL) for name, split in CASES] + [("inside", 1024.0, 2), ("inside", 4.0, 0), ("on_a_face", 1.0, 1)]
     args = []
     for name, split, level in cases:
@@ -193,8 +182,7 @@ def test_host_check_runs_clean_under_the_host_sanitizers_and_agrees_with_the_twi
     args += [str(d) for d in DIMS] + ["0"] * 3 + ["1"] + ["0"] * 3 + ["2", "1", "1"]          # two roots, max_nodes 1
     args += [str(d) for d in DIMS] + ["0"] * 3 + ["1"] + ["0"] * 3 + ["3", "1", "100"]        # a 64-cell root does not divide 32
     args += [str(d) for d in DIMS] + ["0"] * 3 + ["1"] + ["nan", "0", "0"] + ["2", "1", "100"]
-    run = subprocess.run([str(exe)] + args, capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, (run.returncode, run.stdout[-1000:], run.stderr[-2000:])
+    run = run_host_check("lod_host_check", tmp_path, args)   # without arguments first, then with these
     chunks = re.split(r"^case \d+ ", run.stdout, flags=re.M)[1:]
     assert len(chunks) == len(cases) + 3
     for (name, split, level), chunk in zip(cases, chunks):

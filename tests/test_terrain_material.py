@@ -14,6 +14,7 @@ import pytest
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib
 import material_twin as twin
+from host_check import run_host_check
 from terrain_twin import gpu_struct, no_result
 from test_terrain_brushes import WORLD
 
@@ -120,6 +121,11 @@ def test_null_context_is_an_error_not_a_crash():
              L.vtmc_material_vertices(None, ctypes.byref(n)), L.vtmc_material_read_vertices(None, buf.ctypes.data, 8),
              L.vtmc_material_device_results(None, ctypes.byref(p), ctypes.byref(n))]
     assert calls == [_lib.ERR_INVALID_ARG] * 8
+
+
+def test_host_check_runs_clean_under_the_host_sanitizers(tmp_path):
+    """tools/material_host_check.cpp: the host half (csrc/terrain_material.h) as a stand-alone program under ASan and UBSan, on the CPU."""
+    run_host_check("material_host_check", tmp_path)
 
 
 # -- GPU ----------------------------------------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ import pytest
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _header, _lib
 import nav_twin as twin
+from host_check import run_host_check
 from terrain_twin import bits, no_result, sample_range
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -199,17 +200,7 @@ def test_world_positions():
 
 def test_host_check_runs_clean_under_the_host_sanitizers(tmp_path):
     """tools/nav_host_check.cpp: the host half (csrc/terrain_nav.h) as a stand-alone program under ASan and UBSan, on the CPU."""
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no host C++ compiler")
-    exe = tmp_path / "nav_host_check"
-    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
-                            os.path.join(ROOT, "tools", "nav_host_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    if build.returncode != 0 and re.search(r"cannot find .*(asan|ubsan)|unsupported option .*-fsanitize|libasan|libubsan", build.stderr):
-        pytest.skip("the sanitizer runtime is not installed")
-    assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0 and "nav_host_check: ok" in run.stdout, (run.returncode, run.stdout[-1000:], run.stderr[-2000:])
+    run_host_check("nav_host_check", tmp_path)
 
 
 def test_dllimport_stubs_match_the_header():

@@ -18,6 +18,7 @@ import volumetricterrain_amd as vt
 from volumetricterrain_amd import _header, _lib
 import nav_twin
 import navfield_twin as twin
+from host_check import run_host_check
 import test_terrain_nav as nav
 from terrain_twin import no_result
 
@@ -147,17 +148,7 @@ def test_navfield_params_validate():
 
 def test_host_check_runs_clean_under_the_host_sanitizers(tmp_path):
     """tools/navfield_host_check.cpp: the host half (csrc/terrain_navfield.h) as a stand-alone program under ASan and UBSan, on the CPU."""
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no host C++ compiler")
-    exe = tmp_path / "navfield_host_check"
-    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
-                            os.path.join(ROOT, "tools", "navfield_host_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    if build.returncode != 0 and re.search(r"cannot find .*(asan|ubsan)|unsupported option .*-fsanitize|libasan|libubsan", build.stderr):
-        pytest.skip("the sanitizer runtime is not installed")
-    assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0 and "navfield_host_check: ok" in run.stdout, (run.returncode, run.stdout[-1000:], run.stderr[-2000:])
+    run_host_check("navfield_host_check", tmp_path)
 
 
 # -- CPU: the twin against answers stated by hand ---------------------------------------------------------------------------------------------

@@ -8,8 +8,6 @@ degenerate: 40 tiles of 256 triangles, a ragged last tile, tile boundaries insid
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,6 +15,7 @@ import pytest
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib
 import scatter_twin as twin
+from host_check import run_host_check
 from terrain_twin import gpu_struct, no_result, twin_update
 from test_terrain_brushes import DIMS, ORIGIN, SCALE, SEED, WORLD
 
@@ -108,17 +107,7 @@ def test_null_context_is_an_error_not_a_crash():
 
 def test_host_check_runs_clean_under_the_host_sanitizers(tmp_path):
     """tools/scatter_host_check.cpp: the host half (csrc/terrain_scatter.h) as a stand-alone program under ASan and UBSan, on the CPU."""
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    if not cxx:
-        pytest.skip("no host C++ compiler")
-    exe = tmp_path / "scatter_host_check"
-    build = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-ffp-contract=off",
-                            os.path.join(ROOT, "tools", "scatter_host_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
-    if build.returncode != 0 and re.search(r"cannot find .*(asan|ubsan)|unsupported option .*-fsanitize|libasan|libubsan", build.stderr):
-        pytest.skip("the sanitizer runtime is not installed")
-    assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0 and "scatter_host_check: ok" in run.stdout, (run.returncode, run.stdout[-1000:], run.stderr[-2000:])
+    run_host_check("scatter_host_check", tmp_path)
 
 
 # -- CPU: the twin on the oracle's mesh of the world ---------------------------------------------------------------------------------------

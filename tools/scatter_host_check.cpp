@@ -1,11 +1,13 @@
 // scatter_host_check.cpp -- a stand-alone run of the host half of the surface scatter (csrc/terrain_scatter.h: the argument checks, dc,
-// the tile count and the hash of the rule), for the host sanitizers:
+// the tile count and the hash of the rule; csrc/scan_layout.h: the buffer of the scan over the tiles), for the host sanitizers:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -ffp-contract=off tools/scatter_host_check.cpp -o scatter_host_check && ./scatter_host_check
 // Exits 0 when every answer is the expected one.
+#include "../volumetricterrain_amd/csrc/scan_layout.h"
 #include "../volumetricterrain_amd/csrc/terrain_scatter.h"
 #include <cstdio>
 #include <initializer_list>
 #include <limits>
+#include <vector>
 
 using namespace vtmc;
 
@@ -105,6 +107,22 @@ int main()
     EXPECT(scatter_tiles(0) == 0u && scatter_tiles(1) == 1u && scatter_tiles(256) == 1u && scatter_tiles(257) == 2u);
     EXPECT(scatter_tiles(2147483647ll) == 8388608u);
     EXPECT(scatter_mask_bytes(0) == 0u && scatter_mask_bytes(10112) == 10240u && scatter_mask_bytes(2147483647ll) == 2147483648ull);
+
+    // the buffer of the scan over the tiles' totals: 8 bytes of total, then 4 bytes per tile and per group of 1024 tiles, twice
+    const struct { uint64_t tiles, groups; size_t bytes; } layouts[] = {{0, 0, 8}, {1, 1, 24}, {1024, 1, 8208}, {1025, 2, 8224}, {67 * 23, 2, 8u + 8u * (67 * 23 + 2)},
+                                                                      {scatter_tiles(2147483647ll), 8192, 67174408}};   // 2^23 tiles: the most a result holds
+    for (const auto &want : layouts) {
+        const ScanLayout l(want.tiles);
+        EXPECT(l.groups() == want.groups && l.bytes() == want.bytes && l.total() == nullptr);
+    }
+    {
+        std::vector<unsigned char> buffer(ScanLayout(1025).bytes());
+        const ScanLayout l(1025, buffer.data());
+        const unsigned char *at = buffer.data();
+        EXPECT((const unsigned char *)l.total() == at && (const unsigned char *)l.tile_totals() == at + 8 && (const unsigned char *)l.tile_offsets() == at + 8 + 4 * 1025);
+        EXPECT((const unsigned char *)l.group_totals() == at + 8 + 8 * 1025 && (const unsigned char *)l.group_offsets() == at + 8 + 8 * 1025 + 4 * 2);
+        EXPECT((const unsigned char *)(l.group_offsets() + l.groups()) == at + buffer.size());
+    }
 
     // the hash, against values worked out with arbitrary-precision integers
     EXPECT(scatter_fin(0ull) == 0ull);

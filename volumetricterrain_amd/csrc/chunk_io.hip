@@ -138,18 +138,17 @@ int32_t vtmc_chunk_write(vtmc_ctx *ctx, const char *path, int32_t volume, const 
     char *img = (char *)ctx->chunk_image.p;
     VTMC_HIP(ctx, hipMemsetAsync(img, 0, l.total, st));  // padding bytes are zero, as chunkfile.py writes them
     VTMC_HIP(ctx, hipMemcpyAsync(img, &h, sizeof h, hipMemcpyHostToDevice, st));
-    launch_begin();   // the pack launches below report their own status, nothing older
     if (with_samples) {
         const int dx = h.cells[0] + 2, dy = h.cells[1] + 2, dz = h.cells[2] + 2;
         const long long n = (long long)dx * dy * dz;
-        hipLaunchKernelGGL(pack_samples_kernel, dim3(grid_for(n)), dim3(256), 0, st, sp.base + volume * sp.sv, sp.sx, sp.sy, sp.sz, dx, dy,
-                           dz, (float *)(img + l.samples));
+        VTMC_HIP(ctx, launch(pack_samples_kernel, dim3(grid_for(n)), dim3(256), 0, st, sp.base + volume * sp.sv, sp.sx, sp.sy, sp.sz, dx, dy, dz,
+                             (float *)(img + l.samples)));
     }
-    hipLaunchKernelGGL(pack_offsets_kernel, dim3(grid_for(bpv + 1)), dim3(256), 0, st, (const uint32_t *)ctx->offsets.p + b0, bpv + 1,
-                       (uint32_t *)(img + l.tri_offsets));
+    VTMC_HIP(ctx, launch(pack_offsets_kernel, dim3(grid_for(bpv + 1)), dim3(256), 0, st, (const uint32_t *)ctx->offsets.p + b0, bpv + 1,
+                         (uint32_t *)(img + l.tri_offsets)));
     if (ctx->result.indexed) {
-        hipLaunchKernelGGL(pack_offsets_kernel, dim3(grid_for(bpv + 1)), dim3(256), 0, st, (const uint32_t *)ctx->voffsets.p + b0, bpv + 1,
-                           (uint32_t *)(img + l.vert_offsets));
+        VTMC_HIP(ctx, launch(pack_offsets_kernel, dim3(grid_for(bpv + 1)), dim3(256), 0, st, (const uint32_t *)ctx->voffsets.p + b0, bpv + 1,
+                             (uint32_t *)(img + l.vert_offsets)));
         if (h.n_vertices)
             VTMC_HIP(ctx, hipMemcpyAsync(img + l.vertices, (const vtmc_vertex *)ctx->verts.p + span[2], sizeof(vtmc_vertex) * (size_t)h.n_vertices,
                                          hipMemcpyDeviceToDevice, st));
@@ -158,10 +157,9 @@ int32_t vtmc_chunk_write(vtmc_ctx *ctx, const char *path, int32_t volume, const 
                                          sizeof(int32_t) * 3 * (size_t)h.n_triangles, hipMemcpyDeviceToDevice, st));
     } else if (h.n_triangles) {
         const long long nd = 19ll * h.n_triangles;
-        hipLaunchKernelGGL(pack_triangles_kernel, dim3(grid_for(nd)), dim3(256), 0, st, (const uint32_t *)ctx->tris.p + 19ll * span[0], nd,
-                           (uint32_t)b0, (uint32_t *)(img + l.triangles));
+        VTMC_HIP(ctx, launch(pack_triangles_kernel, dim3(grid_for(nd)), dim3(256), 0, st, (const uint32_t *)ctx->tris.p + 19ll * span[0], nd, (uint32_t)b0,
+                             (uint32_t *)(img + l.triangles)));
     }
-    VTMC_HIP(ctx, launch_end());
     std::vector<char> host;
     try {   // nothing is thrown through the C boundary
         host.resize(l.total);

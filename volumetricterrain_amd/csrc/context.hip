@@ -141,12 +141,6 @@ int32_t vtmc_create(int32_t device, vtmc_ctx **out_ctx)
     if ((e = take_stream(device, ctx->stream_own_queue, ctx->n_cus, &ctx->stream)) != hipSuccess) return bail("hipStreamCreate", e);
     for (auto &ev : ctx->ev)
         if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
-    for (auto &ev : ctx->ev_fill)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
-    for (auto &ev : ctx->ev_lod)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
-    for (auto &ev : ctx->ev_scatter)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreateWithFlags(&ctx->ev_origins, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = pin(ctx->h_totals, 64 * sizeof(uint32_t))) != hipSuccess) return bail("hipHostMalloc", e);
     memset(ctx->h_totals.p, 0, 64 * sizeof(uint32_t));
@@ -188,24 +182,15 @@ int32_t vtmc_destroy(vtmc_ctx *ctx)
     park_stream(ctx->device, true, ctx->queue_stream);
     park_stream(ctx->device, ctx->stream_own_queue, ctx->stream);
     ctx->comm_stream = ctx->queue_stream = ctx->stream = nullptr;
-    // 3. events
+    // 3. events: those named here; the stage clocks of the passes (StageClock) destroy theirs in `delete ctx` below -- after steps 1 and 2
+    //    like these, so no stream of the context can still be recording into one
     if (ctx->ev_origins) quiet(hipEventDestroy(ctx->ev_origins));
     for (auto &ev : ctx->ev)
-        if (ev) quiet(hipEventDestroy(ev));
-    for (auto &ev : ctx->ev_fill)
-        if (ev) quiet(hipEventDestroy(ev));
-    for (auto &ev : ctx->ev_lod)
-        if (ev) quiet(hipEventDestroy(ev));
-    for (auto &ev : ctx->ev_scatter)
-        if (ev) quiet(hipEventDestroy(ev));
-    for (auto &ev : ctx->ev_nav)
-        if (ev) quiet(hipEventDestroy(ev));
-    for (auto &ev : ctx->ev_navfield)
         if (ev) quiet(hipEventDestroy(ev));
     if (ctx->ev_gather) quiet(hipEventDestroy(ctx->ev_gather));
     if (ctx->ev_last_gather) quiet(hipEventDestroy(ctx->ev_last_gather));
     if (ctx->ev_comm_chain) quiet(hipEventDestroy(ctx->ev_comm_chain));
-    // 4. device buffers and pinned memory: the members free their own
+    // 4. device buffers, pinned memory and the stage clocks' events: the members free their own
     delete ctx;
     return VTMC_OK;
 }

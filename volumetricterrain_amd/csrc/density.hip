@@ -436,9 +436,7 @@ hipError_t launch_density(const DensityLaunch &dl, const unsigned char *d_perm, 
         const long long n_wgs = n_plane_wgs * n_seg * dl.n_volumes;
         const long long n_rows = (long long)dl.n_volumes * n_steps;
         if (n_wgs <= 0 || n_wgs > 0x7fffffffll || n_rows > 0x7fffffffll) return hipErrorInvalidValue;
-        launch_begin();
-        hipLaunchKernelGGL(density_row_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, stream, dl, d_origins, 2,
-                           n_steps, seg_len, d_rows);
+        if (hipError_t e = launch(density_row_kernel, lanes256(n_rows), dim3(256), 0, stream, dl, d_origins, 2, n_steps, seg_len, d_rows)) return e;
         // residency cap (tuning key "density_wgs_per_cu"): unused dynamic LDS leaves wave slots, registers and LDS to the kernels of
         // another stream -- the extract stages of the previous batch are HBM-bound, this kernel is ALU-bound
         const bool zt = dl.sz == 1 && dl.sx != 1;   // z-fastest: transposed stores
@@ -447,26 +445,18 @@ hipError_t launch_density(const DensityLaunch &dl, const unsigned char *d_perm, 
         const size_t dyn = lds_want > lds_static ? (lds_want - lds_static) & ~(size_t)255 : 0;
 #define VTMC_COL(N)                                                                                                                   \
     case N:                                                                                                                           \
-        if (zt)                                                                                                                       \
-            hipLaunchKernelGGL((density_column_kernel<N, true>), dim3((unsigned)n_wgs), dim3(256), dyn, stream, dl, d_perm, d_origins, d_rows, \
-                               d_out, fast_is_z, (int)n_plane_wgs, n_seg, seg_len, nullptr);                                         \
-        else                                                                                                                          \
-            hipLaunchKernelGGL((density_column_kernel<N, false>), dim3((unsigned)n_wgs), dim3(256), dyn, stream, dl, d_perm, d_origins, d_rows, \
-                               d_out, fast_is_z, (int)n_plane_wgs, n_seg, seg_len, d_signs);                                        \
-        break;
+        return launch(zt ? density_column_kernel<N, true> : density_column_kernel<N, false>, dim3((unsigned)n_wgs), dim3(256), dyn, stream, dl, d_perm, \
+                      d_origins, d_rows, d_out, fast_is_z, (int)n_plane_wgs, n_seg, seg_len, zt ? nullptr : d_signs);
         switch (dl.octaves) {   // the octave count is a template parameter: the eight octaves of a sample are straight-line code
             VTMC_COL(1) VTMC_COL(2) VTMC_COL(3) VTMC_COL(4) VTMC_COL(5) VTMC_COL(6) VTMC_COL(7) VTMC_COL(8)
         }
 #undef VTMC_COL
-        return launch_end();
+        return hipErrorInvalidValue;   // octaves < 1: the entry points refuse it
     }
     const int nseg = (dfast + 255) / 256;
     long long n_wgs = (long long)dl.n_volumes * dslow * dl.dy * nseg;
     if (n_wgs <= 0 || n_wgs > 0x7fffffffll) return hipErrorInvalidValue;
-    launch_begin();
-    hipLaunchKernelGGL(density_generic_kernel, dim3((unsigned)n_wgs), dim3(256), 0, stream, dl, d_perm, d_origins, d_out,
-                       fast_is_z, nseg);
-    return launch_end();
+    return launch(density_generic_kernel, dim3((unsigned)n_wgs), dim3(256), 0, stream, dl, d_perm, d_origins, d_out, fast_is_z, nseg);
 }
 
 size_t density_rows_bytes(int n_volumes, int dy, int dz) { return (size_t)n_volumes * (size_t)(dy > dz ? dy : dz) * kRowDwords * sizeof(float); }
@@ -536,7 +526,7 @@ int32_t vtmc_density_fill_device_async(vtmc_ctx *ctx, const vtmc_density_params 
     hipStream_t up = st;
     if (ctx->queue_stream && st == ctx->queue_stream) {
         up = ctx->stream;
-        if (ctx->fill_timed) VTMC_HIP(ctx, hipStreamWaitEvent(up, ctx->ev_fill[1], 0));
+        if (ctx->fill_clock.armed) VTMC_HIP(ctx, hipStreamWaitEvent(up, ctx->fill_clock.event(1), 0));
     }
     VTMC_HIP(ctx, hipMemcpyAsync(ctx->origins.p, ctx->h_origins.p, org_bytes, hipMemcpyHostToDevice, up));
     VTMC_HIP(ctx, hipEventRecord(ctx->ev_origins, up));
@@ -575,21 +565,20 @@ int32_t vtmc_density_fill_device_async(vtmc_ctx *ctx, const vtmc_density_params 
         ctx->sign_of.n_volumes = n_volumes;
         ctx->sign_of.sv = volume_stride;
     }
-    VTMC_HIP(ctx, hipEventRecord(ctx->ev_fill[0], st));
+    VTMC_HIP(ctx, ctx->fill_clock.begin());
+    VTMC_HIP(ctx, ctx->fill_clock.mark(0, st));
     VTMC_HIP(ctx, launch_density(dl, (const unsigned char *)ctx->perm.p, (const int *)ctx->origins.p, (float *)ctx->yrows.p, d_out, d_signs, st));
-    VTMC_HIP(ctx, hipEventRecord(ctx->ev_fill[1], st));
-    ctx->fill_timed = true;
+    VTMC_HIP(ctx, ctx->fill_clock.mark(1, st));
+    ctx->fill_clock.arm();
     return VTMC_OK;
 }
 
 int32_t vtmc_last_fill_ms(vtmc_ctx *ctx, float *ms)
 {
     if (!ctx || !ms) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->fill_timed) return fail(ctx, VTMC_ERR_NO_RESULT, "last_fill_ms before any density fill");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    VTMC_HIP(ctx, hipEventSynchronize(ctx->ev_fill[1]));
-    VTMC_HIP(ctx, hipEventElapsedTime(ms, ctx->ev_fill[0], ctx->ev_fill[1]));
-    return VTMC_OK;
+    if (!ctx->fill_clock.armed) return fail(ctx, VTMC_ERR_NO_RESULT, "last_fill_ms before any density fill");
+    if (int rc = ctx->fill_clock.sync_last(ctx)) return rc;
+    return ctx->fill_clock.elapsed(ctx, 0, 1, ms);
 }
 
 int32_t vtmc_density_fill_device(vtmc_ctx *ctx, const vtmc_density_params *params, const int32_t *origins, int32_t n_volumes,

@@ -234,9 +234,7 @@ __global__ __launch_bounds__(kRayThreads) void raycast_kernel(RaycastArgs a)
 
 static hipError_t launch_raycast(const RaycastArgs &a, hipStream_t stream)
 {
-    launch_begin();
-    hipLaunchKernelGGL(raycast_kernel, dim3((unsigned)a.n_rays), dim3(kRayThreads), 0, stream, a);
-    return launch_end();
+    return launch(raycast_kernel, dim3((unsigned)a.n_rays), dim3(kRayThreads), 0, stream, a);
 }
 
 static int check_rays(vtmc_ctx *ctx, int32_t n_rays, bool null_arg, float max_distance, uint32_t flags)

@@ -3,14 +3,13 @@
 // of kScanThreads tiles and every group its total; scan_groups_kernel, one workgroup, scans the group totals and leaves the grand total
 // in 64 bits.  A tile's offset is the sum of the two prefixes.  (One workgroup over all the tile totals took 0.19 ms of the scatter pass's
 // 0.88 at 1024^3: profiles/r19/scatter.)  The kernels are static: every translation unit that includes this launches its own copy.
+// The buffer they work in is a ScanLayout (scan_layout.h, which the host halves read too); launch_scan queues the pair over one.
 #ifndef VTMC_SCAN_KERNELS_H
 #define VTMC_SCAN_KERNELS_H
-#include <hip/hip_runtime.h>
-#include <cstdint>
+#include "scan_layout.h"
+#include "vtmc_ctx.h"
 
 namespace vtmc {
-
-constexpr int kScanThreads = 1024;   // threads of a scan workgroup = tiles of a group
 
 // exclusive prefix of v over the 64 * WAVES threads of the workgroup, wave by wave and then across the waves; total = the sum
 template <int WAVES>
@@ -74,6 +73,15 @@ static __global__ __launch_bounds__(kScanThreads) void scan_groups_kernel(const 
         at += group_totals[i];
     }
     if (threadIdx.x == kScanThreads - 1) *total = part[threadIdx.x];
+}
+
+// Both levels over a layout whose tile totals are written (at least one tile), asynchronous on `stream`; the status of the launches
+static hipError_t launch_scan(const ScanLayout &l, hipStream_t stream)
+{
+    const uint32_t groups = (uint32_t)l.groups();
+    if (hipError_t e = launch(scan_tiles_kernel, dim3(groups), dim3(kScanThreads), 0, stream, l.tile_totals(), (uint32_t)l.n_tiles, l.tile_offsets(), l.group_totals()))
+        return e;
+    return launch(scan_groups_kernel, dim3(1), dim3(kScanThreads), 0, stream, l.group_totals(), groups, l.group_offsets(), l.total());
 }
 
 }  // namespace vtmc

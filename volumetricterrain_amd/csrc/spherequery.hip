@@ -386,9 +386,7 @@ __global__ __launch_bounds__(kSqThreads) void sphere_query_kernel(SphereArgs a)
 template <bool Cast>
 static hipError_t launch_sphere_query(const SphereArgs &a, hipStream_t stream)
 {
-    launch_begin();
-    hipLaunchKernelGGL(sphere_query_kernel<Cast>, dim3((unsigned)a.n_q), dim3(kSqThreads), 0, stream, a);
-    return launch_end();
+    return launch(sphere_query_kernel<Cast>, dim3((unsigned)a.n_q), dim3(kSqThreads), 0, stream, a);
 }
 
 // the argument rules the four entry points share (max_distance: casts only)

@@ -155,9 +155,7 @@ hipError_t launch_terrain_fill(float *grid, long long n, uint64_t seed, int n_cu
     long long wgs = (n + 255) / 256;
     if (wgs > (long long)n_cus * 16) wgs = (long long)n_cus * 16;
     if (wgs < 1) wgs = 1;
-    launch_begin();
-    hipLaunchKernelGGL(terrain_fill_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, grid, n, seed);
-    return launch_end();
+    return launch(terrain_fill_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, grid, n, seed);
 }
 
 // declared by vtmc_internal.h, whose text the traffic constant of the extract path is tied to: kept for that declaration, vtmc_terrain_update
@@ -209,6 +207,14 @@ TerrainModifierArgs sample_range(const TerrainShape &sh, const vtmc_modifier &md
     a.lx = low[0], a.ly = low[1], a.lz = low[2];
     a.dx = ext[0], a.dy = ext[1], a.dz = ext[2];
     return a;
+}
+
+TerrainBox bounds_box(const TerrainShape &sh, const float lower[3], const float upper[3])
+{
+    vtmc_modifier md{};
+    for (int k = 0; k < 3; ++k) md.lower[k] = lower[k], md.upper[k] = upper[k];
+    int low[3], up[3];
+    return box_of(sample_range(sh, md, low, up));
 }
 
 // dirty blocks: up >= 8b && low <= 8b + 8 on every axis (VoxelTerrain.cs:307-317), as index ranges; returns how many were newly marked

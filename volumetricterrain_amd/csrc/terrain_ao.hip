@@ -274,12 +274,8 @@ int32_t vtmc_ao_vertices(vtmc_ctx *ctx, const vtmc_ao_params *params, int64_t *n
         a.stats = (uint32_t *)ctx->ao_stats.p;
         a.out = (uint8_t *)ctx->ao.values.p;
         const size_t lds = ao_tile_bytes(tb.extent);
-        launch_begin();
-        if (res.indexed)
-            hipLaunchKernelGGL(ao_kernel<true>, dim3(res.active), dim3(256), lds, ctx->stream, (const uint32_t *)ctx->verts.p, a);
-        else
-            hipLaunchKernelGGL(ao_kernel<false>, dim3(res.active), dim3(256), lds, ctx->stream, (const uint32_t *)ctx->tris.p, a);
-        VTMC_HIP(ctx, launch_end());
+        if (res.indexed) VTMC_HIP(ctx, launch(ao_kernel<true>, dim3(res.active), dim3(256), lds, ctx->stream, (const uint32_t *)ctx->verts.p, a));
+        else VTMC_HIP(ctx, launch(ao_kernel<false>, dim3(res.active), dim3(256), lds, ctx->stream, (const uint32_t *)ctx->tris.p, a));
     }
     VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->ao.n = n;

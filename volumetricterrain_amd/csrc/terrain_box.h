@@ -1,6 +1,6 @@
 // terrain_box.h -- the box walk and the clamp draws every edit kernel of the resident terrain shares: a thread's place in a modifier's
-// sample box, the grid and image indices, Mathf.Clamp against the drawn void / full values, the CSG write rule, and the one launch of a
-// box kernel.
+// sample box, the grid and image indices, Mathf.Clamp against the drawn void / full values, the CSG write rule, and launch_box: the launch
+// (vtmc_ctx.h) in the shape of a box kernel.
 #ifndef VTMC_TERRAIN_BOX_H
 #define VTMC_TERRAIN_BOX_H
 #include "vtmc_ctx.h"
@@ -67,10 +67,7 @@ static bool box_launchable(const TerrainBox &b) { return (b.dz + 3) / 4 <= 65535
 template <class... Params, class... Args>
 static hipError_t launch_box(void (*kernel)(Params...), const TerrainBox &b, hipStream_t stream, Args... args)
 {
-    if (!box_launchable(b)) return hipErrorInvalidValue;
-    launch_begin();
-    hipLaunchKernelGGL(kernel, box_grid(b), dim3(64, 4, 1), 0, stream, args...);
-    return launch_end();
+    return box_launchable(b) ? launch(kernel, box_grid(b), dim3(64, 4, 1), 0, stream, args...) : hipErrorInvalidValue;
 }
 
 }  // namespace vtmc

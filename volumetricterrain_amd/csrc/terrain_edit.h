@@ -34,6 +34,8 @@ static TerrainBox box_of(const TerrainModifierArgs &m) { return TerrainBox{m.lx,
 // terrain.hip: a modifier's kernel arguments: its AABB in sample indices, [low, up] clamped to the grid (up[] is also what the dirty blocks
 // are found from)
 TerrainModifierArgs sample_range(const TerrainShape &sh, const vtmc_modifier &md, int low[3], int up[3]);
+// terrain.hip: the clamped sample box of the world bounds lower..upper, as sample_range finds a modifier's (the queries that take a box)
+TerrainBox bounds_box(const TerrainShape &sh, const float lower[3], const float upper[3]);
 // terrain.hip: `bytes` of host data into a grow-only buffer of the context that the modifier's kernel reads (the heightmap, a path's
 // segments); drains ctx->stream first, and the copy blocks
 int stage_for_queue(vtmc_ctx *ctx, VtmcDevBuf &buf, const void *host, size_t bytes);

@@ -307,9 +307,7 @@ static dim3 row_grid(const TerrainBox &b) { return dim3((unsigned)((b.dx + 63) /
 template <class... Params, class... Args>
 static hipError_t launch_rows(void (*kernel)(Params...), const TerrainBox &b, hipStream_t stream, Args... args)
 {
-    launch_begin();
-    hipLaunchKernelGGL(kernel, row_grid(b), dim3(64, 4, 1), 0, stream, args...);
-    return launch_end();
+    return launch(kernel, row_grid(b), dim3(64, 4, 1), 0, stream, args...);
 }
 
 // The scratch of a box of n samples.  Grown only after the stream has drained: an earlier detach of the same queue may still be reading it.
@@ -334,15 +332,11 @@ static int label_box(vtmc_ctx *ctx, const float *grid, const TerrainBox &b, int 
     const TerrainShape &sh = ctx->tshape;
     hipStream_t s = ctx->stream;
     VTMC_HIP(ctx, hipMemsetAsync(ctl, 0, kCtlWords * sizeof(int), s));
-    launch_begin();
-    hipLaunchKernelGGL(frag_local_kernel, dim3((unsigned)((b.dx + kTileX - 1) / kTileX), (unsigned)((b.dy + kTileY - 1) / kTileY), (unsigned)((b.dz + kTileZ - 1) / kTileZ)),
-                       dim3(64, 4, 1), 0, s, grid, P, aux, ctl + kCtlFlag, sh, b);
-    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, launch(frag_local_kernel, dim3((unsigned)((b.dx + kTileX - 1) / kTileX), (unsigned)((b.dy + kTileY - 1) / kTileY), (unsigned)((b.dz + kTileZ - 1) / kTileZ)),
+                         dim3(64, 4, 1), 0, s, grid, P, aux, ctl + kCtlFlag, sh, b));
     VTMC_HIP(ctx, launch_rows(frag_merge_kernel, b, s, P, ctl + kCtlFlag, b, (int)n));
     const long long faces = 2 * ((long long)b.dx * b.dy + (long long)b.dx * b.dz + (long long)b.dy * b.dz);
-    launch_begin();
-    hipLaunchKernelGGL(frag_anchor_kernel, dim3((unsigned)((faces + 255) / 256)), dim3(256), 0, s, P, aux, ctl + kCtlFlag, b, (int)n);
-    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, launch(frag_anchor_kernel, lanes256(faces), dim3(256), 0, s, P, aux, ctl + kCtlFlag, b, (int)n));
     VTMC_HIP(ctx, launch_rows(frag_flatten_kernel, b, s, P, aux, ctl + kCtlFlag, b, (int)n));
     *P_out = P, *aux_out = aux, *ctl_out = ctl;
     return VTMC_OK;
@@ -380,11 +374,7 @@ int32_t vtmc_terrain_fragments(vtmc_ctx *ctx, const float lower[3], const float 
     if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_fragments before terrain_init");
     if (const char *what = fragments_args_fault(lower, upper, max_samples, capture_min_samples)) return fail(ctx, VTMC_ERR_INVALID_ARG, "terrain_fragments: %s", what);
     const TerrainShape &sh = ctx->tshape;
-    vtmc_modifier md{};
-    memcpy(md.lower, lower, sizeof md.lower);
-    memcpy(md.upper, upper, sizeof md.upper);
-    int low[3], up[3];
-    const TerrainBox b = box_of(sample_range(sh, md, low, up));
+    const TerrainBox b = bounds_box(sh, lower, upper);
     if (box_empty(b)) return VTMC_OK;
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     int *P, *ctl;

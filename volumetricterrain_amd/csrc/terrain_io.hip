@@ -254,8 +254,6 @@ int stage_buffers(vtmc_ctx *ctx)
     return VTMC_OK;
 }
 
-unsigned wgs_for(size_t n) { return (unsigned)((n + 255) / 256); }
-
 // counts (one word per brick, 1 = RAW) -> slots (exclusive scan, slots[n] = n_raw) -> raw_list, queued on the context's stream
 int queue_raw_list(vtmc_ctx *ctx, const BrickScratch &s, size_t n)
 {
@@ -263,9 +261,7 @@ int queue_raw_list(vtmc_ctx *ctx, const BrickScratch &s, size_t n)
     VTMC_HIP(ctx, hipMemsetAsync(s.ctrl, 0, s.ctrl_bytes + 256, st));   // the scan's ticket, error word and tile status; the totals behind them
     const BlockSpace none{};   // the scan reads it only for the active list, which is not asked for
     VTMC_HIP(ctx, launch_scan_fused(none, s.counts, (int)n, s.slots, nullptr, s.ctrl, s.totals, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, st));
-    launch_begin();
-    hipLaunchKernelGGL(brick_list_kernel, dim3(wgs_for(n)), dim3(256), 0, st, s.kinds, s.slots, (unsigned)n, s.raw_list);
-    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, launch(brick_list_kernel, lanes256((int64_t)n), dim3(256), 0, st, s.kinds, s.slots, (unsigned)n, s.raw_list));
     return VTMC_OK;
 }
 
@@ -306,10 +302,8 @@ int save_file(vtmc_ctx *ctx, FILE *f, const char *path, uint32_t flags, int64_t 
     const int nseg = (g.dim_x + 127) / 128;
     const unsigned n_tasks = (unsigned)nseg * (unsigned)g.nby * (unsigned)g.nbz;
     VTMC_HIP(ctx, hipMemsetAsync(s.kinds, 0, pad16(n), st));   // the table's padding bytes are zero in the file
-    launch_begin();
-    if (!exact) hipLaunchKernelGGL(brick_flags_kernel, dim3((n_tasks + 3) / 4), dim3(256), 0, st, (const float *)ctx->terrain.p, g, nseg, n_tasks, s.flags);
-    hipLaunchKernelGGL(brick_kinds_kernel, dim3(wgs_for(n)), dim3(256), 0, st, s.flags, g, (unsigned)n, exact ? 1 : 0, s.kinds, s.counts);
-    VTMC_HIP(ctx, launch_end());
+    if (!exact) VTMC_HIP(ctx, launch(brick_flags_kernel, dim3((n_tasks + 3) / 4), dim3(256), 0, st, (const float *)ctx->terrain.p, g, nseg, n_tasks, s.flags));
+    VTMC_HIP(ctx, launch(brick_kinds_kernel, lanes256((int64_t)n), dim3(256), 0, st, s.flags, g, (unsigned)n, exact ? 1 : 0, s.kinds, s.counts));
     if (int rc = queue_raw_list(ctx, s, n)) return rc;
     std::vector<uint8_t> kinds;
     try {   // nothing is thrown through the C boundary
@@ -342,10 +336,8 @@ int save_file(vtmc_ctx *ctx, FILE *f, const char *path, uint32_t flags, int64_t 
         if (i < n_slices) {
             const size_t half = (i & 1) * kSliceBytes, bytes = (size_t)slice_bricks(i) * kBrickBytes;
             uint32_t *d_stage = (uint32_t *)((char *)ctx->tio_stage.p + half);
-            launch_begin();
-            hipLaunchKernelGGL(brick_pack_kernel, dim3(slice_bricks(i)), dim3(256), 0, st, (const uint32_t *)ctx->terrain.p, g,
-                               s.raw_list + (size_t)i * kSliceBricks, d_stage);
-            VTMC_HIP(ctx, launch_end());
+            VTMC_HIP(ctx, launch(brick_pack_kernel, dim3(slice_bricks(i)), dim3(256), 0, st, (const uint32_t *)ctx->terrain.p, g, s.raw_list + (size_t)i * kSliceBricks,
+                                 d_stage));
             VTMC_HIP(ctx, hipMemcpyAsync(ctx->h_tio.p + half, d_stage, bytes, hipMemcpyDeviceToHost, st));
             VTMC_HIP(ctx, hipEventRecord(events.ev[i & 1], st));
         }
@@ -409,14 +401,10 @@ int load_file(vtmc_ctx *ctx, FILE *f, const char *path, const TerrainHeader &h, 
     Events events;
     VTMC_HIP(ctx, events.create());
     VTMC_HIP(ctx, hipMemcpyAsync(s.kinds, kinds.data(), kinds.size(), hipMemcpyHostToDevice, st));
-    launch_begin();
-    hipLaunchKernelGGL(brick_counts_kernel, dim3(wgs_for(n)), dim3(256), 0, st, s.kinds, (unsigned)n, s.counts);
-    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, launch(brick_counts_kernel, lanes256((int64_t)n), dim3(256), 0, st, s.kinds, (unsigned)n, s.counts));
     if (int rc = queue_raw_list(ctx, s, n)) return rc;
-    launch_begin();
-    hipLaunchKernelGGL(brick_redraw_kernel, dim3((unsigned)((g.dim_x + 63) / 64), (unsigned)((g.dim_z + 3) / 4), (unsigned)((g.dim_y + kRedrawRun - 1) / kRedrawRun)),
-                       dim3(64, 4, 1), 0, st, (float *)ctx->terrain.p, g, s.kinds, h.seed, event);
-    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, launch(brick_redraw_kernel, dim3((unsigned)((g.dim_x + 63) / 64), (unsigned)((g.dim_z + 3) / 4), (unsigned)((g.dim_y + kRedrawRun - 1) / kRedrawRun)),
+                         dim3(64, 4, 1), 0, st, (float *)ctx->terrain.p, g, s.kinds, h.seed, event));
     // slice i is read from the file into half i & 1 of the pinned stage while slice i - 1 is copied and scattered out of the other half
     const uint32_t n_slices = (h.n_raw + kSliceBricks - 1) / kSliceBricks;
     bool got = true;
@@ -429,9 +417,7 @@ int load_file(vtmc_ctx *ctx, FILE *f, const char *path, const TerrainHeader &h, 
         uint32_t *d_stage = (uint32_t *)((char *)ctx->tio_stage.p + half);
         VTMC_HIP(ctx, hipMemcpyAsync(d_stage, ctx->h_tio.p + half, bytes, hipMemcpyHostToDevice, st));
         VTMC_HIP(ctx, hipEventRecord(events.ev[i & 1], st));
-        launch_begin();
-        hipLaunchKernelGGL(brick_unpack_kernel, dim3(nb), dim3(256), 0, st, (uint32_t *)ctx->terrain.p, g, s.raw_list + (size_t)i * kSliceBricks, d_stage);
-        VTMC_HIP(ctx, launch_end());
+        VTMC_HIP(ctx, launch(brick_unpack_kernel, dim3(nb), dim3(256), 0, st, (uint32_t *)ctx->terrain.p, g, s.raw_list + (size_t)i * kSliceBricks, d_stage));
     }
     VTMC_HIP(ctx, hipStreamSynchronize(st));
     uint32_t scan_failed = 0;

@@ -86,14 +86,12 @@ int32_t vtmc_terrain_extract_lod(vtmc_ctx *ctx, const vtmc_lod_params *params, i
     int rc = VTMC_OK;
     {
         hipError_t e = hipMemcpyAsync(ctx->lod_nodes_dev.p, nodes.data(), n * sizeof(vtmc_lod_node), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev_lod[0], ctx->stream);
-        if (e == hipSuccess) {
-            launch_begin();
-            hipLaunchKernelGGL(lod_gather_kernel, dim3((unsigned)n), dim3(kLodThreads), 0, ctx->stream, (const float *)ctx->terrain.p, sh.dim_x, sh.dim_y,
-                               sh.dim_z, (const vtmc_lod_node *)ctx->lod_nodes_dev.p, (float *)ctx->lod_tiles.p);
-            e = launch_end();
-        }
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev_lod[1], ctx->stream);
+        if (e == hipSuccess) e = ctx->lod_clock.begin();
+        if (e == hipSuccess) e = ctx->lod_clock.mark(0, ctx->stream);
+        if (e == hipSuccess)
+            e = launch(lod_gather_kernel, dim3((unsigned)n), dim3(kLodThreads), 0, ctx->stream, (const float *)ctx->terrain.p, sh.dim_x, sh.dim_y, sh.dim_z,
+                       (const vtmc_lod_node *)ctx->lod_nodes_dev.p, (float *)ctx->lod_tiles.p);
+        if (e == hipSuccess) e = ctx->lod_clock.mark(1, ctx->stream);
         if (e != hipSuccess) rc = fail(ctx, VTMC_ERR_DEVICE, "terrain_extract_lod: %s", hipGetErrorString(e));
     }
     if (rc == VTMC_OK) {
@@ -106,7 +104,7 @@ int32_t vtmc_terrain_extract_lod(vtmc_ctx *ctx, const vtmc_lod_params *params, i
         return rc;
     }
     ctx->lod_nodes.swap(nodes);
-    ctx->lod_timed = true;
+    ctx->lod_clock.arm();
     if (n_nodes) *n_nodes = (int32_t)n;
     return VTMC_OK;
 }
@@ -127,11 +125,9 @@ int32_t vtmc_terrain_lod_nodes(vtmc_ctx *ctx, vtmc_lod_node *dst, int32_t capaci
 int32_t vtmc_debug_lod_gather_ms(vtmc_ctx *ctx, float *ms)
 {
     if (!ctx || !ms) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->lod_timed) return fail(ctx, VTMC_ERR_NO_RESULT, "debug_lod_gather_ms before any level-of-detail extract");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    VTMC_HIP(ctx, hipEventSynchronize(ctx->ev_lod[1]));
-    VTMC_HIP(ctx, hipEventElapsedTime(ms, ctx->ev_lod[0], ctx->ev_lod[1]));
-    return VTMC_OK;
+    if (!ctx->lod_clock.armed) return fail(ctx, VTMC_ERR_NO_RESULT, "debug_lod_gather_ms before any level-of-detail extract");
+    if (int rc = ctx->lod_clock.sync_last(ctx)) return rc;
+    return ctx->lod_clock.elapsed(ctx, 0, 1, ms);
 }
 
 // Not part of the ABI (tests): the gathered tiles of the level-of-detail result the context holds, VTMC_TILE_SAMPLES floats per node.

@@ -164,9 +164,7 @@ int32_t vtmc_material_init(vtmc_ctx *ctx, int32_t fineness)
     material_drop(ctx);
     const size_t n = (size_t)C * C * C;
     if (int rc = ensure(ctx, ctx->material, n * VTMC_MATERIAL_CHANNELS)) return rc;
-    launch_begin();
-    hipLaunchKernelGGL(material_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (uint2 *)ctx->material.p, (uint32_t)n);
-    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, launch(material_fill_kernel, lanes256(n), dim3(256), 0, ctx->stream, (uint2 *)ctx->material.p, (uint32_t)n));
     VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->mat_c = C;
     return VTMC_OK;
@@ -186,10 +184,8 @@ int32_t vtmc_material_set_control_map(vtmc_ctx *ctx, const float *rgba, int32_t 
     if (bad >= 0) return fail(ctx, VTMC_ERR_INVALID_ARG, "set_control_map: channel %lld of texel %lld is NaN", bad % 4, bad / 4);
     if (int rc = ensure(ctx, ctx->mat_image, bytes)) return rc;
     VTMC_HIP(ctx, hipMemcpyAsync(ctx->mat_image.p, stage ? stage : rgba, bytes, hipMemcpyHostToDevice, ctx->stream));
-    launch_begin();
-    hipLaunchKernelGGL(material_quantise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (uint32_t *)ctx->material.p,
-                       (const float4 *)ctx->mat_image.p, (uint32_t)n, group - 1);
-    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, launch(material_quantise_kernel, lanes256(n), dim3(256), 0, ctx->stream, (uint32_t *)ctx->material.p, (const float4 *)ctx->mat_image.p, (uint32_t)n,
+                         group - 1));
     VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the stage and rgba are free again
     return VTMC_OK;
 }
@@ -242,10 +238,7 @@ int32_t vtmc_material_paint(vtmc_ctx *ctx, const vtmc_material_stroke *strokes, 
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = ensure(ctx, ctx->mat_strokes, sizeof(vtmc_material_stroke) * VTMC_MATERIAL_MAX_STROKES)) return rc;
     VTMC_HIP(ctx, hipMemcpyAsync(ctx->mat_strokes.p, strokes, sizeof(vtmc_material_stroke) * (size_t)n_strokes, hipMemcpyHostToDevice, ctx->stream));
-    launch_begin();
-    hipLaunchKernelGGL(material_paint_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (uint2 *)ctx->material.p,
-                       (const vtmc_material_stroke *)ctx->mat_strokes.p, a);
-    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, launch(material_paint_kernel, lanes256(n), dim3(256), 0, ctx->stream, (uint2 *)ctx->material.p, (const vtmc_material_stroke *)ctx->mat_strokes.p, a));
     VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // strokes is borrowed for the call; the next call may overwrite mat_strokes
     return VTMC_OK;
 }
@@ -271,17 +264,15 @@ int32_t vtmc_material_vertices(vtmc_ctx *ctx, int64_t *n_vertices)
         a.n_blocks = (uint32_t)res.blocks;
         a.nbx = sp.nbx, a.nby = sp.nby;
         a.d_nbx = sp.d_nbx, a.d_nby = sp.d_nby;
-        launch_begin();
         if (res.indexed) {
             const uint32_t V = (uint32_t)res.verts;
-            hipLaunchKernelGGL(material_indexed_kernel, dim3((V + kMatTile - 1) / kMatTile), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->verts.p, V,
-                               (const uint32_t *)ctx->voffsets.p, (uint2 *)ctx->mat_weights.values.p, a);
+            VTMC_HIP(ctx, launch(material_indexed_kernel, dim3((V + kMatTile - 1) / kMatTile), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->verts.p, V,
+                                 (const uint32_t *)ctx->voffsets.p, (uint2 *)ctx->mat_weights.values.p, a));
         } else {
             const uint32_t T = (uint32_t)res.tris;
-            hipLaunchKernelGGL(material_soup_kernel, dim3((T + kMatTile - 1) / kMatTile), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->tris.p, T,
-                               (uint2 *)ctx->mat_weights.values.p, a);
+            VTMC_HIP(ctx, launch(material_soup_kernel, dim3((T + kMatTile - 1) / kMatTile), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->tris.p, T,
+                                 (uint2 *)ctx->mat_weights.values.p, a));
         }
-        VTMC_HIP(ctx, launch_end());
         VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->mat_weights.n = n;

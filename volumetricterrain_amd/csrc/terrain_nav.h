@@ -4,13 +4,12 @@
 #ifndef VTMC_TERRAIN_NAV_H
 #define VTMC_TERRAIN_NAV_H
 #include "../../include/vtmc_nav.h"
+#include "scan_layout.h"
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 
 namespace vtmc {
-
-constexpr int kNavScanGroup = 1024;   // columns of a group of the two-level scan (scan_kernels.h: kScanThreads)
 
 // What is wrong with the arguments of vtmc_terrain_nav_build by value, or null: the texts of vtmc_last_error (VTMC_ERR_INVALID_ARG)
 inline const char *nav_args_fault(const float *lower, const float *upper, const vtmc_nav_params *p)
@@ -43,18 +42,19 @@ inline bool nav_box_empty(const NavBox &b) { return b.d[0] == 0; }
 // and the bytes of the buffers that depend on the columns alone.
 struct NavSizes {
     int64_t columns;         // dx * dz
-    int64_t groups;          // ceil(columns / kNavScanGroup)
+    int64_t groups;          // the groups of the scan over the columns' counts (scan_layout.h)
     size_t offsets_bytes;    // column_offsets: (columns + 1) int32
-    size_t scan_bytes;       // the grand total (8 bytes), the column counts, their prefixes inside a group, the group totals, their prefixes
+    size_t scan_bytes;       // that scan's buffer: a ScanLayout of `columns` tiles
     bool launchable;         // the columns fit a uint32 tile count and a kernel grid
 };
 inline NavSizes nav_sizes(const NavBox &b)
 {
     NavSizes s;
     s.columns = (int64_t)b.d[0] * (int64_t)b.d[2];
-    s.groups = (s.columns + kNavScanGroup - 1) / kNavScanGroup;
+    const ScanLayout scan((uint64_t)s.columns);
+    s.groups = (int64_t)scan.groups();
     s.offsets_bytes = (size_t)(s.columns + 1) * 4u;
-    s.scan_bytes = 8u + 4u * 2u * (size_t)(s.columns + s.groups);
+    s.scan_bytes = scan.bytes();
     s.launchable = s.columns < (int64_t)1 << 31 && ((int64_t)b.d[2] + 3) / 4 <= 65535;
     return s;
 }

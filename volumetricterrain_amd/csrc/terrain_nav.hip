@@ -26,11 +26,9 @@
 #include "scan_kernels.h"
 #include "union_find.h"
 #include <algorithm>
-#include <cstring>
 
 namespace vtmc {
 
-static_assert(kNavScanGroup == kScanThreads, "terrain_nav.h sizes the scan's buffers");
 static_assert(sizeof(vtmc_nav_span) == 32, "two 16-byte stores per span");
 constexpr int kNavRows = 8;   // rows of a column in flight per lane
 enum { kNavCtlFlag = 0, kNavCtlSplit = 1, kNavCtlWords = 2 };   // the control words: the loops' flag, the verify pass's count
@@ -214,14 +212,7 @@ __global__ __launch_bounds__(256) void nav_verify_kernel(const vtmc_nav_span *__
     if (m && __lane_id() == 0) atomicAdd(split, __popcll(m));
 }
 
-static int nav_events(vtmc_ctx *ctx)
-{
-    for (auto &ev : ctx->ev_nav)
-        if (!ev) VTMC_HIP(ctx, hipEventCreate(&ev));
-    return VTMC_OK;
-}
-
-static dim3 span_grid(int32_t n) { return dim3(((unsigned)n + 255u) / 256u); }
+static dim3 walk_grid(const TerrainBox &b) { return dim3((unsigned)((b.dx + 63) / 64), (unsigned)((b.dz + 3) / 4)); }   // nav_walk_kernel, nav_read_kernel
 
 }  // namespace vtmc
 
@@ -236,11 +227,7 @@ int32_t vtmc_terrain_nav_build(vtmc_ctx *ctx, const float lower[3], const float 
     if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "terrain_nav_build before terrain_init");
     if (const char *what = nav_args_fault(lower, upper, params)) return fail(ctx, VTMC_ERR_INVALID_ARG, "terrain_nav_build: %s", what);
     const TerrainShape &sh = ctx->tshape;
-    vtmc_modifier md{};
-    memcpy(md.lower, lower, sizeof md.lower);
-    memcpy(md.upper, upper, sizeof md.upper);
-    int low[3], up[3];
-    const TerrainBox tb = box_of(sample_range(sh, md, low, up));
+    const TerrainBox tb = bounds_box(sh, lower, upper);
     const int32_t first[3] = {tb.lx, tb.ly, tb.lz}, dims[3] = {tb.dx, tb.dy, tb.dz};
     const NavBox nb = nav_box(first, dims);
     const NavSizes sz = nav_sizes(nb);
@@ -250,42 +237,31 @@ int32_t vtmc_terrain_nav_build(vtmc_ctx *ctx, const float lower[3], const float 
     hipStream_t s = ctx->stream;
     VTMC_HIP(ctx, hipStreamSynchronize(s));
     nav_drop(ctx);   // from here on the buffers no longer hold the previous build, nor does the flow field on it stand
-    nav.timed = false;
+    StageClock<9> &clock = ctx->nav_clock;
+    VTMC_HIP(ctx, clock.begin());   // disarmed: an empty box, or a box without spans, leaves it so
     if (int rc = ensure(ctx, nav.offsets, sz.offsets_bytes)) return rc;
     int32_t *offsets = (int32_t *)nav.offsets.p;
     unsigned long long total = 0;
     if (nav_box_empty(nb)) {
         VTMC_HIP(ctx, hipMemsetAsync(offsets, 0, sz.offsets_bytes, s));
     } else {
-        if (int rc = nav_events(ctx)) return rc;
         if (int rc = ensure(ctx, nav.scan, sz.scan_bytes)) return rc;
         if (int rc = ensure(ctx, nav.ctl, kNavCtlWords * sizeof(int))) return rc;
-        const uint32_t columns = (uint32_t)sz.columns, groups = (uint32_t)sz.groups;
-        unsigned long long *d_total = (unsigned long long *)nav.scan.p;   // then the column counts, their prefixes, the group totals, their prefixes
-        uint32_t *counts = (uint32_t *)(d_total + 1), *tile_offsets = counts + columns;
-        uint32_t *group_totals = tile_offsets + columns, *group_offsets = group_totals + groups;
+        const uint32_t columns = (uint32_t)sz.columns;
+        const ScanLayout scan(columns, nav.scan.p);   // the tiles are the columns, their totals the span counts
         int *flag = (int *)nav.ctl.p;
         const float *grid = (const float *)ctx->terrain.p;
-        const dim3 walk((unsigned)((tb.dx + 63) / 64), (unsigned)((tb.dz + 3) / 4));
+        const dim3 walk = walk_grid(tb);
         VTMC_HIP(ctx, hipMemsetAsync(flag, 0, kNavCtlWords * sizeof(int), s));
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_nav[0], s));
-        launch_begin();
-        hipLaunchKernelGGL(nav_walk_kernel<false>, walk, dim3(64, 4, 1), 0, s, grid, sh, tb, (int)params->agent_height, counts, (const int32_t *)nullptr,
-                           (vtmc_nav_span *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, 0);
-        VTMC_HIP(ctx, launch_end());
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_nav[1], s));
-        launch_begin();
-        hipLaunchKernelGGL(scan_tiles_kernel, dim3(groups), dim3(kScanThreads), 0, s, (const uint32_t *)counts, columns, tile_offsets, group_totals);
-        VTMC_HIP(ctx, launch_end());
-        launch_begin();
-        hipLaunchKernelGGL(scan_groups_kernel, dim3(1), dim3(kScanThreads), 0, s, (const uint32_t *)group_totals, groups, group_offsets, d_total);
-        VTMC_HIP(ctx, launch_end());
-        launch_begin();
-        hipLaunchKernelGGL(nav_offsets_kernel, dim3((columns + 1u + 255u) / 256u), dim3(256), 0, s, (const uint32_t *)tile_offsets, (const uint32_t *)group_offsets,
-                           (const unsigned long long *)d_total, columns, offsets);
-        VTMC_HIP(ctx, launch_end());
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_nav[2], s));
-        VTMC_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s));
+        VTMC_HIP(ctx, clock.mark(0, s));
+        VTMC_HIP(ctx, launch(nav_walk_kernel<false>, walk, dim3(64, 4, 1), 0, s, grid, sh, tb, (int)params->agent_height, scan.tile_totals(), nullptr, nullptr,
+                             nullptr, nullptr, 0));
+        VTMC_HIP(ctx, clock.mark(1, s));
+        VTMC_HIP(ctx, launch_scan(scan, s));
+        VTMC_HIP(ctx, launch(nav_offsets_kernel, lanes256((int64_t)columns + 1), dim3(256), 0, s, scan.tile_offsets(), scan.group_offsets(), scan.total(), columns,
+                             offsets));
+        VTMC_HIP(ctx, clock.mark(2, s));
+        VTMC_HIP(ctx, hipMemcpyAsync(&total, scan.total(), sizeof(total), hipMemcpyDeviceToHost, s));
         VTMC_HIP(ctx, hipStreamSynchronize(s));
         if (!nav_total_fits(total, params->max_spans))
             return fail(ctx, VTMC_ERR_TOO_LARGE, "terrain_nav_build: %llu spans exceed max_spans %d", total, params->max_spans);
@@ -296,20 +272,10 @@ int32_t vtmc_terrain_nav_build(vtmc_ctx *ctx, const float lower[3], const float 
         }
         vtmc_nav_span *spans = (vtmc_nav_span *)nav.spans.p;
         int32_t *col_of = (int32_t *)nav.scratch.p, *parent = col_of + n;
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_nav[3], s));
-        if (n > 0) {
-            launch_begin();
-            hipLaunchKernelGGL(nav_walk_kernel<true>, walk, dim3(64, 4, 1), 0, s, grid, sh, tb, (int)params->agent_height, (uint32_t *)nullptr,
-                               (const int32_t *)offsets, spans, col_of, parent, n);
-            VTMC_HIP(ctx, launch_end());
-        }
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_nav[4], s));
-        if (n > 0) {
-            launch_begin();
-            hipLaunchKernelGGL(nav_link_kernel, span_grid(n), dim3(256), 0, s, spans, (const int32_t *)col_of, (const int32_t *)offsets, flag, tb, n,
-                               (int)params->agent_height, params->max_step);
-            VTMC_HIP(ctx, launch_end());
-        }
+        VTMC_HIP(ctx, clock.mark(3, s));
+        if (n > 0) VTMC_HIP(ctx, launch(nav_walk_kernel<true>, walk, dim3(64, 4, 1), 0, s, grid, sh, tb, (int)params->agent_height, nullptr, offsets, spans, col_of, parent, n));
+        VTMC_HIP(ctx, clock.mark(4, s));
+        if (n > 0) VTMC_HIP(ctx, launch(nav_link_kernel, lanes256(n), dim3(256), 0, s, spans, col_of, offsets, flag, tb, n, (int)params->agent_height, params->max_step));
         // Regions: union, flatten, verify -- and again while the verify pass still finds a link across two regions.  The union pass was
         // seen to lose a union now and then under contention (a few per million on an MI355X, profiles/r21/nav); a repeat only has those
         // few to make, and the result that is kept has passed the check.  The events time the first round.
@@ -317,20 +283,14 @@ int32_t vtmc_terrain_nav_build(vtmc_ctx *ctx, const float lower[3], const float 
         nav.rounds = 0;
         for (int round = 0; n > 0; ++round) {
             const bool timed = round == 0;
-            if (timed) VTMC_HIP(ctx, hipEventRecord(ctx->ev_nav[5], s));
-            launch_begin();
-            hipLaunchKernelGGL(nav_union_kernel, span_grid(n), dim3(256), 0, s, (const vtmc_nav_span *)spans, (int *)parent, flag, n);
-            VTMC_HIP(ctx, launch_end());
-            if (timed) VTMC_HIP(ctx, hipEventRecord(ctx->ev_nav[6], s));
-            launch_begin();
-            hipLaunchKernelGGL(nav_flatten_kernel, span_grid(n), dim3(256), 0, s, spans, (const int *)parent, flag, n);
-            VTMC_HIP(ctx, launch_end());
-            if (timed) VTMC_HIP(ctx, hipEventRecord(ctx->ev_nav[7], s));
+            if (timed) VTMC_HIP(ctx, clock.mark(5, s));
+            VTMC_HIP(ctx, launch(nav_union_kernel, lanes256(n), dim3(256), 0, s, spans, parent, flag, n));
+            if (timed) VTMC_HIP(ctx, clock.mark(6, s));
+            VTMC_HIP(ctx, launch(nav_flatten_kernel, lanes256(n), dim3(256), 0, s, spans, parent, flag, n));
+            if (timed) VTMC_HIP(ctx, clock.mark(7, s));
             VTMC_HIP(ctx, hipMemsetAsync(flag + kNavCtlSplit, 0, sizeof(int), s));
-            launch_begin();
-            hipLaunchKernelGGL(nav_verify_kernel, span_grid(n), dim3(256), 0, s, (const vtmc_nav_span *)spans, flag + kNavCtlSplit, n);
-            VTMC_HIP(ctx, launch_end());
-            if (timed) VTMC_HIP(ctx, hipEventRecord(ctx->ev_nav[8], s));
+            VTMC_HIP(ctx, launch(nav_verify_kernel, lanes256(n), dim3(256), 0, s, spans, flag + kNavCtlSplit, n));
+            if (timed) VTMC_HIP(ctx, clock.mark(8, s));
             VTMC_HIP(ctx, hipMemcpyAsync(h_ctl, flag, sizeof h_ctl, hipMemcpyDeviceToHost, s));
             VTMC_HIP(ctx, hipStreamSynchronize(s));
             nav.rounds = round + 1;
@@ -339,7 +299,7 @@ int32_t vtmc_terrain_nav_build(vtmc_ctx *ctx, const float lower[3], const float 
             if (round + 1 == kNavMaxRounds)
                 return fail(ctx, VTMC_ERR_DEVICE, "terrain_nav_build: labelling did not converge (%d spans across regions after %d rounds)", h_ctl[kNavCtlSplit], kNavMaxRounds);
         }
-        nav.timed = n > 0;
+        if (n > 0) clock.arm();
     }
     VTMC_HIP(ctx, hipStreamSynchronize(s));
     nav.n = (int32_t)total;
@@ -395,12 +355,12 @@ int32_t vtmc_nav_device_results(vtmc_ctx *ctx, const vtmc_nav_span **d_spans, co
 int32_t vtmc_debug_nav_ms(vtmc_ctx *ctx, float ms[8])
 {
     if (!ctx || !ms) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->nav.valid || !ctx->nav.timed) return fail(ctx, VTMC_ERR_NO_RESULT, "debug_nav_ms before a nav build that launched kernels");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    VTMC_HIP(ctx, hipEventSynchronize(ctx->ev_nav[8]));
+    if (!ctx->nav.valid || !ctx->nav_clock.armed) return fail(ctx, VTMC_ERR_NO_RESULT, "debug_nav_ms before a nav build that launched kernels");
+    if (int rc = ctx->nav_clock.sync_last(ctx)) return rc;
     static const int pairs[7][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}, {5, 6}, {6, 7}, {7, 8}};
     ms[7] = (float)ctx->nav.rounds;
-    for (int i = 0; i < 7; ++i) VTMC_HIP(ctx, hipEventElapsedTime(&ms[i], ctx->ev_nav[pairs[i][0]], ctx->ev_nav[pairs[i][1]]));
+    for (int i = 0; i < 7; ++i)
+        if (int rc = ctx->nav_clock.elapsed(ctx, pairs[i][0], pairs[i][1], &ms[i])) return rc;
     return VTMC_OK;
 }
 
@@ -410,11 +370,7 @@ int32_t vtmc_debug_nav_box_read_ms(vtmc_ctx *ctx, const float lower[3], const fl
 {
     if (!ctx || !lower || !upper || !ms || reps < 1 || reps > 64) return VTMC_ERR_INVALID_ARG;
     if (!ctx->has_terrain) return fail(ctx, VTMC_ERR_NO_RESULT, "debug_nav_box_read_ms before terrain_init");
-    vtmc_modifier md{};
-    memcpy(md.lower, lower, sizeof md.lower);
-    memcpy(md.upper, upper, sizeof md.upper);
-    int low[3], up[3];
-    const TerrainBox tb = box_of(sample_range(ctx->tshape, md, low, up));
+    const TerrainBox tb = bounds_box(ctx->tshape, lower, upper);
     const int32_t first[3] = {tb.lx, tb.ly, tb.lz}, dims[3] = {tb.dx, tb.dy, tb.dz};
     const NavBox nb = nav_box(first, dims);
     const NavSizes sz = nav_sizes(nb);
@@ -422,19 +378,18 @@ int32_t vtmc_debug_nav_box_read_ms(vtmc_ctx *ctx, const float lower[3], const fl
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     VTMC_HIP(ctx, hipStreamSynchronize(s));
-    if (int rc = nav_events(ctx)) return rc;
     if (int rc = ensure(ctx, ctx->nav.scan, sz.scan_bytes)) return rc;
-    ctx->nav.timed = false;   // the events are taken
-    const dim3 walk((unsigned)((tb.dx + 63) / 64), (unsigned)((tb.dz + 3) / 4));
+    StageClock<9> &clock = ctx->nav_clock;
+    VTMC_HIP(ctx, clock.begin());   // borrowed, and left disarmed: its events no longer hold the build's times
+    uint32_t *sink = ScanLayout((uint64_t)sz.columns, ctx->nav.scan.p).tile_totals();   // a word per column
     float t[64];
     for (int i = -1; i < reps; ++i) {
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_nav[0], s));
-        launch_begin();
-        hipLaunchKernelGGL(nav_read_kernel, walk, dim3(64, 4, 1), 0, s, (const float *)ctx->terrain.p, ctx->tshape, tb, (uint32_t *)ctx->nav.scan.p + 2);
-        VTMC_HIP(ctx, launch_end());
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_nav[1], s));
-        VTMC_HIP(ctx, hipEventSynchronize(ctx->ev_nav[1]));
-        if (i >= 0) VTMC_HIP(ctx, hipEventElapsedTime(&t[i], ctx->ev_nav[0], ctx->ev_nav[1]));
+        VTMC_HIP(ctx, clock.mark(0, s));
+        VTMC_HIP(ctx, launch(nav_read_kernel, walk_grid(tb), dim3(64, 4, 1), 0, s, (const float *)ctx->terrain.p, ctx->tshape, tb, sink));
+        VTMC_HIP(ctx, clock.mark(1, s));
+        VTMC_HIP(ctx, hipEventSynchronize(clock.event(1)));
+        if (i >= 0)
+            if (int rc = clock.elapsed(ctx, 0, 1, &t[i])) return rc;
     }
     std::sort(t, t + reps);
     *ms = t[reps / 2];

@@ -231,15 +231,6 @@ __global__ __launch_bounds__(256) void navfield_trace_kernel(const vtmc_navfield
     lengths[i] = len;
 }
 
-static int navfield_events(vtmc_ctx *ctx)
-{
-    for (auto &ev : ctx->ev_navfield)
-        if (!ev) VTMC_HIP(ctx, hipEventCreate(&ev));
-    return VTMC_OK;
-}
-
-static dim3 lanes(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 }  // namespace vtmc
 
 using namespace vtmc;
@@ -262,10 +253,8 @@ int32_t vtmc_nav_locate(vtmc_ctx *ctx, const float *positions, int32_t n, float 
     if (int rc = stage_queries(ctx, src, bytes, (size_t)n * 4u, &st)) return rc;
     const TerrainShape &sh = ctx->tshape;
     const NavLocateBox b{{sh.origin[0], sh.origin[1], sh.origin[2]}, sh.scale, nav.lo[0], nav.lo[2], nav.d[0], nav.d[2]};
-    launch_begin();
-    hipLaunchKernelGGL(nav_locate_kernel, lanes(n), dim3(256), 0, s, st.in[0], n, b, (const int32_t *)nav.offsets.p, (const vtmc_nav_span *)nav.spans.p, nav.n,
-                       below, above, (int32_t *)st.hits);
-    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, launch(nav_locate_kernel, lanes256(n), dim3(256), 0, s, st.in[0], n, b, (const int32_t *)nav.offsets.p, (const vtmc_nav_span *)nav.spans.p, nav.n,
+                         below, above, (int32_t *)st.hits));
     return fetch_hits(ctx, st, spans_out);
 }
 
@@ -285,11 +274,11 @@ int32_t vtmc_navfield_build(vtmc_ctx *ctx, const vtmc_navfield_goal *goals, int3
     hipStream_t s = ctx->stream;
     VTMC_HIP(ctx, hipStreamSynchronize(s));
     nf.valid = false;   // from here on the buffers no longer hold the previous field
-    nf.timed = false;
+    StageClock<4> &clock = ctx->navfield_clock;
     if (int rc = ensure(ctx, nf.cells, navfield_cell_bytes(n))) return rc;
     if (int rc = ensure(ctx, nf.work, navfield_work_bytes(n))) return rc;
     if (int rc = ensure(ctx, nf.ctl, kNavFieldCtlWords * sizeof(int))) return rc;
-    if (int rc = navfield_events(ctx)) return rc;
+    VTMC_HIP(ctx, clock.begin());
     const float *const src[3] = {(const float *)goals, nullptr, nullptr};
     const size_t bytes[3] = {(size_t)n_goals * sizeof(vtmc_navfield_goal), 0, 0};
     QueryStage st;
@@ -298,14 +287,10 @@ int32_t vtmc_navfield_build(vtmc_ctx *ctx, const vtmc_navfield_goal *goals, int3
     uint4 *costs = (uint4 *)nf.work.p;   // then D, then the cheapest goal cost
     uint32_t *D = (uint32_t *)(costs + n), *goal_cost = D + n;
     int *ctl = (int *)nf.ctl.p;
-    VTMC_HIP(ctx, hipEventRecord(ctx->ev_navfield[0], s));
-    launch_begin();
-    hipLaunchKernelGGL(navfield_init_kernel, lanes(n), dim3(256), 0, s, spans, costs, D, goal_cost, n, params->climb_cost, params->drop_cost);
-    VTMC_HIP(ctx, launch_end());
-    launch_begin();
-    hipLaunchKernelGGL(navfield_goals_kernel, lanes(n_goals), dim3(256), 0, s, (const vtmc_navfield_goal *)st.in[0], n_goals, D, goal_cost, n);
-    VTMC_HIP(ctx, launch_end());
-    VTMC_HIP(ctx, hipEventRecord(ctx->ev_navfield[1], s));
+    VTMC_HIP(ctx, clock.mark(0, s));
+    VTMC_HIP(ctx, launch(navfield_init_kernel, lanes256(n), dim3(256), 0, s, spans, costs, D, goal_cost, n, params->climb_cost, params->drop_cost));
+    VTMC_HIP(ctx, launch(navfield_goals_kernel, lanes256(n_goals), dim3(256), 0, s, (const vtmc_navfield_goal *)st.in[0], n_goals, D, goal_cost, n));
+    VTMC_HIP(ctx, clock.mark(1, s));
     // the rounds, a batch per read-back; the first one that changed nothing is the last one counted
     const int64_t most = navfield_max_rounds(n);
     const dim3 runs((unsigned)navfield_runs(n));
@@ -314,11 +299,7 @@ int32_t vtmc_navfield_build(vtmc_ctx *ctx, const vtmc_navfield_goal *goals, int3
         if (rounds >= most) return fail(ctx, VTMC_ERR_DEVICE, "navfield_build: relaxation did not converge (%lld rounds over %d spans)", (long long)rounds, n);
         const int batch = (int)std::min<int64_t>(kNavFieldBatch, most - rounds);
         VTMC_HIP(ctx, hipMemsetAsync(ctl, 0, kNavFieldBatch * sizeof(int), s));
-        for (int b = 0; b < batch; ++b) {
-            launch_begin();
-            hipLaunchKernelGGL(navfield_relax_kernel, runs, dim3(kNavFieldThreads), 0, s, spans, (const uint4 *)costs, D, n, params->max_cost, ctl + b);
-            VTMC_HIP(ctx, launch_end());
-        }
+        for (int b = 0; b < batch; ++b) VTMC_HIP(ctx, launch(navfield_relax_kernel, runs, dim3(kNavFieldThreads), 0, s, spans, costs, D, n, params->max_cost, ctl + b));
         int h_flags[kNavFieldBatch] = {};
         VTMC_HIP(ctx, hipMemcpyAsync(h_flags, ctl, sizeof h_flags, hipMemcpyDeviceToHost, s));
         VTMC_HIP(ctx, hipStreamSynchronize(s));
@@ -328,17 +309,15 @@ int32_t vtmc_navfield_build(vtmc_ctx *ctx, const vtmc_navfield_goal *goals, int3
         }
     }
     VTMC_HIP(ctx, hipMemsetAsync(ctl + kNavFieldCtlReached, 0, sizeof(int), s));
-    VTMC_HIP(ctx, hipEventRecord(ctx->ev_navfield[2], s));
-    launch_begin();
-    hipLaunchKernelGGL(navfield_next_kernel, lanes(n), dim3(256), 0, s, spans, (const uint4 *)costs, (const uint32_t *)D, (const uint32_t *)goal_cost,
-                       (vtmc_navfield_cell *)nf.cells.p, n, ctl + kNavFieldCtlReached);
-    VTMC_HIP(ctx, launch_end());
-    VTMC_HIP(ctx, hipEventRecord(ctx->ev_navfield[3], s));
+    VTMC_HIP(ctx, clock.mark(2, s));
+    VTMC_HIP(ctx, launch(navfield_next_kernel, lanes256(n), dim3(256), 0, s, spans, costs, D, goal_cost, (vtmc_navfield_cell *)nf.cells.p, n, ctl + kNavFieldCtlReached));
+    VTMC_HIP(ctx, clock.mark(3, s));
     int reached = 0;
     VTMC_HIP(ctx, hipMemcpyAsync(&reached, ctl + kNavFieldCtlReached, sizeof reached, hipMemcpyDeviceToHost, s));
     VTMC_HIP(ctx, hipStreamSynchronize(s));
     nf.n = n, nf.reached = reached, nf.rounds = (int32_t)rounds;
-    nf.valid = nf.timed = true;
+    nf.valid = true;
+    clock.arm();
     if (n_reached) *n_reached = reached;
     return VTMC_OK;
 }
@@ -395,10 +374,8 @@ int32_t vtmc_navfield_trace(vtmc_ctx *ctx, const int32_t *starts, int32_t n_star
     if (int rc = stage_queries(ctx, src, bytes, path_bytes + length_bytes, &st)) return rc;
     int32_t *d_paths = (int32_t *)st.hits, *d_lengths = (int32_t *)((unsigned char *)st.hits + path_bytes);
     VTMC_HIP(ctx, hipMemsetAsync(d_paths, 0xff, path_bytes, s));
-    launch_begin();
-    hipLaunchKernelGGL(navfield_trace_kernel, lanes(n_starts), dim3(256), 0, s, (const vtmc_navfield_cell *)nf.cells.p, nf.n, (const int32_t *)st.in[0], n_starts,
-                       max_len, d_paths, d_lengths);
-    VTMC_HIP(ctx, launch_end());
+    VTMC_HIP(ctx, launch(navfield_trace_kernel, lanes256(n_starts), dim3(256), 0, s, (const vtmc_navfield_cell *)nf.cells.p, nf.n, (const int32_t *)st.in[0], n_starts,
+                         max_len, d_paths, d_lengths));
     const unsigned char *h = ctx->h_rays.p + st.hit_off;
     VTMC_HIP(ctx, hipMemcpyAsync(ctx->h_rays.p + st.hit_off, st.hits, st.hit_bytes, hipMemcpyDeviceToHost, s));
     VTMC_HIP(ctx, hipStreamSynchronize(s));
@@ -413,10 +390,10 @@ int32_t vtmc_navfield_trace(vtmc_ctx *ctx, const int32_t *starts, int32_t n_star
 int32_t vtmc_debug_navfield_ms(vtmc_ctx *ctx, float ms[4])
 {
     if (!ctx || !ms) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->navfield.valid || !ctx->navfield.timed) return fail(ctx, VTMC_ERR_NO_RESULT, "debug_navfield_ms before navfield_build");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    VTMC_HIP(ctx, hipEventSynchronize(ctx->ev_navfield[3]));
-    for (int i = 0; i < 3; ++i) VTMC_HIP(ctx, hipEventElapsedTime(&ms[i], ctx->ev_navfield[i], ctx->ev_navfield[i + 1]));
+    if (!ctx->navfield.valid || !ctx->navfield_clock.armed) return fail(ctx, VTMC_ERR_NO_RESULT, "debug_navfield_ms before navfield_build");
+    if (int rc = ctx->navfield_clock.sync_last(ctx)) return rc;
+    for (int i = 0; i < 3; ++i)
+        if (int rc = ctx->navfield_clock.elapsed(ctx, i, i + 1, &ms[i])) return rc;
     ms[3] = (float)ctx->navfield.rounds;
     return VTMC_OK;
 }

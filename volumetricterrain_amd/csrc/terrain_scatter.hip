@@ -252,18 +252,16 @@ int32_t vtmc_scatter_surface(vtmc_ctx *ctx, const vtmc_scatter_params *params, i
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = ensure(ctx, sc.block_offsets, sizeof(int32_t) * ((size_t)B + 1))) return rc;
     sc.epoch = 0;   // from here on the buffers no longer hold the previous scatter
-    sc.timed = false;
+    StageClock<6> &clock = ctx->scatter_clock;
+    VTMC_HIP(ctx, clock.begin());   // disarmed: a result without triangles leaves it so
     unsigned long long total = 0;
     if (T == 0 || B == 0) {
         VTMC_HIP(ctx, hipMemsetAsync(sc.block_offsets.p, 0, sizeof(int32_t) * ((size_t)B + 1), ctx->stream));
     } else {
         const uint32_t tiles = scatter_tiles(T);
         if (int rc = ensure(ctx, sc.masks, scatter_mask_bytes(T))) return rc;
-        const uint32_t groups = (tiles + kScanThreads - 1) / kScanThreads;
-        if (int rc = ensure(ctx, sc.tiles, sizeof(unsigned long long) + 2 * sizeof(uint32_t) * ((size_t)tiles + groups))) return rc;
-        unsigned long long *d_total = (unsigned long long *)sc.tiles.p;   // then the tile totals, their prefixes, the group totals, their prefixes
-        uint32_t *tile_totals = (uint32_t *)(d_total + 1), *tile_offsets = tile_totals + tiles;
-        uint32_t *group_totals = tile_offsets + tiles, *group_offsets = group_totals + groups;
+        if (int rc = ensure(ctx, sc.tiles, ScanLayout(tiles).bytes())) return rc;
+        const ScanLayout scan(tiles, sc.tiles.p);
         ScatterArgs a{};
         a.recs = (const uint32_t *)(res.indexed ? ctx->verts.p : ctx->tris.p);
         a.indices = (const int32_t *)ctx->indices.p;
@@ -289,43 +287,26 @@ int32_t vtmc_scatter_surface(vtmc_ctx *ctx, const vtmc_scatter_params *params, i
         a.scale = ctx->tshape.scale;
         for (int k = 0; k < 3; ++k) a.origin[k] = ctx->tshape.origin[k];
         uint8_t *masks = (uint8_t *)sc.masks.p;
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_scatter[0], ctx->stream));
-        launch_begin();
-        if (res.indexed) hipLaunchKernelGGL(scatter_count_kernel<true>, dim3(tiles), dim3(256), 0, ctx->stream, a, masks, tile_totals);
-        else hipLaunchKernelGGL(scatter_count_kernel<false>, dim3(tiles), dim3(256), 0, ctx->stream, a, masks, tile_totals);
-        VTMC_HIP(ctx, launch_end());
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_scatter[1], ctx->stream));
-        launch_begin();
-        hipLaunchKernelGGL(scan_tiles_kernel, dim3(groups), dim3(kScanThreads), 0, ctx->stream, tile_totals, tiles, tile_offsets, group_totals);
-        VTMC_HIP(ctx, launch_end());
-        launch_begin();
-        hipLaunchKernelGGL(scan_groups_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, group_totals, groups, group_offsets, d_total);
-        VTMC_HIP(ctx, launch_end());
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_scatter[2], ctx->stream));
-        VTMC_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+        VTMC_HIP(ctx, clock.mark(0, ctx->stream));
+        VTMC_HIP(ctx, launch(res.indexed ? scatter_count_kernel<true> : scatter_count_kernel<false>, dim3(tiles), dim3(256), 0, ctx->stream, a, masks, scan.tile_totals()));
+        VTMC_HIP(ctx, clock.mark(1, ctx->stream));
+        VTMC_HIP(ctx, launch_scan(scan, ctx->stream));
+        VTMC_HIP(ctx, clock.mark(2, ctx->stream));
+        VTMC_HIP(ctx, hipMemcpyAsync(&total, scan.total(), sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
         VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (total > (unsigned long long)params->max_instances)
             return fail(ctx, VTMC_ERR_TOO_LARGE, "scatter_surface: %llu instances exceed max_instances %d", total, params->max_instances);
         if (total > 0)
             if (int rc = ensure(ctx, sc.instances, sizeof(vtmc_instance) * (size_t)total)) return rc;
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_scatter[3], ctx->stream));
-        if (total > 0) {
-            launch_begin();
-            if (res.indexed)
-                hipLaunchKernelGGL(scatter_emit_kernel<true>, dim3(tiles), dim3(256), 0, ctx->stream, a, masks, tile_offsets, group_offsets, (uint32_t)total,
-                                   (float4 *)sc.instances.p);
-            else
-                hipLaunchKernelGGL(scatter_emit_kernel<false>, dim3(tiles), dim3(256), 0, ctx->stream, a, masks, tile_offsets, group_offsets, (uint32_t)total,
-                                   (float4 *)sc.instances.p);
-            VTMC_HIP(ctx, launch_end());
-        }
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_scatter[4], ctx->stream));
-        launch_begin();
-        hipLaunchKernelGGL(scatter_block_offsets_kernel, dim3(((unsigned)B + 1 + 255) / 256), dim3(256), 0, ctx->stream, a.toffsets, (uint32_t)B, (uint32_t)T,
-                           (const uint32_t *)sc.masks.p, tile_offsets, group_offsets, d_total, (int32_t *)sc.block_offsets.p);
-        VTMC_HIP(ctx, launch_end());
-        VTMC_HIP(ctx, hipEventRecord(ctx->ev_scatter[5], ctx->stream));
-        sc.timed = true;
+        VTMC_HIP(ctx, clock.mark(3, ctx->stream));
+        if (total > 0)
+            VTMC_HIP(ctx, launch(res.indexed ? scatter_emit_kernel<true> : scatter_emit_kernel<false>, dim3(tiles), dim3(256), 0, ctx->stream, a, masks, scan.tile_offsets(),
+                                 scan.group_offsets(), (uint32_t)total, (float4 *)sc.instances.p));
+        VTMC_HIP(ctx, clock.mark(4, ctx->stream));
+        VTMC_HIP(ctx, launch(scatter_block_offsets_kernel, lanes256((int64_t)B + 1), dim3(256), 0, ctx->stream, a.toffsets, (uint32_t)B, (uint32_t)T,
+                             (const uint32_t *)sc.masks.p, scan.tile_offsets(), scan.group_offsets(), scan.total(), (int32_t *)sc.block_offsets.p));
+        VTMC_HIP(ctx, clock.mark(5, ctx->stream));
+        clock.arm();
     }
     VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     sc.n = (int64_t)total;
@@ -364,11 +345,11 @@ int32_t vtmc_scatter_device_results(vtmc_ctx *ctx, const vtmc_instance **d_insta
 int32_t vtmc_debug_scatter_ms(vtmc_ctx *ctx, float ms[4])
 {
     if (!ctx || !ms) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->scatter.timed) return fail(ctx, VTMC_ERR_NO_RESULT, "debug_scatter_ms before a scatter that launched kernels");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    VTMC_HIP(ctx, hipEventSynchronize(ctx->ev_scatter[5]));
+    if (!ctx->scatter_clock.armed) return fail(ctx, VTMC_ERR_NO_RESULT, "debug_scatter_ms before a scatter that launched kernels");
+    if (int rc = ctx->scatter_clock.sync_last(ctx)) return rc;
     static const int pairs[4][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
-    for (int i = 0; i < 4; ++i) VTMC_HIP(ctx, hipEventElapsedTime(&ms[i], ctx->ev_scatter[pairs[i][0]], ctx->ev_scatter[pairs[i][1]]));
+    for (int i = 0; i < 4; ++i)
+        if (int rc = ctx->scatter_clock.elapsed(ctx, pairs[i][0], pairs[i][1], &ms[i])) return rc;
     return VTMC_OK;
 }
 

@@ -1,5 +1,6 @@
 // vtmc_ctx.h -- the context object behind include/vtmc.h and the small host helpers every translation unit of the C-ABI layer shares
-// (every .hip file but the two of extract kernels).  Not installed.
+// (every .hip file but the two of extract kernels): the owned buffers, the stage clocks that time a pass's kernels (StageClock), fail /
+// VTMC_HIP, and the one kernel launch of the layer (launch, with the lanes256 grid).  Not installed.
 #ifndef VTMC_CTX_H
 #define VTMC_CTX_H
 #include "../../include/vtmc.h"
@@ -39,6 +40,35 @@ struct OwnedBuf {
         p = nullptr;
         bytes = 0;
     }
+};
+// The N timing events around the kernels of one pass, and whether they hold a whole run of it.  A pass calls begin() (the first one creates
+// the events; every one disarms the clock), mark(i, stream) between its kernels, and arm() once the last mark is queued; a reader refuses
+// while !armed, then sync_last() and elapsed().  Neither copied nor moved: the events are destroyed with the context that holds the clock.
+template <int N>
+struct StageClock {
+    hipEvent_t ev[N] = {};
+    bool armed = false;
+    StageClock() = default;
+    StageClock(const StageClock &) = delete;
+    StageClock &operator=(const StageClock &) = delete;
+    ~StageClock()
+    {
+        for (hipEvent_t e : ev)
+            if (e) quiet(hipEventDestroy(e));
+    }
+    hipError_t begin()
+    {
+        armed = false;
+        for (hipEvent_t &e : ev)
+            if (!e)
+                if (hipError_t rc = hipEventCreate(&e)) return rc;
+        return hipSuccess;
+    }
+    hipError_t mark(int i, hipStream_t stream) { return hipEventRecord(ev[i], stream); }
+    void arm() { armed = true; }
+    hipEvent_t event(int i) const { return ev[i]; }
+    int sync_last(vtmc_ctx *ctx) const;                           // on the context's device: waits for event N - 1
+    int elapsed(vtmc_ctx *ctx, int i, int j, float *ms) const;    // milliseconds from event i to event j
 };
 }  // namespace vtmc
 typedef vtmc::OwnedBuf<void, hipFree> VtmcDevBuf;
@@ -100,7 +130,6 @@ struct VtmcScatter {
     int64_t n = 0;
     int blocks = 0;        // block_offsets holds blocks + 1 entries
     uint64_t epoch = 0;
-    bool timed = false;    // the events around the last call's kernels were recorded (vtmc_debug_scatter_ms)
 };
 
 // The navigation build the context holds (terrain_nav.hip): library-owned, grow-only; a snapshot of the grid at build time, dropped by
@@ -112,7 +141,6 @@ struct VtmcNav {
     bool valid = false;
     int32_t n = 0;
     int32_t lo[3] = {0, 0, 0}, d[3] = {0, 0, 0};   // the box as reported: first sample, samples per axis
-    bool timed = false;                            // the events around the last build's kernels were recorded (vtmc_debug_nav_ms)
     int rounds = 0;                                // union / flatten / verify rounds of the last build
 };
 
@@ -123,7 +151,6 @@ struct VtmcNavField {
     VtmcDevBuf cells, work, ctl;
     bool valid = false;
     int32_t n = 0, reached = 0, rounds = 0;
-    bool timed = false;   // the events around the last build's kernels were recorded (vtmc_debug_navfield_ms)
 };
 
 // An extract that has been queued on a stream and not yet completed by extract_finish().
@@ -170,8 +197,7 @@ struct vtmc_ctx {
     bool place_pending = false;     // the output buffers were (re)allocated since the last placement trial (tuning key place_outputs)
     float place_ms[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // emit stage per candidate of the last trial ([0]: the buffer that was there), place_n of them
     int place_n = 0, place_kept = 0;
-    hipEvent_t ev_fill[2] = {nullptr, nullptr};  // around the last density kernel (vtmc_last_fill_ms)
-    bool fill_timed = false;
+    vtmc::StageClock<2> fill_clock;   // around the last density kernel (vtmc_last_fill_ms)
     VtmcPending pending;
     VtmcResult result;
     vtmc::Tuning tune;
@@ -211,22 +237,21 @@ struct vtmc_ctx {
     VertexAttr ao;
     VtmcDevBuf ao_stats;
     int32_t ao_direct_max = -1;         // vertices up to which a block takes the direct route; -1: the library's default
-    // terrain_scatter.hip: the instances of the last vtmc_scatter_surface and the events around its kernels
+    // terrain_scatter.hip: the instances of the last vtmc_scatter_surface and the clock of its kernels (armed by a call that launched them)
     VtmcScatter scatter;
-    hipEvent_t ev_scatter[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // terrain_nav.hip: the last navigation build and the events around its kernels (created by the first build)
+    vtmc::StageClock<6> scatter_clock;
+    // terrain_nav.hip: the last navigation build and the clock of its kernels (armed by a build that made spans)
     VtmcNav nav;
-    hipEvent_t ev_nav[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // terrain_navfield.hip: the flow field on that build and the events around its kernels (edge costs and goals, relaxation, next)
+    vtmc::StageClock<9> nav_clock;
+    // terrain_navfield.hip: the flow field on that build and the clock of its kernels (edge costs and goals, relaxation, next)
     VtmcNavField navfield;
-    hipEvent_t ev_navfield[4] = {nullptr, nullptr, nullptr, nullptr};
+    vtmc::StageClock<4> navfield_clock;
     // terrain_lod.hip: the node list of the last level-of-detail result (host, and the copy the gather kernel reads), the packed
-    // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the events around
-    // the last gather launch (vtmc_debug_lod_gather_ms)
+    // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the clock around
+    // the gather launch of the last extract that succeeded (vtmc_debug_lod_gather_ms)
     std::vector<vtmc_lod_node> lod_nodes;
     VtmcDevBuf lod_nodes_dev, lod_tiles;
-    hipEvent_t ev_lod[2] = {nullptr, nullptr};
-    bool lod_timed = false;
+    vtmc::StageClock<2> lod_clock;
     // raycast.hip, spherequery.hip: the queries and hits of vtmc_terrain_raycast / _spherecast / _closest_point (device, then their pinned staging)
     VtmcDevBuf rays;
     VtmcPinnedBuf<unsigned char> h_rays;
@@ -289,6 +314,18 @@ int attr_device_results(vtmc_ctx *ctx, const VertexAttr &a, const char *stale, c
 // terrain.hip, for terrain_io.hip
 void history_clear(vtmc_ctx *ctx);
 int terrain_extract_all(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_count);   // extracts every block of the resident terrain, as an update that dirtied all of them
+
+// The one kernel launch of this layer: clears the runtime's sticky error word, launches, and returns what this launch left (the rule of
+// launch_begin / launch_end in vtmc_internal.h, whose own wrappers in the two files of extract kernels keep the hand-written form).
+template <class... Params, class... Args>
+hipError_t launch(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, Args... args)
+{
+    launch_begin();
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+    return launch_end();
+}
+// the grid of a kernel with one lane per element and 256 lanes per workgroup
+inline dim3 lanes256(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 }  // namespace vtmc
 
 #define VTMC_HIP(ctx, expr)                                                                                \
@@ -298,5 +335,19 @@ int terrain_extract_all(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_cou
             return vtmc::fail(ctx, VTMC_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
                               __FILE__, __LINE__);                                                         \
     } while (0)
+
+template <int N>
+int vtmc::StageClock<N>::sync_last(vtmc_ctx *ctx) const
+{
+    VTMC_HIP(ctx, hipSetDevice(ctx->device));
+    VTMC_HIP(ctx, hipEventSynchronize(ev[N - 1]));
+    return VTMC_OK;
+}
+template <int N>
+int vtmc::StageClock<N>::elapsed(vtmc_ctx *ctx, int i, int j, float *ms) const
+{
+    VTMC_HIP(ctx, hipEventElapsedTime(ms, ev[i], ev[j]));
+    return VTMC_OK;
+}
 
 #endif
