@@ -15,6 +15,15 @@ and, in the second generation (generation=2: worlds b and c, SEEDS2, N_OPS2),
   ("lod", viewer in cells, max_level, split)         vtmc_terrain_extract_lod (world c)
   ("probe", seed)                                    a fixed small batch of rays, sphere casts and closest points (probe_queries)
   ("chunk_write",)                                   the chunk file of the result over every block, directly after a save_load
+and, in the third generation (generation=3: worlds b and c, SEEDS3, N_OPS3),
+  ("fragments", (lower, upper), max_samples, capture_min_samples)     vtmc_terrain_fragments; with capture its stamps take the next ids
+  ("scatter", keyword arguments of vt.ScatterParams)                  vtmc_scatter_surface on the result the context holds
+  ("nav", (lower, upper), agent_height, max_step)                     vtmc_terrain_nav_build (samples, grid units)
+  ("field", ((fraction, cost), ...), climb, drop, max_cost)           vtmc_navfield_build; goals at fractions of the largest region's spans
+  ("walk", seed, max_len)                                             N_AGENTS positions (walk_agents) located and traced
+with ("detach", dict(max_samples=...), (lower, upper)) among the specs of a queue.  How many ids a capturing query takes only the session
+knows, so what refers to a captured stamp is written symbolically -- the spec ("fragment_paste", dict(query=q, rank=k)) and the operation
+("stamp_destroy", ("fragment", q, k)) -- and made concrete by Session.concrete(op) when its turn comes.
 A spec is terrain_twin's (kind, args) or (kind, args, (lower, upper)): the third entry is the AABB the struct gets after to_struct();
 path_twin's ("path", ...) and stamp_twin's ("stamp", ...) among them.
 Stamp ids count up from 1 in the model as in a fresh context, so the generator can name them before any exists.
@@ -22,19 +31,29 @@ Stamp ids count up from 1 in the model as in a fresh context, so the generator c
 Beside the grid the model holds: which stamps came from a mesh (their pastes are the categories "mesh:<mode>"); the material layer, a
 material_twin array or None -- undo and redo leave it alone, a load drops it, material_init brings it back, and paint or control_map
 without one answer VTMC_ERR_NO_RESULT; and which result the context holds (a terrain result with its dirty list, a level-of-detail
-result, or none) and by which operation, since attributes accepts a terrain result only and every new result makes the attributes stale."""
+result, or none) and by which operation, since attributes accepts a terrain result only and every new result makes the attributes stale.
+For the third generation it also holds the rules of the three layers that live beside the result, each quoted from its header at the
+method that keeps it: the scatter instances (every producer of a result drops them; paint, the attribute passes and a nav build do
+not), the nav result (a snapshot of the grid at its build: kept by everything but a load) and the flow field on it (dropped by a nav
+build and by a load, not by an edit).  A detach modifier takes its event number in queue order, is journaled by its box and dirties its
+box's blocks, also when it removes nothing; a fragment query changes nothing but the stamps it captures."""
 import os
 
 import numpy as np
 
+import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib, terrainfile as tf
 import ao_twin
+import fragment_twin
 import lod_twin
 import material_twin
 import mesh_twin
+import nav_twin
+import navfield_twin
 import path_twin
+import scatter_twin
 import stamp_twin
-from terrain_twin import block_list, box_of, image_bytes
+from terrain_twin import bits, block_list, box_of, dirty_ids, image_bytes, with_box
 
 f32 = np.float32
 
@@ -60,6 +79,16 @@ FAMILIES2 = FAMILIES + ("path",)
 REJECTS2 = REJECTS + ("path",)                     # ... and a path of 0 segments
 LOD_MAX_LEVEL = 2
 CORNER_VIEWER = (-1.0, 3.0, 5.0)                   # in cells; with split 1 on world c: 37 nodes of levels 0, 1 and 2
+# the third generation (generate(..., generation=3)): the second one's deck with the detach modifier in the queues and, between them, the
+# fragment query, the surface scatter, the navigation build, the flow field and a batch of located and traced agents.
+SEEDS3 = {"b": (0, 1), "c": (2, 3)}             # chosen so that the third generation's conditions hold
+N_OPS3 = 212
+KINDS3 = KINDS2 + ("detach",)
+FAMILIES3 = FAMILIES2 + ("detach",)
+N_AGENTS = 64                                      # of a walk operation
+FIELD_CUT = 12 * _lib.NAVFIELD_UNIT                # a max_cost that cuts: twelve level steps
+NO_CUT = 0x7fffffff
+SCATTER_KEYS = ("density", "min_up", "max_up", "min_y", "max_y", "material_channel", "seed")   # of scatter_twin.scatter, among a scatter operation's
 
 
 # -- the history ------------------------------------------------------------------------------------------------------------------------
@@ -143,11 +172,14 @@ def category(spec, mesh_ids=()):
 
 
 def family(spec):
-    return spec[0] if spec[0] in ("flatten", "smooth", "noise", "stamp", "path") else "modify"
+    return spec[0] if spec[0] in ("flatten", "smooth", "noise", "stamp", "path", "detach") else "modify"
 
 
 def gpu_struct(spec):
-    """The vtmc_modifier of any spec of a session: path_twin's for a path, stamp_twin's (and through it terrain_twin's) for the rest."""
+    """The vtmc_modifier of any spec of a session: path_twin's for a path, stamp_twin's (and through it terrain_twin's) for the rest;
+    ("detach", dict(max_samples=...), box) is vt.DetachModifier(lower, upper, max_samples)."""
+    if spec[0] == "detach":
+        return with_box(vt.DetachModifier(spec[2][0], spec[2][1], spec[1]["max_samples"]).to_struct(), spec)
     return path_twin.gpu_struct(spec) if spec[0] == "path" else stamp_twin.gpu_struct(spec)
 
 
@@ -206,21 +238,38 @@ class Session:
         # the vertex weights and occlusion bytes were computed for it
         self.result, self.result_source, self.result_dirty, self.attributes_current = None, None, None, False
         # what the generator conditions read
-        self.kinds = dict.fromkeys(KINDS2, 0)
+        # the layers of the third generation.  scatter: the parameters of the instances held, or None; scatter_result: scatter_twin's
+        # (instances, block offsets, info) of them.  nav: nav_twin.build's whole result, a snapshot of the grid at the build, with
+        # nav_key = (box, agent_height, max_step); field: navfield_twin's cells on it, with the goals they were built from
+        self.scatter = self.scatter_result = None
+        self.nav = self.nav_key = self.field = self.field_goals = None
+        self.captured = []           # per capturing fragment query, the fragments it captured, largest first: dict(sid, first, dims, rec, n, mask, grid)
+        self.captured_ids = {}       # stamp id -> that dict
+        self.detaches, self.pastes = [], []      # a note per detach modifier that ran, and per paste of a captured stamp
+        self.pending = dict(detach=False, query=False)   # a detach, a fragment query, has run in an earlier operation ...
+        self.draws_after = dict(detach=0, query=0)       # ... and how many later queues drew from the event counter after one
+        self.kinds = dict.fromkeys(KINDS3, 0)
         self.taken = {True: {"low": 0, "high": 0}, False: {"low": 0, "high": 0}}   # csg_write's clamp branches, by add_or_erode
         self.path_taken = {True: {"low": 0, "high": 0}, False: {"low": 0, "high": 0}}   # the same of the paths alone
         self.footprints = []
         self.mesh_footprints = {"add": [], "erode": [], "replace": []}
-        self.faces = {f: set() for f in FAMILIES2}
+        self.faces = {f: set() for f in FAMILIES3}
         self.loads, self.loads_edited = 0, 0
         self.paths = dict(undone=0, redone=0, evicted=0, after_undo=0, after_load=0)
+        self._queue_detaches = []
+        self.seen = dict(fragments=0, removed=0, instances=0, spans=0, reached=0, located=0)   # what the new operations met, summed
         self.last = None             # the name of the last operation that ran, with "!" behind an undo or redo that was refused
 
     # -- updates --------------------------------------------------------------------------------------------------------------------
     def _apply(self, specs):
         ids = set()
-        for spec in specs:
+        queue_start = np.array(self.ref.grid)
+        for j, spec in enumerate(specs):
             taken, counts = {"low": 0, "high": 0}, []
+            if spec[0] == "detach":
+                ids |= self._detach(spec, queue_start, specs[:j])
+                continue
+            before = np.array(self.ref.grid) if spec[0] == "stamp" and spec[1]["stamp_id"] in self.captured_ids else None
             if spec[0] == "path":
                 hit = path_twin.twin_update(self.ref, self.oracle, [spec], taken)
             else:
@@ -234,13 +283,53 @@ class Session:
                 into = self.taken if spec[0] == "noise" else self.path_taken
                 for k in taken:
                     into[bool(spec[1].get("add_or_erode", True) if spec[0] == "noise" else spec[1]["addOrErode"])][k] += taken[k]
+                if taken["low"] + taken["high"] > 0:          # a clamped sample is a draw keyed on the event number
+                    for what in self.pending:
+                        self.draws_after[what] += self.pending[what]
+            if before is not None:                            # a paste of a captured fragment
+                c = self.captured_ids[spec[1]["stamp_id"]]
+                now, m = self.ref.grid, c["mask"]
+                self.pastes.append(dict(c=c, mode=spec[1]["mode"], unturned=tuple(spec[1]["rotation"]) == (0.0, 0.0, 0.0, 1.0),
+                                        gone_before=bool((~(before[m] > 0)).all()), solid_again=bool((now[m] > 0).all()),
+                                        bits_again=bool(np.array_equal(bits(now[m]), bits(c["grid"][m])))))
         return block_list(ids, self.nb)
+
+    def _detach(self, spec, queue_start, earlier):
+        """include/vtmc.h at VTMC_MOD_DETACH: the modifier takes one event number in queue order, sees what the earlier modifiers of its
+        queue wrote, writes every sample of every fragment of its box as the void draw of that event, and marks the dirty blocks of its
+        box also when nothing was removed.  Returns those block ids; leaves a note for the generator conditions."""
+        w = self.world
+        m = gpu_struct(spec)
+        first, ext, low, up = fragment_twin.sample_box(tuple(m.lower), tuple(m.upper), w["dims"], w["scale"], w["origin"])
+        most = spec[1]["max_samples"]
+        event = self.ref.events + 1
+        grid = np.array(self.ref.grid)
+        new, recs = fragment_twin.detach(grid, first, ext, most, self.ref.seed, event)
+        self.ref.grid[...] = new
+        self.ref.events = event
+        ids = dirty_ids(low, up, self.nb)
+        note = dict(first=first, ext=ext, max_samples=most, recs=recs, n_dirty=len(ids), faces=faces_of(first, ext, self.ref.dims),
+                    protected=0, cut_loose=0, undone=0, redone=0, lost=0)
+        if most > 0:        # what the limit protected: the fragments max_samples = 0 lists and this one does not
+            note["protected"] = len(fragment_twin.fragments(grid, first, ext, 0)[0]) - len(recs)
+        erodes = [sp for sp in earlier if (sp[0] in ("plane", "sphere", "cylinder", "island") and not sp[1][-1]) or (sp[0] == "path" and not sp[1]["addOrErode"])]
+        if erodes and len(recs):    # fragments of 8 samples or more that were no fragments of this box before the queue began
+            was = {tuple(r["seed"]) for r in fragment_twin.fragments(queue_start, first, ext, most)[0]}
+            note["cut_loose"] = sum(int(r["n_samples"]) >= 8 and tuple(r["seed"]) not in was for r in recs)
+        if len(recs):
+            for what in self.pending:
+                self.draws_after[what] += self.pending[what]
+        self.detaches.append(note)
+        self.seen["removed"] += len(recs)
+        self._queue_detaches.append(note)
+        return ids
 
     def boxes(self, specs):
         return [box_of(self.ref, gpu_struct(s))[:2] for s in specs]
 
     def _produced(self, kind, source, dirty=None):
         self.result, self.result_source, self.result_dirty, self.attributes_current = kind, source, dirty, False
+        self.scatter = self.scatter_result = None     # include/vtmc.h: the instances belong to one result, stale after any later extract
 
     def update(self, specs):
         """One vtmc_terrain_update of the whole queue.  Returns its dirty list."""
@@ -251,12 +340,21 @@ class Session:
         nbytes = sum(image_bytes(ext) for _, ext in boxes)
         has_path = any(sp[0] == "path" and min(ext) > 0 for sp, (_, ext) in zip(specs, boxes))
         had_redo = self.hist.done < len(self.hist.steps)
+        redo_stack = self.hist.steps[self.hist.done:]
         before = self.ref._mem.copy()
+        self._queue_detaches = []
         dirty = self._apply(specs)
-        step = self.hist.record(nbytes, dict(before=before, after=self.ref._mem.copy(), dirty=dirty, boxes=boxes, has_path=has_path))
+        step = self.hist.record(nbytes, dict(before=before, after=self.ref._mem.copy(), dirty=dirty, boxes=boxes, has_path=has_path,
+                                             detaches=self._queue_detaches))
         if step is not None:
             self.paths["evicted"] += sum(bool(e.payload["has_path"]) for e in self.hist.evicted)
             self.paths["after_undo"] += bool(has_path and had_redo)
+            for gone in self.hist.evicted + redo_stack:       # the steps this one cost: evicted by the ring, or discarded with the redo stack
+                for note in gone.payload.get("detaches", ()):
+                    note["lost"] += 1
+        for note in self._queue_detaches:
+            note["recorded"] = step is not None
+        self.pending["detach"] = self.pending["detach"] or bool(self._queue_detaches)
         if self.loads and nbytes:
             self.loads_edited = max(self.loads_edited, self.loads)
             self.paths["after_load"] += has_path
@@ -277,6 +375,8 @@ class Session:
         for first, ext in step.payload["boxes"]:
             self.faces["swap"] |= faces_of(first, ext, self.ref.dims)
         self.paths["undone" if which == "before" else "redone"] += bool(step.payload.get("has_path"))
+        for note in step.payload.get("detaches", ()):
+            note["undone" if which == "before" else "redone"] += 1
         self._produced("terrain", "undo" if which == "before" else "redo", step.payload["dirty"])
         return step.payload["dirty"]
 
@@ -330,6 +430,7 @@ class Session:
         self.hist.clear()
         self.loads += 1
         self.layer = None
+        self.nav = self.nav_key = self.field = self.field_goals = None    # include/vtmc_nav.h, vtmc_navfield.h: valid until vtmc_terrain_load
         dirty = block_list(range(self.nb[0] * self.nb[1] * self.nb[2]), self.nb)
         self._produced("terrain", "save_load", dirty)
         return dirty
@@ -383,11 +484,130 @@ class Session:
         self._produced("lod", "lod")
         return nodes, lod_twin.node_tiles(self.ref.grid, nodes)
 
+    # -- the third generation: fragments, scatter, navigation, flow fields --------------------------------------------------------------
+    def sample_box(self, box):
+        """(first, ext) of world bounds: the clamped sample box every modifier, the fragment query and the nav build find (include/vtmc.h, FRAGMENTS)."""
+        w = self.world
+        return fragment_twin.sample_box(box[0], box[1], w["dims"], w["scale"], w["origin"])[:2]
+
+    def fragments(self, box, max_samples, capture_min_samples):
+        """vtmc_terrain_fragments (include/vtmc.h): (records with stamp_id 0, the stamp id of every record or 0).  With capture every listed
+        fragment of at least capture_min_samples samples takes the next id of the one counter all stamps share, in the order of the
+        records, and its stamp is fragment_twin.stamp's.  "It changes nothing": not the grid, the history, the event counter, the dirty
+        list or the result -- so nothing else of the model moves."""
+        first, ext = self.sample_box(box)
+        grid = np.array(self.ref.grid)
+        recs, lab = fragment_twin.fragments(grid, first, ext, max_samples)
+        ids = np.zeros(len(recs), np.int32)
+        if capture_min_samples > 0:
+            made = []
+            for k, rec in enumerate(recs):
+                if rec["n_samples"] >= capture_min_samples:
+                    a, n, samples = fragment_twin.stamp(grid, lab, rec, first, ext)
+                    ids[k] = self._new_stamp(np.ascontiguousarray(samples))
+                    mask = np.zeros(grid.shape, bool)
+                    mask[first[0]:first[0] + ext[0], first[1]:first[1] + ext[1], first[2]:first[2] + ext[2]] = fragment_twin.fragment_mask(lab, recs[k:k + 1], first, ext)
+                    made.append(dict(sid=int(ids[k]), first=a, dims=n, rec=rec.copy(), n=int(rec["n_samples"]), mask=mask, grid=grid))
+                    self.captured_ids[int(ids[k])] = made[-1]
+            self.captured.append(sorted(made, key=lambda c: -c["n"]))
+        self.pending["query"] = True
+        self.seen["fragments"] += len(recs)
+        return recs, ids
+
+    def concrete(self, op):
+        """An operation with what only the session knows filled in: a spec ("fragment_paste", dict(query=q, rank=k)) becomes the paste of
+        the k-th largest fragment the q-th capturing query captured -- unturned, in replace mode, at its own box -- and
+        ("stamp_destroy", ("fragment", q, k)) names that stamp's id.  Every other operation is returned as it is."""
+        if op[0] == "update" and any(sp[0] == "fragment_paste" for sp in op[1]):
+            return ("update", [self._paste_spec(sp) if sp[0] == "fragment_paste" else sp for sp in op[1]])
+        if op[0] == "stamp_destroy" and isinstance(op[1], tuple):
+            return ("stamp_destroy", self._captured(op[1][1], op[1][2])["sid"])
+        return op
+
+    def _captured(self, query, rank):
+        assert query < len(self.captured) and rank < len(self.captured[query]), "capturing query %d captured no fragment %d" % (query, rank)
+        return self.captured[query][rank]
+
+    def _paste_spec(self, sp):
+        c, w = self._captured(sp[1]["query"], sp[1]["rank"]), self.world
+        centre = tuple(float(f32(f32(c["first"][k] + 0.5 * (c["dims"][k] - 1)) * f32(w["scale"]) + f32(w["origin"][k]))) for k in range(3))
+        return ("stamp", dict(stamp_id=c["sid"], dims=c["dims"], position=centre, rotation=(0.0, 0.0, 0.0, 1.0), pitch=w["scale"], mode="replace"))
+
+    def records(self):
+        """(76-byte records, per-block triangle offsets, blocks) of the result the model holds, from the oracle's extract of the model's
+        grid: what scatter_surface works on where it is not handed the device's own records."""
+        dirty = self.result_dirty
+        if not len(dirty):
+            return np.zeros(0, _lib.TRI_DTYPE), np.zeros(1, np.int64), dirty
+        tris, offs, _ = self.oracle.extract_grid(np.ascontiguousarray(self.ref.grid), dirty, threads=8)
+        return tris, offs, dirty
+
+    def scatter_surface(self, params, mesh=None):
+        """vtmc_scatter_surface (include/vtmc.h) for a dict of vt.ScatterParams' keyword arguments.  Returns None where the device answers
+        VTMC_ERR_NO_RESULT (no result, a level-of-detail result, or a material channel without a layer: the instances held stay as
+        they are), "too large" for VTMC_ERR_TOO_LARGE (the context then holds no scatter), else scatter_twin's (instances, block offsets,
+        info).  mesh: (records, triangle offsets, blocks) as the device returned them; the model's own where None."""
+        channel = params.get("material_channel", -1)
+        if self.result != "terrain" or (channel >= 0 and self.layer is None):
+            return None
+        tris, offs, blocks = self.records() if mesh is None else mesh
+        w = self.world
+        want = scatter_twin.scatter(tris, offs, blocks, w["scale"], w["origin"], layer=self.layer, dims=w["dims"],
+                                    **{k: params[k] for k in SCATTER_KEYS if k in params})
+        if len(want[0]) > params.get("max_instances", 1 << 24):
+            self.scatter = self.scatter_result = None
+            return "too large"
+        self.scatter, self.scatter_result = dict(params), want
+        self.seen["instances"] += len(want[0])
+        return want
+
+    def nav_build(self, box, agent_height, max_step):
+        """vtmc_terrain_nav_build (include/vtmc_nav.h): nav_twin.build on the model's grid as it is now, kept whole -- "a snapshot of the
+        grid at build time: later edits do not invalidate it".  include/vtmc_navfield.h: the build drops the field."""
+        first, ext = self.sample_box(box)
+        self.nav, self.nav_key = nav_twin.build(np.array(self.ref.grid), first, ext, agent_height, max_step), (box, agent_height, max_step)
+        self.field = self.field_goals = None
+        self.seen["spans"] += len(self.nav[0])
+        return self.nav
+
+    def goals_of(self, picks):
+        """(span, cost) pairs of goal picks ((fraction, cost), ...): the span at that fraction of the index list of the largest region."""
+        spans = self.nav[0]
+        regions, counts = np.unique(spans["region"], return_counts=True)
+        inside = np.nonzero(spans["region"] == regions[np.argmax(counts)])[0]
+        return [(int(inside[min(int(frac * len(inside)), len(inside) - 1)]), int(cost)) for frac, cost in picks]
+
+    def field_build(self, picks, climb, drop, max_cost):
+        """vtmc_navfield_build (include/vtmc_navfield.h) on the nav snapshot held; None where the device answers VTMC_ERR_NO_RESULT."""
+        if self.nav is None:
+            return None
+        self.field_goals = self.goals_of(picks)
+        self.field = navfield_twin.field(self.nav[0], self.field_goals, climb, drop, max_cost)
+        self.seen["reached"] += int((self.field["cost"] != _lib.NAVFIELD_UNREACHED).sum())
+        return self.field
+
+    def walk(self, seed, max_len):
+        """N_AGENTS agents located (vtmc_nav_locate) and traced (vtmc_navfield_trace) on the snapshots held, whatever the grid has become.
+        Returns (world positions, below, above in world units, located spans or None, (paths, lengths) or None): None where the device
+        answers VTMC_ERR_NO_RESULT -- the locate without a nav result, the trace without a field."""
+        w = self.world
+        pos = walk_agents(self.nav, w, seed)
+        scale = f32(w["scale"])
+        below, above = float(f32(1.0) * scale), float(f32(1.25) * scale)
+        if self.nav is None:
+            return pos, below, above, None, None
+        located = navfield_twin.locate(self.nav, w["origin"], w["scale"], pos, f32(below) / scale, f32(above) / scale)
+        traced = None if self.field is None else navfield_twin.trace(self.field, located, max_len)
+        self.seen["located"] += int((located >= 0).sum())
+        return pos, below, above, located, traced
+
     # -- driving ----------------------------------------------------------------------------------------------------------------------
     def run(self, op, tmp_dir):
         """One operation of generate() on the model alone; returns what the method returns."""
         name = op[0]
-        if name == "update":
+        if name in ("fragments", "scatter", "nav", "field", "walk"):
+            out = getattr(self, {"scatter": "scatter_surface", "nav": "nav_build", "field": "field_build"}.get(name, name))(*op[1:])
+        elif name == "update":
             out = self.update(op[1])
         elif name == "reject":
             out = self.reject(op[1])
@@ -435,6 +655,25 @@ def probe_queries(w, seed, n_rays=32, n_spheres=16):
     return dict(ray_o=ray_o, ray_d=ray_d, cast_o=cast_o, cast_d=cast_d, cast_r=cast_r, ball_c=ball_c, ball_r=ball_r)
 
 
+def walk_agents(nav, w, seed):
+    """The world positions (N_AGENTS, 3) float32 of a walk operation: near spans of the nav result picked at random, up to 0.45 of a
+    column off the column's centre and up to 1.5 above or below the floor; the first eight a few columns outside the nav box along x,
+    the next eight above every floor.  Without a nav result (or without a span): anywhere in the grid."""
+    rng = np.random.default_rng([seed, 99])
+    dims, s, o = np.array(w["dims"], float), w["scale"], np.array(w["origin"], float)
+    if nav is None or not len(nav[0]):
+        g = rng.uniform(0.0, 1.0, (N_AGENTS, 3)) * (dims + 1)
+    else:
+        spans, offsets, first, ext = nav
+        pick = rng.integers(0, len(spans), N_AGENTS)
+        col = np.searchsorted(offsets, pick, side="right") - 1
+        g = np.stack([first[0] + col % ext[0] + rng.uniform(-0.45, 0.45, N_AGENTS), spans["height"][pick] + rng.uniform(-1.5, 1.5, N_AGENTS),
+                      first[2] + col // ext[0] + rng.uniform(-0.45, 0.45, N_AGENTS)], axis=1).astype(np.float64)
+        g[0:8, 0] = first[0] - rng.uniform(1.0, 4.0, 8)
+        g[8:16, 1] = dims[1] + 5.0
+    return (o + g * s).astype(f32)
+
+
 # -- the generator ----------------------------------------------------------------------------------------------------------------------
 class _Draw:
     """The generator's state: the random stream, the world's geometry and the stamps that exist at the point the list has reached."""
@@ -446,6 +685,10 @@ class _Draw:
         self.top = [d + 1 for d in self.dims]
         self.live, self.next_stamp, self.islands = {}, 1, 0   # live: id -> dims
         self.mesh = set()                                     # the ids among them that came from a mesh
+        # False once a capturing fragment query has run: how many ids it took is the session's to know, so the stamps made after it are
+        # no longer named by the generator (their ids still come from the one counter, which the model checks)
+        self.ids_known = True
+        self.queries = 0                                      # the capturing fragment queries so far
 
     def pos(self, i, k):
         return float(f32(i) * f32(self.scale) + f32(self.origin[k]))
@@ -524,6 +767,9 @@ class _Draw:
         elif kind == "path":
             spec = ("path", dict(segments=self.path_segments(mode, spans), addOrErode=cat.endswith("add")))
             own_box = own_box and mode in ("free", "single", "zero")   # on the faces the exact AABB: the path family must touch all six
+        elif kind == "detach":
+            spec = ("detach", dict(max_samples=int((0, 0, 6, 40)[int(r.integers(0, 4))])))
+            own_box = False   # a detach has no bounds of its own: always the exact AABB
         else:   # a paste of a stamp, or ("mesh") of one that came from a mesh
             pool = sorted(i for i in self.live if (i in self.mesh) == (kind == "mesh"))
             sid = pool[int(r.integers(0, len(pool)))]
@@ -605,15 +851,17 @@ class _Draw:
             mesh = ("torus", h * 0.28 * m, h * min(0.14 * m, 0.5 * dims[1] - 1.0), 8, 6, c)
         else:
             mesh = ("box", tuple(c[k] - h * (0.5 * dims[k] - 1.6) for k in range(3)), tuple(c[k] + h * (0.5 * dims[k] - 1.6) for k in range(3)))
-        self.live[self.next_stamp] = dims
-        self.mesh.add(self.next_stamp)
-        self.next_stamp += 1
+        if self.ids_known:
+            self.live[self.next_stamp] = dims
+            self.mesh.add(self.next_stamp)
+            self.next_stamp += 1
         return ("stamp_from_mesh", mesh, first, h, dims)
 
     def create(self):
         dims = tuple(int(v) for v in self.rng.integers(6, 13, 3))
-        self.live[self.next_stamp] = dims
-        self.next_stamp += 1
+        if self.ids_known:
+            self.live[self.next_stamp] = dims
+            self.next_stamp += 1
         return ("stamp_create", int(self.rng.integers(0, 1 << 30)), dims, float(self.rng.uniform(1.2, 2.6)))
 
     def capture(self, corner):
@@ -624,14 +872,75 @@ class _Draw:
             first = tuple(self.top[k] + 1 - dims[k] for k in range(3))
         else:
             first = tuple(int(self.rng.integers(1, self.top[k] - dims[k])) for k in range(3))
-        self.live[self.next_stamp] = dims
-        self.next_stamp += 1
+        if self.ids_known:
+            self.live[self.next_stamp] = dims
+            self.next_stamp += 1
         return ("stamp_capture", first, dims)
 
     def destroy(self):
         sid = sorted(self.live)[0]
         del self.live[sid]
         return ("stamp_destroy", sid)
+
+    # -- the third generation ------------------------------------------------------------------------------------------------------------
+    def at(self, x, y, z):
+        return (self.pos(x, 0), self.pos(y, 1), self.pos(z, 2))
+
+    def aabb(self, spans):
+        """The world bounds that give exactly the samples spans = ((lo, hi), ...), inclusive: a quarter of a sample inside their ends."""
+        q = 0.25 * self.scale
+        return (tuple(self.pos(lo, k) + q for k, (lo, _) in enumerate(spans)), tuple(self.pos(hi, k) - q for k, (_, hi) in enumerate(spans)))
+
+    def site(self):
+        """A column for a set piece: seven samples or more from the x and z faces."""
+        return int(self.rng.integers(7, self.top[0] - 6)), int(self.rng.integers(7, self.top[2] - 6))
+
+    def piece(self, ix, iz):
+        """What the set pieces about floating terrain are made of, at column (ix, iz), y0 = two samples under the first update's plane:
+        clear  an eroding sphere of 5.5 samples about (ix, y0 + 8, iz): whatever earlier operations left there becomes air;
+        stem, cap  a thin upright cylinder from y0 to y0 + 7 with a ball of 2.4 samples on it -- it stands in whatever lies under the cleared air;
+        neck   an eroding ball of 1.8 samples through the stem at y0 + 5: the cap, and the stub of the stem under it, hang on nothing;
+        big, small  two balls in the cleared air, of about 40 samples and of 7;
+        box    the samples ix - 6 .. ix + 6, y0 + 1 .. y0 + 14, iz - 6 .. iz + 6: half a sample wider than the cleared ball, its bottom
+               in the ground under it, so what lies about the cleared air hangs on the box's faces.  Its image is under 10 KB, so that a
+               step with it fits the budgets of a session, which are three times its median step."""
+        s, y0 = self.scale, self.top[1] // 2 - 2
+        return dict(clear=("sphere", (self.at(ix, y0 + 8, iz), 5.5 * s, False)),
+                    stem=("cylinder", (self.at(ix, y0, iz), (0.0, 1.0, 0.0), 7.0 * s, 1.1 * s, True)),
+                    cap=("sphere", (self.at(ix, y0 + 9, iz), 2.4 * s, True)),
+                    neck=("sphere", (self.at(ix, y0 + 5, iz), 1.8 * s, False)),
+                    big=("sphere", (self.at(ix - 2, y0 + 8, iz), 2.1 * s, True)),
+                    small=("sphere", (self.at(ix + 3, y0 + 8, iz), 1.3 * s, True)),
+                    box=self.aabb(((ix - 6, ix + 6), (y0 + 1, y0 + 14), (iz - 6, iz + 6))))
+
+    def whole(self):
+        return self.aabb(tuple((-3, t + 3) for t in self.top))
+
+    def interior(self):
+        """A box none of whose faces is a grid face: three samples inside along x and z, two along y."""
+        return self.aabb(((3, self.top[0] - 3), (2, self.top[1] - 2), (3, self.top[2] - 3)))
+
+    def band(self):
+        """A box of 16 to 24 columns along x and z somewhere inside, over nearly the whole height: it holds the surface wherever it lies."""
+        out = []
+        for k in (0, 2):
+            n = int(self.rng.integers(16, 25))
+            lo = int(self.rng.integers(2, self.top[k] - n - 1))
+            out.append((lo, lo + n))
+        return self.aabb((out[0], (1, self.top[1] - 1), out[1]))
+
+    def scatter(self, cells=None, **kw):
+        """("scatter", keyword arguments of vt.ScatterParams): `cells` instances per cell face (the density limit is 8 of them)."""
+        cells = float(self.rng.uniform(0.5, 3.0)) if cells is None else cells
+        return ("scatter", dict(density=cells / (self.scale * self.scale), seed=int(self.rng.integers(0, 1 << 30)), **kw))
+
+    def field(self, climb, drop, max_cost=NO_CUT):
+        """("field", goal picks, climb, drop, max_cost): three goals of distinct costs at fractions of the nav result's largest region."""
+        fr = sorted(float(v) for v in self.rng.uniform(0.0, 1.0, 3))
+        return ("field", ((fr[0], 300), (fr[1], 0), (fr[2], 5000)), climb, drop, max_cost)
+
+    def walk(self, max_len=512):
+        return ("walk", int(self.rng.integers(0, 1 << 30)), max_len)
 
 
 def _operations1(d, n_ops):
@@ -696,15 +1005,18 @@ def _operations1(d, n_ops):
     return ops
 
 
-def _operations2(d, world, n_ops):
+def _operations2(d, world, n_ops, more_deck=(), more_extras=(), more=None):
     """The second generation: the first one's deck with paths and pastes of mesh stamps beside every old category, and between the
     queues the operations on the material layer, the vertex attributes, the level-of-detail extract (world c), the queries and the
-    chunk file, in the sequences the conditions of test_terrain_session.py ask for."""
+    chunk file, in the sequences the conditions of test_terrain_session.py ask for.  The third generation hands in what it adds:
+    more_deck, (category, mode) pairs shuffled into the deck; more_extras, names shuffled among the extras; more(name, ops, tools), which
+    appends the operations of such a name."""
     r, s = d.rng, d.scale
     modes = ("low", "high", "block", "free")
     deck = [(cat, mode) for cat in KINDS2 for mode in modes if cat not in ("plane", "island") or mode != "free"]
     deck += [("plane", "world"), ("island", "world"), ("island", "world"), ("sphere", "outside")]
     deck += [("path:erode", "single"), ("path:add", "long"), ("path:erode", "zero")]
+    deck += list(more_deck)
     deck = [deck[i] for i in r.permutation(len(deck))]
     extras = ["capture:low", "capture:high", "capture:free", "destroy", "create", "load:chunk", "load:probe", "load:layer",
               "budget", "budget", "material_init", "material_init", "paint", "paint", "paint", "control_map", "control_map"]
@@ -713,6 +1025,7 @@ def _operations2(d, world, n_ops):
     extras += ["undo,probe", "probe", "probe"]
     if world == "c":
         extras += ["undo,lod", "lod,attributes", "lod"]
+    extras += list(more_extras)
     queues = []
     while deck:
         n = min(int(r.integers(1, 5)), len(deck))
@@ -800,6 +1113,8 @@ def _operations2(d, world, n_ops):
             ops += [d.attributes(), after]
         elif arg == "lod":
             ops.append(lod())
+        elif more is not None:
+            more(arg, ops, dict(small=small, queue_of=queue_of, edit_undo=edit_undo))
         else:
             raise AssertionError(arg)
     while len(ops) < n_ops - 1:
@@ -809,17 +1124,80 @@ def _operations2(d, world, n_ops):
     return ops
 
 
+def _operations3(d, world, n_ops):
+    """The third generation: the second one's deck and extras with a detach modifier on the low faces, on the high faces, on block faces
+    and anywhere, and between the queues the set pieces the conditions of test_terrain_session.py ask for -- each a fixed sequence of
+    operations about one place, so that what the condition needs follows from the sequence and not from luck."""
+    r, s = d.rng, d.scale
+    noise = lambda tools: ("update", tools["queue_of"]([(KINDS[int(r.integers(6, 9))], "free")]))   # noqa: E731  a queue that draws
+
+    def more(arg, ops, tools):
+        if arg == "dig":        # a dig and what falls off in one step, undone and redone; a detach with nothing left to remove; a later draw
+            p = d.piece(*d.site())
+            loose = ("detach", dict(max_samples=0), p["box"])
+            ops += [("update", [p["clear"], p["stem"], p["cap"]]), ("update", [p["neck"], loose]), ("undo",), ("redo",), ("update", [loose]), noise(tools)]
+        elif arg == "debris":   # the query around a detach, its undo and its redo; a size limit that protects; a captured fragment pasted back
+            p = d.piece(*d.site())
+            q = d.queries
+            ops += [("update", [p["clear"], p["big"], p["small"]]), ("fragments", p["box"], 0, 0),
+                    ("update", [("detach", dict(max_samples=20), p["box"])]), ("fragments", p["box"], 0, 0),
+                    ("update", [("detach", dict(max_samples=0), p["box"])]), ("fragments", p["box"], 0, 0),
+                    ("undo",), ("fragments", p["box"], 0, 8), ("redo",),
+                    ("update", [("fragment_paste", dict(query=q, rank=0))]), ("fragments", p["box"], 100, 0), noise(tools)]
+            d.ids_known, d.queries = False, q + 1
+            # the ids behind the captured ones, from the one counter: a created, a captured and a voxelized stamp, then the fragment's goes
+            ops += [d.create(), d.capture("free"), d.mesh_stamp("box"), ("stamp_destroy", ("fragment", q, 0)), d.create()]
+        elif arg == "lost":     # a detach step that is undone and then discarded by an edit
+            ops += [("update", tools["queue_of"]([("detach", "free")])), ("undo",), ("update", tools["small"](4, 9))]
+        elif arg == "fragments:all":   # every fragment of the whole grid of four samples or more becomes a stamp
+            ops += [("fragments", d.whole(), 0, 4), d.create(), noise(tools)]
+            d.ids_known, d.queries = False, d.queries + 1
+        elif arg == "scatter:paint":   # a sparse list; a channel a stroke has just painted; paint and the attribute passes leave the instances alone
+            ops.append(("material_init", 1))
+            c = tools["edit_undo"]()
+            strokes = d.strokes(2, at=c)
+            ops += [("paint", strokes), d.scatter(3.0, material_channel=strokes[0][2]), ("paint", d.strokes(2, at=c)), d.attributes(), d.scatter()]
+        elif arg == "scatter:load":    # a load's full list: with a channel and the layer gone, plain, and too large
+            ops += [("save_load",), d.scatter(material_channel=2), d.scatter(), d.scatter(max_instances=int(r.integers(1, 9))), d.scatter(min_up=0.7),
+                    ("update", tools["small"](0, 9))]
+        elif arg == "scatter:undo":
+            tools["edit_undo"]()
+            ops += [("undo",), d.scatter(max_up=0.9), ("redo",), d.scatter(min_y=d.pos(d.top[1] // 2 - 2, 1), max_y=d.pos(d.top[1] // 2 + 3, 1)), ("undo",)]
+        elif arg == "scatter:lod":     # a level-of-detail result is no dirty list's
+            ops += [("lod", CORNER_VIEWER, LOD_MAX_LEVEL if world == "c" else 0, 1.0), d.scatter(), ("undo",), d.scatter()]
+        elif arg == "nav:whole":       # the snapshot and its field held across one of everything that must keep them (include/vtmc_nav.h, Life cycle)
+            ops += [("nav", d.whole(), 2, 1.0), d.field(2.5, 0.5), d.walk(), ("update", tools["small"](0, 9)), d.walk(6), ("paint", d.strokes(1)),
+                    d.attributes(), d.scatter(), ("fragments", d.band(), 0, 0), ("undo",), ("redo",),
+                    ("lod", CORNER_VIEWER, LOD_MAX_LEVEL if world == "c" else 0, 1.0), ("set_history", float(r.uniform(2.6, 3.6))),
+                    ("probe", int(r.integers(0, 1 << 30))), d.walk()]
+        elif arg == "nav:edit":        # a snapshot and its field held across an edit of their box; the rebuild drops the field
+            box = d.interior()
+            ops += [("nav", box, 1, 1.5), d.field(1.0, 0.25, FIELD_CUT), d.walk(6)]
+            tools["edit_undo"]()
+            ops += [d.walk(), ("nav", box, 1, 1.5), d.walk(), d.field(0.0, 0.0), d.walk()]
+        elif arg == "nav:load":        # a load drops both
+            ops += [("nav", d.band(), 3, 0.5), d.field(1024.0, 0.0), d.scatter(), ("save_load",), d.field(1.0, 1.0), d.walk()]
+        elif arg == "walk":
+            ops.append(d.walk())
+        else:
+            raise AssertionError(arg)
+
+    more_extras = ["dig", "debris", "lost", "fragments:all", "scatter:paint", "scatter:load", "scatter:undo", "scatter:lod", "nav:whole", "nav:edit",
+                   "nav:load", "walk", "walk"]
+    return _operations2(d, world, n_ops, [("detach", m) for m in ("low", "high", "block", "free")], more_extras, more)
+
+
 def generate(seed, world, n_ops=None, history_from_start=True, generation=1):
     """The session (seed, world) as a list of n_ops operations (N_OPS, or N_OPS2 for generation 2).  history_from_start False: the same
     list with the history switched on a third of the way in instead of before the first update (budget changes before that point switch
-    it off again).  generation 2: its own deck, seeds and length (_operations2)."""
-    n_ops = n_ops or (N_OPS if generation == 1 else N_OPS2)
+    it off again).  generation 2: its own deck, seeds and length (_operations2); generation 3 likewise (_operations3)."""
+    n_ops = n_ops or {1: N_OPS, 2: N_OPS2, 3: N_OPS3}[generation]
     d = _Draw(seed, world, generation)
     s = d.scale
-    ops = _operations1(d, n_ops) if generation == 1 else _operations2(d, world, n_ops)
+    ops = {1: lambda: _operations1(d, n_ops), 2: lambda: _operations2(d, world, n_ops), 3: lambda: _operations3(d, world, n_ops)}[generation]()
     # budgets relative to the session's own median step size
     ref = type("Shape", (), dict(dims=d.dims, scale=s, origin=np.asarray(d.origin, f32)))
-    sizes = [sum(image_bytes(box_of(ref, gpu_struct(sp))[1]) for sp in op[1]) for op in ops if op[0] == "update"]
+    sizes = [sum(image_bytes(box_of(ref, gpu_struct(sp))[1]) for sp in op[1] if sp[0] != "fragment_paste") for op in ops if op[0] == "update"]
     median = float(np.median([b for b in sizes if b]))
     first = 0 if history_from_start else n_ops // 3
     ops.insert(first, ("set_history", 3.1))

@@ -8,6 +8,8 @@ The rules the table is written from:
   * vtmc_read_triangles reads a soup result, vtmc_read_indexed_mesh / vtmc_last_vertex_count an indexed one;
   * vtmc_material_vertices and vtmc_ao_vertices accept the result of vtmc_terrain_update / _undo / _redo / _load only, and their readers the
     values computed for the result the context holds: every later extract makes them stale;
+  * vtmc_scatter_surface accepts what vtmc_material_vertices accepts ("the life cycle is that of the vertex attributes"), and
+    vtmc_scatter_read / _device_results go stale exactly where the two attribute readers do;
   * vtmc_terrain_lod_nodes accepts a level-of-detail result only;
   * vtmc_chunk_write needs an extract over whole volumes: a device batch, or a terrain extract of every block (vtmc_terrain_load).
 
@@ -23,16 +25,17 @@ from volumetricterrain_amd import _lib
 f32 = np.float32
 OK, NO = _lib.OK, _lib.ERR_NO_RESULT
 CONSUMERS = ("last_counts", "read_triangles", "read_indexed_mesh", "last_vertex_count", "read_cases", "device_results", "material_vertices",
-             "material_read_vertices", "ao_vertices", "ao_read_vertices", "terrain_lod_nodes", "chunk_write", "copy_volume_counts_device")
+             "material_read_vertices", "ao_vertices", "ao_read_vertices", "terrain_lod_nodes", "chunk_write", "copy_volume_counts_device",
+             "scatter_surface", "scatter_read")
 # One letter per consumer, in the order above: Y accepted, - VTMC_ERR_NO_RESULT, S accepted in soup mode only, I in indexed mode only.
-# The two attribute readers are asked after the two attribute passes of the same row.
-NOTHING = "- - - - - - - - - - - - -"
-QUEUED = "- - - - - - - - - - - - Y"
-CALLER_BLOCKS = "Y S I I Y Y - - - - - - Y"       # tiles or a block list of the caller's
-CALLER_VOLUMES = "Y S I I Y Y - - - - - Y Y"      # a device batch of whole volumes
-DIRTY_LIST = "Y S I I Y Y Y Y Y Y - - Y"          # the terrain's dirty list, a proper subset of its blocks
-DIRTY_ALL = "Y S I I Y Y Y Y Y Y - Y Y"           # every block of the terrain: one whole volume
-LOD = "Y S I I Y Y - - - - Y - Y"
+# The two attribute readers are asked after the two attribute passes of the same row, scatter_read after the scatter of the same row.
+NOTHING = "- - - - - - - - - - - - - - -"
+QUEUED = "- - - - - - - - - - - - Y - -"
+CALLER_BLOCKS = "Y S I I Y Y - - - - - - Y - -"       # tiles or a block list of the caller's
+CALLER_VOLUMES = "Y S I I Y Y - - - - - Y Y - -"      # a device batch of whole volumes
+DIRTY_LIST = "Y S I I Y Y Y Y Y Y - - Y Y Y"          # the terrain's dirty list, a proper subset of its blocks
+DIRTY_ALL = "Y S I I Y Y Y Y Y Y - Y Y Y Y"           # every block of the terrain: one whole volume
+LOD = "Y S I I Y Y - - - - Y - Y - -"
 
 
 def sphere_field(n, radius):
@@ -67,6 +70,7 @@ def test_gpu_every_consumer_after_every_producer(indexed, tmp_path):
         tris, verts, idx = np.zeros(4096, _lib.TRI_DTYPE), np.zeros(8192, _lib.VERTEX_DTYPE), np.zeros((4096, 3), np.int32)
         cases, weights, occlusion = np.zeros(8 * 512, np.uint8), np.zeros((12288, 8), np.uint8), np.zeros(12288, np.uint8)
         ao_params, origin = _lib.AoParams(1.0, 1.0, 4, 0), (i32 * 3)(0, 0, 0)
+        instances, scatter_params = np.zeros(1 << 14, _lib.INSTANCE_DTYPE), vt.ScatterParams(2.0, seed=5).to_struct()
         ask = {
             "last_counts": lambda: L.vtmc_last_counts(h, ctypes.byref(i32()), ctypes.byref(i32())),
             "read_triangles": lambda: L.vtmc_read_triangles(h, tris.ctypes.data, len(tris), None),
@@ -81,10 +85,13 @@ def test_gpu_every_consumer_after_every_producer(indexed, tmp_path):
             "terrain_lod_nodes": lambda: L.vtmc_terrain_lod_nodes(h, None, 0, ctypes.byref(i32())),
             "chunk_write": lambda: L.vtmc_chunk_write(h, str(chunk_file).encode(), 0, ctypes.byref(origin), 1),
             "copy_volume_counts_device": lambda: L.vtmc_copy_volume_counts_device(h, d_counts.data_ptr(), 4, None),
+            "scatter_surface": lambda: L.vtmc_scatter_surface(h, ctypes.byref(scatter_params), ctypes.byref(i64())),
+            "scatter_read": lambda: L.vtmc_scatter_read(h, instances.ctypes.data, len(instances), None),
         }
-        readers = ("material_read_vertices", "ao_read_vertices", "material_device_results", "ao_device_results")
+        readers = ("material_read_vertices", "ao_read_vertices", "material_device_results", "ao_device_results", "scatter_read", "scatter_device_results")
         ask_reader = dict(ask, material_device_results=lambda: L.vtmc_material_device_results(h, None, None),
-                          ao_device_results=lambda: L.vtmc_ao_device_results(h, None, None))
+                          ao_device_results=lambda: L.vtmc_ao_device_results(h, None, None),
+                          scatter_device_results=lambda: L.vtmc_scatter_device_results(h, None, None, None))
         computed = [False]   # an attribute pass has succeeded at some earlier row
 
         def check(producer, row, untouched=False):
@@ -97,6 +104,7 @@ def test_gpu_every_consumer_after_every_producer(indexed, tmp_path):
             got = {name: ask[name]() for name in CONSUMERS}
             assert got == want, (producer, {n: (got[n], want[n]) for n in CONSUMERS if got[n] != want[n]})
             assert ask_reader["material_device_results"]() == want["material_vertices"] and ask_reader["ao_device_results"]() == want["ao_vertices"], producer
+            assert ask_reader["scatter_device_results"]() == want["scatter_surface"], producer
             computed[0] = computed[0] or want["material_vertices"] == OK
 
         def layer():   # vtmc_terrain_init / _load drop the material layer; the result is none of its business

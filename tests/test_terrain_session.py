@@ -2,11 +2,18 @@
 of the shared box walk (64 lanes along x, 4 z-planes, runs of 16 along y) for every kernel that runs on it, the path kernel included, and
 the inclusive dirty rule on the device.
 
-Two generations of sessions.  The first (worlds a and b, soup output) is pinned by digests of its operation lists.  The second (worlds b
-and c, one soup and one indexed session each) adds paths and pastes of mesh stamps to the deck and, between the queues, the consumers
-of the resident terrain: the material layer (init, paint, control map), the vertex weights and occlusion bytes of whatever result the
-context holds, the level-of-detail extract, ray and sphere queries and the chunk file -- each against its own twin (material_twin,
-ao_twin, lod_twin, surface_twin, chunkfile) on the MODEL's grid, after undos, redos, ring wraps and loads.
+Three generations of sessions, each pinned by digests of its operation lists before the next one was written.  The first (worlds a and
+b, soup output) is the edit loop alone.  The second (worlds b and c, one soup and one indexed session each) adds paths and pastes of
+mesh stamps to the deck and, between the queues, the consumers of the resident terrain: the material layer (init, paint, control map),
+the vertex weights and occlusion bytes of whatever result the context holds, the level-of-detail extract, ray and sphere queries and
+the chunk file -- each against its own twin (material_twin, ao_twin, lod_twin, surface_twin, chunkfile) on the MODEL's grid, after
+undos, redos, ring wraps and loads.  The third (the same worlds and modes) adds the detach modifier to the queues and, between them,
+the fragment query (with capture: its stamps share the id counter of every other stamp), the surface scatter, the navigation build,
+the flow field and batches of located and traced agents, against fragment_twin, scatter_twin, nav_twin and navfield_twin, all for
+EQUALITY.  What it is about is not the kernels -- each layer's own file covers those -- but the host state that lets the layers live
+beside everything else: after EVERY operation of such a session assert_layers compares the nav result, the field and the instances the
+context holds with the ones the model holds (or VTMC_ERR_NO_RESULT with none), so each keep rule and each drop rule of include/vtmc.h,
+vtmc_nav.h and vtmc_navfield.h is tried against every producer a session holds, not only against the ones a directed test thought of.
 
 CPU: the generator is deterministic and every committed seed meets the coverage conditions (conditions, not measurements: a seed that
 misses one is replaced, the condition stays); the history model gives the answers worked by hand below; the model's snapshots are
@@ -26,14 +33,21 @@ import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib, terrainfile as tf
 import ao_twin
 import material_twin
+import nav_twin
+import navfield_twin
 import path_twin
+import scatter_twin
 import session_twin as st
 import stamp_twin
+import test_terrain_nav as nav
 from extract_checks import ATOL, assert_tris_match
 from session_twin import FACES, FAMILIES, KINDS, SEEDS, History, Session, generate
 from surface_twin import Surface, check_tight, compare as compare_rays, reference as ray_reference
 from terrain_twin import assert_triangles, bits, block_list, box_of, csg_write, gpu_struct, oracle_mod_of
 from test_sphere_queries import SphereSurface, check as check_spheres
+from test_terrain_fragments import same_records
+from test_terrain_navfield import same_cells
+from test_terrain_scatter import assert_instances, mesh_of as scatter_mesh_of
 
 f32 = np.float32
 CASES = [(w, s) for w in sorted(SEEDS) for s in SEEDS[w]]
@@ -214,6 +228,16 @@ def twin_run2(oracle_mod, tmp_path_factory, world, seed, indexed):
     return _runs2[key]
 
 
+# the second generation, pinned the same way: computed before the generator learnt its third generation
+DIGESTS2 = {("b", 3): "1f14d882af20bd26", ("b", 4): "632d45d395ecc829", ("c", 1): "73ac3aa2633360f3", ("c", 3): "5a4fe316cce07151"}
+
+
+@pytest.mark.parametrize("world,seed,indexed", CASES2, ids=IDS2)
+def test_second_generation_sessions_are_unchanged(world, seed, indexed):
+    assert set(DIGESTS2) == {(w, s) for w, s, _ in CASES2}
+    assert digest(generate(seed, world, generation=2)) == DIGESTS2[world, seed]
+
+
 @pytest.mark.parametrize("world,seed,indexed", CASES2, ids=IDS2)
 def test_second_generation_is_deterministic_and_holds_its_deck(world, seed, indexed):
     ops = generate(seed, world, generation=2)
@@ -321,6 +345,152 @@ def test_generator_conditions_of_the_second_generation(oracle_mod, tmp_path_fact
         assert 3 * p["hits"] >= p["n"] and p["sphere_hits"] >= 4, p
         assert p["ambiguous"] == 0 and p["sphere_ambiguous"] == 0, p
 
+
+# -- CPU: the third generation -------------------------------------------------------------------------------------------------------------
+CASES3 = [(w, seed, indexed) for w in sorted(st.SEEDS3) for seed, indexed in zip(st.SEEDS3[w], (False, True))]
+IDS3 = ["%s-%d-%s" % (w, seed, "indexed" if indexed else "soup") for w, seed, indexed in CASES3]
+UNREACHED = _lib.NAVFIELD_UNREACHED
+
+
+def twin_run3(oracle_mod, tmp_path_factory, world, seed, indexed):
+    """A third-generation session on the model alone, once per case (in twin_run2's cache): the model after the last operation, the
+    concrete operations and a note per operation -- what it returned, in numbers, and what the model held after it.  `stale`: the nav
+    snapshot held differs from nav_twin.build of the model's grid as it is now, in the same box with the same parameters."""
+    key = (world, seed, indexed, 3)
+    if key not in _runs2:
+        tmp = tmp_path_factory.mktemp("session3_%s%d" % (world, seed))
+        s = Session(oracle_mod, world, indexed)
+        n_blocks = s.nb[0] * s.nb[1] * s.nb[2]
+        ops, log, stale, builds = [], [], False, 0
+        for i, op in enumerate(generate(seed, world, generation=3)):
+            op = s.concrete(op)
+            ops.append(op)
+            n = dict(i=i, name=op[0], op=op, prev=s.last, source=s.result_source, result=s.result, layer=s.layer is not None, loads=s.loads,
+                     all_blocks=s.result == "terrain" and len(s.result_dirty) == n_blocks, n_detaches=len(s.detaches), n_pastes=len(s.pastes),
+                     draws=dict(s.draws_after), had=dict(scatter=s.scatter is not None, nav=s.nav is not None, field=s.field is not None))
+            grid = bits(s.ref.grid).copy()
+            out = s.run(op, tmp)
+            if op[0] == "fragments":
+                n.update(sizes=out[0]["n_samples"].tolist(), ids=out[1][out[1] > 0].tolist(), faces=st.faces_of(*s.sample_box(op[1]), s.ref.dims))
+            elif op[0] == "scatter":
+                n["out"] = "refused" if out is None else out if isinstance(out, str) else len(out[0])
+                if not isinstance(n["out"], str) and op[1].get("material_channel", -1) >= 0:      # the same without the channel filter
+                    n["unfiltered"] = len(scatter_twin.scatter(*s.records(), s.world["scale"], s.world["origin"],
+                                                               **{k: v for k, v in op[1].items() if k in st.SCATTER_KEYS and k != "material_channel"})[0])
+            elif op[0] == "nav":
+                builds, stale = builds + 1, False
+                n.update(spans=len(out[0]), regions=len(np.unique(out[0]["region"])), box=(out[2], out[3]), faces=st.faces_of(out[2], out[3], s.ref.dims))
+            elif op[0] == "field":
+                n["out"] = "refused" if out is None else int((out["cost"] != UNREACHED).sum())
+                if out is not None:
+                    n["spans"] = len(out)
+                    n["uncut"] = int((navfield_twin.field(s.nav[0], s.field_goals, op[2], op[3])["cost"] != UNREACHED).sum())
+            elif op[0] == "walk":
+                _, _, _, located, traced = out
+                n["out"] = "refused" if located is None else "located" if traced is None else "traced"
+                if traced is not None:
+                    paths, lengths = traced
+                    last = paths[np.arange(len(paths)), np.maximum(lengths, 1) - 1]
+                    n.update(hits=int((located >= 0).sum()), misses=int((located < 0).sum()),
+                             cut=int(((lengths == op[2]) & (s.field["next"][last] >= 0)).sum()), whole=int(((lengths > 1) & (lengths < op[2])).sum()),
+                             unreached=int(((located >= 0) & (s.field["cost"][np.maximum(located, 0)] == UNREACHED)).sum()))
+            if s.nav is not None and op[0] != "nav" and not np.array_equal(grid, bits(s.ref.grid)):
+                now = nav_twin.build(np.array(s.ref.grid), *s.sample_box(s.nav_key[0]), *s.nav_key[1:])
+                stale = not (nav_twin.nan_aware_equal(now[0], s.nav[0]) and np.array_equal(now[1], s.nav[1]))
+            n.update(last=s.last, build=builds if s.nav is not None else None, stale=stale and s.nav is not None, key=s.nav_key,
+                     held=dict(scatter=s.scatter is not None, nav=s.nav is not None, field=s.field is not None))
+            log.append(n)
+        _runs2[key] = (s, ops, log)
+    return _runs2[key]
+
+
+@pytest.mark.parametrize("world,seed,indexed", CASES3, ids=IDS3)
+def test_third_generation_is_deterministic_and_keeps_the_older_ones(world, seed, indexed):
+    ops = generate(seed, world, generation=3)
+    assert len(ops) == st.N_OPS3 and plain(ops) == plain(generate(seed, world, generation=3))
+    assert plain(ops) != plain(generate(seed + 1000, world, generation=3)) and plain(ops[:20]) != plain(generate(seed, world, generation=2)[:20])
+    assert ops[0][0] == "set_history" and ops[0][1] > 0 and all(op[1] > 0 for op in ops if op[0] == "set_history")
+    names = [op[0] for op in ops]
+    for name, least in (("fragments", 6), ("scatter", 11), ("nav", 4), ("field", 5), ("walk", 9)):
+        assert names.count(name) >= least, (name, names.count(name))
+    assert sum(sp[0] == "detach" for op in ops if op[0] == "update" for sp in op[1]) >= 9
+    assert len(CASES3) == 4 and {w for w, _, _ in CASES3} == {"b", "c"}
+
+
+@pytest.mark.parametrize("world,seed,indexed", CASES3, ids=IDS3)
+def test_generator_conditions_of_the_third_generation(oracle_mod, tmp_path_factory, world, seed, indexed):
+    """Conditions, not measurements, per committed session; each with an assert of its own.  The paste that puts a captured fragment back
+    bit for bit (include/vtmc.h at vtmc_terrain_fragments) needs sample positions that float32 holds exactly: world c's dyadic scale and
+    origin give them.  With world b's scale of 0.3 the stamp coordinates of the pasted samples are whole numbers only to within an ulp
+    or two, and the model says what the device must write there: the same samples solid again, the fragment listed again with its seed
+    and its count; for world b that is what the condition asks."""
+    s, ops, log = twin_run3(oracle_mod, tmp_path_factory, world, seed, indexed)
+    names = [n["name"] for n in log]
+    kinds = {k: names.count(k) for k in ("fragments", "scatter", "nav", "field", "walk")}
+    print("%s %d %s: %s, %d detach modifiers; seen %s" % (world, seed, "indexed" if indexed else "soup", kinds, len(s.detaches), s.seen))
+    for k in st.KINDS3:   # every old category still, and the new one
+        assert s.kinds[k] >= 3, (k, s.kinds)
+    # -- detach
+    D = s.detaches
+    assert any(d["cut_loose"] >= 1 and d["undone"] >= 1 and d["redone"] >= 1 for d in D), "a detach behind the erode that cut a fragment of 8 samples loose, undone and redone"
+    assert any(len(d["recs"]) == 0 and min(d["ext"]) > 0 and d["n_dirty"] > 0 for d in D), "a detach whose box holds no fragment, its dirty list not empty"
+    assert any(d["max_samples"] > 0 and d["protected"] >= 1 and len(d["recs"]) >= 1 for d in D), "a size limit that protects a fragment and lets one go"
+    assert any(d["faces"] for d in D) and s.faces["detach"] == set(FACES), "detach boxes on every grid face: %s" % sorted(s.faces["detach"])
+    assert any(d["lost"] >= 1 and d["recorded"] for d in D), "a detach step evicted by the ring or discarded from the redo stack"
+    assert s.draws_after["detach"] >= 1, "an update that draws from the event counter in a queue after a detach"
+    assert all(d["recorded"] or min(d["ext"]) == 0 or s.hist.over_budget for d in D), "a detach with a box is journaled, also when it removed nothing"
+    # -- fragments
+    F = [n for n in log if n["name"] == "fragments"]
+    assert any(n["prev"] == "undo" and n["sizes"] and not before["sizes"] and before["op"][1:3] == n["op"][1:3]
+               for before, n in zip(F, F[1:]) if log[n["i"] - 1]["name"] == "undo" and before["i"] == n["i"] - 2), "a query after an undo brought fragments back: empty before it, not after"
+    P = s.pastes
+    assert any(p["mode"] == "replace" and p["unturned"] and p["gone_before"] and p["solid_again"] for p in P), "a captured stamp pasted unturned in replace mode over its removed fragment"
+    if world == "c":
+        assert any(p["gone_before"] and p["bits_again"] for p in P), "the paste puts the fragment's samples back bit for bit"
+    else:
+        back = [n for n in F if log[n["i"] - 1]["n_pastes"] < n["n_pastes"]]       # the queries directly after a paste
+        assert any(p["c"]["n"] in n["sizes"] for p in P for n in back), "the pasted fragment is listed again with its sample count"
+    assert any(n["ids"] for n in F) and any(n["name"] == "stamp_destroy" and n["op"][1] in s.captured_ids for n in log), "a captured stamp is destroyed"
+    mixed = [n["name"] for n in log if n["i"] > min(n["i"] for n in F if n["ids"])]
+    assert {"stamp_create", "stamp_capture", "stamp_from_mesh", "stamp_destroy", "fragments"} <= set(mixed), "every stamp operation after a capturing query, in one id space"
+    assert len(s.captured) >= 2 and sum(len(c) for c in s.captured) >= 2, "two capturing queries"
+    assert s.draws_after["query"] >= 1, "an update that draws from the event counter after a query"
+    assert any(n["faces"] for n in F) and any(not n["faces"] and n["sizes"] for n in F), "queries on the grid's faces and inside"
+    # -- scatter
+    S = [n for n in log if n["name"] == "scatter"]
+    made = [n for n in S if not isinstance(n["out"], str)]
+    assert any(n["out"] > 0 and not n["all_blocks"] for n in made) and any(n["out"] > 0 and n["all_blocks"] and n["source"] == "save_load" for n in made), "a sparse dirty list and a load's full list"
+    assert any(n["out"] > 0 and n["source"] == "undo" for n in made), "a scatter after an undo"
+    assert any("unfiltered" in n and 0 < n["out"] < n["unfiltered"] for n in made), "a material channel that rejects some instances and keeps others"
+    assert any(n["out"] == "refused" and n["op"][1].get("material_channel", -1) >= 0 and n["source"] == "save_load" and not n["layer"] for n in S), "a channel after a load dropped the layer"
+    assert any(n["out"] == "refused" and n["result"] == "lod" for n in S), "a scatter on a level-of-detail result"
+    assert any(n["out"] == "too large" and n["had"]["scatter"] and not n["held"]["scatter"] for n in S), "a scatter too large, which leaves none"
+    assert any(n["held"]["scatter"] and log[n["i"] + 1]["name"] == "paint" and log[n["i"] + 1]["held"]["scatter"] and n["out"] > 0 for n in made), "paint after a scatter"
+    assert any(n["name"] == "attributes" and n["had"]["scatter"] and n["held"]["scatter"] and n["layer"] and n["result"] == "terrain" for n in log), "attributes beside a scatter, with a layer"
+    producers = [n for n in log if n["name"] in ("update", "undo", "redo", "save_load", "lod") and not n["last"].endswith("!") and n["had"]["scatter"]]
+    assert {n["name"] for n in producers} >= {"update", "undo", "redo", "save_load"} and all(not n["held"]["scatter"] for n in producers), "every producer of a result drops the scatter"
+    # -- nav
+    N = [n for n in log if n["name"] == "nav"]
+    assert len({n["box"] for n in N}) >= 3 and any(n["faces"] == set(FACES) for n in N) and any(not n["faces"] and min(n["box"][1]) > 0 for n in N), "three boxes: the whole grid, one inside"
+    assert any(n["spans"] >= 200 and n["regions"] >= 2 for n in N), "200 spans and two regions in one build"
+    assert any(n["stale"] for n in log), "a snapshot held that differs from the twin of the grid as it is then: a rebuild or a drop on an edit cannot pass"
+    assert any(log[n["i"] - 1]["stale"] and log[n["i"] - 1]["key"] == n["key"] for n in N), "a rebuild in the same box after that edit"
+    dropped = [n for n in log if n["name"] == "save_load" and n["had"]["nav"] and n["had"]["field"]]
+    assert dropped and all(not n["held"]["nav"] and not n["held"]["field"] for n in dropped), "a load drops the nav result and the field"
+    assert any(log[n["i"] + 1]["name"] == "field" and log[n["i"] + 1]["out"] == "refused" and log[n["i"] + 2]["name"] == "walk" and log[n["i"] + 2]["out"] == "refused"
+               for n in dropped), "after that load the field and the walk are refused"
+    kept = [n for n in log if n["had"]["nav"] and n["name"] in ("update", "undo", "redo", "lod", "set_history", "paint", "attributes", "scatter", "fragments", "probe")]
+    assert {n["name"] for n in kept} >= {"update", "undo", "redo", "lod", "set_history", "paint", "attributes", "scatter", "fragments", "probe"} and all(n["held"]["nav"] for n in kept), "the nav result is kept"
+    # -- field and walk
+    Fd = [n for n in log if n["name"] == "field" and n["out"] != "refused"]
+    assert any(0 < n["out"] < n["spans"] for n in Fd), "a field with reached and unreached spans"
+    assert any(n["op"][4] != st.NO_CUT and n["out"] < n["uncut"] for n in Fd), "a max_cost that cuts"
+    assert any(n["stale"] and n["held"]["field"] for n in log), "a field held across an edit that changed its box"
+    assert any(n["name"] == "nav" and n["had"]["field"] and not n["held"]["field"] for n in log), "a field dropped by a nav rebuild"
+    W = [n for n in log if n["name"] == "walk"]
+    assert any(n["out"] == "located" for n in W) and any(n["out"] == "refused" for n in W), "a walk without a field, and one without a nav result"
+    assert any(n["out"] == "traced" and n["hits"] and n["misses"] and n["cut"] and n["unreached"] for n in W), "a walk with hits, misses, a cut row and an unreached start"
+    assert any(n["out"] == "traced" and n["whole"] and n["stale"] for n in W), "a walk traced to its goal on a snapshot the grid has left behind"
 
 
 def test_twins_take_an_overridden_box(oracle_mod):
@@ -491,10 +661,48 @@ def describe(s, i, op):
         return "op %d %s %s" % (i, op[0], [(st.category(sp, s.mesh_ids), "box" if len(sp) > 2 else "own", *box_of(s.ref, st.gpu_struct(sp))[:2]) for sp in op[1]])
     if op[0] == "paint":
         return "op %d paint %s (layer %s)" % (i, [(tuple(round(v, 3) for v in c), round(r, 3), ch) for c, r, ch, _ in op[1]], "present" if s.layer is not None else "missing")
-    if op[0] in ("attributes", "lod", "probe", "chunk_write", "control_map", "material_init", "stamp_from_mesh"):
+    if op[0] in ("attributes", "lod", "probe", "chunk_write", "control_map", "material_init", "stamp_from_mesh", "fragments", "scatter", "nav", "field", "walk"):
         return "op %d %r on the result of %s (%s), layer %s" % (i, op, s.result_source, "%d dirty blocks" % len(s.result_dirty) if s.result == "terrain" else s.result,
                                                                  "present" if s.layer is not None else "missing")
     return "op %d %r" % (i, op[:1] + tuple(op[1:])[:3])
+
+
+_INSTANCES = np.zeros(1 << 17, _lib.INSTANCE_DTYPE)
+
+
+def scatter_read(ex, n_blocks):
+    """vtmc_scatter_read as it is: (status, (instances, the n_blocks + 1 block offsets) or None)."""
+    offs = np.zeros(n_blocks + 1, np.int32)
+    rc = ex._L.vtmc_scatter_read(ex._h, _INSTANCES.ctypes.data, len(_INSTANCES), offs.ctypes.data)
+    return rc, ((_INSTANCES[:offs[-1]].copy(), offs) if rc == _lib.OK else None)
+
+
+def assert_layers(ex, s, tag):
+    """The layers a third-generation session holds beside the grid, after ANY operation: the nav result (vtmc_nav_info and vtmc_nav_read),
+    the flow field and the scatter instances equal what the model holds -- snapshots of builds long past among them -- and where the
+    model holds none, the reader answers VTMC_ERR_NO_RESULT.  Equality throughout (a NaN height apart, as test_terrain_nav.py has it)."""
+    if s.nav is None:
+        assert code_of(ex.nav_read) == _lib.ERR_NO_RESULT, tag + ": a nav result is held that the model dropped"
+    else:
+        assert code_of(ex.nav_read) == _lib.OK, tag + ": the nav result the model holds is gone"
+        nav.assert_same(ex.nav_read(), s.nav, tag + ": the nav result held")
+    if s.field is None:
+        assert code_of(ex.navfield_read) == _lib.ERR_NO_RESULT, tag + ": a field is held that the model dropped"
+    else:
+        assert code_of(ex.navfield_read) == _lib.OK, tag + ": the field the model holds is gone"
+        assert same_cells(ex.navfield_read(), s.field), tag + ": the field held"
+    if s.scatter is None:
+        assert scatter_read(ex, 0)[0] == _lib.ERR_NO_RESULT, tag + ": instances are held that the model dropped"
+    else:
+        rc, got = scatter_read(ex, len(s.result_dirty))
+        assert rc == _lib.OK, "%s: the instances the model holds are gone (%d)" % (tag, rc)
+        assert_instances(got, s.scatter_result)
+
+
+def untouched(ex):
+    """What the fragment query, the nav build, the field build and a walk must leave as it was, beside the grid, the history and the
+    stamps: the attribute readers' answers, the dirty list and the counts of the result held."""
+    return reader_codes(ex), ex.terrain_dirty_blocks().tobytes(), code_of(ex.last_counts) or ex.last_counts()
 
 
 def step_session(ex, s, op, tmp, tag, mine):
@@ -662,6 +870,77 @@ def step_session(ex, s, op, tmp, tag, mine):
             assert np.array_equal(f["tri_offsets"], want_offs.astype(np.uint32)), tag
             assert_tris_match(f["triangles"], want)
         assert_state(ex, s, tag)
+    elif name == "fragments":
+        box, most, least = op[1:]
+        before = untouched(ex)
+        want, want_ids = s.fragments(box, most, least)
+        got = ex.terrain_fragments(box[0], box[1], most, least)
+        ids = got["stamp_id"].copy()
+        got["stamp_id"] = 0
+        assert same_records(got, want), (tag, got, want)
+        assert np.array_equal(ids, want_ids), (tag, ids, want_ids)      # the ids of the one counter, in the order of the records
+        for sid in want_ids[want_ids > 0]:
+            assert ex.stamp_dims(int(sid)) == s.stamps[int(sid)].shape, (tag, sid)
+        assert_stamps(ex, s, tag)
+        assert_state(ex, s, tag)                # the grid, the history; the event counter shows in the next update that draws
+        assert untouched(ex) == before, tag
+    elif name == "scatter":
+        p = op[1]
+        params = vt.ScatterParams(**p)
+        before = reader_codes(ex)
+        if s.result != "terrain" or (p.get("material_channel", -1) >= 0 and s.layer is None):
+            assert s.scatter_surface(p) is None
+            assert code_of(lambda: ex.scatter_surface(params)) == _lib.ERR_NO_RESULT, tag
+        else:
+            want = s.scatter_surface(p, scatter_mesh_of(ex, s.indexed))     # the device's own records, the model's layer
+            if isinstance(want, str):
+                assert code_of(lambda: ex.scatter_surface(params)) == _lib.ERR_TOO_LARGE, tag
+            else:
+                assert_instances(ex.scatter_surface(params), want)
+        assert reader_codes(ex) == before, tag
+        assert_state(ex, s, tag)
+    elif name == "nav":
+        box, agent_height, max_step = op[1:]
+        before = untouched(ex)
+        want = s.nav_build(box, agent_height, max_step)
+        got = ex.terrain_nav(box[0], box[1], _lib.NavParamsStruct(agent_height, max_step, 1 << 20, 0))
+        nav.assert_same(got, want, tag)
+        assert_state(ex, s, tag)
+        assert_stamps(ex, s, tag)
+        assert untouched(ex) == before, tag
+    elif name == "field":
+        picks, climb, drop, max_cost = op[1:]
+        before = untouched(ex)
+        params = vt.NavFieldParams(climb, drop, max_cost)
+        if s.nav is None:
+            assert s.field_build(*op[1:]) is None
+            assert code_of(lambda: ex.nav_field([(0, 0)], params)) == _lib.ERR_NO_RESULT, tag
+        else:
+            want = s.field_build(*op[1:])
+            got = ex.nav_field(s.field_goals, params)
+            assert same_cells(got, want), (tag, np.nonzero(got["cost"] != want["cost"])[0][:8], np.nonzero(got["next"] != want["next"])[0][:8])
+            n, n_reached, rounds = ex.navfield_info()
+            assert n == len(want) and n_reached == int((want["cost"] != UNREACHED).sum()) and 1 <= rounds <= n + 1, (tag, n, n_reached, rounds)
+        assert_state(ex, s, tag)
+        assert_stamps(ex, s, tag)
+        assert untouched(ex) == before, tag
+    elif name == "walk":
+        before = untouched(ex)
+        pos, below, above, located, traced = s.walk(*op[1:])
+        if located is None:
+            assert code_of(lambda: ex.nav_locate(pos, below, above)) == _lib.ERR_NO_RESULT, tag
+            assert code_of(lambda: ex.nav_trace(np.full(len(pos), -1, np.int32), op[2])) == _lib.ERR_NO_RESULT, tag
+        else:
+            got = ex.nav_locate(pos, below, above)
+            assert got.dtype == np.int32 and np.array_equal(got, located), (tag, np.nonzero(got != located)[0][:8])
+            if traced is None:
+                assert code_of(lambda: ex.nav_trace(located, op[2])) == _lib.ERR_NO_RESULT, tag
+            else:
+                paths, lengths = ex.nav_trace(located, op[2])
+                assert np.array_equal(lengths, traced[1]) and np.array_equal(paths, traced[0]), tag
+        assert_state(ex, s, tag)
+        assert_stamps(ex, s, tag)
+        assert untouched(ex) == before, tag
     else:
         raise AssertionError(name)
     s.last = name
@@ -683,6 +962,32 @@ def test_gpu_session_second_generation(oracle_mod, tmp_path, world, seed, indexe
         for i, op in enumerate(ops):
             step_session(ex, s, op, str(tmp_path), describe(s, i, op), mine)
         assert_stamps(ex, s, "the end")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("world,seed,indexed", CASES3, ids=IDS3)
+def test_gpu_session_third_generation(oracle_mod, tmp_path, world, seed, indexed):
+    """The second generation's sessions with the detach modifier in the queues and, between them, the fragment query, the scatter, the
+    nav build, the flow field and walks; after EVERY operation the layers held are compared with the model (assert_layers), so every
+    drop and keep rule of include/vtmc.h, vtmc_nav.h and vtmc_navfield.h is tried against every producer the session holds."""
+    w = st.WORLDS[world]
+    ops = generate(seed, world, generation=3)
+    s = Session(oracle_mod, world, indexed)
+    mine = {"undo": [], "redo": []}
+    with vt.Extractor(0) as ex:
+        ex.set_output_mode(indexed)
+        ex.terrain_init(*w["dims"], w["scale"], w["origin"], w["seed"])
+        assert_state(ex, s, "init")
+        assert_layers(ex, s, "init")
+        for i, op in enumerate(ops):
+            op = s.concrete(op)
+            tag = describe(s, i, op)
+            step_session(ex, s, op, str(tmp_path), tag, mine)
+            assert_layers(ex, s, tag)
+        assert_stamps(ex, s, "the end")
+    names = [op[0] for op in ops]
+    print("%s %d %s: %s, %d detach modifiers; seen %s" % (world, seed, "indexed" if indexed else "soup",
+                                                           {k: names.count(k) for k in ("fragments", "scatter", "nav", "field", "walk")}, len(s.detaches), s.seen))
 
 
 @pytest.mark.gpu
