@@ -5,6 +5,7 @@
 //   host_selftest --gpu-resident <out_dir>  the same scene, grid in HBM, Update on the device
 //   host_selftest --gpu-lod <out_dir>  a resident terrain meshed at three levels of detail around a viewer; dumps nodes + per-node counts
 //   host_selftest --gpu-nav <out_dir>  the navigation layer of a box of a resident terrain; dumps the spans, the column offsets and the box
+//   host_selftest --gpu-naverode <out_dir>  the agent radius on that build: dumps the distances, then the eroded spans, offsets and origin
 //   host_selftest --gpu-navfield <out_dir>  a flow field on that build: dumps the cells, every span's path and the located goal spans
 #include <cmath>
 #include <cstdio>
@@ -271,6 +272,55 @@ static int gpu_nav_run(const std::string &out)
     return 0;
 }
 
+// the world of --gpu-nav and its box; the distances of an agent 1.2 world units wide (3 columns), then the erosion by 0.8 (2 columns)
+// with the box's faces open
+static int gpu_naverode_run(const std::string &out)
+{
+    VoxelTerrain vt;
+    vt._width = 64;
+    vt._elevation = 32;
+    vt._height = 32;
+    vt._voxelScale = 0.5f;
+    vt.TerrainOrigin = Vector3(-3.0f, 1.0f, 2.0f);
+    vt._deviceResident = true;
+    vt._seed = 977;
+    vt.Init();
+    Vector2 lo, up;
+    lo.x = -100; lo.y = -100; up.x = 100; up.y = 100;
+    vt.InsertModifier(std::make_shared<PlaneModifier>(6.3f, lo, up, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(27.5f, 8.0f, 10.0f), 4.25f, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(5.0f, 6.0f, 9.0f), 3.0f, false));
+    vt.Update();
+    const int updateTriangles = vt.LastTriangleCount();
+    const NavResult nav = vt.BuildNav(Vector3(-1.0f, 1.0f, 3.0f), Vector3(14.0f, 15.0f, 16.5f), 0.9f, 0.4f);
+    const std::vector<int> dist = vt.NavDistance(1.2f);
+    if (dist.size() != nav._spans.size() || !nav._origin.empty()) return 7;
+    const NavResult eroded = vt.ErodeNav(0.8f, true);
+    std::printf("naverode: spans %zu kept %zu\n", nav._spans.size(), eroded._spans.size());
+    if (eroded._spans.empty() || eroded._spans.size() >= nav._spans.size() || eroded._origin.size() != eroded._spans.size()) return 8;
+    if (eroded._columnOffsets.size() != nav._columnOffsets.size() || eroded._columnOffsets.back() != (int)eroded._spans.size()) return 9;
+    if (eroded._boxLo._x != nav._boxLo._x || eroded._boxDims._z != nav._boxDims._z || vt.LastTriangleCount() != updateTriangles) return 10;   // what Update left stands
+    for (size_t i = 0; i < eroded._spans.size(); i++) {
+        const int o = eroded._origin[i];
+        if (o < 0 || o >= (int)nav._spans.size() || (i > 0 && o <= eroded._origin[i - 1]) || eroded._spans[i]._y != nav._spans[(size_t)o]._y) return 11;
+    }
+    std::ofstream fd(out + "/naverode_distance.i32", std::ios::binary), fs(out + "/naverode_spans.bin", std::ios::binary),
+        fo(out + "/naverode_offsets.i32", std::ios::binary), fg(out + "/naverode_origin.i32", std::ios::binary);
+    fd.write(reinterpret_cast<const char *>(dist.data()), (std::streamsize)(dist.size() * sizeof(int)));
+    fs.write(reinterpret_cast<const char *>(eroded._spans.data()), (std::streamsize)(eroded._spans.size() * sizeof(NavSpan)));
+    fo.write(reinterpret_cast<const char *>(eroded._columnOffsets.data()), (std::streamsize)(eroded._columnOffsets.size() * sizeof(int)));
+    fg.write(reinterpret_cast<const char *>(eroded._origin.data()), (std::streamsize)(eroded._origin.size() * sizeof(int)));
+    bool refused = false;   // 200 world units are 400 columns: more than the layer takes
+    try {
+        vt.ErodeNav(200.0f);
+    } catch (const UnityException &) {
+        refused = true;
+    }
+    if (!refused) return 12;
+    std::printf("HOST-NAVERODE-OK\n");
+    return 0;
+}
+
 // the world of --gpu-nav and its box; a field towards two goals found by position, then every span's path
 static int gpu_navfield_run(const std::string &out)
 {
@@ -384,11 +434,12 @@ int main(int argc, char **argv)
         if (argc >= 3 && std::string(argv[1]) == "--gpu-resident") return gpu_resident_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-lod") return gpu_lod_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-nav") return gpu_nav_run(argv[2]);
+        if (argc >= 3 && std::string(argv[1]) == "--gpu-naverode") return gpu_naverode_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-navfield") return gpu_navfield_run(argv[2]);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "exception: %s\n", e.what());
         return 3;
     }
-    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir> | --gpu-resident <out_dir> | --gpu-lod <out_dir> | --gpu-nav <out_dir> | --gpu-navfield <out_dir>\n");
+    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir> | --gpu-resident <out_dir> | --gpu-lod <out_dir> | --gpu-nav <out_dir> | --gpu-naverode <out_dir> | --gpu-navfield <out_dir>\n");
     return 64;
 }

@@ -8,6 +8,7 @@
 #include <unordered_set>
 
 #include "../include/vtmc_navfield.h"   // includes vtmc_nav.h, which includes vtmc.h
+#include "../include/vtmc_naverode.h"
 
 namespace PGRTerrain {
 
@@ -201,9 +202,17 @@ public:
         const float lo[3] = {lower.x, lower.y, lower.z}, up[3] = {upper.x, upper.y, upper.z};
         vtmc_nav_params p;
         p.agent_height = agentHeight, p.max_step = maxStep, p.max_spans = maxSpans, p.flags = 0;
+        int32_t n = 0;
+        if (vtmc_terrain_nav_build(_ctx, lo, up, &p, &n) != VTMC_OK) throw UnityException(std::string("vtmc_terrain_nav_build: ") + vtmc_last_error(_ctx));
+        ReadNav(out);
+        out._origin.clear();
+    }
+
+    // the nav result the context holds
+    void ReadNav(NavResult &out)
+    {
         int32_t n = 0, first[3], dims[3];
-        if (vtmc_terrain_nav_build(_ctx, lo, up, &p, &n) != VTMC_OK || vtmc_nav_info(_ctx, first, dims, &n) != VTMC_OK)
-            throw UnityException(std::string("vtmc_terrain_nav_build: ") + vtmc_last_error(_ctx));
+        if (vtmc_nav_info(_ctx, first, dims, &n) != VTMC_OK) throw UnityException(std::string("vtmc_nav_info: ") + vtmc_last_error(_ctx));
         std::vector<vtmc_nav_span> list((size_t)n);
         out._columnOffsets.assign((size_t)dims[0] * (size_t)dims[2] + 1, 0);
         static_assert(sizeof(int) == sizeof(int32_t), "column offsets are read in place");
@@ -213,6 +222,33 @@ public:
         out._boxDims = Int3(dims[0], dims[1], dims[2]);
         out._spans.clear();
         for (const vtmc_nav_span &s : list) out._spans.push_back(NavSpan{s.height, s.y, s.clearance, {s.link[0], s.link[1], s.link[2], s.link[3]}, s.region});
+    }
+
+    static vtmc_naverode_params ErodeParams(int radius, bool openBoxFaces)
+    {
+        vtmc_naverode_params p;
+        p.radius = radius, p.flags = openBoxFaces ? VTMC_NAVERODE_OPEN_BOX_FACES : 0u, p.reserved[0] = p.reserved[1] = 0;
+        return p;
+    }
+
+    void NavDistance(int radius, bool openBoxFaces, std::vector<int> &out) override
+    {
+        const vtmc_naverode_params p = ErodeParams(radius, openBoxFaces);
+        int32_t n = 0;
+        if (vtmc_nav_distance_build(_ctx, &p, nullptr) != VTMC_OK || vtmc_nav_distance_device_results(_ctx, nullptr, &n) != VTMC_OK)
+            throw UnityException(std::string("vtmc_nav_distance_build: ") + vtmc_last_error(_ctx));
+        out.assign((size_t)n, 0);
+        if (vtmc_nav_distance_read(_ctx, out.data(), n) != VTMC_OK) throw UnityException(std::string("vtmc_nav_distance_read: ") + vtmc_last_error(_ctx));
+    }
+
+    void NavErode(int radius, bool openBoxFaces, NavResult &out) override
+    {
+        const vtmc_naverode_params p = ErodeParams(radius, openBoxFaces);
+        int32_t n = 0;
+        if (vtmc_nav_erode(_ctx, &p, &n) != VTMC_OK) throw UnityException(std::string("vtmc_nav_erode: ") + vtmc_last_error(_ctx));
+        ReadNav(out);
+        out._origin.assign((size_t)n, 0);
+        if (vtmc_nav_erode_origin(_ctx, out._origin.data(), n) != VTMC_OK) throw UnityException(std::string("vtmc_nav_erode_origin: ") + vtmc_last_error(_ctx));
     }
 
     void NavLocate(const std::vector<Vector3> &positions, float below, float above, std::vector<int> &out) override
@@ -386,6 +422,29 @@ NavResult VoxelTerrain::BuildNav(const Vector3 &lower, const Vector3 &upper, flo
     if (!(samples >= 1.0f && samples <= (float)VTMC_NAV_MAX_AGENT_HEIGHT)) throw UnityException("BuildNav: agentHeight outside 1..256 samples");
     NavResult out;
     _backend->TerrainNav(lower, upper, (int)samples, maxStep / _voxelScale, maxSpans, out);
+    return out;
+}
+
+static int NavRadiusColumns(float radius, float voxelScale, const char *who)
+{
+    const float columns = std::ceil(radius / voxelScale);
+    if (!(columns >= 0.0f && columns <= (float)VTMC_NAVERODE_MAX_RADIUS)) throw UnityException(std::string(who) + ": radius outside 0..255 columns");
+    return (int)columns;
+}
+
+std::vector<int> VoxelTerrain::NavDistance(float radius, bool openBoxFaces)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("NavDistance needs an initialised device-resident terrain");
+    std::vector<int> out;
+    _backend->NavDistance(NavRadiusColumns(radius, _voxelScale, "NavDistance"), openBoxFaces, out);
+    return out;
+}
+
+NavResult VoxelTerrain::ErodeNav(float radius, bool openBoxFaces)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("ErodeNav needs an initialised device-resident terrain");
+    NavResult out;
+    _backend->NavErode(NavRadiusColumns(radius, _voxelScale, "ErodeNav"), openBoxFaces, out);
     return out;
 }
 

@@ -322,6 +322,7 @@ struct NavResult {
     std::vector<NavSpan> _spans;
     std::vector<int> _columnOffsets;
     MathHelper::Int3 _boxLo, _boxDims;
+    std::vector<int> _origin;   // after VoxelTerrain::ErodeNav: per span its index in the result that was eroded; empty after BuildNav
 };
 
 // New (not in the reference): a flow field on the last BuildNav (include/vtmc_navfield.h, where the rule is).  A goal is a span and the
@@ -418,6 +419,9 @@ struct ExtractBackend {
         throw std::logic_error("TerrainNav on a backend without device-resident terrain");
     }
     // Flow fields on that build (vtmc_nav_locate, vtmc_navfield_build with _read, vtmc_navfield_trace); below / above in grid units.
+    // The agent radius on that build (vtmc_nav_distance_build with _read; vtmc_nav_erode with vtmc_nav_read and _erode_origin); radius in columns.
+    virtual void NavDistance(int, bool, std::vector<int> &) { throw std::logic_error("NavDistance unsupported"); }
+    virtual void NavErode(int, bool, NavResult &) { throw std::logic_error("NavErode unsupported"); }
     virtual void NavLocate(const std::vector<Vector3> &, float, float, std::vector<int> &) { throw std::logic_error("NavLocate unsupported"); }
     virtual void NavField(const std::vector<NavGoal> &, float, float, unsigned, std::vector<NavFieldCell> &) { throw std::logic_error("NavField unsupported"); }
     virtual void NavTrace(const std::vector<int> &, int, NavPaths &) { throw std::logic_error("NavTrace unsupported"); }
@@ -491,15 +495,25 @@ public:
     // New: where something can walk, and which places are connected (device-resident terrains).  Builds the walkable spans, their links
     // and regions for the box and changes nothing; agentHeight and maxStep are in world units (ceil(agentHeight / _voxelScale) samples of
     // headroom, maxStep / _voxelScale grid units between neighbour columns).  The result is a snapshot: after an edit, build the edit's
-    // box plus a margin again.  No agent radius, no slope by normal, no stitching across boxes; the path search is BuildNavField below.
+    // box plus a margin again.  No agent radius in the build itself (ErodeNav below), no slope by normal, no stitching across boxes; the
+    // path search is BuildNavField below.
     NavResult BuildNav(const Vector3 &lower, const Vector3 &upper, float agentHeight, float maxStep, int maxSpans = 1 << 24);
+
+    // New: where THIS agent can walk (include/vtmc_naverode.h, where the rule is).  On the last BuildNav: NavDistance gives every span's
+    // distance to the nearest border of the walkable area (a span with a missing link) in half columns, capped at twice the radius, and
+    // leaves the result as it is; ErodeNav replaces it by the spans an agent of that radius can occupy (links remapped, regions labelled
+    // again) and returns them with _origin, every kept span's index before the call.  LocateOnNav, BuildNavField and TracePaths then work
+    // on the eroded spans.  radius is in world units, ceil(radius / _voxelScale) columns; with openBoxFaces the box's own faces are no
+    // borders.  ErodeNav drops the field and the distances; the next BuildNav drops all of it; an edit drops nothing.
+    std::vector<int> NavDistance(float radius, bool openBoxFaces = false);
+    NavResult ErodeNav(float radius, bool openBoxFaces = false);
 
     // New: how to get there.  On the last BuildNav: LocateOnNav gives the span each world position stands on (the nearest span of its
     // column within `below` under and `above` over it, world units; -1: none); BuildNavField every span's cheapest cost to the nearest
     // goal and the span to step to next (a level step costs 1024; climbCost / dropCost, 0..1024, are added per grid unit of height
     // climbed / dropped; a span beyond maxCost is unreached); TracePaths the spans an agent visits from each start by following next, at
     // most maxLen of them.  One field serves any number of agents.  The next BuildNav drops the field; an edit does not.  No agent
-    // radius, no any-angle smoothing, no field across two boxes.
+    // radius of its own (ErodeNav first), no any-angle smoothing, no field across two boxes.
     std::vector<int> LocateOnNav(const std::vector<Vector3> &positions, float below, float above);
     std::vector<NavFieldCell> BuildNavField(const std::vector<NavGoal> &goals, float climbCost, float dropCost, unsigned maxCost = 0x7fffffffu);
     NavPaths TracePaths(const std::vector<int> &starts, int maxLen);

@@ -35,12 +35,13 @@
  *              not be symmetric (the nearest span of the neighbour column may have a nearer one of its own).
  *   Region     the components of the undirected graph whose edges are the links, taken in either direction.  region is the smallest span
  *              index of the component.
- * OUT OF SCOPE, deliberately, and left to the host: no agent-radius erosion; no slope test by normal (slope is limited through max_step,
- * the largest height difference between neighbour columns); no stitching of the results of two boxes.  Path search is not here either but
- * in a layer of its own on top of this one: vtmc_navfield.h (locate, cost field, traced paths; PATHFINDING.md).
+ * OUT OF SCOPE, deliberately: no agent-radius erosion in the build itself (a layer of its own on top of this one does it on the device:
+ * vtmc_naverode.h, border distance and span erosion; NAVEROSION.md); no slope test by normal (slope is limited through max_step, the
+ * largest height difference between neighbour columns); no stitching of the results of two boxes.  Path search is not here either but in
+ * a layer of its own on top of this one: vtmc_navfield.h (locate, cost field, traced paths; PATHFINDING.md).
  *
  * Life cycle.  The buffers are library-owned and grow-only, valid until the next vtmc_terrain_nav_build, vtmc_terrain_init,
- * vtmc_terrain_load or vtmc_destroy.  The result is a snapshot of the grid at build time: later edits do not invalidate it (rebuild the
+ * vtmc_terrain_load or vtmc_destroy, or until a vtmc_nav_erode (vtmc_naverode.h), which replaces the result held by its erosion.  The result is a snapshot of the grid at build time: later edits do not invalidate it (rebuild the
  * box an edit touched, plus a margin of a column and agent_height samples).  The build changes nothing else: not the grid, the history,
  * the event counter, the dirty list, the extract result the context holds, the materials, the occlusion bytes or the scatter instances.
  * It waits for work queued on the context's stream, as vtmc_terrain_fragments does.
@@ -54,7 +55,8 @@
  *   VTMC_ERR_DEVICE        ("labelling did not converge") should the region pass ever break its own bounds; no result is left.
  * vtmc_nav_read            copies the spans and (when not NULL) the dx * dz + 1 offsets; VTMC_ERR_CAPACITY when capacity is below the total.
  * vtmc_nav_info            the box (first grid sample, samples per axis) and the total of the result held; each may be NULL.
- * vtmc_nav_device_results  the device pointers of the same; each may be NULL.
+ * vtmc_nav_device_results  the device pointers of the same; each may be NULL.  They change with every build and with every
+ *                          vtmc_nav_erode: ask again after either.
  * The last three answer VTMC_ERR_NO_RESULT before a build.
  */
 #ifndef VTMC_NAV_H

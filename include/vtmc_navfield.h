@@ -34,7 +34,7 @@
  *   Trace      for start i: paths[i * max_len + 0] = start, then next, next ... until a span whose next is -1 or until max_len entries;
  *              lengths[i] is the number of entries written and the rest of the row is -1.  A start of -1 (a locate miss) or an unreached
  *              start gives length 0 and a row of -1.
- * OUT OF SCOPE, deliberately, and left to the host: no agent radius (the spans are not eroded); no any-angle smoothing (a path moves
+ * OUT OF SCOPE, deliberately: no agent radius here (erode the spans first: vtmc_naverode.h); no any-angle smoothing (a path moves
  * from column to neighbour column); no field across the results of two boxes.
  *
  * Life cycle.  The field belongs to the nav result it was built on: vtmc_terrain_nav_build drops it (also a build that fails after it

@@ -11,19 +11,21 @@ import os
 import sys
 
 from . import build as _build
-from ._header import HEADER as _H, NAV_HEADER as _N, NAVFIELD_HEADER as _F
+from ._header import HEADER as _H, NAV_HEADER as _N, NAVFIELD_HEADER as _F, NAVERODE_HEADER as _E
 
 # every #define VTMC_<NAME> of the header as <NAME>: OK and the ERR_* codes, FLAG_*, OUTPUT_*, MOD_*, TERRAIN_SAVE_EXACT,
 # TERRAIN_LOAD_NO_EXTRACT, MESH_*, MATERIAL_*, AO_*, SCATTER_*, LOD_MAX_LEVEL, RAY_TWO_SIDED, SPHERE_MAX_RADIUS_CELLS, COMM_ID_BYTES ...
 globals().update((name[len("VTMC_"):], value) for name, value in _H.constants.items())
 globals().update((name[len("VTMC_"):], value) for name, value in _N.constants.items())   # include/vtmc_nav.h: NAV_OPEN, NAV_MAX_AGENT_HEIGHT
 globals().update((name[len("VTMC_"):], value) for name, value in _F.constants.items())   # include/vtmc_navfield.h: NAVFIELD_UNIT, NAVFIELD_UNREACHED, NAVFIELD_MAX_GOALS
+globals().update((name[len("VTMC_"):], value) for name, value in _E.constants.items())   # include/vtmc_naverode.h: NAVERODE_UNIT, NAVERODE_MAX_RADIUS, NAVERODE_OPEN_BOX_FACES
 STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27   # vtmc_stamp_create: the limits of a stamp's dims (the header states them in prose)
 PATH_CHUNK, PATH_MAX_SEGMENTS = 256, 65536   # csrc/terrain_path.h: segments a workgroup prunes at a time; the most a modifier may hold
 
 SYMBOLS = list(_H.prototypes)   # every symbol include/vtmc.h declares (tests/test_abi_symbols.py finds them with a regex of its own)
 NAV_SYMBOLS = list(_N.prototypes)   # every symbol include/vtmc_nav.h declares
 NAVFIELD_SYMBOLS = list(_F.prototypes)   # every symbol include/vtmc_navfield.h declares
+NAVERODE_SYMBOLS = list(_E.prototypes)   # every symbol include/vtmc_naverode.h declares
 
 # the wire record (CSTriangle.stride = 76, VoxelTerrain.cs:36) under the short names the package uses
 TRI_DTYPE = _H.dtype("vtmc_triangle", ("p0", "p1", "p2", "n0", "n1", "n2", "block"))
@@ -49,6 +51,7 @@ Fragment = _H.structure("vtmc_fragment", "Fragment", """vtmc_fragment: seed (the
 NavParamsStruct = _N.structure("vtmc_nav_params", "NavParamsStruct", "vtmc_nav_params: agent_height in samples, max_step in grid units, max_spans > 0, flags 0.")
 NavSpan = _N.structure("vtmc_nav_span", "NavSpan", "vtmc_nav_span: floor height (grid units), floor sample y, clearance, four links, region.")
 NavFieldParamsStruct = _F.structure("vtmc_navfield_params", "NavFieldParamsStruct", "vtmc_navfield_params: climb and drop cost per grid unit in [0, 1024], max_cost 1..0x7fffffff, flags 0.")
+NavErodeParamsStruct = _E.structure("vtmc_naverode_params", "NavErodeParamsStruct", "vtmc_naverode_params: radius in columns, 0..NAVERODE_MAX_RADIUS, flags NAVERODE_OPEN_BOX_FACES or 0, two reserved words, 0.")
 LodNode = _H.structure("vtmc_lod_node", "LodNode", "vtmc_lod_node: cell origin (multiples of 8 * 2^level) and level of one node of a level-of-detail extract.")
 VolumeBatch = _H.structure("vtmc_volume_batch", "VolumeBatch")
 ChunkView = _H.structure("vtmc_chunk_view", "ChunkView", "vtmc_chunk_view: device pointers into an uploaded chunk-file image.")
@@ -63,6 +66,7 @@ DEBUG_ARGTYPES = {   # entry points that are deliberately not in the header; all
     "vtmc_debug_nav_ms": [_vp, _P(ctypes.c_float * 8)],             # device time of the last nav build's seven stages, and its rounds
     "vtmc_debug_nav_box_read_ms": [_vp, _vp, _vp, _i32, _P(ctypes.c_float)],   # device time of a plain read of a box in the nav walk's layout
     "vtmc_debug_navfield_ms": [_vp, _P(ctypes.c_float * 4)],        # device time of the last field build's three stages, and its rounds
+    "vtmc_debug_naverode_ms": [_vp, _P(ctypes.c_float * 5)],        # device time of the last distance build's or erode's four stages, and its rounds
 }
 
 
@@ -93,7 +97,7 @@ def load(path=None):
         except Exception:
             pass
     L = ctypes.CDLL(path)
-    signatures = [(p.name, p.restype, p.argtypes) for h in (_H, _N, _F) for p in h.prototypes.values()] + [(n, _i32, a) for n, a in DEBUG_ARGTYPES.items()]
+    signatures = [(p.name, p.restype, p.argtypes) for h in (_H, _N, _F, _E) for p in h.prototypes.values()] + [(n, _i32, a) for n, a in DEBUG_ARGTYPES.items()]
     for name, restype, argtypes in signatures:
         if explicit and not hasattr(L, name):   # an older build loaded beside the product's (A/B tools) may lack the newest entry points;
             continue                            # in the product's own library a missing name is an error

@@ -17,7 +17,8 @@
 //   5. nav_union_kernel, nav_flatten_kernel, nav_verify_kernel   union-find over the span indices through the links (union_find.h, shared
 //      with the fragment labelling: union by smaller index, bounded loops, a flag word), then every span to its root: the smallest index
 //      of its component; then the regions are checked against their definition (no link crosses two regions), and the three passes run
-//      again while the check fails.  A link that is answered by the span at its other end is one union, made by the upper span.
+//      again while the check fails (nav_label_regions, which the erosion of terrain_naverode.hip calls on the spans it kept).  A link that is
+//      answered by the span at its other end is one union, made by the upper span.
 // Every random-access read is bounded by the box or the span count and every loop by a count.
 // Traffic that must reach HBM: the box twice (the emit walk skips only whole waves of empty columns), 8 bytes per column, and per span
 // 32 bytes written, read by its four neighbours' lanes and written again twice (links, region), plus 8 bytes of scratch.
@@ -212,6 +213,45 @@ __global__ __launch_bounds__(256) void nav_verify_kernel(const vtmc_nav_span *__
     if (m && __lane_id() == 0) atomicAdd(split, __popcll(m));
 }
 
+// column_offsets of a scanned layout whose tiles are the columns (vtmc_ctx.h: terrain_naverode.hip compacts with it too)
+hipError_t nav_launch_offsets(const ScanLayout &scan, int32_t *offsets, hipStream_t stream)
+{
+    const uint32_t columns = (uint32_t)scan.n_tiles;
+    return launch(nav_offsets_kernel, lanes256((int64_t)columns + 1), dim3(256), 0, stream, scan.tile_offsets(), scan.group_offsets(), scan.total(), columns, offsets);
+}
+
+// Pass 5 over n > 0 spans whose links are final and whose parent words are their own indices (vtmc_ctx.h: the build, and the erosion of
+// terrain_naverode.hip on the spans it kept).  Regions: union, flatten, verify -- and again while the verify pass still finds a link across
+// two regions.  The union pass was seen to lose a union now and then under contention (a few per million on an MI355X, profiles/r21/nav);
+// a repeat only has those few to make, and the result that is kept has passed the check.  With `timed` the nav clock's events 5..8 time
+// the first round.  Uses the control words of the nav build; *rounds is the number of rounds taken.
+int nav_label_regions(vtmc_ctx *ctx, const char *who, vtmc_nav_span *spans, int32_t *parent, int32_t n, bool timed, int *rounds)
+{
+    hipStream_t s = ctx->stream;
+    StageClock<9> &clock = ctx->nav_clock;
+    int *flag = (int *)ctx->nav.ctl.p;
+    int h_ctl[kNavCtlWords] = {0, 0};
+    *rounds = 0;
+    for (int round = 0;; ++round) {
+        const bool mark = timed && round == 0;
+        if (mark) VTMC_HIP(ctx, clock.mark(5, s));
+        VTMC_HIP(ctx, launch(nav_union_kernel, lanes256(n), dim3(256), 0, s, spans, parent, flag, n));
+        if (mark) VTMC_HIP(ctx, clock.mark(6, s));
+        VTMC_HIP(ctx, launch(nav_flatten_kernel, lanes256(n), dim3(256), 0, s, spans, parent, flag, n));
+        if (mark) VTMC_HIP(ctx, clock.mark(7, s));
+        VTMC_HIP(ctx, hipMemsetAsync(flag + kNavCtlSplit, 0, sizeof(int), s));
+        VTMC_HIP(ctx, launch(nav_verify_kernel, lanes256(n), dim3(256), 0, s, spans, flag + kNavCtlSplit, n));
+        if (mark) VTMC_HIP(ctx, clock.mark(8, s));
+        VTMC_HIP(ctx, hipMemcpyAsync(h_ctl, flag, sizeof h_ctl, hipMemcpyDeviceToHost, s));
+        VTMC_HIP(ctx, hipStreamSynchronize(s));
+        *rounds = round + 1;
+        if (h_ctl[kNavCtlFlag]) return fail(ctx, VTMC_ERR_DEVICE, "%s: labelling did not converge (flag %d)", who, h_ctl[kNavCtlFlag]);
+        if (h_ctl[kNavCtlSplit] == 0) return VTMC_OK;
+        if (round + 1 == kNavMaxRounds)
+            return fail(ctx, VTMC_ERR_DEVICE, "%s: labelling did not converge (%d spans across regions after %d rounds)", who, h_ctl[kNavCtlSplit], kNavMaxRounds);
+    }
+}
+
 static dim3 walk_grid(const TerrainBox &b) { return dim3((unsigned)((b.dx + 63) / 64), (unsigned)((b.dz + 3) / 4)); }   // nav_walk_kernel, nav_read_kernel
 
 }  // namespace vtmc
@@ -258,8 +298,7 @@ int32_t vtmc_terrain_nav_build(vtmc_ctx *ctx, const float lower[3], const float 
                              nullptr, nullptr, 0));
         VTMC_HIP(ctx, clock.mark(1, s));
         VTMC_HIP(ctx, launch_scan(scan, s));
-        VTMC_HIP(ctx, launch(nav_offsets_kernel, lanes256((int64_t)columns + 1), dim3(256), 0, s, scan.tile_offsets(), scan.group_offsets(), scan.total(), columns,
-                             offsets));
+        VTMC_HIP(ctx, nav_launch_offsets(scan, offsets, s));
         VTMC_HIP(ctx, clock.mark(2, s));
         VTMC_HIP(ctx, hipMemcpyAsync(&total, scan.total(), sizeof(total), hipMemcpyDeviceToHost, s));
         VTMC_HIP(ctx, hipStreamSynchronize(s));
@@ -276,30 +315,11 @@ int32_t vtmc_terrain_nav_build(vtmc_ctx *ctx, const float lower[3], const float 
         if (n > 0) VTMC_HIP(ctx, launch(nav_walk_kernel<true>, walk, dim3(64, 4, 1), 0, s, grid, sh, tb, (int)params->agent_height, nullptr, offsets, spans, col_of, parent, n));
         VTMC_HIP(ctx, clock.mark(4, s));
         if (n > 0) VTMC_HIP(ctx, launch(nav_link_kernel, lanes256(n), dim3(256), 0, s, spans, col_of, offsets, flag, tb, n, (int)params->agent_height, params->max_step));
-        // Regions: union, flatten, verify -- and again while the verify pass still finds a link across two regions.  The union pass was
-        // seen to lose a union now and then under contention (a few per million on an MI355X, profiles/r21/nav); a repeat only has those
-        // few to make, and the result that is kept has passed the check.  The events time the first round.
-        int h_ctl[kNavCtlWords] = {0, 0};
         nav.rounds = 0;
-        for (int round = 0; n > 0; ++round) {
-            const bool timed = round == 0;
-            if (timed) VTMC_HIP(ctx, clock.mark(5, s));
-            VTMC_HIP(ctx, launch(nav_union_kernel, lanes256(n), dim3(256), 0, s, spans, parent, flag, n));
-            if (timed) VTMC_HIP(ctx, clock.mark(6, s));
-            VTMC_HIP(ctx, launch(nav_flatten_kernel, lanes256(n), dim3(256), 0, s, spans, parent, flag, n));
-            if (timed) VTMC_HIP(ctx, clock.mark(7, s));
-            VTMC_HIP(ctx, hipMemsetAsync(flag + kNavCtlSplit, 0, sizeof(int), s));
-            VTMC_HIP(ctx, launch(nav_verify_kernel, lanes256(n), dim3(256), 0, s, spans, flag + kNavCtlSplit, n));
-            if (timed) VTMC_HIP(ctx, clock.mark(8, s));
-            VTMC_HIP(ctx, hipMemcpyAsync(h_ctl, flag, sizeof h_ctl, hipMemcpyDeviceToHost, s));
-            VTMC_HIP(ctx, hipStreamSynchronize(s));
-            nav.rounds = round + 1;
-            if (h_ctl[kNavCtlFlag]) return fail(ctx, VTMC_ERR_DEVICE, "terrain_nav_build: labelling did not converge (flag %d)", h_ctl[kNavCtlFlag]);
-            if (h_ctl[kNavCtlSplit] == 0) break;
-            if (round + 1 == kNavMaxRounds)
-                return fail(ctx, VTMC_ERR_DEVICE, "terrain_nav_build: labelling did not converge (%d spans across regions after %d rounds)", h_ctl[kNavCtlSplit], kNavMaxRounds);
+        if (n > 0) {
+            if (int rc = nav_label_regions(ctx, "terrain_nav_build", spans, parent, n, true, &nav.rounds)) return rc;
+            clock.arm();
         }
-        if (n > 0) clock.arm();
     }
     VTMC_HIP(ctx, hipStreamSynchronize(s));
     nav.n = (int32_t)total;

@@ -5,6 +5,7 @@
 #define VTMC_CTX_H
 #include "../../include/vtmc.h"
 #include "vtmc_internal.h"
+struct vtmc_nav_span;   // include/vtmc_nav.h
 
 #include <deque>
 #include <map>
@@ -138,6 +139,7 @@ struct VtmcScatter {
 // and the verify pass's count.
 struct VtmcNav {
     VtmcDevBuf spans, offsets, scan, scratch, ctl;
+    VtmcDevBuf spans_next, offsets_next;           // what vtmc_nav_erode writes its result into before it swaps them with spans / offsets
     bool valid = false;
     int32_t n = 0;
     int32_t lo[3] = {0, 0, 0}, d[3] = {0, 0, 0};   // the box as reported: first sample, samples per axis
@@ -151,6 +153,17 @@ struct VtmcNavField {
     VtmcDevBuf cells, work, ctl;
     bool valid = false;
     int32_t n = 0, reached = 0, rounds = 0;
+};
+
+// The agent radius on the nav result above (terrain_naverode.hip): library-owned, grow-only.  state: two arrays of 8-byte state words, a
+// round reads one and writes the other; links: the four links of every span, packed; dist: the distances of vtmc_nav_distance_build, which
+// describe the nav result they were built on and are dropped when an erode replaces it; remap: the old-to-new index words of an erode;
+// origin: its result beside the spans, valid until the next erode or nav build; ctl: the border count.
+struct VtmcNavErode {
+    VtmcDevBuf state, links, dist, remap, origin, ctl;
+    bool dist_valid = false, origin_valid = false;
+    int32_t dist_n = 0, origin_n = 0;
+    int32_t rounds = 0;        // of the last distance pass
 };
 
 // An extract that has been queued on a stream and not yet completed by extract_finish().
@@ -246,6 +259,10 @@ struct vtmc_ctx {
     // terrain_navfield.hip: the flow field on that build and the clock of its kernels (edge costs and goals, relaxation, next)
     VtmcNavField navfield;
     vtmc::StageClock<4> navfield_clock;
+    // terrain_naverode.hip: the distance to the border and the origin of an erosion of that build, and the clock of its kernels (border
+    // test, rounds, compaction, relabelling)
+    VtmcNavErode naverode;
+    vtmc::StageClock<5> naverode_clock;
     // terrain_lod.hip: the node list of the last level-of-detail result (host, and the copy the gather kernel reads), the packed
     // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the clock around
     // the gather launch of the last extract that succeeded (vtmc_debug_lod_gather_ms)
@@ -301,8 +318,9 @@ int check_dims(vtmc_ctx *ctx, int nx, int ny, int nz);
 BlockSpace dense_space(const float *d_base, int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz, int n_volumes, int64_t sv);
 float *pinned_stage(vtmc_ctx *ctx, size_t bytes);   // the pinned stage of host-gathered data (vtmc_api.hip), grown to `bytes`; null: none to be had, go pageable
 void material_drop(vtmc_ctx *ctx);   // terrain_material.hip: vtmc_terrain_init / _load drop the layer
-// whatever invalidates the nav result drops the flow field built on it: vtmc_terrain_init / _load and every vtmc_terrain_nav_build
-inline void nav_drop(vtmc_ctx *ctx) { ctx->nav.valid = false, ctx->navfield.valid = false; }
+// whatever invalidates the nav result drops what describes it, the flow field, the border distance and the origin of an erosion:
+// vtmc_terrain_init / _load and every vtmc_terrain_nav_build
+inline void nav_drop(vtmc_ctx *ctx) { ctx->nav.valid = false, ctx->navfield.valid = false, ctx->naverode.dist_valid = false, ctx->naverode.origin_valid = false; }
 int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp);   // sp then walks the (bx,by,bz) list
 int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, ResultSource source, int32_t *tri_count);   // queued on the context's stream and finished
 // The vertex attributes of a terrain result (terrain_material.hip, terrain_ao.hip), in vtmc_api.hip.  attr_gate: may `who` compute one for
@@ -314,6 +332,12 @@ int attr_device_results(vtmc_ctx *ctx, const VertexAttr &a, const char *stale, c
 // terrain.hip, for terrain_io.hip
 void history_clear(vtmc_ctx *ctx);
 int terrain_extract_all(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_count);   // extracts every block of the resident terrain, as an update that dirtied all of them
+
+// terrain_nav.hip, for terrain_naverode.hip: column_offsets from a scanned layout whose tiles are the columns, and the region pass over
+// n > 0 spans with final links and parent[i] == i (union, flatten, verify, repeated while the check fails)
+struct ScanLayout;
+hipError_t nav_launch_offsets(const ScanLayout &scan, int32_t *offsets, hipStream_t stream);
+int nav_label_regions(vtmc_ctx *ctx, const char *who, vtmc_nav_span *spans, int32_t *parent, int32_t n, bool timed, int *rounds);
 
 // The one kernel launch of this layer: clears the runtime's sticky error word, launches, and returns what this launch left (the rule of
 // launch_begin / launch_end in vtmc_internal.h, whose own wrappers in the two files of extract kernels keep the hand-written form).

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, NAVFIELD_CELL_DTYPE, NAVFIELD_GOAL_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
-from .modifiers import AmbientOcclusion, LodParams, NavParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
+from .modifiers import AmbientOcclusion, LodParams, NavErodeParams, NavParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
 
 
 def _ptr(a):
@@ -537,6 +537,48 @@ class Extractor:
         paths, lengths = np.full((len(s), max(int(max_len), 0)), -1, np.int32), np.zeros(len(s), np.int32)
         self._check(self._L.vtmc_navfield_trace(self._h, _ptr(s), len(s), int(max_len), _ptr(paths), _ptr(lengths)))
         return paths, lengths
+
+    # -- an agent radius on the navigation build the context holds (include/vtmc_naverode.h) --------------------------
+    def _naverode_struct(self, params):
+        return params.to_struct(self._terrain_placement[1]) if isinstance(params, NavErodeParams) else _struct(params)
+
+    def nav_distance(self, params):
+        """Every span's distance to the nearest border of the nav result held, in half columns and capped at 2 * radius, for a
+        NavErodeParams (world units; or a vtmc_naverode_params struct, in columns).  Returns an int32 array indexed as the spans are; the
+        border spans are those at 0 (with a radius above 0).  The nav result and the flow field stay."""
+        p, n = self._naverode_struct(params), ctypes.c_int32()
+        self._check(self._L.vtmc_nav_distance_build(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return self.nav_distance_read()
+
+    def nav_distance_read(self):
+        """The distances of the last nav_distance."""
+        _, n = self.device_nav_distance()
+        dist = np.zeros(n, np.int32)
+        self._check(self._L.vtmc_nav_distance_read(self._h, _ptr(dist), n))
+        return dist
+
+    def device_nav_distance(self):
+        """(device address of the int32 distances, the number of spans) of the last nav_distance; valid until the next one, the next
+        nav_erode or terrain_nav, terrain_init, terrain_load or close."""
+        p, n = ctypes.c_void_p(), ctypes.c_int32()
+        self._check(self._L.vtmc_nav_distance_device_results(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def nav_erode(self, params):
+        """Replaces the nav result held by the spans an agent of the radius of a NavErodeParams (or a vtmc_naverode_params struct) can
+        occupy.  Returns nav_read() + (origin,): origin[new] is the span's index before the call.  Drops the flow field and the distances;
+        the addresses of device_nav change."""
+        p, n = self._naverode_struct(params), ctypes.c_int32()
+        self._check(self._L.vtmc_nav_erode(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return self.nav_read() + (self.nav_erode_origin(),)
+
+    def nav_erode_origin(self):
+        """origin of the last nav_erode: per span of the nav result held, its index in the result that was eroded."""
+        n = ctypes.c_int32()
+        self._check(self._L.vtmc_nav_info(self._h, None, None, ctypes.byref(n)))
+        origin = np.zeros(n.value, np.int32)
+        self._check(self._L.vtmc_nav_erode_origin(self._h, _ptr(origin), n.value))
+        return origin
 
     # -- material layer: VoxelTerrain.SetControlMap's splat volumes in HBM, paint, and per-vertex weights -------------
     def material_init(self, fineness):

@@ -485,6 +485,30 @@ class NavParams:
         return s
 
 
+class NavErodeParams:
+    """The parameters of Extractor.nav_distance and Extractor.nav_erode in WORLD units: the agent's radius, and whether the faces of the
+    nav box count as open (a box cut out of a larger walkable area does not erode from its own faces).  to_struct(voxel_scale) gives the
+    vtmc_naverode_params of a terrain of that scale: radius = ceil(radius / voxel_scale) columns in float32, as NavParams does for the
+    height (0..NAVERODE_MAX_RADIUS is the library's to refuse); radius 0 stays 0."""
+
+    def __init__(self, radius, open_box_faces=False):
+        with np.errstate(over="ignore"):
+            self._radius = _f(radius)
+        if not np.isfinite(self._radius) or not self._radius >= 0:
+            raise ValueError("nav erode radius must be finite and >= 0")
+        self._open = bool(open_box_faces)
+
+    def to_struct(self, voxel_scale):
+        scale = _f(voxel_scale)
+        with np.errstate(over="ignore"):
+            columns = float(np.ceil(self._radius / scale))
+        if not columns < 2.0 ** 31:
+            raise ValueError("nav erode radius overflows at voxel scale %r" % (voxel_scale,))
+        s = _lib.NavErodeParamsStruct()
+        s.radius, s.flags = int(columns), _lib.NAVERODE_OPEN_BOX_FACES if self._open else 0
+        return s
+
+
 class NavFieldParams:
     """The parameters of Extractor.nav_field: what a unit of height climbed and a unit dropped add to a step's cost, in level steps (a
     level step costs NAVFIELD_UNIT), both in [0, 1024], and the cost beyond which a span counts as unreached.  The costs are dimensionless
