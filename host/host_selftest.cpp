@@ -7,6 +7,7 @@
 //   host_selftest --gpu-nav <out_dir>  the navigation layer of a box of a resident terrain; dumps the spans, the column offsets and the box
 //   host_selftest --gpu-naverode <out_dir>  the agent radius on that build: dumps the distances, then the eroded spans, offsets and origin
 //   host_selftest --gpu-navfield <out_dir>  a flow field on that build: dumps the cells, every span's path and the located goal spans
+//   host_selftest --gpu-navsight <out_dir>  any-angle paths on that field: dumps the hits of a set of pairs and every span's smoothed path
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -371,6 +372,70 @@ static int gpu_navfield_run(const std::string &out)
     return 0;
 }
 
+// the world, the box and the field of --gpu-navfield; the sight of span i towards span (7 i + 3) mod n and towards each of its links, and
+// every span's smoothed path under a cost bound of 0 and under none
+static int gpu_navsight_run(const std::string &out)
+{
+    VoxelTerrain vt;
+    vt._width = 64;
+    vt._elevation = 32;
+    vt._height = 32;
+    vt._voxelScale = 0.5f;
+    vt.TerrainOrigin = Vector3(-3.0f, 1.0f, 2.0f);
+    vt._deviceResident = true;
+    vt._seed = 977;
+    vt.Init();
+    Vector2 lo, up;
+    lo.x = -100; lo.y = -100; up.x = 100; up.y = 100;
+    vt.InsertModifier(std::make_shared<PlaneModifier>(6.3f, lo, up, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(27.5f, 8.0f, 10.0f), 4.25f, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(5.0f, 6.0f, 9.0f), 3.0f, false));
+    vt.Update();
+    const int updateTriangles = vt.LastTriangleCount();
+    const NavResult nav = vt.BuildNav(Vector3(-1.0f, 1.0f, 3.0f), Vector3(14.0f, 15.0f, 16.5f), 0.9f, 0.4f);
+    const std::vector<int> at = vt.LocateOnNav({Vector3(0.0f, 6.3f, 4.0f), Vector3(12.0f, 6.3f, 15.0f)}, 1.0f, 1.0f);
+    if (at.size() != 2 || at[0] < 0 || at[1] < 0) return 7;
+    const int n = (int)nav._spans.size();
+    std::vector<int> from, to;
+    for (int i = 0; i < n; i++) {
+        from.push_back(i), to.push_back((int)((7LL * i + 3) % n));
+        for (int k = 0; k < 4; k++) from.push_back(i), to.push_back(nav._spans[(size_t)i]._link[k]);   // a missing link is a -1: {-1, 0}
+    }
+    const std::vector<NavSightHit> hits = vt.NavSight(from, to);   // needs no field
+    if (hits.size() != from.size()) return 8;
+    for (size_t i = 0; i < hits.size(); i++)
+        if (to[i] < 0 ? hits[i]._last != -1 || hits[i]._steps != 0 : i % 5 != 0 && (hits[i]._last != to[i] || hits[i]._steps != 1)) return 9;   // a linked neighbour is visible in one step
+    vt.BuildNavField({NavGoal{at[0], 0u}, NavGoal{at[1], 3000u}}, 2.0f, 0.5f);
+    std::vector<int> starts(nav._spans.size());
+    for (size_t i = 0; i < starts.size(); i++) starts[i] = (int)i;
+    starts.push_back(-1);
+    const NavPaths bound = vt.SmoothPaths(starts, 64, 64, 0u), any = vt.SmoothPaths(starts, 64);
+    const NavPaths plain = vt.TracePaths(starts, 64);
+    if (bound._lengths.size() != starts.size() || bound._paths.size() != starts.size() * 64 || bound._lengths.back() != 0 || any._lengths.size() != starts.size()) return 10;
+    for (size_t i = 0; i < starts.size(); i++)
+        if (any._lengths[i] > plain._lengths[i] || bound._lengths[i] > plain._lengths[i] || any._paths[i * 64] != plain._paths[i * 64]) return 11;   // waypoints are spans of the trace
+    if (vt.LastTriangleCount() != updateTriangles) return 12;   // what Update left stands
+    std::printf("navsight: spans %d pairs %zu\n", n, hits.size());
+    static_assert(sizeof(NavSightHit) == 8, "dumped as it lies");
+    std::ofstream fh(out + "/navsight_hits.bin", std::ios::binary), fb(out + "/navsight_bound_paths.i32", std::ios::binary),
+        fbl(out + "/navsight_bound_lengths.i32", std::ios::binary), fa(out + "/navsight_any_paths.i32", std::ios::binary),
+        fal(out + "/navsight_any_lengths.i32", std::ios::binary);
+    fh.write(reinterpret_cast<const char *>(hits.data()), (std::streamsize)(hits.size() * sizeof(NavSightHit)));
+    fb.write(reinterpret_cast<const char *>(bound._paths.data()), (std::streamsize)(bound._paths.size() * sizeof(int)));
+    fbl.write(reinterpret_cast<const char *>(bound._lengths.data()), (std::streamsize)(bound._lengths.size() * sizeof(int)));
+    fa.write(reinterpret_cast<const char *>(any._paths.data()), (std::streamsize)(any._paths.size() * sizeof(int)));
+    fal.write(reinterpret_cast<const char *>(any._lengths.data()), (std::streamsize)(any._lengths.size() * sizeof(int)));
+    bool refused = false;   // a look of 0 refuses the call
+    try {
+        vt.SmoothPaths(starts, 64, 0);
+    } catch (const UnityException &) {
+        refused = true;
+    }
+    if (!refused) return 13;
+    std::printf("HOST-NAVSIGHT-OK\n");
+    return 0;
+}
+
 static int gpu_lod_run(const std::string &out)
 {
     VoxelTerrain vt;
@@ -436,10 +501,11 @@ int main(int argc, char **argv)
         if (argc >= 3 && std::string(argv[1]) == "--gpu-nav") return gpu_nav_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-naverode") return gpu_naverode_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-navfield") return gpu_navfield_run(argv[2]);
+        if (argc >= 3 && std::string(argv[1]) == "--gpu-navsight") return gpu_navsight_run(argv[2]);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "exception: %s\n", e.what());
         return 3;
     }
-    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir> | --gpu-resident <out_dir> | --gpu-lod <out_dir> | --gpu-nav <out_dir> | --gpu-naverode <out_dir> | --gpu-navfield <out_dir>\n");
+    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir> | --gpu-resident <out_dir> | --gpu-lod <out_dir> | --gpu-nav <out_dir> | --gpu-naverode <out_dir> | --gpu-navfield <out_dir> | --gpu-navsight <out_dir>\n");
     return 64;
 }

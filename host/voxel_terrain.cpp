@@ -9,6 +9,7 @@
 
 #include "../include/vtmc_navfield.h"   // includes vtmc_nav.h, which includes vtmc.h
 #include "../include/vtmc_naverode.h"
+#include "../include/vtmc_navsight.h"
 
 namespace PGRTerrain {
 
@@ -282,6 +283,25 @@ public:
         if (vtmc_navfield_trace(_ctx, starts.data(), (int32_t)starts.size(), maxLen, out._paths.data(), out._lengths.data()) != VTMC_OK)
             throw UnityException(std::string("vtmc_navfield_trace: ") + vtmc_last_error(_ctx));
     }
+    void NavSight(const std::vector<int> &from, const std::vector<int> &to, std::vector<NavSightHit> &out) override
+    {
+        if (from.size() != to.size()) throw UnityException("NavSight: as many from as to spans");
+        std::vector<vtmc_navsight_hit> hits(from.size());
+        if (vtmc_nav_sight(_ctx, from.data(), to.data(), (int32_t)from.size(), hits.data()) != VTMC_OK)
+            throw UnityException(std::string("vtmc_nav_sight: ") + vtmc_last_error(_ctx));
+        out.clear();
+        for (const vtmc_navsight_hit &h : hits) out.push_back(NavSightHit{h.last, h.steps});
+    }
+    void NavTraceSmooth(const std::vector<int> &starts, int maxLen, int maxLook, unsigned maxExtraCost, NavPaths &out) override
+    {
+        out._maxLen = maxLen;
+        out._paths.assign(starts.size() * (size_t)(maxLen > 0 ? maxLen : 0), -1);
+        out._lengths.assign(starts.size(), 0);
+        vtmc_navsight_params p;
+        p.max_look = maxLook, p.max_extra_cost = maxExtraCost, p.flags = 0, p.reserved = 0;
+        if (vtmc_navfield_trace_smooth(_ctx, starts.data(), (int32_t)starts.size(), maxLen, &p, out._paths.data(), out._lengths.data()) != VTMC_OK)
+            throw UnityException(std::string("vtmc_navfield_trace_smooth: ") + vtmc_last_error(_ctx));
+    }
 
     int MaterialInit(int fineness) override
     {
@@ -469,6 +489,22 @@ NavPaths VoxelTerrain::TracePaths(const std::vector<int> &starts, int maxLen)
     if (!_initialised || !_deviceResident) throw UnityException("TracePaths needs an initialised device-resident terrain");
     NavPaths out;
     _backend->NavTrace(starts, maxLen, out);
+    return out;
+}
+
+std::vector<NavSightHit> VoxelTerrain::NavSight(const std::vector<int> &from, const std::vector<int> &to)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("NavSight needs an initialised device-resident terrain");
+    std::vector<NavSightHit> out;
+    _backend->NavSight(from, to, out);
+    return out;
+}
+
+NavPaths VoxelTerrain::SmoothPaths(const std::vector<int> &starts, int maxLen, int maxLook, unsigned maxExtraCost)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("SmoothPaths needs an initialised device-resident terrain");
+    NavPaths out;
+    _backend->NavTraceSmooth(starts, maxLen, maxLook, maxExtraCost, out);
     return out;
 }
 

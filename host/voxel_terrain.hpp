@@ -341,6 +341,13 @@ struct NavPaths {
     std::vector<int> _paths, _lengths;
     int _maxLen = 0;
 };
+// New (not in the reference): one answer of VoxelTerrain::NavSight (include/vtmc_navsight.h, where the rule is): the span the straight walk
+// from one span towards another ended on and the links it followed; the pair is visible iff _last is the span walked towards.
+constexpr unsigned kNavSightAnyCost = 0xffffffffu;
+struct NavSightHit {
+    int _last;
+    int _steps;
+};
 
 // New (not in the reference, which can only replace a control map whole): one paint stroke on the material layer (vtmc_material_stroke
 // of include/vtmc.h).  Every texel within _radius of _center (world space) is blended towards the one-hot of _channel (0..3: control map
@@ -425,6 +432,9 @@ struct ExtractBackend {
     virtual void NavLocate(const std::vector<Vector3> &, float, float, std::vector<int> &) { throw std::logic_error("NavLocate unsupported"); }
     virtual void NavField(const std::vector<NavGoal> &, float, float, unsigned, std::vector<NavFieldCell> &) { throw std::logic_error("NavField unsupported"); }
     virtual void NavTrace(const std::vector<int> &, int, NavPaths &) { throw std::logic_error("NavTrace unsupported"); }
+    // Any-angle paths on that build and its field (vtmc_nav_sight, vtmc_navfield_trace_smooth).
+    virtual void NavSight(const std::vector<int> &, const std::vector<int> &, std::vector<NavSightHit> &) { throw std::logic_error("NavSight unsupported"); }
+    virtual void NavTraceSmooth(const std::vector<int> &, int, int, unsigned, NavPaths &) { throw std::logic_error("NavTraceSmooth unsupported"); }
 
     // Material layer of a device-resident terrain (vtmc_material_*).  MaterialInit returns the layer's size C = 16 * fineness.
     virtual int MaterialInit(int) { throw std::logic_error("MaterialInit on a backend without a material layer"); }
@@ -517,6 +527,15 @@ public:
     std::vector<int> LocateOnNav(const std::vector<Vector3> &positions, float below, float above);
     std::vector<NavFieldCell> BuildNavField(const std::vector<NavGoal> &goals, float climbCost, float dropCost, unsigned maxCost = 0x7fffffffu);
     NavPaths TracePaths(const std::vector<int> &starts, int maxLen);
+
+    // New: any-angle paths (include/vtmc_navsight.h, where the rule is).  NavSight walks, for every pair, the straight line between the
+    // centres of the two spans' columns over the spans of the last BuildNav or ErodeNav, following links forwards: the pair is visible
+    // iff the hit's _last is `to`; a pair with a -1 gives {-1, 0}.  SmoothPaths is TracePaths with the waypoints only: of the spans that
+    // following next visits, those between which that walk succeeds.  maxLook (1..256) is how many spans ahead of a waypoint are tried;
+    // maxExtraCost what a straight stretch may cost above the field's own path between its ends (kNavSightAnyCost: anything).  Waypoints
+    // are column centres; the only clearance is ErodeNav's radius; greedy, not the globally shortest path.
+    std::vector<NavSightHit> NavSight(const std::vector<int> &from, const std::vector<int> &to);
+    NavPaths SmoothPaths(const std::vector<int> &starts, int maxLen, int maxLook = 64, unsigned maxExtraCost = kNavSightAnyCost);
 
     // -- inspection (tests, callers that consume the meshes) ----------------------------------
     const BlockMesh &Block(int x, int y, int z) const { return _blocks[((size_t)x * (_elevation / blockSize) + y) * (_height / blockSize) + z]; }

@@ -38,7 +38,8 @@
  * OUT OF SCOPE, deliberately: no agent-radius erosion in the build itself (a layer of its own on top of this one does it on the device:
  * vtmc_naverode.h, border distance and span erosion; NAVEROSION.md); no slope test by normal (slope is limited through max_step, the
  * largest height difference between neighbour columns); no stitching of the results of two boxes.  Path search is not here either but in
- * a layer of its own on top of this one: vtmc_navfield.h (locate, cost field, traced paths; PATHFINDING.md).
+ * a layer of its own on top of this one: vtmc_navfield.h (locate, cost field, traced paths; PATHFINDING.md), and on that one
+ * vtmc_navsight.h (line of sight over the spans, smoothed traces; PATHSMOOTHING.md).
  *
  * Life cycle.  The buffers are library-owned and grow-only, valid until the next vtmc_terrain_nav_build, vtmc_terrain_init,
  * vtmc_terrain_load or vtmc_destroy, or until a vtmc_nav_erode (vtmc_naverode.h), which replaces the result held by its erosion.  The result is a snapshot of the grid at build time: later edits do not invalidate it (rebuild the

@@ -1,4 +1,4 @@
-"""Reader of include/vtmc.h, the project's contract, and of the headers of its optional layers (include/vtmc_nav.h, include/vtmc_navfield.h, include/vtmc_naverode.h): their constants,
+"""Reader of include/vtmc.h, the project's contract, and of the headers of its optional layers (include/vtmc_nav.h, include/vtmc_navfield.h, include/vtmc_naverode.h, include/vtmc_navsight.h): their constants,
 structs and prototypes as Python values, so that the ctypes binding (_lib.py) is the headers' by construction.  It knows the forms the header uses and nothing else, and it never skips: whatever it cannot
 read raises HeaderError with the line, so a new form is taught to the reader in the pull request that first writes it."""
 import collections
@@ -14,6 +14,7 @@ PATH = os.path.normpath(os.path.join(_build.CSRC, _build.HEADERS[-1]))
 NAV_PATH = os.path.join(os.path.dirname(PATH), "vtmc_nav.h")   # the navigation layer; includes vtmc.h
 NAVFIELD_PATH = os.path.join(os.path.dirname(PATH), "vtmc_navfield.h")   # flow fields on the navigation layer; includes vtmc_nav.h
 NAVERODE_PATH = os.path.join(os.path.dirname(PATH), "vtmc_naverode.h")   # the agent radius on the navigation layer; includes vtmc_nav.h
+NAVSIGHT_PATH = os.path.join(os.path.dirname(PATH), "vtmc_navsight.h")   # line of sight and smoothed traces; includes vtmc_navfield.h
 
 SCALARS = {"float": (ctypes.c_float, "<f4"), "int32_t": (ctypes.c_int32, "<i4"), "uint32_t": (ctypes.c_uint32, "<u4"),
            "int64_t": (ctypes.c_int64, "<i8"), "uint64_t": (ctypes.c_uint64, "<u8")}
@@ -133,3 +134,4 @@ HEADER = Header()
 NAV_HEADER = Header(NAV_PATH, base=HEADER)
 NAVFIELD_HEADER = Header(NAVFIELD_PATH, base=NAV_HEADER)
 NAVERODE_HEADER = Header(NAVERODE_PATH, base=NAV_HEADER)
+NAVSIGHT_HEADER = Header(NAVSIGHT_PATH, base=NAVFIELD_HEADER)

@@ -11,7 +11,7 @@ import os
 import sys
 
 from . import build as _build
-from ._header import HEADER as _H, NAV_HEADER as _N, NAVFIELD_HEADER as _F, NAVERODE_HEADER as _E
+from ._header import HEADER as _H, NAV_HEADER as _N, NAVFIELD_HEADER as _F, NAVERODE_HEADER as _E, NAVSIGHT_HEADER as _S
 
 # every #define VTMC_<NAME> of the header as <NAME>: OK and the ERR_* codes, FLAG_*, OUTPUT_*, MOD_*, TERRAIN_SAVE_EXACT,
 # TERRAIN_LOAD_NO_EXTRACT, MESH_*, MATERIAL_*, AO_*, SCATTER_*, LOD_MAX_LEVEL, RAY_TWO_SIDED, SPHERE_MAX_RADIUS_CELLS, COMM_ID_BYTES ...
@@ -19,6 +19,7 @@ globals().update((name[len("VTMC_"):], value) for name, value in _H.constants.it
 globals().update((name[len("VTMC_"):], value) for name, value in _N.constants.items())   # include/vtmc_nav.h: NAV_OPEN, NAV_MAX_AGENT_HEIGHT
 globals().update((name[len("VTMC_"):], value) for name, value in _F.constants.items())   # include/vtmc_navfield.h: NAVFIELD_UNIT, NAVFIELD_UNREACHED, NAVFIELD_MAX_GOALS
 globals().update((name[len("VTMC_"):], value) for name, value in _E.constants.items())   # include/vtmc_naverode.h: NAVERODE_UNIT, NAVERODE_MAX_RADIUS, NAVERODE_OPEN_BOX_FACES
+globals().update((name[len("VTMC_"):], value) for name, value in _S.constants.items())   # include/vtmc_navsight.h: NAVSIGHT_MAX_LOOK, NAVSIGHT_ANY_COST
 STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27   # vtmc_stamp_create: the limits of a stamp's dims (the header states them in prose)
 PATH_CHUNK, PATH_MAX_SEGMENTS = 256, 65536   # csrc/terrain_path.h: segments a workgroup prunes at a time; the most a modifier may hold
 
@@ -26,6 +27,7 @@ SYMBOLS = list(_H.prototypes)   # every symbol include/vtmc.h declares (tests/te
 NAV_SYMBOLS = list(_N.prototypes)   # every symbol include/vtmc_nav.h declares
 NAVFIELD_SYMBOLS = list(_F.prototypes)   # every symbol include/vtmc_navfield.h declares
 NAVERODE_SYMBOLS = list(_E.prototypes)   # every symbol include/vtmc_naverode.h declares
+NAVSIGHT_SYMBOLS = list(_S.prototypes)   # every symbol include/vtmc_navsight.h declares
 
 # the wire record (CSTriangle.stride = 76, VoxelTerrain.cs:36) under the short names the package uses
 TRI_DTYPE = _H.dtype("vtmc_triangle", ("p0", "p1", "p2", "n0", "n1", "n2", "block"))
@@ -37,6 +39,7 @@ FRAGMENT_DTYPE = _H.dtype("vtmc_fragment")       # one record of vtmc_terrain_fr
 NAV_SPAN_DTYPE = _N.dtype("vtmc_nav_span")       # one span of vtmc_terrain_nav_build
 NAVFIELD_CELL_DTYPE = _F.dtype("vtmc_navfield_cell")   # one cell of vtmc_navfield_build: cost and next
 NAVFIELD_GOAL_DTYPE = _F.dtype("vtmc_navfield_goal")   # one goal of vtmc_navfield_build: span and cost
+NAVSIGHT_HIT_DTYPE = _S.dtype("vtmc_navsight_hit")     # one answer of vtmc_nav_sight: the span the walk ended on and its steps
 
 Modifier = _H.structure("vtmc_modifier", "Modifier", """vtmc_modifier: one queued TerrainModifier (TerrainModifier.cs:19-33), bounds as the C#
     LowerBound / UpperBound properties return them.""")
@@ -52,6 +55,7 @@ NavParamsStruct = _N.structure("vtmc_nav_params", "NavParamsStruct", "vtmc_nav_p
 NavSpan = _N.structure("vtmc_nav_span", "NavSpan", "vtmc_nav_span: floor height (grid units), floor sample y, clearance, four links, region.")
 NavFieldParamsStruct = _F.structure("vtmc_navfield_params", "NavFieldParamsStruct", "vtmc_navfield_params: climb and drop cost per grid unit in [0, 1024], max_cost 1..0x7fffffff, flags 0.")
 NavErodeParamsStruct = _E.structure("vtmc_naverode_params", "NavErodeParamsStruct", "vtmc_naverode_params: radius in columns, 0..NAVERODE_MAX_RADIUS, flags NAVERODE_OPEN_BOX_FACES or 0, two reserved words, 0.")
+NavSightParamsStruct = _S.structure("vtmc_navsight_params", "NavSightParamsStruct", "vtmc_navsight_params: max_look 1..NAVSIGHT_MAX_LOOK, max_extra_cost or NAVSIGHT_ANY_COST, flags 0, reserved 0.")
 LodNode = _H.structure("vtmc_lod_node", "LodNode", "vtmc_lod_node: cell origin (multiples of 8 * 2^level) and level of one node of a level-of-detail extract.")
 VolumeBatch = _H.structure("vtmc_volume_batch", "VolumeBatch")
 ChunkView = _H.structure("vtmc_chunk_view", "ChunkView", "vtmc_chunk_view: device pointers into an uploaded chunk-file image.")
@@ -67,6 +71,7 @@ DEBUG_ARGTYPES = {   # entry points that are deliberately not in the header; all
     "vtmc_debug_nav_box_read_ms": [_vp, _vp, _vp, _i32, _P(ctypes.c_float)],   # device time of a plain read of a box in the nav walk's layout
     "vtmc_debug_navfield_ms": [_vp, _P(ctypes.c_float * 4)],        # device time of the last field build's three stages, and its rounds
     "vtmc_debug_naverode_ms": [_vp, _P(ctypes.c_float * 5)],        # device time of the last distance build's or erode's four stages, and its rounds
+    "vtmc_debug_navsight_ms": [_vp, _P(ctypes.c_float * 2)],        # device time of the last sight query's or smoothed trace's row fill and kernel
 }
 
 
@@ -97,7 +102,7 @@ def load(path=None):
         except Exception:
             pass
     L = ctypes.CDLL(path)
-    signatures = [(p.name, p.restype, p.argtypes) for h in (_H, _N, _F, _E) for p in h.prototypes.values()] + [(n, _i32, a) for n, a in DEBUG_ARGTYPES.items()]
+    signatures = [(p.name, p.restype, p.argtypes) for h in (_H, _N, _F, _E, _S) for p in h.prototypes.values()] + [(n, _i32, a) for n, a in DEBUG_ARGTYPES.items()]
     for name, restype, argtypes in signatures:
         if explicit and not hasattr(L, name):   # an older build loaded beside the product's (A/B tools) may lack the newest entry points;
             continue                            # in the product's own library a missing name is an error

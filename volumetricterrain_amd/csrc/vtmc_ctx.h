@@ -263,6 +263,10 @@ struct vtmc_ctx {
     // test, rounds, compaction, relabelling)
     VtmcNavErode naverode;
     vtmc::StageClock<5> naverode_clock;
+    // terrain_navsight.hip: the packed links a smoothed trace makes for itself in every call (scratch, grow-only: the layer keeps nothing
+    // of the nav result or the field between calls), and the clock of the last call (the fill of the rows with the packing, the kernel)
+    VtmcDevBuf navsight_links;
+    vtmc::StageClock<3> navsight_clock;
     // terrain_lod.hip: the node list of the last level-of-detail result (host, and the copy the gather kernel reads), the packed
     // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the clock around
     // the gather launch of the last extract that succeeded (vtmc_debug_lod_gather_ms)

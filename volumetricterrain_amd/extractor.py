@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, NAVFIELD_CELL_DTYPE, NAVFIELD_GOAL_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, NAVFIELD_CELL_DTYPE, NAVFIELD_GOAL_DTYPE, NAVSIGHT_HIT_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
 from .modifiers import AmbientOcclusion, LodParams, NavErodeParams, NavParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
 
 
@@ -579,6 +579,28 @@ class Extractor:
         origin = np.zeros(n.value, np.int32)
         self._check(self._L.vtmc_nav_erode_origin(self._h, _ptr(origin), n.value))
         return origin
+
+    # -- any-angle paths on the navigation build and the flow field the context holds (include/vtmc_navsight.h) -------
+    def nav_sight(self, from_spans, to_spans):
+        """The line-of-sight walk of every pair over the spans of the nav result held: a NAVSIGHT_HIT_DTYPE array, `last` the span the
+        walk from from_spans[i] towards to_spans[i] ended on and `steps` the links it followed; the pair is visible iff last == to.  A pair
+        with a -1 gives (-1, 0).  Links are followed forwards: visibility is not symmetric."""
+        a, b = np.ascontiguousarray(from_spans, np.int32).reshape(-1), np.ascontiguousarray(to_spans, np.int32).reshape(-1)
+        if len(a) != len(b):
+            raise ValueError("nav_sight needs as many from as to spans")
+        hits = np.zeros(len(a), NAVSIGHT_HIT_DTYPE)
+        self._check(self._L.vtmc_nav_sight(self._h, _ptr(a), _ptr(b), len(a), _ptr(hits)))
+        return hits
+
+    def nav_trace_smooth(self, starts, max_len, params):
+        """(paths, lengths) as nav_trace gives them, of the waypoints only: of the spans that following `next` visits, those between which
+        the line-of-sight walk succeeds, for a NavSightParams (or a vtmc_navsight_params struct).  A row ends on the span nav_trace's ends
+        on unless it was cut at max_len."""
+        s = np.ascontiguousarray(starts, np.int32).reshape(-1)
+        p = _struct(params)
+        paths, lengths = np.full((len(s), max(int(max_len), 0)), -1, np.int32), np.zeros(len(s), np.int32)
+        self._check(self._L.vtmc_navfield_trace_smooth(self._h, _ptr(s), len(s), int(max_len), ctypes.byref(p), _ptr(paths), _ptr(lengths)))
+        return paths, lengths
 
     # -- material layer: VoxelTerrain.SetControlMap's splat volumes in HBM, paint, and per-vertex weights -------------
     def material_init(self, fineness):

@@ -509,6 +509,24 @@ class NavErodeParams:
         return s
 
 
+class NavSightParams:
+    """The parameters of Extractor.nav_trace_smooth: how many spans ahead of a waypoint are tried as the next one (1..NAVSIGHT_MAX_LOOK is
+    the library's to refuse), and how much a straight stretch may cost above the field's own path between its ends, in the field's cost
+    units; None: any (NAVSIGHT_ANY_COST), the smoothing is geometric only."""
+
+    def __init__(self, max_look=64, max_extra_cost=None):
+        if isinstance(max_look, bool) or int(max_look) != max_look or not -2 ** 31 <= max_look < 2 ** 31:
+            raise ValueError("nav sight max_look must be an integer")
+        if max_extra_cost is not None and (isinstance(max_extra_cost, bool) or int(max_extra_cost) != max_extra_cost or not 0 <= max_extra_cost < _lib.NAVSIGHT_ANY_COST):
+            raise ValueError("nav sight max_extra_cost must be None or an integer in 0..2^32-2")
+        self._look, self._extra = int(max_look), _lib.NAVSIGHT_ANY_COST if max_extra_cost is None else int(max_extra_cost)
+
+    def to_struct(self):
+        s = _lib.NavSightParamsStruct()
+        s.max_look, s.max_extra_cost, s.flags, s.reserved = self._look, self._extra, 0, 0
+        return s
+
+
 class NavFieldParams:
     """The parameters of Extractor.nav_field: what a unit of height climbed and a unit dropped add to a step's cost, in level steps (a
     level step costs NAVFIELD_UNIT), both in [0, 1024], and the cost beyond which a span counts as unreached.  The costs are dimensionless
