@@ -14,8 +14,9 @@ def c_prototypes():
     return {name: (p.ret, p.params) for name, p in _header.HEADER.prototypes.items()}
 
 
-def cs_stubs():
-    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+def cs_stubs(path=os.path.join(ROOT, "INTEGRATION.md")):
+    """{name: (return type, parameter declarations)} of every [DllImport] stub of a document"""
+    text = open(path).read()
     stubs = {}
     for m in re.finditer(r"\[DllImport\([^\]]*\)\]\s*public static extern\s+(\w+)\s+(vtmc_\w+)\s*\((.*?)\)\s*;", text, flags=re.S):
         ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())

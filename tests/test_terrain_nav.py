@@ -2,16 +2,9 @@
 
 The rule (NAVIGATION in include/vtmc_nav.h) is one float32 operation per step and integers otherwise, so the device is compared with
 nav_twin.py for EQUALITY: spans as raw bytes, column_offsets as int32.  There is no tolerance anywhere except in the mesh check.  Fields
-are placed with terrain_write_samples, so every bit is chosen.
-
-The terrain is 72 x 16 x 32 cells = 74 x 18 x 34 samples: a row of columns crosses a 64-lane wave along x and nine workgroup rows along
-z; the same field is run once turned, with 74 samples along z.  The crafted field stands on a flat floor (solid up to sample 2, height
-2.5) and holds what crafted_field() lists; heights are dyadic (a = t, b = t - 1, so a - b = 1 and height = y + t exactly)."""
+are placed with terrain_write_samples, so every bit is chosen.  The fields, boxes and helpers are nav_support.py's; the contract every
+layer's header keeps is tests/test_abi_layers.py's."""
 import ctypes
-import functools
-import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -21,128 +14,19 @@ import volumetricterrain_amd as vt
 from volumetricterrain_amd import _header, _lib
 import nav_twin as twin
 from host_check import run_host_check
+from nav_support import (BOXES, DIMS, ORIGIN, RANDOM_BOXES, SCALE, SEED, assert_same, box_of, column, crafted_field, f32, held, mirror_world, raw_params, terrain,
+                         turned_field, twin_of, world_of)
 from terrain_twin import bits, no_result, sample_range
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-f32 = np.float32
-DIMS, SCALE, ORIGIN, SEED = (72, 16, 32), 0.5, (-3.0, 1.0, 2.0), 99
-AIR, SOLID = f32(-0.5), f32(0.5)
 OPEN = _lib.NAV_OPEN
-ULP4, ULP2 = f32(2.0 ** -21), f32(2.0 ** -22)   # one ulp of a height in [4, 8) and in [2, 4)
 AGENT_HEIGHTS, MAX_STEPS = (1, 3), (0.0, 0.5, 1.0, 2.5)
-
-
-def world_of(sample, origin=ORIGIN, scale=SCALE):
-    """The world position of a sample index triple: exact for these dyadic values, also as float32."""
-    w = tuple(origin[k] + sample[k] * scale for k in range(3))
-    assert all(float(f32(v)) == v for v in w)
-    return w
-
-
-# name -> (lower, upper) in world space
-BOXES = {"far": ((-1e6,) * 3, (1e6,) * 3),                               # clamps to the whole grid
-         "interior": (world_of((5, 1, 3)), world_of((71, 13, 25))),       # 67 x 13 x 23 samples: origin and size no multiples of 64, 8 or 4
-         "outside": ((1000.0,) * 3, (1010.0,) * 3)}                       # wholly outside the grid: 0 spans
-
-
-def floor(g, x, z, y, t=0.5, bottom=0):
-    """Column (x, z): solid from `bottom` up to sample y, whose value is t, with t - 1 above it: a floor of height y + t exactly."""
-    t = f32(t)
-    assert 0 < t <= 1 and f32(t - f32(1)) <= 0 and f32(t - f32(t - f32(1))) == 1
-    g[x, bottom:y, z] = SOLID
-    g[x, y, z] = t
-    g[x, y + 1, z] = f32(t - f32(1))   # t = 1: +0.0f, not solid
-
-
-def roof(g, x, z, y0, y1):
-    g[x, y0:y1 + 1, z] = SOLID
-
-
-@functools.lru_cache(maxsize=None)
-def crafted_field():
-    g = np.full(tuple(d + 2 for d in DIMS), AIR, f32)
-    g[:, 0:3, :] = SOLID                                   # the flat floor: height 2.5, open above
-    # A. staircases along x whose last step is exactly max_step and whose next one is one ulp of the height more
-    floor(g, 4, 3, 2, 1.0), floor(g, 5, 3, 3, 0.5), floor(g, 6, 3, 4, ULP4)            # 2.5 | 3.0, 3.5, 4 + ulp: steps 0.5, 0.5, 0.5 + ulp
-    floor(g, 4, 6, 3, 0.5), floor(g, 5, 6, 4, f32(0.5) + ULP4)                          # 2.5 | 3.5, 4.5 + ulp: steps 1, 1 + ulp
-    floor(g, 4, 9, 4, 1.0), floor(g, 5, 9, 7, f32(0.5) + ULP4)                          # 2.5 | 5.0, 7.5 + ulp: steps 2.5, 2.5 + ulp
-    floor(g, 4, 12, 2, f32(0.5) + ULP2)                                                 # 2.5 | 2.5 + ulp: step 0 + ulp
-    # B. a cave over the flat floor: ceilings that leave 3, 2, 1 and 0 open samples
-    roof(g, 12, 3, 6, 8), roof(g, 13, 3, 5, 8), roof(g, 14, 3, 4, 8), roof(g, 15, 3, 3, 8)
-    # C. three stacked floors: the flat floor, a slab at 6..7 and one at 11..12
-    roof(g, 20, 3, 6, 7), roof(g, 20, 3, 11, 12)
-    # D. a pillar of height 5.5 and, in the column at +x, two spans under and over a gap: at |d| = 2 and 2 (the tie), 1.5 and 2, 2.25 and 1.75
-    for z, (t_low, t_up) in ((3, (0.5, 0.5)), (6, (1.0, 0.5)), (9, (0.25, 0.25))):
-        floor(g, 26, z, 5)
-        floor(g, 27, z, 3, t_low)
-        floor(g, 27, z, 7, t_up, bottom=7)
-    # E. a one-directional link: (32, 3) holds the flat floor under a slab (ceil 6) and the slab's top (6.5); (33, 3) one span at 5.0, whose
-    #    nearest in that column is the slab's top, while the floor under the slab has nothing but it
-    roof(g, 32, 3, 6, 6)
-    floor(g, 33, 3, 4, 1.0)
-    # F. ledges whose common opening with the neighbour is too low although |d| = 1 passes: ceil 4 against height 3.5 (agent_height 1),
-    #    ceil 6 against 3.5 (agent_height 3)
-    roof(g, 38, 3, 4, 5), floor(g, 39, 3, 3)
-    roof(g, 38, 6, 6, 7), floor(g, 39, 6, 3)
-    # G. a floating platform (its own region) and a bridge joining two plateaus (one region through it, across x = 64)
-    g[44:48, 10, 3:6] = SOLID
-    g[52:55, 0:9, 8:13] = SOLID
-    g[63:67, 0:9, 8:13] = SOLID
-    g[55:63, 8, 10] = SOLID
-    # H. a column solid to the top (no floor), and one solid up to sample 13, the interior box's top plane (no floor in that box)
-    g[70, :, 3] = SOLID
-    g[70, 0:14, 6] = SOLID
-    # I. NaN, +0.0f and -0.0f directly above a solid sample, and inside an open run under a roof at 7
-    g[10, 3, 16], g[11, 3, 16], g[12, 3, 16] = f32(np.nan), f32(0.0), f32(-0.0)
-    for x, v in ((13, f32(np.nan)), (14, f32(0.0)), (15, f32(-0.0))):
-        roof(g, x, 16, 7, 7)
-        g[x, 5, 16] = v
-    # J. a = +inf: a NaN height, listed, never linked
-    g[20, 2, 16] = f32(np.inf)
-    g.setflags(write=False)
-    return g
-
-
-@functools.lru_cache(maxsize=None)
-def turned_field():
-    g = np.ascontiguousarray(crafted_field().transpose(2, 1, 0))
-    g.setflags(write=False)
-    return g
-
-
-def box_of(name, dims=DIMS, scale=SCALE, origin=ORIGIN):
-    lower, upper = BOXES[name]
-    m = type("M", (), {"lower": [f32(v) for v in lower], "upper": [f32(v) for v in upper]})
-    low, up, first, ext = sample_range(m, tuple(d + 2 for d in dims), scale, origin)
-    return tuple(first), tuple(ext)
-
-
-@functools.lru_cache(maxsize=None)
-def twin_of(field, box, agent_height, max_step):
-    g = {"crafted": crafted_field, "turned": turned_field}[field]()
-    dims = tuple(d - 2 for d in g.shape)
-    spans, offsets, first, ext = twin.build(g, *box_of(box, dims), agent_height, max_step)
-    spans.setflags(write=False)
-    offsets.setflags(write=False)
-    return spans, offsets, first, ext
-
-
-def raw_params(agent_height=1, max_step=0.5, max_spans=1 << 20, flags=0):
-    return _lib.NavParamsStruct(agent_height, max_step, max_spans, flags)
-
-
-def column(result, x, z):
-    """The spans of grid column (x, z) of a build."""
-    spans, offsets, first, ext = result
-    c = (x - first[0]) + ext[0] * (z - first[2])
-    return spans[offsets[c]:offsets[c + 1]], int(offsets[c])
 
 
 # -- CPU: the header, the mirror, the host half ---------------------------------------------------------------------------------------------
 def test_header_declares_the_layer():
-    N = _header.NAV_HEADER
+    N = _header.LAYERS["nav"]
     assert N.constants == {"VTMC_NAV_OPEN": 0x7fffffff, "VTMC_NAV_MAX_AGENT_HEIGHT": 256} and _lib.NAV_OPEN == 2 ** 31 - 1
-    assert list(N.prototypes) == ["vtmc_terrain_nav_build", "vtmc_nav_read", "vtmc_nav_info", "vtmc_nav_device_results"] == _lib.NAV_SYMBOLS
+    assert list(N.prototypes) == ["vtmc_terrain_nav_build", "vtmc_nav_read", "vtmc_nav_info", "vtmc_nav_device_results"] == _lib.LAYER_SYMBOLS["nav"]
     assert set(N.structs) == {"vtmc_nav_params", "vtmc_nav_span"}
     VP, I32 = ctypes.c_void_p, ctypes.c_int32
     assert N.prototypes["vtmc_terrain_nav_build"].argtypes == [VP] * 5 and N.prototypes["vtmc_nav_read"].argtypes == [VP, VP, I32, VP]
@@ -150,32 +34,18 @@ def test_header_declares_the_layer():
     d = vt.NAV_SPAN_DTYPE
     assert d.itemsize == 32 and d.names == ("height", "y", "clearance", "link", "region")
     assert [d.fields[n][1] for n in d.names] == [0, 4, 8, 12, 28] and d["link"].shape == (4,)
-    text = re.sub(r"/\*.*?\*/", "", open(_header.NAV_PATH).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(vtmc_[a-z_0-9]+)\s*\(", text))) == sorted(_lib.NAV_SYMBOLS)   # as test_abi_symbols.py finds them
-    assert not set(_lib.NAV_SYMBOLS) & set(_lib.SYMBOLS)
-    rule = open(_header.NAV_PATH).read()
+    rule = open(N.path).read()
     for word in ("NAVIGATION", "Floor", "Clearance", "Span", "Link", "Region", "no agent-radius erosion", "no slope test by normal"):
         assert word in rule, word
 
 
 def test_library_exports_the_entry_points_and_refuses_null():
     L = vt.load()
-    for name in _lib.NAV_SYMBOLS + ["vtmc_debug_nav_ms"]:
-        assert hasattr(L, name), name
+    assert hasattr(L, "vtmc_debug_nav_ms")
     lo, up, p, n = (ctypes.c_float * 3)(0, 0, 0), (ctypes.c_float * 3)(1, 1, 1), raw_params(), ctypes.c_int32()
     assert L.vtmc_terrain_nav_build(None, ctypes.byref(lo), ctypes.byref(up), ctypes.byref(p), ctypes.byref(n)) == _lib.ERR_INVALID_ARG
     assert L.vtmc_nav_read(None, None, 0, None) == _lib.ERR_INVALID_ARG and L.vtmc_nav_info(None, None, None, None) == _lib.ERR_INVALID_ARG
     assert L.vtmc_nav_device_results(None, None, None, None) == _lib.ERR_INVALID_ARG
-
-
-def test_the_c_header_compiles_as_pedantic_c(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if not cc:
-        pytest.skip("no host C compiler")
-    src = tmp_path / "nav.c"
-    src.write_text('#include "vtmc_nav.h"\nint main(void) { return sizeof(vtmc_nav_span) == 32 && sizeof(vtmc_nav_params) == 16 ? 0 : 1; }\n')
-    subprocess.run([cc, "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", str(src)],
-                   check=True, capture_output=True, text=True)
 
 
 def test_nav_params_take_world_units():
@@ -201,22 +71,6 @@ def test_world_positions():
 def test_host_check_runs_clean_under_the_host_sanitizers(tmp_path):
     """tools/nav_host_check.cpp: the host half (csrc/terrain_nav.h) as a stand-alone program under ASan and UBSan, on the CPU."""
     run_host_check("nav_host_check", tmp_path)
-
-
-def test_dllimport_stubs_match_the_header():
-    """The [DllImport] stubs of the layer (NAVIGATION.md) against include/vtmc_nav.h, by the rules test_dllimport_stubs.py applies to
-    INTEGRATION.md's against include/vtmc.h."""
-    import test_dllimport_stubs as stubs
-    text = open(os.path.join(ROOT, "NAVIGATION.md")).read()
-    found = {}
-    for m in re.finditer(r"\[DllImport\([^\]]*\)\]\s*public static extern\s+(\w+)\s+(vtmc_\w+)\s*\((.*?)\)\s*;", text, flags=re.S):
-        found[m.group(2)] = (m.group(1), [a.strip() for a in re.split(r",(?![^\[]*\])", " ".join(m.group(3).split()))])
-    assert sorted(found) == sorted(_lib.NAV_SYMBOLS)
-    for name, (ret, params) in found.items():
-        p = _header.NAV_HEADER.prototypes[name]
-        assert ret == "int" and p.ret == "int32_t" and len(params) == len(p.params), name
-        for cs, c in zip(params, p.params):
-            assert stubs.matches(cs, c), (name, cs, c)
 
 
 # -- CPU: the twin against answers stated by hand ---------------------------------------------------------------------------------------------
@@ -291,25 +145,6 @@ def test_twin_reproduces_hand_stated_answers():
 
 
 # -- GPU --------------------------------------------------------------------------------------------------------------------------------------
-def terrain(grid=None, dims=DIMS):
-    ex = vt.Extractor(0)
-    ex.terrain_init(*dims, SCALE, ORIGIN, SEED)
-    if grid is not None:
-        ex.terrain_write_samples(grid)
-    return ex
-
-
-def assert_same(got, want, what):
-    assert got[2] == want[2] and got[3] == want[3], what
-    assert got[1].dtype == np.int32 and np.array_equal(got[1], want[1]), what
-    assert len(got[0]) == len(want[0]), what
-    nan = np.isnan(want[0]["height"])
-    if nan.any():   # the a = +inf span: a NaN-aware equality for its height only
-        assert twin.nan_aware_equal(got[0], want[0]) and twin.same_bytes(got[0][~nan], want[0][~nan]), what
-    else:
-        assert twin.same_bytes(got[0], want[0]), what
-
-
 @pytest.fixture(scope="module")
 def crafted_results():
     out = {}
@@ -341,9 +176,6 @@ def test_gpu_turned_field_equals_the_twin():
     with terrain(turned_field(), dims) as ex:
         for ah, step in ((1, 2.5), (3, 0.5)):
             assert_same(ex.terrain_nav(*BOXES["far"], raw_params(ah, step)), twin_of("turned", "far", ah, step), (ah, step))
-
-
-RANDOM_BOXES = {"whole": ((-1e6,) * 3, (1e6,) * 3), "a": (world_of((5, 0, 3)), world_of((70, 17, 20))), "b": (world_of((9, 2, 7)), world_of((41, 14, 33)))}
 
 
 @pytest.fixture(scope="module")
@@ -431,19 +263,6 @@ def test_gpu_spans_are_vertices_of_the_mesh(random_world):
         worst = max(worst, min(abs(y - float(s["height"])) for y in ys))
     print("worst |vertex - span height| = %.3g grid units over %d spans" % (worst, keep.sum()))
     assert worst <= 1e-5
-
-
-def held(ex, L, h):
-    """Everything the context holds besides the nav result, as bytes."""
-    tris, offs = ex.read_triangles()
-    n = ex.last_counts()[1] * 3
-    mat, ao = np.zeros((n, 8), np.uint8), np.zeros(n, np.uint8)
-    assert L.vtmc_material_read_vertices(h, mat.ctypes.data, n) == 0 and L.vtmc_ao_read_vertices(h, ao.ctypes.data, n) == 0
-    p, o, ni = ex.device_scatter()
-    inst, ioffs = np.zeros(ni, vt.INSTANCE_DTYPE), np.zeros(len(offs), np.int32)
-    assert L.vtmc_scatter_read(h, inst.ctypes.data, ni, ioffs.ctypes.data) == 0
-    return [bits(ex.terrain_read_samples()).tobytes(), ex.terrain_history(), ex.terrain_dirty_blocks().tobytes(), tris.tobytes(), offs.tobytes(),
-            mat.tobytes(), ao.tobytes(), inst.tobytes(), ioffs.tobytes(), (p, o, ni)]
 
 
 @pytest.mark.gpu
@@ -569,10 +388,7 @@ def test_gpu_host_mirror(tmp_path):
     spans = np.fromfile(tmp_path / "nav_spans.bin", vt.NAV_SPAN_DTYPE)
     offsets, box = np.fromfile(tmp_path / "nav_offsets.i32", np.int32), np.fromfile(tmp_path / "nav_box.i32", np.int32)
     with vt.Extractor(0) as ex:
-        ex.terrain_init(64, 32, 32, 0.5, (-3.0, 1.0, 2.0), 977)
-        ex.terrain_update([vt.PlaneModifier(6.3, (-100.0, -100.0), (100.0, 100.0)), vt.SphereModifier((27.5, 8.0, 10.0), 4.25, True),
-                           vt.SphereModifier((5.0, 6.0, 9.0), 3.0, False)])
-        want = ex.terrain_nav((-1.0, 1.0, 3.0), (14.0, 15.0, 16.5), vt.NavParams(0.9, 0.4))
+        want = mirror_world(ex)
     assert len(want[0]) > 100 and tuple(box[:3]) == want[2] and tuple(box[3:]) == want[3]
     assert twin.same_bytes(spans, want[0]) and np.array_equal(offsets, want[1])
 

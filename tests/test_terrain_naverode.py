@@ -2,12 +2,11 @@
 
 The rule (NAVERODE in include/vtmc_naverode.h) is integers only, so the device is compared with naverode_twin.py for EQUALITY: distances
 and origins as int32, spans as the nav tests compare them.  The twin holds the distance in two formulations (Jacobi rounds; settling over
-the reversed steps) and is itself pinned to answers worked out by hand.  Fields, boxes and helpers are test_terrain_nav.py's."""
+the reversed steps) and is itself pinned to answers worked out by hand.  Fields, boxes and helpers are nav_support.py's; the contract every layer's header keeps is
+tests/test_abi_layers.py's."""
 import ctypes
 import functools
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -19,7 +18,8 @@ import nav_twin
 import navfield_twin
 import naverode_twin as twin
 from host_check import run_host_check
-import test_terrain_nav as nav
+import nav_support as nav
+from nav_support import flat_grid, nav_of, world
 from terrain_twin import no_result
 
 ROOT = nav.ROOT
@@ -33,16 +33,6 @@ GPU_RADII = (0, 1, 2, 5)
 
 def raw(radius, flags=0, reserved=(0, 0)):
     return _lib.NavErodeParamsStruct(radius, flags, (ctypes.c_int32 * 2)(*reserved))
-
-
-def flat_grid(dx, dz, dy=6):
-    g = np.full((dx, dy, dz), nav.AIR, f32)
-    g[:, 0:3, :] = nav.SOLID
-    return g
-
-
-def nav_of(g, max_step=0.5):
-    return nav_twin.build(g, (0, 0, 0), g.shape, 1, max_step)
 
 
 def by_column(nav_result, values):
@@ -59,35 +49,30 @@ def assert_eroded(got, want, what):
 
 # -- CPU: the header, the binding, the documents, the host half -----------------------------------------------------------------------------
 def test_header_declares_the_layer():
-    E = _header.NAVERODE_HEADER
+    E = _header.LAYERS["naverode"]
     assert E.constants == {"VTMC_NAVERODE_UNIT": 2, "VTMC_NAVERODE_MAX_RADIUS": 255, "VTMC_NAVERODE_OPEN_BOX_FACES": 1}
     assert (_lib.NAVERODE_UNIT, _lib.NAVERODE_MAX_RADIUS, _lib.NAVERODE_OPEN_BOX_FACES) == (2, 255, 1)
     assert list(E.prototypes) == ["vtmc_nav_distance_build", "vtmc_nav_distance_read", "vtmc_nav_distance_device_results", "vtmc_nav_erode",
-                                  "vtmc_nav_erode_origin"] == _lib.NAVERODE_SYMBOLS
+                                  "vtmc_nav_erode_origin"] == _lib.LAYER_SYMBOLS["naverode"]
     assert set(E.structs) == {"vtmc_naverode_params"}
     VP, I32 = ctypes.c_void_p, ctypes.c_int32
     assert E.prototypes["vtmc_nav_distance_build"].argtypes == [VP, VP, VP] == E.prototypes["vtmc_nav_erode"].argtypes
     assert E.prototypes["vtmc_nav_distance_read"].argtypes == [VP, VP, I32] == E.prototypes["vtmc_nav_erode_origin"].argtypes
-    assert E.prototypes["vtmc_nav_distance_device_results"].argtypes == [VP, VP, VP] and all(p.restype is I32 for p in E.prototypes.values())
+    assert E.prototypes["vtmc_nav_distance_device_results"].argtypes == [VP, VP, VP]
     S = _lib.NavErodeParamsStruct
     assert ctypes.sizeof(S) == 16 and (S.radius.offset, S.flags.offset, S.reserved.offset) == (0, 4, 8)
-    text = re.sub(r"/\*.*?\*/", "", open(_header.NAVERODE_PATH).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(vtmc_[a-z_0-9]+)\s*\(", text))) == sorted(_lib.NAVERODE_SYMBOLS)   # as test_abi_symbols.py finds them
-    assert not set(_lib.NAVERODE_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.NAV_SYMBOLS) | set(_lib.NAVFIELD_SYMBOLS))
-    assert '#include "vtmc_nav.h"' in text
-    rule = open(_header.NAVERODE_PATH).read()
+    rule = open(E.path).read()
     for word in ("NAVERODE", "Border", "Steps", "Distance", "Erosion", "radius - 1 Jacobi rounds", "origin[new] = old index"):
         assert word in rule, word
     # the layers under it point here
-    for path in (_header.NAV_PATH, _header.NAVFIELD_PATH):
+    for path in (_header.LAYERS["nav"].path, _header.LAYERS["navfield"].path):
         assert "vtmc_naverode.h" in open(path).read(), path
 
 
 def test_library_exports_the_entry_points_and_refuses_null():
     """Fails without the layer: the library has no such symbols."""
     L = vt.load()
-    for name in _lib.NAVERODE_SYMBOLS + ["vtmc_debug_naverode_ms"]:
-        assert hasattr(L, name), name
+    assert hasattr(L, "vtmc_debug_naverode_ms")
     p, n, out = raw(1), ctypes.c_int32(), (ctypes.c_int32 * 4)()
     assert L.vtmc_nav_distance_build(None, ctypes.byref(p), ctypes.byref(n)) == _lib.ERR_INVALID_ARG
     assert L.vtmc_nav_distance_read(None, ctypes.byref(out), 4) == _lib.ERR_INVALID_ARG
@@ -95,17 +80,6 @@ def test_library_exports_the_entry_points_and_refuses_null():
     assert L.vtmc_nav_erode(None, ctypes.byref(p), ctypes.byref(n)) == _lib.ERR_INVALID_ARG
     assert L.vtmc_nav_erode_origin(None, ctypes.byref(out), 4) == _lib.ERR_INVALID_ARG
     assert L.vtmc_debug_naverode_ms(None, None) == _lib.ERR_INVALID_ARG
-
-
-def test_the_c_header_compiles_as_pedantic_c(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if not cc:
-        pytest.skip("no host C compiler")
-    src = tmp_path / "naverode.c"
-    src.write_text('#include "vtmc_naverode.h"\nint main(void) { return sizeof(vtmc_naverode_params) == 16 && sizeof(vtmc_nav_span) == 32 && '
-                   'VTMC_NAVERODE_UNIT * VTMC_NAVERODE_MAX_RADIUS == 510 && VTMC_NAVERODE_OPEN_BOX_FACES == 1u ? 0 : 1; }\n')
-    subprocess.run([cc, "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", str(src)],
-                   check=True, capture_output=True, text=True)
 
 
 def test_naverode_params_take_world_units():
@@ -125,23 +99,10 @@ def test_host_check_runs_clean_under_the_host_sanitizers(tmp_path):
     run_host_check("naverode_host_check", tmp_path)
 
 
-def test_dllimport_stubs_match_the_header():
-    """The [DllImport] stubs of the layer (NAVEROSION.md) against include/vtmc_naverode.h, by the rules test_dllimport_stubs.py applies to
-    INTEGRATION.md's against include/vtmc.h."""
-    import test_dllimport_stubs as stubs
+def test_document_states_the_layer():
     text = open(os.path.join(ROOT, "NAVEROSION.md")).read()
-    found = {}
-    for m in re.finditer(r"\[DllImport\([^\]]*\)\]\s*public static extern\s+(\w+)\s+(vtmc_\w+)\s*\((.*?)\)\s*;", text, flags=re.S):
-        found[m.group(2)] = (m.group(1), [a.strip() for a in re.split(r",(?![^\[]*\])", " ".join(m.group(3).split()))])
-    assert sorted(found) == sorted(_lib.NAVERODE_SYMBOLS)
-    for name, (ret, params) in found.items():
-        p = _header.NAVERODE_HEADER.prototypes[name]
-        assert ret == "int" and p.ret == "int32_t" and len(params) == len(p.params), name
-        for cs, c in zip(params, p.params):
-            assert stubs.matches(cs, c), (name, cs, c)
     for word in ("VtmcNavErodeParams", "chamfer", "whole columns", "snapshot", "OPEN_BOX_FACES"):
         assert word in text, word
-    assert "NAVEROSION.md" in open(os.path.join(ROOT, "INTEGRATION.md")).read() and "NAVEROSION.md" in open(os.path.join(ROOT, "README.md")).read()
 
 
 # -- CPU: the twin against answers stated by hand ---------------------------------------------------------------------------------------------
@@ -337,13 +298,6 @@ def test_gpu_large_field_equals_the_twin():
         assert nav_twin.same_bytes(other[3][0], eroded[0]) and np.array_equal(other[3][1], eroded[1]) and np.array_equal(other[3][4], eroded[4])
 
 
-def world(g):
-    """World positions (float32, exact) of grid positions whose halves are float32 numbers."""
-    w = np.asarray(ORIGIN, np.float64) + np.asarray(g, np.float64).reshape(-1, 3) * SCALE
-    assert np.array_equal(w.astype(f32).astype(np.float64), w)
-    return w.astype(f32)
-
-
 @pytest.mark.gpu
 def test_gpu_composition_and_the_layers_above():
     base = nav.twin_of("crafted", "far", 1, 2.5)
@@ -524,10 +478,7 @@ def test_gpu_host_mirror(tmp_path):
     dist, origin = np.fromfile(tmp_path / "naverode_distance.i32", np.int32), np.fromfile(tmp_path / "naverode_origin.i32", np.int32)
     spans, offsets = np.fromfile(tmp_path / "naverode_spans.bin", vt.NAV_SPAN_DTYPE), np.fromfile(tmp_path / "naverode_offsets.i32", np.int32)
     with vt.Extractor(0) as ex:
-        ex.terrain_init(64, 32, 32, 0.5, (-3.0, 1.0, 2.0), 977)
-        ex.terrain_update([vt.PlaneModifier(6.3, (-100.0, -100.0), (100.0, 100.0)), vt.SphereModifier((27.5, 8.0, 10.0), 4.25, True),
-                           vt.SphereModifier((5.0, 6.0, 9.0), 3.0, False)])
-        built = ex.terrain_nav((-1.0, 1.0, 3.0), (14.0, 15.0, 16.5), vt.NavParams(0.9, 0.4))
+        built = nav.mirror_world(ex)
         want_d = ex.nav_distance(vt.NavErodeParams(1.2))
         want = ex.nav_erode(vt.NavErodeParams(0.8, open_box_faces=True))
     assert len(built[0]) > 100 and 0 < len(want[0]) < len(built[0]) and (want_d > 0).any()

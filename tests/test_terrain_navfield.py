@@ -3,12 +3,10 @@
 The rule (NAVFIELD in include/vtmc_navfield.h) is integers, and float32 of one operation per step for the edge costs and the locate, so
 the device is compared with navfield_twin.py for EQUALITY: cells, located spans, paths and lengths as raw bytes.  The twin finds the costs
 with another algorithm (Dijkstra over the reversed links; the device relaxes by pulling along the links), and is itself pinned to answers
-worked out by hand.  Fields, boxes and helpers are test_terrain_nav.py's."""
+worked out by hand.  Fields, boxes and helpers are nav_support.py's; the contract every layer's header keeps is tests/test_abi_layers.py's."""
 import ctypes
 import functools
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -19,7 +17,8 @@ from volumetricterrain_amd import _header, _lib
 import nav_twin
 import navfield_twin as twin
 from host_check import run_host_check
-import test_terrain_nav as nav
+import nav_support as nav
+from nav_support import largest_region, raw_field_params, same_cells, world
 from terrain_twin import no_result
 
 ROOT = nav.ROOT
@@ -30,10 +29,6 @@ NO_CUT, CUT = 0x7fffffff, 40 * 1024          # the cut: 40 level steps, on a flo
 NAV_PARAMS = ((1, 2.5), (3, 0.5))             # (agent_height, max_step) of the nav builds under the fields
 COSTS = ((0.0, 0.0), (1.0, 0.25), (1024.0, 0.0))
 GOAL_COSTS = (0, 5000, 0)                     # floor, plateau, platform
-
-
-def raw_field_params(climb=0.0, drop=0.0, max_cost=NO_CUT, flags=0):
-    return _lib.NavFieldParamsStruct(climb, drop, max_cost, flags)
 
 
 def span_at(result, x, z, height):
@@ -49,10 +44,6 @@ def crafted_goals(result, turned=False):
     return list(zip((at(8, 20, 2.5), at(53, 10, 8.5), at(45, 4, 10.5)), GOAL_COSTS))
 
 
-def same_cells(a, b):
-    return a.dtype == b.dtype == vt.NAVFIELD_CELL_DTYPE and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
 def choices(spans, cells, climb, drop):
     """Per span, how many k explain its cost."""
     cost, link, D = twin.edge_costs(spans, climb, drop), spans["link"].astype(np.int64), cells["cost"].astype(np.int64)
@@ -63,37 +54,31 @@ def choices(spans, cells, climb, drop):
 
 # -- CPU: the header, the binding, the documents, the host half -----------------------------------------------------------------------------
 def test_header_declares_the_layer():
-    F = _header.NAVFIELD_HEADER
+    F = _header.LAYERS["navfield"]
     assert F.constants == {"VTMC_NAVFIELD_UNIT": 1024, "VTMC_NAVFIELD_UNREACHED": 0xffffffff, "VTMC_NAVFIELD_MAX_GOALS": 1 << 20}
     assert (_lib.NAVFIELD_UNIT, _lib.NAVFIELD_UNREACHED, _lib.NAVFIELD_MAX_GOALS) == (1024, 2 ** 32 - 1, 2 ** 20)
     assert list(F.prototypes) == ["vtmc_nav_locate", "vtmc_navfield_build", "vtmc_navfield_read", "vtmc_navfield_info", "vtmc_navfield_device_results",
-                                  "vtmc_navfield_trace"] == _lib.NAVFIELD_SYMBOLS
+                                  "vtmc_navfield_trace"] == _lib.LAYER_SYMBOLS["navfield"]
     assert set(F.structs) == {"vtmc_navfield_params", "vtmc_navfield_goal", "vtmc_navfield_cell"}
     VP, I32, FL = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
     assert F.prototypes["vtmc_nav_locate"].argtypes == [VP, VP, I32, FL, FL, VP] and F.prototypes["vtmc_navfield_build"].argtypes == [VP, VP, I32, VP, VP]
     assert F.prototypes["vtmc_navfield_trace"].argtypes == [VP, VP, I32, I32, VP, VP] and F.prototypes["vtmc_navfield_read"].argtypes == [VP, VP, I32]
-    assert all(p.restype is ctypes.c_int32 for p in F.prototypes.values())
     # struct sizes: 16, 8 and 8
     assert ctypes.sizeof(_lib.NavFieldParamsStruct) == 16 and _lib.NavFieldParamsStruct.flags.offset == 12 and _lib.NavFieldParamsStruct.max_cost.offset == 8
     c, g = vt.NAVFIELD_CELL_DTYPE, vt.NAVFIELD_GOAL_DTYPE
     assert c.itemsize == 8 and c.names == ("cost", "next") and [c.fields[n][1] for n in c.names] == [0, 4] and c["cost"] == np.uint32 and c["next"] == np.int32
     assert g.itemsize == 8 and g.names == ("span", "cost") and [g.fields[n][1] for n in g.names] == [0, 4] and g["span"] == np.int32 and g["cost"] == np.uint32
-    text = re.sub(r"/\*.*?\*/", "", open(_header.NAVFIELD_PATH).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(vtmc_[a-z_0-9]+)\s*\(", text))) == sorted(_lib.NAVFIELD_SYMBOLS)   # as test_abi_symbols.py finds them
-    assert not set(_lib.NAVFIELD_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.NAV_SYMBOLS))
-    assert '#include "vtmc_nav.h"' in text
-    rule = open(_header.NAVFIELD_PATH).read()
+    rule = open(F.path).read()
     for word in ("NAVFIELD", "Edge cost", "Goals", "Cost", "Next", "Cell", "Locate", "Trace", "no agent radius", "no any-angle smoothing", "no field across"):
         assert word in rule, word
     # the navigation layer's own header and document point here and gained nothing
-    assert "vtmc_navfield.h" in open(_header.NAV_PATH).read() and "PATHFINDING.md" in open(os.path.join(ROOT, "NAVIGATION.md")).read()
+    assert "vtmc_navfield.h" in open(_header.LAYERS["nav"].path).read() and "PATHFINDING.md" in open(os.path.join(ROOT, "NAVIGATION.md")).read()
 
 
 def test_library_exports_the_entry_points_and_refuses_null():
     """Fails without the layer: the library has no such symbols."""
     L = vt.load()
-    for name in _lib.NAVFIELD_SYMBOLS + ["vtmc_debug_navfield_ms"]:
-        assert hasattr(L, name), name
+    assert hasattr(L, "vtmc_debug_navfield_ms")
     pos, out, n = (ctypes.c_float * 3)(0, 0, 0), (ctypes.c_int32 * 4)(), ctypes.c_int32()
     goal, p = np.zeros(1, vt.NAVFIELD_GOAL_DTYPE), raw_field_params()
     assert L.vtmc_nav_locate(None, ctypes.byref(pos), 1, 0.5, 0.5, ctypes.byref(out)) == _lib.ERR_INVALID_ARG
@@ -104,34 +89,10 @@ def test_library_exports_the_entry_points_and_refuses_null():
     assert L.vtmc_navfield_trace(None, ctypes.byref(out), 1, 2, ctypes.byref(out), ctypes.byref(n)) == _lib.ERR_INVALID_ARG
 
 
-def test_the_c_header_compiles_as_pedantic_c(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if not cc:
-        pytest.skip("no host C compiler")
-    src = tmp_path / "navfield.c"
-    src.write_text('#include "vtmc_navfield.h"\nint main(void) { return sizeof(vtmc_navfield_params) == 16 && sizeof(vtmc_navfield_goal) == 8 && '
-                   'sizeof(vtmc_navfield_cell) == 8 && sizeof(vtmc_nav_span) == 32 && VTMC_NAVFIELD_UNREACHED == 4294967295u ? 0 : 1; }\n')
-    subprocess.run([cc, "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", str(src)],
-                   check=True, capture_output=True, text=True)
-
-
-def test_dllimport_stubs_match_the_header():
-    """The [DllImport] stubs of the layer (PATHFINDING.md) against include/vtmc_navfield.h, by the rules test_dllimport_stubs.py applies to
-    INTEGRATION.md's against include/vtmc.h."""
-    import test_dllimport_stubs as stubs
+def test_document_states_the_layer():
     text = open(os.path.join(ROOT, "PATHFINDING.md")).read()
-    found = {}
-    for m in re.finditer(r"\[DllImport\([^\]]*\)\]\s*public static extern\s+(\w+)\s+(vtmc_\w+)\s*\((.*?)\)\s*;", text, flags=re.S):
-        found[m.group(2)] = (m.group(1), [a.strip() for a in re.split(r",(?![^\[]*\])", " ".join(m.group(3).split()))])
-    assert sorted(found) == sorted(_lib.NAVFIELD_SYMBOLS)
-    for name, (ret, params) in found.items():
-        p = _header.NAVFIELD_HEADER.prototypes[name]
-        assert ret == "int" and p.ret == "int32_t" and len(params) == len(p.params), name
-        for cs, c in zip(params, p.params):
-            assert stubs.matches(cs, c), (name, cs, c)
     for word in ("VtmcNavFieldParams", "VtmcNavFieldGoal", "VtmcNavFieldCell", "agent radius", "any-angle", "two boxes"):
         assert word in text, word
-    assert "PATHFINDING.md" in open(os.path.join(ROOT, "INTEGRATION.md")).read() and "PATHFINDING.md" in open(os.path.join(ROOT, "README.md")).read()
 
 
 def test_navfield_params_validate():
@@ -307,11 +268,6 @@ def test_gpu_serpentine_converges_in_few_rounds(turned):
     assert rounds * 4 <= L
 
 
-def largest_region(spans):
-    regions, counts = np.unique(spans["region"], return_counts=True)
-    return int(regions[np.argmax(counts)]), regions
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["whole", "b"])
 def test_gpu_random_field_equals_the_twin(name):
@@ -333,14 +289,6 @@ def test_gpu_random_field_equals_the_twin(name):
     assert len(regions) >= 2 and any(not reached[spans["region"] == r].any() for r in regions)   # a region nobody can leave for a goal
     assert reached[spans["region"] == region].any() and n_reached == reached.sum()
     assert same_cells(got, want)
-
-
-def world(g):
-    """World positions (float32, exact) of grid positions whose halves are float32 numbers."""
-    g = np.asarray(g, np.float64).reshape(-1, 3)
-    w = np.asarray(ORIGIN, np.float64) + g * SCALE
-    assert np.array_equal(w.astype(f32).astype(np.float64), w)
-    return w.astype(f32)
 
 
 @pytest.mark.gpu
@@ -622,10 +570,7 @@ def test_gpu_host_mirror(tmp_path):
     paths, lengths = np.fromfile(tmp_path / "navfield_paths.i32", np.int32), np.fromfile(tmp_path / "navfield_lengths.i32", np.int32)
     located = np.fromfile(tmp_path / "navfield_located.i32", np.int32)
     with vt.Extractor(0) as ex:
-        ex.terrain_init(64, 32, 32, 0.5, (-3.0, 1.0, 2.0), 977)
-        ex.terrain_update([vt.PlaneModifier(6.3, (-100.0, -100.0), (100.0, 100.0)), vt.SphereModifier((27.5, 8.0, 10.0), 4.25, True),
-                           vt.SphereModifier((5.0, 6.0, 9.0), 3.0, False)])
-        spans = ex.terrain_nav((-1.0, 1.0, 3.0), (14.0, 15.0, 16.5), vt.NavParams(0.9, 0.4))[0]
+        spans = nav.mirror_world(ex)[0]
         at = ex.nav_locate([(0.0, 6.3, 4.0), (12.0, 6.3, 15.0), (500.0, 6.3, 4.0)], 1.0, 1.0)
         want = ex.nav_field([(at[0], 0), (at[1], 3000)], vt.NavFieldParams(2.0, 0.5))
         want_paths, want_lengths = ex.nav_trace(list(range(len(spans))) + [-1], 64)

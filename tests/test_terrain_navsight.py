@@ -2,12 +2,10 @@
 
 The rule (NAVSIGHT in include/vtmc_navsight.h) is integers only, so the device is compared with navsight_twin.py for EQUALITY: hits as
 bytes, rows and lengths as int32.  The twin is itself pinned to answers worked out by hand.  Fields, boxes and helpers are
-test_terrain_nav.py's; fields of costs are navfield_twin.py's."""
+nav_support.py's; fields of costs are navfield_twin.py's; the contract every layer's header keeps is tests/test_abi_layers.py's."""
 import ctypes
 import functools
 import os
-import re
-import shutil
 import subprocess
 import time
 
@@ -16,13 +14,12 @@ import pytest
 
 import volumetricterrain_amd as vt
 from volumetricterrain_amd import _header, _lib
-import nav_twin
 import navfield_twin
 import naverode_twin
 import navsight_twin as twin
 from host_check import run_host_check
-import test_terrain_nav as nav
-import test_terrain_navfield as navfield
+import nav_support as nav
+from nav_support import flat_grid, nav_of
 from terrain_twin import no_result
 
 ROOT = nav.ROOT
@@ -40,16 +37,6 @@ def raw(look, extra=ANY, flags=0, reserved=0):
     return _lib.NavSightParamsStruct(look, extra, flags, reserved)
 
 
-def flat_grid(dx, dz, dy=6):
-    g = np.full((dx, dy, dz), nav.AIR, f32)
-    g[:, 0:3, :] = nav.SOLID
-    return g
-
-
-def nav_of(g, max_step=0.5):
-    return nav_twin.build(g, (0, 0, 0), g.shape, 1, max_step)
-
-
 def at(r, x, z, floor=0):
     """The index of a span of grid column (x, z), counted from the bottom."""
     spans, first = nav.column(r, x, z)
@@ -59,7 +46,7 @@ def at(r, x, z, floor=0):
 
 def goal_of(spans):
     """One goal: the middle member of the largest region."""
-    region, _ = navfield.largest_region(spans)
+    region, _ = nav.largest_region(spans)
     inside = np.nonzero(spans["region"] == region)[0]
     return int(inside[len(inside) // 2])
 
@@ -92,51 +79,34 @@ def crafted_case(field, box):
 
 # -- CPU: the header, the binding, the documents, the host half -----------------------------------------------------------------------------
 def test_header_declares_the_layer():
-    S = _header.NAVSIGHT_HEADER
+    S = _header.LAYERS["navsight"]
     assert S.constants == {"VTMC_NAVSIGHT_MAX_LOOK": 256, "VTMC_NAVSIGHT_ANY_COST": 0xffffffff}
     assert (_lib.NAVSIGHT_MAX_LOOK, _lib.NAVSIGHT_ANY_COST) == (256, 0xffffffff)
-    assert list(S.prototypes) == ["vtmc_nav_sight", "vtmc_navfield_trace_smooth"] == _lib.NAVSIGHT_SYMBOLS
+    assert list(S.prototypes) == ["vtmc_nav_sight", "vtmc_navfield_trace_smooth"] == _lib.LAYER_SYMBOLS["navsight"]
     assert set(S.structs) == {"vtmc_navsight_params", "vtmc_navsight_hit"}
     VP, I32 = ctypes.c_void_p, ctypes.c_int32
     assert S.prototypes["vtmc_nav_sight"].argtypes == [VP, VP, VP, I32, VP]
-    assert S.prototypes["vtmc_navfield_trace_smooth"].argtypes == [VP, VP, I32, I32, VP, VP, VP] and all(p.restype is I32 for p in S.prototypes.values())
+    assert S.prototypes["vtmc_navfield_trace_smooth"].argtypes == [VP, VP, I32, I32, VP, VP, VP]
     P = _lib.NavSightParamsStruct
     assert ctypes.sizeof(P) == 16 and (P.max_look.offset, P.max_extra_cost.offset, P.flags.offset, P.reserved.offset) == (0, 4, 8, 12)
     H = _lib.NAVSIGHT_HIT_DTYPE
     assert H.itemsize == 8 and H.names == ("last", "steps") and [H.fields[f][1] for f in H.names] == [0, 4] and vt.NAVSIGHT_HIT_DTYPE is H
-    text = re.sub(r"/\*.*?\*/", "", open(_header.NAVSIGHT_PATH).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(vtmc_[a-z_0-9]+)\s*\(", text))) == sorted(_lib.NAVSIGHT_SYMBOLS)   # as test_abi_symbols.py finds them
-    others = set(_lib.SYMBOLS) | set(_lib.NAV_SYMBOLS) | set(_lib.NAVFIELD_SYMBOLS) | set(_lib.NAVERODE_SYMBOLS)
-    assert not set(_lib.NAVSIGHT_SYMBOLS) & others
-    assert '#include "vtmc_navfield.h"' in text
-    rule = open(_header.NAVSIGHT_PATH).read()
+    rule = open(S.path).read()
     for word in ("NAVSIGHT", "Column", "Walk", "Visible", "Sight", "Smoothed trace", "ex == ez", "NOT symmetric", "the LAST chain entry", "in 64 bits"):
         assert word in rule, word
     # the layers under it, and the document that named the gap, point here
-    for path in (_header.NAV_PATH, _header.NAVFIELD_PATH, os.path.join(ROOT, "PATHFINDING.md")):
+    for path in (_header.LAYERS["nav"].path, _header.LAYERS["navfield"].path, os.path.join(ROOT, "PATHFINDING.md")):
         assert "vtmc_navsight.h" in open(path).read() and "PATHSMOOTHING.md" in open(path).read(), path
 
 
 def test_library_exports_the_entry_points_and_refuses_null():
     """Fails without the layer: the library has no such symbols."""
     L = vt.load()
-    for name in _lib.NAVSIGHT_SYMBOLS + ["vtmc_debug_navsight_ms"]:
-        assert hasattr(L, name), name
+    assert hasattr(L, "vtmc_debug_navsight_ms")
     p, spans, hits = raw(64), np.zeros(4, np.int32), np.zeros(4, vt.NAVSIGHT_HIT_DTYPE)
     assert L.vtmc_nav_sight(None, spans.ctypes.data, spans.ctypes.data, 4, hits.ctypes.data) == _lib.ERR_INVALID_ARG
     assert L.vtmc_navfield_trace_smooth(None, spans.ctypes.data, 4, 1, ctypes.byref(p), spans.ctypes.data, spans.ctypes.data) == _lib.ERR_INVALID_ARG
     assert L.vtmc_debug_navsight_ms(None, None) == _lib.ERR_INVALID_ARG
-
-
-def test_the_c_header_compiles_as_pedantic_c(tmp_path):
-    cc = shutil.which("gcc") or shutil.which("cc")
-    if not cc:
-        pytest.skip("no host C compiler")
-    src = tmp_path / "navsight.c"
-    src.write_text('#include "vtmc_navsight.h"\nint main(void) { return sizeof(vtmc_navsight_params) == 16 && sizeof(vtmc_navsight_hit) == 8 && '
-                   'sizeof(vtmc_navfield_cell) == 8 && VTMC_NAVSIGHT_MAX_LOOK == 256 && VTMC_NAVSIGHT_ANY_COST == 0xffffffffu ? 0 : 1; }\n')
-    subprocess.run([cc, "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), "-fsyntax-only", str(src)],
-                   check=True, capture_output=True, text=True)
 
 
 def test_navsight_params():
@@ -156,23 +126,10 @@ def test_host_check_runs_clean_under_the_host_sanitizers(tmp_path):
     run_host_check("navsight_host_check", tmp_path)
 
 
-def test_dllimport_stubs_match_the_header():
-    """The [DllImport] stubs of the layer (PATHSMOOTHING.md) against include/vtmc_navsight.h, by the rules test_dllimport_stubs.py applies
-    to INTEGRATION.md's against include/vtmc.h."""
-    import test_dllimport_stubs as stubs
+def test_document_states_the_layer():
     text = open(os.path.join(ROOT, "PATHSMOOTHING.md")).read()
-    found = {}
-    for m in re.finditer(r"\[DllImport\([^\]]*\)\]\s*public static extern\s+(\w+)\s+(vtmc_\w+)\s*\((.*?)\)\s*;", text, flags=re.S):
-        found[m.group(2)] = (m.group(1), [a.strip() for a in re.split(r",(?![^\[]*\])", " ".join(m.group(3).split()))])
-    assert sorted(found) == sorted(_lib.NAVSIGHT_SYMBOLS)
-    for name, (ret, params) in found.items():
-        p = _header.NAVSIGHT_HEADER.prototypes[name]
-        assert ret == "int" and p.ret == "int32_t" and len(params) == len(p.params), name
-        for cs, c in zip(params, p.params):
-            assert stubs.matches(cs, c), (name, cs, c)
     for word in ("VtmcNavSightParams", "VtmcNavSightHit", "column centres", "greedy", "One box only", "snapshot", "not symmetric"):
         assert word in text, word
-    assert "PATHSMOOTHING.md" in open(os.path.join(ROOT, "INTEGRATION.md")).read() and "PATHSMOOTHING.md" in open(os.path.join(ROOT, "README.md")).read()
 
 
 # -- CPU: the twin against answers stated by hand ---------------------------------------------------------------------------------------------
@@ -628,10 +585,7 @@ def test_gpu_host_mirror(tmp_path):
     hits = np.fromfile(tmp_path / "navsight_hits.bin", vt.NAVSIGHT_HIT_DTYPE)
     files = {k: np.fromfile(tmp_path / ("navsight_%s.i32" % k), np.int32) for k in ("bound_paths", "bound_lengths", "any_paths", "any_lengths")}
     with vt.Extractor(0) as ex:
-        ex.terrain_init(64, 32, 32, 0.5, (-3.0, 1.0, 2.0), 977)
-        ex.terrain_update([vt.PlaneModifier(6.3, (-100.0, -100.0), (100.0, 100.0)), vt.SphereModifier((27.5, 8.0, 10.0), 4.25, True),
-                           vt.SphereModifier((5.0, 6.0, 9.0), 3.0, False)])
-        spans = ex.terrain_nav((-1.0, 1.0, 3.0), (14.0, 15.0, 16.5), vt.NavParams(0.9, 0.4))[0]
+        spans = nav.mirror_world(ex)[0]
         n = len(spans)
         a = np.repeat(np.arange(n, dtype=np.int32), 5)
         b = np.concatenate([((7 * np.arange(n, dtype=np.int64) + 3) % n).astype(np.int32)[:, None], spans["link"]], axis=1).reshape(-1)

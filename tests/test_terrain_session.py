@@ -33,20 +33,20 @@ import volumetricterrain_amd as vt
 from volumetricterrain_amd import _lib, terrainfile as tf
 import ao_twin
 import material_twin
+import nav_support as nav
 import nav_twin
 import navfield_twin
 import path_twin
 import scatter_twin
 import session_twin as st
 import stamp_twin
-import test_terrain_nav as nav
 from extract_checks import ATOL, assert_tris_match
+from nav_support import same_cells
 from session_twin import FACES, FAMILIES, KINDS, SEEDS, History, Session, generate
 from surface_twin import Surface, check_tight, compare as compare_rays, reference as ray_reference
 from terrain_twin import assert_triangles, bits, block_list, box_of, csg_write, gpu_struct, oracle_mod_of
 from test_sphere_queries import SphereSurface, check as check_spheres
 from test_terrain_fragments import same_records
-from test_terrain_navfield import same_cells
 from test_terrain_scatter import assert_instances, mesh_of as scatter_mesh_of
 
 f32 = np.float32

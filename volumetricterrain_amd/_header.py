@@ -1,4 +1,4 @@
-"""Reader of include/vtmc.h, the project's contract, and of the headers of its optional layers (include/vtmc_nav.h, include/vtmc_navfield.h, include/vtmc_naverode.h, include/vtmc_navsight.h): their constants,
+"""Reader of include/vtmc.h, the project's contract, and of the headers of its optional layers (the rows of build.ABI_LAYERS): their constants,
 structs and prototypes as Python values, so that the ctypes binding (_lib.py) is the headers' by construction.  It knows the forms the header uses and nothing else, and it never skips: whatever it cannot
 read raises HeaderError with the line, so a new form is taught to the reader in the pull request that first writes it."""
 import collections
@@ -10,11 +10,7 @@ import numpy as np
 
 from . import build as _build
 
-PATH = os.path.normpath(os.path.join(_build.CSRC, _build.HEADERS[-1]))
-NAV_PATH = os.path.join(os.path.dirname(PATH), "vtmc_nav.h")   # the navigation layer; includes vtmc.h
-NAVFIELD_PATH = os.path.join(os.path.dirname(PATH), "vtmc_navfield.h")   # flow fields on the navigation layer; includes vtmc_nav.h
-NAVERODE_PATH = os.path.join(os.path.dirname(PATH), "vtmc_naverode.h")   # the agent radius on the navigation layer; includes vtmc_nav.h
-NAVSIGHT_PATH = os.path.join(os.path.dirname(PATH), "vtmc_navsight.h")   # line of sight and smoothed traces; includes vtmc_navfield.h
+PATH = os.path.join(_build.INCLUDE, _build.ABI_LAYERS[0][1])   # include/vtmc.h
 
 SCALARS = {"float": (ctypes.c_float, "<f4"), "int32_t": (ctypes.c_int32, "<i4"), "uint32_t": (ctypes.c_uint32, "<u4"),
            "int64_t": (ctypes.c_int64, "<i8"), "uint64_t": (ctypes.c_uint64, "<u8")}
@@ -130,8 +126,15 @@ class Header:
                          "offsets": [getattr(layout, f.name).offset for f in fields], "itemsize": ctypes.sizeof(layout)})
 
 
-HEADER = Header()
-NAV_HEADER = Header(NAV_PATH, base=HEADER)
-NAVFIELD_HEADER = Header(NAVFIELD_PATH, base=NAV_HEADER)
-NAVERODE_HEADER = Header(NAVERODE_PATH, base=NAV_HEADER)
-NAVSIGHT_HEADER = Header(NAVSIGHT_PATH, base=NAVFIELD_HEADER)
+def read_layers(rows=_build.ABI_LAYERS, include=_build.INCLUDE):
+    """name -> Header of every row, in the table's order; a row's base is an earlier row's Header."""
+    layers = {}
+    for name, file, base, _doc in rows:
+        if base is not None and base not in layers:
+            raise HeaderError("ABI layer %r: its base %r is not an earlier row of the table" % (name, base))
+        layers[name] = Header(os.path.join(include, file), base=layers.get(base))
+    return layers
+
+
+LAYERS = read_layers()
+HEADER = LAYERS["core"]

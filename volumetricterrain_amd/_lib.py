@@ -11,55 +11,50 @@ import os
 import sys
 
 from . import build as _build
-from ._header import HEADER as _H, NAV_HEADER as _N, NAVFIELD_HEADER as _F, NAVERODE_HEADER as _E, NAVSIGHT_HEADER as _S
+from ._header import HEADER, LAYERS
 
-# every #define VTMC_<NAME> of the header as <NAME>: OK and the ERR_* codes, FLAG_*, OUTPUT_*, MOD_*, TERRAIN_SAVE_EXACT,
+# every #define VTMC_<NAME> of every layer's header as <NAME>.  include/vtmc.h: OK and the ERR_* codes, FLAG_*, OUTPUT_*, MOD_*, TERRAIN_SAVE_EXACT,
 # TERRAIN_LOAD_NO_EXTRACT, MESH_*, MATERIAL_*, AO_*, SCATTER_*, LOD_MAX_LEVEL, RAY_TWO_SIDED, SPHERE_MAX_RADIUS_CELLS, COMM_ID_BYTES ...
-globals().update((name[len("VTMC_"):], value) for name, value in _H.constants.items())
-globals().update((name[len("VTMC_"):], value) for name, value in _N.constants.items())   # include/vtmc_nav.h: NAV_OPEN, NAV_MAX_AGENT_HEIGHT
-globals().update((name[len("VTMC_"):], value) for name, value in _F.constants.items())   # include/vtmc_navfield.h: NAVFIELD_UNIT, NAVFIELD_UNREACHED, NAVFIELD_MAX_GOALS
-globals().update((name[len("VTMC_"):], value) for name, value in _E.constants.items())   # include/vtmc_naverode.h: NAVERODE_UNIT, NAVERODE_MAX_RADIUS, NAVERODE_OPEN_BOX_FACES
-globals().update((name[len("VTMC_"):], value) for name, value in _S.constants.items())   # include/vtmc_navsight.h: NAVSIGHT_MAX_LOOK, NAVSIGHT_ANY_COST
+# The optional layers' headers: NAV_OPEN, NAVFIELD_UNIT, NAVERODE_MAX_RADIUS, NAVSIGHT_ANY_COST ...
+for _layer in LAYERS.values():
+    globals().update((name[len("VTMC_"):], value) for name, value in _layer.constants.items())
 STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27   # vtmc_stamp_create: the limits of a stamp's dims (the header states them in prose)
 PATH_CHUNK, PATH_MAX_SEGMENTS = 256, 65536   # csrc/terrain_path.h: segments a workgroup prunes at a time; the most a modifier may hold
 
-SYMBOLS = list(_H.prototypes)   # every symbol include/vtmc.h declares (tests/test_abi_symbols.py finds them with a regex of its own)
-NAV_SYMBOLS = list(_N.prototypes)   # every symbol include/vtmc_nav.h declares
-NAVFIELD_SYMBOLS = list(_F.prototypes)   # every symbol include/vtmc_navfield.h declares
-NAVERODE_SYMBOLS = list(_E.prototypes)   # every symbol include/vtmc_naverode.h declares
-NAVSIGHT_SYMBOLS = list(_S.prototypes)   # every symbol include/vtmc_navsight.h declares
+LAYER_SYMBOLS = {name: list(header.prototypes) for name, header in LAYERS.items()}   # per layer, every symbol its header declares
+SYMBOLS = LAYER_SYMBOLS["core"]   # every symbol include/vtmc.h declares (tests/test_abi_symbols.py finds them with a regex of its own)
 
 # the wire record (CSTriangle.stride = 76, VoxelTerrain.cs:36) under the short names the package uses
-TRI_DTYPE = _H.dtype("vtmc_triangle", ("p0", "p1", "p2", "n0", "n1", "n2", "block"))
-VERTEX_DTYPE = _H.dtype("vtmc_vertex")
-RAY_HIT_DTYPE = _H.dtype("vtmc_ray_hit")         # one answer of vtmc_terrain_raycast / vtmc_raycast_device
-SPHERE_HIT_DTYPE = _H.dtype("vtmc_sphere_hit")   # one answer of vtmc_terrain_spherecast / _closest_point and their _device forms
-INSTANCE_DTYPE = _H.dtype("vtmc_instance")       # one instance of vtmc_scatter_surface
-FRAGMENT_DTYPE = _H.dtype("vtmc_fragment")       # one record of vtmc_terrain_fragments
-NAV_SPAN_DTYPE = _N.dtype("vtmc_nav_span")       # one span of vtmc_terrain_nav_build
-NAVFIELD_CELL_DTYPE = _F.dtype("vtmc_navfield_cell")   # one cell of vtmc_navfield_build: cost and next
-NAVFIELD_GOAL_DTYPE = _F.dtype("vtmc_navfield_goal")   # one goal of vtmc_navfield_build: span and cost
-NAVSIGHT_HIT_DTYPE = _S.dtype("vtmc_navsight_hit")     # one answer of vtmc_nav_sight: the span the walk ended on and its steps
+TRI_DTYPE = HEADER.dtype("vtmc_triangle", ("p0", "p1", "p2", "n0", "n1", "n2", "block"))
+VERTEX_DTYPE = HEADER.dtype("vtmc_vertex")
+RAY_HIT_DTYPE = HEADER.dtype("vtmc_ray_hit")         # one answer of vtmc_terrain_raycast / vtmc_raycast_device
+SPHERE_HIT_DTYPE = HEADER.dtype("vtmc_sphere_hit")   # one answer of vtmc_terrain_spherecast / _closest_point and their _device forms
+INSTANCE_DTYPE = HEADER.dtype("vtmc_instance")       # one instance of vtmc_scatter_surface
+FRAGMENT_DTYPE = HEADER.dtype("vtmc_fragment")       # one record of vtmc_terrain_fragments
+NAV_SPAN_DTYPE = LAYERS["nav"].dtype("vtmc_nav_span")       # one span of vtmc_terrain_nav_build
+NAVFIELD_CELL_DTYPE = LAYERS["navfield"].dtype("vtmc_navfield_cell")   # one cell of vtmc_navfield_build: cost and next
+NAVFIELD_GOAL_DTYPE = LAYERS["navfield"].dtype("vtmc_navfield_goal")   # one goal of vtmc_navfield_build: span and cost
+NAVSIGHT_HIT_DTYPE = LAYERS["navsight"].dtype("vtmc_navsight_hit")     # one answer of vtmc_nav_sight: the span the walk ended on and its steps
 
-Modifier = _H.structure("vtmc_modifier", "Modifier", """vtmc_modifier: one queued TerrainModifier (TerrainModifier.cs:19-33), bounds as the C#
+Modifier = HEADER.structure("vtmc_modifier", "Modifier", """vtmc_modifier: one queued TerrainModifier (TerrainModifier.cs:19-33), bounds as the C#
     LowerBound / UpperBound properties return them.""")
-MaterialStroke = _H.structure("vtmc_material_stroke", "MaterialStroke", "vtmc_material_stroke: one paint stroke on the material layer, centre in world space.")
-AoParams = _H.structure("vtmc_ao_params", "AoParams", "vtmc_ao_params: radius in world units, strength in [0, 1], steps 1..AO_MAX_STEPS, flags 0.")
-ScatterParams = _H.structure("vtmc_scatter_params", "ScatterParams", """vtmc_scatter_params: density per world unit^2, the slope band on the face normal's y,
+MaterialStroke = HEADER.structure("vtmc_material_stroke", "MaterialStroke", "vtmc_material_stroke: one paint stroke on the material layer, centre in world space.")
+AoParams = HEADER.structure("vtmc_ao_params", "AoParams", "vtmc_ao_params: radius in world units, strength in [0, 1], steps 1..AO_MAX_STEPS, flags 0.")
+ScatterParams = HEADER.structure("vtmc_scatter_params", "ScatterParams", """vtmc_scatter_params: density per world unit^2, the slope band on the face normal's y,
     the world height band, the material channel (-1: none), the seed, the most instances the call may make, flags 0.""")
-Instance = _H.structure("vtmc_instance", "Instance", "vtmc_instance: world position, interpolated record normal, the triangle's index in the result, 32 random bits.")
-LodParams = _H.structure("vtmc_lod_params", "LodParams", "vtmc_lod_params: viewer in world space, split >= 1, max_level 0..LOD_MAX_LEVEL, max_nodes > 0.")
-Fragment = _H.structure("vtmc_fragment", "Fragment", """vtmc_fragment: seed (the sample of smallest grid index), tight inclusive bounds, solid sample count,
+Instance = HEADER.structure("vtmc_instance", "Instance", "vtmc_instance: world position, interpolated record normal, the triangle's index in the result, 32 random bits.")
+LodParams = HEADER.structure("vtmc_lod_params", "LodParams", "vtmc_lod_params: viewer in world space, split >= 1, max_level 0..LOD_MAX_LEVEL, max_nodes > 0.")
+Fragment = HEADER.structure("vtmc_fragment", "Fragment", """vtmc_fragment: seed (the sample of smallest grid index), tight inclusive bounds, solid sample count,
     the stamp's id (0: not captured).""")
-NavParamsStruct = _N.structure("vtmc_nav_params", "NavParamsStruct", "vtmc_nav_params: agent_height in samples, max_step in grid units, max_spans > 0, flags 0.")
-NavSpan = _N.structure("vtmc_nav_span", "NavSpan", "vtmc_nav_span: floor height (grid units), floor sample y, clearance, four links, region.")
-NavFieldParamsStruct = _F.structure("vtmc_navfield_params", "NavFieldParamsStruct", "vtmc_navfield_params: climb and drop cost per grid unit in [0, 1024], max_cost 1..0x7fffffff, flags 0.")
-NavErodeParamsStruct = _E.structure("vtmc_naverode_params", "NavErodeParamsStruct", "vtmc_naverode_params: radius in columns, 0..NAVERODE_MAX_RADIUS, flags NAVERODE_OPEN_BOX_FACES or 0, two reserved words, 0.")
-NavSightParamsStruct = _S.structure("vtmc_navsight_params", "NavSightParamsStruct", "vtmc_navsight_params: max_look 1..NAVSIGHT_MAX_LOOK, max_extra_cost or NAVSIGHT_ANY_COST, flags 0, reserved 0.")
-LodNode = _H.structure("vtmc_lod_node", "LodNode", "vtmc_lod_node: cell origin (multiples of 8 * 2^level) and level of one node of a level-of-detail extract.")
-VolumeBatch = _H.structure("vtmc_volume_batch", "VolumeBatch")
-ChunkView = _H.structure("vtmc_chunk_view", "ChunkView", "vtmc_chunk_view: device pointers into an uploaded chunk-file image.")
-DensityParams = _H.structure("vtmc_density_params", "DensityParams")
+NavParamsStruct = LAYERS["nav"].structure("vtmc_nav_params", "NavParamsStruct", "vtmc_nav_params: agent_height in samples, max_step in grid units, max_spans > 0, flags 0.")
+NavSpan = LAYERS["nav"].structure("vtmc_nav_span", "NavSpan", "vtmc_nav_span: floor height (grid units), floor sample y, clearance, four links, region.")
+NavFieldParamsStruct = LAYERS["navfield"].structure("vtmc_navfield_params", "NavFieldParamsStruct", "vtmc_navfield_params: climb and drop cost per grid unit in [0, 1024], max_cost 1..0x7fffffff, flags 0.")
+NavErodeParamsStruct = LAYERS["naverode"].structure("vtmc_naverode_params", "NavErodeParamsStruct", "vtmc_naverode_params: radius in columns, 0..NAVERODE_MAX_RADIUS, flags NAVERODE_OPEN_BOX_FACES or 0, two reserved words, 0.")
+NavSightParamsStruct = LAYERS["navsight"].structure("vtmc_navsight_params", "NavSightParamsStruct", "vtmc_navsight_params: max_look 1..NAVSIGHT_MAX_LOOK, max_extra_cost or NAVSIGHT_ANY_COST, flags 0, reserved 0.")
+LodNode = HEADER.structure("vtmc_lod_node", "LodNode", "vtmc_lod_node: cell origin (multiples of 8 * 2^level) and level of one node of a level-of-detail extract.")
+VolumeBatch = HEADER.structure("vtmc_volume_batch", "VolumeBatch")
+ChunkView = HEADER.structure("vtmc_chunk_view", "ChunkView", "vtmc_chunk_view: device pointers into an uploaded chunk-file image.")
+DensityParams = HEADER.structure("vtmc_density_params", "DensityParams")
 
 _vp, _i32, _i64, _P = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.POINTER
 DEBUG_ARGTYPES = {   # entry points that are deliberately not in the header; all return int32_t
@@ -102,7 +97,7 @@ def load(path=None):
         except Exception:
             pass
     L = ctypes.CDLL(path)
-    signatures = [(p.name, p.restype, p.argtypes) for h in (_H, _N, _F, _E, _S) for p in h.prototypes.values()] + [(n, _i32, a) for n, a in DEBUG_ARGTYPES.items()]
+    signatures = [(p.name, p.restype, p.argtypes) for h in LAYERS.values() for p in h.prototypes.values()] + [(n, _i32, a) for n, a in DEBUG_ARGTYPES.items()]
     for name, restype, argtypes in signatures:
         if explicit and not hasattr(L, name):   # an older build loaded beside the product's (A/B tools) may lack the newest entry points;
             continue                            # in the product's own library a missing name is an error

@@ -16,7 +16,18 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvtmc.so")
 SOURCES = ["context.hip", "vtmc_api.hip", "classify_kernels.hip", "emit_kernels.hip", "terrain.hip", "terrain_brush.hip", "terrain_noise.hip", "terrain_stamp.hip", "stamp_mesh.hip", "terrain_path.hip", "terrain_fragments.hip", "terrain_nav.hip", "terrain_navfield.hip", "terrain_naverode.hip", "terrain_navsight.hip", "terrain_material.hip", "terrain_ao.hip", "terrain_scatter.hip", "terrain_lod.hip", "terrain_io.hip", "density.hip",
            "chunk_io.hip", "comm.hip", "raycast.hip", "spherequery.hip"]
-HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in ("vtmc_nav.h", "vtmc_navfield.h", "vtmc_naverode.h", "vtmc_navsight.h", "vtmc.h")]   # for is_stale; the last one is the contract _header.py reads first
+# The ABI's headers under include/, in order: (name, file, the name of the row whose file it includes or None, the document that holds its
+# [DllImport] stubs).  This is the one place a layer is registered: _header.py reads the files, _lib.py binds what they declare, and
+# tests/test_abi_layers.py holds every row to the same contract.
+ABI_LAYERS = (
+    ("core", "vtmc.h", None, "INTEGRATION.md"),
+    ("nav", "vtmc_nav.h", "core", "NAVIGATION.md"),
+    ("navfield", "vtmc_navfield.h", "nav", "PATHFINDING.md"),
+    ("naverode", "vtmc_naverode.h", "nav", "NAVEROSION.md"),
+    ("navsight", "vtmc_navsight.h", "navfield", "PATHSMOOTHING.md"),
+)
+INCLUDE = os.path.normpath(os.path.join(HERE, "..", "include"))
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(INCLUDE, row[1]) for row in ABI_LAYERS]   # for is_stale
 # -fno-slp-vectorize: hipcc's SLP pass packs adjacent FP32 operations into v_pk_fma_f32 / v_pk_add_f32 (+ moves to
 # pair the operands); on gfx950 a packed FP32 op costs more than the two scalar ones it replaces
 # (MI355X_MICROARCH.md, "packed f32 VALU ... an anti-lever"): the sampler runs 30 % faster without it.

@@ -252,6 +252,13 @@ int nav_label_regions(vtmc_ctx *ctx, const char *who, vtmc_nav_span *spans, int3
     }
 }
 
+NavBox nav_held_box(const VtmcNav &nav)
+{
+    NavBox nb;
+    for (int k = 0; k < 3; ++k) nb.lo[k] = nav.lo[k], nb.d[k] = nav.d[k];
+    return nb;
+}
+
 static dim3 walk_grid(const TerrainBox &b) { return dim3((unsigned)((b.dx + 63) / 64), (unsigned)((b.dz + 3) / 4)); }   // nav_walk_kernel, nav_read_kernel
 
 }  // namespace vtmc
@@ -338,11 +345,7 @@ int32_t vtmc_nav_read(vtmc_ctx *ctx, vtmc_nav_span *dst, int32_t capacity, int32
     if (nav.n > 0 && !dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "dst is null");
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     if (nav.n > 0) VTMC_HIP(ctx, hipMemcpy(dst, nav.spans.p, nav_span_bytes(nav.n), hipMemcpyDeviceToHost));
-    if (column_offsets) {
-        NavBox nb;
-        for (int k = 0; k < 3; ++k) nb.lo[k] = nav.lo[k], nb.d[k] = nav.d[k];
-        VTMC_HIP(ctx, hipMemcpy(column_offsets, nav.offsets.p, nav_sizes(nb).offsets_bytes, hipMemcpyDeviceToHost));
-    }
+    if (column_offsets) VTMC_HIP(ctx, hipMemcpy(column_offsets, nav.offsets.p, nav_sizes(nav_held_box(nav)).offsets_bytes, hipMemcpyDeviceToHost));
     return VTMC_OK;
 }
 

@@ -281,9 +281,7 @@ int32_t vtmc_nav_erode(vtmc_ctx *ctx, const vtmc_naverode_params *params, int32_
     VTMC_HIP(ctx, clock.begin());   // disarmed: a nav result without spans leaves it so
     int32_t kept = 0;
     if (n > 0) {
-        NavBox nb;
-        for (int k = 0; k < 3; ++k) nb.lo[k] = nav.lo[k], nb.d[k] = nav.d[k];
-        const NavSizes sz = nav_sizes(nb);   // n > 0: the box is not empty, and the build has sized the scan buffer and the scratch for it
+        const NavSizes sz = nav_sizes(nav_held_box(nav));   // n > 0: the box is not empty, and the build has sized the scan buffer and the scratch for it
         if (int rc = ensure(ctx, nav.spans_next, nav_span_bytes(n))) return rc;
         if (int rc = ensure(ctx, nav.offsets_next, sz.offsets_bytes)) return rc;
         if (int rc = ensure(ctx, nav.scan, sz.scan_bytes)) return rc;

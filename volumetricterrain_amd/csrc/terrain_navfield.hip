@@ -231,6 +231,29 @@ __global__ __launch_bounds__(256) void navfield_trace_kernel(const vtmc_navfield
     lengths[i] = len;
 }
 
+int trace_rows_stage(vtmc_ctx *ctx, const int32_t *starts, int32_t n_starts, int32_t max_len, TraceRows *rows)
+{
+    const float *const src[3] = {(const float *)starts, nullptr, nullptr};
+    const size_t bytes[3] = {(size_t)n_starts * 4u, 0, 0};
+    rows->path_bytes = navfield_path_bytes(n_starts, max_len), rows->length_bytes = (size_t)n_starts * 4u;
+    QueryStage st;   // the answers: the rows, then the lengths
+    if (int rc = stage_queries(ctx, src, bytes, rows->path_bytes + rows->length_bytes, &st)) return rc;
+    rows->starts = (const int32_t *)st.in[0];
+    rows->paths = (int32_t *)st.hits, rows->lengths = (int32_t *)((unsigned char *)st.hits + rows->path_bytes);
+    rows->host_off = st.hit_off;
+    return VTMC_OK;
+}
+
+int trace_rows_fetch(vtmc_ctx *ctx, const TraceRows &rows, int32_t *paths, int32_t *lengths)
+{
+    const unsigned char *h = ctx->h_rays.p + rows.host_off;
+    VTMC_HIP(ctx, hipMemcpyAsync(ctx->h_rays.p + rows.host_off, rows.paths, rows.path_bytes + rows.length_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(paths, h, rows.path_bytes);
+    memcpy(lengths, h + rows.path_bytes, rows.length_bytes);
+    return VTMC_OK;
+}
+
 }  // namespace vtmc
 
 using namespace vtmc;
@@ -367,21 +390,12 @@ int32_t vtmc_navfield_trace(vtmc_ctx *ctx, const int32_t *starts, int32_t n_star
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     VTMC_HIP(ctx, hipStreamSynchronize(s));
-    const float *const src[3] = {(const float *)starts, nullptr, nullptr};
-    const size_t bytes[3] = {(size_t)n_starts * 4u, 0, 0};
-    const size_t path_bytes = navfield_path_bytes(n_starts, max_len), length_bytes = (size_t)n_starts * 4u;
-    QueryStage st;   // the answers: the rows, then the lengths
-    if (int rc = stage_queries(ctx, src, bytes, path_bytes + length_bytes, &st)) return rc;
-    int32_t *d_paths = (int32_t *)st.hits, *d_lengths = (int32_t *)((unsigned char *)st.hits + path_bytes);
-    VTMC_HIP(ctx, hipMemsetAsync(d_paths, 0xff, path_bytes, s));
-    VTMC_HIP(ctx, launch(navfield_trace_kernel, lanes256(n_starts), dim3(256), 0, s, (const vtmc_navfield_cell *)nf.cells.p, nf.n, (const int32_t *)st.in[0], n_starts,
-                         max_len, d_paths, d_lengths));
-    const unsigned char *h = ctx->h_rays.p + st.hit_off;
-    VTMC_HIP(ctx, hipMemcpyAsync(ctx->h_rays.p + st.hit_off, st.hits, st.hit_bytes, hipMemcpyDeviceToHost, s));
-    VTMC_HIP(ctx, hipStreamSynchronize(s));
-    memcpy(paths, h, path_bytes);
-    memcpy(lengths, h + path_bytes, length_bytes);
-    return VTMC_OK;
+    TraceRows rows;
+    if (int rc = trace_rows_stage(ctx, starts, n_starts, max_len, &rows)) return rc;
+    VTMC_HIP(ctx, hipMemsetAsync(rows.paths, 0xff, rows.path_bytes, s));
+    VTMC_HIP(ctx, launch(navfield_trace_kernel, lanes256(n_starts), dim3(256), 0, s, (const vtmc_navfield_cell *)nf.cells.p, nf.n, rows.starts, n_starts, max_len,
+                         rows.paths, rows.lengths));
+    return trace_rows_fetch(ctx, rows, paths, lengths);
 }
 
 // Not part of the ABI (tools/navfield_bench.py): device time of the last vtmc_navfield_build, ms[0..2] = the edge costs with the goals, the

@@ -220,33 +220,25 @@ int32_t vtmc_navfield_trace_smooth(vtmc_ctx *ctx, const int32_t *starts, int32_t
     StageClock<3> &clock = ctx->navsight_clock;
     VTMC_HIP(ctx, clock.begin());
     if (int rc = ensure(ctx, ctx->navsight_links, navsight_link_bytes(nf.n))) return rc;
-    const float *const src[3] = {(const float *)starts, nullptr, nullptr};
-    const size_t bytes[3] = {(size_t)n_starts * 4u, 0, 0};
-    const size_t path_bytes = navfield_path_bytes(n_starts, max_len), length_bytes = (size_t)n_starts * 4u;
-    QueryStage st;   // the answers: the rows, then the lengths
-    if (int rc = stage_queries(ctx, src, bytes, path_bytes + length_bytes, &st)) return rc;
-    int32_t *d_paths = (int32_t *)st.hits, *d_lengths = (int32_t *)((unsigned char *)st.hits + path_bytes);
+    TraceRows rows;
+    if (int rc = trace_rows_stage(ctx, starts, n_starts, max_len, &rows)) return rc;
     const vtmc_nav_span *spans = (const vtmc_nav_span *)ctx->nav.spans.p;
     const uint32_t *costs = (const uint32_t *)nf.work.p;   // the four edge costs of every span, as navfield_build left them
     const vtmc_navfield_cell *cells = (const vtmc_navfield_cell *)nf.cells.p;
     const dim3 grid((unsigned)(((int64_t)n_starts + kNavSightWaves - 1) / kNavSightWaves)), block(64 * kNavSightWaves);
     VTMC_HIP(ctx, clock.mark(0, s));
-    VTMC_HIP(ctx, hipMemsetAsync(d_paths, 0xff, path_bytes, s));
+    VTMC_HIP(ctx, hipMemsetAsync(rows.paths, 0xff, rows.path_bytes, s));
     VTMC_HIP(ctx, launch(navsight_pack_kernel, lanes256(nf.n), dim3(256), 0, s, spans, (int4 *)ctx->navsight_links.p, nf.n));
     const NavSightPackedLinks link{(const int32_t *)ctx->navsight_links.p};
     VTMC_HIP(ctx, clock.mark(1, s));
     if (params->max_extra_cost == VTMC_NAVSIGHT_ANY_COST)
-        VTMC_HIP(ctx, launch(navfield_smooth_kernel<false>, grid, block, 0, s, link, costs, cells, nf.n, (const int32_t *)st.in[0], n_starts, max_len, params->max_look,
-                             params->max_extra_cost, d_paths, d_lengths));
+        VTMC_HIP(ctx, launch(navfield_smooth_kernel<false>, grid, block, 0, s, link, costs, cells, nf.n, rows.starts, n_starts, max_len, params->max_look, params->max_extra_cost,
+                             rows.paths, rows.lengths));
     else
-        VTMC_HIP(ctx, launch(navfield_smooth_kernel<true>, grid, block, 0, s, link, costs, cells, nf.n, (const int32_t *)st.in[0], n_starts, max_len, params->max_look,
-                             params->max_extra_cost, d_paths, d_lengths));
+        VTMC_HIP(ctx, launch(navfield_smooth_kernel<true>, grid, block, 0, s, link, costs, cells, nf.n, rows.starts, n_starts, max_len, params->max_look, params->max_extra_cost,
+                             rows.paths, rows.lengths));
     VTMC_HIP(ctx, clock.mark(2, s));
-    const unsigned char *h = ctx->h_rays.p + st.hit_off;
-    VTMC_HIP(ctx, hipMemcpyAsync(ctx->h_rays.p + st.hit_off, st.hits, st.hit_bytes, hipMemcpyDeviceToHost, s));
-    VTMC_HIP(ctx, hipStreamSynchronize(s));
-    memcpy(paths, h, path_bytes);
-    memcpy(lengths, h + path_bytes, length_bytes);
+    if (int rc = trace_rows_fetch(ctx, rows, paths, lengths)) return rc;
     clock.arm();
     return VTMC_OK;
 }

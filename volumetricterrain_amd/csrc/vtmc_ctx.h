@@ -342,6 +342,22 @@ int terrain_extract_all(vtmc_ctx *ctx, int32_t *n_dirty_blocks, int32_t *tri_cou
 struct ScanLayout;
 hipError_t nav_launch_offsets(const ScanLayout &scan, int32_t *offsets, hipStream_t stream);
 int nav_label_regions(vtmc_ctx *ctx, const char *who, vtmc_nav_span *spans, int32_t *parent, int32_t n, bool timed, int *rounds);
+// ... and the box a nav result holds, as terrain_nav.h's sizes take it
+struct NavBox;
+NavBox nav_held_box(const VtmcNav &nav);
+
+// terrain_navfield.hip, for terrain_navsight.hip: the rows of a trace, plain or smoothed, on their way through the context's query stage
+// (surface_query.h): n_starts rows of max_len spans, then n_starts lengths, one block on the device and in pinned memory.
+struct TraceRows {
+    const int32_t *starts;      // device: the staged starts
+    int32_t *paths, *lengths;   // device
+    size_t path_bytes, length_bytes, host_off;   // host_off: of the block in ctx->h_rays
+};
+// stages the starts (their upload is queued on the context's stream) and carves the block; between this and the fetch the caller queues
+// the fill of the rows with -1 (0xff bytes over path_bytes) and its kernel
+int trace_rows_stage(vtmc_ctx *ctx, const int32_t *starts, int32_t n_starts, int32_t max_len, TraceRows *rows);
+// behind the kernel: the block comes back, the stream is drained, and the rows and lengths go to the caller's arrays
+int trace_rows_fetch(vtmc_ctx *ctx, const TraceRows &rows, int32_t *paths, int32_t *lengths);
 
 // The one kernel launch of this layer: clears the runtime's sticky error word, launches, and returns what this launch left (the rule of
 // launch_begin / launch_end in vtmc_internal.h, whose own wrappers in the two files of extract kernels keep the hand-written form).
