@@ -8,6 +8,7 @@
 //   host_selftest --gpu-naverode <out_dir>  the agent radius on that build: dumps the distances, then the eroded spans, offsets and origin
 //   host_selftest --gpu-navfield <out_dir>  a flow field on that build: dumps the cells, every span's path and the located goal spans
 //   host_selftest --gpu-navsight <out_dir>  any-angle paths on that field: dumps the hits of a set of pairs and every span's smoothed path
+//   host_selftest --gpu-navcrowd <out_dir>  a crowd on that field: dumps agents, occupancy and counts after the spawn, 24 ticks and a re-route
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -436,6 +437,83 @@ static int gpu_navsight_run(const std::string &out)
     return 0;
 }
 
+// the world, the box and the field of --gpu-navfield; agents on every second span (those divisible by 7 ask for -1, and span 2 is asked
+// for three times), 24 ticks with any detour that leave on arrival, then a field of the second goal alone and 16 ticks within 1024
+static int gpu_navcrowd_run(const std::string &out)
+{
+    VoxelTerrain vt;
+    vt._width = 64;
+    vt._elevation = 32;
+    vt._height = 32;
+    vt._voxelScale = 0.5f;
+    vt.TerrainOrigin = Vector3(-3.0f, 1.0f, 2.0f);
+    vt._deviceResident = true;
+    vt._seed = 977;
+    vt.Init();
+    Vector2 lo, up;
+    lo.x = -100; lo.y = -100; up.x = 100; up.y = 100;
+    vt.InsertModifier(std::make_shared<PlaneModifier>(6.3f, lo, up, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(27.5f, 8.0f, 10.0f), 4.25f, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(5.0f, 6.0f, 9.0f), 3.0f, false));
+    vt.Update();
+    const int updateTriangles = vt.LastTriangleCount();
+    const NavResult nav = vt.BuildNav(Vector3(-1.0f, 1.0f, 3.0f), Vector3(14.0f, 15.0f, 16.5f), 0.9f, 0.4f);
+    const std::vector<int> at = vt.LocateOnNav({Vector3(0.0f, 6.3f, 4.0f), Vector3(12.0f, 6.3f, 15.0f)}, 1.0f, 1.0f);
+    if (at.size() != 2 || at[0] < 0 || at[1] < 0) return 7;
+    vt.BuildNavField({NavGoal{at[0], 0u}, NavGoal{at[1], 3000u}}, 2.0f, 0.5f);
+    const int n = (int)nav._spans.size();
+    std::vector<int> starts;
+    for (int s = 0; s < n; s += 2) starts.push_back(s % 7 ? s : -1);
+    starts.push_back(2), starts.push_back(2);
+    std::vector<unsigned> speeds;
+    for (size_t i = 0; i < starts.size(); i++) speeds.push_back(400u + (unsigned)((131 * i) % 1200));
+    static_assert(sizeof(CrowdAgent) == 16, "dumped as it lies");
+    std::ofstream fi(out + "/navcrowd_info.i32", std::ios::binary);
+    auto dump = [&](const char *name) {
+        const CrowdResult r = vt.ReadCrowd();
+        std::ofstream fa(out + "/navcrowd_" + name + ".bin", std::ios::binary), fo(out + "/navcrowd_" + name + "_occupancy.i32", std::ios::binary);
+        fa.write(reinterpret_cast<const char *>(r._agents.data()), (std::streamsize)(r._agents.size() * sizeof(CrowdAgent)));
+        fo.write(reinterpret_cast<const char *>(r._occupancy.data()), (std::streamsize)(r._occupancy.size() * sizeof(int)));
+        const int info[5] = {(int)r._agents.size(), r._occupying, r._arrived, r._ticks, r._movedLast};
+        fi.write(reinterpret_cast<const char *>(info), sizeof info);
+        return r;
+    };
+    const int placed = vt.SpawnCrowd(starts, speeds);
+    const CrowdResult spawned = dump("spawned");
+    if (spawned._agents.size() != starts.size() || (int)spawned._occupancy.size() != n || placed <= 0 || placed >= (int)starts.size() || spawned._occupying != placed ||
+        spawned._ticks != 0)
+        return 8;
+    if (spawned._agents[0]._state != kCrowdUnplaced || spawned._agents[0]._span != -1 || spawned._agents[1]._state != kCrowdWalking || spawned._occupancy[2] != 1 ||
+        spawned._agents.back()._state != kCrowdUnplaced)
+        return 9;   // agent 1 asked for span 2 first
+    vt.StepCrowd(24, kNavCrowdAnyDetour, true);
+    const CrowdResult stepped = dump("stepped");
+    if (stepped._ticks != 24 || stepped._arrived <= 0 || stepped._occupying + stepped._arrived != placed) return 10;   // who arrived has left
+    vt.BuildNavField({NavGoal{at[1], 0u}}, 2.0f, 0.5f);   // the re-route keeps the crowd
+    vt.StepCrowd(16, 1024u);
+    const CrowdResult rerouted = dump("rerouted");
+    if (rerouted._ticks != 40 || rerouted._agents.size() != starts.size()) return 11;
+    if (vt.LastTriangleCount() != updateTriangles) return 12;   // what Update left stands
+    std::printf("navcrowd: spans %d agents %zu placed %d arrived %d\n", n, starts.size(), placed, rerouted._arrived);
+    bool refused = false;   // a speed of 0 refuses the call and keeps the crowd
+    try {
+        vt.SpawnCrowd({0}, {0u});
+    } catch (const UnityException &) {
+        refused = true;
+    }
+    if (!refused || vt.ReadCrowd()._ticks != 40) return 13;
+    vt.BuildNav(Vector3(-1.0f, 1.0f, 3.0f), Vector3(14.0f, 15.0f, 16.5f), 0.9f, 0.4f);   // a nav build drops it
+    refused = false;
+    try {
+        vt.ReadCrowd();
+    } catch (const UnityException &) {
+        refused = true;
+    }
+    if (!refused) return 14;
+    std::printf("HOST-NAVCROWD-OK\n");
+    return 0;
+}
+
 static int gpu_lod_run(const std::string &out)
 {
     VoxelTerrain vt;
@@ -502,10 +580,11 @@ int main(int argc, char **argv)
         if (argc >= 3 && std::string(argv[1]) == "--gpu-naverode") return gpu_naverode_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-navfield") return gpu_navfield_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-navsight") return gpu_navsight_run(argv[2]);
+        if (argc >= 3 && std::string(argv[1]) == "--gpu-navcrowd") return gpu_navcrowd_run(argv[2]);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "exception: %s\n", e.what());
         return 3;
     }
-    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir> | --gpu-resident <out_dir> | --gpu-lod <out_dir> | --gpu-nav <out_dir> | --gpu-naverode <out_dir> | --gpu-navfield <out_dir> | --gpu-navsight <out_dir>\n");
+    std::fprintf(stderr, "usage: host_selftest --cpu | --gpu <out_dir> | --gpu-resident <out_dir> | --gpu-lod <out_dir> | --gpu-nav <out_dir> | --gpu-naverode <out_dir> | --gpu-navfield <out_dir> | --gpu-navsight <out_dir> | --gpu-navcrowd <out_dir>\n");
     return 64;
 }

@@ -10,6 +10,7 @@
 #include "../include/vtmc_navfield.h"   // includes vtmc_nav.h, which includes vtmc.h
 #include "../include/vtmc_naverode.h"
 #include "../include/vtmc_navsight.h"
+#include "../include/vtmc_navcrowd.h"
 
 namespace PGRTerrain {
 
@@ -302,6 +303,32 @@ public:
         if (vtmc_navfield_trace_smooth(_ctx, starts.data(), (int32_t)starts.size(), maxLen, &p, out._paths.data(), out._lengths.data()) != VTMC_OK)
             throw UnityException(std::string("vtmc_navfield_trace_smooth: ") + vtmc_last_error(_ctx));
     }
+    int CrowdSpawn(const std::vector<int> &spans, const std::vector<unsigned> &speeds) override
+    {
+        if (spans.size() != speeds.size()) throw UnityException("SpawnCrowd: as many speeds as spans");
+        static_assert(sizeof(unsigned) == sizeof(uint32_t), "speeds are read in place");
+        int32_t placed = 0;
+        if (vtmc_navcrowd_spawn(_ctx, spans.data(), speeds.data(), (int32_t)spans.size(), &placed) != VTMC_OK)
+            throw UnityException(std::string("vtmc_navcrowd_spawn: ") + vtmc_last_error(_ctx));
+        return placed;
+    }
+    void CrowdStep(unsigned maxDetour, bool leaveOnArrival, int ticks) override
+    {
+        vtmc_navcrowd_params p;
+        p.max_detour = maxDetour, p.flags = leaveOnArrival ? VTMC_NAVCROWD_LEAVE_ON_ARRIVAL : 0u, p.reserved[0] = p.reserved[1] = 0u;
+        if (vtmc_navcrowd_step(_ctx, &p, ticks) != VTMC_OK) throw UnityException(std::string("vtmc_navcrowd_step: ") + vtmc_last_error(_ctx));
+    }
+    void CrowdRead(CrowdResult &out) override
+    {
+        int32_t n = 0, nSpans = 0;
+        if (vtmc_navcrowd_info(_ctx, &n, &out._occupying, &out._arrived, &out._ticks, &out._movedLast) != VTMC_OK || vtmc_nav_info(_ctx, nullptr, nullptr, &nSpans) != VTMC_OK)
+            throw UnityException(std::string("vtmc_navcrowd_info: ") + vtmc_last_error(_ctx));
+        std::vector<vtmc_navcrowd_agent> agents((size_t)n);
+        out._occupancy.assign((size_t)nSpans, -1);
+        if (vtmc_navcrowd_read(_ctx, agents.data(), n, out._occupancy.data()) != VTMC_OK) throw UnityException(std::string("vtmc_navcrowd_read: ") + vtmc_last_error(_ctx));
+        out._agents.clear();
+        for (const vtmc_navcrowd_agent &a : agents) out._agents.push_back(CrowdAgent{a.span, a.budget, a.speed, a.state});
+    }
 
     int MaterialInit(int fineness) override
     {
@@ -505,6 +532,26 @@ NavPaths VoxelTerrain::SmoothPaths(const std::vector<int> &starts, int maxLen, i
     if (!_initialised || !_deviceResident) throw UnityException("SmoothPaths needs an initialised device-resident terrain");
     NavPaths out;
     _backend->NavTraceSmooth(starts, maxLen, maxLook, maxExtraCost, out);
+    return out;
+}
+
+int VoxelTerrain::SpawnCrowd(const std::vector<int> &spans, const std::vector<unsigned> &speeds)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("SpawnCrowd needs an initialised device-resident terrain");
+    return _backend->CrowdSpawn(spans, speeds);
+}
+
+void VoxelTerrain::StepCrowd(int ticks, unsigned maxDetour, bool leaveOnArrival)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("StepCrowd needs an initialised device-resident terrain");
+    _backend->CrowdStep(maxDetour, leaveOnArrival, ticks);
+}
+
+CrowdResult VoxelTerrain::ReadCrowd()
+{
+    if (!_initialised || !_deviceResident) throw UnityException("ReadCrowd needs an initialised device-resident terrain");
+    CrowdResult out;
+    _backend->CrowdRead(out);
     return out;
 }
 

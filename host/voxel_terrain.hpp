@@ -348,6 +348,20 @@ struct NavSightHit {
     int _last;
     int _steps;
 };
+// New (not in the reference): a crowd stepped along the flow field (include/vtmc_navcrowd.h, where the rule is).  An agent stands on a
+// span, one agent per span, earns _speed cost units per tick and saves them in _budget; CrowdResult is what ReadCrowd returns: the agents,
+// per span the index of the agent on it or -1, and the counts of vtmc_navcrowd_info.
+constexpr unsigned kNavCrowdAnyDetour = 0xffffffffu;
+enum NavCrowdState : unsigned { kCrowdWalking = 0, kCrowdArrived = 1, kCrowdStranded = 2, kCrowdGone = 3, kCrowdUnplaced = 4 };
+struct CrowdAgent {
+    int _span;
+    unsigned _budget, _speed, _state;
+};
+struct CrowdResult {
+    std::vector<CrowdAgent> _agents;
+    std::vector<int> _occupancy;
+    int _occupying = 0, _arrived = 0, _ticks = 0, _movedLast = 0;
+};
 
 // New (not in the reference, which can only replace a control map whole): one paint stroke on the material layer (vtmc_material_stroke
 // of include/vtmc.h).  Every texel within _radius of _center (world space) is blended towards the one-hot of _channel (0..3: control map
@@ -434,6 +448,10 @@ struct ExtractBackend {
     virtual void NavTrace(const std::vector<int> &, int, NavPaths &) { throw std::logic_error("NavTrace unsupported"); }
     // Any-angle paths on that build and its field (vtmc_nav_sight, vtmc_navfield_trace_smooth).
     virtual void NavSight(const std::vector<int> &, const std::vector<int> &, std::vector<NavSightHit> &) { throw std::logic_error("NavSight unsupported"); }
+    // A crowd on that build and its field (vtmc_navcrowd_spawn, _step, _read with _info).
+    virtual int CrowdSpawn(const std::vector<int> &, const std::vector<unsigned> &) { throw std::logic_error("CrowdSpawn unsupported"); }
+    virtual void CrowdStep(unsigned, bool, int) { throw std::logic_error("CrowdStep unsupported"); }
+    virtual void CrowdRead(CrowdResult &) { throw std::logic_error("CrowdRead unsupported"); }
     virtual void NavTraceSmooth(const std::vector<int> &, int, int, unsigned, NavPaths &) { throw std::logic_error("NavTraceSmooth unsupported"); }
 
     // Material layer of a device-resident terrain (vtmc_material_*).  MaterialInit returns the layer's size C = 16 * fineness.
@@ -536,6 +554,16 @@ public:
     // are column centres; the only clearance is ErodeNav's radius; greedy, not the globally shortest path.
     std::vector<NavSightHit> NavSight(const std::vector<int> &from, const std::vector<int> &to);
     NavPaths SmoothPaths(const std::vector<int> &starts, int maxLen, int maxLook = 64, unsigned maxExtraCost = kNavSightAnyCost);
+
+    // New: a crowd on the last BuildNav (include/vtmc_navcrowd.h, where the rule is).  SpawnCrowd replaces the crowd: agent i asks for
+    // spans[i] (or -1) and earns speeds[i] cost units per tick; of several that ask for one span the smallest index stands; returns the
+    // number of placed agents.  StepCrowd moves everybody along the field of the last BuildNavField for `ticks` ticks, on the device: an
+    // agent takes the cheapest neighbour nearer the goal that was empty when the tick began and costs at most maxDetour above the cheapest
+    // way (kNavCrowdAnyDetour: any); with leaveOnArrival an agent that arrives frees its span.  BuildNavField keeps the crowd (the
+    // re-route); BuildNav and ErodeNav drop it.  ReadCrowd copies the agents, the occupancy and the counts.
+    int SpawnCrowd(const std::vector<int> &spans, const std::vector<unsigned> &speeds);
+    void StepCrowd(int ticks, unsigned maxDetour = kNavCrowdAnyDetour, bool leaveOnArrival = false);
+    CrowdResult ReadCrowd();
 
     // -- inspection (tests, callers that consume the meshes) ----------------------------------
     const BlockMesh &Block(int x, int y, int z) const { return _blocks[((size_t)x * (_elevation / blockSize) + y) * (_height / blockSize) + z]; }

@@ -36,7 +36,8 @@
  *              start gives length 0 and a row of -1.
  * OUT OF SCOPE, deliberately: no agent radius here (erode the spans first: vtmc_naverode.h); no any-angle smoothing (a path moves
  * from column to neighbour column; a layer of its own on top of this one pulls the traced paths straight on the device: vtmc_navsight.h,
- * line of sight and smoothed traces; PATHSMOOTHING.md); no field across the results of two boxes.
+ * line of sight and smoothed traces; PATHSMOOTHING.md); no agents that get in each other's way (a trace routes every start as if it were
+ * alone; vtmc_navcrowd.h steps a crowd along the field on the device, one agent per span; CROWD.md); no field across the results of two boxes.
  *
  * Life cycle.  The field belongs to the nav result it was built on: vtmc_terrain_nav_build drops it (also a build that fails after it
  * invalidated the nav result), and so do vtmc_terrain_init, vtmc_terrain_load and vtmc_destroy.  An edit does not: the field is a snapshot,

@@ -15,7 +15,7 @@ from ._header import HEADER, LAYERS
 
 # every #define VTMC_<NAME> of every layer's header as <NAME>.  include/vtmc.h: OK and the ERR_* codes, FLAG_*, OUTPUT_*, MOD_*, TERRAIN_SAVE_EXACT,
 # TERRAIN_LOAD_NO_EXTRACT, MESH_*, MATERIAL_*, AO_*, SCATTER_*, LOD_MAX_LEVEL, RAY_TWO_SIDED, SPHERE_MAX_RADIUS_CELLS, COMM_ID_BYTES ...
-# The optional layers' headers: NAV_OPEN, NAVFIELD_UNIT, NAVERODE_MAX_RADIUS, NAVSIGHT_ANY_COST ...
+# The optional layers' headers: NAV_OPEN, NAVFIELD_UNIT, NAVERODE_MAX_RADIUS, NAVSIGHT_ANY_COST, NAVCROWD_ANY_DETOUR ...
 for _layer in LAYERS.values():
     globals().update((name[len("VTMC_"):], value) for name, value in _layer.constants.items())
 STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27   # vtmc_stamp_create: the limits of a stamp's dims (the header states them in prose)
@@ -35,6 +35,7 @@ NAV_SPAN_DTYPE = LAYERS["nav"].dtype("vtmc_nav_span")       # one span of vtmc_t
 NAVFIELD_CELL_DTYPE = LAYERS["navfield"].dtype("vtmc_navfield_cell")   # one cell of vtmc_navfield_build: cost and next
 NAVFIELD_GOAL_DTYPE = LAYERS["navfield"].dtype("vtmc_navfield_goal")   # one goal of vtmc_navfield_build: span and cost
 NAVSIGHT_HIT_DTYPE = LAYERS["navsight"].dtype("vtmc_navsight_hit")     # one answer of vtmc_nav_sight: the span the walk ended on and its steps
+NAVCROWD_AGENT_DTYPE = LAYERS["navcrowd"].dtype("vtmc_navcrowd_agent")   # one agent of vtmc_navcrowd_spawn: span, budget, speed, state
 
 Modifier = HEADER.structure("vtmc_modifier", "Modifier", """vtmc_modifier: one queued TerrainModifier (TerrainModifier.cs:19-33), bounds as the C#
     LowerBound / UpperBound properties return them.""")
@@ -51,6 +52,7 @@ NavSpan = LAYERS["nav"].structure("vtmc_nav_span", "NavSpan", "vtmc_nav_span: fl
 NavFieldParamsStruct = LAYERS["navfield"].structure("vtmc_navfield_params", "NavFieldParamsStruct", "vtmc_navfield_params: climb and drop cost per grid unit in [0, 1024], max_cost 1..0x7fffffff, flags 0.")
 NavErodeParamsStruct = LAYERS["naverode"].structure("vtmc_naverode_params", "NavErodeParamsStruct", "vtmc_naverode_params: radius in columns, 0..NAVERODE_MAX_RADIUS, flags NAVERODE_OPEN_BOX_FACES or 0, two reserved words, 0.")
 NavSightParamsStruct = LAYERS["navsight"].structure("vtmc_navsight_params", "NavSightParamsStruct", "vtmc_navsight_params: max_look 1..NAVSIGHT_MAX_LOOK, max_extra_cost or NAVSIGHT_ANY_COST, flags 0, reserved 0.")
+NavCrowdParamsStruct = LAYERS["navcrowd"].structure("vtmc_navcrowd_params", "NavCrowdParamsStruct", "vtmc_navcrowd_params: max_detour or NAVCROWD_ANY_DETOUR, flags NAVCROWD_LEAVE_ON_ARRIVAL or 0, two reserved words, 0.")
 LodNode = HEADER.structure("vtmc_lod_node", "LodNode", "vtmc_lod_node: cell origin (multiples of 8 * 2^level) and level of one node of a level-of-detail extract.")
 VolumeBatch = HEADER.structure("vtmc_volume_batch", "VolumeBatch")
 ChunkView = HEADER.structure("vtmc_chunk_view", "ChunkView", "vtmc_chunk_view: device pointers into an uploaded chunk-file image.")
@@ -67,6 +69,7 @@ DEBUG_ARGTYPES = {   # entry points that are deliberately not in the header; all
     "vtmc_debug_navfield_ms": [_vp, _P(ctypes.c_float * 4)],        # device time of the last field build's three stages, and its rounds
     "vtmc_debug_naverode_ms": [_vp, _P(ctypes.c_float * 5)],        # device time of the last distance build's or erode's four stages, and its rounds
     "vtmc_debug_navsight_ms": [_vp, _P(ctypes.c_float * 2)],        # device time of the last sight query's or smoothed trace's row fill and kernel
+    "vtmc_debug_navcrowd_ms": [_vp, _P(ctypes.c_float * 1)],        # device time of the ticks of the last crowd step
 }
 
 

@@ -275,8 +275,8 @@ int32_t vtmc_nav_erode(vtmc_ctx *ctx, const vtmc_naverode_params *params, int32_
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     VTMC_HIP(ctx, hipStreamSynchronize(s));
-    // from here on neither the flow field nor the distances describe the nav result, and the origin buffer is being rewritten
-    ctx->navfield.valid = false, ne.dist_valid = false, ne.origin_valid = false;
+    // from here on neither the flow field nor the distances nor the crowd describe the nav result, and the origin buffer is being rewritten
+    ctx->navfield.valid = false, ne.dist_valid = false, ne.origin_valid = false, ctx->navcrowd.valid = false;
     StageClock<5> &clock = ctx->naverode_clock;
     VTMC_HIP(ctx, clock.begin());   // disarmed: a nav result without spans leaves it so
     int32_t kept = 0;

@@ -166,6 +166,17 @@ struct VtmcNavErode {
     int32_t rounds = 0;        // of the last distance pass
 };
 
+// The crowd the context holds (terrain_navcrowd.hip), spawned on the nav result above and dropped with it; a new flow field keeps it:
+// library-owned, grow-only.  agents: the records; pending: per agent the {target, cost} words a tick's claim kernel leaves for its resolve
+// kernel; occupancy, claims: a word per span; links: the four links of every span, packed at the spawn; ctl: the counters of a spawn or of
+// the last tick of a step.  The counts are the host's copy of what the last spawn or step left.
+struct VtmcNavCrowd {
+    VtmcDevBuf agents, pending, occupancy, claims, links, ctl;
+    bool valid = false;
+    int32_t n_agents = 0, n_spans = 0;
+    int32_t occupying = 0, arrived = 0, ticks = 0, moved_last = 0;
+};
+
 // An extract that has been queued on a stream and not yet completed by extract_finish().
 struct VtmcPending {
     bool active = false;    // queued, extract_finish() not yet called
@@ -267,6 +278,9 @@ struct vtmc_ctx {
     // of the nav result or the field between calls), and the clock of the last call (the fill of the rows with the packing, the kernel)
     VtmcDevBuf navsight_links;
     vtmc::StageClock<3> navsight_clock;
+    // terrain_navcrowd.hip: the crowd on that build, and the clock around the ticks of the last step that ran any
+    VtmcNavCrowd navcrowd;
+    vtmc::StageClock<2> navcrowd_clock;
     // terrain_lod.hip: the node list of the last level-of-detail result (host, and the copy the gather kernel reads), the packed
     // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the clock around
     // the gather launch of the last extract that succeeded (vtmc_debug_lod_gather_ms)
@@ -322,9 +336,9 @@ int check_dims(vtmc_ctx *ctx, int nx, int ny, int nz);
 BlockSpace dense_space(const float *d_base, int nx, int ny, int nz, int64_t sx, int64_t sy, int64_t sz, int n_volumes, int64_t sv);
 float *pinned_stage(vtmc_ctx *ctx, size_t bytes);   // the pinned stage of host-gathered data (vtmc_api.hip), grown to `bytes`; null: none to be had, go pageable
 void material_drop(vtmc_ctx *ctx);   // terrain_material.hip: vtmc_terrain_init / _load drop the layer
-// whatever invalidates the nav result drops what describes it, the flow field, the border distance and the origin of an erosion:
-// vtmc_terrain_init / _load and every vtmc_terrain_nav_build
-inline void nav_drop(vtmc_ctx *ctx) { ctx->nav.valid = false, ctx->navfield.valid = false, ctx->naverode.dist_valid = false, ctx->naverode.origin_valid = false; }
+// whatever invalidates the nav result drops what describes it, the flow field, the border distance and the origin of an erosion, and the
+// crowd that stands on it: vtmc_terrain_init / _load and every vtmc_terrain_nav_build
+inline void nav_drop(vtmc_ctx *ctx) { ctx->nav.valid = false, ctx->navfield.valid = false, ctx->naverode.dist_valid = false, ctx->naverode.origin_valid = false, ctx->navcrowd.valid = false; }
 int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp);   // sp then walks the (bx,by,bz) list
 int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, ResultSource source, int32_t *tri_count);   // queued on the context's stream and finished
 // The vertex attributes of a terrain result (terrain_material.hip, terrain_ao.hip), in vtmc_api.hip.  attr_gate: may `who` compute one for

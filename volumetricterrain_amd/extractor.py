@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, NAVFIELD_CELL_DTYPE, NAVFIELD_GOAL_DTYPE, NAVSIGHT_HIT_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, NAVCROWD_AGENT_DTYPE, NAVFIELD_CELL_DTYPE, NAVFIELD_GOAL_DTYPE, NAVSIGHT_HIT_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
 from .modifiers import AmbientOcclusion, LodParams, NavErodeParams, NavParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
 
 
@@ -601,6 +601,53 @@ class Extractor:
         paths, lengths = np.full((len(s), max(int(max_len), 0)), -1, np.int32), np.zeros(len(s), np.int32)
         self._check(self._L.vtmc_navfield_trace_smooth(self._h, _ptr(s), len(s), int(max_len), ctypes.byref(p), _ptr(paths), _ptr(lengths)))
         return paths, lengths
+
+    # -- a crowd stepped along the flow field the context holds (include/vtmc_navcrowd.h) -----------------------------
+    def navcrowd_spawn(self, spans, speeds):
+        """Replaces the crowd: agent i asks for spans[i] (a span of the nav result held, or -1) and earns speeds[i] (one value for all, or
+        one per agent) cost units per tick.  Where several ask for one span the smallest index stands on it; the others, and the -1s, are
+        UNPLACED.  Returns the number of placed agents."""
+        s = np.ascontiguousarray(spans, np.int32).reshape(-1)
+        v = np.asarray(speeds, np.int64)
+        if v.ndim == 0:
+            v = np.full(len(s), int(v), np.int64)
+        if v.shape != s.shape or (v < 0).any() or (v > 0xffffffff).any():
+            raise ValueError("navcrowd_spawn needs one speed, or as many as spans, in 0..2^32-1")
+        v, n = np.ascontiguousarray(v, np.uint32), ctypes.c_int32()
+        self._check(self._L.vtmc_navcrowd_spawn(self._h, _ptr(s), _ptr(v), len(s), ctypes.byref(n)))
+        return n.value
+
+    def navcrowd_step(self, params, n_ticks=1):
+        """n_ticks ticks of the crowd along the flow field held, for a NavCrowdParams (or a vtmc_navcrowd_params struct); nothing is copied
+        back.  Returns navcrowd_info()."""
+        p = _struct(params)
+        self._check(self._L.vtmc_navcrowd_step(self._h, ctypes.byref(p), int(n_ticks)))
+        return self.navcrowd_info()
+
+    def navcrowd_info(self):
+        """(agents, occupying agents, arrived agents: ARRIVED plus GONE, ticks since the spawn, moves of the last tick) of the crowd."""
+        v = [ctypes.c_int32() for _ in range(5)]
+        self._check(self._L.vtmc_navcrowd_info(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def navcrowd_read(self, occupancy=True):
+        """(agents, occupancy): the records (NAVCROWD_AGENT_DTYPE: span, budget, speed, state) and, per span of the nav result, the index
+        of the agent that occupies it or -1 (None when not asked for)."""
+        agents = np.zeros(self.navcrowd_info()[0], NAVCROWD_AGENT_DTYPE)
+        occ = None
+        if occupancy:
+            n = ctypes.c_int32()
+            self._check(self._L.vtmc_nav_info(self._h, None, None, ctypes.byref(n)))
+            occ = np.zeros(n.value, np.int32)
+        self._check(self._L.vtmc_navcrowd_read(self._h, _ptr(agents), len(agents), _ptr(occ)))
+        return agents, occ
+
+    def device_navcrowd(self):
+        """(device address of the agent records, device address of the occupancy words, the number of agents) of the crowd; valid until the
+        next navcrowd_spawn, terrain_nav, nav_erode, terrain_init, terrain_load or close."""
+        a, o, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int32()
+        self._check(self._L.vtmc_navcrowd_device_results(self._h, ctypes.byref(a), ctypes.byref(o), ctypes.byref(n)))
+        return a.value, o.value, n.value
 
     # -- material layer: VoxelTerrain.SetControlMap's splat volumes in HBM, paint, and per-vertex weights -------------
     def material_init(self, fineness):

@@ -527,6 +527,22 @@ class NavSightParams:
         return s
 
 
+class NavCrowdParams:
+    """The parameters of Extractor.navcrowd_step: how much a step may cost above the cheapest one when that one is taken, in the field's
+    cost units; None: any (NAVCROWD_ANY_DETOUR), an agent sidesteps to whatever neighbour lies nearer the goal.  leave_on_arrival: an agent
+    that arrives leaves the crowd (GONE) and frees its span, where otherwise it stays on it (ARRIVED)."""
+
+    def __init__(self, max_detour=None, leave_on_arrival=False):
+        if max_detour is not None and (isinstance(max_detour, bool) or int(max_detour) != max_detour or not 0 <= max_detour < _lib.NAVCROWD_ANY_DETOUR):
+            raise ValueError("nav crowd max_detour must be None or an integer in 0..2^32-2")
+        self._detour, self._flags = _lib.NAVCROWD_ANY_DETOUR if max_detour is None else int(max_detour), _lib.NAVCROWD_LEAVE_ON_ARRIVAL if leave_on_arrival else 0
+
+    def to_struct(self):
+        s = _lib.NavCrowdParamsStruct()
+        s.max_detour, s.flags, s.reserved[0], s.reserved[1] = self._detour, self._flags, 0, 0
+        return s
+
+
 class NavFieldParams:
     """The parameters of Extractor.nav_field: what a unit of height climbed and a unit dropped add to a step's cost, in level steps (a
     level step costs NAVFIELD_UNIT), both in [0, 1024], and the cost beyond which a span counts as unreached.  The costs are dimensionless
