@@ -21,6 +21,15 @@ and, in the third generation (generation=3: worlds b and c, SEEDS3, N_OPS3),
   ("nav", (lower, upper), agent_height, max_step)                     vtmc_terrain_nav_build (samples, grid units)
   ("field", ((fraction, cost), ...), climb, drop, max_cost)           vtmc_navfield_build; goals at fractions of the largest region's spans
   ("walk", seed, max_len)                                             N_AGENTS positions (walk_agents) located and traced
+and, in the fourth generation (generation=4: worlds b and c, SEEDS4, N_OPS4),
+  ("distance", radius, flags)   ("erode", radius, flags)                 vtmc_nav_distance_build, vtmc_nav_erode (columns; NAVERODE_OPEN_BOX_FACES or 0)
+  ("nav", (lower, upper), agent_height, max_step, max_spans)              a nav build that fails where the box holds more spans than max_spans
+  ("field", picks, climb, drop, max_cost) with a goal cost above max_cost  the field build the library refuses (VTMC_ERR_INVALID_ARG)
+  ("sight", seed, n)                                                      n pairs of spans or -1 (sight_pairs) through vtmc_nav_sight
+  ("smooth", seed, max_len, max_look, max_extra_cost or None)             walk_agents' positions located and traced by vtmc_navfield_trace_smooth
+  ("spawn", seed, every)                                                  vtmc_navcrowd_spawn on every every-th span, duplicates and -1s among them (spawn_requests)
+  ("step", max_detour or None, flags, ticks)                              vtmc_navcrowd_step
+  ("nothing",)                                                            every call of the four layers, where the context must hold none of them
 with ("detach", dict(max_samples=...), (lower, upper)) among the specs of a queue.  How many ids a capturing query takes only the session
 knows, so what refers to a captured stamp is written symbolically -- the spec ("fragment_paste", dict(query=q, rank=k)) and the operation
 ("stamp_destroy", ("fragment", q, k)) -- and made concrete by Session.concrete(op) when its turn comes.
@@ -36,7 +45,11 @@ For the third generation it also holds the rules of the three layers that live b
 method that keeps it: the scatter instances (every producer of a result drops them; paint, the attribute passes and a nav build do
 not), the nav result (a snapshot of the grid at its build: kept by everything but a load) and the flow field on it (dropped by a nav
 build and by a load, not by an edit).  A detach modifier takes its event number in queue order, is journaled by its box and dirties its
-box's blocks, also when it removes nothing; a fragment query changes nothing but the stamps it captures."""
+box's blocks, also when it removes nothing; a fragment query changes nothing but the stamps it captures.
+For the fourth generation it holds what stands on the nav result beside the field: the border distance and the origin of an erosion
+(include/vtmc_naverode.h) and the crowd (include/vtmc_navcrowd.h), each a twin's result (naverode_twin, navcrowd_twin), with the rule
+that keeps or drops it quoted at the method; the line of sight and the smoothed trace (navsight_twin) keep nothing."""
+import hashlib
 import os
 
 import numpy as np
@@ -49,7 +62,11 @@ import lod_twin
 import material_twin
 import mesh_twin
 import nav_twin
+import navcrowd_twin
+import naverode_twin
 import navfield_twin
+import navsight_twin
+from nav_support import speeds_of
 import path_twin
 import scatter_twin
 import stamp_twin
@@ -88,6 +105,12 @@ FAMILIES3 = FAMILIES2 + ("detach",)
 N_AGENTS = 64                                      # of a walk operation
 FIELD_CUT = 12 * _lib.NAVFIELD_UNIT                # a max_cost that cuts: twelve level steps
 NO_CUT = 0x7fffffff
+# the fourth generation (generate(..., generation=4)): the third one's deck and set pieces and, between them, set pieces about the border
+# distance, the erosion, the line of sight, the smoothed trace and the crowd, and about every call that must keep or drop them.
+SEEDS4 = {"b": (4, 5), "c": (4, 5)}             # chosen so that the fourth generation's conditions hold
+N_OPS4 = 294
+MAX_TICKS = 32                                     # of a step operation
+NO_SPANS = 10                                      # a max_spans below the span count of any band of 16 x 16 columns with ground in it
 SCATTER_KEYS = ("density", "min_up", "max_up", "min_y", "max_y", "material_channel", "seed")   # of scatter_twin.scatter, among a scatter operation's
 
 
@@ -243,6 +266,11 @@ class Session:
         # nav_key = (box, agent_height, max_step); field: navfield_twin's cells on it, with the goals they were built from
         self.scatter = self.scatter_result = None
         self.nav = self.nav_key = self.field = self.field_goals = None
+        # the fourth generation's: dist, the border distances of the nav result held; origin, of the last erosion, held beside the eroded
+        # spans; erosions, the (radius, flags) the nav result held went through since its build; crowd, a navcrowd_twin.Crowd on its links;
+        # field_costs, the (climb, drop) of the field held, from which the edge costs the smoothed trace and the crowd read are made
+        self.dist = self.origin = self.crowd = self.field_costs = self._edge_costs = None
+        self.erosions, self._builds = [], {}
         self.captured = []           # per capturing fragment query, the fragments it captured, largest first: dict(sid, first, dims, rec, n, mask, grid)
         self.captured_ids = {}       # stamp id -> that dict
         self.detaches, self.pastes = [], []      # a note per detach modifier that ran, and per paste of a captured stamp
@@ -431,6 +459,7 @@ class Session:
         self.loads += 1
         self.layer = None
         self.nav = self.nav_key = self.field = self.field_goals = None    # include/vtmc_nav.h, vtmc_navfield.h: valid until vtmc_terrain_load
+        self._drop_with_nav()
         dirty = block_list(range(self.nb[0] * self.nb[1] * self.nb[2]), self.nb)
         self._produced("terrain", "save_load", dirty)
         return dirty
@@ -561,30 +590,74 @@ class Session:
         self.seen["instances"] += len(want[0])
         return want
 
-    def nav_build(self, box, agent_height, max_step):
+    def _drop_with_nav(self):
+        """include/vtmc_naverode.h: "vtmc_terrain_nav_build (also one that fails after it invalidated the nav result), vtmc_terrain_init,
+        vtmc_terrain_load and vtmc_destroy drop the distance and the origin with the nav result."  include/vtmc_navcrowd.h: the crowd
+        "belongs to the nav result it was spawned on: vtmc_terrain_nav_build drops it (also a build that fails after it invalidated the
+        nav result), and so do vtmc_nav_erode, vtmc_terrain_init, vtmc_terrain_load and vtmc_destroy"."""
+        self.dist = self.origin = self.crowd = None
+        self.erosions = []
+
+    def nav_build(self, box, agent_height, max_step, max_spans=1 << 20):
         """vtmc_terrain_nav_build (include/vtmc_nav.h): nav_twin.build on the model's grid as it is now, kept whole -- "a snapshot of the
-        grid at build time: later edits do not invalidate it".  include/vtmc_navfield.h: the build drops the field."""
-        first, ext = self.sample_box(box)
-        self.nav, self.nav_key = nav_twin.build(np.array(self.ref.grid), first, ext, agent_height, max_step), (box, agent_height, max_step)
+        grid at build time: later edits do not invalidate it".  include/vtmc_navfield.h: the build drops the field, "also a build that
+        fails after it invalidated the nav result": more spans than max_spans is such a failure (VTMC_ERR_TOO_LARGE), None here, and
+        the context then holds no nav result at all."""
+        built = self._built(box, agent_height, max_step)
         self.field = self.field_goals = None
+        self._drop_with_nav()
+        if len(built[0]) > max_spans:
+            self.nav = self.nav_key = None
+            return None
+        self.nav, self.nav_key = built, (box, agent_height, max_step)
         self.seen["spans"] += len(self.nav[0])
         return self.nav
+
+    def _built(self, box, agent_height, max_step):
+        """nav_twin.build of the grid as it is now; the last few are remembered by the grid's bytes, for the rebuild of a box on a grid that
+        an undo has put back."""
+        first, ext = self.sample_box(box)
+        grid = np.array(self.ref.grid)
+        key = (hashlib.sha256(grid.tobytes()).digest(), tuple(first), tuple(ext), agent_height, max_step)
+        if key not in self._builds:
+            if len(self._builds) >= 8:
+                self._builds.pop(next(iter(self._builds)))
+            self._builds[key] = nav_twin.build(grid, first, ext, agent_height, max_step)
+        return self._builds[key]
 
     def goals_of(self, picks):
         """(span, cost) pairs of goal picks ((fraction, cost), ...): the span at that fraction of the index list of the largest region."""
         spans = self.nav[0]
+        if not len(spans):
+            return []
         regions, counts = np.unique(spans["region"], return_counts=True)
         inside = np.nonzero(spans["region"] == regions[np.argmax(counts)])[0]
         return [(int(inside[min(int(frac * len(inside)), len(inside) - 1)]), int(cost)) for frac, cost in picks]
 
     def field_build(self, picks, climb, drop, max_cost):
-        """vtmc_navfield_build (include/vtmc_navfield.h) on the nav snapshot held; None where the device answers VTMC_ERR_NO_RESULT."""
+        """vtmc_navfield_build (include/vtmc_navfield.h) on the nav snapshot held; None where the device answers VTMC_ERR_NO_RESULT,
+        "invalid" where it answers VTMC_ERR_INVALID_ARG "(the previous field is kept)": "a goal cost above max_cost", or no span to
+        put a goal on.  include/vtmc_navcrowd.h: "vtmc_navfield_build KEEPS it: that is the re-route" -- the crowd held walks the new
+        field from its next tick on; a refused build leaves the field and the crowd as they were."""
         if self.nav is None:
             return None
-        self.field_goals = self.goals_of(picks)
+        goals = self.goals_of(picks)
+        if not goals or any(cost > max_cost for _, cost in goals):
+            return "invalid"
+        self.field_goals = goals
         self.field = navfield_twin.field(self.nav[0], self.field_goals, climb, drop, max_cost)
+        self.field_costs, self._edge_costs = (climb, drop), None
+        if self.crowd is not None:
+            self.crowd.set_field(self.field, self.edge_costs())
         self.seen["reached"] += int((self.field["cost"] != _lib.NAVFIELD_UNREACHED).sum())
         return self.field
+
+    def edge_costs(self):
+        """navfield_twin.edge_costs of the spans held with the climb and the drop of the field held: what the field build leaves behind
+        for the smoothed trace and the crowd."""
+        if self._edge_costs is None:
+            self._edge_costs = navfield_twin.edge_costs(self.nav[0], *self.field_costs)
+        return self._edge_costs
 
     def walk(self, seed, max_len):
         """N_AGENTS agents located (vtmc_nav_locate) and traced (vtmc_navfield_trace) on the snapshots held, whatever the grid has become.
@@ -601,11 +674,86 @@ class Session:
         self.seen["located"] += int((located >= 0).sum())
         return pos, below, above, located, traced
 
+    # -- the fourth generation: border distance, erosion, line of sight, smoothed traces, the crowd --------------------------------------
+    def distance(self, radius, flags):
+        """vtmc_nav_distance_build (include/vtmc_naverode.h): naverode_twin.distance on the nav result held; returns the border count,
+        or None where the device answers VTMC_ERR_NO_RESULT.  "The nav result and the flow field stay", and so does the crowd: "no call
+        changes anything else the context holds" but what the Life cycle names."""
+        if self.nav is None:
+            return None
+        self.dist = naverode_twin.distance(self.nav, radius, flags)[0]
+        return int(naverode_twin.border(self.nav, flags).sum())
+
+    def erode(self, radius, flags):
+        """vtmc_nav_erode (include/vtmc_naverode.h): "REPLACES the nav result the context holds ... it drops the flow field and the
+        distance, which both describe the old spans, and leaves the origin valid until the next vtmc_nav_erode or
+        vtmc_terrain_nav_build"; include/vtmc_navcrowd.h: the erosion drops the crowd.  A second erosion works on the eroded spans, and
+        its origin indexes those.  Returns naverode_twin.erode's (spans, offsets, first, ext, origin), or None without a nav result."""
+        if self.nav is None:
+            return None
+        out = naverode_twin.erode(self.nav, radius, flags)
+        self.nav, self.origin = out[:4], out[4]
+        self.field = self.field_goals = self.dist = self.crowd = None
+        self.erosions.append((radius, flags))
+        return out
+
+    def rebuilt(self):
+        """The nav result the parameters of the one held give on the grid as it is NOW, its erosions repeated: what a library that
+        rebuilt on an edit would hold."""
+        now = self._built(*self.nav_key)
+        for radius, flags in self.erosions:
+            now = naverode_twin.erode(now, radius, flags)[:4]
+        return now
+
+    def sight(self, seed, n):
+        """vtmc_nav_sight (include/vtmc_navsight.h) for sight_pairs of the nav result held: "needs a nav result only".  Returns (from,
+        to, hits): hits by navsight_twin, or None where the device answers VTMC_ERR_NO_RESULT."""
+        a, b = sight_pairs(self.nav, seed, n)
+        return a, b, None if self.nav is None else navsight_twin.Walker(self.nav).sight(a, b)
+
+    def smooth(self, seed, max_len, max_look, max_extra_cost):
+        """walk_agents' positions located as walk locates them and smoothed (vtmc_navfield_trace_smooth, include/vtmc_navsight.h: "it
+        reads the nav result, the cells and the edge costs the field build left"; "needs a field").  max_extra_cost None: any.  Returns
+        walk's tuple, with the smoothed (paths, lengths) for the traced ones."""
+        w = self.world
+        pos = walk_agents(self.nav, w, seed)
+        scale = f32(w["scale"])
+        below, above = float(f32(1.0) * scale), float(f32(1.25) * scale)
+        if self.nav is None:
+            return pos, below, above, None, None
+        located = navfield_twin.locate(self.nav, w["origin"], w["scale"], pos, f32(below) / scale, f32(above) / scale)
+        if self.field is None:
+            return pos, below, above, located, None
+        extra = navsight_twin.ANY if max_extra_cost is None else max_extra_cost
+        return pos, below, above, located, navsight_twin.Walker(self.nav, self.edge_costs()).smooth(self.field, located, max_len, max_look, extra)
+
+    def spawn(self, seed, every):
+        """vtmc_navcrowd_spawn (include/vtmc_navcrowd.h) for spawn_requests of the nav result held: "needs a nav result only", replaces
+        the crowd.  Returns (spans, speeds, placed); placed None where the device answers VTMC_ERR_NO_RESULT."""
+        spans, speeds = spawn_requests(0 if self.nav is None else len(self.nav[0]), seed, every)
+        if self.nav is None:
+            return spans, speeds, None
+        self.crowd = navcrowd_twin.Crowd(self.nav[0]["link"])
+        if self.field is not None:
+            self.crowd.set_field(self.field, self.edge_costs())
+        return spans, speeds, self.crowd.spawn(spans, speeds)
+
+    def step(self, max_detour, flags, ticks):
+        """vtmc_navcrowd_step: navcrowd_twin's ticks; returns the info, or None for VTMC_ERR_NO_RESULT -- "step when it holds no crowd or
+        no field" -- which leaves the crowd untouched.  max_detour None: any."""
+        if self.crowd is None or self.field is None:
+            return None
+        return self.crowd.step(navcrowd_twin.ANY if max_detour is None else max_detour, flags, ticks)
+
+    def nothing(self):
+        """What stands on a nav result, and the nav result: all None where a "nothing" operation is due."""
+        return dict(nav=self.nav, field=self.field, dist=self.dist, origin=self.origin, crowd=self.crowd)
+
     # -- driving ----------------------------------------------------------------------------------------------------------------------
     def run(self, op, tmp_dir):
         """One operation of generate() on the model alone; returns what the method returns."""
         name = op[0]
-        if name in ("fragments", "scatter", "nav", "field", "walk"):
+        if name in ("fragments", "scatter", "nav", "field", "walk", "distance", "erode", "sight", "smooth", "spawn", "step", "nothing"):
             out = getattr(self, {"scatter": "scatter_surface", "nav": "nav_build", "field": "field_build"}.get(name, name))(*op[1:])
         elif name == "update":
             out = self.update(op[1])
@@ -672,6 +820,34 @@ def walk_agents(nav, w, seed):
         g[0:8, 0] = first[0] - rng.uniform(1.0, 4.0, 8)
         g[8:16, 1] = dims[1] + 5.0
     return (o + g * s).astype(f32)
+
+
+def sight_pairs(nav, seed, n):
+    """(from, to) of a sight operation, n int32 each, drawn from -1..n_spans-1 of the nav result: the first quarter a few spans apart (the
+    spans are ordered by column, so these stand near each other along x), the rest anywhere; a -1 in the first `from` and in the second
+    `to`.  Without a nav result, or without a span: all -1."""
+    rng = np.random.default_rng([seed, 44])
+    spans = 0 if nav is None else len(nav[0])
+    a, b = rng.integers(-1, spans, (2, n)) if spans else np.full((2, n), -1)
+    near = n // 4
+    if spans:
+        b[:near] = np.clip(a[:near] + rng.integers(-4, 5, near), 0, spans - 1)
+        a[:near] = np.maximum(a[:near], 0)
+    a[:1], b[1:2] = -1, -1
+    return a.astype(np.int32), b.astype(np.int32)
+
+
+def spawn_requests(n_spans, seed, every):
+    """(spans, speeds) of a spawn operation: every every-th span of the n_spans, an eighth of the requests then set to the span of another
+    request (duplicates) and a sixteenth to -1; at least three requests, -1 where there is no span to ask for.  Speeds by speeds_of."""
+    rng = np.random.default_rng([seed, 55])
+    want = np.arange(0, n_spans, every, dtype=np.int64)
+    if len(want):
+        k = max(len(want) // 8, 2)
+        want[rng.integers(0, len(want), k)] = want[rng.integers(0, len(want), k)]
+        want[rng.integers(0, len(want), max(len(want) // 16, 1))] = -1
+    want = np.concatenate([want, np.full(max(3 - len(want), 0), -1)])
+    return want.astype(np.int32), speeds_of(len(want))
 
 
 # -- the generator ----------------------------------------------------------------------------------------------------------------------
@@ -942,6 +1118,16 @@ class _Draw:
     def walk(self, max_len=512):
         return ("walk", int(self.rng.integers(0, 1 << 30)), max_len)
 
+    # -- the fourth generation -----------------------------------------------------------------------------------------------------------
+    def sight(self, n=N_AGENTS):
+        return ("sight", int(self.rng.integers(0, 1 << 30)), n)
+
+    def smooth(self, max_len=64, max_look=8, max_extra_cost=None):
+        return ("smooth", int(self.rng.integers(0, 1 << 30)), max_len, max_look, max_extra_cost)
+
+    def spawn(self, every):
+        return ("spawn", int(self.rng.integers(0, 1 << 30)), every)
+
 
 def _operations1(d, n_ops):
     """The first generation's operations, without the first set_history."""
@@ -1124,10 +1310,11 @@ def _operations2(d, world, n_ops, more_deck=(), more_extras=(), more=None):
     return ops
 
 
-def _operations3(d, world, n_ops):
+def _operations3(d, world, n_ops, more_extras=(), more_pieces=None):
     """The third generation: the second one's deck and extras with a detach modifier on the low faces, on the high faces, on block faces
     and anywhere, and between the queues the set pieces the conditions of test_terrain_session.py ask for -- each a fixed sequence of
-    operations about one place, so that what the condition needs follows from the sequence and not from luck."""
+    operations about one place, so that what the condition needs follows from the sequence and not from luck.  The fourth generation
+    hands in what it adds: more_extras, names shuffled among the extras, and more_pieces(name, ops, tools), which appends such a piece."""
     r, s = d.rng, d.scale
     noise = lambda tools: ("update", tools["queue_of"]([(KINDS[int(r.integers(6, 9))], "free")]))   # noqa: E731  a queue that draws
 
@@ -1179,22 +1366,77 @@ def _operations3(d, world, n_ops):
             ops += [("nav", d.band(), 3, 0.5), d.field(1024.0, 0.0), d.scatter(), ("save_load",), d.field(1.0, 1.0), d.walk()]
         elif arg == "walk":
             ops.append(d.walk())
+        elif more_pieces is not None:
+            more_pieces(arg, ops, tools)
         else:
             raise AssertionError(arg)
 
-    more_extras = ["dig", "debris", "lost", "fragments:all", "scatter:paint", "scatter:load", "scatter:undo", "scatter:lod", "nav:whole", "nav:edit",
-                   "nav:load", "walk", "walk"]
-    return _operations2(d, world, n_ops, [("detach", m) for m in ("low", "high", "block", "free")], more_extras, more)
+    extras = ["dig", "debris", "lost", "fragments:all", "scatter:paint", "scatter:load", "scatter:undo", "scatter:lod", "nav:whole", "nav:edit",
+              "nav:load", "walk", "walk"]
+    return _operations2(d, world, n_ops, [("detach", m) for m in ("low", "high", "block", "free")], extras + list(more_extras), more)
+
+
+def _operations4(d, world, n_ops):
+    """The fourth generation: the third one's deck, extras and set pieces and, shuffled among them, the set pieces about what stands on a
+    nav result -- the border distance, the erosion and its origin, the line of sight, the smoothed trace and the crowd -- each a fixed
+    sequence, so that what holds them and what drops them follows from the sequence."""
+    r = d.rng
+    OPEN = _lib.NAVERODE_OPEN_BOX_FACES
+    LEAVE = _lib.NAVCROWD_LEAVE_ON_ARRIVAL
+    lod_level = LOD_MAX_LEVEL if world == "c" else 0
+
+    def pieces(arg, ops, tools):
+        if arg == "crowd:whole":     # a crowd on the whole grid held across one of everything that must keep it, stepped on the way, then re-routed
+            p = d.piece(*d.site())
+            ops += [("nav", d.whole(), 2, 1.0), d.field(2.5, 0.5), d.spawn(3), ("step", None, 0, 24), ("material_init", 1)]
+            smooth = d.smooth()
+            keepers = [("update", [p["clear"], p["big"], p["small"]]), ("undo",), ("redo",), ("paint", d.strokes(1)), d.attributes(), d.scatter(), ("fragments", p["box"], 0, 8),
+                       ("update", tools["queue_of"]([("detach", "free")])), ("lod", CORNER_VIEWER, lod_level, 1.0), ("set_history", float(r.uniform(2.6, 3.6))),
+                       ("probe", int(r.integers(0, 1 << 30))), d.walk(), d.sight(), smooth, smooth[:4] + (0,), ("distance", 2, 0), d.field(2.5, 0.5, 4000)]
+            d.ids_known, d.queries = False, d.queries + 1          # the fragment query captures
+            steps = [("step", 0, 0, 8), ("step", 2048, 0, 8), ("step", None, 0, 8), ("step", 0, 0, 4), ("step", None, 0, 8), ("step", 1024, 0, 4)]
+            for k, op in enumerate(keepers):
+                ops.append(op)
+                if k % 3 == 2:
+                    ops.append(steps[k // 3])
+            ops += [d.field(0.5, 2.0), ("step", None, 0, 16)]       # other goals and other costs: the re-route
+        elif arg == "crowd:edit":    # a crowd held across an edit of its box and the undo; the rebuild drops it; a spawn before any field
+            box = d.interior()
+            ops += [("nav", box, 1, 1.5), d.field(1.0, 0.25), d.spawn(2), ("step", 2048, LEAVE, 16), d.smooth(max_len=4)]
+            tools["edit_undo"]()
+            ops += [("undo",), ("step", None, LEAVE, 8), ("nav", box, 1, 1.5), ("step", None, 0, 4), d.spawn(2), ("step", 0, 0, 4), d.field(0.0, 0.0),
+                    ("step", 0, LEAVE, 16)]
+        elif arg == "erode:chain":   # two erosions, the second of the first one's spans; the origin across an edit; what each drops
+            box = d.band()          # the edit: a bowl dug where the first update's plane crosses the middle of the box
+            middle = (0.5 * (box[0][0] + box[1][0]), d.pos(d.top[1] // 2, 1) + 0.375 * d.scale, 0.5 * (box[0][2] + box[1][2]))
+            ops += [("nav", box, 2, 1.0), ("distance", 3, 0), d.field(2.5, 0.5), d.spawn(2), ("step", None, LEAVE, 12), ("erode", 2, 0),
+                    ("update", [("sphere", (middle, 3.5 * d.scale, False))])]
+            ops += [("undo",), d.field(2.5, 0.5), d.smooth(), d.spawn(2), ("step", 1024, 0, 12), ("erode", 1, OPEN), ("distance", 2, OPEN),
+                    d.field(1.0, 1.0), d.smooth(max_extra_cost=0), ("nav", d.band(), 2, 1.0)]
+        elif arg == "erode:load":    # everything held, then a load
+            ops += [("nav", d.band(), 2, 1.0), ("erode", 1, 0), ("distance", 2, 0), d.field(2.5, 0.5), d.spawn(3), ("step", None, 0, 8), ("save_load",),
+                    ("nothing",)]
+        elif arg == "nav:fail":      # everything held, then a nav build that fails after it invalidated the result
+            box = d.band()
+            ops += [("nav", box, 1, 1.5), ("erode", 1, OPEN), ("distance", 3, OPEN), d.field(1.0, 0.25, FIELD_CUT), d.spawn(2), ("step", 0, LEAVE, 8),
+                    ("nav", box, 1, 1.5, NO_SPANS), ("nothing",)]
+        elif arg == "erode:empty":   # an erosion that keeps no span (a band is at most 24 columns wide: no span is 16 columns from its faces), and the calls on 0 spans
+            ops += [("nav", d.band(), 2, 1.0), ("erode", 16, 0), ("distance", 2, 0), d.sight(0), d.spawn(1)]
+        else:
+            raise AssertionError(arg)
+
+    return _operations3(d, world, n_ops, ["crowd:whole", "crowd:edit", "erode:chain", "erode:load", "nav:fail", "erode:empty"], pieces)
 
 
 def generate(seed, world, n_ops=None, history_from_start=True, generation=1):
     """The session (seed, world) as a list of n_ops operations (N_OPS, or N_OPS2 for generation 2).  history_from_start False: the same
     list with the history switched on a third of the way in instead of before the first update (budget changes before that point switch
-    it off again).  generation 2: its own deck, seeds and length (_operations2); generation 3 likewise (_operations3)."""
-    n_ops = n_ops or {1: N_OPS, 2: N_OPS2, 3: N_OPS3}[generation]
+    it off again).  generation 2: its own deck, seeds and length (_operations2); generations 3 and 4 likewise (_operations3, _operations4)."""
+    n_ops = n_ops or {1: N_OPS, 2: N_OPS2, 3: N_OPS3, 4: N_OPS4}[generation]
     d = _Draw(seed, world, generation)
     s = d.scale
-    ops = {1: lambda: _operations1(d, n_ops), 2: lambda: _operations2(d, world, n_ops), 3: lambda: _operations3(d, world, n_ops)}[generation]()
+    ops = {1: lambda: _operations1(d, n_ops), 2: lambda: _operations2(d, world, n_ops), 3: lambda: _operations3(d, world, n_ops),
+           4: lambda: _operations4(d, world, n_ops)}[generation]()
     # budgets relative to the session's own median step size
     ref = type("Shape", (), dict(dims=d.dims, scale=s, origin=np.asarray(d.origin, f32)))
     sizes = [sum(image_bytes(box_of(ref, gpu_struct(sp))[1]) for sp in op[1] if sp[0] != "fragment_paste") for op in ops if op[0] == "update"]

@@ -19,7 +19,7 @@ import naverode_twin
 import navcrowd_twin as twin
 from host_check import run_host_check
 import nav_support as nav
-from nav_support import flat_grid, nav_of
+from nav_support import flat_grid, nav_of, speeds_of
 from terrain_twin import no_result
 
 ROOT = nav.ROOT
@@ -34,10 +34,6 @@ CLIMB, DROP = 1.0, 0.5
 
 def raw(detour=ANY, flags=0, reserved=(0, 0)):
     return _lib.NavCrowdParamsStruct(detour, flags, (ctypes.c_uint32 * 2)(*reserved))
-
-
-def speeds_of(count):
-    return [300 + (7919 * i) % 1500 for i in range(count)]
 
 
 def spread_goals(spans, count=3):

@@ -2,7 +2,7 @@
 of the shared box walk (64 lanes along x, 4 z-planes, runs of 16 along y) for every kernel that runs on it, the path kernel included, and
 the inclusive dirty rule on the device.
 
-Three generations of sessions, each pinned by digests of its operation lists before the next one was written.  The first (worlds a and
+Four generations of sessions, each pinned by digests of its operation lists before the next one was written.  The first (worlds a and
 b, soup output) is the edit loop alone.  The second (worlds b and c, one soup and one indexed session each) adds paths and pastes of
 mesh stamps to the deck and, between the queues, the consumers of the resident terrain: the material layer (init, paint, control map),
 the vertex weights and occlusion bytes of whatever result the context holds, the level-of-detail extract, ray and sphere queries and
@@ -14,6 +14,10 @@ EQUALITY.  What it is about is not the kernels -- each layer's own file covers t
 beside everything else: after EVERY operation of such a session assert_layers compares the nav result, the field and the instances the
 context holds with the ones the model holds (or VTMC_ERR_NO_RESULT with none), so each keep rule and each drop rule of include/vtmc.h,
 vtmc_nav.h and vtmc_navfield.h is tried against every producer a session holds, not only against the ones a directed test thought of.
+The fourth adds what stands on a nav result beside the field -- the border distance, the erosion and its origin, the line of sight, the
+smoothed trace and the crowd, against naverode_twin, navsight_twin and navcrowd_twin, for EQUALITY -- in set pieces that hold each of
+them across every call that must keep it and then make the call that must drop it; assert_layers4 adds the distance, the origin and the
+crowd to what is compared after every operation.
 
 CPU: the generator is deterministic and every committed seed meets the coverage conditions (conditions, not measurements: a seed that
 misses one is replaced, the condition stays); the history model gives the answers worked by hand below; the model's snapshots are
@@ -35,6 +39,7 @@ import ao_twin
 import material_twin
 import nav_support as nav
 import nav_twin
+import navcrowd_twin
 import navfield_twin
 import path_twin
 import scatter_twin
@@ -47,6 +52,8 @@ from surface_twin import Surface, check_tight, compare as compare_rays, referenc
 from terrain_twin import assert_triangles, bits, block_list, box_of, csg_write, gpu_struct, oracle_mod_of
 from test_sphere_queries import SphereSurface, check as check_spheres
 from test_terrain_fragments import same_records
+from test_terrain_navcrowd import raw as crowd_params
+from test_terrain_naverode import distance_of, raw as erode_params
 from test_terrain_scatter import assert_instances, mesh_of as scatter_mesh_of
 
 f32 = np.float32
@@ -352,23 +359,33 @@ IDS3 = ["%s-%d-%s" % (w, seed, "indexed" if indexed else "soup") for w, seed, in
 UNREACHED = _lib.NAVFIELD_UNREACHED
 
 
-def twin_run3(oracle_mod, tmp_path_factory, world, seed, indexed):
-    """A third-generation session on the model alone, once per case (in twin_run2's cache): the model after the last operation, the
-    concrete operations and a note per operation -- what it returned, in numbers, and what the model held after it.  `stale`: the nav
-    snapshot held differs from nav_twin.build of the model's grid as it is now, in the same box with the same parameters."""
-    key = (world, seed, indexed, 3)
+HELD = ("scatter", "nav", "field", "dist", "origin", "crowd")
+
+
+def held_of(s):
+    return {k: getattr(s, k) is not None for k in HELD}
+
+
+def twin_run3(oracle_mod, tmp_path_factory, world, seed, indexed, generation=3):
+    """A third-generation (or fourth-generation) session on the model alone, once per case (in twin_run2's cache): the model after the
+    last operation, the concrete operations and a note per operation -- what it returned, in numbers, and what the model held after it.
+    `stale`: the nav snapshot held differs from nav_twin.build of the model's grid as it is now, in the same box with the same
+    parameters (and through the same erosions)."""
+    key = (world, seed, indexed, generation)
     if key not in _runs2:
-        tmp = tmp_path_factory.mktemp("session3_%s%d" % (world, seed))
+        tmp = tmp_path_factory.mktemp("session%d_%s%d" % (generation, world, seed))
         s = Session(oracle_mod, world, indexed)
         n_blocks = s.nb[0] * s.nb[1] * s.nb[2]
-        ops, log, stale, builds = [], [], False, 0
-        for i, op in enumerate(generate(seed, world, generation=3)):
+        ops, log, stale, changed, builds, rerouted, wanted = [], [], False, False, 0, None, {"step", "origin"}
+        for i, op in enumerate(generate(seed, world, generation=generation)):
             op = s.concrete(op)
             ops.append(op)
             n = dict(i=i, name=op[0], op=op, prev=s.last, source=s.result_source, result=s.result, layer=s.layer is not None, loads=s.loads,
                      all_blocks=s.result == "terrain" and len(s.result_dirty) == n_blocks, n_detaches=len(s.detaches), n_pastes=len(s.pastes),
-                     draws=dict(s.draws_after), had=dict(scatter=s.scatter is not None, nav=s.nav is not None, field=s.field is not None))
+                     draws=dict(s.draws_after), had=held_of(s))
             grid = bits(s.ref.grid).copy()
+            crowd_before = None if s.crowd is None else (s.crowd.read(), (s.crowd.moves, s.crowd.lost, s.crowd.sidesteps))
+            nav_before = s.nav
             out = s.run(op, tmp)
             if op[0] == "fragments":
                 n.update(sizes=out[0]["n_samples"].tolist(), ids=out[1][out[1] > 0].tolist(), faces=st.faces_of(*s.sample_box(op[1]), s.ref.dims))
@@ -377,12 +394,17 @@ def twin_run3(oracle_mod, tmp_path_factory, world, seed, indexed):
                 if not isinstance(n["out"], str) and op[1].get("material_channel", -1) >= 0:      # the same without the channel filter
                     n["unfiltered"] = len(scatter_twin.scatter(*s.records(), s.world["scale"], s.world["origin"],
                                                                **{k: v for k, v in op[1].items() if k in st.SCATTER_KEYS and k != "material_channel"})[0])
+            elif op[0] == "nav" and out is None:
+                stale = False
+                n.update(failed=True)
             elif op[0] == "nav":
                 builds, stale = builds + 1, False
                 n.update(spans=len(out[0]), regions=len(np.unique(out[0]["region"])), box=(out[2], out[3]), faces=st.faces_of(out[2], out[3], s.ref.dims))
             elif op[0] == "field":
-                n["out"] = "refused" if out is None else int((out["cost"] != UNREACHED).sum())
-                if out is not None:
+                n["out"] = "refused" if out is None else out if isinstance(out, str) else int((out["cost"] != UNREACHED).sum())
+                if crowd_before is not None and not isinstance(n["out"], str):      # a re-route: who stands ARRIVED as it comes
+                    rerouted = np.nonzero(crowd_before[0][0]["state"] == navcrowd_twin.ARRIVED)[0]
+                if not isinstance(n["out"], str):
                     n["spans"] = len(out)
                     n["uncut"] = int((navfield_twin.field(s.nav[0], s.field_goals, op[2], op[3])["cost"] != UNREACHED).sum())
             elif op[0] == "walk":
@@ -394,11 +416,49 @@ def twin_run3(oracle_mod, tmp_path_factory, world, seed, indexed):
                     n.update(hits=int((located >= 0).sum()), misses=int((located < 0).sum()),
                              cut=int(((lengths == op[2]) & (s.field["next"][last] >= 0)).sum()), whole=int(((lengths > 1) & (lengths < op[2])).sum()),
                              unreached=int(((located >= 0) & (s.field["cost"][np.maximum(located, 0)] == UNREACHED)).sum()))
-            if s.nav is not None and op[0] != "nav" and not np.array_equal(grid, bits(s.ref.grid)):
-                now = nav_twin.build(np.array(s.ref.grid), *s.sample_box(s.nav_key[0]), *s.nav_key[1:])
+            elif op[0] == "probe" and generation >= 4:
+                ref = probe_reference(s, op[1])
+                n.update(ambiguous=sum(r["ambiguous"] for r in ref["rays"]), sphere_ambiguous=sum(r["kind"] == "ambiguous" for r in ref["casts"] + ref["balls"]))
+            elif op[0] == "distance":
+                n.update(out=out, spans=None if out is None else len(s.nav[0]))
+            elif op[0] == "erode" and out is not None:
+                n.update(before=len(nav_before[0]), kept=len(out[0]), regions_before=len(np.unique(nav_before[0]["region"])), regions=len(np.unique(out[0]["region"])),
+                         again=len(s.erosions) > 1)
+            elif op[0] == "sight" and out[2] is not None:
+                a, b, hits = out
+                n.update(pairs=len(a), visible=int(((a >= 0) & (b >= 0) & (hits["last"] == b)).sum()), minus=int(((a < 0) | (b < 0)).sum()),
+                         blocked=int(((a >= 0) & (b >= 0) & (hits["last"] != b) & (hits["steps"] >= 1)).sum()))
+            elif op[0] == "smooth":
+                located, rows = out[3], out[4]
+                n["out"] = "refused" if located is None else "located" if rows is None else "smoothed"
+                if rows is not None:
+                    paths, lengths = rows
+                    last = paths[np.arange(len(paths)), np.maximum(lengths, 1) - 1]
+                    n.update(rows=rows, rows3=int((lengths >= 3).sum()), cut=int(((lengths == op[2]) & (s.field["next"][last] >= 0)).sum()), eroded=bool(s.erosions))
+            elif op[0] == "spawn":
+                spans, _, placed = out
+                n.update(out=placed, asked=len(spans), minus=int((spans < 0).sum()), doubles=int((spans >= 0).sum()) - len(np.unique(spans[spans >= 0])))
+            elif op[0] == "step":
+                n["out"] = out
+                if out is None:
+                    n["same"] = crowd_before is None or all(x.tobytes() == y.tobytes() for x, y in zip(crowd_before[0], s.crowd.read()))
+                else:
+                    agents = s.crowd.read()[0]
+                    n.update(moves=s.crowd.moves - crowd_before[1][0], lost=s.crowd.lost - crowd_before[1][1], sidesteps=s.crowd.sidesteps - crowd_before[1][2])
+                    if rerouted is not None:     # of those that stood ARRIVED when the new field came: who walks again
+                        n["walk_again"] = int(((agents["state"][rerouted] == navcrowd_twin.WALKING) | (agents["span"][rerouted] != crowd_before[0][0]["span"][rerouted])).sum())
+                        rerouted = None
+            changed = op[0] != "nav" and (changed or not np.array_equal(grid, bits(s.ref.grid)))
+            # the fourth generation holds a nav result nearly all the time: it asks for `stale` at a step and at an edit under an origin, until
+            # each has been found once (a condition needs no second one)
+            if changed and s.nav is not None and (generation == 3 or (op[0] == "step" and "step" in wanted) or (s.origin is not None and "origin" in wanted)):
+                now, changed = s.rebuilt(), False
                 stale = not (nav_twin.nan_aware_equal(now[0], s.nav[0]) and np.array_equal(now[1], s.nav[1]))
-            n.update(last=s.last, build=builds if s.nav is not None else None, stale=stale and s.nav is not None, key=s.nav_key,
-                     held=dict(scatter=s.scatter is not None, nav=s.nav is not None, field=s.field is not None))
+                if stale and op[0] == "step" and n.get("moves"):
+                    wanted.discard("step")
+                if stale and op[0] == "update" and s.origin is not None:
+                    wanted.discard("origin")
+            n.update(last=s.last, build=builds if s.nav is not None else None, stale=stale and s.nav is not None, key=s.nav_key, held=held_of(s))
             log.append(n)
         _runs2[key] = (s, ops, log)
     return _runs2[key]
@@ -491,6 +551,105 @@ def test_generator_conditions_of_the_third_generation(oracle_mod, tmp_path_facto
     assert any(n["out"] == "located" for n in W) and any(n["out"] == "refused" for n in W), "a walk without a field, and one without a nav result"
     assert any(n["out"] == "traced" and n["hits"] and n["misses"] and n["cut"] and n["unreached"] for n in W), "a walk with hits, misses, a cut row and an unreached start"
     assert any(n["out"] == "traced" and n["whole"] and n["stale"] for n in W), "a walk traced to its goal on a snapshot the grid has left behind"
+
+
+# the third generation, pinned the same way: computed before the generator learnt its fourth generation
+DIGESTS3 = {("b", 0): "445ba96cc0c853f6", ("b", 1): "6d1da4e7be5d0ef3", ("c", 2): "347d257c070a092e", ("c", 3): "d40ed7efd0daf069"}
+
+
+@pytest.mark.parametrize("world,seed,indexed", CASES3, ids=IDS3)
+def test_third_generation_sessions_are_unchanged(world, seed, indexed):
+    assert set(DIGESTS3) == {(w, s) for w, s, _ in CASES3}
+    assert digest(generate(seed, world, generation=3)) == DIGESTS3[world, seed]
+
+
+# -- CPU: the fourth generation ------------------------------------------------------------------------------------------------------------
+CASES4 = [(w, seed, indexed) for w in sorted(st.SEEDS4) for seed, indexed in zip(st.SEEDS4[w], (False, True))]
+IDS4 = ["%s-%d-%s" % (w, seed, "indexed" if indexed else "soup") for w, seed, indexed in CASES4]
+NEW_OPS = ("distance", "erode", "sight", "smooth", "spawn", "step", "nothing")
+
+
+@pytest.mark.parametrize("world,seed,indexed", CASES4, ids=IDS4)
+def test_fourth_generation_is_deterministic_and_keeps_its_caps(world, seed, indexed):
+    ops = generate(seed, world, generation=4)
+    assert len(ops) == st.N_OPS4 <= 300 and plain(ops) == plain(generate(seed, world, generation=4))
+    assert plain(ops) != plain(generate(seed + 1000, world, generation=4)) and plain(ops[:20]) != plain(generate(seed, world, generation=3)[:20])
+    assert ops[0][0] == "set_history" and ops[0][1] > 0 and all(op[1] > 0 for op in ops if op[0] == "set_history")
+    names = [op[0] for op in ops]
+    for name, least in (("fragments", 7), ("scatter", 12), ("nav", 11), ("field", 13), ("walk", 10), ("distance", 6), ("erode", 5), ("sight", 2), ("smooth", 4),
+                        ("spawn", 7), ("step", 14), ("nothing", 2)):
+        assert names.count(name) >= least, (name, names.count(name))
+    assert all(1 <= op[3] <= st.MAX_TICKS <= 32 for op in ops if op[0] == "step")
+    assert all(op[2] <= st.N_AGENTS for op in ops if op[0] == "sight") and st.N_AGENTS <= 64
+    assert len(CASES4) == 4 and {w for w, _, _ in CASES4} == {"b", "c"} and [c[2] for c in CASES4] == [False, True, False, True]
+
+
+@pytest.mark.parametrize("world,seed,indexed", CASES4, ids=IDS4)
+def test_generator_conditions_of_the_fourth_generation(oracle_mod, tmp_path_factory, world, seed, indexed):
+    """Conditions, not measurements, per committed session; each with an assert of its own.  A seed that misses one is replaced, the
+    condition stays."""
+    s, ops, log = twin_run3(oracle_mod, tmp_path_factory, world, seed, indexed, generation=4)
+    names = [n["name"] for n in log]
+    print("%s %d %s: %s; seen %s" % (world, seed, "indexed" if indexed else "soup", {k: names.count(k) for k in ("nav", "field", "walk") + NEW_OPS}, s.seen))
+    for k in st.KINDS3:
+        assert s.kinds[k] >= 3, "every older category still occurs three times: %s %s" % (k, s.kinds)
+    granted = [n for n in log if not n["last"].endswith("!")]
+    # -- what keeps the crowd
+    live = [n for n in granted if n["had"]["crowd"] and n["had"]["field"]]
+    keepers = ("update", "undo", "redo", "lod", "set_history", "paint", "attributes", "scatter", "fragments", "probe", "walk", "sight", "smooth", "distance", "field")
+    for name in keepers:
+        mine = [n for n in live if n["name"] == name and (name != "paint" or n["layer"]) and (name not in ("attributes", "scatter") or n["result"] == "terrain")]
+        assert mine, "a live crowd is held across a %s" % name
+        assert all(n["held"]["crowd"] and n["held"]["field"] for n in mine), "%s keeps the crowd and the field" % name
+    assert any(n["name"] == "field" and n["out"] == "invalid" and n["held"]["crowd"] for n in live), "a refused field build beside a live crowd"
+    assert any(n["name"] == "fragments" and n["ids"] for n in live), "a capturing fragment query beside a live crowd"
+    assert any(n["name"] == "update" and any(sp[0] == "detach" for sp in n["op"][1]) for n in live), "a detach queue beside a live crowd"
+    # -- steps
+    S = [n for n in log if n["name"] == "step"]
+    ran = [n for n in S if n["out"] is not None]
+    assert any(n["stale"] and n["moves"] > 0 for n in ran), "a step that moves on a snapshot the grid has left behind"
+    assert any(n["moves"] >= 100 and n["lost"] >= 10 and n["sidesteps"] >= 10 for n in ran), "a contended step: %s" % [(n["moves"], n["lost"], n["sidesteps"]) for n in ran]
+    assert {n["op"][1] is None for n in ran} == {True, False} and any(n["op"][1] == 0 for n in ran), "both kinds of max_detour, 0 among them"
+    assert {n["op"][2] for n in ran} == {0, _lib.NAVCROWD_LEAVE_ON_ARRIVAL}, "both flag values"
+    assert any(n.get("walk_again", 0) >= 1 for n in ran), "a re-route after which an agent that had ARRIVED walks again"
+    refused = [n for n in S if n["out"] is None]
+    assert any(not n["had"]["crowd"] for n in refused), "a step refused for want of a crowd"
+    assert any(n["had"]["crowd"] and not n["had"]["field"] and n["held"]["crowd"] and n["same"] for n in refused), "a step refused for want of a field, the spawn as it was"
+    P = [n for n in log if n["name"] == "spawn" and n["out"] is not None]
+    assert any(n["doubles"] and n["minus"] and 0 < n["out"] < n["asked"] for n in P), "a spawn with duplicates and -1s"
+    assert any(not n["had"]["field"] and n["out"] > 0 for n in P), "a spawn before any field"
+    assert any(n["out"] == 0 and n["asked"] == n["minus"] == 3 for n in P), "a spawn of three -1 requests on a nav result of 0 spans"
+    assert any(n["name"] == "nav" and n["had"]["crowd"] and not n["held"]["crowd"] and not n.get("failed") for n in log), "a nav rebuild drops the crowd"
+    # -- erosion, distance, origin
+    E = [n for n in log if n["name"] == "erode" and "kept" in n]
+    assert any(1 <= n["kept"] <= n["before"] - 1 and n["regions"] != n["regions_before"] for n in E), "an erosion that keeps some spans and changes the region count: %s" % [(n["before"], n["kept"], n["regions_before"], n["regions"]) for n in E]
+    assert any(n["again"] and n["kept"] >= 1 for n in E), "an erosion of an eroded result"
+    assert any(n["kept"] == 0 and n["before"] > 0 for n in E), "an erosion that keeps none"
+    assert all(not n["held"]["field"] and not n["held"]["dist"] and not n["held"]["crowd"] and n["held"]["origin"] for n in E), "an erosion drops field, distance and crowd and holds the origin"
+    assert any(n["had"]["field"] and n["had"]["dist"] and n["had"]["crowd"] for n in E), "... all three held before it"
+    assert any(n["name"] == "update" and n["had"]["origin"] and n["held"]["origin"] and n["stale"] for n in log), "an origin held across an edit of its box"
+    assert any(n["name"] == "nav" and n["had"]["origin"] and not n["held"]["origin"] and n["held"]["nav"] for n in log), "an origin dropped by a nav build"
+    assert any(n["held"]["dist"] and n["held"]["crowd"] and n["held"]["field"] for n in log), "a distance beside a crowd and a field"
+    D = [n for n in log if n["name"] == "distance"]
+    assert any(n["out"] == 0 and n["spans"] == 0 for n in D) and any(n["out"] and n["out"] < n["spans"] for n in D), "a distance of 0 spans, and one with borders and inner spans"
+    # -- sight and smooth
+    G = [n for n in log if n["name"] == "sight" and "pairs" in n]
+    assert any(n["visible"] and n["blocked"] and n["minus"] for n in G), "a sight batch with visible pairs, blocked pairs and -1 pairs: %s" % [(n["visible"], n["blocked"], n["minus"]) for n in G]
+    assert any(n["pairs"] == 0 and not n["had"]["field"] for n in G), "a sight of 0 pairs"
+    M = [n for n in log if n["name"] == "smooth" and n["out"] == "smoothed"]
+    assert any(n["rows3"] for n in M), "a smoothed row of three waypoints or more"
+    assert any(n["cut"] and n["op"][2] == 4 for n in M), "a smoothed row cut at a max_len of 4"
+    pairs = [(a, b) for a, b in zip(M, M[1:]) if b["i"] == a["i"] + 1 and a["op"][1:4] == b["op"][1:4] and a["op"][4] is None and b["op"][4] == 0]
+    assert any(a["rows"][0].tobytes() != b["rows"][0].tobytes() for a, b in pairs), "max_extra_cost 0 gives other rows than any cost on the same starts"
+    assert any(n["eroded"] and n["rows3"] for n in M), "a smooth on an eroded result"
+    # -- probe: the rule of surface_twin allows ambiguous queries below 1 % of a test's; with 32 and 16 that is none, so none is drawn
+    assert all(n["ambiguous"] == 0 and n["sphere_ambiguous"] == 0 for n in log if n["name"] == "probe"), "no probe draws an ambiguous query"
+    # -- the two drops of everything
+    everything = ("nav", "field", "dist", "origin", "crowd")
+    for what, drops in (("erode:load", [n for n in log if n["name"] == "save_load"]), ("nav:fail", [n for n in log if n.get("failed")])):
+        full = [n for n in drops if all(n["had"][k] for k in everything)]
+        assert full and all(not any(n["held"][k] for k in everything) for n in drops), "%s finds crowd, field, distance and origin held, and leaves none" % what
+        assert all(log[n["i"] + 1]["name"] == "nothing" for n in full), "... and every call is tried after it"
 
 
 def test_twins_take_an_overridden_box(oracle_mod):
@@ -661,7 +820,7 @@ def describe(s, i, op):
         return "op %d %s %s" % (i, op[0], [(st.category(sp, s.mesh_ids), "box" if len(sp) > 2 else "own", *box_of(s.ref, st.gpu_struct(sp))[:2]) for sp in op[1]])
     if op[0] == "paint":
         return "op %d paint %s (layer %s)" % (i, [(tuple(round(v, 3) for v in c), round(r, 3), ch) for c, r, ch, _ in op[1]], "present" if s.layer is not None else "missing")
-    if op[0] in ("attributes", "lod", "probe", "chunk_write", "control_map", "material_init", "stamp_from_mesh", "fragments", "scatter", "nav", "field", "walk"):
+    if op[0] in ("attributes", "lod", "probe", "chunk_write", "control_map", "material_init", "stamp_from_mesh", "fragments", "scatter", "nav", "field", "walk") + NEW_OPS:
         return "op %d %r on the result of %s (%s), layer %s" % (i, op, s.result_source, "%d dirty blocks" % len(s.result_dirty) if s.result == "terrain" else s.result,
                                                                  "present" if s.layer is not None else "missing")
     return "op %d %r" % (i, op[:1] + tuple(op[1:])[:3])
@@ -697,6 +856,37 @@ def assert_layers(ex, s, tag):
         rc, got = scatter_read(ex, len(s.result_dirty))
         assert rc == _lib.OK, "%s: the instances the model holds are gone (%d)" % (tag, rc)
         assert_instances(got, s.scatter_result)
+
+
+def assert_layers4(ex, s, tag):
+    """assert_layers, and what a fourth-generation session holds on the nav result beside the field: the border distance
+    (vtmc_nav_distance_read), the origin of the last erosion (vtmc_nav_erode_origin) and the crowd (vtmc_navcrowd_read and _info) equal the
+    model's as bytes; where the model holds none, the reader answers VTMC_ERR_NO_RESULT -- asked with no room to copy into, so that a
+    library that wrongly holds one is caught by its answer alone.  A step that was refused has left the model's crowd as it was: so
+    must the device's be."""
+    assert_layers(ex, s, tag)
+    L, h, none = ex._L, ex._h, _lib.ERR_NO_RESULT
+    if s.dist is None:
+        assert L.vtmc_nav_distance_device_results(h, None, None) == none and L.vtmc_nav_distance_read(h, None, 0) == none, tag + ": a distance is held that the model dropped"
+    else:
+        assert code_of(ex.nav_distance_read) == _lib.OK, tag + ": the distance the model holds is gone"
+        got = ex.nav_distance_read()
+        assert got.dtype == s.dist.dtype == np.int32 and got.tobytes() == s.dist.tobytes(), tag + ": the distance held"
+    if s.origin is None:
+        assert L.vtmc_nav_erode_origin(h, None, 0) == none, tag + ": an origin is held that the model dropped"
+    else:
+        assert code_of(ex.nav_erode_origin) == _lib.OK, tag + ": the origin the model holds is gone"
+        got = ex.nav_erode_origin()
+        assert got.dtype == s.origin.dtype == np.int32 and got.tobytes() == s.origin.tobytes(), tag + ": the origin held"
+    if s.crowd is None:
+        assert L.vtmc_navcrowd_info(h, None, None, None, None, None) == none and L.vtmc_navcrowd_read(h, None, 0, None) == none and \
+            L.vtmc_navcrowd_device_results(h, None, None, None) == none, tag + ": a crowd is held that the model dropped"
+    else:
+        assert code_of(ex.navcrowd_info) == _lib.OK, tag + ": the crowd the model holds is gone"
+        (agents, occ), (want_agents, want_occ) = ex.navcrowd_read(), s.crowd.read()
+        assert agents.dtype == vt.NAVCROWD_AGENT_DTYPE and agents.tobytes() == want_agents.tobytes(), (tag + ": the agents held", np.nonzero(agents != want_agents)[0][:8])
+        assert occ.dtype == np.int32 and occ.tobytes() == want_occ.tobytes(), tag + ": the occupancy held"
+        assert ex.navcrowd_info() == s.crowd.info(), tag + ": the crowd's info"
 
 
 def untouched(ex):
@@ -900,11 +1090,14 @@ def step_session(ex, s, op, tmp, tag, mine):
         assert reader_codes(ex) == before, tag
         assert_state(ex, s, tag)
     elif name == "nav":
-        box, agent_height, max_step = op[1:]
+        box, agent_height, max_step, max_spans = (op[1:] + (1 << 20,))[:4]
         before = untouched(ex)
-        want = s.nav_build(box, agent_height, max_step)
-        got = ex.terrain_nav(box[0], box[1], _lib.NavParamsStruct(agent_height, max_step, 1 << 20, 0))
-        nav.assert_same(got, want, tag)
+        want = s.nav_build(box, agent_height, max_step, max_spans)
+        params = _lib.NavParamsStruct(agent_height, max_step, max_spans, 0)
+        if want is None:        # more spans than max_spans: the build fails after it invalidated the result
+            assert code_of(lambda: ex.terrain_nav(box[0], box[1], params)) == _lib.ERR_TOO_LARGE, tag
+        else:
+            nav.assert_same(ex.terrain_nav(box[0], box[1], params), want, tag)
         assert_state(ex, s, tag)
         assert_stamps(ex, s, tag)
         assert untouched(ex) == before, tag
@@ -915,8 +1108,10 @@ def step_session(ex, s, op, tmp, tag, mine):
         if s.nav is None:
             assert s.field_build(*op[1:]) is None
             assert code_of(lambda: ex.nav_field([(0, 0)], params)) == _lib.ERR_NO_RESULT, tag
+        elif isinstance(s.field_build(*op[1:]), str):      # a goal cost above max_cost (or no span to put a goal on): the field held stays
+            assert code_of(lambda: ex.nav_field(s.goals_of(picks) or [(0, 0)], params)) == _lib.ERR_INVALID_ARG, tag
         else:
-            want = s.field_build(*op[1:])
+            want = s.field
             got = ex.nav_field(s.field_goals, params)
             assert same_cells(got, want), (tag, np.nonzero(got["cost"] != want["cost"])[0][:8], np.nonzero(got["next"] != want["next"])[0][:8])
             n, n_reached, rounds = ex.navfield_info()
@@ -941,9 +1136,83 @@ def step_session(ex, s, op, tmp, tag, mine):
         assert_state(ex, s, tag)
         assert_stamps(ex, s, tag)
         assert untouched(ex) == before, tag
+    elif name in NEW_OPS:
+        before = untouched(ex)
+        assert_state(ex, s, tag + " (before)")
+        assert_stamps(ex, s, tag + " (before)")
+        step_nav_layers(ex, s, op, tag)
+        assert_state(ex, s, tag)
+        assert_stamps(ex, s, tag)
+        assert untouched(ex) == before, tag
     else:
         raise AssertionError(name)
     s.last = name
+
+
+def step_nav_layers(ex, s, op, tag):
+    """The fourth generation's operations on the device and on the model, each compared for equality as its layer's own file compares it;
+    where the model answers None, the device answers VTMC_ERR_NO_RESULT."""
+    name, none = op[0], _lib.ERR_NO_RESULT
+    if name == "distance":
+        want, p = s.distance(*op[1:]), erode_params(*op[1:])
+        if want is None:
+            assert code_of(lambda: distance_of(ex, p)) == none, tag
+        else:
+            dist, n_border = distance_of(ex, p)
+            assert n_border == want and dist.dtype == np.int32 and dist.tobytes() == s.dist.tobytes(), (tag, n_border, want)
+    elif name == "erode":
+        want, p = s.erode(*op[1:]), erode_params(*op[1:])
+        if want is None:
+            assert code_of(lambda: ex.nav_erode(p)) == none, tag
+        else:
+            got = ex.nav_erode(p)
+            nav.assert_same(got[:4], want[:4], tag)
+            assert got[4].dtype == np.int32 and got[4].tobytes() == want[4].tobytes(), tag + ": origin"
+    elif name == "sight":
+        a, b, want = s.sight(*op[1:])
+        if want is None:
+            assert code_of(lambda: ex.nav_sight(a, b)) == none, tag
+        else:
+            got = ex.nav_sight(a, b)
+            assert got.dtype == _lib.NAVSIGHT_HIT_DTYPE and got.tobytes() == want.tobytes(), (tag, np.nonzero(got != want)[0][:8])
+    elif name == "smooth":
+        pos, below, above, located, rows = s.smooth(*op[1:])
+        params = vt.NavSightParams(op[3], op[4])
+        if located is None:
+            assert code_of(lambda: ex.nav_locate(pos, below, above)) == none, tag
+            assert code_of(lambda: ex.nav_trace_smooth(np.full(len(pos), -1, np.int32), op[2], params)) == none, tag
+        else:
+            got = ex.nav_locate(pos, below, above)
+            assert got.dtype == np.int32 and np.array_equal(got, located), (tag, np.nonzero(got != located)[0][:8])
+            if rows is None:
+                assert code_of(lambda: ex.nav_trace_smooth(located, op[2], params)) == none, tag
+            else:
+                paths, lengths = ex.nav_trace_smooth(located, op[2], params)
+                assert lengths.tobytes() == rows[1].tobytes() and paths.tobytes() == rows[0].tobytes(), (tag, np.nonzero(lengths != rows[1])[0][:8])
+    elif name == "spawn":
+        spans, speeds, placed = s.spawn(*op[1:])
+        if placed is None:
+            assert code_of(lambda: ex.navcrowd_spawn(spans, speeds)) == none, tag
+        else:
+            assert ex.navcrowd_spawn(spans, speeds) == placed, tag
+    elif name == "step":
+        detour, flags, ticks = op[1:]
+        want, p = s.step(detour, flags, ticks), crowd_params(navcrowd_twin.ANY if detour is None else detour, flags)
+        if want is None:        # no crowd, or no field: assert_layers4 then finds the crowd's bytes as they were
+            assert code_of(lambda: ex.navcrowd_step(p, ticks)) == none, tag
+        else:
+            assert ex.navcrowd_step(p, ticks) == want, tag
+    else:                       # "nothing": every call of the four layers, with none of them held
+        assert all(v is None for v in s.nothing().values()), tag
+        pos, sight, erode, crowd = np.zeros((1, 3), f32), vt.NavSightParams(), erode_params(1), crowd_params()
+        calls = dict(nav_read=ex.nav_read, device_nav=ex.device_nav, locate=lambda: ex.nav_locate(pos, 1.0, 1.0), field=lambda: ex.nav_field([(0, 0)], vt.NavFieldParams(0.0, 0.0)),
+                     field_read=ex.navfield_read, field_info=ex.navfield_info, device_field=ex.device_navfield, trace=lambda: ex.nav_trace([-1], 4),
+                     distance=lambda: distance_of(ex, erode), distance_read=ex.nav_distance_read, device_distance=ex.device_nav_distance,
+                     erode=lambda: ex.nav_erode(erode), origin=ex.nav_erode_origin, sight=lambda: ex.nav_sight([-1], [-1]),
+                     smooth=lambda: ex.nav_trace_smooth([-1], 4, sight), spawn=lambda: ex.navcrowd_spawn([-1], 300), step=lambda: ex.navcrowd_step(crowd, 1),
+                     crowd_read=ex.navcrowd_read, crowd_info=ex.navcrowd_info, device_crowd=ex.device_navcrowd)
+        for what, call in calls.items():
+            assert code_of(call) == none, "%s: %s answers %d" % (tag, what, code_of(call))
 
 
 @pytest.mark.gpu
@@ -988,6 +1257,32 @@ def test_gpu_session_third_generation(oracle_mod, tmp_path, world, seed, indexed
     names = [op[0] for op in ops]
     print("%s %d %s: %s, %d detach modifiers; seen %s" % (world, seed, "indexed" if indexed else "soup",
                                                            {k: names.count(k) for k in ("fragments", "scatter", "nav", "field", "walk")}, len(s.detaches), s.seen))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("world,seed,indexed", CASES4, ids=IDS4)
+def test_gpu_session_fourth_generation(oracle_mod, tmp_path, world, seed, indexed):
+    """The third generation's sessions with the set pieces about the border distance, the erosion, the line of sight, the smoothed trace
+    and the crowd between them; after EVERY operation assert_layers4 compares what the context holds on its nav result with the model,
+    so every keep rule and every drop rule of include/vtmc_naverode.h, vtmc_navsight.h and vtmc_navcrowd.h is tried against every
+    operation a session holds, a load, a failed nav build and an erosion of an eroded result among them."""
+    w = st.WORLDS[world]
+    ops = generate(seed, world, generation=4)
+    s = Session(oracle_mod, world, indexed)
+    mine = {"undo": [], "redo": []}
+    with vt.Extractor(0) as ex:
+        ex.set_output_mode(indexed)
+        ex.terrain_init(*w["dims"], w["scale"], w["origin"], w["seed"])
+        assert_state(ex, s, "init")
+        assert_layers4(ex, s, "init")
+        for i, op in enumerate(ops):
+            op = s.concrete(op)
+            tag = describe(s, i, op)
+            step_session(ex, s, op, str(tmp_path), tag, mine)
+            assert_layers4(ex, s, tag)
+        assert_stamps(ex, s, "the end")
+    names = [op[0] for op in ops]
+    print("%s %d %s: %s; seen %s" % (world, seed, "indexed" if indexed else "soup", {k: names.count(k) for k in ("nav", "field", "walk") + NEW_OPS}, s.seen))
 
 
 @pytest.mark.gpu
