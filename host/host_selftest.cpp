@@ -6,8 +6,9 @@
 //   host_selftest --gpu-lod <out_dir>  a resident terrain meshed at three levels of detail around a viewer; dumps nodes + per-node counts
 //   host_selftest --gpu-nav <out_dir>  the navigation layer of a box of a resident terrain; dumps the spans, the column offsets and the box
 //   host_selftest --gpu-naverode <out_dir>  the agent radius on that build: dumps the distances, then the eroded spans, offsets and origin
-//   host_selftest --gpu-navfield <out_dir>  a flow field on that build: dumps the cells, every span's path and the located goal spans
+//   host_selftest --gpu-water <out_dir> | --gpu-navfield <out_dir>  a flow field on that build: dumps the cells, every span's path and the located goal spans
 //   host_selftest --gpu-navsight <out_dir>  any-angle paths on that field: dumps the hits of a set of pairs and every span's smoothed path
+//   host_selftest --gpu-water <out_dir>     standing water on that world: dumps the bodies, both volumes and three probes of one flood
 //   host_selftest --gpu-navcrowd <out_dir>  a crowd on that field: dumps agents, occupancy and counts after the spawn, 24 ticks and a re-route
 #include <cmath>
 #include <cstdio>
@@ -437,6 +438,66 @@ static int gpu_navsight_run(const std::string &out)
     return 0;
 }
 
+// the world of --gpu-navfield; two sources in the dug hollow, the lower one joining the higher one's body, and one far outside, flooded in a
+// box that cuts the world
+static int gpu_water_run(const std::string &out)
+{
+    VoxelTerrain vt;
+    vt._width = 64;
+    vt._elevation = 32;
+    vt._height = 32;
+    vt._voxelScale = 0.5f;
+    vt.TerrainOrigin = Vector3(-3.0f, 1.0f, 2.0f);
+    vt._deviceResident = true;
+    vt._seed = 977;
+    vt.Init();
+    Vector2 lo, up;
+    lo.x = -100; lo.y = -100; up.x = 100; up.y = 100;
+    vt.InsertModifier(std::make_shared<PlaneModifier>(6.3f, lo, up, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(27.5f, 8.0f, 10.0f), 4.25f, true));
+    vt.InsertModifier(std::make_shared<SphereModifier>(Vector3(5.0f, 6.0f, 9.0f), 3.0f, false));
+    vt.Update();
+    const int updateTriangles = vt.LastTriangleCount();
+    const std::vector<WaterSource> sources = {WaterSource{Vector3(5.0f, 5.0f, 9.0f), 6.0f}, WaterSource{Vector3(5.0f, 4.5f, 9.5f), 5.5f}, WaterSource{Vector3(500.0f, 6.0f, 10.0f), 7.0f}};
+    const WaterResult w = vt.Flood(Vector3(-1.0f, 1.0f, 3.0f), Vector3(30.0f, 15.0f, 16.5f), sources);
+    if (w._sourceBody.size() != 3 || w._sourceBody[0] != 0 || w._sourceBody[1] != 0 || w._sourceBody[2] != -1 || w._bodies.size() != 1 || w._bodies[0]._sources != 2) return 7;
+    long long wet = 0;
+    for (const WaterBody &b : w._bodies) wet += b._samples;
+    const size_t vn = (size_t)w._volumeDims[0] * w._volumeDims[1] * w._volumeDims[2];
+    if (wet != w._wet || w._water.size() != vn || w._bodyVolume.size() != vn || vn == 0) return 8;
+    for (int k = 0; k < 3; k++)
+        if (w._volumeDims[k] < w._boxDims[k] || (w._volumeDims[k] - 2) % 8 != 0) return 9;
+    long long counted = 0;
+    for (int v : w._bodyVolume) counted += v >= 0;
+    if (counted != wet) return 10;
+    const std::vector<WaterProbe> probes = vt.ProbeWater({Vector3(5.0f, 4.0f, 9.0f), Vector3(27.5f, 12.0f, 10.0f), Vector3(5.0f, 5.75f, 9.0f)});
+    if (probes.size() != 3 || probes[0]._body != 0 || probes[0]._depth != 2.0f || probes[1]._body != -1 || probes[1]._depth != 0.0f || probes[2]._body != 0) return 11;
+    for (const WaterProbe &p : probes)
+        if (p._body >= (int)w._bodies.size()) return 12;
+    if (vt.LastTriangleCount() != updateTriangles) return 13;   // what Update left stands
+    std::printf("water: bodies %zu wet %lld volume %d x %d x %d\n", w._bodies.size(), w._wet, w._volumeDims[0], w._volumeDims[1], w._volumeDims[2]);
+    static_assert(sizeof(WaterBody) == 64, "dumped as it lies");
+    std::ofstream fs(out + "/water_source_body.i32", std::ios::binary), fb(out + "/water_bodies.bin", std::ios::binary), fw(out + "/water_volume.f32", std::ios::binary),
+        fv(out + "/water_body_volume.i32", std::ios::binary), fpb(out + "/water_probe_body.i32", std::ios::binary), fpd(out + "/water_probe_depth.f32", std::ios::binary);
+    fs.write(reinterpret_cast<const char *>(w._sourceBody.data()), (std::streamsize)(w._sourceBody.size() * sizeof(int)));
+    fb.write(reinterpret_cast<const char *>(w._bodies.data()), (std::streamsize)(w._bodies.size() * sizeof(WaterBody)));
+    fw.write(reinterpret_cast<const char *>(w._water.data()), (std::streamsize)(vn * sizeof(float)));
+    fv.write(reinterpret_cast<const char *>(w._bodyVolume.data()), (std::streamsize)(vn * sizeof(int)));
+    for (const WaterProbe &p : probes) {
+        fpb.write(reinterpret_cast<const char *>(&p._body), sizeof(int));
+        fpd.write(reinterpret_cast<const char *>(&p._depth), sizeof(float));
+    }
+    bool refused = false;   // a level that is not finite refuses the call and keeps the result
+    try {
+        vt.Flood(Vector3(-1.0f, 1.0f, 3.0f), Vector3(30.0f, 15.0f, 16.5f), {WaterSource{Vector3(5.0f, 6.0f, 9.0f), INFINITY}});
+    } catch (const UnityException &) {
+        refused = true;
+    }
+    if (!refused || vt.ProbeWater({Vector3(5.0f, 4.0f, 9.0f)})[0]._body != probes[0]._body) return 14;
+    std::printf("HOST-WATER-OK\n");
+    return 0;
+}
+
 // the world, the box and the field of --gpu-navfield; agents on every second span (those divisible by 7 ask for -1, and span 2 is asked
 // for three times), 24 ticks with any detour that leave on arrival, then a field of the second goal alone and 16 ticks within 1024
 static int gpu_navcrowd_run(const std::string &out)
@@ -581,6 +642,7 @@ int main(int argc, char **argv)
         if (argc >= 3 && std::string(argv[1]) == "--gpu-navfield") return gpu_navfield_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-navsight") return gpu_navsight_run(argv[2]);
         if (argc >= 3 && std::string(argv[1]) == "--gpu-navcrowd") return gpu_navcrowd_run(argv[2]);
+        if (argc >= 3 && std::string(argv[1]) == "--gpu-water") return gpu_water_run(argv[2]);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "exception: %s\n", e.what());
         return 3;

@@ -11,6 +11,7 @@
 #include "../include/vtmc_naverode.h"
 #include "../include/vtmc_navsight.h"
 #include "../include/vtmc_navcrowd.h"
+#include "../include/vtmc_water.h"
 
 namespace PGRTerrain {
 
@@ -329,6 +330,40 @@ public:
         out._agents.clear();
         for (const vtmc_navcrowd_agent &a : agents) out._agents.push_back(CrowdAgent{a.span, a.budget, a.speed, a.state});
     }
+    void Flood(const float *lower, const float *upper, const std::vector<WaterSource> &sources, WaterResult &out) override
+    {
+        static_assert(sizeof(WaterBody) == sizeof(vtmc_water_body) && sizeof(WaterSource) == sizeof(vtmc_water_source), "copied as they lie");
+        std::vector<vtmc_water_source> src(sources.size());
+        for (size_t i = 0; i < sources.size(); i++) {
+            src[i].position[0] = sources[i]._position.x, src[i].position[1] = sources[i]._position.y, src[i].position[2] = sources[i]._position.z;
+            src[i].level = sources[i]._level;
+        }
+        out = WaterResult();
+        out._sourceBody.assign(sources.size(), -1);
+        int32_t n = 0;
+        if (vtmc_terrain_flood(_ctx, lower, upper, src.data(), (int32_t)src.size(), 0u, out._sourceBody.data(), &n) != VTMC_OK)
+            throw UnityException(std::string("vtmc_terrain_flood: ") + vtmc_last_error(_ctx));
+        int64_t wet = 0;
+        if (vtmc_water_info(_ctx, out._boxLo, out._boxDims, out._volumeDims, &n, &wet) != VTMC_OK) throw UnityException(std::string("vtmc_water_info: ") + vtmc_last_error(_ctx));
+        out._wet = wet;
+        out._bodies.resize((size_t)n);
+        if (vtmc_water_bodies(_ctx, reinterpret_cast<vtmc_water_body *>(out._bodies.data()), n) != VTMC_OK)
+            throw UnityException(std::string("vtmc_water_bodies: ") + vtmc_last_error(_ctx));
+        const size_t vn = (size_t)out._volumeDims[0] * out._volumeDims[1] * out._volumeDims[2];
+        out._water.resize(vn), out._bodyVolume.resize(vn);
+        if (vtmc_water_read(_ctx, out._water.data(), out._bodyVolume.data(), (int64_t)vn) != VTMC_OK) throw UnityException(std::string("vtmc_water_read: ") + vtmc_last_error(_ctx));
+    }
+    void ProbeWater(const std::vector<Vector3> &positions, std::vector<WaterProbe> &out) override
+    {
+        std::vector<float> p;
+        for (const Vector3 &v : positions) p.push_back(v.x), p.push_back(v.y), p.push_back(v.z);
+        std::vector<int32_t> body(positions.size(), -1);
+        std::vector<float> depth(positions.size(), 0.0f);
+        if (vtmc_water_probe(_ctx, p.data(), (int32_t)positions.size(), body.data(), depth.data()) != VTMC_OK)
+            throw UnityException(std::string("vtmc_water_probe: ") + vtmc_last_error(_ctx));
+        out.clear();
+        for (size_t i = 0; i < positions.size(); i++) out.push_back(WaterProbe{body[i], depth[i]});
+    }
 
     int MaterialInit(int fineness) override
     {
@@ -552,6 +587,23 @@ CrowdResult VoxelTerrain::ReadCrowd()
     if (!_initialised || !_deviceResident) throw UnityException("ReadCrowd needs an initialised device-resident terrain");
     CrowdResult out;
     _backend->CrowdRead(out);
+    return out;
+}
+
+WaterResult VoxelTerrain::Flood(Vector3 lower, Vector3 upper, const std::vector<WaterSource> &sources)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("Flood needs an initialised device-resident terrain");
+    const float lo[3] = {lower.x, lower.y, lower.z}, up[3] = {upper.x, upper.y, upper.z};
+    WaterResult out;
+    _backend->Flood(lo, up, sources, out);
+    return out;
+}
+
+std::vector<WaterProbe> VoxelTerrain::ProbeWater(const std::vector<Vector3> &positions)
+{
+    if (!_initialised || !_deviceResident) throw UnityException("ProbeWater needs an initialised device-resident terrain");
+    std::vector<WaterProbe> out;
+    _backend->ProbeWater(positions, out);
     return out;
 }
 

@@ -363,6 +363,36 @@ struct CrowdResult {
     int _occupying = 0, _arrived = 0, _ticks = 0, _movedLast = 0;
 };
 
+// New (not in the reference): standing water (include/vtmc_water.h, where the rule is).  A source pours at _position (world space; its
+// nearest sample is the source's) up to _level; WaterResult is what Flood returns: per source its body or -1 (dry), the bodies in the
+// rule's order (descending level, then ascending grid index of the seed), the box and the two volumes (x fastest, _volumeDims samples per
+// axis): the body index of every sample or -1, and the density whose extraction is the water's surface.
+constexpr unsigned kWaterAtFace = 1u;
+struct WaterSource {
+    Vector3 _position;
+    float _level;
+};
+struct WaterBody {
+    int _seed[3], _lo[3], _hi[3];
+    float _level;
+    int _samples, _surface;
+    unsigned _flags;
+    int _sources;
+    unsigned _reserved[2];
+};
+struct WaterResult {
+    std::vector<int> _sourceBody;
+    std::vector<WaterBody> _bodies;
+    int _boxLo[3] = {0, 0, 0}, _boxDims[3] = {0, 0, 0}, _volumeDims[3] = {0, 0, 0};
+    long long _wet = 0;
+    std::vector<float> _water;
+    std::vector<int> _bodyVolume;
+};
+struct WaterProbe {
+    int _body;      // -1: dry
+    float _depth;   // level - y, 0 when dry
+};
+
 // New (not in the reference, which can only replace a control map whole): one paint stroke on the material layer (vtmc_material_stroke
 // of include/vtmc.h).  Every texel within _radius of _center (world space) is blended towards the one-hot of _channel (0..3: control map
 // 1's r, g, b, a; 4..7: control map 2's) by _strength * clamp01(2 (1 - d / _radius)).
@@ -452,6 +482,9 @@ struct ExtractBackend {
     virtual int CrowdSpawn(const std::vector<int> &, const std::vector<unsigned> &) { throw std::logic_error("CrowdSpawn unsupported"); }
     virtual void CrowdStep(unsigned, bool, int) { throw std::logic_error("CrowdStep unsupported"); }
     virtual void CrowdRead(CrowdResult &) { throw std::logic_error("CrowdRead unsupported"); }
+    // Standing water on the resident terrain (vtmc_terrain_flood with _info, _bodies and _read; vtmc_water_probe).
+    virtual void Flood(const float *, const float *, const std::vector<WaterSource> &, WaterResult &) { throw std::logic_error("Flood unsupported"); }
+    virtual void ProbeWater(const std::vector<Vector3> &, std::vector<WaterProbe> &) { throw std::logic_error("ProbeWater unsupported"); }
     virtual void NavTraceSmooth(const std::vector<int> &, int, int, unsigned, NavPaths &) { throw std::logic_error("NavTraceSmooth unsupported"); }
 
     // Material layer of a device-resident terrain (vtmc_material_*).  MaterialInit returns the layer's size C = 16 * fineness.
@@ -564,6 +597,12 @@ public:
     int SpawnCrowd(const std::vector<int> &spans, const std::vector<unsigned> &speeds);
     void StepCrowd(int ticks, unsigned maxDetour = kNavCrowdAnyDetour, bool leaveOnArrival = false);
     CrowdResult ReadCrowd();
+
+    // New: standing water (include/vtmc_water.h, where the rule is).  Flood fills the box lower..upper (world bounds) from the sources to
+    // their levels, on the device, and returns the bodies and the volumes; it changes nothing in the terrain and keeps a snapshot that
+    // Init drops and an edit keeps.  ProbeWater asks that snapshot what a swimmer asks: the body and the depth at a position.
+    WaterResult Flood(Vector3 lower, Vector3 upper, const std::vector<WaterSource> &sources);
+    std::vector<WaterProbe> ProbeWater(const std::vector<Vector3> &positions);
 
     // -- inspection (tests, callers that consume the meshes) ----------------------------------
     const BlockMesh &Block(int x, int y, int z) const { return _blocks[((size_t)x * (_elevation / blockSize) + y) * (_height / blockSize) + z]; }

@@ -15,7 +15,7 @@ from ._header import HEADER, LAYERS
 
 # every #define VTMC_<NAME> of every layer's header as <NAME>.  include/vtmc.h: OK and the ERR_* codes, FLAG_*, OUTPUT_*, MOD_*, TERRAIN_SAVE_EXACT,
 # TERRAIN_LOAD_NO_EXTRACT, MESH_*, MATERIAL_*, AO_*, SCATTER_*, LOD_MAX_LEVEL, RAY_TWO_SIDED, SPHERE_MAX_RADIUS_CELLS, COMM_ID_BYTES ...
-# The optional layers' headers: NAV_OPEN, NAVFIELD_UNIT, NAVERODE_MAX_RADIUS, NAVSIGHT_ANY_COST, NAVCROWD_ANY_DETOUR ...
+# The optional layers' headers: NAV_OPEN, NAVFIELD_UNIT, NAVERODE_MAX_RADIUS, NAVSIGHT_ANY_COST, NAVCROWD_ANY_DETOUR, WATER_AT_FACE ...
 for _layer in LAYERS.values():
     globals().update((name[len("VTMC_"):], value) for name, value in _layer.constants.items())
 STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27   # vtmc_stamp_create: the limits of a stamp's dims (the header states them in prose)
@@ -36,6 +36,8 @@ NAVFIELD_CELL_DTYPE = LAYERS["navfield"].dtype("vtmc_navfield_cell")   # one cel
 NAVFIELD_GOAL_DTYPE = LAYERS["navfield"].dtype("vtmc_navfield_goal")   # one goal of vtmc_navfield_build: span and cost
 NAVSIGHT_HIT_DTYPE = LAYERS["navsight"].dtype("vtmc_navsight_hit")     # one answer of vtmc_nav_sight: the span the walk ended on and its steps
 NAVCROWD_AGENT_DTYPE = LAYERS["navcrowd"].dtype("vtmc_navcrowd_agent")   # one agent of vtmc_navcrowd_spawn: span, budget, speed, state
+WATER_SOURCE_DTYPE = LAYERS["water"].dtype("vtmc_water_source")   # one source of vtmc_terrain_flood: world position and level
+WATER_BODY_DTYPE = LAYERS["water"].dtype("vtmc_water_body")       # one body of vtmc_water_bodies: seed, bounds, level, counts, flags
 
 Modifier = HEADER.structure("vtmc_modifier", "Modifier", """vtmc_modifier: one queued TerrainModifier (TerrainModifier.cs:19-33), bounds as the C#
     LowerBound / UpperBound properties return them.""")
@@ -70,6 +72,7 @@ DEBUG_ARGTYPES = {   # entry points that are deliberately not in the header; all
     "vtmc_debug_naverode_ms": [_vp, _P(ctypes.c_float * 5)],        # device time of the last distance build's or erode's four stages, and its rounds
     "vtmc_debug_navsight_ms": [_vp, _P(ctypes.c_float * 2)],        # device time of the last sight query's or smoothed trace's row fill and kernel
     "vtmc_debug_navcrowd_ms": [_vp, _P(ctypes.c_float * 1)],        # device time of the ticks of the last crowd step
+    "vtmc_debug_water_ms": [_vp, _P(ctypes.c_float * 3)],           # device time of the last flood's levels, statistics and volume kernel
 }
 
 

@@ -10,7 +10,7 @@
 //                          LDS over the runs along x (a run is one ballot); leaves every solid sample pointing at the smallest index of
 //                          its piece of the tile, -1 in the others.  The one read of the grid.
 //   2. frag_merge_kernel   the samples on a tile's low faces join their neighbour across the face: union by smaller index on the global
-//                          parent array.
+//                          parent array (tile_label.h, shared with terrain_water.hip, as are the tile constants and the row walk).
 //   3. frag_flatten_kernel every sample to its root; fused with the per-root sample counts (reduced per run of a wave before the atomic).
 // Between 2 and 3, frag_anchor_kernel walks the six faces of the box and marks the roots it meets.
 //
@@ -27,19 +27,15 @@
 #include "terrain_edit.h"
 #include "terrain_fragments.h"
 #include "terrain_stamp.h"
-#include "union_find.h"
+#include "tile_label.h"
 #include <climits>
 #include <cstring>
 #include <vector>
 
 namespace vtmc {
 
-constexpr int kTileX = 64, kTileY = 8, kTileZ = 8, kTileSamples = kTileX * kTileY * kTileZ;
 constexpr uint32_t kAnchoredBit = 0x80000000u;   // aux[root]: anchored; the bits below it count the samples of an unanchored root (<= 2^30)
 enum { kCtlFlag = 0, kCtlCount = 1, kCtlSlots = 2, kCtlWords = 16 };
-
-// box-linear index of sample (ix, iy, iz) of the box; below 2^31 for every box of a grid
-__device__ __forceinline__ int frag_index(const TerrainBox &b, int ix, int iy, int iz) { return ix + b.dx * (iy + b.dy * iz); }
 
 // Phase 1.  64 x 4 threads; thread (tx, tq) owns the 16 samples (tx, r & 7, r >> 3), r = tq + 4 k, of the tile, so a wave holds one row
 // of 64 samples along x at a time.  A row's solid mask is one ballot: every sample starts out pointing at the first sample of its run
@@ -96,52 +92,8 @@ __global__ __launch_bounds__(256) void frag_local_kernel(const float *__restrict
     }
 }
 
-// The walk of the kernels below: 64 x 4 threads, one sample per thread, a wave is 64 samples along x of one row; grid = (x segments,
-// y quads, z planes).
-struct RowThread {
-    int ix, iy, iz;
-    __device__ __forceinline__ RowThread() : ix(blockIdx.x * 64 + threadIdx.x), iy(blockIdx.y * 4 + threadIdx.y), iz(blockIdx.z) {}
-    __device__ __forceinline__ bool inside(const TerrainBox &b) const { return ix < b.dx && iy < b.dy; }
-};
-
-// Phase 2.  Only rows on a low face of their tile load anything.  A wave is the 64 samples of one tile's row, and within a tile
-// neighbours along x are joined already, so across a y or z face one union per stretch in which both rows are solid is enough (its first
-// lane makes it); across an x face the row's first lane joins its neighbour.  fx, fy, fz are the same for every lane of a wave.
-__global__ __launch_bounds__(256) void frag_merge_kernel(int *__restrict__ P, int *__restrict__ flag, TerrainBox b, int n)
-{
-    constexpr int kScope = __HIP_MEMORY_SCOPE_AGENT;
-    const RowThread t;
-    const int lane = threadIdx.x;
-    const bool row = t.iy < b.dy;
-    const bool fx = row && blockIdx.x > 0, fy = row && t.iy % kTileY == 0 && t.iy > 0, fz = row && t.iz % kTileZ == 0 && t.iz > 0;
-    if (!(fx || fy || fz)) return;
-    const bool in = t.ix < b.dx;
-    const int j = in ? frag_index(b, t.ix, t.iy, t.iz) : 0;
-    const bool solid = in && (fy || fz || lane == 0) && uf_load<kScope>(P, j) >= 0;
-    if (fy) {
-        const bool both = solid && uf_load<kScope>(P, j - b.dx) >= 0;
-        const unsigned long long m = __ballot(both);
-        if (both && !(lane > 0 && (m >> (lane - 1) & 1))) uf_union<kScope, true>(P, j, j - b.dx, n, flag);
-    }
-    if (fz) {
-        const bool both = solid && uf_load<kScope>(P, j - b.dx * b.dy) >= 0;
-        const unsigned long long m = __ballot(both);
-        if (both && !(lane > 0 && (m >> (lane - 1) & 1))) uf_union<kScope, true>(P, j, j - b.dx * b.dy, n, flag);
-    }
-    if (fx && lane == 0 && solid && uf_load<kScope>(P, j - 1) >= 0) uf_union<kScope, true>(P, j, j - 1, n, flag);
-}
-
-// Lanes of a wave that hold the same key >= 0 next to each other form a run; its first lane learns the run's length, the others 0.
-__device__ __forceinline__ int run_length(int key)
-{
-    const int lane = __lane_id();
-    const int prev = __shfl_up(key, 1);
-    const bool head = lane == 0 || prev != key;
-    const unsigned long long heads = __ballot(head);
-    if (!head || key < 0) return 0;
-    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-    return above ? __ffsll(above) : 64 - lane;
-}
+// Phase 2 (tile_label.h).
+__global__ __launch_bounds__(256) void frag_merge_kernel(int *__restrict__ P, int *__restrict__ flag, TerrainBox b, int n) { label_merge(P, flag, b, n); }
 
 // The six faces of the box, one thread per face sample (edges twice): the root above a solid one is anchored.
 __global__ __launch_bounds__(256) void frag_anchor_kernel(const int *__restrict__ P, uint32_t *__restrict__ aux, int *__restrict__ flag, TerrainBox b, int n)
@@ -302,14 +254,6 @@ __global__ __launch_bounds__(256) void frag_capture_kernel(const float *__restri
     }
 }
 
-static dim3 row_grid(const TerrainBox &b) { return dim3((unsigned)((b.dx + 63) / 64), (unsigned)((b.dy + 3) / 4), (unsigned)b.dz); }
-
-template <class... Params, class... Args>
-static hipError_t launch_rows(void (*kernel)(Params...), const TerrainBox &b, hipStream_t stream, Args... args)
-{
-    return launch(kernel, row_grid(b), dim3(64, 4, 1), 0, stream, args...);
-}
-
 // The scratch of a box of n samples.  Grown only after the stream has drained: an earlier detach of the same queue may still be reading it.
 static int fragment_scratch(vtmc_ctx *ctx, size_t n)
 {
@@ -332,8 +276,7 @@ static int label_box(vtmc_ctx *ctx, const float *grid, const TerrainBox &b, int 
     const TerrainShape &sh = ctx->tshape;
     hipStream_t s = ctx->stream;
     VTMC_HIP(ctx, hipMemsetAsync(ctl, 0, kCtlWords * sizeof(int), s));
-    VTMC_HIP(ctx, launch(frag_local_kernel, dim3((unsigned)((b.dx + kTileX - 1) / kTileX), (unsigned)((b.dy + kTileY - 1) / kTileY), (unsigned)((b.dz + kTileZ - 1) / kTileZ)),
-                         dim3(64, 4, 1), 0, s, grid, P, aux, ctl + kCtlFlag, sh, b));
+    VTMC_HIP(ctx, launch(frag_local_kernel, tile_grid(b), dim3(64, 4, 1), 0, s, grid, P, aux, ctl + kCtlFlag, sh, b));
     VTMC_HIP(ctx, launch_rows(frag_merge_kernel, b, s, P, ctl + kCtlFlag, b, (int)n));
     const long long faces = 2 * ((long long)b.dx * b.dy + (long long)b.dx * b.dz + (long long)b.dy * b.dz);
     VTMC_HIP(ctx, launch(frag_anchor_kernel, lanes256(faces), dim3(256), 0, s, P, aux, ctl + kCtlFlag, b, (int)n));

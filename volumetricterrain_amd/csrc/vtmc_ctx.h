@@ -6,6 +6,7 @@
 #include "../../include/vtmc.h"
 #include "vtmc_internal.h"
 struct vtmc_nav_span;   // include/vtmc_nav.h
+#include "../../include/vtmc_water.h"
 
 #include <deque>
 #include <map>
@@ -177,6 +178,18 @@ struct VtmcNavCrowd {
     int32_t occupying = 0, arrived = 0, ticks = 0, moved_last = 0;
 };
 
+// The water result the context holds (terrain_water.hip): library-owned, grow-only; a snapshot of the grid at flood time, dropped by
+// vtmc_terrain_init / _load.  water, body: the two volumes (vd samples per axis); labels: a parent word per sample of the box; records:
+// VTMC_WATER_MAX_SOURCES body records; seeds: the sources of the call, level by level; source_body: a word per source; ctl: the flag
+// word and the body count; probe: the positions and answers of vtmc_water_probe.  bodies: the host's copy of the records.
+struct VtmcWater {
+    VtmcDevBuf water, body, labels, records, seeds, source_body, ctl, probe;
+    bool valid = false;
+    int32_t lo[3] = {0, 0, 0}, d[3] = {0, 0, 0}, vd[3] = {0, 0, 0};   // the box as reported, and the volume dims
+    int64_t wet = 0;
+    std::vector<vtmc_water_body> bodies;
+};
+
 // An extract that has been queued on a stream and not yet completed by extract_finish().
 struct VtmcPending {
     bool active = false;    // queued, extract_finish() not yet called
@@ -281,6 +294,9 @@ struct vtmc_ctx {
     // terrain_navcrowd.hip: the crowd on that build, and the clock around the ticks of the last step that ran any
     VtmcNavCrowd navcrowd;
     vtmc::StageClock<2> navcrowd_clock;
+    // terrain_water.hip: the last flood, and the clock of its kernels (the levels' labelling, the statistics, the volume)
+    VtmcWater water;
+    vtmc::StageClock<4> water_clock;
     // terrain_lod.hip: the node list of the last level-of-detail result (host, and the copy the gather kernel reads), the packed
     // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the clock around
     // the gather launch of the last extract that succeeded (vtmc_debug_lod_gather_ms)
@@ -339,6 +355,7 @@ void material_drop(vtmc_ctx *ctx);   // terrain_material.hip: vtmc_terrain_init 
 // whatever invalidates the nav result drops what describes it, the flow field, the border distance and the origin of an erosion, and the
 // crowd that stands on it: vtmc_terrain_init / _load and every vtmc_terrain_nav_build
 inline void nav_drop(vtmc_ctx *ctx) { ctx->nav.valid = false, ctx->navfield.valid = false, ctx->naverode.dist_valid = false, ctx->naverode.origin_valid = false, ctx->navcrowd.valid = false; }
+inline void water_drop(vtmc_ctx *ctx) { ctx->water.valid = false; }   // vtmc_terrain_init / _load: the snapshot's grid is gone
 int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp);   // sp then walks the (bx,by,bz) list
 int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, ResultSource source, int32_t *tri_count);   // queued on the context's stream and finished
 // The vertex attributes of a terrain result (terrain_material.hip, terrain_ao.hip), in vtmc_api.hip.  attr_gate: may `who` compute one for

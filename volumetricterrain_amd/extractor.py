@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, NAVCROWD_AGENT_DTYPE, NAVFIELD_CELL_DTYPE, NAVFIELD_GOAL_DTYPE, NAVSIGHT_HIT_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, NAVCROWD_AGENT_DTYPE, NAVFIELD_CELL_DTYPE, NAVFIELD_GOAL_DTYPE, NAVSIGHT_HIT_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, WATER_BODY_DTYPE, WATER_SOURCE_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
 from .modifiers import AmbientOcclusion, LodParams, NavErodeParams, NavParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
 
 
@@ -648,6 +648,83 @@ class Extractor:
         a, o, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int32()
         self._check(self._L.vtmc_navcrowd_device_results(self._h, ctypes.byref(a), ctypes.byref(o), ctypes.byref(n)))
         return a.value, o.value, n.value
+
+    # -- standing water: flood a box of the resident terrain from sources to their levels (include/vtmc_water.h) --------
+    def terrain_flood(self, sources, lower=None, upper=None):
+        """Floods the box lower..upper (world bounds; None: the whole terrain) by the rule WATER.  `sources`: a WATER_SOURCE_DTYPE array or
+        rows of (x, y, z, level) in world space.  Returns (source_body, n_bodies): per source its body index or -1 (dry).  Changes nothing
+        in the terrain; the result is a snapshot, read with water_info / water_bodies / water_read / water_probe / water_extract."""
+        lo, up = fragment_bounds(lower, upper)
+        src = np.asarray(sources)
+        if src.dtype != WATER_SOURCE_DTYPE:
+            rows = np.asarray(sources, np.float32).reshape(-1, 4)
+            src = np.zeros(len(rows), WATER_SOURCE_DTYPE)
+            src["position"], src["level"] = rows[:, :3], rows[:, 3]
+        src = np.ascontiguousarray(src)
+        lo_c, up_c = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*up)
+        out, n = np.full(len(src), -1, np.int32), ctypes.c_int32()
+        self._check(self._L.vtmc_terrain_flood(self._h, ctypes.byref(lo_c), ctypes.byref(up_c), _ptr(src) if len(src) else None, len(src), 0,
+                                               _ptr(out) if len(src) else None, ctypes.byref(n)))
+        return out, n.value
+
+    def water_info(self):
+        """(box_lo, box_dims, volume_dims, n_bodies, n_wet) of the flood the context holds."""
+        lo, d, vd, n, wet = (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)(), ctypes.c_int32(), ctypes.c_int64()
+        self._check(self._L.vtmc_water_info(self._h, ctypes.byref(lo), ctypes.byref(d), ctypes.byref(vd), ctypes.byref(n), ctypes.byref(wet)))
+        return tuple(lo), tuple(d), tuple(vd), n.value, wet.value
+
+    def water_bodies(self):
+        """The body records (WATER_BODY_DTYPE) in the rule's order: descending level, then ascending grid index of the seed."""
+        out = np.zeros(self.water_info()[3], WATER_BODY_DTYPE)
+        self._check(self._L.vtmc_water_bodies(self._h, _ptr(out), len(out)))
+        return out
+
+    def water_read(self, water=True, bodies=True):
+        """(water volume float32, body volume int32), each indexed [x, y, z] with the volume dims (x fastest in memory), or None when not
+        asked for: volume sample (ix, iy, iz) is box sample (ix, iy, iz), the padding is dry."""
+        vd = self.water_info()[2]
+        shape = (vd[2], vd[1], vd[0])
+        w = np.empty(shape, np.float32) if water else None
+        b = np.empty(shape, np.int32) if bodies else None
+        self._check(self._L.vtmc_water_read(self._h, _ptr(w), _ptr(b), vd[0] * vd[1] * vd[2]))
+        return (w.transpose(2, 1, 0) if water else None), (b.transpose(2, 1, 0) if bodies else None)
+
+    def device_water(self):
+        """(device address of the water volume, device address of the body volume, volume dims) of the flood; valid until the next
+        terrain_flood, terrain_init, terrain_load or close."""
+        w, b, vd = ctypes.c_void_p(), ctypes.c_void_p(), (ctypes.c_int32 * 3)()
+        self._check(self._L.vtmc_water_device_results(self._h, ctypes.byref(w), ctypes.byref(b), ctypes.byref(vd)))
+        return w.value, b.value, tuple(vd)
+
+    def water_probe(self, positions):
+        """(body, depth) of world positions (n, 3): the body of the nearest sample when it is wet and the depth level - y under its level;
+        -1 and 0 otherwise.  What a swimmer or a buoyant body asks."""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        body, depth = np.full(len(p), -1, np.int32), np.zeros(len(p), np.float32)
+        self._check(self._L.vtmc_water_probe(self._h, _ptr(p) if len(p) else None, len(p), _ptr(body), _ptr(depth)))
+        return body, depth
+
+    def water_extract(self):
+        """The water's surface: the water volume, as it lies on the device, through extract_volumes_device as a batch of one.  Returns T.
+        This REPLACES the context's extract result, as any extract does (read_triangles gives the water's records; water_world_positions
+        places them); 0 without a launch for an empty box."""
+        w, _, vd = self.device_water()
+        if not w:
+            return 0
+        return self.extract_volumes_device(w, tuple(d - 2 for d in vd), (1, vd[0], vd[0] * vd[1]))
+
+    def water_world_positions(self, block, local_positions):
+        """World positions (float64) of block-local positions of a water_extract mesh: terrain origin + (box_lo + 8b + p) * voxel scale,
+        with b the block coordinates of `block` in the volume.  block: (n,); local_positions: (n, 3) or (n, m, 3)."""
+        lo, _, vd, _, _ = self.water_info()
+        nbx, nby = max((vd[0] - 2) // 8, 1), max((vd[1] - 2) // 8, 1)
+        block = np.asarray(block, np.int64)
+        b = np.stack([block % nbx, block // nbx % nby, block // (nbx * nby)], axis=-1).astype(np.float64)
+        p = np.asarray(local_positions, np.float64)
+        if p.ndim == 3:
+            b = b[:, None, :]
+        origin, scale = self._terrain_placement
+        return np.asarray(origin, np.float64) + (np.asarray(lo, np.float64) + 8.0 * b + p) * float(scale)
 
     # -- material layer: VoxelTerrain.SetControlMap's splat volumes in HBM, paint, and per-vertex weights -------------
     def material_init(self, fineness):
