@@ -106,325 +106,87 @@ float IslandModifier::QueryDensity(const Vector3 &pos) const
 }
 
 // ---------------------------------------------------------------------------------------------
-// default backend: libvtmc.so
+// the vtmc context: the default backend of host grids, and what every device-resident method calls
 // ---------------------------------------------------------------------------------------------
-namespace {
-class VtmcBackend : public ExtractBackend {
+// One ABI call and its check: the name in the message is the call's own text up to its '('.
+#define VTMC_CHECK(c, call) (c).Check((call), #call)
+
+class VtmcContext : public ExtractBackend {
 public:
-    explicit VtmcBackend(int device)
+    vtmc_ctx *ctx = nullptr;
+    int dims[3] = {0, 0, 0};  // of the resident terrain, as Init made it
+
+    // replaces the three table uploads of Init (VoxelTerrain.cs:151-156); ctx stays null on failure, which reads the global error text
+    explicit VtmcContext(int device) { VTMC_CHECK(*this, vtmc_create(device, &ctx)); }
+    ~VtmcContext() override { vtmc_destroy(ctx); }  // VoxelTerrain.cs:228-244
+
+    void Check(int status, const char *call) const
     {
-        // replaces the three table uploads of Init (VoxelTerrain.cs:151-156)
-        if (vtmc_create(device, &_ctx) != VTMC_OK) throw UnityException(std::string("vtmc_create: ") + vtmc_last_error(nullptr));
+        if (status != VTMC_OK) throw UnityException(std::string(call, std::strcspn(call, "(")) + ": " + vtmc_last_error(ctx));
     }
-    ~VtmcBackend() override { vtmc_destroy(_ctx); }  // VoxelTerrain.cs:228-244
+
+    // the triangles of the result the context holds, sliced by the `lists` blocks or nodes they were extracted for
+    void ReadTriangles(int32_t triNum, size_t lists, std::vector<CSTriangle> &tris, std::vector<int> &offsets)
+    {
+        tris.resize((size_t)triNum);
+        offsets.assign(lists + 1, 0);
+        VTMC_CHECK(*this, vtmc_read_triangles(ctx, reinterpret_cast<vtmc_triangle *>(tris.data()), triNum, offsets.data()));
+    }
+
     void Extract(const float *grid, int w, int e, int h, const std::vector<Int3> &blocks, std::vector<CSTriangle> &tris,
                  std::vector<int> &offsets) override
     {
         std::vector<int32_t> list;
         list.reserve(blocks.size() * 3);
-        for (const Int3 &b : blocks) {
-            list.push_back(b._x);
-            list.push_back(b._y);
-            list.push_back(b._z);
-        }
+        for (const Int3 &b : blocks) list.insert(list.end(), {b._x, b._y, b._z});
         int32_t triNum = 0;
         // a C# float[W+2,E+2,H+2] is z fastest: strides ((E+2)(H+2), H+2, 1)
-        int rc = vtmc_extract_grid(_ctx, grid, w, e, h, (int64_t)(e + 2) * (h + 2), h + 2, 1, list.data(), (int32_t)blocks.size(), &triNum);
-        if (rc != VTMC_OK) throw UnityException(std::string("vtmc_extract_grid: ") + vtmc_last_error(_ctx));
-        tris.resize((size_t)triNum);
-        offsets.assign(blocks.size() + 1, 0);
-        rc = vtmc_read_triangles(_ctx, reinterpret_cast<vtmc_triangle *>(tris.data()), triNum, offsets.data());
-        if (rc != VTMC_OK) throw UnityException(std::string("vtmc_read_triangles: ") + vtmc_last_error(_ctx));
+        VTMC_CHECK(*this, vtmc_extract_grid(ctx, grid, w, e, h, (int64_t)(e + 2) * (h + 2), h + 2, 1, list.data(), (int32_t)blocks.size(), &triNum));
+        ReadTriangles(triNum, blocks.size(), tris, offsets);
     }
-
-    bool TerrainInit(int w, int e, int h, float scale, const Vector3 &origin, uint64_t seed) override
-    {
-        const float o[3] = {origin.x, origin.y, origin.z};
-        if (vtmc_terrain_init(_ctx, w, e, h, scale, o, seed) != VTMC_OK)
-            throw UnityException(std::string("vtmc_terrain_init: ") + vtmc_last_error(_ctx));
-        _dims[0] = w;
-        _dims[1] = e;
-        _dims[2] = h;
-        return true;
-    }
-    void TerrainUpdate(const std::vector<QueuedModifier> &queue, std::vector<Int3> &blocks, std::vector<CSTriangle> &tris,
-                       std::vector<int> &offsets) override
-    {
-        std::vector<vtmc_modifier> mods(queue.size());
-        for (size_t i = 0; i < queue.size(); i++) {
-            vtmc_modifier &m = mods[i];
-            m.kind = queue[i].desc.kind;
-            m.add_or_erode = queue[i].addOrErode ? 1 : 0;
-            const Vector3 &lo = queue[i].lower, &up = queue[i].upper;
-            m.lower[0] = lo.x, m.lower[1] = lo.y, m.lower[2] = lo.z;
-            m.upper[0] = up.x, m.upper[1] = up.y, m.upper[2] = up.z;
-            std::memcpy(m.p, queue[i].desc.p, sizeof m.p);
-            m.data = queue[i].desc.data;
-            m.data_dims[0] = queue[i].desc.dims[0];
-            m.data_dims[1] = queue[i].desc.dims[1];
-        }
-        int32_t nDirty = 0, triNum = 0;
-        if (vtmc_terrain_update(_ctx, mods.data(), (int32_t)mods.size(), &nDirty, &triNum) != VTMC_OK)
-            throw UnityException(std::string("vtmc_terrain_update: ") + vtmc_last_error(_ctx));
-        std::vector<int32_t> list((size_t)nDirty * 3);
-        if (vtmc_terrain_dirty_blocks(_ctx, list.data(), nDirty, nullptr) != VTMC_OK)
-            throw UnityException(std::string("vtmc_terrain_dirty_blocks: ") + vtmc_last_error(_ctx));
-        blocks.clear();
-        for (int32_t i = 0; i < nDirty; i++) blocks.emplace_back(list[3 * (size_t)i], list[3 * (size_t)i + 1], list[3 * (size_t)i + 2]);
-        tris.resize((size_t)triNum);
-        offsets.assign((size_t)nDirty + 1, 0);
-        if (nDirty > 0 && vtmc_read_triangles(_ctx, reinterpret_cast<vtmc_triangle *>(tris.data()), triNum, offsets.data()) != VTMC_OK)
-            throw UnityException(std::string("vtmc_read_triangles: ") + vtmc_last_error(_ctx));
-    }
-    void TerrainReadSamples(std::vector<float> &out) override
-    {
-        const int64_t ey = _dims[1] + 2, ez = _dims[2] + 2;
-        out.resize((size_t)(_dims[0] + 2) * ey * ez);
-        // into the C# float[W+2,E+2,H+2] layout: z fastest
-        if (vtmc_terrain_read_samples(_ctx, out.data(), ey * ez, ez, 1) != VTMC_OK)
-            throw UnityException(std::string("vtmc_terrain_read_samples: ") + vtmc_last_error(_ctx));
-    }
-
-    void TerrainFragments(const Vector3 &lower, const Vector3 &upper, int maxSamples, int captureMinSamples, std::vector<Fragment> &out) override
-    {
-        const float lo[3] = {lower.x, lower.y, lower.z}, up[3] = {upper.x, upper.y, upper.z};
-        int32_t n = 0;
-        if (vtmc_terrain_fragments(_ctx, lo, up, maxSamples, 0, nullptr, 0, &n) != VTMC_OK)
-            throw UnityException(std::string("vtmc_terrain_fragments: ") + vtmc_last_error(_ctx));
-        std::vector<vtmc_fragment> list((size_t)n);
-        if (n > 0 && vtmc_terrain_fragments(_ctx, lo, up, maxSamples, captureMinSamples, list.data(), n, &n) != VTMC_OK)
-            throw UnityException(std::string("vtmc_terrain_fragments: ") + vtmc_last_error(_ctx));
-        out.clear();
-        for (const vtmc_fragment &f : list)
-            out.push_back(Fragment{Int3(f.seed[0], f.seed[1], f.seed[2]), Int3(f.lo[0], f.lo[1], f.lo[2]), Int3(f.hi[0], f.hi[1], f.hi[2]), f.n_samples,
-                                   f.stamp_id});
-    }
-
-    void TerrainNav(const Vector3 &lower, const Vector3 &upper, int agentHeight, float maxStep, int maxSpans, NavResult &out) override
-    {
-        const float lo[3] = {lower.x, lower.y, lower.z}, up[3] = {upper.x, upper.y, upper.z};
-        vtmc_nav_params p;
-        p.agent_height = agentHeight, p.max_step = maxStep, p.max_spans = maxSpans, p.flags = 0;
-        int32_t n = 0;
-        if (vtmc_terrain_nav_build(_ctx, lo, up, &p, &n) != VTMC_OK) throw UnityException(std::string("vtmc_terrain_nav_build: ") + vtmc_last_error(_ctx));
-        ReadNav(out);
-        out._origin.clear();
-    }
-
-    // the nav result the context holds
-    void ReadNav(NavResult &out)
-    {
-        int32_t n = 0, first[3], dims[3];
-        if (vtmc_nav_info(_ctx, first, dims, &n) != VTMC_OK) throw UnityException(std::string("vtmc_nav_info: ") + vtmc_last_error(_ctx));
-        std::vector<vtmc_nav_span> list((size_t)n);
-        out._columnOffsets.assign((size_t)dims[0] * (size_t)dims[2] + 1, 0);
-        static_assert(sizeof(int) == sizeof(int32_t), "column offsets are read in place");
-        if (vtmc_nav_read(_ctx, list.data(), n, out._columnOffsets.data()) != VTMC_OK)
-            throw UnityException(std::string("vtmc_nav_read: ") + vtmc_last_error(_ctx));
-        out._boxLo = Int3(first[0], first[1], first[2]);
-        out._boxDims = Int3(dims[0], dims[1], dims[2]);
-        out._spans.clear();
-        for (const vtmc_nav_span &s : list) out._spans.push_back(NavSpan{s.height, s.y, s.clearance, {s.link[0], s.link[1], s.link[2], s.link[3]}, s.region});
-    }
-
-    static vtmc_naverode_params ErodeParams(int radius, bool openBoxFaces)
-    {
-        vtmc_naverode_params p;
-        p.radius = radius, p.flags = openBoxFaces ? VTMC_NAVERODE_OPEN_BOX_FACES : 0u, p.reserved[0] = p.reserved[1] = 0;
-        return p;
-    }
-
-    void NavDistance(int radius, bool openBoxFaces, std::vector<int> &out) override
-    {
-        const vtmc_naverode_params p = ErodeParams(radius, openBoxFaces);
-        int32_t n = 0;
-        if (vtmc_nav_distance_build(_ctx, &p, nullptr) != VTMC_OK || vtmc_nav_distance_device_results(_ctx, nullptr, &n) != VTMC_OK)
-            throw UnityException(std::string("vtmc_nav_distance_build: ") + vtmc_last_error(_ctx));
-        out.assign((size_t)n, 0);
-        if (vtmc_nav_distance_read(_ctx, out.data(), n) != VTMC_OK) throw UnityException(std::string("vtmc_nav_distance_read: ") + vtmc_last_error(_ctx));
-    }
-
-    void NavErode(int radius, bool openBoxFaces, NavResult &out) override
-    {
-        const vtmc_naverode_params p = ErodeParams(radius, openBoxFaces);
-        int32_t n = 0;
-        if (vtmc_nav_erode(_ctx, &p, &n) != VTMC_OK) throw UnityException(std::string("vtmc_nav_erode: ") + vtmc_last_error(_ctx));
-        ReadNav(out);
-        out._origin.assign((size_t)n, 0);
-        if (vtmc_nav_erode_origin(_ctx, out._origin.data(), n) != VTMC_OK) throw UnityException(std::string("vtmc_nav_erode_origin: ") + vtmc_last_error(_ctx));
-    }
-
-    void NavLocate(const std::vector<Vector3> &positions, float below, float above, std::vector<int> &out) override
-    {
-        std::vector<float> p;
-        for (const Vector3 &v : positions) p.insert(p.end(), {v.x, v.y, v.z});
-        out.assign(positions.size(), -1);
-        static_assert(sizeof(int) == sizeof(int32_t), "spans are read in place");
-        if (vtmc_nav_locate(_ctx, p.data(), (int32_t)positions.size(), below, above, out.data()) != VTMC_OK)
-            throw UnityException(std::string("vtmc_nav_locate: ") + vtmc_last_error(_ctx));
-    }
-    void NavField(const std::vector<NavGoal> &goals, float climbCost, float dropCost, unsigned maxCost, std::vector<NavFieldCell> &out) override
-    {
-        std::vector<vtmc_navfield_goal> g;
-        for (const NavGoal &goal : goals) g.push_back(vtmc_navfield_goal{goal._span, goal._cost});
-        vtmc_navfield_params p;
-        p.climb_cost = climbCost, p.drop_cost = dropCost, p.max_cost = maxCost, p.flags = 0;
-        int32_t n = 0;
-        if (vtmc_navfield_build(_ctx, g.data(), (int32_t)g.size(), &p, nullptr) != VTMC_OK || vtmc_navfield_info(_ctx, &n, nullptr, nullptr) != VTMC_OK)
-            throw UnityException(std::string("vtmc_navfield_build: ") + vtmc_last_error(_ctx));
-        std::vector<vtmc_navfield_cell> cells((size_t)n);
-        if (vtmc_navfield_read(_ctx, cells.data(), n) != VTMC_OK) throw UnityException(std::string("vtmc_navfield_read: ") + vtmc_last_error(_ctx));
-        out.clear();
-        for (const vtmc_navfield_cell &c : cells) out.push_back(NavFieldCell{c.cost, c.next});
-    }
-    void NavTrace(const std::vector<int> &starts, int maxLen, NavPaths &out) override
-    {
-        out._maxLen = maxLen;
-        out._paths.assign(starts.size() * (size_t)(maxLen > 0 ? maxLen : 0), -1);
-        out._lengths.assign(starts.size(), 0);
-        if (vtmc_navfield_trace(_ctx, starts.data(), (int32_t)starts.size(), maxLen, out._paths.data(), out._lengths.data()) != VTMC_OK)
-            throw UnityException(std::string("vtmc_navfield_trace: ") + vtmc_last_error(_ctx));
-    }
-    void NavSight(const std::vector<int> &from, const std::vector<int> &to, std::vector<NavSightHit> &out) override
-    {
-        if (from.size() != to.size()) throw UnityException("NavSight: as many from as to spans");
-        std::vector<vtmc_navsight_hit> hits(from.size());
-        if (vtmc_nav_sight(_ctx, from.data(), to.data(), (int32_t)from.size(), hits.data()) != VTMC_OK)
-            throw UnityException(std::string("vtmc_nav_sight: ") + vtmc_last_error(_ctx));
-        out.clear();
-        for (const vtmc_navsight_hit &h : hits) out.push_back(NavSightHit{h.last, h.steps});
-    }
-    void NavTraceSmooth(const std::vector<int> &starts, int maxLen, int maxLook, unsigned maxExtraCost, NavPaths &out) override
-    {
-        out._maxLen = maxLen;
-        out._paths.assign(starts.size() * (size_t)(maxLen > 0 ? maxLen : 0), -1);
-        out._lengths.assign(starts.size(), 0);
-        vtmc_navsight_params p;
-        p.max_look = maxLook, p.max_extra_cost = maxExtraCost, p.flags = 0, p.reserved = 0;
-        if (vtmc_navfield_trace_smooth(_ctx, starts.data(), (int32_t)starts.size(), maxLen, &p, out._paths.data(), out._lengths.data()) != VTMC_OK)
-            throw UnityException(std::string("vtmc_navfield_trace_smooth: ") + vtmc_last_error(_ctx));
-    }
-    int CrowdSpawn(const std::vector<int> &spans, const std::vector<unsigned> &speeds) override
-    {
-        if (spans.size() != speeds.size()) throw UnityException("SpawnCrowd: as many speeds as spans");
-        static_assert(sizeof(unsigned) == sizeof(uint32_t), "speeds are read in place");
-        int32_t placed = 0;
-        if (vtmc_navcrowd_spawn(_ctx, spans.data(), speeds.data(), (int32_t)spans.size(), &placed) != VTMC_OK)
-            throw UnityException(std::string("vtmc_navcrowd_spawn: ") + vtmc_last_error(_ctx));
-        return placed;
-    }
-    void CrowdStep(unsigned maxDetour, bool leaveOnArrival, int ticks) override
-    {
-        vtmc_navcrowd_params p;
-        p.max_detour = maxDetour, p.flags = leaveOnArrival ? VTMC_NAVCROWD_LEAVE_ON_ARRIVAL : 0u, p.reserved[0] = p.reserved[1] = 0u;
-        if (vtmc_navcrowd_step(_ctx, &p, ticks) != VTMC_OK) throw UnityException(std::string("vtmc_navcrowd_step: ") + vtmc_last_error(_ctx));
-    }
-    void CrowdRead(CrowdResult &out) override
-    {
-        int32_t n = 0, nSpans = 0;
-        if (vtmc_navcrowd_info(_ctx, &n, &out._occupying, &out._arrived, &out._ticks, &out._movedLast) != VTMC_OK || vtmc_nav_info(_ctx, nullptr, nullptr, &nSpans) != VTMC_OK)
-            throw UnityException(std::string("vtmc_navcrowd_info: ") + vtmc_last_error(_ctx));
-        std::vector<vtmc_navcrowd_agent> agents((size_t)n);
-        out._occupancy.assign((size_t)nSpans, -1);
-        if (vtmc_navcrowd_read(_ctx, agents.data(), n, out._occupancy.data()) != VTMC_OK) throw UnityException(std::string("vtmc_navcrowd_read: ") + vtmc_last_error(_ctx));
-        out._agents.clear();
-        for (const vtmc_navcrowd_agent &a : agents) out._agents.push_back(CrowdAgent{a.span, a.budget, a.speed, a.state});
-    }
-    void Flood(const float *lower, const float *upper, const std::vector<WaterSource> &sources, WaterResult &out) override
-    {
-        static_assert(sizeof(WaterBody) == sizeof(vtmc_water_body) && sizeof(WaterSource) == sizeof(vtmc_water_source), "copied as they lie");
-        std::vector<vtmc_water_source> src(sources.size());
-        for (size_t i = 0; i < sources.size(); i++) {
-            src[i].position[0] = sources[i]._position.x, src[i].position[1] = sources[i]._position.y, src[i].position[2] = sources[i]._position.z;
-            src[i].level = sources[i]._level;
-        }
-        out = WaterResult();
-        out._sourceBody.assign(sources.size(), -1);
-        int32_t n = 0;
-        if (vtmc_terrain_flood(_ctx, lower, upper, src.data(), (int32_t)src.size(), 0u, out._sourceBody.data(), &n) != VTMC_OK)
-            throw UnityException(std::string("vtmc_terrain_flood: ") + vtmc_last_error(_ctx));
-        int64_t wet = 0;
-        if (vtmc_water_info(_ctx, out._boxLo, out._boxDims, out._volumeDims, &n, &wet) != VTMC_OK) throw UnityException(std::string("vtmc_water_info: ") + vtmc_last_error(_ctx));
-        out._wet = wet;
-        out._bodies.resize((size_t)n);
-        if (vtmc_water_bodies(_ctx, reinterpret_cast<vtmc_water_body *>(out._bodies.data()), n) != VTMC_OK)
-            throw UnityException(std::string("vtmc_water_bodies: ") + vtmc_last_error(_ctx));
-        const size_t vn = (size_t)out._volumeDims[0] * out._volumeDims[1] * out._volumeDims[2];
-        out._water.resize(vn), out._bodyVolume.resize(vn);
-        if (vtmc_water_read(_ctx, out._water.data(), out._bodyVolume.data(), (int64_t)vn) != VTMC_OK) throw UnityException(std::string("vtmc_water_read: ") + vtmc_last_error(_ctx));
-    }
-    void ProbeWater(const std::vector<Vector3> &positions, std::vector<WaterProbe> &out) override
-    {
-        std::vector<float> p;
-        for (const Vector3 &v : positions) p.push_back(v.x), p.push_back(v.y), p.push_back(v.z);
-        std::vector<int32_t> body(positions.size(), -1);
-        std::vector<float> depth(positions.size(), 0.0f);
-        if (vtmc_water_probe(_ctx, p.data(), (int32_t)positions.size(), body.data(), depth.data()) != VTMC_OK)
-            throw UnityException(std::string("vtmc_water_probe: ") + vtmc_last_error(_ctx));
-        out.clear();
-        for (size_t i = 0; i < positions.size(); i++) out.push_back(WaterProbe{body[i], depth[i]});
-    }
-
-    int MaterialInit(int fineness) override
-    {
-        if (vtmc_material_init(_ctx, fineness) != VTMC_OK) throw UnityException(std::string("vtmc_material_init: ") + vtmc_last_error(_ctx));
-        return 16 * fineness;
-    }
-    void MaterialSetControlMap(const Color *mapData, int group) override
-    {
-        if (vtmc_material_set_control_map(_ctx, reinterpret_cast<const float *>(mapData), group) != VTMC_OK)
-            throw UnityException(std::string("vtmc_material_set_control_map: ") + vtmc_last_error(_ctx));
-    }
-    void MaterialPaint(const std::vector<MaterialStroke> &strokes) override
-    {
-        std::vector<vtmc_material_stroke> s(strokes.size());
-        for (size_t i = 0; i < strokes.size(); i++) {
-            s[i].center[0] = strokes[i]._center.x, s[i].center[1] = strokes[i]._center.y, s[i].center[2] = strokes[i]._center.z;
-            s[i].radius = strokes[i]._radius;
-            s[i].strength = strokes[i]._strength;
-            s[i].channel = strokes[i]._channel;
-        }
-        if (vtmc_material_paint(_ctx, s.data(), (int32_t)s.size()) != VTMC_OK)
-            throw UnityException(std::string("vtmc_material_paint: ") + vtmc_last_error(_ctx));
-    }
-    void MaterialVertices(std::vector<uint8_t> &out) override
-    {
-        int64_t n = 0;
-        if (vtmc_material_vertices(_ctx, &n) != VTMC_OK) throw UnityException(std::string("vtmc_material_vertices: ") + vtmc_last_error(_ctx));
-        out.resize((size_t)n * VTMC_MATERIAL_CHANNELS);
-        if (vtmc_material_read_vertices(_ctx, out.data(), n) != VTMC_OK)
-            throw UnityException(std::string("vtmc_material_read_vertices: ") + vtmc_last_error(_ctx));
-    }
-
-    void TerrainExtractLod(const Vector3 &viewer, int maxLevel, float split, int maxNodes, std::vector<LodNode> &nodes,
-                           std::vector<CSTriangle> &tris, std::vector<int> &offsets) override
-    {
-        vtmc_lod_params p;
-        p.viewer[0] = viewer.x, p.viewer[1] = viewer.y, p.viewer[2] = viewer.z;
-        p.split = split;
-        p.max_level = maxLevel;
-        p.max_nodes = maxNodes;
-        int32_t nNodes = 0, triNum = 0;
-        if (vtmc_terrain_extract_lod(_ctx, &p, &nNodes, &triNum) != VTMC_OK)
-            throw UnityException(std::string("vtmc_terrain_extract_lod: ") + vtmc_last_error(_ctx));
-        std::vector<vtmc_lod_node> list((size_t)nNodes);
-        if (vtmc_terrain_lod_nodes(_ctx, list.data(), nNodes, nullptr) != VTMC_OK)
-            throw UnityException(std::string("vtmc_terrain_lod_nodes: ") + vtmc_last_error(_ctx));
-        nodes.clear();
-        for (const vtmc_lod_node &nd : list) nodes.push_back(LodNode{MathHelper::Int3(nd.origin[0], nd.origin[1], nd.origin[2]), nd.level});
-        tris.resize((size_t)triNum);
-        offsets.assign((size_t)nNodes + 1, 0);
-        if (vtmc_read_triangles(_ctx, reinterpret_cast<vtmc_triangle *>(tris.data()), triNum, offsets.data()) != VTMC_OK)
-            throw UnityException(std::string("vtmc_read_triangles: ") + vtmc_last_error(_ctx));
-    }
-
-private:
-    vtmc_ctx *_ctx = nullptr;
-    int _dims[3] = {0, 0, 0};
 };
-}  // namespace
 
-std::shared_ptr<ExtractBackend> MakeVtmcBackend(int device) { return std::make_shared<VtmcBackend>(device); }
+std::shared_ptr<ExtractBackend> MakeVtmcBackend(int device) { return std::make_shared<VtmcContext>(device); }
+
+static_assert(sizeof(int) == sizeof(int32_t) && sizeof(unsigned) == sizeof(uint32_t), "spans, offsets and speeds are read in place");
+
+// a Vector3 as the ABI's float[3]; returns what follows it, for arrays of them
+static float *Put3(float *out, const Vector3 &v)
+{
+    out[0] = v.x, out[1] = v.y, out[2] = v.z;
+    return out + 3;
+}
+
+static std::vector<float> Flatten(const std::vector<Vector3> &positions)
+{
+    std::vector<float> p(positions.size() * 3);
+    float *q = p.data();
+    for (const Vector3 &v : positions) q = Put3(q, v);
+    return p;
+}
+
+// the rows TracePaths and SmoothPaths fill: maxLen spans per start, padded with -1
+static NavPaths PathRows(size_t starts, int maxLen)
+{
+    NavPaths out;
+    out._maxLen = maxLen;
+    out._paths.assign(starts * (size_t)(maxLen > 0 ? maxLen : 0), -1);
+    out._lengths.assign(starts, 0);
+    return out;
+}
+
+// VoxelTerrain.cs:430-465: one mesh of the triangles [begin, end): vertices (scaled), normals, trivial indices
+static void FillMesh(BlockMesh &mesh, const std::vector<CSTriangle> &csTriangles, int begin, int end, float scale)
+{
+    mesh.Clear();  // VoxelTerrain.cs:453
+    for (int t = begin; t < end; t++) {
+        const CSTriangle &vt = csTriangles[(size_t)t];
+        for (const float *p : {vt._position0, vt._position1, vt._position2}) mesh.vertices.push_back(Vector3(p[0], p[1], p[2]) * scale);
+        for (const float *n : {vt._normal0, vt._normal1, vt._normal2}) mesh.normals.push_back(Vector3(n[0], n[1], n[2]));
+    }
+    mesh.triangles.resize(mesh.vertices.size());
+    for (size_t k = 0; k < mesh.triangles.size(); k++) mesh.triangles[k] = (int)k;  // Enumerable.Range, VoxelTerrain.cs:457
+}
 
 // ---------------------------------------------------------------------------------------------
 VoxelTerrain::VoxelTerrain() = default;
@@ -442,10 +204,14 @@ void VoxelTerrain::Init()
     _blocks.assign((size_t)(_width / blockSize) * (_elevation / blockSize) * (_height / blockSize), BlockMesh());
     // augmented by one layer so normals on the positive boundary are defined (VoxelTerrain.cs:145)
     if (!_backend) _backend = MakeVtmcBackend(_device);  // throws when no HIP device: there is no CPU path
+    _vtmc = std::dynamic_pointer_cast<VtmcContext>(_backend);  // null for a backend of the caller's (SetBackend)
     if (_deviceResident) {
         _voxelSamples.clear();  // the grid lives in HBM
-        if (!_backend->TerrainInit(_width, _elevation, _height, _voxelScale, TerrainOrigin, _seed))
-            throw UnityException("backend has no device-resident terrain");
+        if (!_vtmc) throw UnityException("backend has no device-resident terrain");
+        float origin[3];
+        Put3(origin, TerrainOrigin);
+        VTMC_CHECK(*_vtmc, vtmc_terrain_init(_vtmc->ctx, _width, _elevation, _height, _voxelScale, origin, _seed));
+        _vtmc->dims[0] = _width, _vtmc->dims[1] = _elevation, _vtmc->dims[2] = _height;
     } else {
         _voxelSamples.resize((size_t)(_width + 2) * (_elevation + 2) * (_height + 2));
         for (float &s : _voxelSamples) s = voidDensity();
@@ -457,13 +223,20 @@ void VoxelTerrain::Init()
     _initialised = true;
 }
 
-void VoxelTerrain::EnsureMaterialLayer()
+VtmcContext &VoxelTerrain::RequireResident(const char *who) const
 {
-    if (!_initialised || !_deviceResident) throw UnityException("the material layer needs an initialised device-resident terrain");
-    if (_hasMaterialLayer) return;
+    if (!_initialised || !_deviceResident || !_vtmc) throw UnityException(std::string(who) + " needs an initialised device-resident terrain");
+    return *_vtmc;
+}
+
+VtmcContext &VoxelTerrain::EnsureMaterialLayer()
+{
+    VtmcContext &c = RequireResident("the material layer");
+    if (_hasMaterialLayer) return c;
     _matControlFineness = std::min(std::max(_matControlFineness, 1), 8);  // Mathf.Clamp, VoxelTerrain.cs:191
-    _backend->MaterialInit(_matControlFineness);
+    VTMC_CHECK(c, vtmc_material_init(c.ctx, _matControlFineness));
     _hasMaterialLayer = true;
+    return c;
 }
 
 // VoxelTerrain.cs:186-209
@@ -472,163 +245,247 @@ void VoxelTerrain::SetControlMap(const Color *mapData, size_t length, int group)
     if (group < 1 || group > 2) throw UnityException("invalid control map group");
     const size_t controlMapSize = (size_t)std::min(std::max(_matControlFineness, 1), 8) * 16;
     if (!mapData || length != controlMapSize * controlMapSize * controlMapSize) throw UnityException("invalid control map data size");
-    EnsureMaterialLayer();
-    _backend->MaterialSetControlMap(mapData, group);
+    VtmcContext &c = EnsureMaterialLayer();
+    VTMC_CHECK(c, vtmc_material_set_control_map(c.ctx, reinterpret_cast<const float *>(mapData), group));
 }
 
 void VoxelTerrain::Paint(const std::vector<MaterialStroke> &strokes)
 {
-    EnsureMaterialLayer();
-    _backend->MaterialPaint(strokes);
+    VtmcContext &c = EnsureMaterialLayer();
+    std::vector<vtmc_material_stroke> s(strokes.size());
+    for (size_t i = 0; i < strokes.size(); i++) {
+        Put3(s[i].center, strokes[i]._center);
+        s[i].radius = strokes[i]._radius;
+        s[i].strength = strokes[i]._strength;
+        s[i].channel = strokes[i]._channel;
+    }
+    VTMC_CHECK(c, vtmc_material_paint(c.ctx, s.data(), (int32_t)s.size()));
 }
 
+// 8 bytes per vertex of the last Update's result: vertex 3 t + v of triangle t
 const std::vector<uint8_t> &VoxelTerrain::VertexMaterials()
 {
-    EnsureMaterialLayer();
-    _backend->MaterialVertices(_vertexMaterials);
+    VtmcContext &c = EnsureMaterialLayer();
+    int64_t n = 0;
+    VTMC_CHECK(c, vtmc_material_vertices(c.ctx, &n));
+    _vertexMaterials.resize((size_t)n * VTMC_MATERIAL_CHANNELS);
+    VTMC_CHECK(c, vtmc_material_read_vertices(c.ctx, _vertexMaterials.data(), n));
     return _vertexMaterials;
 }
 
 std::vector<Fragment> VoxelTerrain::Fragments(const Vector3 &lower, const Vector3 &upper, int maxSamples, int captureMinSamples)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("Fragments needs an initialised device-resident terrain");
+    VtmcContext &c = RequireResident("Fragments");
+    float lo[3], up[3];
+    Put3(lo, lower), Put3(up, upper);
+    int32_t n = 0;
+    VTMC_CHECK(c, vtmc_terrain_fragments(c.ctx, lo, up, maxSamples, 0, nullptr, 0, &n));
+    std::vector<vtmc_fragment> list((size_t)n);
+    if (n > 0) VTMC_CHECK(c, vtmc_terrain_fragments(c.ctx, lo, up, maxSamples, captureMinSamples, list.data(), n, &n));
     std::vector<Fragment> out;
-    _backend->TerrainFragments(lower, upper, maxSamples, captureMinSamples, out);
+    for (const vtmc_fragment &f : list)
+        out.push_back(Fragment{Int3(f.seed[0], f.seed[1], f.seed[2]), Int3(f.lo[0], f.lo[1], f.lo[2]), Int3(f.hi[0], f.hi[1], f.hi[2]), f.n_samples,
+                               f.stamp_id});
+    return out;
+}
+
+// the nav result the context holds
+static NavResult ReadNav(VtmcContext &c)
+{
+    NavResult out;
+    int32_t n = 0, first[3], dims[3];
+    VTMC_CHECK(c, vtmc_nav_info(c.ctx, first, dims, &n));
+    std::vector<vtmc_nav_span> list((size_t)n);
+    out._columnOffsets.assign((size_t)dims[0] * (size_t)dims[2] + 1, 0);
+    VTMC_CHECK(c, vtmc_nav_read(c.ctx, list.data(), n, out._columnOffsets.data()));
+    out._boxLo = Int3(first[0], first[1], first[2]);
+    out._boxDims = Int3(dims[0], dims[1], dims[2]);
+    for (const vtmc_nav_span &s : list) out._spans.push_back(NavSpan{s.height, s.y, s.clearance, {s.link[0], s.link[1], s.link[2], s.link[3]}, s.region});
     return out;
 }
 
 NavResult VoxelTerrain::BuildNav(const Vector3 &lower, const Vector3 &upper, float agentHeight, float maxStep, int maxSpans)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("BuildNav needs an initialised device-resident terrain");
+    VtmcContext &c = RequireResident("BuildNav");
     const float samples = std::ceil(agentHeight / _voxelScale);
     if (!(samples >= 1.0f && samples <= (float)VTMC_NAV_MAX_AGENT_HEIGHT)) throw UnityException("BuildNav: agentHeight outside 1..256 samples");
-    NavResult out;
-    _backend->TerrainNav(lower, upper, (int)samples, maxStep / _voxelScale, maxSpans, out);
-    return out;
+    float lo[3], up[3];
+    Put3(lo, lower), Put3(up, upper);
+    const vtmc_nav_params p = {(int)samples, maxStep / _voxelScale, maxSpans, 0u};
+    int32_t n = 0;
+    VTMC_CHECK(c, vtmc_terrain_nav_build(c.ctx, lo, up, &p, &n));
+    return ReadNav(c);
 }
 
-static int NavRadiusColumns(float radius, float voxelScale, const char *who)
+// radius in columns, as both calls of include/vtmc_naverode.h take it
+static vtmc_naverode_params ErodeParams(float radius, float voxelScale, bool openBoxFaces, const char *who)
 {
     const float columns = std::ceil(radius / voxelScale);
     if (!(columns >= 0.0f && columns <= (float)VTMC_NAVERODE_MAX_RADIUS)) throw UnityException(std::string(who) + ": radius outside 0..255 columns");
-    return (int)columns;
+    return vtmc_naverode_params{(int)columns, openBoxFaces ? VTMC_NAVERODE_OPEN_BOX_FACES : 0u, {0, 0}};
 }
 
 std::vector<int> VoxelTerrain::NavDistance(float radius, bool openBoxFaces)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("NavDistance needs an initialised device-resident terrain");
-    std::vector<int> out;
-    _backend->NavDistance(NavRadiusColumns(radius, _voxelScale, "NavDistance"), openBoxFaces, out);
+    VtmcContext &c = RequireResident("NavDistance");
+    const vtmc_naverode_params p = ErodeParams(radius, _voxelScale, openBoxFaces, "NavDistance");
+    int32_t n = 0;
+    VTMC_CHECK(c, vtmc_nav_distance_build(c.ctx, &p, nullptr));
+    VTMC_CHECK(c, vtmc_nav_distance_device_results(c.ctx, nullptr, &n));
+    std::vector<int> out((size_t)n, 0);
+    VTMC_CHECK(c, vtmc_nav_distance_read(c.ctx, out.data(), n));
     return out;
 }
 
 NavResult VoxelTerrain::ErodeNav(float radius, bool openBoxFaces)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("ErodeNav needs an initialised device-resident terrain");
-    NavResult out;
-    _backend->NavErode(NavRadiusColumns(radius, _voxelScale, "ErodeNav"), openBoxFaces, out);
+    VtmcContext &c = RequireResident("ErodeNav");
+    const vtmc_naverode_params p = ErodeParams(radius, _voxelScale, openBoxFaces, "ErodeNav");
+    int32_t n = 0;
+    VTMC_CHECK(c, vtmc_nav_erode(c.ctx, &p, &n));
+    NavResult out = ReadNav(c);
+    out._origin.assign((size_t)n, 0);
+    VTMC_CHECK(c, vtmc_nav_erode_origin(c.ctx, out._origin.data(), n));
     return out;
 }
 
 std::vector<int> VoxelTerrain::LocateOnNav(const std::vector<Vector3> &positions, float below, float above)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("LocateOnNav needs an initialised device-resident terrain");
-    std::vector<int> out;
-    _backend->NavLocate(positions, below / _voxelScale, above / _voxelScale, out);
+    VtmcContext &c = RequireResident("LocateOnNav");
+    std::vector<int> out(positions.size(), -1);
+    VTMC_CHECK(c, vtmc_nav_locate(c.ctx, Flatten(positions).data(), (int32_t)positions.size(), below / _voxelScale, above / _voxelScale, out.data()));
     return out;
 }
 
 std::vector<NavFieldCell> VoxelTerrain::BuildNavField(const std::vector<NavGoal> &goals, float climbCost, float dropCost, unsigned maxCost)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("BuildNavField needs an initialised device-resident terrain");
+    VtmcContext &c = RequireResident("BuildNavField");
+    std::vector<vtmc_navfield_goal> g;
+    for (const NavGoal &goal : goals) g.push_back(vtmc_navfield_goal{goal._span, goal._cost});
+    const vtmc_navfield_params p = {climbCost, dropCost, maxCost, 0u};
+    int32_t n = 0;
+    VTMC_CHECK(c, vtmc_navfield_build(c.ctx, g.data(), (int32_t)g.size(), &p, nullptr));
+    VTMC_CHECK(c, vtmc_navfield_info(c.ctx, &n, nullptr, nullptr));
+    std::vector<vtmc_navfield_cell> cells((size_t)n);
+    VTMC_CHECK(c, vtmc_navfield_read(c.ctx, cells.data(), n));
     std::vector<NavFieldCell> out;
-    _backend->NavField(goals, climbCost, dropCost, maxCost, out);
+    for (const vtmc_navfield_cell &cell : cells) out.push_back(NavFieldCell{cell.cost, cell.next});
     return out;
 }
 
 NavPaths VoxelTerrain::TracePaths(const std::vector<int> &starts, int maxLen)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("TracePaths needs an initialised device-resident terrain");
-    NavPaths out;
-    _backend->NavTrace(starts, maxLen, out);
+    VtmcContext &c = RequireResident("TracePaths");
+    NavPaths out = PathRows(starts.size(), maxLen);
+    VTMC_CHECK(c, vtmc_navfield_trace(c.ctx, starts.data(), (int32_t)starts.size(), maxLen, out._paths.data(), out._lengths.data()));
     return out;
 }
 
 std::vector<NavSightHit> VoxelTerrain::NavSight(const std::vector<int> &from, const std::vector<int> &to)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("NavSight needs an initialised device-resident terrain");
+    VtmcContext &c = RequireResident("NavSight");
+    if (from.size() != to.size()) throw UnityException("NavSight: as many from as to spans");
+    std::vector<vtmc_navsight_hit> hits(from.size());
+    VTMC_CHECK(c, vtmc_nav_sight(c.ctx, from.data(), to.data(), (int32_t)from.size(), hits.data()));
     std::vector<NavSightHit> out;
-    _backend->NavSight(from, to, out);
+    for (const vtmc_navsight_hit &h : hits) out.push_back(NavSightHit{h.last, h.steps});
     return out;
 }
 
 NavPaths VoxelTerrain::SmoothPaths(const std::vector<int> &starts, int maxLen, int maxLook, unsigned maxExtraCost)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("SmoothPaths needs an initialised device-resident terrain");
-    NavPaths out;
-    _backend->NavTraceSmooth(starts, maxLen, maxLook, maxExtraCost, out);
+    VtmcContext &c = RequireResident("SmoothPaths");
+    NavPaths out = PathRows(starts.size(), maxLen);
+    const vtmc_navsight_params p = {maxLook, maxExtraCost, 0u, 0u};
+    VTMC_CHECK(c, vtmc_navfield_trace_smooth(c.ctx, starts.data(), (int32_t)starts.size(), maxLen, &p, out._paths.data(), out._lengths.data()));
     return out;
 }
 
 int VoxelTerrain::SpawnCrowd(const std::vector<int> &spans, const std::vector<unsigned> &speeds)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("SpawnCrowd needs an initialised device-resident terrain");
-    return _backend->CrowdSpawn(spans, speeds);
+    VtmcContext &c = RequireResident("SpawnCrowd");
+    if (spans.size() != speeds.size()) throw UnityException("SpawnCrowd: as many speeds as spans");
+    int32_t placed = 0;
+    VTMC_CHECK(c, vtmc_navcrowd_spawn(c.ctx, spans.data(), speeds.data(), (int32_t)spans.size(), &placed));
+    return placed;
 }
 
 void VoxelTerrain::StepCrowd(int ticks, unsigned maxDetour, bool leaveOnArrival)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("StepCrowd needs an initialised device-resident terrain");
-    _backend->CrowdStep(maxDetour, leaveOnArrival, ticks);
+    VtmcContext &c = RequireResident("StepCrowd");
+    const vtmc_navcrowd_params p = {maxDetour, leaveOnArrival ? VTMC_NAVCROWD_LEAVE_ON_ARRIVAL : 0u, {0u, 0u}};
+    VTMC_CHECK(c, vtmc_navcrowd_step(c.ctx, &p, ticks));
 }
 
 CrowdResult VoxelTerrain::ReadCrowd()
 {
-    if (!_initialised || !_deviceResident) throw UnityException("ReadCrowd needs an initialised device-resident terrain");
+    VtmcContext &c = RequireResident("ReadCrowd");
     CrowdResult out;
-    _backend->CrowdRead(out);
+    int32_t n = 0, nSpans = 0;
+    VTMC_CHECK(c, vtmc_navcrowd_info(c.ctx, &n, &out._occupying, &out._arrived, &out._ticks, &out._movedLast));
+    VTMC_CHECK(c, vtmc_nav_info(c.ctx, nullptr, nullptr, &nSpans));
+    std::vector<vtmc_navcrowd_agent> agents((size_t)n);
+    out._occupancy.assign((size_t)nSpans, -1);
+    VTMC_CHECK(c, vtmc_navcrowd_read(c.ctx, agents.data(), n, out._occupancy.data()));
+    for (const vtmc_navcrowd_agent &a : agents) out._agents.push_back(CrowdAgent{a.span, a.budget, a.speed, a.state});
     return out;
 }
 
 WaterResult VoxelTerrain::Flood(Vector3 lower, Vector3 upper, const std::vector<WaterSource> &sources)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("Flood needs an initialised device-resident terrain");
-    const float lo[3] = {lower.x, lower.y, lower.z}, up[3] = {upper.x, upper.y, upper.z};
+    VtmcContext &c = RequireResident("Flood");
+    static_assert(sizeof(WaterBody) == sizeof(vtmc_water_body), "copied as they lie");
+    float lo[3], up[3];
+    Put3(lo, lower), Put3(up, upper);
+    std::vector<vtmc_water_source> src(sources.size());
+    for (size_t i = 0; i < sources.size(); i++) {
+        Put3(src[i].position, sources[i]._position);
+        src[i].level = sources[i]._level;
+    }
     WaterResult out;
-    _backend->Flood(lo, up, sources, out);
+    out._sourceBody.assign(sources.size(), -1);
+    int32_t n = 0;
+    VTMC_CHECK(c, vtmc_terrain_flood(c.ctx, lo, up, src.data(), (int32_t)src.size(), 0u, out._sourceBody.data(), &n));
+    int64_t wet = 0;
+    VTMC_CHECK(c, vtmc_water_info(c.ctx, out._boxLo, out._boxDims, out._volumeDims, &n, &wet));
+    out._wet = wet;
+    out._bodies.resize((size_t)n);
+    VTMC_CHECK(c, vtmc_water_bodies(c.ctx, reinterpret_cast<vtmc_water_body *>(out._bodies.data()), n));
+    const size_t vn = (size_t)out._volumeDims[0] * out._volumeDims[1] * out._volumeDims[2];
+    out._water.resize(vn), out._bodyVolume.resize(vn);
+    VTMC_CHECK(c, vtmc_water_read(c.ctx, out._water.data(), out._bodyVolume.data(), (int64_t)vn));
     return out;
 }
 
 std::vector<WaterProbe> VoxelTerrain::ProbeWater(const std::vector<Vector3> &positions)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("ProbeWater needs an initialised device-resident terrain");
+    VtmcContext &c = RequireResident("ProbeWater");
+    std::vector<int32_t> body(positions.size(), -1);
+    std::vector<float> depth(positions.size(), 0.0f);
+    VTMC_CHECK(c, vtmc_water_probe(c.ctx, Flatten(positions).data(), (int32_t)positions.size(), body.data(), depth.data()));
     std::vector<WaterProbe> out;
-    _backend->ProbeWater(positions, out);
+    for (size_t i = 0; i < positions.size(); i++) out.push_back(WaterProbe{body[i], depth[i]});
     return out;
 }
 
 int VoxelTerrain::ExtractLod(const Vector3 &viewer, int maxLevel, float split, int maxNodes)
 {
-    if (!_initialised || !_deviceResident) throw UnityException("ExtractLod needs an initialised device-resident terrain");
-    std::vector<CSTriangle> csTriangles;
+    VtmcContext &c = RequireResident("ExtractLod");
+    vtmc_lod_params p;
+    Put3(p.viewer, viewer);
+    p.split = split, p.max_level = maxLevel, p.max_nodes = maxNodes;
+    int32_t nNodes = 0, triNum = 0;
+    VTMC_CHECK(c, vtmc_terrain_extract_lod(c.ctx, &p, &nNodes, &triNum));
+    std::vector<vtmc_lod_node> list((size_t)nNodes);
+    VTMC_CHECK(c, vtmc_terrain_lod_nodes(c.ctx, list.data(), nNodes, nullptr));
+    _lodNodes.clear();
+    for (const vtmc_lod_node &nd : list) _lodNodes.push_back(LodNode{Int3(nd.origin[0], nd.origin[1], nd.origin[2]), nd.level});
+    std::vector<CSTriangle> csTriangles;  // canonical order, _block = the node's index
     std::vector<int> offsets;
-    _backend->TerrainExtractLod(viewer, maxLevel, split, maxNodes, _lodNodes, csTriangles, offsets);
+    c.ReadTriangles(triNum, _lodNodes.size(), csTriangles, offsets);
     _lodMeshes.assign(_lodNodes.size(), BlockMesh());
-    for (size_t i = 0; i < _lodNodes.size(); i++) {
-        BlockMesh &mesh = _lodMeshes[i];
-        const float cell = (float)(1 << _lodNodes[i]._level) * _voxelScale;  // a node's cell in world units
-        for (int t = offsets[i]; t < offsets[i + 1]; t++) {
-            const CSTriangle &vt = csTriangles[(size_t)t];
-            mesh.vertices.push_back(Vector3(vt._position0[0], vt._position0[1], vt._position0[2]) * cell);
-            mesh.vertices.push_back(Vector3(vt._position1[0], vt._position1[1], vt._position1[2]) * cell);
-            mesh.vertices.push_back(Vector3(vt._position2[0], vt._position2[1], vt._position2[2]) * cell);
-            mesh.normals.push_back(Vector3(vt._normal0[0], vt._normal0[1], vt._normal0[2]));
-            mesh.normals.push_back(Vector3(vt._normal1[0], vt._normal1[1], vt._normal1[2]));
-            mesh.normals.push_back(Vector3(vt._normal2[0], vt._normal2[1], vt._normal2[2]));
-        }
-        mesh.triangles.resize(mesh.vertices.size());
-        for (size_t k = 0; k < mesh.triangles.size(); k++) mesh.triangles[k] = (int)k;
-    }
+    for (size_t i = 0; i < _lodNodes.size(); i++)  // a node's cell in world units is 2^level * _voxelScale
+        FillMesh(_lodMeshes[i], csTriangles, offsets[i], offsets[i + 1], (float)(1 << _lodNodes[i]._level) * _voxelScale);
     return (int)csTriangles.size();
 }
 
@@ -640,6 +497,7 @@ void VoxelTerrain::Free()
     _lodNodes.clear();
     _lodMeshes.clear();
     _backend.reset();
+    _vtmc.reset();
     _initialised = false;
 }
 
@@ -652,25 +510,38 @@ void VoxelTerrain::Update()
     if (!_initialised) throw UnityException("VoxelTerrain.Update before Init");
     if (_deviceResident) {
         // the whole of Update on the device: density writes, dirty set, BatchUpdate (VoxelTerrain.cs:262-325)
-        std::vector<ExtractBackend::QueuedModifier> queue;
+        VtmcContext &c = RequireResident("Update");
+        std::vector<vtmc_modifier> mods;
         std::vector<std::shared_ptr<TerrainModifier>> alive;  // descriptors borrow from the modifiers (heightmap) until the call returns
         while (!_modifierQueue.empty()) {
             std::shared_ptr<TerrainModifier> modifier = _modifierQueue.front();
             _modifierQueue.pop_front();
-            ExtractBackend::QueuedModifier q;
-            if (!modifier->Describe(q.desc)) throw UnityException("modifier cannot be evaluated on the device (Describe() returned false)");
-            q.addOrErode = modifier->AddOrErode;
-            q.lower = modifier->LowerBound();
-            q.upper = modifier->UpperBound();
-            queue.push_back(q);
+            ModifierDesc desc;
+            if (!modifier->Describe(desc)) throw UnityException("modifier cannot be evaluated on the device (Describe() returned false)");
+            vtmc_modifier m;
+            m.kind = desc.kind;
+            m.add_or_erode = modifier->AddOrErode ? 1 : 0;
+            Put3(m.lower, modifier->LowerBound());  // evaluated on the host, as VoxelTerrain.cs:273-279 does
+            Put3(m.upper, modifier->UpperBound());
+            std::memcpy(m.p, desc.p, sizeof m.p);
+            m.data = desc.data;
+            m.data_dims[0] = desc.dims[0], m.data_dims[1] = desc.dims[1];
+            mods.push_back(m);
             alive.push_back(std::move(modifier));
         }
         _lastUpdateBlocks.clear();
         _lastTriNum = 0;
-        if (queue.empty()) return;
+        if (mods.empty()) return;
+        // applies the queue in order and extracts the dirty set: its blocks ordered by block id, its triangles sliced by block
+        int32_t nDirty = 0, triNum = 0;
+        VTMC_CHECK(c, vtmc_terrain_update(c.ctx, mods.data(), (int32_t)mods.size(), &nDirty, &triNum));
+        std::vector<int32_t> list((size_t)nDirty * 3);
+        VTMC_CHECK(c, vtmc_terrain_dirty_blocks(c.ctx, list.data(), nDirty, nullptr));
+        _nextUpdateblocks.clear();
+        for (int32_t i = 0; i < nDirty; i++) _nextUpdateblocks.emplace_back(list[3 * (size_t)i], list[3 * (size_t)i + 1], list[3 * (size_t)i + 2]);
         std::vector<CSTriangle> csTriangles;
         std::vector<int> offsets;
-        _backend->TerrainUpdate(queue, _nextUpdateblocks, csTriangles, offsets);
+        if (nDirty > 0) c.ReadTriangles(triNum, (size_t)nDirty, csTriangles, offsets);
         _lastUpdateBlocks = _nextUpdateblocks;
         _lastTriNum = (int)csTriangles.size();
         if (!csTriangles.empty()) ApplyMeshes(csTriangles, offsets);
@@ -746,35 +617,26 @@ void VoxelTerrain::BatchUpdate()
     ApplyMeshes(csTriangles, offsets);
 }
 
+// the grid copied back into the C# float[W+2,E+2,H+2] layout: z fastest
 std::vector<float> VoxelTerrain::DeviceSamples() const
 {
-    std::vector<float> out;
-    if (!_deviceResident || !_backend) throw UnityException("DeviceSamples needs an initialised device-resident terrain");
-    _backend->TerrainReadSamples(out);
+    VtmcContext &c = RequireResident("DeviceSamples");
+    const int64_t ey = c.dims[1] + 2, ez = c.dims[2] + 2;
+    std::vector<float> out((size_t)(c.dims[0] + 2) * ey * ez);
+    VTMC_CHECK(c, vtmc_terrain_read_samples(c.ctx, out.data(), ey * ez, ez, 1));
     return out;
 }
 
-// VoxelTerrain.cs:430-465: per dirty block, vertices (scaled by _voxelScale), normals, trivial indices
+// VoxelTerrain.cs:430-465: the meshes of the dirty blocks, vertices scaled by _voxelScale
 void VoxelTerrain::ApplyMeshes(const std::vector<CSTriangle> &csTriangles, const std::vector<int> &offsets)
 {
     const int nby = _elevation / blockSize, nbz = _height / blockSize;
     for (size_t i = 0; i < _nextUpdateblocks.size(); i++) {
         const Int3 &b = _nextUpdateblocks[i];
-        BlockMesh &mesh = _blocks[((size_t)b._x * nby + b._y) * nbz + b._z];
-        mesh.Clear();  // VoxelTerrain.cs:453
-        for (int t = offsets[i]; t < offsets[i + 1]; t++) {
-            const CSTriangle &vt = csTriangles[(size_t)t];
-            mesh.vertices.push_back(Vector3(vt._position0[0], vt._position0[1], vt._position0[2]) * _voxelScale);
-            mesh.vertices.push_back(Vector3(vt._position1[0], vt._position1[1], vt._position1[2]) * _voxelScale);
-            mesh.vertices.push_back(Vector3(vt._position2[0], vt._position2[1], vt._position2[2]) * _voxelScale);
-            mesh.normals.push_back(Vector3(vt._normal0[0], vt._normal0[1], vt._normal0[2]));
-            mesh.normals.push_back(Vector3(vt._normal1[0], vt._normal1[1], vt._normal1[2]));
-            mesh.normals.push_back(Vector3(vt._normal2[0], vt._normal2[1], vt._normal2[2]));
-        }
-        mesh.triangles.resize(mesh.vertices.size());
-        for (size_t k = 0; k < mesh.triangles.size(); k++) mesh.triangles[k] = (int)k;  // Enumerable.Range, VoxelTerrain.cs:457
+        FillMesh(_blocks[((size_t)b._x * nby + b._y) * nbz + b._z], csTriangles, offsets[i], offsets[i + 1], _voxelScale);
     }
 }
 
 }  // namespace Render
 }  // namespace PGRTerrain
+

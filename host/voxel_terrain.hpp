@@ -435,72 +435,20 @@ struct CSTriangle {
 };
 static_assert(sizeof(CSTriangle) == 76, "CSTriangle must stay 76 bytes");
 
-// The extraction seam of BatchUpdate (VoxelTerrain.cs:365-427).  The default implementation calls
-// libvtmc.so; tests may install a recorder to check the host logic without a GPU.
+// The extraction seam of BatchUpdate (VoxelTerrain.cs:365-427), and the only seam there is: it serves terrains whose grid lives on the
+// host.  The default implementation calls libvtmc.so; tests may install a recorder to check the host logic without a GPU.  Everything
+// device-resident (vtmc_terrain_*, the material layer, level of detail, navigation, water) is not pluggable: VoxelTerrain calls the
+// library itself, through the one context the default backend owns, so a terrain with a backend of the caller's cannot be resident.
 struct ExtractBackend {
     virtual ~ExtractBackend() = default;
     // grid: float[(W+2),(E+2),(H+2)] z fastest; blocks: (x,y,z) triples.  Fills tris (canonical
     // order) and blockTriOffsets (B+1).  Throws UnityException on failure.
     virtual void Extract(const float *grid, int width, int elevation, int height, const std::vector<MathHelper::Int3> &blocks,
                          std::vector<CSTriangle> &tris, std::vector<int> &blockTriOffsets) = 0;
-
-    // Device-resident terrain (vtmc_terrain_*): the grid lives in HBM, Update's density write runs on
-    // the GPU.  A backend without it returns false from TerrainInit and the host path is used.
-    struct QueuedModifier {
-        ModifierDesc desc;
-        bool addOrErode;
-        Vector3 lower, upper;  // LowerBound / UpperBound, evaluated on the host as VoxelTerrain.cs:273-279 does
-    };
-    virtual bool TerrainInit(int, int, int, float, const Vector3 &, uint64_t) { return false; }
-    // Applies the queue in order and extracts the dirty set; fills blocks (ordered by block id), tris, offsets.
-    virtual void TerrainUpdate(const std::vector<QueuedModifier> &, std::vector<MathHelper::Int3> &, std::vector<CSTriangle> &,
-                               std::vector<int> &)
-    {
-        throw std::logic_error("TerrainUpdate on a backend without device-resident terrain");
-    }
-    virtual void TerrainReadSamples(std::vector<float> &) { throw std::logic_error("TerrainReadSamples unsupported"); }
-    // The floating fragments of a box of a device-resident terrain (vtmc_terrain_fragments), in increasing grid index of the seed.
-    virtual void TerrainFragments(const Vector3 &, const Vector3 &, int, int, std::vector<Fragment> &)
-    {
-        throw std::logic_error("TerrainFragments on a backend without device-resident terrain");
-    }
-    // The navigation build of a box of a device-resident terrain (vtmc_terrain_nav_build, vtmc_nav_read); agent height in samples, step in grid units.
-    virtual void TerrainNav(const Vector3 &, const Vector3 &, int, float, int, NavResult &)
-    {
-        throw std::logic_error("TerrainNav on a backend without device-resident terrain");
-    }
-    // Flow fields on that build (vtmc_nav_locate, vtmc_navfield_build with _read, vtmc_navfield_trace); below / above in grid units.
-    // The agent radius on that build (vtmc_nav_distance_build with _read; vtmc_nav_erode with vtmc_nav_read and _erode_origin); radius in columns.
-    virtual void NavDistance(int, bool, std::vector<int> &) { throw std::logic_error("NavDistance unsupported"); }
-    virtual void NavErode(int, bool, NavResult &) { throw std::logic_error("NavErode unsupported"); }
-    virtual void NavLocate(const std::vector<Vector3> &, float, float, std::vector<int> &) { throw std::logic_error("NavLocate unsupported"); }
-    virtual void NavField(const std::vector<NavGoal> &, float, float, unsigned, std::vector<NavFieldCell> &) { throw std::logic_error("NavField unsupported"); }
-    virtual void NavTrace(const std::vector<int> &, int, NavPaths &) { throw std::logic_error("NavTrace unsupported"); }
-    // Any-angle paths on that build and its field (vtmc_nav_sight, vtmc_navfield_trace_smooth).
-    virtual void NavSight(const std::vector<int> &, const std::vector<int> &, std::vector<NavSightHit> &) { throw std::logic_error("NavSight unsupported"); }
-    // A crowd on that build and its field (vtmc_navcrowd_spawn, _step, _read with _info).
-    virtual int CrowdSpawn(const std::vector<int> &, const std::vector<unsigned> &) { throw std::logic_error("CrowdSpawn unsupported"); }
-    virtual void CrowdStep(unsigned, bool, int) { throw std::logic_error("CrowdStep unsupported"); }
-    virtual void CrowdRead(CrowdResult &) { throw std::logic_error("CrowdRead unsupported"); }
-    // Standing water on the resident terrain (vtmc_terrain_flood with _info, _bodies and _read; vtmc_water_probe).
-    virtual void Flood(const float *, const float *, const std::vector<WaterSource> &, WaterResult &) { throw std::logic_error("Flood unsupported"); }
-    virtual void ProbeWater(const std::vector<Vector3> &, std::vector<WaterProbe> &) { throw std::logic_error("ProbeWater unsupported"); }
-    virtual void NavTraceSmooth(const std::vector<int> &, int, int, unsigned, NavPaths &) { throw std::logic_error("NavTraceSmooth unsupported"); }
-
-    // Material layer of a device-resident terrain (vtmc_material_*).  MaterialInit returns the layer's size C = 16 * fineness.
-    virtual int MaterialInit(int) { throw std::logic_error("MaterialInit on a backend without a material layer"); }
-    virtual void MaterialSetControlMap(const Color *, int) { throw std::logic_error("MaterialSetControlMap unsupported"); }
-    virtual void MaterialPaint(const std::vector<MaterialStroke> &) { throw std::logic_error("MaterialPaint unsupported"); }
-    // 8 bytes per vertex of the last TerrainUpdate's result: vertex 3 t + v of triangle t
-    virtual void MaterialVertices(std::vector<uint8_t> &) { throw std::logic_error("MaterialVertices unsupported"); }
-
-    // Level-of-detail extract of a device-resident terrain (vtmc_terrain_extract_lod): fills nodes (list order), tris (canonical order,
-    // _block = the node's index) and offsets (nodes + 1).
-    virtual void TerrainExtractLod(const Vector3 &, int, float, int, std::vector<LodNode> &, std::vector<CSTriangle> &, std::vector<int> &)
-    {
-        throw std::logic_error("TerrainExtractLod on a backend without device-resident terrain");
-    }
 };
+
+// The default backend and the owner of the vtmc context, defined in voxel_terrain.cpp so that this header stays free of the C ABI.
+class VtmcContext;
 
 class VoxelTerrain {
 public:
@@ -616,7 +564,9 @@ public:
 
 private:
     void ApplyMeshes(const std::vector<CSTriangle> &csTriangles, const std::vector<int> &offsets);  // VoxelTerrain.cs:430-465
-    void EnsureMaterialLayer();
+    // the one gate of everything device-resident: the context, or UnityException("<who> needs an initialised device-resident terrain")
+    VtmcContext &RequireResident(const char *who) const;
+    VtmcContext &EnsureMaterialLayer();
     bool _hasMaterialLayer = false;
     std::vector<uint8_t> _vertexMaterials;
     std::vector<LodNode> _lodNodes;
@@ -626,13 +576,14 @@ private:
     std::vector<MathHelper::Int3> _nextUpdateblocks, _lastUpdateBlocks;
     std::deque<std::shared_ptr<TerrainModifier>> _modifierQueue;
     std::shared_ptr<ExtractBackend> _backend;
+    std::shared_ptr<VtmcContext> _vtmc;  // _backend by its own type when it is the default one (set by Init), else null
     bool _initialised = false;
     int _lastTriNum = 0;
     std::mt19937 _rng{12345u};
     std::uniform_real_distribution<float> _uniform{0.0f, 1.0f};
 };
 
-// Default backend: the HIP library behind include/vtmc.h.
+// Default backend: the HIP library behind include/vtmc.h (a VtmcContext).
 std::shared_ptr<ExtractBackend> MakeVtmcBackend(int device);
 
 }  // namespace Render

@@ -12,6 +12,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "host", "_build", "host_selftest")
 
 
+# every mode of host_selftest that a test runs, and the token it prints when all went well
+OK_TOKEN = {"--cpu": "HOST-CPU-OK", "--gpu": "HOST-GPU-OK", "--gpu-resident": "HOST-RESIDENT-OK", "--gpu-lod": "HOST-LOD-OK",
+            "--gpu-nav": "HOST-NAV-OK", "--gpu-naverode": "HOST-NAVERODE-OK", "--gpu-navfield": "HOST-NAVFIELD-OK",
+            "--gpu-navsight": "HOST-NAVSIGHT-OK", "--gpu-navcrowd": "HOST-NAVCROWD-OK", "--gpu-water": "HOST-WATER-OK"}
+TIME_LIMIT = 120   # seconds: the worlds are 64 x 32 x 32 cells, a mode takes seconds
+
+
 def build_host():
     import volumetricterrain_amd as vt
     vt.load()   # libvtmc.so must exist to link against
@@ -19,17 +26,34 @@ def build_host():
     return EXE
 
 
-def test_host_logic_without_gpu():
+def run_host_mirror(mode, tmp_path=None):
+    """Builds the mirror, runs one mode of host_selftest (its dumps go to tmp_path) under the time limit, asserts status 0 and the mode's
+    token, and returns the CompletedProcess."""
     exe = build_host()
-    r = subprocess.run([exe, "--cpu"], capture_output=True, text=True)
-    assert r.returncode == 0 and "HOST-CPU-OK" in r.stdout, r.stderr
+    try:
+        r = subprocess.run([exe, mode] + ([] if tmp_path is None else [str(tmp_path)]), capture_output=True, text=True, timeout=TIME_LIMIT)
+    except subprocess.TimeoutExpired as e:
+        pytest.fail("host_selftest %s did not end within %d s (output so far: %r)" % (mode, TIME_LIMIT, (e.stdout or b"")[-400:]))
+    assert r.returncode == 0 and OK_TOKEN[mode] in r.stdout, (r.returncode, r.stdout[-600:], r.stderr[-600:])
+    return r
+
+
+def test_host_logic_without_gpu():
+    run_host_mirror("--cpu")
+
+
+def test_host_selftest_usage_names_every_mode():
+    """Without arguments: status 64 and a usage text that names every mode the tests run."""
+    exe = build_host()
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=TIME_LIMIT)
+    assert r.returncode == 64, (r.returncode, r.stderr)
+    named = r.stderr.split()
+    assert [mode for mode in OK_TOKEN if mode not in named] == [], r.stderr
 
 
 @pytest.mark.gpu
 def test_host_mirror_end_to_end(tmp_path, oracle_mod):
-    exe = build_host()
-    r = subprocess.run([exe, "--gpu", str(tmp_path)], capture_output=True, text=True)
-    assert r.returncode == 0 and "HOST-GPU-OK" in r.stdout, r.stdout + r.stderr
+    run_host_mirror("--gpu", tmp_path)
     W, E, H, scale = 64, 32, 64, np.float32(0.5)
     grid = np.fromfile(tmp_path / "grid.f32", np.float32).reshape(W + 2, E + 2, H + 2)   # C# float[,,]: z fastest
     blocks = np.fromfile(tmp_path / "blocks.i32", np.int32).reshape(-1, 3)
@@ -50,9 +74,7 @@ def test_host_mirror_device_resident(tmp_path, oracle_mod):
     """_deviceResident = true: Init / Update run on the GPU (vtmc_terrain_*); the grid read back
     equals the oracle's Update bit for bit, the meshes of the last Update match the oracle's
     extraction of that grid."""
-    exe = build_host()
-    r = subprocess.run([exe, "--gpu-resident", str(tmp_path)], capture_output=True, text=True)
-    assert r.returncode == 0 and "HOST-RESIDENT-OK" in r.stdout, r.stdout + r.stderr
+    run_host_mirror("--gpu-resident", tmp_path)
     W, E, H, scale, origin = 64, 32, 64, 0.5, (-3.0, 1.0, 2.0)
     ref = oracle_mod.Terrain(W, E, H, scale, origin, seed=4242)
     ref.update([oracle_mod.plane_modifier(6.3, (-100, -100), (100, 100)),

@@ -10,7 +10,6 @@ each comparison of the selection is exact in double and the node lists must be E
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -463,10 +462,8 @@ def test_gpu_errors(ex):
 @pytest.mark.gpu
 def test_gpu_host_mirror(tmp_path):
     """The C++ VoxelTerrain mirror's ExtractLod / LodNodes against the Python path on the same world (host/host_selftest.cpp --gpu-lod)."""
-    from test_host_mirror import build_host
-    exe = build_host()
-    r = subprocess.run([exe, "--gpu-lod", str(tmp_path)], capture_output=True, text=True)
-    assert r.returncode == 0 and "HOST-LOD-OK" in r.stdout, r.stdout + r.stderr
+    from test_host_mirror import run_host_mirror
+    r = run_host_mirror("--gpu-lod", tmp_path)
     nodes = np.fromfile(tmp_path / "lod_nodes.i32", np.int32).reshape(-1, 4)
     counts = np.fromfile(tmp_path / "lod_counts.i32", np.int32)
     with vt.Extractor(0) as ex:

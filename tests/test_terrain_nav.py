@@ -5,7 +5,6 @@ nav_twin.py for EQUALITY: spans as raw bytes, column_offsets as int32.  There is
 are placed with terrain_write_samples, so every bit is chosen.  The fields, boxes and helpers are nav_support.py's; the contract every
 layer's header keeps is tests/test_abi_layers.py's."""
 import ctypes
-import subprocess
 
 import numpy as np
 import pytest
@@ -381,10 +380,8 @@ def test_gpu_limits_and_device_pointers():
 @pytest.mark.gpu
 def test_gpu_host_mirror(tmp_path):
     """The C++ VoxelTerrain mirror's BuildNav against the Python path on the same world (host/host_selftest.cpp --gpu-nav)."""
-    from test_host_mirror import build_host
-    exe = build_host()
-    r = subprocess.run([exe, "--gpu-nav", str(tmp_path)], capture_output=True, text=True)
-    assert r.returncode == 0 and "HOST-NAV-OK" in r.stdout, r.stdout + r.stderr
+    from test_host_mirror import run_host_mirror
+    run_host_mirror("--gpu-nav", tmp_path)
     spans = np.fromfile(tmp_path / "nav_spans.bin", vt.NAV_SPAN_DTYPE)
     offsets, box = np.fromfile(tmp_path / "nav_offsets.i32", np.int32), np.fromfile(tmp_path / "nav_box.i32", np.int32)
     with vt.Extractor(0) as ex:

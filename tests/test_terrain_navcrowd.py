@@ -6,7 +6,6 @@ are nav_support.py's; fields of costs are navfield_twin.py's; the contract every
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -624,10 +623,8 @@ def test_gpu_device_results(crafted_ex):
 def test_gpu_host_mirror(tmp_path):
     """The C++ VoxelTerrain mirror's SpawnCrowd, StepCrowd and ReadCrowd against the Python path on the same world (host/host_selftest.cpp
     --gpu-navcrowd)."""
-    from test_host_mirror import build_host
-    exe = build_host()
-    r = subprocess.run([exe, "--gpu-navcrowd", str(tmp_path)], capture_output=True, text=True)
-    assert r.returncode == 0 and "HOST-NAVCROWD-OK" in r.stdout, r.stdout + r.stderr
+    from test_host_mirror import run_host_mirror
+    run_host_mirror("--gpu-navcrowd", tmp_path)
     files = {k: np.fromfile(tmp_path / ("navcrowd_%s.bin" % k), vt.NAVCROWD_AGENT_DTYPE) for k in ("spawned", "stepped", "rerouted")}
     occs = {k: np.fromfile(tmp_path / ("navcrowd_%s_occupancy.i32" % k), np.int32) for k in ("spawned", "stepped", "rerouted")}
     info = np.fromfile(tmp_path / "navcrowd_info.i32", np.int32).reshape(3, 5)

@@ -7,7 +7,6 @@ tests/test_abi_layers.py's."""
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -471,10 +470,8 @@ def test_gpu_device_pointers():
 def test_gpu_host_mirror(tmp_path):
     """The C++ VoxelTerrain mirror's NavDistance and ErodeNav against the Python path on the same world (host/host_selftest.cpp
     --gpu-naverode)."""
-    from test_host_mirror import build_host
-    exe = build_host()
-    r = subprocess.run([exe, "--gpu-naverode", str(tmp_path)], capture_output=True, text=True)
-    assert r.returncode == 0 and "HOST-NAVERODE-OK" in r.stdout, r.stdout + r.stderr
+    from test_host_mirror import run_host_mirror
+    run_host_mirror("--gpu-naverode", tmp_path)
     dist, origin = np.fromfile(tmp_path / "naverode_distance.i32", np.int32), np.fromfile(tmp_path / "naverode_origin.i32", np.int32)
     spans, offsets = np.fromfile(tmp_path / "naverode_spans.bin", vt.NAV_SPAN_DTYPE), np.fromfile(tmp_path / "naverode_offsets.i32", np.int32)
     with vt.Extractor(0) as ex:

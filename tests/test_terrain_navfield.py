@@ -7,7 +7,6 @@ worked out by hand.  Fields, boxes and helpers are nav_support.py's; the contrac
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -562,10 +561,8 @@ def test_gpu_nothing_else_moves():
 def test_gpu_host_mirror(tmp_path):
     """The C++ VoxelTerrain mirror's LocateOnNav, BuildNavField and TracePaths against the Python path on the same world
     (host/host_selftest.cpp --gpu-navfield)."""
-    from test_host_mirror import build_host
-    exe = build_host()
-    r = subprocess.run([exe, "--gpu-navfield", str(tmp_path)], capture_output=True, text=True)
-    assert r.returncode == 0 and "HOST-NAVFIELD-OK" in r.stdout, r.stdout + r.stderr
+    from test_host_mirror import run_host_mirror
+    run_host_mirror("--gpu-navfield", tmp_path)
     cells = np.fromfile(tmp_path / "navfield_cells.bin", vt.NAVFIELD_CELL_DTYPE)
     paths, lengths = np.fromfile(tmp_path / "navfield_paths.i32", np.int32), np.fromfile(tmp_path / "navfield_lengths.i32", np.int32)
     located = np.fromfile(tmp_path / "navfield_located.i32", np.int32)

@@ -6,7 +6,6 @@ nav_support.py's; fields of costs are navfield_twin.py's; the contract every lay
 import ctypes
 import functools
 import os
-import subprocess
 import time
 
 import numpy as np
@@ -578,10 +577,8 @@ def test_gpu_stage_clock():
 def test_gpu_host_mirror(tmp_path):
     """The C++ VoxelTerrain mirror's NavSight and SmoothPaths against the Python path on the same world (host/host_selftest.cpp
     --gpu-navsight)."""
-    from test_host_mirror import build_host
-    exe = build_host()
-    r = subprocess.run([exe, "--gpu-navsight", str(tmp_path)], capture_output=True, text=True)
-    assert r.returncode == 0 and "HOST-NAVSIGHT-OK" in r.stdout, r.stdout + r.stderr
+    from test_host_mirror import run_host_mirror
+    run_host_mirror("--gpu-navsight", tmp_path)
     hits = np.fromfile(tmp_path / "navsight_hits.bin", vt.NAVSIGHT_HIT_DTYPE)
     files = {k: np.fromfile(tmp_path / ("navsight_%s.i32" % k), np.int32) for k in ("bound_paths", "bound_lengths", "any_paths", "any_lengths")}
     with vt.Extractor(0) as ex:

@@ -3,7 +3,6 @@
 comparison here is for EQUALITY: records and volumes as raw bytes.  The crafted field, its boxes and its source sets are water_support.py's."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -399,10 +398,8 @@ def test_gpu_extraction_of_the_water_volume(crafted_ex, case, box):
 @pytest.mark.gpu
 def test_gpu_host_mirror(tmp_path):
     """The C++ VoxelTerrain mirror's Flood and ProbeWater against the Python path on the same world (host/host_selftest.cpp --gpu-water)."""
-    from test_host_mirror import build_host
-    exe = build_host()
-    r = subprocess.run([exe, "--gpu-water", str(tmp_path)], capture_output=True, text=True)
-    assert r.returncode == 0 and "HOST-WATER-OK" in r.stdout, r.stdout + r.stderr
+    from test_host_mirror import run_host_mirror
+    run_host_mirror("--gpu-water", tmp_path)
     import nav_support as nav
     with vt.Extractor(0) as ex:
         nav.mirror_world(ex)
