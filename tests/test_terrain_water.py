@@ -127,37 +127,20 @@ def test_twin_helpers():
 def test_twin_reproduces_the_table(case, box):
     source_body, bodies, wet, counts = TABLE[(case, box)]
     r = ws.twin_of(case, box)
-    assert r.source_body.tolist() == source_body and r.wet == wet and twin.volume_counts(r) == counts
-    got = [(float(b["level"]), int(b["n_samples"]), int(b["n_surface"]), tuple(b["lo"].tolist()), tuple(b["hi"].tolist()), int(b["flags"]), int(b["n_sources"])) for b in r.bodies]
-    assert got == bodies
+    assert ws.figures(r) == (source_body, bodies, wet, counts)
     assert r.vd == tuple(twin.volume_dim(d) for d in ws.BOXES[box][1]) and r.water.shape == r.body.shape == r.vd
     if len(r.bodies):
         assert r.water.max() <= 1 and r.water.min() == -1 and (r.water[r.body >= 0] >= 0).all()
 
 
 # -- GPU ------------------------------------------------------------------------------------------------------------------------------------
-def terrain(grid=None, dims=ws.DIMS):
-    ex = vt.Extractor(0)
-    ex.terrain_init(*dims, ws.SCALE, ws.ORIGIN, ws.SEED)
-    if grid is not None:
-        ex.terrain_write_samples(grid)
-    return ex
+terrain, device_volumes = ws.terrain, ws.device_volumes
 
 
 @pytest.fixture(scope="module")
 def crafted_ex():
     with terrain(ws.crafted_field()) as ex:
         yield ex
-
-
-def device_volumes(ex):
-    """The two volumes as they lie behind vtmc_water_device_results, indexed [x, y, z]."""
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    w, b, vd = ex.device_water()
-    water, body = np.empty(vd[::-1], f32), np.empty(vd[::-1], np.int32)
-    assert w and b and hip.hipMemcpy(water.ctypes.data, w, water.nbytes, 2) == 0 and hip.hipMemcpy(body.ctypes.data, b, body.nbytes, 2) == 0
-    return water.transpose(2, 1, 0), body.transpose(2, 1, 0)
 
 
 @pytest.mark.gpu
@@ -313,8 +296,7 @@ def random_case(seed):
     are long and cross many tiles --, and 32 sources on 8 levels on random open samples, a little off them."""
     rng = np.random.default_rng(seed)
     dims = (64, 16, 64)
-    shape = tuple(d + 2 for d in dims)
-    g = np.where(rng.random(shape) < 0.33, f32(-0.5), f32(0.5)).astype(f32)
+    g = ws.random_field(rng, dims)
     levels = ws.h(rng.choice(np.arange(2, 18), 8, replace=False)) + rng.choice([0.0, 0.25, 0.125], 8)
     open_samples = np.argwhere(~(g > 0))
     samples = open_samples[rng.choice(len(open_samples), 32, replace=False)]       # on open samples: above its level, a source is dry all the same
