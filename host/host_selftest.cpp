@@ -518,6 +518,34 @@ static int gpu_lod_run(const std::string &out)
     return 0;
 }
 
+// the seams of that mixed-level mesh covered: skirts at depth 1, then on every face, and what is refused
+static int gpu_lodskirt_run(const std::string &out)
+{
+    VoxelTerrain vt;
+    const int updateTriangles = resident_world(vt);
+    CHECK(Refused([&] { vt.LodSkirts(); }));   // no level-of-detail result yet
+    const int triNum = vt.ExtractLod(Vector3(-3.5f, 2.5f, 4.5f), 2, 1.0f);
+    const int skirts = vt.LodSkirts(1.0f);
+    std::printf("lodskirt: nodes %zu triangles %d skirt triangles %d\n", vt.LodNodes().size(), triNum, skirts);
+    CHECK(skirts > 0 && skirts % 2 == 0 && vt.LodSkirtMeshes().size() == vt.LodNodes().size());
+    std::vector<int> counts;
+    size_t vertices = 0;
+    for (size_t i = 0; i < vt.LodNodes().size(); i++) {
+        const BlockMesh &m = vt.LodSkirtMeshes()[i];
+        counts.push_back((int)m.vertices.size());
+        vertices += m.vertices.size();
+        const float cell = (float)(1 << vt.LodNodes()[i]._level) * vt._voxelScale, size = 8.0f * cell;   // a skirt leaves its node's box by its depth at the most
+        for (const Vector3 &v : m.vertices) CHECK(v.x >= -1.001f * cell && v.x <= size + 1.001f * cell && v.y >= -1.001f * cell && v.y <= size + 1.001f * cell && v.z >= -1.001f * cell && v.z <= size + 1.001f * cell);
+    }
+    Dump(out, "lodskirt_counts.i32", counts);
+    CHECK(vertices == (size_t)skirts * 3);
+    CHECK(Refused([&] { vt.LodSkirts(0.0f); }) && Refused([&] { vt.LodSkirts(9.0f); }) && vt.LodSkirtMeshes().size() == counts.size());
+    CHECK(vt.LodSkirts(1.0f, true) > skirts);
+    CHECK(vt.LastTriangleCount() == updateTriangles);
+    vt.Free();
+    return 0;
+}
+
 // flag, whether it takes an <out_dir>, the run, the token printed after a run that returned 0, and what the run does
 static const struct Mode {
     const char *flag;
@@ -535,6 +563,7 @@ static const struct Mode {
     {"--gpu-navsight", true, gpu_navsight_run, "HOST-NAVSIGHT-OK", "any-angle paths on that field; dumps the hits of a set of pairs and every span's smoothed path"},
     {"--gpu-navcrowd", true, gpu_navcrowd_run, "HOST-NAVCROWD-OK", "a crowd on that field; dumps agents, occupancy and counts after the spawn, 24 ticks and a re-route"},
     {"--gpu-water", true, gpu_water_run, "HOST-WATER-OK", "standing water on that terrain; dumps the bodies, both volumes and three probes of one flood"},
+    {"--gpu-lodskirt", true, gpu_lodskirt_run, "HOST-LODSKIRT-OK", "the seams of that mixed-level mesh covered by skirts; dumps the per-node vertex counts"},
 };
 
 int main(int argc, char **argv)

@@ -12,6 +12,7 @@
 #include "../include/vtmc_navsight.h"
 #include "../include/vtmc_navcrowd.h"
 #include "../include/vtmc_water.h"
+#include "../include/vtmc_lodskirt.h"
 
 namespace PGRTerrain {
 
@@ -486,7 +487,25 @@ int VoxelTerrain::ExtractLod(const Vector3 &viewer, int maxLevel, float split, i
     _lodMeshes.assign(_lodNodes.size(), BlockMesh());
     for (size_t i = 0; i < _lodNodes.size(); i++)  // a node's cell in world units is 2^level * _voxelScale
         FillMesh(_lodMeshes[i], csTriangles, offsets[i], offsets[i + 1], (float)(1 << _lodNodes[i]._level) * _voxelScale);
+    _lodSkirtMeshes.clear();  // they belonged to the result this one replaced
     return (int)csTriangles.size();
+}
+
+int VoxelTerrain::LodSkirts(float depth, bool allFaces)
+{
+    VtmcContext &c = RequireResident("LodSkirts");
+    const vtmc_lodskirt_params p = {depth, allFaces ? VTMC_LODSKIRT_ALL_FACES : 0u};
+    int64_t n = 0;
+    VTMC_CHECK(c, vtmc_lod_skirts(c.ctx, &p, &n));
+    int32_t nNodes = 0;
+    VTMC_CHECK(c, vtmc_lodskirt_info(c.ctx, &nNodes, nullptr, nullptr));
+    std::vector<CSTriangle> csTriangles((size_t)n);
+    std::vector<int> offsets((size_t)nNodes + 1, 0);
+    VTMC_CHECK(c, vtmc_lodskirt_read(c.ctx, reinterpret_cast<vtmc_triangle *>(csTriangles.data()), n, offsets.data()));
+    _lodSkirtMeshes.assign((size_t)nNodes, BlockMesh());
+    for (size_t i = 0; i < _lodSkirtMeshes.size() && i < _lodNodes.size(); i++)
+        FillMesh(_lodSkirtMeshes[i], csTriangles, offsets[i], offsets[i + 1], (float)(1 << _lodNodes[i]._level) * _voxelScale);
+    return (int)n;
 }
 
 // VoxelTerrain.cs:214-245
@@ -496,6 +515,7 @@ void VoxelTerrain::Free()
     _blocks.clear();
     _lodNodes.clear();
     _lodMeshes.clear();
+    _lodSkirtMeshes.clear();
     _backend.reset();
     _vtmc.reset();
     _initialised = false;

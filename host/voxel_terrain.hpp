@@ -495,6 +495,12 @@ public:
     int ExtractLod(const Vector3 &viewer, int maxLevel, float split = 2.0f, int maxNodes = 1 << 18);
     const std::vector<LodNode> &LodNodes() const { return _lodNodes; }      // the nodes of the last ExtractLod, in list order
     const std::vector<BlockMesh> &LodMeshes() const { return _lodMeshes; }  // one mesh per node
+    // New: the seams of the last ExtractLod covered (include/vtmc_lodskirt.h, where the rule is): a strip of triangles in the plane of every
+    // node face where the level changes (allFaces: every face with a node behind it), hung `depth` node cells from the node's boundary
+    // curve towards the solid side, built on the device from the result ExtractLod left.  Returns the number of skirt triangles; mesh i of
+    // LodSkirtMeshes belongs where LodMeshes()[i] does, scaled the same way, and is drawn beside it.  Any later extract drops the skirts.
+    int LodSkirts(float depth = 1.0f, bool allFaces = false);
+    const std::vector<BlockMesh> &LodSkirtMeshes() const { return _lodSkirtMeshes; }  // one mesh per node, most of them empty
 
     // New: what no longer hangs on anything (device-resident terrains).  Lists the fragments a DetachModifier with the same bounds and
     // maxSamples would remove now and changes nothing; captureMinSamples > 0 also captures every fragment of at least that many samples
@@ -570,7 +576,7 @@ private:
     bool _hasMaterialLayer = false;
     std::vector<uint8_t> _vertexMaterials;
     std::vector<LodNode> _lodNodes;
-    std::vector<BlockMesh> _lodMeshes;
+    std::vector<BlockMesh> _lodMeshes, _lodSkirtMeshes;
     std::vector<float> _voxelSamples;  // float[W+2, E+2, H+2], row-major, z fastest (VoxelTerrain.cs:145)
     std::vector<BlockMesh> _blocks;    // GameObject[,,] stand-in (VoxelTerrain.cs:61)
     std::vector<MathHelper::Int3> _nextUpdateblocks, _lastUpdateBlocks;

@@ -911,7 +911,9 @@ int32_t vtmc_scatter_device_results(vtmc_ctx *ctx, const vtmc_instance **d_insta
  *
  * SEAMS BETWEEN LEVELS ARE NOT STITCHED.  Where a level-L node meets a level-(L+1) node the two meshes are built from different samples
  * and can differ on the shared face by up to the coarse cell's interpolation error: cracks are possible there.  No skirts are added and
- * no sample is snapped.  The 2:1 property above is what a later transition pass needs.
+ * no sample is snapped.  The 2:1 property above is what a later transition pass needs.  That holds for this call's own result, which stays
+ * as it is; vtmc_lod_skirts (include/vtmc_lodskirt.h, an optional layer) covers the seams with skirt triangles built from this result on
+ * the device, to be drawn beside it.
  *
  * vtmc_terrain_extract_lod  works in both output modes and leaves its result for vtmc_read_triangles, vtmc_read_indexed_mesh,
  *   vtmc_read_cases, vtmc_device_results, vtmc_device_indexed_results and vtmc_last_counts (n_blocks = the number of nodes) exactly as any

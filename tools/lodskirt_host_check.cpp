@@ -1,0 +1,126 @@
+// lodskirt_host_check.cpp -- a stand-alone run of the host half of the level-of-detail skirts (csrc/terrain_lodskirt.h: the argument
+// checks, the face masks of a node list, the count bound and the sizes of the pass's buffers), for the host sanitizers:
+//   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -ffp-contract=off tools/lodskirt_host_check.cpp -o lodskirt_host_check && ./lodskirt_host_check
+// Without arguments it checks known answers and exits 0 when every one is the expected one.  With arguments it prints the masks of node
+// lists, for tests/test_terrain_lodskirt.py to compare with the twin; every list is
+//   W E H flags n  followed by n times  ox oy oz level
+// and is answered by a line "case <i> ok" and a line of n masks.
+#include "../volumetricterrain_amd/csrc/terrain_lodskirt.h"
+#include "../volumetricterrain_amd/csrc/scan_layout.h"
+#include <climits>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+
+using namespace vtmc;
+
+static int failures = 0;
+#define EXPECT(c) \
+    do { \
+        if (!(c)) { \
+            std::printf("line %d: %s\n", __LINE__, #c); \
+            ++failures; \
+        } \
+    } while (0)
+
+static vtmc_lodskirt_params params(float depth, uint32_t flags)
+{
+    vtmc_lodskirt_params p;
+    p.depth = depth, p.flags = flags;
+    return p;
+}
+
+static std::vector<uint8_t> masks_of(const std::vector<vtmc_lod_node> &nodes, const int32_t cells[3], uint32_t flags, int32_t *flagged = nullptr)
+{
+    std::vector<uint8_t> out(3, 0xff);   // whatever it held is replaced
+    const int32_t n = lodskirt_face_masks(nodes.data(), nodes.size(), cells, flags, out);
+    if (flagged) *flagged = n;
+    return out;
+}
+
+static int print_lists(int argc, char **argv)
+{
+    int at = 1, index = 0;
+    while (at < argc) {
+        if (argc - at < 5) return 2;
+        const int32_t cells[3] = {std::atoi(argv[at]), std::atoi(argv[at + 1]), std::atoi(argv[at + 2])};
+        const uint32_t flags = (uint32_t)std::strtoul(argv[at + 3], nullptr, 0);
+        const long n = std::atol(argv[at + 4]);
+        at += 5;
+        if (n < 0 || (long)(argc - at) < 4 * n) return 2;
+        std::vector<vtmc_lod_node> nodes((size_t)n);
+        for (long i = 0; i < n; ++i, at += 4) nodes[(size_t)i] = vtmc_lod_node{{std::atoi(argv[at]), std::atoi(argv[at + 1]), std::atoi(argv[at + 2])}, std::atoi(argv[at + 3])};
+        std::vector<uint8_t> masks;
+        lodskirt_face_masks(nodes.data(), nodes.size(), cells, flags, masks);
+        std::printf("case %d ok\n", index++);
+        for (uint8_t m : masks) std::printf("%d ", (int)m);
+        std::printf("\n");
+    }
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1) return print_lists(argc, argv);
+    const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
+
+    // the argument checks: every fault of include/vtmc_lodskirt.h
+    for (float good : {1.0f, 0.5f, 8.0f, 1e-30f, 1.17549435e-38f, 1e-45f}) EXPECT(lodskirt_params_fault(params(good, 0u)) == nullptr);
+    for (float bad : {0.0f, -0.0f, -1.0f, 9.0f, std::nextafter(8.0f, inf), 3e38f, inf, -inf, nan}) EXPECT(lodskirt_params_fault(params(bad, 0u)) != nullptr);
+    EXPECT(lodskirt_params_fault(params(1.0f, VTMC_LODSKIRT_ALL_FACES)) == nullptr);
+    for (uint32_t bad : {2u, 3u, 0x80000000u, 0xffffffffu}) EXPECT(lodskirt_params_fault(params(1.0f, bad)) != nullptr);
+
+    // the face masks.  Two roots of level 2 in 64 x 32 x 32 cells: neighbours of one level, so nothing without ALL_FACES and the shared
+    // face of each with it
+    const int32_t cells[3] = {64, 32, 32};
+    const std::vector<vtmc_lod_node> roots = {{{0, 0, 0}, 2}, {{32, 0, 0}, 2}};
+    int32_t flagged = -1;
+    std::vector<uint8_t> m = masks_of(roots, cells, 0u, &flagged);
+    EXPECT(m.size() == 2 && m[0] == 0 && m[1] == 0 && flagged == 0);
+    m = masks_of(roots, cells, VTMC_LODSKIRT_ALL_FACES, &flagged);
+    EXPECT(m.size() == 2 && m[0] == 2 && m[1] == 1 && flagged == 2);
+    // the near root split once: the far root is flagged towards it, its children at x = 16 towards the root, those at x = 0 not at all
+    std::vector<vtmc_lod_node> mixed;
+    for (int k = 0; k < 8; ++k) mixed.push_back(vtmc_lod_node{{16 * (k & 1), 16 * ((k >> 1) & 1), 16 * ((k >> 2) & 1)}, 1});
+    mixed.push_back(vtmc_lod_node{{32, 0, 0}, 2});
+    m = masks_of(mixed, cells, 0u, &flagged);
+    EXPECT(m.size() == 9 && flagged == 5 && m[8] == 1);
+    for (int k = 0; k < 8; ++k) EXPECT(m[(size_t)k] == ((k & 1) ? 2 : 0));
+    m = masks_of(mixed, cells, VTMC_LODSKIRT_ALL_FACES, &flagged);
+    EXPECT(flagged == 9 && m[8] == 1 && m[0] == (2 | 8 | 32) && m[7] == (1 | 2 | 4 | 16));
+    // a list that is not 2:1 -- a root beside level-0 nodes -- and one that does not tile: nothing is assumed of either
+    std::vector<vtmc_lod_node> steep = {{{32, 0, 0}, 2}, {{24, 0, 0}, 0}, {{24, 8, 0}, 0}, {{16, 0, 0}, 0}};
+    m = masks_of(steep, cells, 0u, &flagged);
+    EXPECT(m[0] == 1 && m[1] == (2 | 32) && m[2] == (1 | 2 | 8 | 32) && m[3] == (1 | 8 | 32) && flagged == 4);
+    // the same node twice, a level outside 0..VTMC_LOD_MAX_LEVEL, origins at the ends of int32: no mask, no overflow
+    std::vector<vtmc_lod_node> odd = {{{0, 0, 0}, 2}, {{0, 0, 0}, 2}, {{0, 0, 0}, -1}, {{0, 0, 0}, 8}, {{INT32_MAX, INT32_MAX, INT32_MAX}, 7}, {{INT32_MIN, 0, INT32_MIN}, 7}, {{32, 0, 0}, 2}};
+    m = masks_of(odd, cells, VTMC_LODSKIRT_ALL_FACES, &flagged);
+    EXPECT(m.size() == 7 && m[0] == 2 && m[1] == 2 && m[2] == 0 && m[3] == 0 && m[4] == 0 && m[5] == 0 && m[6] == 1 && flagged == 3);
+    const int32_t huge[3] = {INT32_MAX, INT32_MAX, INT32_MAX};
+    m = masks_of(odd, huge, 0u, &flagged);
+    EXPECT(m[4] == (1 | 4 | 16) && m[0] == (8 | 32));   // +x of the first root is the last one: not flagged; +y and +z hold no node
+    EXPECT(masks_of({}, cells, 0u, &flagged).empty() && flagged == 0);
+    // many nodes: every level-0 node of a 128^3 terrain, none flagged, all interior faces with ALL_FACES
+    std::vector<vtmc_lod_node> many;
+    for (int z = 0; z < 16; ++z)
+        for (int y = 0; y < 16; ++y)
+            for (int x = 0; x < 16; ++x) many.push_back(vtmc_lod_node{{8 * x, 8 * y, 8 * z}, 0});
+    const int32_t cube[3] = {128, 128, 128};
+    m = masks_of(many, cube, 0u, &flagged);
+    EXPECT(flagged == 0);
+    m = masks_of(many, cube, VTMC_LODSKIRT_ALL_FACES, &flagged);
+    EXPECT(flagged == 4096 && m[0] == (2 | 8 | 32) && m[4095] == (1 | 4 | 16) && m[1 + 16 + 256] == 63);
+
+    // the count bound and the sizes
+    EXPECT(lodskirt_tiles(0) == 0 && lodskirt_tiles(1) == 1 && lodskirt_tiles(256) == 1 && lodskirt_tiles(257) == 2 && lodskirt_tiles(INT32_MAX) == 8388608u);
+    EXPECT(lodskirt_mask_bytes(0) == 0 && lodskirt_mask_bytes(1) == 256 && lodskirt_mask_bytes(257) == 512 && lodskirt_mask_bytes(INT32_MAX) == 2147483648ull);
+    EXPECT(lodskirt_max_records(0) == 0 && lodskirt_max_records(INT32_MAX) == 12ll * INT32_MAX);
+    EXPECT(lodskirt_total_fits(0) && lodskirt_total_fits(0x7fffffffull) && !lodskirt_total_fits(0x80000000ull) && !lodskirt_total_fits((unsigned long long)lodskirt_max_records(INT32_MAX)));
+    EXPECT((uint64_t)kLodSkirtTile * kLodSkirtPerTriangle * kScanThreads < (1ull << 32));   // a scan group's total fits its 32 bits
+    EXPECT(lodskirt_tiles(INT32_MAX) <= (1u << 23));                                          // ... and the tiles fit the scan's two levels
+    EXPECT(ScanLayout(lodskirt_tiles(257)).bytes() == 8u + 8u * (2u + 1u) && ScanLayout(lodskirt_tiles(INT32_MAX)).bytes() == 8u + 8u * (8388608ull + 8192ull));
+
+    if (failures) std::printf("%d check(s) failed\n", failures);
+    else std::printf("lodskirt_host_check: ok\n");
+    return failures ? 1 : 0;
+}

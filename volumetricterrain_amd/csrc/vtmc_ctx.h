@@ -190,6 +190,19 @@ struct VtmcWater {
     std::vector<vtmc_water_body> bodies;
 };
 
+// The skirts over the seams of the level-of-detail result `epoch` names (terrain_lodskirt.hip): library-owned, grow-only, stale after the
+// next extract.  tris: the records; node_offsets: nodes + 1 entries; masks: one face-mask byte per triangle, whole tiles; tiles: the scan's
+// layout; node_masks: the face masks of the nodes as the kernels read them, face_masks the host's copy of those of the skirts held; sink:
+// what vtmc_debug_lodskirt_read_ms's kernel leaves.  staged: the emit kernel's store variant (vtmc_debug_lodskirt_store).
+struct VtmcLodSkirt {
+    VtmcDevBuf tris, node_offsets, masks, tiles, node_masks, sink;
+    std::vector<uint8_t> face_masks;
+    int64_t n = 0;
+    int32_t nodes = 0, flagged = 0;
+    uint64_t epoch = 0;
+    bool staged = false;
+};
+
 // An extract that has been queued on a stream and not yet completed by extract_finish().
 struct VtmcPending {
     bool active = false;    // queued, extract_finish() not yet called
@@ -303,6 +316,9 @@ struct vtmc_ctx {
     std::vector<vtmc_lod_node> lod_nodes;
     VtmcDevBuf lod_nodes_dev, lod_tiles;
     vtmc::StageClock<2> lod_clock;
+    // terrain_lodskirt.hip: the skirts of the last vtmc_lod_skirts and the clock of its kernels (armed by a call that launched them)
+    VtmcLodSkirt lodskirt;
+    vtmc::StageClock<6> lodskirt_clock;
     // raycast.hip, spherequery.hip: the queries and hits of vtmc_terrain_raycast / _spherecast / _closest_point (device, then their pinned staging)
     VtmcDevBuf rays;
     VtmcPinnedBuf<unsigned char> h_rays;

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, NAVCROWD_AGENT_DTYPE, NAVFIELD_CELL_DTYPE, NAVFIELD_GOAL_DTYPE, NAVSIGHT_HIT_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, WATER_BODY_DTYPE, WATER_SOURCE_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
-from .modifiers import AmbientOcclusion, LodParams, NavErodeParams, NavParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
+from .modifiers import AmbientOcclusion, LodParams, LodSkirtParams, NavErodeParams, NavParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
 
 
 def _ptr(a):
@@ -862,6 +862,42 @@ class Extractor:
             s = s[:, None]
         origin, scale = self._terrain_placement
         return np.asarray(origin, np.float64) + (o + p * s) * float(scale)
+
+    # -- level-of-detail seams: skirt triangles over the faces where the level changes (include/vtmc_lodskirt.h) --------
+    def lod_skirts(self, depth=1.0, all_faces=False):
+        """Builds the skirts of the level-of-detail result the context holds, on the device, by the rule LODSKIRT: `depth` in the node's
+        own cells, all_faces for every face with a node behind it.  `depth` may be a LodSkirtParams (or a vtmc_lodskirt_params struct)
+        instead.  Returns the number of skirt records; the extract's own result is unchanged.  Draw both."""
+        p = _struct(depth if hasattr(depth, "to_struct") or isinstance(depth, _lib.LodSkirtParamsStruct) else LodSkirtParams(depth, all_faces))
+        n = ctypes.c_int64()
+        self._check(self._L.vtmc_lod_skirts(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return n.value
+
+    def lodskirt_info(self):
+        """(nodes, nodes with a flagged face, skirt records) of the skirts the context holds."""
+        n, f, t = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        self._check(self._L.vtmc_lodskirt_info(self._h, ctypes.byref(n), ctypes.byref(f), ctypes.byref(t)))
+        return n.value, f.value, t.value
+
+    def lodskirt_masks(self):
+        """The face mask of every node (uint8; bit f: face f of -x, +x, -y, +y, -z, +z is flagged)."""
+        out = np.zeros(self.lodskirt_info()[0], np.uint8)
+        self._check(self._L.vtmc_lodskirt_masks(self._h, _ptr(out) if len(out) else None, len(out)))
+        return out
+
+    def lodskirt_read(self):
+        """(records, node_offsets): the skirt records as a TRI_DTYPE array (`block` the node's index, positions node-local: place them
+        with lod_world_positions) and the nodes + 1 offsets, so node i owns records[node_offsets[i]:node_offsets[i + 1]]."""
+        nodes, _, n = self.lodskirt_info()
+        out, offs = np.zeros(n, TRI_DTYPE), np.zeros(nodes + 1, np.int32)
+        self._check(self._L.vtmc_lodskirt_read(self._h, _ptr(out) if n else None, n, _ptr(offs)))
+        return out, offs
+
+    def device_lodskirts(self):
+        """(device address of the skirt records, device address of the nodes + 1 offsets, the number of records) of the last lod_skirts."""
+        p, o, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        self._check(self._L.vtmc_lodskirt_device_results(self._h, ctypes.byref(p), ctypes.byref(o), ctypes.byref(n)))
+        return p.value, o.value, n.value
 
     # -- ray picking: Physics.Raycast of the interactive edit (SceneManager.cs:114-131) on the device ---------------
     def terrain_raycast(self, origins, directions, max_distance=float("inf"), two_sided=False):

@@ -306,6 +306,24 @@ class LodParams:
         return s
 
 
+class LodSkirtParams:
+    """The parameters of Extractor.lod_skirts (vtmc_lodskirt_params): `depth`, how far a skirt hangs from the boundary curve of its node, in
+    the node's own cells (finite, > 0, at most LODSKIRT_MAX_DEPTH); all_faces: skirts on every face with a node behind it, not only on
+    faces where the level changes."""
+
+    def __init__(self, depth=1.0, all_faces=False):
+        with np.errstate(over="ignore"):
+            self._depth = _f(depth)
+        if not np.isfinite(self._depth) or not 0 < self._depth <= _lib.LODSKIRT_MAX_DEPTH:
+            raise ValueError("skirt depth must be finite, > 0 and at most %d" % _lib.LODSKIRT_MAX_DEPTH)
+        self._flags = _lib.LODSKIRT_ALL_FACES if all_faces else 0
+
+    def to_struct(self):
+        s = _lib.LodSkirtParamsStruct()
+        s.depth, s.flags = float(self._depth), self._flags
+        return s
+
+
 # -- noise (include/vtmc.h VTMC_MOD_NOISE) -----------------------------------------------------------------------------------------------
 NOISE_BASES = {"fbm": 0, "billow": 1, "ridged": 2}
 
