@@ -19,6 +19,7 @@ from volumetricterrain_amd import _lib
 import lod_twin as twin
 from host_check import run_host_check
 from extract_checks import FLOATS, assert_tris_match
+from lod_support import bits, lod_tiles, oracle_indexed_soup
 from terrain_twin import assert_triangles, no_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -198,16 +199,6 @@ def lod_params(viewer_world, max_level=MAX_LEVEL, split=2.0, max_nodes=1 << 18):
     return _lib.LodParams(tuple(float(v) for v in viewer_world), float(split), int(max_level), int(max_nodes))
 
 
-def lod_tiles(ex, n_nodes):
-    out = np.zeros((n_nodes, 1000), f32)
-    assert ex._L.vtmc_debug_lod_tiles(ex._h, out.ctypes.data, out.size) == _lib.OK
-    return out
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 @pytest.fixture(scope="module")
 def world():
     """The terrain, built once per output mode from the same seed and queue: the context (left in soup mode), its grid, and the
@@ -277,16 +268,6 @@ def test_gpu_level_0_is_the_ordinary_extract(ex, world):
     for i, b in enumerate(block):
         assert gv[gvo[i]:gvo[i + 1]].tobytes() == fv[fvo[b]:fvo[b + 1]].tobytes(), (i, b)
         assert np.array_equal(gi[gto[i]:gto[i + 1]], fi[fto[b]:fto[b + 1]]), (i, b)
-
-
-def oracle_indexed_soup(oracle_mod, tiles):
-    """The oracle's welded mesh of every tile (a tile is a grid of one block), de-indexed into records in list order."""
-    out = []
-    for n, t in enumerate(tiles):
-        soup = oracle_mod.deindex(*oracle_mod.extract_grid_indexed(np.ascontiguousarray(t.reshape(10, 10, 10).transpose(2, 1, 0))))
-        soup["block"] = n
-        out.append(soup)
-    return np.concatenate(out)
 
 
 @pytest.fixture(scope="module")

@@ -20,6 +20,8 @@ from volumetricterrain_amd import _lib
 import lod_twin
 import lodskirt_twin as twin
 from host_check import run_host_check
+from lod_support import (assert_skirts_match_the_twin, bits, brute_masks, check_closure, check_skirt_properties, device_records, interior_masks,
+                         poison_skirts)
 from terrain_twin import no_result
 from test_terrain_lod import CASES, DIMS, MAX_LEVEL, ORIGIN, SCALE, SEED, VIEWERS, select, world_of
 
@@ -34,37 +36,6 @@ def scene_samples():
     h = 14.0 + 5.0 * np.sin(0.23 * x) * np.cos(0.31 * z) + 3.0 * np.sin(0.11 * x + 0.4 * z)
     ball = np.sqrt((x - 20.0) ** 2 + (y - 10.0) ** 2 + (z - 16.0) ** 2) - 6.0
     return np.minimum(h - y, ball).astype(f32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def brute_masks(nodes, all_faces=False):
-    """Flagged, restated over the level of every 8^3-cell block: the same-size box beyond a face lies inside the terrain and (unless
-    all_faces) is not one node of the node's own level -- a box aligned to its size whose blocks all have level L is a node of level L."""
-    lv = lod_twin.level_map(DIMS, nodes)
-    out = np.zeros(len(nodes), np.uint8)
-    for i, (ox, oy, oz, level) in enumerate(np.asarray(nodes, np.int64).tolist()):
-        n = 8 << level
-        for f in range(6):
-            lo = [ox, oy, oz]
-            lo[f >> 1] += n if f & 1 else -n
-            if lo[f >> 1] < 0 or lo[f >> 1] + n > DIMS[f >> 1]:
-                continue
-            box = lv[tuple(slice(lo[k] // 8, (lo[k] + n) // 8) for k in range(3))]
-            if all_faces or not (box == level).all():
-                out[i] |= 1 << f
-    return out
-
-
-def interior_masks(nodes):
-    nodes = np.asarray(nodes, np.int64)
-    out = np.zeros(len(nodes), np.uint8)
-    for k in range(3):
-        size = 8 << nodes[:, 3]
-        out |= ((nodes[:, k] > 0).astype(np.uint8) << (2 * k)) | ((nodes[:, k] + size < DIMS[k]).astype(np.uint8) << (2 * k + 1))
-    return out
 
 
 # -- CPU: the interface -----------------------------------------------------------------------------------------------------------------
@@ -111,8 +82,8 @@ def test_null_pointers_are_errors_not_crashes():
 def test_twin_masks_equal_the_brute_force(name, split):
     nodes = select(name, split)
     for all_faces in (False, True):
-        assert np.array_equal(twin.face_masks(DIMS, nodes, all_faces), brute_masks(nodes, all_faces)), (name, split, all_faces)
-    assert np.array_equal(twin.face_masks(DIMS, nodes, True), interior_masks(nodes))          # ALL_FACES: exactly the interior faces
+        assert np.array_equal(twin.face_masks(DIMS, nodes, all_faces), brute_masks(DIMS, nodes, all_faces)), (name, split, all_faces)
+    assert np.array_equal(twin.face_masks(DIMS, nodes, True), interior_masks(DIMS, nodes))    # ALL_FACES: exactly the interior faces
 
 
 def test_twin_known_masks():
@@ -120,7 +91,7 @@ def test_twin_known_masks():
         if name != "far":
             nodes = select(name, 1024.0)                                                         # every node level 0: no face is flagged
             assert (nodes[:, 3] == 0).all() and not twin.face_masks(DIMS, nodes).any()
-            assert np.array_equal(twin.face_masks(DIMS, nodes, True), interior_masks(nodes))
+            assert np.array_equal(twin.face_masks(DIMS, nodes, True), interior_masks(DIMS, nodes))
     roots = select("far", 1.0)                                                                   # two roots: nothing, and their shared face
     assert twin.face_masks(DIMS, roots).tolist() == [0, 0] and twin.face_masks(DIMS, roots, True).tolist() == [2, 1]
     nodes = select("corner", 1.0)
@@ -142,36 +113,6 @@ def scene(oracle_mod):
     return dict(S=S, nodes=nodes, records=records, offs=offs, masks=masks, skirt=skirt, node_offsets=node_offsets, faces=faces)
 
 
-def check_skirt_properties(skirt, faces, depth):
-    """The properties of a skirt list, of the twin or of the device; returns (quads, quads with a source edge, second triangles inwards)."""
-    assert len(skirt) == 2 * len(faces) and len(faces) > 50
-    first, second = skirt[0::2], skirt[1::2]
-    axis = faces >> 1
-    want = np.where(faces & 1, twin.EIGHT, twin.ZERO).astype(np.uint32)
-    rows = np.arange(len(faces))
-    for rec in (first, second):
-        for k in ("p0", "p1", "p2"):
-            assert np.array_equal(bits(rec[k].astype(f32))[rows, axis], want), k                 # the face-axis coordinate is bitwise 0 or 8
-    assert np.array_equal(twin.quad_faces(skirt), faces)
-    # every displaced vertex lies `depth` from its source within 1e-5, or on it
-    for moved, source in ((first["p2"], first["p1"]), (second["p2"], second["p0"])):
-        d = np.sqrt(((moved.astype(np.float64) - source.astype(np.float64)) ** 2).sum(axis=1))
-        assert ((np.abs(d - depth) <= 1e-5) | (d == 0)).all(), np.abs(d - depth)[d != 0].max()
-    assert first["p2"].tobytes() == second["p1"].tobytes()                                       # a' is one vertex
-    # orientation: (b, a, a') faces out of the node through the face wherever the source edge has a length
-    outward = np.where(faces & 1, 1.0, -1.0)
-
-    def normal_out(rec):
-        p0, p1, p2 = (rec[k].astype(np.float64) for k in ("p0", "p1", "p2"))
-        return np.cross(p1 - p0, p2 - p0)[rows, axis] * outward
-
-    with_edge = (first["p0"] != first["p1"]).any(axis=1)
-    assert (normal_out(first)[with_edge] > 0).all()
-    inwards = int((normal_out(second)[with_edge] <= 0).sum())
-    assert inwards <= 0.10 * with_edge.sum(), (inwards, int(with_edge.sum()))                  # a cap, not a measurement
-    return len(faces), int(with_edge.sum()), inwards
-
-
 def test_twin_properties(scene):
     skirt, faces, records = scene["skirt"], scene["faces"], scene["records"]
     quads, with_edge, inwards = check_skirt_properties(skirt, faces, DEPTH)
@@ -191,17 +132,6 @@ def test_twin_properties(scene):
     assert np.array_equal(twin.displace(P, np.array([[np.nan, np.nan, np.nan]], f32), 0, 1.0), P)
     assert np.array_equal(twin.displace(P, np.array([[0.0, 3e38, 3e38]], f32), 0, 1.0), P)       # l2 overflows
     assert np.array_equal(twin.displace(P, np.array([[9.0, 0.0, -2.0]], f32), 0, 1.5), np.array([[0.0, 3.0, 5.5]], f32))
-
-
-def check_closure(nodes, records, masks, skirt, depth):
-    walk = twin.closure_walk(nodes, records, masks, skirt, depth)
-    print("closure at depth %g: %s" % (depth, walk))
-    assert walk["fine_points"] > 200 and walk["points"] > 1000
-    assert walk["skipped"] <= 0.05 * walk["fine_points"], walk                                  # a cap
-    assert walk["uncovered"] == 0, walk
-    empty = twin.closure_walk(nodes, records, masks, skirt[:0], depth)
-    assert empty["points"] == walk["points"] and empty["uncovered"] > 0.2 * empty["points"], empty   # the walk can fail
-    return walk
 
 
 def test_twin_skirts_close_the_seams(scene):
@@ -246,38 +176,6 @@ def ex(world):
     assert e._L.vtmc_debug_lodskirt_store(e._h, 0) == _lib.OK
 
 
-def device_records(ex, oracle_mod, indexed):
-    """The records of the result the context holds (indexed: de-indexed in order)."""
-    if not indexed:
-        return ex.read_triangles()[0]
-    return oracle_mod.deindex(*ex.read_indexed_mesh())
-
-
-def assert_skirts_match_the_twin(ex, oracle_mod, nodes, indexed, depth, all_faces=False):
-    """lod_skirts on the result the context holds against the twin fed with the device's own records.  Returns (records, device skirts,
-    masks, the number of displaced components whose bits differ from the twin's)."""
-    records = device_records(ex, oracle_mod, indexed)
-    masks = twin.face_masks(DIMS, nodes, all_faces)
-    want, want_offsets, faces = twin.skirts(records, masks, depth)
-    n = ex.lod_skirts(depth, all_faces)
-    assert n == len(want) and ex.lodskirt_info() == (len(nodes), int((masks != 0).sum()), n)
-    assert np.array_equal(ex.lodskirt_masks(), masks)
-    got, offsets = ex.lodskirt_read()
-    assert offsets.dtype == np.int32 and np.array_equal(offsets, want_offsets) and np.array_equal(got["block"], want["block"])
-    for k in ("n0", "n1", "n2"):
-        assert np.array_equal(bits(got[k]), bits(want[k])), k                                    # all normals: bitwise
-    first, second = (got[0::2], want[0::2]), (got[1::2], want[1::2])
-    for (g, w), k in ((first, "p0"), (first, "p1"), (second, "p0")):
-        assert np.array_equal(bits(g[k]), bits(w[k])), k                                         # the copied positions: bitwise
-    differ = 0
-    for (g, w), k in ((first, "p2"), (second, "p1"), (second, "p2")):
-        assert np.array_equal(np.isnan(g[k]), np.isnan(w[k])) and np.allclose(g[k], w[k], rtol=0.0, atol=1e-5, equal_nan=True), k
-        differ += int((bits(g[k]) != bits(w[k])).sum())
-        rows = np.arange(len(faces))
-        assert np.array_equal(bits(g[k])[rows, faces >> 1], bits(w[k])[rows, faces >> 1])       # the face-axis component is copied
-    return records, got, masks, differ
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("indexed", [False, True], ids=["soup", "indexed"])
 @pytest.mark.parametrize("exact", [False, True], ids=["fast_math", "exact"])
@@ -288,7 +186,7 @@ def test_gpu_skirts_equal_the_twin(ex, oracle_mod, indexed, exact):
     n_nodes, T = ex.terrain_extract_lod(world_of(VIEWERS["corner"]), MAX_LEVEL, 1.0)
     assert n_nodes == len(nodes) and np.array_equal(ex.terrain_lod_nodes(), nodes) and T > 1000
     before = ex.read_indexed_mesh() if indexed else ex.read_triangles()
-    records, got, masks, differ = assert_skirts_match_the_twin(ex, oracle_mod, nodes, indexed, DEPTH)
+    records, got, masks, differ = assert_skirts_match_the_twin(ex, oracle_mod, DIMS, nodes, indexed, DEPTH)
     print("%s, %s: %d triangles, %d skirt records, displaced components whose bits differ from the twin's: %d"
           % ("indexed" if indexed else "soup", "exact" if exact else "fast math", T, len(got), differ))
     quads, with_edge, inwards = check_skirt_properties(got, twin.quad_faces(got), DEPTH)
@@ -298,6 +196,7 @@ def test_gpu_skirts_equal_the_twin(ex, oracle_mod, indexed, exact):
     assert all(a.tobytes() == b.tobytes() for a, b in zip(before, after)) and ex.last_counts() == (n_nodes, T)
     # the staged store variant writes the same bytes and the same offsets
     direct_offsets = ex.lodskirt_read()[1]
+    poison_skirts(ex)                                                    # the staged pass must write every byte, not find them there
     assert ex._L.vtmc_debug_lodskirt_store(ex._h, 1) == _lib.OK
     assert ex.lod_skirts(DEPTH) == len(got)
     staged, staged_offsets = ex.lodskirt_read()
@@ -310,7 +209,7 @@ def test_gpu_skirts_equal_the_twin(ex, oracle_mod, indexed, exact):
 def test_gpu_viewers_and_splits(ex, oracle_mod, name, split):
     nodes = select(name, split)
     ex.terrain_extract_lod(world_of(VIEWERS[name]), MAX_LEVEL, split)
-    _, got, masks, _ = assert_skirts_match_the_twin(ex, oracle_mod, nodes, False, 0.75)
+    _, got, masks, _ = assert_skirts_match_the_twin(ex, oracle_mod, DIMS, nodes, False, 0.75)
     assert (len(got) > 0) == bool(masks.any()) == bool((nodes[:, 3] > 0).any())                # on_a_face at split 2 is all level 0: no skirts
     # a flagged node without a triangle is handled: its range of the offsets is empty
     offs = ex.read_triangles()[1]
@@ -323,8 +222,8 @@ def test_gpu_viewers_and_splits(ex, oracle_mod, name, split):
 def test_gpu_all_faces_and_flagged_nodes_without_triangles(ex, oracle_mod):
     nodes = select("inside", 2.0)
     ex.terrain_extract_lod(world_of(VIEWERS["inside"]), MAX_LEVEL, 2.0)
-    _, plain, masks, _ = assert_skirts_match_the_twin(ex, oracle_mod, nodes, False, DEPTH)
-    _, every, all_masks, _ = assert_skirts_match_the_twin(ex, oracle_mod, nodes, False, DEPTH, all_faces=True)
+    _, plain, masks, _ = assert_skirts_match_the_twin(ex, oracle_mod, DIMS, nodes, False, DEPTH)
+    _, every, all_masks, _ = assert_skirts_match_the_twin(ex, oracle_mod, DIMS, nodes, False, DEPTH, all_faces=True)
     assert len(every) > len(plain) and (all_masks & masks == masks).all() and (all_masks != 0).all()
     offs = ex.read_triangles()[1]
     assert ((all_masks != 0) & (np.diff(offs) == 0)).any()                                       # some flagged node has no triangles
@@ -332,7 +231,7 @@ def test_gpu_all_faces_and_flagged_nodes_without_triangles(ex, oracle_mod):
     ex.set_output_mode(True)
     ex.terrain_extract_lod(world_of(VIEWERS["inside"]), MAX_LEVEL, 2.0)
     assert ex._L.vtmc_debug_lodskirt_store(ex._h, 1) == _lib.OK
-    assert_skirts_match_the_twin(ex, oracle_mod, nodes, True, DEPTH, all_faces=True)
+    assert_skirts_match_the_twin(ex, oracle_mod, DIMS, nodes, True, DEPTH, all_faces=True)
 
 
 @pytest.mark.gpu
