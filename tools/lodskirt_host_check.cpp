@@ -112,13 +112,13 @@ int main(int argc, char **argv)
     EXPECT(flagged == 4096 && m[0] == (2 | 8 | 32) && m[4095] == (1 | 4 | 16) && m[1 + 16 + 256] == 63);
 
     // the count bound and the sizes
-    EXPECT(lodskirt_tiles(0) == 0 && lodskirt_tiles(1) == 1 && lodskirt_tiles(256) == 1 && lodskirt_tiles(257) == 2 && lodskirt_tiles(INT32_MAX) == 8388608u);
-    EXPECT(lodskirt_mask_bytes(0) == 0 && lodskirt_mask_bytes(1) == 256 && lodskirt_mask_bytes(257) == 512 && lodskirt_mask_bytes(INT32_MAX) == 2147483648ull);
+    EXPECT(tri_tiles(0) == 0 && tri_tiles(1) == 1 && tri_tiles(256) == 1 && tri_tiles(257) == 2 && tri_tiles(INT32_MAX) == 8388608u);
+    EXPECT(tri_mask_bytes(0) == 0 && tri_mask_bytes(1) == 256 && tri_mask_bytes(257) == 512 && tri_mask_bytes(INT32_MAX) == 2147483648ull);
     EXPECT(lodskirt_max_records(0) == 0 && lodskirt_max_records(INT32_MAX) == 12ll * INT32_MAX);
     EXPECT(lodskirt_total_fits(0) && lodskirt_total_fits(0x7fffffffull) && !lodskirt_total_fits(0x80000000ull) && !lodskirt_total_fits((unsigned long long)lodskirt_max_records(INT32_MAX)));
-    EXPECT((uint64_t)kLodSkirtTile * kLodSkirtPerTriangle * kScanThreads < (1ull << 32));   // a scan group's total fits its 32 bits
-    EXPECT(lodskirt_tiles(INT32_MAX) <= (1u << 23));                                          // ... and the tiles fit the scan's two levels
-    EXPECT(ScanLayout(lodskirt_tiles(257)).bytes() == 8u + 8u * (2u + 1u) && ScanLayout(lodskirt_tiles(INT32_MAX)).bytes() == 8u + 8u * (8388608ull + 8192ull));
+    EXPECT((uint64_t)kTriTile * kLodSkirtPerTriangle * kScanThreads < (1ull << 32));   // a scan group's total fits its 32 bits
+    EXPECT(tri_tiles(INT32_MAX) <= (1u << 23));                                          // ... and the tiles fit the scan's two levels
+    EXPECT(ScanLayout(tri_tiles(257)).bytes() == 8u + 8u * (2u + 1u) && ScanLayout(tri_tiles(INT32_MAX)).bytes() == 8u + 8u * (8388608ull + 8192ull));
 
     if (failures) std::printf("%d check(s) failed\n", failures);
     else std::printf("lodskirt_host_check: ok\n");

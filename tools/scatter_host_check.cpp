@@ -38,7 +38,7 @@ int main()
     const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
     static_assert(sizeof(vtmc_scatter_params) == 36 && sizeof(vtmc_instance) == 32, "the structs of include/vtmc.h");
     static_assert(VTMC_SCATTER_MAX_PER_TRIANGLE == 8, "one mask byte per triangle");
-    static_assert(kScatterTile % 4 == 0, "a tile's mask bytes are whole dwords");
+    static_assert(kTriTile % 4 == 0, "a tile's mask bytes are whole dwords");
 
     // the checks: every fault of include/vtmc.h
     EXPECT(scatter_params_fault(params(1.0f), 1.0f) == nullptr);
@@ -104,13 +104,13 @@ int main()
     // dc and the tiles
     EXPECT(scatter_density_cells(2.0f, 0.5f) == 0.5f && scatter_density_cells(3.5f, 1.0f) == 3.5f);
     EXPECT(scatter_density_cells(0.1f, 0.3f) == 0.1f * (0.3f * 0.3f));
-    EXPECT(scatter_tiles(0) == 0u && scatter_tiles(1) == 1u && scatter_tiles(256) == 1u && scatter_tiles(257) == 2u);
-    EXPECT(scatter_tiles(2147483647ll) == 8388608u);
-    EXPECT(scatter_mask_bytes(0) == 0u && scatter_mask_bytes(10112) == 10240u && scatter_mask_bytes(2147483647ll) == 2147483648ull);
+    EXPECT(tri_tiles(0) == 0u && tri_tiles(1) == 1u && tri_tiles(256) == 1u && tri_tiles(257) == 2u);
+    EXPECT(tri_tiles(2147483647ll) == 8388608u);
+    EXPECT(tri_mask_bytes(0) == 0u && tri_mask_bytes(10112) == 10240u && tri_mask_bytes(2147483647ll) == 2147483648ull);
 
     // the buffer of the scan over the tiles' totals: 8 bytes of total, then 4 bytes per tile and per group of 1024 tiles, twice
     const struct { uint64_t tiles, groups; size_t bytes; } layouts[] = {{0, 0, 8}, {1, 1, 24}, {1024, 1, 8208}, {1025, 2, 8224}, {67 * 23, 2, 8u + 8u * (67 * 23 + 2)},
-                                                                      {scatter_tiles(2147483647ll), 8192, 67174408}};   // 2^23 tiles: the most a result holds
+                                                                      {tri_tiles(2147483647ll), 8192, 67174408}};   // 2^23 tiles: the most a result holds
     for (const auto &want : layouts) {
         const ScanLayout l(want.tiles);
         EXPECT(l.groups() == want.groups && l.bytes() == want.bytes && l.total() == nullptr);

@@ -1,6 +1,8 @@
-// material_filter.h -- the material layer's trilinear filter and the block mapping of a terrain result, shared by the passes that read the
-// layer at points of the surface: the vertex weights (terrain_material.hip) and the material filter of the scatter (terrain_scatter.hip).
-// One piece of code, so both follow the rule of include/vtmc.h (vtmc_material_vertices) operation by operation.  Device code only.
+// material_filter.h -- the material layer's trilinear filter, shared by the passes that read the layer at points of the surface (the vertex
+// weights, terrain_material.hip, and the material filter of the scatter, terrain_scatter.hip: one piece of code, so both follow the rule
+// of include/vtmc.h, vtmc_material_vertices, operation by operation), and the block mapping of a result: BlockMap, which block_map() fills
+// from the result's BlockSpace for every pass that turns a block index into (bx, by, bz) (those two and terrain_ao.hip), and the search
+// of a block in the per-block offsets (material_block_of: terrain_material.hip and tri_stream_kernels.h).  Device code but for block_map().
 #ifndef VTMC_MATERIAL_FILTER_H
 #define VTMC_MATERIAL_FILTER_H
 #include "vtmc_internal.h"
@@ -8,18 +10,26 @@
 
 namespace vtmc {
 
-struct MaterialVertexArgs {
-    const uint2 *layer;  // C^3 texels, x fastest
-    int C;
-    float s[3];       // texels per cell, per axis
+// how the blocks of a result map to (bx, by, bz)
+struct BlockMap {
     const int *list;  // device (bx, by, bz) triples of the dirty list, or null: every block, b = bx + nbx * (by + nby * bz)
     uint32_t n_blocks;
     int nbx, nby;
     FastDiv d_nbx, d_nby;
 };
 
+// the mapping of a result of `blocks` blocks over `sp`
+inline BlockMap block_map(const BlockSpace &sp, int blocks) { return BlockMap{sp.list, (uint32_t)blocks, sp.nbx, sp.nby, sp.d_nbx, sp.d_nby}; }
+
+struct MaterialVertexArgs {
+    const uint2 *layer;  // C^3 texels, x fastest
+    int C;
+    float s[3];       // texels per cell, per axis
+    BlockMap map;
+};
+
 // (bx, by, bz) of block b, an index into the dirty list
-__device__ __forceinline__ void material_block(const MaterialVertexArgs &a, uint32_t b, int &bx, int &by, int &bz)
+__device__ __forceinline__ void material_block(const BlockMap &a, uint32_t b, int &bx, int &by, int &bz)
 {
     if (b >= a.n_blocks) b = a.n_blocks - 1;  // never taken for a result of the library; keeps a foreign record inside the list
     if (a.list) {
@@ -102,7 +112,7 @@ __device__ __forceinline__ uint32_t material_filter_channel(const MaterialTaps &
 __device__ __forceinline__ uint2 material_weights(const MaterialVertexArgs &a, uint32_t b, float p0, float p1, float p2)
 {
     int bx, by, bz;
-    material_block(a, b, bx, by, bz);
+    material_block(a.map, b, bx, by, bz);
     const MaterialTaps t = material_taps(a, bx, by, bz, p0, p1, p2);
     uint32_t out[2] = {0u, 0u};
 #pragma unroll

@@ -1,9 +1,10 @@
-// scan_kernels.h -- the two-level exclusive scan of up to 2^23 uint32 totals that the counting passes share (terrain_scatter.hip: the
-// survivors of a tile of triangles; terrain_nav.hip: the spans of a column).  scan_tiles_kernel gives every tile its prefix inside its group
-// of kScanThreads tiles and every group its total; scan_groups_kernel, one workgroup, scans the group totals and leaves the grand total
-// in 64 bits.  A tile's offset is the sum of the two prefixes.  (One workgroup over all the tile totals took 0.19 ms of the scatter pass's
-// 0.88 at 1024^3: profiles/r19/scatter.)  The kernels are static: every translation unit that includes this launches its own copy.
-// The buffer they work in is a ScanLayout (scan_layout.h, which the host halves read too); launch_scan queues the pair over one.
+// scan_kernels.h -- the two-level exclusive scan of up to 2^23 uint32 totals that the counting passes share (tri_stream_kernels.h: the
+// records of a tile of triangles, for the scatter and the skirts; terrain_nav.hip and terrain_naverode.hip: the spans of a column).
+// scan_tiles_kernel gives every tile its prefix inside its group of kScanThreads tiles and every group its total; scan_groups_kernel,
+// one workgroup, scans the group totals and leaves the grand total in 64 bits.  A tile's offset is the sum of the two prefixes.  (One
+// workgroup over all the tile totals took 0.19 ms of the scatter pass's 0.88 at 1024^3: profiles/r19/scatter.)  The kernels are static:
+// every translation unit that includes this launches its own copy.  The buffer they work in is a ScanLayout (scan_layout.h, which the
+// host halves read too); launch_scan queues the pair over one.
 #ifndef VTMC_SCAN_KERNELS_H
 #define VTMC_SCAN_KERNELS_H
 #include "scan_layout.h"

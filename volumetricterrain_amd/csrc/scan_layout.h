@@ -1,7 +1,7 @@
 // scan_layout.h -- the buffer the two-level scan of scan_kernels.h works in, for n_tiles uint32 totals: the grand total (64 bits), the tile
 // totals, their prefixes inside a group of kScanThreads tiles, the group totals and their prefixes.  Plain C++ with no HIP header, so the
-// host halves that size the buffer (terrain_nav.h) and the stand-alone host checks (tools/nav_host_check.cpp, tools/scatter_host_check.cpp)
-// read the one layout the launches use.  Every size is 64-bit arithmetic.
+// host halves that size the buffer (terrain_nav.h) and the stand-alone host checks (tools/nav_host_check.cpp, tools/scatter_host_check.cpp,
+// tools/lodskirt_host_check.cpp) read the one layout the launches use.  Every size is 64-bit arithmetic.
 #ifndef VTMC_SCAN_LAYOUT_H
 #define VTMC_SCAN_LAYOUT_H
 #include <cstddef>

@@ -15,6 +15,7 @@
 // so the load starts at the aligned piece below it.  The bytes of a chunk are assembled in LDS at the byte phase they have in the output
 // and leave as whole dwords; only the first and the last dword of a chunk, shared with the neighbouring blocks, leave byte by byte.
 #include "terrain_ao.h"
+#include "material_filter.h"
 #include "record_tile.h"
 #include "vtmc_ctx.h"
 #include <cmath>
@@ -31,9 +32,7 @@ struct AoArgs {
     const float *grid;  // the terrain's samples, x fastest
     int n[3];           // samples per axis
     const BlockDesc *active;
-    const int *list;    // device (bx, by, bz) triples of the dirty list, or null: every block, b = bx + nbx * (by + nby * bz)
-    int nbx, nby;
-    FastDiv d_nbx, d_nby;
+    BlockMap map;       // material_filter.h
     int reach, extent;  // R and 10 + 2R
     FastDiv d_extent;
     int steps;
@@ -159,14 +158,7 @@ __global__ __launch_bounds__(256) void ao_kernel(const uint32_t *__restrict__ re
     if (count == 0u) return;
     const uint32_t vpr = INDEXED ? 1u : 3u;
     int b[3];
-    if (a.list) {
-        b[0] = a.list[3 * (size_t)d.b], b[1] = a.list[3 * (size_t)d.b + 1], b[2] = a.list[3 * (size_t)d.b + 2];
-    } else {
-        const unsigned q = a.d_nbx.quot(d.b);
-        b[0] = (int)(d.b - q * (unsigned)a.nbx);
-        b[2] = (int)a.d_nby.quot(q);
-        b[1] = (int)(q - (unsigned)b[2] * (unsigned)a.nby);
-    }
+    material_block(a.map, d.b, b[0], b[1], b[2]);
     AoField F;
     F.tile = tile;
     F.grid = a.grid;
@@ -258,10 +250,7 @@ int32_t vtmc_ao_vertices(vtmc_ctx *ctx, const vtmc_ao_params *params, int64_t *n
         a.grid = (const float *)ctx->terrain.p;
         a.n[0] = ctx->tshape.dim_x, a.n[1] = ctx->tshape.dim_y, a.n[2] = ctx->tshape.dim_z;
         a.active = (const BlockDesc *)ctx->active.p;
-        const BlockSpace &sp = res.space;
-        a.list = sp.list;
-        a.nbx = sp.nbx, a.nby = sp.nby;
-        a.d_nbx = sp.d_nbx, a.d_nby = sp.d_nby;
+        a.map = block_map(res.space, res.blocks);
         a.reach = tb.reach, a.extent = tb.extent;
         a.d_extent = FastDiv((unsigned)tb.extent);
         a.steps = params->steps;

@@ -1,10 +1,11 @@
 // terrain_lodskirt.h -- the host half of the level-of-detail skirts (terrain_lodskirt.hip): the argument checks, the face masks of the node
-// list (a hash of (origin, level)), the count bound and the sizes of the pass's buffers.  Plain C++ with no device code and no HIP header, so
-// a stand-alone program compiles it for the CPU (tools/lodskirt_host_check.cpp runs it under the host sanitizers).  The rule is LODSKIRT of
-// include/vtmc_lodskirt.h.
+// list (a hash of (origin, level)) and the count bound; the sizes of the pass's buffers are tri_stream.h's.  Plain C++ with no device code
+// and no HIP header, so a stand-alone program compiles it for the CPU (tools/lodskirt_host_check.cpp runs it under the host sanitizers).
+// The rule is LODSKIRT of include/vtmc_lodskirt.h.
 #ifndef VTMC_TERRAIN_LODSKIRT_H
 #define VTMC_TERRAIN_LODSKIRT_H
 #include "../../include/vtmc_lodskirt.h"
+#include "tri_stream.h"
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -12,7 +13,6 @@
 
 namespace vtmc {
 
-constexpr int kLodSkirtTile = 256;          // triangles per workgroup, one lane each
 constexpr int kLodSkirtFaces = 6;
 constexpr int kLodSkirtPerTriangle = 12;    // records a triangle can yield at the most: a quad of two records on each of six faces
 
@@ -26,12 +26,6 @@ inline const char *lodskirt_params_fault(const vtmc_lodskirt_params &p)
     if (p.flags & ~VTMC_LODSKIRT_ALL_FACES) return "unknown flag bits";
     return nullptr;
 }
-
-// workgroups of a pass over T triangles (T >= 0)
-inline uint32_t lodskirt_tiles(int64_t n_tris) { return (uint32_t)((n_tris + kLodSkirtTile - 1) / kLodSkirtTile); }
-
-// the mask bytes of T triangles, padded so that every tile's bytes are whole dwords
-inline size_t lodskirt_mask_bytes(int64_t n_tris) { return (size_t)lodskirt_tiles(n_tris) * kLodSkirtTile; }
 
 // The count bound: no result of T triangles yields more records than this, and a tile's total (at most 256 * 12 = 3072) and a scan group's
 // (1024 tiles: 3 145 728) stay far inside the 32 bits the scan keeps them in; the grand total is summed in 64 bits and compared with

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void material_indexed_kernel(const uint32_t *_
     const uint32_t v0 = blockIdx.x * (uint32_t)kMatTile;
     const uint32_t nv = n_verts - v0 < (uint32_t)kMatTile ? n_verts - v0 : (uint32_t)kMatTile;
     load_record_tile(rec, verts + (size_t)v0 * 6, nv * 6);  // tile base: 256 * 24 bytes per tile, 16-byte aligned
-    if (threadIdx.x < 2) range[threadIdx.x] = material_block_of(voffsets, 0u, a.n_blocks - 1, threadIdx.x ? v0 + nv - 1 : v0);
+    if (threadIdx.x < 2) range[threadIdx.x] = material_block_of(voffsets, 0u, a.map.n_blocks - 1, threadIdx.x ? v0 + nv - 1 : v0);
     __syncthreads();
     if (threadIdx.x < nv) {
         const uint32_t v = v0 + threadIdx.x;
@@ -259,11 +259,7 @@ int32_t vtmc_material_vertices(vtmc_ctx *ctx, int64_t *n_vertices)
         a.layer = (const uint2 *)ctx->material.p;
         a.C = ctx->mat_c;
         material_vertex_scale(cells, a.C, a.s);
-        const BlockSpace &sp = res.space;
-        a.list = sp.list;
-        a.n_blocks = (uint32_t)res.blocks;
-        a.nbx = sp.nbx, a.nby = sp.nby;
-        a.d_nbx = sp.d_nbx, a.d_nby = sp.d_nby;
+        a.map = block_map(res.space, res.blocks);
         if (res.indexed) {
             const uint32_t V = (uint32_t)res.verts;
             VTMC_HIP(ctx, launch(material_indexed_kernel, dim3((V + kMatTile - 1) / kMatTile), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->verts.p, V,

@@ -1,11 +1,12 @@
-// terrain_scatter.h -- the host half of the surface scatter (terrain_scatter.hip): the argument checks, dc, the tile count, and the hash of
-// the rule, which host and device share.  Outside the library's own build it takes no HIP header and holds no device-only code, so a stand-alone
-// program compiles it for the CPU
-// (tools/scatter_host_check.cpp runs it under the host sanitizers).  The arithmetic of scatter_density_cells is part of the rule of
-// include/vtmc.h: FP32, one IEEE operation per step (-ffp-contract=off).
+// terrain_scatter.h -- the host half of the surface scatter (terrain_scatter.hip): the argument checks, dc, and the hash of the rule, which
+// host and device share; the tile count and the mask bytes are tri_stream.h's.  Outside the library's own build it takes no HIP header and
+// holds no device-only code, so a stand-alone program compiles it for the CPU (tools/scatter_host_check.cpp runs it under the host
+// sanitizers).  The arithmetic of scatter_density_cells is part of the rule of include/vtmc.h: FP32, one IEEE operation per step
+// (-ffp-contract=off).
 #ifndef VTMC_TERRAIN_SCATTER_H
 #define VTMC_TERRAIN_SCATTER_H
 #include "../../include/vtmc.h"
+#include "tri_stream.h"
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -18,8 +19,6 @@
 #endif
 
 namespace vtmc {
-
-constexpr int kScatterTile = 256;   // triangles per workgroup, one lane each
 
 // dc = density * (voxel_scale * voxel_scale): instances per cell^2, the factor the kernel multiplies a triangle's area (in cells) with
 inline float scatter_density_cells(float density, float voxel_scale)
@@ -40,12 +39,6 @@ inline const char *scatter_params_fault(const vtmc_scatter_params &p, float voxe
     if (p.flags != 0u) return "flags must be 0";
     return nullptr;
 }
-
-// workgroups of a pass over T triangles (T >= 0)
-inline uint32_t scatter_tiles(int64_t n_tris) { return (uint32_t)((n_tris + kScatterTile - 1) / kScatterTile); }
-
-// the mask bytes of T triangles, padded so that every tile's bytes are whole dwords
-inline size_t scatter_mask_bytes(int64_t n_tris) { return (size_t)scatter_tiles(n_tris) * kScatterTile; }
 
 // -- the hash of the rule ------------------------------------------------------------------------------------------------------------------
 constexpr uint64_t kScatterGolden = 0x9E3779B97F4A7C15ull;

@@ -1,44 +1,24 @@
 // terrain_scatter.hip -- instances scattered over the surface of a terrain extract (vtmc_scatter_*): area-weighted points on the triangles
 // of the result, filtered by slope, world height and one channel of the material layer.  The rule, operation by operation, is in
 // include/vtmc.h; the kernels follow it bit for bit (library built with -ffp-contract=off).  The host half -- argument checks, dc, the
-// tile count, the hash -- is terrain_scatter.h; the material filter and the block mapping are material_filter.h, the code the vertex
-// weights use.
+// hash -- is terrain_scatter.h; the material filter and the block mapping are material_filter.h, the code the vertex weights use.
 //
-// The pass is a stream over the records, in tiles of kScatterTile = 256 triangles, one lane per triangle, and no atomic decides where an
-// instance goes: the order is a function of the result alone.
-//   1. scatter_count_kernel  evaluates every candidate of its triangle and writes one SURVIVOR MASK byte per triangle (bit i: candidate i
-//      survives; n <= 8) and the tile's survivor total.
-//   2. the scan of the tile totals, in two levels: scan_tiles_kernel gives every tile its prefix inside its group of 1024 tiles
-//      and every group its total; scan_groups_kernel, one workgroup, scans the group totals (at most 8192 of them) and leaves the
-//      grand total, which goes to the host for the max_instances check and the growth of the instance buffer.  A tile's offset is the sum
-//      of the two prefixes.  (One workgroup over all the tile totals took 0.19 ms of the pass's 0.88 at 1024^3: profiles/r19/scatter.)
-//   3. scatter_emit_kernel   the same tiling; a workgroup scan of the masks' popcounts gives every lane its slot; only triangles with a
-//      set bit are loaded into registers and hashed again, only set bits are recomputed, and the filters, which the mask has already
-//      answered, are skipped.  An instance leaves as two 16-byte stores to its 32-byte slot; a lane's instances are consecutive slots and
-//      consecutive lanes continue each other, so a wave's stores fall into one contiguous run of the output.
-//   4. scatter_block_offsets_kernel  a thread per block of the result: the tile offset of the block's first triangle plus the popcounts
-//      of the mask bytes of the tile before it, read as dwords.
-// Soup records come into LDS as consecutive 16-byte pieces (record_tile.h), never at a 76-byte lane stride; a lane then reads its record
-// at a stride of 19 dwords, which is odd, so the LDS banks do not collide.  In indexed mode a lane finds its block in the triangle offsets
-// (two lanes bracket the tile's blocks first), reads its index triple and gathers its three vtmc_vertex through the block's vertex offset;
-// the vertices of a block are shared by about six triangles and come from L2.
-// Traffic that must reach HBM, soup: 76 T (count) + T (masks out) + T (masks in) + 76 T' (emit: the tiles with a survivor) + 32 N.
+// The pass is the stream over the result's triangles of tri_stream_kernels.h: the scheme, its traffic and the bounds of every access are
+// written down there, and the view of the result, the tiles, the loader (which clamps what it gathers: the scatter rests on the same
+// bounds argument as the skirts), the offsets kernel and the host glue come from there.  The scatter's own: scatter_count_kernel
+// evaluates every candidate of its triangle and writes one SURVIVOR MASK byte per triangle (bit i: candidate i survives; n <= 8); the
+// host checks the grand total against max_instances; scatter_emit_kernel hashes only triangles with a set bit again and skips the
+// filters, which the mask has already answered; an instance leaves as two 16-byte stores to its 32-byte slot, so a wave's stores fall
+// into one contiguous run of the output.  One record per set bit.
 #include "terrain_scatter.h"
-#include "material_filter.h"
-#include "record_tile.h"
-#include "scan_kernels.h"
 #include "terrain_material.h"
-#include "vtmc_ctx.h"
+#include "tri_stream_kernels.h"
 #include <cmath>
 
 namespace vtmc {
 
 struct ScatterArgs {
-    const uint32_t *recs;      // soup: T records of 19 dwords (vtmc_triangle); indexed: V records of 6 dwords (vtmc_vertex)
-    const int32_t *indices;    // indexed: 3 T block-local indices
-    const uint32_t *toffsets;  // the n_blocks + 1 per-block triangle offsets
-    const uint32_t *voffsets;  // indexed: the n_blocks + 1 per-block vertex offsets
-    uint32_t n_tris;
+    TriView v;
     MaterialVertexArgs m;      // the block mapping, and the layer when channel >= 0
     int channel;
     uint64_t k0;               // fin(seed + G)
@@ -55,26 +35,14 @@ struct ScatterTri {
 template <bool INDEXED>
 __device__ __forceinline__ void scatter_load(const ScatterArgs &a, const uint32_t *rec, const uint32_t *range, uint32_t t, ScatterTri &tri)
 {
-    if (INDEXED) {
-        const uint32_t b = material_block_of(a.toffsets, range[0], range[1], t);
-        material_block(a.m, b, tri.b[0], tri.b[1], tri.b[2]);
-        const uint32_t vb = a.voffsets[b];
+    const uint32_t b = tri_block_of<INDEXED>(a.v, rec, range, t);
+    material_block(a.m.map, b, tri.b[0], tri.b[1], tri.b[2]);   // before the gather: the list entry's load goes out first
+    TriWords w;
+    tri_load<INDEXED>(a.v, rec, t, b, w);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            // a vtmc_vertex is 24 bytes at a multiple of 24: three 8-byte loads
-            const uint2 *r = reinterpret_cast<const uint2 *>(a.recs + 6 * ((size_t)vb + (uint32_t)a.indices[3 * (size_t)t + c]));
-            const uint2 r0 = r[0], r1 = r[1], r2 = r[2];
-            tri.p[c][0] = __uint_as_float(r0.x), tri.p[c][1] = __uint_as_float(r0.y), tri.p[c][2] = __uint_as_float(r1.x);
-            tri.n[c][0] = __uint_as_float(r1.y), tri.n[c][1] = __uint_as_float(r2.x), tri.n[c][2] = __uint_as_float(r2.y);
-        }
-    } else {
-        const uint32_t *r = rec + 19u * (t % (uint32_t)kScatterTile);
-        material_block(a.m, r[18], tri.b[0], tri.b[1], tri.b[2]);
+    for (int c = 0; c < 3; ++c)
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) tri.p[c][k] = __uint_as_float(r[3 * c + k]), tri.n[c][k] = __uint_as_float(r[9 + 3 * c + k]);
-    }
+        for (int k = 0; k < 3; ++k) tri.p[c][k] = __uint_as_float(w.p[c][k]), tri.n[c][k] = __uint_as_float(w.n[c][k]);
 }
 
 // the triangle's key: the seed, then the nine grid coordinates of its corners (+ 0.0f: -0 becomes +0)
@@ -141,26 +109,15 @@ __device__ __forceinline__ bool scatter_candidate(const ScatterArgs &a, const Sc
     return true;
 }
 
-// the tile of a workgroup: soup records into LDS; indexed, the blocks of the tile's first and last triangle
-template <bool INDEXED>
-__device__ __forceinline__ void scatter_stage(const ScatterArgs &a, uint32_t *rec, uint32_t *range, uint32_t t0, uint32_t nt)
-{
-    if (INDEXED) {
-        if (threadIdx.x < 2) range[threadIdx.x] = material_block_of(a.toffsets, 0u, a.m.n_blocks - 1, threadIdx.x ? t0 + nt - 1 : t0);
-    } else {
-        load_record_tile(rec, a.recs + (size_t)t0 * 19, nt * 19);  // tile base: 256 * 76 bytes per tile, 16-byte aligned
-    }
-    __syncthreads();
-}
-
 template <bool INDEXED>
 __global__ __launch_bounds__(256) void scatter_count_kernel(ScatterArgs a, uint8_t *__restrict__ masks, uint32_t *__restrict__ tile_totals)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t rec[INDEXED ? 4 : kScatterTile * 19];
+    __shared__ __attribute__((aligned(16))) uint32_t rec[INDEXED ? 4 : kTriTile * 19];
     __shared__ uint32_t range[2], wave_sums[4];
-    const uint32_t t0 = blockIdx.x * (uint32_t)kScatterTile;
-    const uint32_t nt = a.n_tris - t0 < (uint32_t)kScatterTile ? a.n_tris - t0 : (uint32_t)kScatterTile;
-    scatter_stage<INDEXED>(a, rec, range, t0, nt);
+    uint32_t t0, nt;
+    tri_tile_bounds(a.v, t0, nt);
+    if (INDEXED) tri_tile_bracket(a.v, range, t0, nt);
+    else tri_tile_stage(a.v, rec, t0, nt);
     uint32_t mask = 0u;
     if (threadIdx.x < nt) {
         ScatterTri tri;
@@ -181,15 +138,16 @@ template <bool INDEXED>
 __global__ __launch_bounds__(256) void scatter_emit_kernel(ScatterArgs a, const uint8_t *__restrict__ masks, const uint32_t *__restrict__ tile_offsets,
                                                            const uint32_t *__restrict__ group_offsets, uint32_t capacity, float4 *__restrict__ out)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t rec[INDEXED ? 4 : kScatterTile * 19];
+    __shared__ __attribute__((aligned(16))) uint32_t rec[INDEXED ? 4 : kTriTile * 19];
     __shared__ uint32_t range[2], wave_sums[4];
-    const uint32_t t0 = blockIdx.x * (uint32_t)kScatterTile;
-    const uint32_t nt = a.n_tris - t0 < (uint32_t)kScatterTile ? a.n_tris - t0 : (uint32_t)kScatterTile;
+    uint32_t t0, nt;
+    tri_tile_bounds(a.v, t0, nt);
     uint32_t mask = masks[(size_t)t0 + threadIdx.x];
     uint32_t total;
     const uint32_t before = block_scan<4>((uint32_t)__popc(mask), wave_sums, total);
     if (total == 0u) return;   // a tile without survivors reads no record (uniform across the workgroup)
-    scatter_stage<INDEXED>(a, rec, range, t0, nt);
+    if (INDEXED) tri_tile_bracket(a.v, range, t0, nt);
+    else tri_tile_stage(a.v, rec, t0, nt);
     if (mask == 0u || threadIdx.x >= nt) return;
     ScatterTri tri;
     scatter_load<INDEXED>(a, rec, range, t0 + threadIdx.x, tri);
@@ -206,27 +164,6 @@ __global__ __launch_bounds__(256) void scatter_emit_kernel(ScatterArgs a, const 
         }
         ++slot;
     }
-}
-
-// out[b], b = 0..n_blocks: the instances on triangles before the block's first one
-__global__ __launch_bounds__(256) void scatter_block_offsets_kernel(const uint32_t *__restrict__ toffsets, uint32_t n_blocks, uint32_t n_tris,
-                                                                    const uint32_t *__restrict__ mask_words, const uint32_t *__restrict__ tile_offsets,
-                                                                    const uint32_t *__restrict__ group_offsets, const unsigned long long *__restrict__ total,
-                                                                    int32_t *__restrict__ out)
-{
-    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
-    if (b > n_blocks) return;
-    const uint32_t t = toffsets[b];
-    if (t >= n_tris) {
-        out[b] = (int32_t)*total;
-        return;
-    }
-    const uint32_t tile = t / (uint32_t)kScatterTile, r = t % (uint32_t)kScatterTile;
-    const uint32_t *w = mask_words + (size_t)tile * (kScatterTile / 4);
-    uint32_t sum = group_offsets[tile / (uint32_t)kScanThreads] + tile_offsets[tile];
-    for (uint32_t j = 0; j < r / 4u; ++j) sum += (uint32_t)__popc(w[j]);
-    if (r & 3u) sum += (uint32_t)__popc(w[r / 4u] & ((1u << (8u * (r & 3u))) - 1u));
-    out[b] = (int32_t)sum;
 }
 
 static bool scatter_current(const vtmc_ctx *ctx) { return ctx->result.valid && ctx->scatter.epoch == ctx->result.epoch; }
@@ -246,7 +183,7 @@ int32_t vtmc_scatter_surface(vtmc_ctx *ctx, const vtmc_scatter_params *params, i
     if (params->material_channel >= 0 && !ctx->mat_c)
         return fail(ctx, VTMC_ERR_NO_RESULT, "scatter_surface: material_channel %d before material_init", params->material_channel);
     const VtmcResult &res = ctx->result;
-    VtmcScatter &sc = ctx->scatter;
+    VtmcTriStream &sc = ctx->scatter;
     const int64_t T = res.tris;
     const int B = res.blocks;
     VTMC_HIP(ctx, hipSetDevice(ctx->device));
@@ -258,21 +195,12 @@ int32_t vtmc_scatter_surface(vtmc_ctx *ctx, const vtmc_scatter_params *params, i
     if (T == 0 || B == 0) {
         VTMC_HIP(ctx, hipMemsetAsync(sc.block_offsets.p, 0, sizeof(int32_t) * ((size_t)B + 1), ctx->stream));
     } else {
-        const uint32_t tiles = scatter_tiles(T);
-        if (int rc = ensure(ctx, sc.masks, scatter_mask_bytes(T))) return rc;
-        if (int rc = ensure(ctx, sc.tiles, ScanLayout(tiles).bytes())) return rc;
-        const ScanLayout scan(tiles, sc.tiles.p);
+        const uint32_t tiles = tri_tiles(T);
+        ScanLayout scan(tiles);
+        if (int rc = tri_stream_scratch(ctx, sc, T, &scan)) return rc;
         ScatterArgs a{};
-        a.recs = (const uint32_t *)(res.indexed ? ctx->verts.p : ctx->tris.p);
-        a.indices = (const int32_t *)ctx->indices.p;
-        a.toffsets = (const uint32_t *)ctx->offsets.p;
-        a.voffsets = (const uint32_t *)ctx->voffsets.p;
-        a.n_tris = (uint32_t)T;
-        const BlockSpace &sp = res.space;
-        a.m.list = sp.list;
-        a.m.n_blocks = (uint32_t)B;
-        a.m.nbx = sp.nbx, a.m.nby = sp.nby;
-        a.m.d_nbx = sp.d_nbx, a.m.d_nby = sp.d_nby;
+        if (int rc = tri_view(ctx, "scatter_surface", &a.v)) return rc;   // refuses indexed triangles without vertices; the scatter is gone by now
+        a.m.map = block_map(res.space, B);
         a.channel = params->material_channel;
         if (a.channel >= 0) {
             const int cells[3] = {ctx->tshape.dim_x - 2, ctx->tshape.dim_y - 2, ctx->tshape.dim_z - 2};
@@ -289,24 +217,16 @@ int32_t vtmc_scatter_surface(vtmc_ctx *ctx, const vtmc_scatter_params *params, i
         uint8_t *masks = (uint8_t *)sc.masks.p;
         VTMC_HIP(ctx, clock.mark(0, ctx->stream));
         VTMC_HIP(ctx, launch(res.indexed ? scatter_count_kernel<true> : scatter_count_kernel<false>, dim3(tiles), dim3(256), 0, ctx->stream, a, masks, scan.tile_totals()));
-        VTMC_HIP(ctx, clock.mark(1, ctx->stream));
-        VTMC_HIP(ctx, launch_scan(scan, ctx->stream));
-        VTMC_HIP(ctx, clock.mark(2, ctx->stream));
-        VTMC_HIP(ctx, hipMemcpyAsync(&total, scan.total(), sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
-        VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (int rc = tri_scan_total(ctx, scan, clock, &total)) return rc;
         if (total > (unsigned long long)params->max_instances)
             return fail(ctx, VTMC_ERR_TOO_LARGE, "scatter_surface: %llu instances exceed max_instances %d", total, params->max_instances);
         if (total > 0)
-            if (int rc = ensure(ctx, sc.instances, sizeof(vtmc_instance) * (size_t)total)) return rc;
+            if (int rc = ensure(ctx, sc.records, sizeof(vtmc_instance) * (size_t)total)) return rc;
         VTMC_HIP(ctx, clock.mark(3, ctx->stream));
         if (total > 0)
             VTMC_HIP(ctx, launch(res.indexed ? scatter_emit_kernel<true> : scatter_emit_kernel<false>, dim3(tiles), dim3(256), 0, ctx->stream, a, masks, scan.tile_offsets(),
-                                 scan.group_offsets(), (uint32_t)total, (float4 *)sc.instances.p));
-        VTMC_HIP(ctx, clock.mark(4, ctx->stream));
-        VTMC_HIP(ctx, launch(scatter_block_offsets_kernel, lanes256((int64_t)B + 1), dim3(256), 0, ctx->stream, a.toffsets, (uint32_t)B, (uint32_t)T,
-                             (const uint32_t *)sc.masks.p, scan.tile_offsets(), scan.group_offsets(), scan.total(), (int32_t *)sc.block_offsets.p));
-        VTMC_HIP(ctx, clock.mark(5, ctx->stream));
-        clock.arm();
+                                 scan.group_offsets(), (uint32_t)total, (float4 *)sc.records.p));
+        if (int rc = tri_launch_offsets(ctx, a.v, sc, scan, 1u, clock)) return rc;
     }
     VTMC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     sc.n = (int64_t)total;
@@ -320,23 +240,14 @@ int32_t vtmc_scatter_read(vtmc_ctx *ctx, vtmc_instance *dst, int64_t capacity, i
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
     if (!scatter_current(ctx)) return fail(ctx, VTMC_ERR_NO_RESULT, "scatter_read: no instances of the current result (call vtmc_scatter_surface)");
-    const VtmcScatter &sc = ctx->scatter;
-    if (capacity < sc.n) return fail(ctx, VTMC_ERR_INVALID_ARG, "capacity %lld < %lld instances", (long long)capacity, (long long)sc.n);
-    if (sc.n > 0 && !dst) return fail(ctx, VTMC_ERR_INVALID_ARG, "dst is null");
-    VTMC_HIP(ctx, hipSetDevice(ctx->device));
-    if (sc.n > 0) VTMC_HIP(ctx, hipMemcpy(dst, sc.instances.p, sizeof(vtmc_instance) * (size_t)sc.n, hipMemcpyDeviceToHost));
-    if (block_instance_offsets)
-        VTMC_HIP(ctx, hipMemcpy(block_instance_offsets, sc.block_offsets.p, sizeof(int32_t) * ((size_t)sc.blocks + 1), hipMemcpyDeviceToHost));
-    return VTMC_OK;
+    return tri_stream_read(ctx, ctx->scatter, sizeof(vtmc_instance), "instances", VTMC_ERR_INVALID_ARG, dst, capacity, block_instance_offsets);
 }
 
 int32_t vtmc_scatter_device_results(vtmc_ctx *ctx, const vtmc_instance **d_instances, const int32_t **d_block_offsets, int64_t *n_instances)
 {
     if (!ctx) return VTMC_ERR_INVALID_ARG;
     if (!scatter_current(ctx)) return fail(ctx, VTMC_ERR_NO_RESULT, "scatter_device_results: no instances of the current result (call vtmc_scatter_surface)");
-    if (d_instances) *d_instances = (const vtmc_instance *)ctx->scatter.instances.p;
-    if (d_block_offsets) *d_block_offsets = (const int32_t *)ctx->scatter.block_offsets.p;
-    if (n_instances) *n_instances = ctx->scatter.n;
+    tri_stream_device_results(ctx->scatter, d_instances, d_block_offsets, n_instances);
     return VTMC_OK;
 }
 
@@ -345,12 +256,7 @@ int32_t vtmc_scatter_device_results(vtmc_ctx *ctx, const vtmc_instance **d_insta
 int32_t vtmc_debug_scatter_ms(vtmc_ctx *ctx, float ms[4])
 {
     if (!ctx || !ms) return VTMC_ERR_INVALID_ARG;
-    if (!ctx->scatter_clock.armed) return fail(ctx, VTMC_ERR_NO_RESULT, "debug_scatter_ms before a scatter that launched kernels");
-    if (int rc = ctx->scatter_clock.sync_last(ctx)) return rc;
-    static const int pairs[4][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
-    for (int i = 0; i < 4; ++i)
-        if (int rc = ctx->scatter_clock.elapsed(ctx, pairs[i][0], pairs[i][1], &ms[i])) return rc;
-    return VTMC_OK;
+    return tri_stream_ms(ctx, ctx->scatter_clock, "debug_scatter_ms before a scatter that launched kernels", ms);
 }
 
 }  // extern "C"

@@ -124,13 +124,13 @@ struct VertexAttr {
     uint64_t epoch = 0;
 };
 
-// The instances scattered over the result `epoch` names (terrain_scatter.hip): library-owned, grow-only, stale after the next extract.
-// masks: one survivor byte per triangle, whole tiles; tiles: the grand total (64 bits), the tile totals and their prefixes inside a
-// group of tiles, the group totals and their prefixes.
-struct VtmcScatter {
-    VtmcDevBuf instances, block_offsets, masks, tiles;
+// What a pass over the triangles of the result `epoch` names holds (tri_stream_kernels.h): library-owned, grow-only, stale after the next
+// extract.  records: the n records the pass emitted; block_offsets: blocks + 1 entries; masks: one byte per triangle, whole tiles; scan:
+// the ScanLayout of the tiles' totals.
+struct VtmcTriStream {
+    VtmcDevBuf records, block_offsets, masks, scan;
     int64_t n = 0;
-    int blocks = 0;        // block_offsets holds blocks + 1 entries
+    int blocks = 0;
     uint64_t epoch = 0;
 };
 
@@ -190,16 +190,15 @@ struct VtmcWater {
     std::vector<vtmc_water_body> bodies;
 };
 
-// The skirts over the seams of the level-of-detail result `epoch` names (terrain_lodskirt.hip): library-owned, grow-only, stale after the
-// next extract.  tris: the records; node_offsets: nodes + 1 entries; masks: one face-mask byte per triangle, whole tiles; tiles: the scan's
-// layout; node_masks: the face masks of the nodes as the kernels read them, face_masks the host's copy of those of the skirts held; sink:
-// what vtmc_debug_lodskirt_read_ms's kernel leaves.  staged: the emit kernel's store variant (vtmc_debug_lodskirt_store).
+// The skirts over the seams of a level-of-detail result (terrain_lodskirt.hip): the records are vtmc_triangle, the blocks are nodes, a
+// mask byte holds a triangle's faces.  node_masks: the face masks of the nodes as the kernels read them, face_masks the host's copy of
+// those of the skirts held; sink: what vtmc_debug_lodskirt_read_ms's kernel leaves.  staged: the emit kernel's store variant
+// (vtmc_debug_lodskirt_store).
 struct VtmcLodSkirt {
-    VtmcDevBuf tris, node_offsets, masks, tiles, node_masks, sink;
+    VtmcTriStream pass;
+    VtmcDevBuf node_masks, sink;
     std::vector<uint8_t> face_masks;
-    int64_t n = 0;
-    int32_t nodes = 0, flagged = 0;
-    uint64_t epoch = 0;
+    int32_t flagged = 0;
     bool staged = false;
 };
 
@@ -287,8 +286,9 @@ struct vtmc_ctx {
     VertexAttr ao;
     VtmcDevBuf ao_stats;
     int32_t ao_direct_max = -1;         // vertices up to which a block takes the direct route; -1: the library's default
-    // terrain_scatter.hip: the instances of the last vtmc_scatter_surface and the clock of its kernels (armed by a call that launched them)
-    VtmcScatter scatter;
+    // terrain_scatter.hip: the instances of the last vtmc_scatter_surface (the records are vtmc_instance, a mask byte holds a triangle's
+    // survivors) and the clock of its kernels (armed by a call that launched them)
+    VtmcTriStream scatter;
     vtmc::StageClock<6> scatter_clock;
     // terrain_nav.hip: the last navigation build and the clock of its kernels (armed by a build that made spans)
     VtmcNav nav;
