@@ -919,7 +919,8 @@ int32_t vtmc_scatter_device_results(vtmc_ctx *ctx, const vtmc_instance **d_insta
  *   vtmc_read_cases, vtmc_device_results, vtmc_device_indexed_results and vtmc_last_counts (n_blocks = the number of nodes) exactly as any
  *   extract does.  It changes nothing in the terrain: not the grid, the dirty list, the history or the event counter.  Its result is NOT a
  *   result of the dirty list: vtmc_material_vertices and vtmc_ao_vertices answer VTMC_ERR_NO_RESULT after it, until the next
- *   vtmc_terrain_update / _undo / _redo / _load (per-vertex materials and occlusion on coarse nodes are not defined yet).
+ *   vtmc_terrain_update / _undo / _redo / _load.  Those two entry points keep refusing: per-vertex materials and occlusion of this result
+ *   and of its skirts are vtmc_lod_material_vertices and vtmc_lod_ao_vertices (include/vtmc_lodattr.h, an optional layer with its own buffers).
  *   *n_nodes and *tri_count may be NULL.
  *   VTMC_ERR_NO_RESULT before vtmc_terrain_init.  VTMC_ERR_INVALID_ARG: params null; viewer or split not finite; split < 1; max_level
  *   outside 0..VTMC_LOD_MAX_LEVEL; max_nodes <= 0.  VTMC_ERR_DIMS: 8 * 2^max_level does not divide W, E and H.  VTMC_ERR_TOO_LARGE: the

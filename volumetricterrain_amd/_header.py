@@ -92,7 +92,7 @@ class Header:
 
     def _prototype(self, m):
         name, at = m.group(1), m.start()
-        ret = self.text[max(self.text.rfind(";", 0, at), self.text.rfind("}", 0, at)) + 1:at].split("\n")   # before the name, back to the last declaration,
+        ret = self.text[max(self.text.rfind(c, 0, at) for c in ";}{") + 1:at].split("\n")   # before the name, back to the last declaration or the extern "C" {,
         ret = re.sub(r"\s*\*\s*", " *", " ".join(" ".join(l for l in ret if not l.lstrip().startswith("#")).split()))   # less preprocessor lines
         tail = re.compile(r"\(([^;{}()]*)\)\s*;").match(self.text, m.end() - 1)
         if ret not in RETURNS or not tail or name in self.prototypes:

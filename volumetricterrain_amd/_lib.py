@@ -15,7 +15,7 @@ from ._header import HEADER, LAYERS
 
 # every #define VTMC_<NAME> of every layer's header as <NAME>.  include/vtmc.h: OK and the ERR_* codes, FLAG_*, OUTPUT_*, MOD_*, TERRAIN_SAVE_EXACT,
 # TERRAIN_LOAD_NO_EXTRACT, MESH_*, MATERIAL_*, AO_*, SCATTER_*, LOD_MAX_LEVEL, RAY_TWO_SIDED, SPHERE_MAX_RADIUS_CELLS, COMM_ID_BYTES ...
-# The optional layers' headers: NAV_OPEN, NAVFIELD_UNIT, NAVERODE_MAX_RADIUS, NAVSIGHT_ANY_COST, NAVCROWD_ANY_DETOUR, WATER_AT_FACE, LODSKIRT_ALL_FACES ...
+# The optional layers' headers: NAV_OPEN, NAVFIELD_UNIT, NAVERODE_MAX_RADIUS, NAVSIGHT_ANY_COST, NAVCROWD_ANY_DETOUR, WATER_AT_FACE, LODSKIRT_ALL_FACES, LODATTR_AO ...
 for _layer in LAYERS.values():
     globals().update((name[len("VTMC_"):], value) for name, value in _layer.constants.items())
 STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27   # vtmc_stamp_create: the limits of a stamp's dims (the header states them in prose)
@@ -77,6 +77,9 @@ DEBUG_ARGTYPES = {   # entry points that are deliberately not in the header; all
     "vtmc_debug_lodskirt_ms": [_vp, _P(ctypes.c_float * 4)],        # device time of the last skirt pass's four kernels
     "vtmc_debug_lodskirt_store": [_vp, _i32],                       # the emit kernel's store variant of later skirt passes: 0 direct, 1 staged in LDS
     "vtmc_debug_lodskirt_read_ms": [_vp, _i32, _P(ctypes.c_float)],  # median device time of a plain read of the result's records
+    "vtmc_debug_lodattr_routes": [_vp, _P(ctypes.c_uint32 * 2), _i32],   # the route counters of the last vtmc_lod_ao_vertices
+    "vtmc_debug_lodattr_skirts_in_node": [_vp, _i32],               # later occlusion calls: a node's skirt quads in its own workgroup (1, the default) or a pass of their own (0)
+    "vtmc_debug_lodattr_ms": [_vp, _P(ctypes.c_float * 2)],         # device time of the last occlusion call's nodes' kernel and skirts' pass
 }
 
 

@@ -1,4 +1,4 @@
-// record_tile.h -- how the passes over an extract's records (per vertex: terrain_material.hip, terrain_ao.hip; per triangle: the stream of
+// record_tile.h -- how the passes over an extract's records (per vertex: material_filter.h, ao_march.h; per triangle: the stream of
 // tri_stream_kernels.h, for terrain_scatter.hip and terrain_lodskirt.hip) bring a run of records into LDS: a soup record is 19 dwords and
 // a lane that read "its" record would walk memory at a 76-byte stride, so a workgroup of 256 threads loads the run as consecutive
 // 16-byte pieces instead.  Device code only.

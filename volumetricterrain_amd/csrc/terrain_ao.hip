@@ -11,22 +11,13 @@
 // coordinates and subtracts the tile's origin, and a clamped i0 names a sample that is inside both the grid and the tile.
 // Empty blocks have no BlockDesc and launch nothing.  A block with at most kAoDirectMax vertices is not worth a tile (10648 loads at R = 6):
 // its workgroup fetches from global memory with the same code (route counters: vtmc_debug_ao_routes).
-// Records go through LDS in 16-byte pieces (record_tile.h), kAoChunk at a time; a block's first record is not 16-byte aligned in general,
-// so the load starts at the aligned piece below it.  The bytes of a chunk are assembled in LDS at the byte phase they have in the output
-// and leave as whole dwords; only the first and the last dword of a chunk, shared with the neighbouring blocks, leave byte by byte.
-#include "terrain_ao.h"
+// The march itself and the pass of a workgroup over its block's records (the record loader, the chunks, the dword-assembled byte output)
+// are ao_march.h's, shared with the level-of-detail pass of terrain_lodattr.hip.
+#include "ao_march.h"
 #include "material_filter.h"
-#include "record_tile.h"
 #include "vtmc_ctx.h"
-#include <cmath>
-#include <type_traits>
 
 namespace vtmc {
-
-constexpr int kAoSoupChunk = 128;     // triangles (384 vertices) per pass of a workgroup: 9.7 KB of records, so tile + records stay under 53 KB and
-                                      // three workgroups share a CU's 160 KB at the largest radius
-constexpr int kAoIndexedChunk = 256;  // vertices per pass
-constexpr int kAoDirectMax = 12;      // vertices up to which a block's workgroup reads global memory directly
 
 struct AoArgs {
     const float *grid;  // the terrain's samples, x fastest
@@ -35,123 +26,19 @@ struct AoArgs {
     BlockMap map;       // material_filter.h
     int reach, extent;  // R and 10 + 2R
     FastDiv d_extent;
-    int steps;
-    float strength;
-    float hd[3][VTMC_AO_MAX_STEPS];  // terrain_ao.h
-    float fall[VTMC_AO_MAX_STEPS];
+    AoMarch march;      // ao_march.h
     uint32_t direct_max;
     uint32_t *stats;  // [0] workgroups that staged a tile, [1] workgroups on the direct route
     uint8_t *out;
 };
 
-// where the workgroup's samples lie: the tile (origin o in grid samples, E per axis) and the grid
-struct AoField {
-    const float *tile;
-    const float *__restrict__ grid;
-    int o[3];
-    int E;
-    int n[3];
-};
-
-struct AoAxis {
-    uint32_t off;  // the lower sample's offset along this axis, multiplied out
-    float f;
-};
-
-// the rule's per-axis step of fetch(): the clamped coordinate cut into the sample below it and the weight
-template <bool TILE>
-__device__ __forceinline__ AoAxis ao_axis(const AoField &F, int k, float q)
-{
-    const int n = F.n[k];
-    const float top = (float)(n - 1);
-    const float t = q < 0.0f ? 0.0f : (q > top ? top : q);
-    int i0 = (int)floorf(t);
-    if (i0 > n - 2) i0 = n - 2;
-    if (i0 < 0) i0 = 0;  // a NaN coordinate only (no result of the library holds one): stay inside the grid
-    AoAxis a;
-    a.f = t - (float)i0;
-    if (TILE) a.off = (uint32_t)(i0 - F.o[k]) * (k == 0 ? 1u : (k == 1 ? (uint32_t)F.E : (uint32_t)(F.E * F.E)));
-    else a.off = (uint32_t)i0 * (k == 0 ? 1u : (k == 1 ? (uint32_t)F.n[0] : (uint32_t)F.n[0] * (uint32_t)F.n[1]));
-    return a;
-}
-
-template <bool TILE>
-__device__ __forceinline__ float ao_fetch(const AoField &F, AoAxis X, AoAxis Y, AoAxis Z)
-{
-    const uint32_t sy = TILE ? (uint32_t)F.E : (uint32_t)F.n[0];
-    const uint32_t sz = TILE ? (uint32_t)(F.E * F.E) : (uint32_t)F.n[0] * (uint32_t)F.n[1];
-    const float *p = (TILE ? F.tile : F.grid) + (size_t)(X.off + Y.off + Z.off);
-    const float v000 = p[0], v100 = p[1], v010 = p[sy], v110 = p[sy + 1];
-    const float v001 = p[sz], v101 = p[sz + 1], v011 = p[sz + sy], v111 = p[sz + sy + 1];
-    const float a00 = v000 + (v100 - v000) * X.f, a10 = v010 + (v110 - v010) * X.f;
-    const float a01 = v001 + (v101 - v001) * X.f, a11 = v011 + (v111 - v011) * X.f;
-    const float b0 = a00 + (a10 - a00) * Y.f, b1 = a01 + (a11 - a01) * Y.f;
-    return b0 + (b1 - b0) * Z.f;
-}
-
-template <int M, class Fn>
-__device__ __forceinline__ void ao_for_directions(Fn &&fn)
-{
-    if constexpr (M < 27) {
-        if constexpr (M != 13) fn(std::integral_constant<int, M>{});
-        ao_for_directions<M + 1>(fn);
-    }
-}
-
-// The byte of a vertex at grid coordinates g with record normal nrm.  The directions are compile-time constants; a component of d that
-// is zero contributes +-0 to a sum of the rule, which changes no value the rule goes on to use (c only where c > 0, q only through the
-// clamp), so those terms are left out; (+-len) * h[s] is +-hd[s] exactly.
-template <bool TILE>
-__device__ __forceinline__ uint32_t ao_vertex(const AoArgs &a, const AoField &F, float gx, float gy, float gz, float n0, float n1, float n2)
-{
-    const float l = sqrtf((n0 * n0 + n1 * n1) + n2 * n2);
-    if (!(l > 0.0f) || !(l < INFINITY)) return 255u;
-    const float N0 = n0 / l, N1 = n1 / l, N2 = n2 / l;
-    // the axes a direction leaves alone fetch at the vertex's own coordinate
-    const AoAxis X0 = ao_axis<TILE>(F, 0, gx), Y0 = ao_axis<TILE>(F, 1, gy), Z0 = ao_axis<TILE>(F, 2, gz);
-    float num = 0.0f, den = 0.0f;
-    const int S = a.steps;
-    ao_for_directions<0>([&](auto code) {
-        constexpr int M = decltype(code)::value;
-        constexpr int I = M % 3 - 1, J = (M / 3) % 3 - 1, K = M / 9 - 1;
-        constexpr int NZ = (I != 0) + (J != 0) + (K != 0);
-        constexpr float LEN = NZ == 1 ? 1.0f : (NZ == 2 ? 0.70710678f : 0.57735027f);
-        float c = 0.0f;
-        if (I) c = N0 * ((float)I * LEN);
-        if (J) c = I ? c + N1 * ((float)J * LEN) : N1 * ((float)J * LEN);
-        if (K) c = (I || J) ? c + N2 * ((float)K * LEN) : N2 * ((float)K * LEN);
-        if (c > 0.0f) {
-            float o = 0.0f;
-            for (int s = 0; s < S; ++s) {
-                const float hd = a.hd[NZ - 1][s];
-                const AoAxis X = I ? ao_axis<TILE>(F, 0, I > 0 ? gx + hd : gx - hd) : X0;
-                const AoAxis Y = J ? ao_axis<TILE>(F, 1, J > 0 ? gy + hd : gy - hd) : Y0;
-                const AoAxis Z = K ? ao_axis<TILE>(F, 2, K > 0 ? gz + hd : gz - hd) : Z0;
-                float r = ao_fetch<TILE>(F, X, Y, Z);
-                r = r > 0.0f ? (r < 1.0f ? r : 1.0f) : 0.0f;
-                r = r * a.fall[s];
-                if (r > o) o = r;
-            }
-            num = num + c * o;
-            den = den + c;
-        }
-    });
-    float v = 1.0f - a.strength * (num / den);
-    v = v > 0.0f ? (v < 1.0f ? v : 1.0f) : 0.0f;
-    return (uint32_t)rintf(v * 255.0f);
-}
-
-// One workgroup per non-empty block.  RD = dwords per record: 19 (soup, three vertices: corner c has its position at dwords 3c.. and its
-// normal at 9 + 3c..) or 6 (indexed: position, normal).
+// One workgroup per non-empty block; the march and the pass over the block's records are ao_march.h's.
 template <bool INDEXED>
 __global__ __launch_bounds__(256) void ao_kernel(const uint32_t *__restrict__ recs, AoArgs a)
 {
-    constexpr uint32_t RD = INDEXED ? 6u : 19u;
-    constexpr uint32_t CHUNK = INDEXED ? (uint32_t)kAoIndexedChunk : (uint32_t)kAoSoupChunk;
-    constexpr uint32_t CHUNK_VERTS = INDEXED ? CHUNK : 3u * CHUNK;
     extern __shared__ __attribute__((aligned(16))) float tile[];
-    __shared__ __attribute__((aligned(16))) uint32_t rec[CHUNK * RD + 4];
-    __shared__ uint32_t outw[CHUNK_VERTS / 4 + 2];
+    __shared__ __attribute__((aligned(16))) uint32_t rec[AoChunkLds<INDEXED>::REC_WORDS];
+    __shared__ uint32_t outw[AoChunkLds<INDEXED>::OUT_WORDS];
     const BlockDesc d = a.active[blockIdx.x];
     const uint32_t first = INDEXED ? d.vert_base : d.tri_base;
     const uint32_t count = INDEXED ? d.vert_cnt : (d.cnt_mask & kCountMask);
@@ -163,7 +50,8 @@ __global__ __launch_bounds__(256) void ao_kernel(const uint32_t *__restrict__ re
     F.tile = tile;
     F.grid = a.grid;
     F.E = a.extent;
-    for (int k = 0; k < 3; ++k) F.n[k] = a.n[k], F.o[k] = 8 * b[k] - a.reach;
+    F.stride = 1;
+    for (int k = 0; k < 3; ++k) F.n[k] = F.dim[k] = a.n[k], F.o[k] = 8 * b[k] - a.reach;
     const bool direct = count * vpr <= a.direct_max;
     if (threadIdx.x == 0) atomicAdd(a.stats + (direct ? 1 : 0), 1u);
     if (!direct) {
@@ -179,51 +67,8 @@ __global__ __launch_bounds__(256) void ao_kernel(const uint32_t *__restrict__ re
             tile[i] = F.grid[(size_t)gx + (size_t)F.n[0] * ((size_t)gy + (size_t)F.n[1] * (size_t)gz)];
         }
     }
-    const float bx = (float)(8 * b[0]), by = (float)(8 * b[1]), bz = (float)(8 * b[2]);
-    uint8_t *bytes = reinterpret_cast<uint8_t *>(outw);
-    for (uint32_t r0 = 0; r0 < count; r0 += CHUNK) {
-        const uint32_t nr = count - r0 < CHUNK ? count - r0 : CHUNK;
-        const size_t d0 = ((size_t)first + r0) * RD;
-        const uint32_t head = (uint32_t)(d0 & 3u);  // dwords between the 16-byte piece the chunk starts in and its first record
-        if (r0) __syncthreads();                    // the pass before has read rec and outw
-        load_record_tile(rec, recs + (d0 - head), nr * RD + head);
-        __syncthreads();  // also behind the tile
-        const uint32_t nv = nr * vpr;
-        const size_t v0 = ((size_t)first + r0) * vpr;  // the chunk's first vertex = its first byte of the output
-        const uint32_t phase = (uint32_t)(v0 & 3u);
-        for (uint32_t v = threadIdx.x; v < nv; v += 256u) {
-            const uint32_t *r;
-            uint32_t c;
-            if (INDEXED) {
-                r = rec + head + 6u * v, c = 0u;
-            } else {
-                const uint32_t t = v / 3u;
-                r = rec + head + 19u * t, c = v - 3u * t;
-            }
-            const float p0 = __uint_as_float(r[3 * c]), p1 = __uint_as_float(r[3 * c + 1]), p2 = __uint_as_float(r[3 * c + 2]);
-            const uint32_t *nr3 = r + (INDEXED ? 3u : 9u + 3u * c);
-            const float n0 = __uint_as_float(nr3[0]), n1 = __uint_as_float(nr3[1]), n2 = __uint_as_float(nr3[2]);
-            const float gx = bx + p0, gy = by + p1, gz = bz + p2;
-            // the tile holds every fetch of a vertex inside its block's cells, p in [0, 8]; any other record reads the grid itself
-            const bool inside = p0 >= 0.0f && p0 <= 8.0f && p1 >= 0.0f && p1 <= 8.0f && p2 >= 0.0f && p2 <= 8.0f;
-            uint32_t val;
-            if (!direct && inside) val = ao_vertex<true>(a, F, gx, gy, gz, n0, n1, n2);
-            else val = ao_vertex<false>(a, F, gx, gy, gz, n0, n1, n2);
-            bytes[phase + v] = (uint8_t)val;
-        }
-        __syncthreads();
-        // dword w of outw is dword w of the output counted from the aligned byte below v0
-        uint8_t *dst = a.out + (v0 - phase);
-        const uint32_t end = phase + nv;
-        for (uint32_t w = threadIdx.x; 4u * w < end; w += 256u) {
-            if (4u * w >= phase && 4u * w + 4u <= end) {
-                reinterpret_cast<uint32_t *>(dst)[w] = outw[w];
-            } else {
-                const uint32_t lo = 4u * w < phase ? phase : 4u * w, hi = 4u * w + 4u < end ? 4u * w + 4u : end;
-                for (uint32_t i = lo; i < hi; ++i) dst[i] = bytes[i];
-            }
-        }
-    }
+    const float base[3] = {(float)(8 * b[0]), (float)(8 * b[1]), (float)(8 * b[2])};
+    ao_chunks<INDEXED, kAoGrid>(recs, first, count, direct, base, a.march, F, a.out, rec, outw);
 }
 
 }  // namespace vtmc
@@ -253,12 +98,7 @@ int32_t vtmc_ao_vertices(vtmc_ctx *ctx, const vtmc_ao_params *params, int64_t *n
         a.map = block_map(res.space, res.blocks);
         a.reach = tb.reach, a.extent = tb.extent;
         a.d_extent = FastDiv((unsigned)tb.extent);
-        a.steps = params->steps;
-        a.strength = params->strength;
-        for (int s = 0; s < VTMC_AO_MAX_STEPS; ++s) {
-            a.fall[s] = tb.fall[s];
-            for (int c = 0; c < 3; ++c) a.hd[c][s] = tb.hd[c][s];
-        }
+        a.march = ao_march(*params, tb);
         a.direct_max = (uint32_t)(ctx->ao_direct_max >= 0 ? ctx->ao_direct_max : kAoDirectMax);
         a.stats = (uint32_t *)ctx->ao_stats.p;
         a.out = (uint8_t *)ctx->ao.values.p;

@@ -272,6 +272,7 @@ int32_t vtmc_lod_skirts(vtmc_ctx *ctx, const vtmc_lodskirt_params *params, int64
     // From here on the buffers no longer hold the previous skirts.  What is refused above (INVALID_ARG, NO_RESULT, TOO_LARGE) keeps them; a
     // device error below (a buffer that cannot grow, a launch that fails) leaves the context without skirts, as the scatter does.
     st.epoch = 0;
+    lodattr_drop_skirts(ctx);   // include/vtmc_lodattr.h: the values of the previous skirts' corners go with them
     if (int rc = ensure(ctx, st.block_offsets, sizeof(int32_t) * (B + 1))) return rc;
     if (total > 0)
         if (int rc = ensure(ctx, st.records, sizeof(vtmc_triangle) * (size_t)total)) return rc;

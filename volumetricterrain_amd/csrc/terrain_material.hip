@@ -18,8 +18,6 @@
 
 namespace vtmc {
 
-constexpr int kMatTile = 256;  // records (triangles or vertices) per workgroup, one workgroup of 256 threads per tile
-
 struct MaterialPaintArgs {
     float ts[3], origin[3];
     int C;
@@ -27,40 +25,20 @@ struct MaterialPaintArgs {
     int n_strokes;
 };
 
-// soup: tris = T records of 19 dwords (vtmc_triangle); out[3t + v] = the weights of corner v of triangle t
+// soup: out[3t + v] = the weights of corner v of triangle t
 __global__ __launch_bounds__(256) void material_soup_kernel(const uint32_t *__restrict__ tris, uint32_t n_tris, uint2 *__restrict__ out, MaterialVertexArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint32_t rec[kMatTile * 19];
-    const uint32_t t0 = blockIdx.x * (uint32_t)kMatTile;
-    const uint32_t nt = n_tris - t0 < (uint32_t)kMatTile ? n_tris - t0 : (uint32_t)kMatTile;
-    load_record_tile(rec, tris + (size_t)t0 * 19, nt * 19);  // tile base: 256 * 76 bytes per tile, 16-byte aligned
-    __syncthreads();
-    for (uint32_t v = threadIdx.x; v < 3 * nt; v += 256) {
-        const uint32_t t = v / 3, c = v - 3 * t;
-        const uint32_t *r = rec + 19 * t;
-        const uint2 w = material_weights(a, r[18], __uint_as_float(r[3 * c]), __uint_as_float(r[3 * c + 1]), __uint_as_float(r[3 * c + 2]));
-        out[(size_t)t0 * 3 + v] = w;
-    }
+    material_soup_tile(tris, n_tris, out, a, MaterialOfBlocks{}, rec);
 }
 
-// indexed: verts = V records of 6 dwords (vtmc_vertex), voffsets = the n_blocks + 1 per-block vertex offsets; out[v] = the weights of
-// vertex v.  Two lanes find the blocks of the tile's first and last vertex; every lane then searches only between them.
+// indexed: out[v] = the weights of vertex v, its block found through the n_blocks + 1 per-block vertex offsets
 __global__ __launch_bounds__(256) void material_indexed_kernel(const uint32_t *__restrict__ verts, uint32_t n_verts, const uint32_t *__restrict__ voffsets,
                                                                uint2 *__restrict__ out, MaterialVertexArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint32_t rec[kMatTile * 6];
     __shared__ uint32_t range[2];
-    const uint32_t v0 = blockIdx.x * (uint32_t)kMatTile;
-    const uint32_t nv = n_verts - v0 < (uint32_t)kMatTile ? n_verts - v0 : (uint32_t)kMatTile;
-    load_record_tile(rec, verts + (size_t)v0 * 6, nv * 6);  // tile base: 256 * 24 bytes per tile, 16-byte aligned
-    if (threadIdx.x < 2) range[threadIdx.x] = material_block_of(voffsets, 0u, a.map.n_blocks - 1, threadIdx.x ? v0 + nv - 1 : v0);
-    __syncthreads();
-    if (threadIdx.x < nv) {
-        const uint32_t v = v0 + threadIdx.x;
-        const uint32_t b = material_block_of(voffsets, range[0], range[1], v);
-        const uint32_t *r = rec + 6 * threadIdx.x;
-        out[v] = material_weights(a, b, __uint_as_float(r[0]), __uint_as_float(r[1]), __uint_as_float(r[2]));
-    }
+    material_indexed_tile(verts, n_verts, voffsets, out, a, MaterialOfBlocks{}, rec, range);
 }
 
 // every texel (255,0,0,0, 0,0,0,0): TerrainSample starts with _matComponents[0] = 1

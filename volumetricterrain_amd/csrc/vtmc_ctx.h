@@ -202,6 +202,18 @@ struct VtmcLodSkirt {
     bool staged = false;
 };
 
+// The materials and the occlusion of a level-of-detail result and of its skirts (terrain_lodattr.hip), the layer's own: values[attribute]
+// [target], each current while its epoch is the result's; vtmc_lod_skirts clears the epochs of the skirt targets.  stats: the two route
+// counters of the last occlusion call (vtmc_debug_lodattr_routes); direct_max: vertices up to which a node takes the direct route, -1 the
+// library's default; skirts_in_node: the occlusion of a node's skirt corners comes from the node's own workgroup (the library's choice), not
+// from a pass of its own (vtmc_debug_lodattr_skirts_in_node).
+struct VtmcLodAttr {
+    VertexAttr values[2][2];
+    VtmcDevBuf stats;
+    int32_t direct_max = -1;
+    bool skirts_in_node = true;
+};
+
 // An extract that has been queued on a stream and not yet completed by extract_finish().
 struct VtmcPending {
     bool active = false;    // queued, extract_finish() not yet called
@@ -319,6 +331,10 @@ struct vtmc_ctx {
     // terrain_lodskirt.hip: the skirts of the last vtmc_lod_skirts and the clock of its kernels (armed by a call that launched them)
     VtmcLodSkirt lodskirt;
     vtmc::StageClock<6> lodskirt_clock;
+    // terrain_lodattr.hip: per-vertex materials and occlusion of that result and of those skirts, and the clock around the occlusion kernels
+    // of the last call that launched them (the nodes' pass, the skirts' pass)
+    VtmcLodAttr lodattr;
+    vtmc::StageClock<3> lodattr_clock;
     // raycast.hip, spherequery.hip: the queries and hits of vtmc_terrain_raycast / _spherecast / _closest_point (device, then their pinned staging)
     VtmcDevBuf rays;
     VtmcPinnedBuf<unsigned char> h_rays;
@@ -371,6 +387,8 @@ void material_drop(vtmc_ctx *ctx);   // terrain_material.hip: vtmc_terrain_init 
 // whatever invalidates the nav result drops what describes it, the flow field, the border distance and the origin of an erosion, and the
 // crowd that stands on it: vtmc_terrain_init / _load and every vtmc_terrain_nav_build
 inline void nav_drop(vtmc_ctx *ctx) { ctx->nav.valid = false, ctx->navfield.valid = false, ctx->naverode.dist_valid = false, ctx->naverode.origin_valid = false, ctx->navcrowd.valid = false; }
+// vtmc_lod_skirts replaces the skirts: what was computed for the corners of the previous ones names nothing any more
+inline void lodattr_drop_skirts(vtmc_ctx *ctx) { ctx->lodattr.values[0][1].epoch = 0, ctx->lodattr.values[1][1].epoch = 0; }
 inline void water_drop(vtmc_ctx *ctx) { ctx->water.valid = false; }   // vtmc_terrain_init / _load: the snapshot's grid is gone
 int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp);   // sp then walks the (bx,by,bz) list
 int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, ResultSource source, int32_t *tri_count);   // queued on the context's stream and finished

@@ -899,6 +899,64 @@ class Extractor:
         self._check(self._L.vtmc_lodskirt_device_results(self._h, ctypes.byref(p), ctypes.byref(o), ctypes.byref(n)))
         return p.value, o.value, n.value
 
+    # -- level-of-detail shading: materials and occlusion of that result and of its skirts (include/vtmc_lodattr.h) ------
+    def lod_material_vertices(self):
+        """Computes the material weights of every vertex of the level-of-detail result the context holds and, when skirts of it exist, of
+        every skirt corner, by the rule LODATTR, and leaves them on the device.  Returns (mesh vertices, skirt vertices)."""
+        n, s = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._L.vtmc_lod_material_vertices(self._h, ctypes.byref(n), ctypes.byref(s)))
+        return n.value, s.value
+
+    def lod_ao_vertices(self, params):
+        """The same for the occlusion bytes of an AmbientOcclusion (or a vtmc_ao_params struct): the radius counts the node's own cells."""
+        p = _struct(params)
+        n, s = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._L.vtmc_lod_ao_vertices(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(s)))
+        return n.value, s.value
+
+    def lodattr_info(self, attribute):
+        """(mesh vertices, skirt vertices) an attribute (LODATTR_MATERIAL, LODATTR_AO) holds for the current result; 0 skirt vertices
+        without a skirt target."""
+        n, s = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._L.vtmc_lodattr_info(self._h, int(attribute), ctypes.byref(n), ctypes.byref(s)))
+        return n.value, s.value
+
+    def lodattr_read(self, attribute, target):
+        """The values an attribute holds for a target (LODATTR_MESH, LODATTR_SKIRTS), as computed by the last lod_material_vertices /
+        lod_ao_vertices: an (n, 8) uint8 array of weights or n occlusion bytes."""
+        n = ctypes.c_int64()
+        self._check(self._L.vtmc_lodattr_device_results(self._h, int(attribute), int(target), None, ctypes.byref(n)))
+        out = np.empty((n.value, MATERIAL_CHANNELS) if attribute == _lib.LODATTR_MATERIAL else n.value, np.uint8)
+        self._check(self._L.vtmc_lodattr_read(self._h, int(attribute), int(target), _ptr(out) if n.value else None, n.value))
+        return out
+
+    def lod_vertex_materials(self):
+        """lod_material_vertices, then the weights of the mesh as an (n, 8) uint8 array: row 3 t + v for corner v of soup triangle t, or
+        one row per vtmc_vertex of the indexed mesh."""
+        self.lod_material_vertices()
+        return self.lodattr_read(_lib.LODATTR_MATERIAL, _lib.LODATTR_MESH)
+
+    def lod_vertex_ao(self, radius, strength=1.0, steps=4):
+        """lod_ao_vertices, then the bytes of the mesh (255 = open).  radius in world units, at most AO_MAX_RADIUS_CELLS cells; a node of
+        level L marches 2^L times as far in the world."""
+        self.lod_ao_vertices(AmbientOcclusion(radius, strength, steps))
+        return self.lodattr_read(_lib.LODATTR_AO, _lib.LODATTR_MESH)
+
+    def lod_skirt_materials(self):
+        """The weights of the 3 n corners of the skirt records, record order, as the last lod_material_vertices left them: every corner
+        carries the weights of the mesh vertex it came from."""
+        return self.lodattr_read(_lib.LODATTR_MATERIAL, _lib.LODATTR_SKIRTS)
+
+    def lod_skirt_ao(self):
+        """The occlusion bytes of the 3 n corners of the skirt records, as the last lod_ao_vertices left them."""
+        return self.lodattr_read(_lib.LODATTR_AO, _lib.LODATTR_SKIRTS)
+
+    def device_lod_attributes(self, attribute, target):
+        """(device address of the values, their number) of an attribute and target of the last compute call."""
+        p, n = ctypes.c_void_p(), ctypes.c_int64()
+        self._check(self._L.vtmc_lodattr_device_results(self._h, int(attribute), int(target), ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
     # -- ray picking: Physics.Raycast of the interactive edit (SceneManager.cs:114-131) on the device ---------------
     def terrain_raycast(self, origins, directions, max_distance=float("inf"), two_sided=False):
         """Nearest surface hit of each ray (world-space origins / directions, (n, 3)) on the resident terrain: a RAY_HIT_DTYPE
