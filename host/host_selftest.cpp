@@ -152,6 +152,7 @@ static int cpu_tests(const std::string &)
         NEEDS_RESIDENT("ReadCrowd", vt.ReadCrowd());
         NEEDS_RESIDENT("Flood", vt.Flood(lo, up, {WaterSource{lo, 1.0f}}));
         NEEDS_RESIDENT("ProbeWater", vt.ProbeWater({lo}));
+        NEEDS_RESIDENT("ReadErosion", vt.ReadErosion());
         NEEDS_RESIDENT("Fragments", vt.Fragments(lo, up));
         NEEDS_RESIDENT("ExtractLod", vt.ExtractLod(lo, 1));
         NEEDS_RESIDENT("DeviceSamples", vt.DeviceSamples());
@@ -160,6 +161,17 @@ static int cpu_tests(const std::string &)
         NEEDS_RESIDENT("the material layer", vt.VertexMaterials());
 #undef NEEDS_RESIDENT
         CHECK(rec->calls == 2);   // and none of them reached the backend
+        // the erosion mirror refuses what the library refuses, and describes itself as kind 12
+        CHECK(Refused<std::invalid_argument>([&] { ErosionModifier(lo, up, 0); }) && Refused<std::invalid_argument>([&] { ErosionModifier(lo, up, 65537); }));
+        CHECK(Refused<std::invalid_argument>([&] { ErosionModifier(lo, up, 8, NAN); }) && Refused<std::invalid_argument>([&] { ErosionModifier(lo, up, 8, -0.1f); }));
+        CHECK(Refused<std::invalid_argument>([&] { ErosionModifier(lo, up, 8, 0.01f, 8.0f, 1.0f, 0.3f, 0.3f, 0.25f); }));   // evaporation * dt > 1
+        CHECK(Refused<std::invalid_argument>([&] { ErosionModifier(lo, up, 8, 0.01f, 0.02f, 1.0f, 0.3f, 0.3f, 0.0f); }));   // dt = 0
+        CHECK(Refused<std::invalid_argument>([&] { ErosionModifier(lo, up, 8, 0.01f, 0.02f, 1.0f, 0.3f, 0.3f, 0.25f, 1.0f, 0.2f); }));   // thermal rate
+        ModifierDesc d;
+        const ErosionModifier erosion(lo, up, 40, 0.02f, 0.05f, 1.0f, 0.3f, 0.25f, 0.5f, 0.75f, 0.1f);
+        CHECK(erosion.Describe(d) && d.kind == 12 && d.dims[0] == 40 && d.dims[1] == 0 && d.data == nullptr);
+        CHECK(d.p[0] == 0.02f && d.p[1] == 0.05f && d.p[2] == 1.0f && d.p[3] == 0.3f && d.p[4] == 0.25f && d.p[5] == 0.5f && d.p[6] == 0.75f && d.p[7] == 0.1f);
+        CHECK(Refused<std::logic_error>([&] { erosion.QueryDensity(lo); }));
     }
     return 0;
 }
@@ -441,6 +453,41 @@ static int gpu_water_run(const std::string &out)
     return 0;
 }
 
+// An erosion of a box of that terrain in one Update with a dig before it; dumps the grid before and after, the box and the five maps
+static int gpu_erosion_run(const std::string &out)
+{
+    VoxelTerrain vt;
+    resident_world(vt);
+    Dump(out, "erosion_grid_before.f32", vt.DeviceSamples());
+    const Vector3 lower(-1.0f, -50.0f, 3.0f), upper(25.0f, 50.0f, 16.5f);
+    vt.InsertModifier(std::make_shared<ErosionModifier>(lower, upper, 24, 0.02f, 0.05f, 1.0f, 0.3f, 0.3f, 0.25f, 0.5f, 0.1f));
+    vt.Update();
+    const ErosionResult r = vt.ReadErosion();
+    const size_t n = (size_t)r._nx * (size_t)r._nz;
+    CHECK(n != 0 && r._iterations == 24 && r._nx == r._boxHi[0] - r._boxLo[0] + 1 && r._nz == r._boxHi[2] - r._boxLo[2] + 1);
+    CHECK(r._heightBefore.size() == n && r._heightAfter.size() == n && r._water.size() == n && r._sediment.size() == n && r._activeMask.size() == n);
+    int active = 0, rewritten = 0;
+    for (size_t i = 0; i < n; i++) {
+        active += r._activeMask[i] != 0;
+        rewritten += r._activeMask[i] && r._heightAfter[i] != r._heightBefore[i];
+        if (!r._activeMask[i]) CHECK(r._heightBefore[i] == 0.0f && r._heightAfter[i] == 0.0f && r._water[i] == 0.0f && r._sediment[i] == 0.0f);
+    }
+    CHECK(active == r._active && rewritten == r._rewritten && active > 0 && rewritten > 0 && r._clamped == 0);
+    CHECK(!vt.LastUpdateBlocks().empty() && vt.LastTriangleCount() > 0);
+    std::printf("erosion: %d x %d columns, %d active, %d rewritten\n", r._nx, r._nz, r._active, r._rewritten);
+    const int box[9] = {r._boxLo[0], r._boxLo[1], r._boxLo[2], r._boxHi[0], r._boxHi[1], r._boxHi[2], r._active, r._rewritten, r._clamped};
+    Dump(out, "erosion_box.i32", box, 9);
+    Dump(out, "erosion_grid_after.f32", vt.DeviceSamples());
+    Dump(out, "erosion_before.f32", r._heightBefore);
+    Dump(out, "erosion_after.f32", r._heightAfter);
+    Dump(out, "erosion_water.f32", r._water);
+    Dump(out, "erosion_sediment.f32", r._sediment);
+    Dump(out, "erosion_active.u8", r._activeMask);
+    vt.Free();
+    CHECK(Refused([&] { vt.ReadErosion(); }));
+    return 0;
+}
+
 // the field of --gpu-navfield; agents on every second span (those divisible by 7 ask for -1, and span 2 is asked for three times), 24 ticks
 // with any detour that leave on arrival, then a field of the second goal alone and 16 ticks within 1024
 static int gpu_navcrowd_run(const std::string &out)
@@ -563,6 +610,7 @@ static const struct Mode {
     {"--gpu-navsight", true, gpu_navsight_run, "HOST-NAVSIGHT-OK", "any-angle paths on that field; dumps the hits of a set of pairs and every span's smoothed path"},
     {"--gpu-navcrowd", true, gpu_navcrowd_run, "HOST-NAVCROWD-OK", "a crowd on that field; dumps agents, occupancy and counts after the spawn, 24 ticks and a re-route"},
     {"--gpu-water", true, gpu_water_run, "HOST-WATER-OK", "standing water on that terrain; dumps the bodies, both volumes and three probes of one flood"},
+    {"--gpu-erosion", true, gpu_erosion_run, "HOST-EROSION-OK", "an erosion of a box of that terrain; dumps the grid before and after, the box and the five maps"},
     {"--gpu-lodskirt", true, gpu_lodskirt_run, "HOST-LODSKIRT-OK", "the seams of that mixed-level mesh covered by skirts; dumps the per-node vertex counts"},
 };
 

@@ -12,6 +12,7 @@
 #include "../include/vtmc_navsight.h"
 #include "../include/vtmc_navcrowd.h"
 #include "../include/vtmc_water.h"
+#include "../include/vtmc_erosion.h"
 #include "../include/vtmc_lodskirt.h"
 
 namespace PGRTerrain {
@@ -466,6 +467,27 @@ std::vector<WaterProbe> VoxelTerrain::ProbeWater(const std::vector<Vector3> &pos
     VTMC_CHECK(c, vtmc_water_probe(c.ctx, Flatten(positions).data(), (int32_t)positions.size(), body.data(), depth.data()));
     std::vector<WaterProbe> out;
     for (size_t i = 0; i < positions.size(); i++) out.push_back(WaterProbe{body[i], depth[i]});
+    return out;
+}
+
+ErosionResult VoxelTerrain::ReadErosion()
+{
+    VtmcContext &c = RequireResident("ReadErosion");
+    vtmc_erosion_report r;
+    VTMC_CHECK(c, vtmc_erosion_info(c.ctx, &r));
+    ErosionResult out;
+    for (int k = 0; k < 3; k++) out._boxLo[k] = r.lo[k], out._boxHi[k] = r.hi[k];
+    out._nx = r.nx, out._nz = r.nz, out._iterations = r.iterations;
+    out._active = r.n_active, out._rewritten = r.n_rewritten, out._clamped = r.n_clamped;
+    const size_t n = (size_t)r.nx * (size_t)r.nz;
+    std::vector<float> *planes[4] = {&out._heightBefore, &out._heightAfter, &out._water, &out._sediment};
+    const int32_t maps[4] = {VTMC_EROSION_HEIGHT_BEFORE, VTMC_EROSION_HEIGHT_AFTER, VTMC_EROSION_WATER, VTMC_EROSION_SEDIMENT};
+    for (int k = 0; k < 4; k++) {
+        planes[k]->resize(n);
+        VTMC_CHECK(c, vtmc_erosion_read(c.ctx, maps[k], planes[k]->data(), (int64_t)(n * sizeof(float))));
+    }
+    out._activeMask.resize(n);
+    VTMC_CHECK(c, vtmc_erosion_read(c.ctx, VTMC_EROSION_ACTIVE, out._activeMask.data(), (int64_t)n));
     return out;
 }
 

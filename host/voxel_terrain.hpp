@@ -300,6 +300,55 @@ public:
     }
 };
 
+// New (not in the reference): hydraulic and thermal erosion of the heightfield of the box _lower.._upper (VTMC_MOD_EROSION of
+// include/vtmc_erosion.h, where the rule is), simulated on the device for _iterations steps.  Everything but the box is in grid units:
+// rain depth per unit time, evaporation, sediment capacity, dissolve and deposit in 0..1, dt in (0, 1], the talus (the largest stable
+// height step between neighbouring columns) and the thermal rate in 0..0.125 (0: thermal erosion off).  The constructor refuses what the
+// library refuses.  AddOrErode is ignored by the library.  Device-resident terrains only: QueryDensity throws.  The maps of the run are
+// read with VoxelTerrain::ReadErosion.
+class ErosionModifier : public TerrainModifier {
+public:
+    Vector3 _lower, _upper;
+    int _iterations;
+    float _rain, _evaporation, _capacity, _dissolve, _deposit, _dt, _talus, _thermalRate;
+    ErosionModifier(Vector3 lower, Vector3 upper, int iterations, float rain = 0.01f, float evaporation = 0.02f, float capacity = 1.0f, float dissolve = 0.3f,
+                    float deposit = 0.3f, float dt = 0.25f, float talus = 1.0f, float thermalRate = 0.0f)
+        : _lower(lower), _upper(upper), _iterations(iterations), _rain(rain), _evaporation(evaporation), _capacity(capacity), _dissolve(dissolve),
+          _deposit(deposit), _dt(dt), _talus(talus), _thermalRate(thermalRate)
+    {
+        const float p[8] = {rain, evaporation, capacity, dissolve, deposit, dt, talus, thermalRate};
+        bool ok = iterations >= 1 && iterations <= 65536;
+        for (float v : p) ok = ok && std::isfinite(v) && !(v < 0.0f);
+        ok = ok && rain <= 256.0f && capacity <= 65536.0f && dissolve <= 1.0f && deposit <= 1.0f && dt > 0.0f && dt <= 1.0f && thermalRate <= 0.125f &&
+             !(evaporation * dt > 1.0f);
+        if (!ok || std::isnan(lower.x) || std::isnan(lower.y) || std::isnan(lower.z) || std::isnan(upper.x) || std::isnan(upper.y) || std::isnan(upper.z))
+            throw std::invalid_argument("ErosionModifier: a parameter is not finite, negative or outside its range, or a bound is NaN");
+    }
+    Vector3 LowerBound() const override { return _lower; }
+    Vector3 UpperBound() const override { return _upper; }
+    float QueryDensity(const Vector3 &) const override { throw std::logic_error("ErosionModifier has no host density: it is simulated on the device"); }
+    bool Describe(ModifierDesc &d) const override
+    {
+        d.kind = 12;
+        const float p[8] = {_rain, _evaporation, _capacity, _dissolve, _deposit, _dt, _talus, _thermalRate};
+        for (int k = 0; k < 8; k++) d.p[k] = p[k];
+        d.dims[0] = _iterations;
+        d.dims[1] = 0;
+        return true;
+    }
+};
+
+// New (not in the reference): the maps of the last ErosionModifier, as VoxelTerrain::ReadErosion returns them (include/vtmc_erosion.h): the
+// clamped sample box, its _nx x _nz columns, and per column (x fastest) the height before and after in grid units, the water depth and the
+// suspended sediment left after the last step, and whether the column took part; every map holds 0 on a column that did not.
+struct ErosionResult {
+    int _boxLo[3] = {0, 0, 0}, _boxHi[3] = {0, 0, 0};
+    int _nx = 0, _nz = 0, _iterations = 0;
+    int _active = 0, _rewritten = 0, _clamped = 0;
+    std::vector<float> _heightBefore, _heightAfter, _water, _sediment;
+    std::vector<unsigned char> _activeMask;
+};
+
 // New (not in the reference): one floating fragment of VoxelTerrain::Fragments (vtmc_fragment of include/vtmc.h): the sample of smallest
 // grid index, the tight inclusive sample bounds, the solid sample count, and the id of the stamp it was captured into (0: none).
 struct Fragment {
@@ -557,6 +606,10 @@ public:
     // Init drops and an edit keeps.  ProbeWater asks that snapshot what a swimmer asks: the body and the depth at a position.
     WaterResult Flood(Vector3 lower, Vector3 upper, const std::vector<WaterSource> &sources);
     std::vector<WaterProbe> ProbeWater(const std::vector<Vector3> &positions);
+
+    // New: the maps the last ErosionModifier of an Update left (include/vtmc_erosion.h): a snapshot that an edit keeps and Init drops.
+    // What lets a host paint sand where _heightAfter - _heightBefore > 0, or pick Flood sources where water stands.
+    ErosionResult ReadErosion();
 
     // -- inspection (tests, callers that consume the meshes) ----------------------------------
     const BlockMesh &Block(int x, int y, int z) const { return _blocks[((size_t)x * (_elevation / blockSize) + y) * (_height / blockSize) + z]; }

@@ -15,7 +15,7 @@ from ._header import HEADER, LAYERS
 
 # every #define VTMC_<NAME> of every layer's header as <NAME>.  include/vtmc.h: OK and the ERR_* codes, FLAG_*, OUTPUT_*, MOD_*, TERRAIN_SAVE_EXACT,
 # TERRAIN_LOAD_NO_EXTRACT, MESH_*, MATERIAL_*, AO_*, SCATTER_*, LOD_MAX_LEVEL, RAY_TWO_SIDED, SPHERE_MAX_RADIUS_CELLS, COMM_ID_BYTES ...
-# The optional layers' headers: NAV_OPEN, NAVFIELD_UNIT, NAVERODE_MAX_RADIUS, NAVSIGHT_ANY_COST, NAVCROWD_ANY_DETOUR, WATER_AT_FACE, LODSKIRT_ALL_FACES, LODATTR_AO ...
+# The optional layers' headers: NAV_OPEN, NAVFIELD_UNIT, NAVERODE_MAX_RADIUS, NAVSIGHT_ANY_COST, NAVCROWD_ANY_DETOUR, WATER_AT_FACE, LODSKIRT_ALL_FACES, LODATTR_AO, MOD_EROSION, EROSION_G ...
 for _layer in LAYERS.values():
     globals().update((name[len("VTMC_"):], value) for name, value in _layer.constants.items())
 STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27   # vtmc_stamp_create: the limits of a stamp's dims (the header states them in prose)
@@ -56,6 +56,7 @@ NavErodeParamsStruct = LAYERS["naverode"].structure("vtmc_naverode_params", "Nav
 NavSightParamsStruct = LAYERS["navsight"].structure("vtmc_navsight_params", "NavSightParamsStruct", "vtmc_navsight_params: max_look 1..NAVSIGHT_MAX_LOOK, max_extra_cost or NAVSIGHT_ANY_COST, flags 0, reserved 0.")
 NavCrowdParamsStruct = LAYERS["navcrowd"].structure("vtmc_navcrowd_params", "NavCrowdParamsStruct", "vtmc_navcrowd_params: max_detour or NAVCROWD_ANY_DETOUR, flags NAVCROWD_LEAVE_ON_ARRIVAL or 0, two reserved words, 0.")
 LodSkirtParamsStruct = LAYERS["lodskirt"].structure("vtmc_lodskirt_params", "LodSkirtParamsStruct", "vtmc_lodskirt_params: depth in the node's own cells, in (0, LODSKIRT_MAX_DEPTH]; flags LODSKIRT_ALL_FACES or 0.")
+ErosionReport = LAYERS["erosion"].structure("vtmc_erosion_report", "ErosionReport", "vtmc_erosion_report: the clamped box lo..hi, nx, nz, iterations, and the active, rewritten and clamped column counts.")
 LodNode = HEADER.structure("vtmc_lod_node", "LodNode", "vtmc_lod_node: cell origin (multiples of 8 * 2^level) and level of one node of a level-of-detail extract.")
 VolumeBatch = HEADER.structure("vtmc_volume_batch", "VolumeBatch")
 ChunkView = HEADER.structure("vtmc_chunk_view", "ChunkView", "vtmc_chunk_view: device pointers into an uploaded chunk-file image.")
@@ -74,6 +75,9 @@ DEBUG_ARGTYPES = {   # entry points that are deliberately not in the header; all
     "vtmc_debug_navsight_ms": [_vp, _P(ctypes.c_float * 2)],        # device time of the last sight query's or smoothed trace's row fill and kernel
     "vtmc_debug_navcrowd_ms": [_vp, _P(ctypes.c_float * 1)],        # device time of the ticks of the last crowd step
     "vtmc_debug_water_ms": [_vp, _P(ctypes.c_float * 3)],           # device time of the last flood's levels, statistics and volume kernel
+    "vtmc_debug_erosion_lds": [_vp, _i32],                          # the step's variant of later erosions: 0 neighbour loads through the caches (the default), 1 staged in LDS
+    "vtmc_debug_erosion_ms": [_vp, _P(ctypes.c_float * 3)],         # device time of the last erosion's height pass, steps, and finish with write-back
+    "vtmc_debug_erosion_step_ms": [_vp, _i32, _i32, _P(ctypes.c_float)],   # device time of more steps on the last erosion's state: variant 0 direct, 1 LDS, 2 empty launches
     "vtmc_debug_lodskirt_ms": [_vp, _P(ctypes.c_float * 4)],        # device time of the last skirt pass's four kernels
     "vtmc_debug_lodskirt_store": [_vp, _i32],                       # the emit kernel's store variant of later skirt passes: 0 direct, 1 staged in LDS
     "vtmc_debug_lodskirt_read_ms": [_vp, _i32, _P(ctypes.c_float)],  # median device time of a plain read of the result's records

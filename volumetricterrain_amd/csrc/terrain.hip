@@ -285,6 +285,7 @@ static const ModifierKind kModifierKinds[] = {
     {VTMC_MOD_STAMP, check_stamp, apply_stamp},
     {VTMC_MOD_PATH, check_path, apply_path},
     {VTMC_MOD_DETACH, check_detach, apply_detach},
+    {VTMC_MOD_EROSION, check_erosion, apply_erosion},
 };
 
 const ModifierKind *find_modifier_kind(int32_t kind)
@@ -426,6 +427,7 @@ int32_t vtmc_terrain_init(vtmc_ctx *ctx, int32_t width, int32_t elevation, int32
     material_drop(ctx);
     nav_drop(ctx);
     water_drop(ctx);
+    erosion_drop(ctx);
     TerrainShape sh{};
     sh.dim_x = width + 2;
     sh.dim_y = elevation + 2;

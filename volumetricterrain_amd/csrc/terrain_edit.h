@@ -1,5 +1,5 @@
 // terrain_edit.h -- what terrain.hip (vtmc_terrain_update's queue walk and the table of modifier kinds) and the files of the kinds
-// (terrain_brush.hip, terrain_noise.hip, terrain_stamp.hip, terrain_path.hip, terrain_fragments.hip) need of each other.  Host side only.
+// (terrain_brush.hip, terrain_noise.hip, terrain_stamp.hip, terrain_path.hip, terrain_fragments.hip, terrain_erosion.hip) need of each other.  Host side only.
 #ifndef VTMC_TERRAIN_EDIT_H
 #define VTMC_TERRAIN_EDIT_H
 #include "terrain_box.h"
@@ -23,12 +23,14 @@ int check_noise(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i);
 int check_stamp(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i);
 int check_path(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i);
 int check_detach(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i);
+int check_erosion(vtmc_ctx *ctx, const vtmc_modifier &md, int32_t i);
 int apply_smooth(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &a, float *grid, float *image);
 int apply_flatten(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &a, float *grid, float *image);
 int apply_noise(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &a, float *grid, float *image);
 int apply_stamp(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &a, float *grid, float *image);
 int apply_path(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &a, float *grid, float *image);
 int apply_detach(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &a, float *grid, float *image);
+int apply_erosion(vtmc_ctx *ctx, const vtmc_modifier &md, const TerrainModifierArgs &a, float *grid, float *image);
 
 static TerrainBox box_of(const TerrainModifierArgs &m) { return TerrainBox{m.lx, m.ly, m.lz, m.dx, m.dy, m.dz}; }
 // terrain.hip: a modifier's kernel arguments: its AABB in sample indices, [low, up] clamped to the grid (up[] is also what the dirty blocks

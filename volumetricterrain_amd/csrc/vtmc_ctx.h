@@ -7,6 +7,7 @@
 #include "vtmc_internal.h"
 struct vtmc_nav_span;   // include/vtmc_nav.h
 #include "../../include/vtmc_water.h"
+#include "../../include/vtmc_erosion.h"
 
 #include <deque>
 #include <map>
@@ -190,6 +191,18 @@ struct VtmcWater {
     std::vector<vtmc_water_body> bodies;
 };
 
+// The maps of the last VTMC_MOD_EROSION (terrain_erosion.hip): library-owned, grow-only; a snapshot, kept by edits, undo and redo, dropped
+// by vtmc_terrain_init / _load, replaced by the next erosion.  state: the planes of the simulation, the mask bytes and the three counters
+// (terrain_erosion.h: ErosionLayout), in which the maps lie where the last step left them.  info: the host's copy of the report; its three
+// counts are fetched from the device by the first vtmc_erosion_info that asks (counts_pending).
+struct VtmcErosion {
+    VtmcDevBuf state;
+    bool valid = false, counts_pending = false;
+    bool has_state = false;   // the planes are those of info's nx x nz box, whether or not the maps still are a snapshot (vtmc_debug_erosion_step_ms)
+    bool lds = false;         // the step's variant (vtmc_debug_erosion_lds)
+    vtmc_erosion_report info{};
+};
+
 // The skirts over the seams of a level-of-detail result (terrain_lodskirt.hip): the records are vtmc_triangle, the blocks are nodes, a
 // mask byte holds a triangle's faces.  node_masks: the face masks of the nodes as the kernels read them, face_masks the host's copy of
 // those of the skirts held; sink: what vtmc_debug_lodskirt_read_ms's kernel leaves.  staged: the emit kernel's store variant
@@ -322,6 +335,9 @@ struct vtmc_ctx {
     // terrain_water.hip: the last flood, and the clock of its kernels (the levels' labelling, the statistics, the volume)
     VtmcWater water;
     vtmc::StageClock<4> water_clock;
+    // terrain_erosion.hip: the state and the maps of the last erosion
+    VtmcErosion erosion;
+    vtmc::StageClock<4> erosion_clock;   // around the height pass, the steps, and the finish with the write-back of the last erosion
     // terrain_lod.hip: the node list of the last level-of-detail result (host, and the copy the gather kernel reads), the packed
     // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the clock around
     // the gather launch of the last extract that succeeded (vtmc_debug_lod_gather_ms)
@@ -390,6 +406,7 @@ inline void nav_drop(vtmc_ctx *ctx) { ctx->nav.valid = false, ctx->navfield.vali
 // vtmc_lod_skirts replaces the skirts: what was computed for the corners of the previous ones names nothing any more
 inline void lodattr_drop_skirts(vtmc_ctx *ctx) { ctx->lodattr.values[0][1].epoch = 0, ctx->lodattr.values[1][1].epoch = 0; }
 inline void water_drop(vtmc_ctx *ctx) { ctx->water.valid = false; }   // vtmc_terrain_init / _load: the snapshot's grid is gone
+inline void erosion_drop(vtmc_ctx *ctx) { ctx->erosion.valid = false; }   // vtmc_terrain_init / _load: the snapshot's grid is gone
 int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp);   // sp then walks the (bx,by,bz) list
 int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, ResultSource source, int32_t *tri_count);   // queued on the context's stream and finished
 // The vertex attributes of a terrain result (terrain_material.hip, terrain_ao.hip), in vtmc_api.hip.  attr_gate: may `who` compute one for

@@ -726,6 +726,34 @@ class Extractor:
         origin, scale = self._terrain_placement
         return np.asarray(origin, np.float64) + (np.asarray(lo, np.float64) + 8.0 * b + p) * float(scale)
 
+    # -- erosion: the maps the last ErosionModifier left (include/vtmc_erosion.h) ---------------------------------------
+    EROSION_MAPS = {"height_before": _lib.EROSION_HEIGHT_BEFORE, "height_after": _lib.EROSION_HEIGHT_AFTER, "water": _lib.EROSION_WATER,
+                    "sediment": _lib.EROSION_SEDIMENT, "active": _lib.EROSION_ACTIVE}
+
+    def erosion_info(self):
+        """The report of the last erosion as a dict: lo, hi (the clamped sample box, inclusive), nx, nz, iterations, n_active, n_rewritten,
+        n_clamped.  Waits for the erosion if it is still running."""
+        r = _lib.ErosionReport()
+        self._check(self._L.vtmc_erosion_info(self._h, ctypes.byref(r)))
+        return {"lo": tuple(r.lo), "hi": tuple(r.hi), "nx": r.nx, "nz": r.nz, "iterations": r.iterations, "n_active": r.n_active,
+                "n_rewritten": r.n_rewritten, "n_clamped": r.n_clamped}
+
+    def erosion_read(self, name):
+        """One map of the last erosion, indexed [z, x] (x fastest in memory): "height_before", "height_after", "water", "sediment"
+        (float32) or "active" (uint8).  Every map holds 0 on an inactive column."""
+        if name not in self.EROSION_MAPS:
+            raise ValueError("erosion map must be one of %s" % ", ".join(self.EROSION_MAPS))
+        info = self.erosion_info()
+        out = np.empty((info["nz"], info["nx"]), np.uint8 if name == "active" else np.float32)
+        self._check(self._L.vtmc_erosion_read(self._h, self.EROSION_MAPS[name], _ptr(out), out.nbytes))
+        return out
+
+    def device_erosion(self):
+        """The device addresses of the five maps, by name; valid until the next erosion, terrain_init, terrain_load or close."""
+        p = [ctypes.c_void_p() for _ in range(5)]
+        self._check(self._L.vtmc_erosion_device_results(self._h, *[ctypes.byref(q) for q in p]))
+        return {name: p[i].value for name, i in self.EROSION_MAPS.items()}
+
     # -- material layer: VoxelTerrain.SetControlMap's splat volumes in HBM, paint, and per-vertex weights -------------
     def material_init(self, fineness):
         """The control volume of 16 * fineness texels per axis (fineness 1..8) over the resident terrain, every texel (255,0,0,0, 0,0,0,0).

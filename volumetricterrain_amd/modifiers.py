@@ -9,7 +9,7 @@ order of the C# expressions.
 import numpy as np
 
 from . import _lib
-from ._lib import (AO_MAX_STEPS, LOD_MAX_LEVEL, MATERIAL_CHANNELS, MESH_MAX_TRIANGLES, MOD_CYLINDER, MOD_DETACH, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP,
+from ._lib import (AO_MAX_STEPS, LOD_MAX_LEVEL, MATERIAL_CHANNELS, MESH_MAX_TRIANGLES, MOD_CYLINDER, MOD_DETACH, MOD_EROSION, MOD_FLATTEN, MOD_HEIGHTMAP, MOD_NOISE, MOD_PATH, MOD_PLANE, MOD_SMOOTH, MOD_SPHERE, MOD_STAMP,
                    PATH_MAX_SEGMENTS, STAMP_MAX_DIM, STAMP_MAX_SAMPLES, STAMP_MIN_DIM, Modifier)
 
 _f = np.float32
@@ -471,6 +471,68 @@ class DetachModifier(TerrainModifier):
 
     def attach(self, m):
         m.data_dims[:] = (self._max, 0)
+
+
+# -- erosion (include/vtmc_erosion.h VTMC_MOD_EROSION) -----------------------------------------------------------------------------------
+def erosion_fault(p, iterations):
+    """What csrc/terrain_erosion.h's erosion_args_fault says of the eight float32 parameters (rain, evaporation, capacity, dissolve,
+    deposit, dt, talus, thermal_rate) and the iteration count, in its words, or None."""
+    p = np.asarray(p, _f)
+    if not np.isfinite(p).all():
+        return "parameter not finite"
+    if (p < 0).any():
+        return "parameter negative"
+    if p[0] > _f(_lib.EROSION_MAX_RAIN):
+        return "rain above VTMC_EROSION_MAX_RAIN"
+    if p[2] > _f(_lib.EROSION_MAX_CAPACITY):
+        return "capacity above VTMC_EROSION_MAX_CAPACITY"
+    if p[3] > 1:
+        return "dissolve outside 0..1"
+    if p[4] > 1:
+        return "deposit outside 0..1"
+    if not p[5] > 0 or p[5] > 1:
+        return "dt outside (0, 1]"
+    if p[7] > _f(_lib.EROSION_MAX_THERMAL):
+        return "thermal rate above VTMC_EROSION_MAX_THERMAL"
+    if _f(p[1] * p[5]) > 1:
+        return "evaporation * dt above 1"
+    if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= iterations <= _lib.EROSION_MAX_ITERATIONS:
+        return "iterations outside 1..VTMC_EROSION_MAX_ITERATIONS"
+    return None
+
+
+class ErosionModifier(TerrainModifier):
+    """Hydraulic and thermal erosion of the heightfield of the box lower..upper (world bounds; None: the whole terrain), simulated on the
+    device for `iterations` steps by the rule EROSION of include/vtmc_erosion.h.  Everything but the box is in GRID units.  rain: depth per
+    unit time; evaporation; capacity: sediment a unit of speed and slope carries; dissolve, deposit in 0..1; dt in (0, 1]; talus: the
+    largest stable height step between neighbouring columns; thermal_rate in 0..EROSION_MAX_THERMAL, 0 turns the thermal part off.  The
+    checks are the library's (ValueError here, VTMC_ERR_INVALID_ARG there, the same words).  AddOrErode is ignored by the library.  The
+    maps of the run are read with Extractor.erosion_info / erosion_read / device_erosion."""
+    kind = MOD_EROSION
+
+    def __init__(self, lower, upper, iterations, rain=0.01, evaporation=0.02, capacity=1.0, dissolve=0.3, deposit=0.3, dt=0.25, talus=1.0,
+                 thermal_rate=0.0):
+        self._low, self._up = fragment_bounds(lower, upper)
+        with np.errstate(over="ignore"):
+            self._p = np.array([rain, evaporation, capacity, dissolve, deposit, dt, talus, thermal_rate], np.float64).astype(_f)
+        fault = erosion_fault(self._p, iterations)
+        if fault:
+            raise ValueError("erosion " + fault)
+        self._iterations = int(iterations)
+
+    @property
+    def LowerBound(self):
+        return self._low
+
+    @property
+    def UpperBound(self):
+        return self._up
+
+    def params(self):
+        return list(self._p)
+
+    def attach(self, m):
+        m.data_dims[:] = (self._iterations, 0)
 
 
 # -- navigation (include/vtmc_nav.h) ----------------------------------------------------------------------------------------------------
