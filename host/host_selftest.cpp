@@ -152,6 +152,8 @@ static int cpu_tests(const std::string &)
         NEEDS_RESIDENT("ReadCrowd", vt.ReadCrowd());
         NEEDS_RESIDENT("Flood", vt.Flood(lo, up, {WaterSource{lo, 1.0f}}));
         NEEDS_RESIDENT("ProbeWater", vt.ProbeWater({lo}));
+        NEEDS_RESIDENT("Light", vt.Light(lo, up, 255, 16, 16, {LightSource{lo, 1}}));
+        NEEDS_RESIDENT("ProbeLight", vt.ProbeLight({lo}));
         NEEDS_RESIDENT("ReadErosion", vt.ReadErosion());
         NEEDS_RESIDENT("Fragments", vt.Fragments(lo, up));
         NEEDS_RESIDENT("ExtractLod", vt.ExtractLod(lo, 1));
@@ -453,6 +455,39 @@ static int gpu_water_run(const std::string &out)
     return 0;
 }
 
+// Sky light and three torches -- one in the dug hollow, one in rock, one far outside -- in a box that cuts the world; dumps the volume, the
+// lit flags, the info and three probes
+static int gpu_light_run(const std::string &out)
+{
+    VoxelTerrain vt;
+    const int updateTriangles = resident_world(vt);
+    const Vector3 lower(-1.0f, 1.0f, 3.0f), upper(30.0f, 15.0f, 16.5f);
+    const std::vector<LightSource> torches = {LightSource{Vector3(5.0f, 4.5f, 9.0f), 200}, LightSource{Vector3(5.0f, 2.0f, 9.0f), 255}, LightSource{Vector3(500.0f, 6.0f, 10.0f), 90}};
+    const LightResult r = vt.Light(lower, upper, 240, 16, 12, torches);
+    CHECK(r._sourceLit.size() == 3 && r._sourceLit[0] == 1 && r._sourceLit[1] == 0 && r._sourceLit[2] == 0);
+    const size_t n = (size_t)r._boxDims[0] * r._boxDims[1] * r._boxDims[2];
+    CHECK(n != 0 && r._volume.size() == n && r._rounds >= 1 && r._rounds <= 256);
+    long long sky = 0, torch = 0;
+    int brightest = 0;
+    for (const LightSample &s : r._volume) sky += s._sky != 0, torch += s._torch != 0, brightest = s._torch > brightest ? s._torch : brightest;
+    CHECK(sky == r._skySamples && torch == r._torchSamples && sky > 0 && torch > 0 && brightest == 200);
+    const std::vector<LightSample> probes = vt.ProbeLight({Vector3(5.0f, 4.5f, 9.0f), Vector3(5.0f, 2.0f, 9.0f), Vector3(500.0f, 0.0f, 0.0f), Vector3(5.0f, 14.0f, 9.0f)});
+    CHECK(probes.size() == 4 && probes[0]._torch == 200 && probes[1]._sky == 0 && probes[1]._torch == 0 && probes[2]._sky == 0 && probes[2]._torch == 0 && probes[3]._sky == 240);
+    CHECK(vt.LastTriangleCount() == updateTriangles);
+    std::printf("light: sky %lld torch %lld rounds %d volume %d x %d x %d\n", r._skySamples, r._torchSamples, r._rounds, r._boxDims[0], r._boxDims[1], r._boxDims[2]);
+    static_assert(sizeof(LightSample) == 2, "dumped as it lies");
+    const std::vector<long long> info = {r._boxLo[0], r._boxLo[1], r._boxLo[2], r._boxDims[0], r._boxDims[1], r._boxDims[2], r._skySamples, r._torchSamples};
+    Dump(out, "light_volume.bin", r._volume);
+    Dump(out, "light_source_lit.u8", r._sourceLit);
+    Dump(out, "light_info.i64", info);
+    Dump(out, "light_probes.bin", probes);
+    // a level outside 1..255 refuses the call and keeps the result
+    CHECK(Refused([&] { vt.Light(lower, upper, 240, 16, 12, {LightSource{Vector3(5.0f, 4.5f, 9.0f), 256}}); }));
+    CHECK(Refused([&] { vt.Light(lower, upper, 240, 0, 12, {}); }));
+    CHECK(vt.ProbeLight({Vector3(5.0f, 4.5f, 9.0f)})[0]._torch == probes[0]._torch);
+    return 0;
+}
+
 // An erosion of a box of that terrain in one Update with a dig before it; dumps the grid before and after, the box and the five maps
 static int gpu_erosion_run(const std::string &out)
 {
@@ -610,6 +645,7 @@ static const struct Mode {
     {"--gpu-navsight", true, gpu_navsight_run, "HOST-NAVSIGHT-OK", "any-angle paths on that field; dumps the hits of a set of pairs and every span's smoothed path"},
     {"--gpu-navcrowd", true, gpu_navcrowd_run, "HOST-NAVCROWD-OK", "a crowd on that field; dumps agents, occupancy and counts after the spawn, 24 ticks and a re-route"},
     {"--gpu-water", true, gpu_water_run, "HOST-WATER-OK", "standing water on that terrain; dumps the bodies, both volumes and three probes of one flood"},
+    {"--gpu-light", true, gpu_light_run, "HOST-LIGHT-OK", "sky and torch light on that terrain; dumps the volume, the lit flags, the info and four probes of one light call"},
     {"--gpu-erosion", true, gpu_erosion_run, "HOST-EROSION-OK", "an erosion of a box of that terrain; dumps the grid before and after, the box and the five maps"},
     {"--gpu-lodskirt", true, gpu_lodskirt_run, "HOST-LODSKIRT-OK", "the seams of that mixed-level mesh covered by skirts; dumps the per-node vertex counts"},
 };

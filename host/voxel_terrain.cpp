@@ -12,6 +12,7 @@
 #include "../include/vtmc_navsight.h"
 #include "../include/vtmc_navcrowd.h"
 #include "../include/vtmc_water.h"
+#include "../include/vtmc_light.h"
 #include "../include/vtmc_erosion.h"
 #include "../include/vtmc_lodskirt.h"
 
@@ -467,6 +468,41 @@ std::vector<WaterProbe> VoxelTerrain::ProbeWater(const std::vector<Vector3> &pos
     VTMC_CHECK(c, vtmc_water_probe(c.ctx, Flatten(positions).data(), (int32_t)positions.size(), body.data(), depth.data()));
     std::vector<WaterProbe> out;
     for (size_t i = 0; i < positions.size(); i++) out.push_back(WaterProbe{body[i], depth[i]});
+    return out;
+}
+
+LightResult VoxelTerrain::Light(Vector3 lower, Vector3 upper, int skyLevel, int skyFalloff, int torchFalloff, const std::vector<LightSource> &sources)
+{
+    VtmcContext &c = RequireResident("Light");
+    static_assert(sizeof(LightSample) == sizeof(vtmc_light_sample), "copied as they lie");
+    float lo[3], up[3];
+    Put3(lo, lower), Put3(up, upper);
+    std::vector<vtmc_light_source> src(sources.size());
+    for (size_t i = 0; i < sources.size(); i++) {
+        Put3(src[i].position, sources[i]._position);
+        src[i].level = sources[i]._level;
+    }
+    const vtmc_light_params p = {skyLevel, skyFalloff, torchFalloff, 0u};
+    LightResult out;
+    out._sourceLit.assign(sources.size(), 0);
+    VTMC_CHECK(c, vtmc_terrain_light(c.ctx, lo, up, &p, src.data(), (int32_t)src.size(), out._sourceLit.data()));
+    int64_t nSky = 0, nTorch = 0;
+    int32_t rounds = 0;
+    VTMC_CHECK(c, vtmc_light_info(c.ctx, out._boxLo, out._boxDims, &nSky, &nTorch, &rounds));
+    out._skySamples = nSky, out._torchSamples = nTorch, out._rounds = rounds;
+    const size_t n = (size_t)out._boxDims[0] * out._boxDims[1] * out._boxDims[2];
+    out._volume.resize(n);
+    VTMC_CHECK(c, vtmc_light_read(c.ctx, reinterpret_cast<vtmc_light_sample *>(out._volume.data()), (int64_t)n));
+    return out;
+}
+
+std::vector<LightSample> VoxelTerrain::ProbeLight(const std::vector<Vector3> &positions)
+{
+    VtmcContext &c = RequireResident("ProbeLight");
+    std::vector<uint8_t> sky(positions.size(), 0), torch(positions.size(), 0);
+    VTMC_CHECK(c, vtmc_light_probe(c.ctx, Flatten(positions).data(), (int32_t)positions.size(), sky.data(), torch.data()));
+    std::vector<LightSample> out;
+    for (size_t i = 0; i < positions.size(); i++) out.push_back(LightSample{sky[i], torch[i]});
     return out;
 }
 

@@ -442,6 +442,25 @@ struct WaterProbe {
     float _depth;   // level - y, 0 when dry
 };
 
+// New (not in the reference): voxel lighting (include/vtmc_light.h, where the rule is).  A torch sits at _position (world space; its nearest
+// sample is the torch's) with _level 1..255; LightResult is what Light returns: per torch 1 (lit) or 0 (dark: outside the box or in
+// solid), the box, the counts of lit samples per channel, the rounds of the relaxation, and the volume (x fastest, _boxDims samples per
+// axis, no padding): two bytes per sample, sky and torch.
+struct LightSource {
+    Vector3 _position;
+    int _level;
+};
+struct LightSample {
+    unsigned char _sky, _torch;
+};
+struct LightResult {
+    std::vector<unsigned char> _sourceLit;
+    int _boxLo[3] = {0, 0, 0}, _boxDims[3] = {0, 0, 0};
+    long long _skySamples = 0, _torchSamples = 0;
+    int _rounds = 0;
+    std::vector<LightSample> _volume;
+};
+
 // New (not in the reference, which can only replace a control map whole): one paint stroke on the material layer (vtmc_material_stroke
 // of include/vtmc.h).  Every texel within _radius of _center (world space) is blended towards the one-hot of _channel (0..3: control map
 // 1's r, g, b, a; 4..7: control map 2's) by _strength * clamp01(2 (1 - d / _radius)).
@@ -606,6 +625,13 @@ public:
     // Init drops and an edit keeps.  ProbeWater asks that snapshot what a swimmer asks: the body and the depth at a position.
     WaterResult Flood(Vector3 lower, Vector3 upper, const std::vector<WaterSource> &sources);
     std::vector<WaterProbe> ProbeWater(const std::vector<Vector3> &positions);
+
+    // New: voxel lighting (include/vtmc_light.h, where the rule is).  Light floods sky light (skyLevel 0..255 from the top face of the box,
+    // 0: none) and the torches' light through the open samples of the box lower..upper (world bounds), each channel losing its falloff
+    // (1..255) per hop, on the device, and returns the volume; it changes nothing in the terrain and keeps a snapshot that Init drops and
+    // an edit keeps.  ProbeLight asks that snapshot for the two bytes at a position: (0, 0) outside the box.
+    LightResult Light(Vector3 lower, Vector3 upper, int skyLevel, int skyFalloff, int torchFalloff, const std::vector<LightSource> &sources);
+    std::vector<LightSample> ProbeLight(const std::vector<Vector3> &positions);
 
     // New: the maps the last ErosionModifier of an Update left (include/vtmc_erosion.h): a snapshot that an edit keeps and Init drops.
     // What lets a host paint sand where _heightAfter - _heightBefore > 0, or pick Flood sources where water stands.

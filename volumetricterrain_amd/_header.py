@@ -13,7 +13,7 @@ from . import build as _build
 PATH = os.path.join(_build.INCLUDE, _build.ABI_LAYERS[0][1])   # include/vtmc.h
 
 SCALARS = {"float": (ctypes.c_float, "<f4"), "int32_t": (ctypes.c_int32, "<i4"), "uint32_t": (ctypes.c_uint32, "<u4"),
-           "int64_t": (ctypes.c_int64, "<i8"), "uint64_t": (ctypes.c_uint64, "<u8")}
+           "int64_t": (ctypes.c_int64, "<i8"), "uint64_t": (ctypes.c_uint64, "<u8"), "uint8_t": (ctypes.c_uint8, "u1")}
 RETURNS = {"int32_t": ctypes.c_int32, "const char *": ctypes.c_char_p, "void": None}
 
 # name; return type and parameter declarations as written (one space between words); what ctypes is given

@@ -15,7 +15,7 @@ from ._header import HEADER, LAYERS
 
 # every #define VTMC_<NAME> of every layer's header as <NAME>.  include/vtmc.h: OK and the ERR_* codes, FLAG_*, OUTPUT_*, MOD_*, TERRAIN_SAVE_EXACT,
 # TERRAIN_LOAD_NO_EXTRACT, MESH_*, MATERIAL_*, AO_*, SCATTER_*, LOD_MAX_LEVEL, RAY_TWO_SIDED, SPHERE_MAX_RADIUS_CELLS, COMM_ID_BYTES ...
-# The optional layers' headers: NAV_OPEN, NAVFIELD_UNIT, NAVERODE_MAX_RADIUS, NAVSIGHT_ANY_COST, NAVCROWD_ANY_DETOUR, WATER_AT_FACE, LODSKIRT_ALL_FACES, LODATTR_AO, MOD_EROSION, EROSION_G ...
+# The optional layers' headers: NAV_OPEN, NAVFIELD_UNIT, NAVERODE_MAX_RADIUS, NAVSIGHT_ANY_COST, NAVCROWD_ANY_DETOUR, WATER_AT_FACE, LODSKIRT_ALL_FACES, LODATTR_AO, MOD_EROSION, EROSION_G, LIGHT_MAX_ROUNDS ...
 for _layer in LAYERS.values():
     globals().update((name[len("VTMC_"):], value) for name, value in _layer.constants.items())
 STAMP_MIN_DIM, STAMP_MAX_DIM, STAMP_MAX_SAMPLES = 2, 1026, 1 << 27   # vtmc_stamp_create: the limits of a stamp's dims (the header states them in prose)
@@ -38,6 +38,8 @@ NAVSIGHT_HIT_DTYPE = LAYERS["navsight"].dtype("vtmc_navsight_hit")     # one ans
 NAVCROWD_AGENT_DTYPE = LAYERS["navcrowd"].dtype("vtmc_navcrowd_agent")   # one agent of vtmc_navcrowd_spawn: span, budget, speed, state
 WATER_SOURCE_DTYPE = LAYERS["water"].dtype("vtmc_water_source")   # one source of vtmc_terrain_flood: world position and level
 WATER_BODY_DTYPE = LAYERS["water"].dtype("vtmc_water_body")       # one body of vtmc_water_bodies: seed, bounds, level, counts, flags
+LIGHT_SOURCE_DTYPE = LAYERS["light"].dtype("vtmc_light_source")   # one source of vtmc_terrain_light: world position and level 1..255
+LIGHT_SAMPLE_DTYPE = LAYERS["light"].dtype("vtmc_light_sample")   # one sample of the light volume, one vertex of vtmc_light_vertices: sky, torch
 
 Modifier = HEADER.structure("vtmc_modifier", "Modifier", """vtmc_modifier: one queued TerrainModifier (TerrainModifier.cs:19-33), bounds as the C#
     LowerBound / UpperBound properties return them.""")
@@ -57,6 +59,7 @@ NavSightParamsStruct = LAYERS["navsight"].structure("vtmc_navsight_params", "Nav
 NavCrowdParamsStruct = LAYERS["navcrowd"].structure("vtmc_navcrowd_params", "NavCrowdParamsStruct", "vtmc_navcrowd_params: max_detour or NAVCROWD_ANY_DETOUR, flags NAVCROWD_LEAVE_ON_ARRIVAL or 0, two reserved words, 0.")
 LodSkirtParamsStruct = LAYERS["lodskirt"].structure("vtmc_lodskirt_params", "LodSkirtParamsStruct", "vtmc_lodskirt_params: depth in the node's own cells, in (0, LODSKIRT_MAX_DEPTH]; flags LODSKIRT_ALL_FACES or 0.")
 ErosionReport = LAYERS["erosion"].structure("vtmc_erosion_report", "ErosionReport", "vtmc_erosion_report: the clamped box lo..hi, nx, nz, iterations, and the active, rewritten and clamped column counts.")
+LightParamsStruct = LAYERS["light"].structure("vtmc_light_params", "LightParamsStruct", "vtmc_light_params: sky_level 0..255, sky_falloff and torch_falloff 1..255, flags 0.")
 LodNode = HEADER.structure("vtmc_lod_node", "LodNode", "vtmc_lod_node: cell origin (multiples of 8 * 2^level) and level of one node of a level-of-detail extract.")
 VolumeBatch = HEADER.structure("vtmc_volume_batch", "VolumeBatch")
 ChunkView = HEADER.structure("vtmc_chunk_view", "ChunkView", "vtmc_chunk_view: device pointers into an uploaded chunk-file image.")
@@ -78,6 +81,8 @@ DEBUG_ARGTYPES = {   # entry points that are deliberately not in the header; all
     "vtmc_debug_erosion_lds": [_vp, _i32],                          # the step's variant of later erosions: 0 neighbour loads through the caches (the default), 1 staged in LDS
     "vtmc_debug_erosion_ms": [_vp, _P(ctypes.c_float * 3)],         # device time of the last erosion's height pass, steps, and finish with write-back
     "vtmc_debug_erosion_step_ms": [_vp, _i32, _i32, _P(ctypes.c_float)],   # device time of more steps on the last erosion's state: variant 0 direct, 1 LDS, 2 empty launches
+    "vtmc_debug_light_variant": [_vp, _i32, _i32],                  # the relaxation of later light calls: 0 tiled rounds (the default), 1 plain one-hop rounds, -1 as it is; rounds per read-back
+    "vtmc_debug_light_ms": [_vp, _P(ctypes.c_float * 3)],           # device time of the last light call's seeds, relaxation (with its read-backs) and count
     "vtmc_debug_lodskirt_ms": [_vp, _P(ctypes.c_float * 4)],        # device time of the last skirt pass's four kernels
     "vtmc_debug_lodskirt_store": [_vp, _i32],                       # the emit kernel's store variant of later skirt passes: 0 direct, 1 staged in LDS
     "vtmc_debug_lodskirt_read_ms": [_vp, _i32, _P(ctypes.c_float)],  # median device time of a plain read of the result's records

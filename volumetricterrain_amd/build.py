@@ -14,7 +14,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvtmc.so")
-SOURCES = ["context.hip", "vtmc_api.hip", "classify_kernels.hip", "emit_kernels.hip", "terrain.hip", "terrain_brush.hip", "terrain_noise.hip", "terrain_stamp.hip", "stamp_mesh.hip", "terrain_path.hip", "terrain_fragments.hip", "terrain_nav.hip", "terrain_navfield.hip", "terrain_naverode.hip", "terrain_navsight.hip", "terrain_navcrowd.hip", "terrain_water.hip", "terrain_erosion.hip", "terrain_material.hip", "terrain_ao.hip", "terrain_scatter.hip", "terrain_lod.hip", "terrain_lodskirt.hip", "terrain_lodattr.hip", "terrain_io.hip", "density.hip",
+SOURCES = ["context.hip", "vtmc_api.hip", "classify_kernels.hip", "emit_kernels.hip", "terrain.hip", "terrain_brush.hip", "terrain_noise.hip", "terrain_stamp.hip", "stamp_mesh.hip", "terrain_path.hip", "terrain_fragments.hip", "terrain_nav.hip", "terrain_navfield.hip", "terrain_naverode.hip", "terrain_navsight.hip", "terrain_navcrowd.hip", "terrain_water.hip", "terrain_erosion.hip", "terrain_light.hip", "terrain_material.hip", "terrain_ao.hip", "terrain_scatter.hip", "terrain_lod.hip", "terrain_lodskirt.hip", "terrain_lodattr.hip", "terrain_io.hip", "density.hip",
            "chunk_io.hip", "comm.hip", "raycast.hip", "spherequery.hip"]
 # The ABI's headers under include/, in order: (name, file, the name of the row whose file it includes or None, the document that holds its
 # [DllImport] stubs).  This is the one place a layer is registered: _header.py reads the files, _lib.py binds what they declare, and
@@ -30,6 +30,7 @@ ABI_LAYERS = (
     ("lodskirt", "vtmc_lodskirt.h", "core", "LODSEAMS.md"),
     ("lodattr", "vtmc_lodattr.h", "lodskirt", "LODSHADING.md"),
     ("erosion", "vtmc_erosion.h", "core", "EROSION.md"),
+    ("light", "vtmc_light.h", "core", "LIGHTING.md"),
 )
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "include"))
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(INCLUDE, row[1]) for row in ABI_LAYERS]   # for is_stale

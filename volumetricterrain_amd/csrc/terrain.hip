@@ -428,6 +428,7 @@ int32_t vtmc_terrain_init(vtmc_ctx *ctx, int32_t width, int32_t elevation, int32
     nav_drop(ctx);
     water_drop(ctx);
     erosion_drop(ctx);
+    light_drop(ctx);
     TerrainShape sh{};
     sh.dim_x = width + 2;
     sh.dim_y = elevation + 2;

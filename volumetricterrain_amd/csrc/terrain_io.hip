@@ -478,6 +478,7 @@ int32_t vtmc_terrain_load(vtmc_ctx *ctx, const char *path, uint32_t flags, int32
     nav_drop(ctx);
     water_drop(ctx);
     erosion_drop(ctx);
+    light_drop(ctx);
     ctx->dirty.clear();
     ctx->dirty_is_all = false;
     if (int rc = load_file(ctx, file.f, path, h, kinds)) return rc;

@@ -203,6 +203,25 @@ struct VtmcErosion {
     vtmc_erosion_report info{};
 };
 
+// The light result the context holds (terrain_light.hip): library-owned, grow-only; a snapshot of the grid at the time of the call, dropped
+// by vtmc_terrain_init / _load.  volume: the two volumes a round reads and writes in turn, equal once the relaxation has settled, [0]
+// the result; mask: the open mask, a 64-bit word per row of up to 64 samples along x; tiles: a changed byte per tile and round parity;
+// seeds: the sources of the call; lit: a byte per source; ctl: the changed word of every round, then the two counts; probe: the positions
+// and answers of vtmc_light_probe.  serial counts the light results, so the vertex bytes know which one they were read from.  plain,
+// batch: the relaxation's variant and the rounds queued between two read-backs (vtmc_debug_light_variant).
+struct VtmcLight {
+    VtmcDevBuf volume[2], mask, tiles, seeds, lit, ctl, probe;
+    bool valid = false;
+    int32_t lo[3] = {0, 0, 0}, d[3] = {0, 0, 0};
+    int64_t n_sky = 0, n_torch = 0;
+    int32_t rounds = 0;
+    uint64_t serial = 0;
+    bool plain = false;
+    int32_t batch = 4;
+    VertexAttr vertices;           // two bytes per vertex of the result vertices.epoch names ...
+    uint64_t vertices_serial = 0;  // ... read from the light result of this serial
+};
+
 // The skirts over the seams of a level-of-detail result (terrain_lodskirt.hip): the records are vtmc_triangle, the blocks are nodes, a
 // mask byte holds a triangle's faces.  node_masks: the face masks of the nodes as the kernels read them, face_masks the host's copy of
 // those of the skirts held; sink: what vtmc_debug_lodskirt_read_ms's kernel leaves.  staged: the emit kernel's store variant
@@ -338,6 +357,9 @@ struct vtmc_ctx {
     // terrain_erosion.hip: the state and the maps of the last erosion
     VtmcErosion erosion;
     vtmc::StageClock<4> erosion_clock;   // around the height pass, the steps, and the finish with the write-back of the last erosion
+    // terrain_light.hip: the last light result, and the clock of its kernels (the seed passes, the relaxation, the count)
+    VtmcLight light;
+    vtmc::StageClock<4> light_clock;
     // terrain_lod.hip: the node list of the last level-of-detail result (host, and the copy the gather kernel reads), the packed
     // tiles the kernel gathers (VTMC_TILE_SAMPLES floats per node: the BlockSpace of that result points into them), and the clock around
     // the gather launch of the last extract that succeeded (vtmc_debug_lod_gather_ms)
@@ -407,6 +429,7 @@ inline void nav_drop(vtmc_ctx *ctx) { ctx->nav.valid = false, ctx->navfield.vali
 inline void lodattr_drop_skirts(vtmc_ctx *ctx) { ctx->lodattr.values[0][1].epoch = 0, ctx->lodattr.values[1][1].epoch = 0; }
 inline void water_drop(vtmc_ctx *ctx) { ctx->water.valid = false; }   // vtmc_terrain_init / _load: the snapshot's grid is gone
 inline void erosion_drop(vtmc_ctx *ctx) { ctx->erosion.valid = false; }   // vtmc_terrain_init / _load: the snapshot's grid is gone
+inline void light_drop(vtmc_ctx *ctx) { ctx->light.valid = false; }       // vtmc_terrain_init / _load: the snapshot's grid is gone
 int upload_block_list(vtmc_ctx *ctx, const int32_t *xyz, int n, BlockSpace &sp);   // sp then walks the (bx,by,bz) list
 int extract_core(vtmc_ctx *ctx, const BlockSpace &sp, int n_volumes, ResultSource source, int32_t *tri_count);   // queued on the context's stream and finished
 // The vertex attributes of a terrain result (terrain_material.hip, terrain_ao.hip), in vtmc_api.hip.  attr_gate: may `who` compute one for

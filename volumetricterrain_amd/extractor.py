@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, NAVCROWD_AGENT_DTYPE, NAVFIELD_CELL_DTYPE, NAVFIELD_GOAL_DTYPE, NAVSIGHT_HIT_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, WATER_BODY_DTYPE, WATER_SOURCE_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
+from ._lib import COMM_ID_BYTES, FRAGMENT_DTYPE, INSTANCE_DTYPE, LIGHT_SAMPLE_DTYPE, LIGHT_SOURCE_DTYPE, MATERIAL_CHANNELS, MESH_TRUST_CLOSED, NAV_SPAN_DTYPE, NAVCROWD_AGENT_DTYPE, NAVFIELD_CELL_DTYPE, NAVFIELD_GOAL_DTYPE, NAVSIGHT_HIT_DTYPE, RAY_HIT_DTYPE, RAY_TWO_SIDED, SPHERE_HIT_DTYPE, TRI_DTYPE, VERTEX_DTYPE, WATER_BODY_DTYPE, WATER_SOURCE_DTYPE, ChunkView, DensityParams, Modifier, VolumeBatch, VtmcError
 from .modifiers import AmbientOcclusion, LodParams, LodSkirtParams, NavErodeParams, NavParams, ScatterParams, fragment_bounds, fragment_count, mesh_stamp_args
 
 
@@ -725,6 +725,76 @@ class Extractor:
             b = b[:, None, :]
         origin, scale = self._terrain_placement
         return np.asarray(origin, np.float64) + (np.asarray(lo, np.float64) + 8.0 * b + p) * float(scale)
+
+    # -- voxel lighting: sky and torch light flooded through the open samples of a box (include/vtmc_light.h) ------------
+    def terrain_light(self, params, sources=(), lower=None, upper=None):
+        """Lights the box lower..upper (world bounds; None: the whole terrain) by the rule LIGHT for a LightParams (or a vtmc_light_params
+        struct).  `sources`: a LIGHT_SOURCE_DTYPE array or rows of (x, y, z, level) in world space, level 1..255.  Returns source_lit: per
+        source 1 (lit) or 0 (dark: outside the box or in solid).  Changes nothing in the terrain; the result is a snapshot, read with
+        light_info / light_read / light_probe / vertex_light."""
+        lo, up = fragment_bounds(lower, upper)
+        src = np.asarray(sources)
+        if src.dtype != LIGHT_SOURCE_DTYPE:
+            rows = np.asarray(sources, np.float64).reshape(-1, 4)
+            src = np.zeros(len(rows), LIGHT_SOURCE_DTYPE)
+            src["position"], src["level"] = rows[:, :3], rows[:, 3]
+        src = np.ascontiguousarray(src)
+        p = _struct(params)
+        lo_c, up_c = (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*up)
+        lit = np.zeros(len(src), np.uint8)
+        self._check(self._L.vtmc_terrain_light(self._h, ctypes.byref(lo_c), ctypes.byref(up_c), ctypes.byref(p), _ptr(src) if len(src) else None, len(src),
+                                               _ptr(lit) if len(src) else None))
+        return lit
+
+    def light_info(self):
+        """(box_lo, box_dims, samples with sky > 0, samples with torch > 0, rounds of the relaxation) of the light result the context holds."""
+        lo, d, n_sky, n_torch, rounds = (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        self._check(self._L.vtmc_light_info(self._h, ctypes.byref(lo), ctypes.byref(d), ctypes.byref(n_sky), ctypes.byref(n_torch), ctypes.byref(rounds)))
+        return tuple(lo), tuple(d), n_sky.value, n_torch.value, rounds.value
+
+    def light_read(self):
+        """The light volume, a LIGHT_SAMPLE_DTYPE array (fields sky, torch) indexed [x, y, z] with the box's dims (x fastest in memory)."""
+        d = self.light_info()[1]
+        out = np.zeros((d[2], d[1], d[0]), LIGHT_SAMPLE_DTYPE)
+        self._check(self._L.vtmc_light_read(self._h, _ptr(out) if out.size else None, d[0] * d[1] * d[2]))
+        return out.transpose(2, 1, 0)
+
+    def device_light(self):
+        """(device address of the light volume or None, box dims) of the light result; valid until the next terrain_light, terrain_init,
+        terrain_load or close."""
+        p, d = ctypes.c_void_p(), (ctypes.c_int32 * 3)()
+        self._check(self._L.vtmc_light_device_results(self._h, ctypes.byref(p), ctypes.byref(d)))
+        return p.value, tuple(d)
+
+    def light_probe(self, positions):
+        """(sky, torch), uint8 each, of world positions (n, 3): the two bytes of the nearest sample when it lies in the light box, else
+        (0, 0).  What something that moves asks."""
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        sky, torch = np.zeros(len(p), np.uint8), np.zeros(len(p), np.uint8)
+        self._check(self._L.vtmc_light_probe(self._h, _ptr(p) if len(p) else None, len(p), _ptr(sky), _ptr(torch)))
+        return sky, torch
+
+    def light_vertices(self):
+        """Computes the two light bytes of every vertex of the result the context holds (from terrain_update / undo / redo / load) from
+        the light result the context holds and leaves them on the device.  Returns their number: 3 T (soup) or V (indexed)."""
+        n = ctypes.c_int64()
+        self._check(self._L.vtmc_light_vertices(self._h, ctypes.byref(n)))
+        return n.value
+
+    def vertex_light(self):
+        """light_vertices, then the bytes as a LIGHT_SAMPLE_DTYPE array: entry 3 t + v for corner v of soup triangle t, or one per
+        vtmc_vertex of the indexed mesh."""
+        n = self.light_vertices()
+        out = np.zeros(n, LIGHT_SAMPLE_DTYPE)
+        self._check(self._L.vtmc_light_read_vertices(self._h, _ptr(out) if n else None, n))
+        return out
+
+    def device_vertex_light(self):
+        """(device address of the vertex light bytes, their number) of the last light_vertices; stale (VtmcError, ERR_NO_RESULT) after the
+        next extract and after the next terrain_light."""
+        p, n = ctypes.c_void_p(), ctypes.c_int64()
+        self._check(self._L.vtmc_light_vertices_device_results(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
 
     # -- erosion: the maps the last ErosionModifier left (include/vtmc_erosion.h) ---------------------------------------
     EROSION_MAPS = {"height_before": _lib.EROSION_HEIGHT_BEFORE, "height_after": _lib.EROSION_HEIGHT_AFTER, "water": _lib.EROSION_WATER,

@@ -644,6 +644,22 @@ class NavFieldParams:
         return s
 
 
+class LightParams:
+    """The parameters of Extractor.terrain_light (vtmc_light_params): the level the open sky emits (0..255; 0: no sky light) and what each
+    channel loses per hop through the open samples (1..255)."""
+
+    def __init__(self, sky_level=255, sky_falloff=16, torch_falloff=16):
+        for name, v, lowest in (("sky_level", sky_level, 0), ("sky_falloff", sky_falloff, 1), ("torch_falloff", torch_falloff, 1)):
+            if isinstance(v, bool) or int(v) != v or not lowest <= v <= 255:
+                raise ValueError("light %s must be an integer in %d..255" % (name, lowest))
+        self._sky, self._sky_falloff, self._torch_falloff = int(sky_level), int(sky_falloff), int(torch_falloff)
+
+    def to_struct(self):
+        s = _lib.LightParamsStruct()
+        s.sky_level, s.sky_falloff, s.torch_falloff, s.flags = self._sky, self._sky_falloff, self._torch_falloff, 0
+        return s
+
+
 # -- mesh stamps (include/vtmc.h vtmc_stamp_from_mesh) ------------------------------------------------------------------------------------
 MESH_MAX_COORDINATE = 2.0 ** 20
 
