@@ -41,80 +41,163 @@ class State:
         self.d, self.s, self.f = zero.copy(), zero.copy(), [zero.copy() for _ in range(4)]
 
 
-def step(st, p):
+# -- the operations a test may swap for a near neighbour (test_terrain_erosion_edges.py, "mutants"): as they stand they are the rule's ------
+def result(a):
+    """Every FP32 result of a step passes through here, unchanged: IEEE keeps subnormals."""
+    return a
+
+
+def keep_of(t, ke, dt):
+    """1 - Ke * dt: two operations."""
+    return t(t(1) - t(ke * dt))
+
+
+def dt_g_of(t, dt):
+    """dt * G, G rounded to the step's type first."""
+    return t(dt * t(G))
+
+
+def inv_dt_of(t, dt, given_dt):
+    """1 / dt of the ROUNDED dt; given_dt is the parameter as the caller wrote it."""
+    return t(t(1) / dt)
+
+
+def quotient(a, b):
+    """Speed: wx / db."""
+    return a / b
+
+
+def fraction_of(f, dt, d1):
+    """Transport: (f' * dt) / d1."""
+    return result(result(f * dt) / d1)
+
+
+def lesser(a, b):
+    """min(a, b) = a < b ? a : b"""
+    return np.where(a < b, a, b)
+
+
+def greater(a, b):
+    """max(a, b) = a > b ? a : b"""
+    return np.where(a > b, a, b)
+
+
+CENSUS_KEYS = ("flux_zeroed", "scaled", "not_scaled", "d2_clipped", "deep", "shallow", "sp_capped", "sa_raised", "takes", "deposits", "e_limited",
+               "transport_dry", "thermal_moves", "sign_minus", "sign_plus", "sign_zero", "subnormal_b", "subnormal_d", "subnormal_s",
+               "subnormal_f", "negative_s", "not_finite")
+
+
+def new_census():
+    return dict.fromkeys(CENSUS_KEYS, 0)
+
+
+def subnormals(a):
+    tiny = np.finfo(a.dtype).tiny
+    return int(((a != 0) & (np.abs(a) < tiny)).sum())
+
+
+def step(st, p, census=None):
+    """One step of the rule on st.  census: a dict (new_census()) to which the step adds, per branch of the rule, the number of active
+    columns that took it -- for a branch taken per direction (flux_zeroed, thermal_moves, sign_*) the number of column-directions whose
+    neighbour counts -- and the number of subnormal values b, d, s and f hold after the step, of negative s, and of values of the state
+    that are not finite.  It changes no bit."""
     t, act, cnt = st.t, st.active, st.counts
+    R = result
     zero = np.zeros(act.shape, t)
     dt, kr, ke, kc, ks, kd, talus, kt = t(p.dt), t(p.rain), t(p.evaporation), t(p.capacity), t(p.dissolve), t(p.deposit), t(p.talus), t(p.thermal_rate)
-    dt_rain, dt_g, inv_dt = t(dt * kr), t(dt * t(G)), t(t(1) / dt)
-    keep = t(t(1) - t(ke * dt))
+    dt_rain, dt_g, inv_dt = R(t(dt * kr)), R(dt_g_of(t, dt)), R(inv_dt_of(t, dt, p.dt))
+    keep = R(keep_of(t, ke, dt))
     half, eps, sin_min = t(0.5), t(DEPTH_EPS), t(SIN_MIN)
     b, d, s = st.b, st.d, st.s
+    note = {} if census is not None else None
     with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
         # flux
-        d1 = d + dt_rain
-        H = b + d1
-        f = []
+        d1 = R(d + dt_rain)
+        H = R(b + d1)
+        f, dropped = [], 0
         for k in range(4):
-            g = st.f[k] + dt_g * (H - neighbour(H, k))
+            g = R(st.f[k] + R(dt_g * R(H - neighbour(H, k))))
             f.append(np.where(cnt[k] & (g > 0), g, zero))
-        out = sum4(f)
-        vol = out * dt
+            if note is not None:
+                dropped += int((cnt[k] & ~(g > 0)).sum())
+        out = R(sum4r(f))
+        vol = R(out * dt)
         scale = vol > d1
-        K = d1 / vol
-        f = [np.where(scale, f[k] * K, f[k]) for k in range(4)]
-        out = sum4(f)
+        K = R(d1 / vol)
+        f = [np.where(scale, R(f[k] * K), f[k]) for k in range(4)]
+        out = sum4r(f)
         # water and speed
         fin = [np.where(cnt[k], neighbour(f[k ^ 1], k), zero) for k in range(4)]
-        inn = sum4(fin)
-        d2 = d1 + dt * (inn - out)
-        d2 = np.where(d2 > 0, d2, zero)
-        wx = ((fin[0] - f[0]) + (f[1] - fin[1])) * half
-        wz = ((fin[2] - f[2]) + (f[3] - fin[3])) * half
-        db = (d1 + d2) * half
+        inn = sum4r(fin)
+        d2 = R(d1 + R(dt * R(inn - out)))
+        wet = d2 > 0
+        d2 = np.where(wet, d2, zero)
+        wx = R(R(R(fin[0] - f[0]) + R(f[1] - fin[1])) * half)
+        wz = R(R(R(fin[2] - f[2]) + R(f[3] - fin[3])) * half)
+        db = R(R(d1 + d2) * half)
         deep = db > eps
-        u = np.where(deep, wx / db, zero)
-        w = np.where(deep, wz / db, zero)
-        sp = np.sqrt(u * u + w * w)
-        sp = np.where(sp < inv_dt, sp, inv_dt)
+        u = np.where(deep, R(quotient(wx, db)), zero)
+        w = np.where(deep, R(quotient(wz, db)), zero)
+        sp_free = R(np.sqrt(R(R(u * u) + R(w * w))))
+        sp = lesser(sp_free, inv_dt)
         # erosion and deposition
         bn = [np.where(cnt[k], neighbour(b, k), b) for k in range(4)]
-        gx = (bn[1] - bn[0]) * half
-        gz = (bn[3] - bn[2]) * half
-        g2 = gx * gx + gz * gz
-        sa = np.sqrt(g2 / (t(1) + g2))
-        sa = np.where(sa > sin_min, sa, sin_min)
-        C = kc * sa * sp
+        gx = R(R(bn[1] - bn[0]) * half)
+        gz = R(R(bn[3] - bn[2]) * half)
+        g2 = R(R(gx * gx) + R(gz * gz))
+        sa_free = R(np.sqrt(R(g2 / R(t(1) + g2))))
+        sa = greater(sa_free, sin_min)
+        C = R(R(kc * sa) * sp)
         take = C > s
-        e = ks * (C - s)
-        e = np.where(e < d2, e, d2)
-        q = kd * (s - C)
-        b1 = np.where(take, b - e, b + q)
-        s1 = np.where(take, s + e, s - q)
+        e_free = R(ks * R(C - s))
+        e = lesser(e_free, d2)
+        q = R(kd * R(s - C))
+        b1 = np.where(take, R(b - e), R(b + q))
+        s1 = np.where(take, R(s + e), R(s - q))
         # transport
-        give = [s1 * np.where(d1 > 0, (f[k] * dt) / d1, zero) for k in range(4)]
+        rained = d1 > 0
+        give = [R(s1 * np.where(rained, fraction_of(f[k], dt, d1), zero)) for k in range(4)]
         gin = [np.where(cnt[k], neighbour(give[k ^ 1], k), zero) for k in range(4)]
-        s2 = (s1 - sum4(give)) + sum4(gin)
+        s2 = R(R(s1 - sum4r(give)) + sum4r(gin))
         # evaporation
-        d3 = d2 * keep
+        d3 = R(d2 * keep)
         # thermal
-        th = []
+        th, moves, signs = [], 0, [0, 0, 0]
         for k in range(4):
             b1n = neighbour(b1, k)
-            hi, lo = np.where(b1 > b1n, b1, b1n), np.where(b1 < b1n, b1, b1n)
-            m = kt * ((hi - lo) - talus)
+            hi, lo = greater(b1, b1n), lesser(b1, b1n)
+            m = R(kt * R(R(hi - lo) - talus))
             m = np.where(cnt[k] & (m > 0), m, zero)
             sign = np.where(b1 > b1n, t(-1), np.where(b1 < b1n, t(1), t(0)))
-            th.append(sign * m)
-        b2 = b1 + sum4(th)
+            th.append(R(sign * m))
+            if note is not None:
+                moves += int((m > 0).sum())
+                for i, v in enumerate((-1, 1, 0)):
+                    signs[i] += int((cnt[k] & (sign == v)).sum())
+        b2 = R(b1 + sum4r(th))
     st.b, st.d, st.s = np.where(act, b2, zero), np.where(act, d3, zero), np.where(act, s2, zero)
     st.f = [np.where(act, f[k], zero) for k in range(4)]
+    if census is not None:
+        n = lambda flag: int((act & flag).sum())   # noqa: E731
+        for key, v in (("flux_zeroed", dropped), ("scaled", n(scale)), ("not_scaled", n(~scale)), ("d2_clipped", n(~wet)), ("deep", n(deep)),
+                       ("shallow", n(~deep)), ("sp_capped", n(~(sp_free < inv_dt))), ("sa_raised", n(~(sa_free > sin_min))), ("takes", n(take)),
+                       ("deposits", n(~take)), ("e_limited", n(take & ~(e_free < d2))), ("transport_dry", n(~rained)), ("thermal_moves", moves),
+                       ("sign_minus", signs[0]), ("sign_plus", signs[1]), ("sign_zero", signs[2]), ("subnormal_b", subnormals(st.b)),
+                       ("subnormal_d", subnormals(st.d)), ("subnormal_s", subnormals(st.s)), ("subnormal_f", sum(subnormals(a) for a in st.f)),
+                       ("negative_s", int((st.s < 0).sum())), ("not_finite", sum(int((~np.isfinite(a)).sum()) for a in (st.b, st.d, st.s, *st.f)))):
+            census[key] = census.get(key, 0) + v
     return st
 
 
-def simulate(h0, active, iterations, params=DEFAULT, dtype=np.float32):
+def sum4r(v):
+    """sum4 with each of its three results passed through result()."""
+    return result(result(v[0] + v[1]) + result(v[2] + v[3]))
+
+
+def simulate(h0, active, iterations, params=DEFAULT, dtype=np.float32, census=None):
     st = State(h0, active, dtype)
     for _ in range(iterations):
-        step(st, params)
+        step(st, params, census)
     return st
 
 
@@ -161,10 +244,10 @@ def write_back(grid, lo, hi, h0, h1, active):
     return out
 
 
-def erode(grid, lo, hi, iterations, params=DEFAULT):
+def erode(grid, lo, hi, iterations, params=DEFAULT, census=None):
     """VTMC_MOD_EROSION on the inclusive, already clamped sample box lo..hi of grid[x, y, z]: the new grid, the five maps and the report."""
     h0, active = heights(grid, lo, hi)
-    st = simulate(h0, active, iterations, params)
+    st = simulate(h0, active, iterations, params, census=census)
     h1, clamped = clamp_heights(st.b, active, lo[1], hi[1])
     info = {"lo": tuple(lo), "hi": tuple(hi), "nx": hi[0] - lo[0] + 1, "nz": hi[2] - lo[2] + 1, "iterations": iterations,
             "n_active": int(active.sum()), "n_rewritten": int((active & (h1 != h0)).sum()), "n_clamped": int(clamped.sum())}

@@ -15,13 +15,12 @@ import volumetricterrain_amd as vt
 from volumetricterrain_amd import _header, _lib, modifiers
 from volumetricterrain_amd import terrainfile as tf
 import erosion_twin as twin
+from erosion_support import DIMS, MAPS, NX, NZ, ORIGIN, P, SCALE, SEED, WHOLE, World, craft_grid, dirty_ids, erode_and_compare, erosion, plane, world_of
 from host_check import run_host_check
-from terrain_twin import bits, block_list, dirty_ids, invalid, no_result
+from terrain_twin import bits, block_list, invalid, no_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-P = twin.Params(rain=0.02, evaporation=0.05, capacity=1.0, dissolve=0.3, deposit=0.3, dt=0.25, talus=0.5, thermal_rate=0.1)
-MAPS = ("height_before", "height_after", "water", "sediment", "active")
 
 
 # -- CPU: the header, the binding, the mirror, the documents, the host half ----------------------------------------------------------------
@@ -118,20 +117,7 @@ def test_library_exports_the_entry_points_and_refuses_null():
     assert L.vtmc_debug_erosion_lds(None, 0) == L.vtmc_debug_erosion_ms(None, None) == L.vtmc_debug_erosion_step_ms(None, 0, 1, None) == _lib.ERR_INVALID_ARG
 
 
-# -- CPU: the twin against the rule's promises ---------------------------------------------------------------------------------------------
-NZ, NX = 45, 70
-
-
-def plane(seed=3):
-    """A 70 x 45 heightfield with a 3 x 2 block of inactive columns: rolling ground on a ramp, roughened."""
-    rng = np.random.default_rng(seed)
-    z, x = np.mgrid[0:NZ, 0:NX]
-    h = 20 + 6 * np.sin(x * 0.23) * np.cos(z * 0.31) + 0.1 * x + 2 * rng.random((NZ, NX))
-    active = np.ones((NZ, NX), bool)
-    active[20:22, 30:33] = False
-    return h.astype(f32), active
-
-
+# -- CPU: the twin against the rule's promises (the plane and craft_grid: erosion_support.py) -----------------------------------------------
 def test_twin_stays_finite_and_moves_material():
     h, active = plane()
     st = twin.simulate(h, active, 400, P)
@@ -191,16 +177,6 @@ def test_twin_thermal_steps_never_steepen_the_steepest_step():
     assert last < first / 2 and (st.d == 0).all() and (st.s == 0).all()
 
 
-def craft_grid(h, active, ny=40):
-    """grid[x, y, z] whose Heights are (h, active): the flatten profile around h; inactive columns alternately solid throughout and open."""
-    nz, nx = h.shape
-    y = np.arange(ny, dtype=f32)[None, :, None]
-    g = np.clip(h.T[:, None, :] - y, f32(-1), f32(1)).astype(f32)
-    ix, iz = np.nonzero(~active.T)
-    g[ix, :, iz] = np.where((ix + iz) % 2 == 0, f32(0.75), f32(-0.75))[:, None]
-    return g
-
-
 def test_twin_write_back_reads_back_exactly():
     h, active = plane()
     lo, hi = (0, 0, 0), (NX - 1, 39, NZ - 1)
@@ -223,64 +199,7 @@ def test_twin_write_back_reads_back_exactly():
 
 
 # -- GPU ----------------------------------------------------------------------------------------------------------------------------------
-DIMS, SCALE, ORIGIN, SEED = (80, 32, 48), 0.5, (-3.0, 1.0, 2.0), 2024
-TOP = tuple(d + 1 for d in DIMS)
-WHOLE = ((0, 0, 0), TOP)
-
-
-def world_of(index):
-    """The world position of a sample index: exact at this scale and origin, so a box given in samples comes back from the library's
-    floor and ceil as it went in."""
-    return tuple(ORIGIN[k] + SCALE * index[k] for k in range(3))
-
-
-def build_mods():
-    """Noise over a plane, a pillar that leaves through the top of the grid and a shaft that is open all the way down."""
-    return [vt.PlaneModifier(world_of((0, 10, 0))[1], (-100.0, -100.0), (100.0, 100.0)).to_struct(),
-            vt.NoiseModifier(11, 4, 0.09, amplitude=4.0, ramp_scale=1.0, ramp_center=world_of((0, 15, 0))[1], lower=(-100,) * 3, upper=(100,) * 3).to_struct(),
-            vt.CylinderModifier((world_of((30, 0, 20))[0], -10.0, world_of((30, 0, 20))[2]), (0.0, 1.0, 0.0), 60.0, 1.6).to_struct(),
-            vt.CylinderModifier((world_of((55, 0, 30))[0], -10.0, world_of((55, 0, 30))[2]), (0.0, 1.0, 0.0), 60.0, 1.3, addOrErode=False).to_struct()]
-
-
-class World:
-    def __init__(self, history=0):
-        self.ex = vt.Extractor(0)
-        self.ex.terrain_init(*DIMS, SCALE, ORIGIN, SEED)
-        self.ex.terrain_update(build_mods())
-        if history:
-            self.ex.terrain_set_history(history)
-
-    def __enter__(self):
-        return self.ex
-
-    def __exit__(self, *exc):
-        self.ex.close()
-
-
-def erosion(lo, hi, iterations, params=P):
-    return vt.ErosionModifier(world_of(lo), world_of(hi), iterations, **params._asdict()).to_struct()
-
-
-def same_maps(ex, want):
-    assert ex.erosion_info() == want.info
-    for name in MAPS:
-        got, ref = ex.erosion_read(name), getattr(want, name.replace("height_", ""))
-        assert got.shape == ref.shape and got.dtype == ref.dtype, name
-        assert got.tobytes() == np.ascontiguousarray(ref).tobytes(), (name, int((got != ref).sum()))
-
-
-def erode_and_compare(ex, lo, hi, iterations, params=P):
-    before = ex.terrain_read_samples()
-    want = twin.erode(before, lo, hi, iterations, params)
-    n_dirty, _ = ex.terrain_update([erosion(lo, hi, iterations, params)])
-    same_maps(ex, want)
-    got = ex.terrain_read_samples()
-    assert np.array_equal(bits(got), bits(want.grid)), int((bits(got) != bits(want.grid)).sum())
-    nb = tuple(d // 8 for d in DIMS)
-    assert np.array_equal(ex.terrain_dirty_blocks(), block_list(dirty_ids(lo, hi, nb), nb)) and n_dirty == len(ex.terrain_dirty_blocks())
-    return before, want
-
-
+# the noise world, its boxes and the comparison with the twin: erosion_support.py
 @pytest.mark.gpu
 @pytest.mark.parametrize("iterations", [1, 2, 3, 40])
 def test_gpu_whole_grid_equals_the_twin(iterations):
